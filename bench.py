@@ -8,7 +8,7 @@ Nature-CNN actor-critic, 1xMI355X") with the NS-2 learner preset of SURVEY.md §
 torch.distributed.run, one rank per GPU) every rank runs the same per-GPU workload on its own env shard and gradients /
 advantage moments are all-reduced over RCCL: weak scaling, value = whole-job env-steps/s.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c5] [--dump-outputs DIR]
 
 `--workload c5` = BASELINE.json configs[4] on one GPU per rank: Ant-shaped synthetic continuous env (obs f32[27],
 Box(8)), 2048 envs, MLP[64,64] tanh encoder + LSTM-512 core, V-trace, KL loss, rollout = recurrence = 32.
@@ -20,9 +20,12 @@ a rank-stamped all-reduce) and the device of every rank.
 from __future__ import annotations
 
 import argparse
+import atexit
 import json
 import os
+import shutil
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -179,8 +182,6 @@ def reference_on_this_gpu():
         # MIOpen's kernel search for the reference's 18 fp32 convolution problems takes ~3 minutes on a fresh box; its
         # result (the user find-db written by such a run on an MI355X) is committed under oracle/miopen_db and handed to
         # the subprocess through a scratch copy, so the reference runs on the kernels MIOpen itself picked, in seconds
-        import shutil
-        import tempfile
         env = dict(os.environ)
         src_db = os.path.join(ROOT, "oracle", "miopen_db")
         if os.path.isdir(src_db) and "MIOPEN_USER_DB_PATH" not in env:
@@ -313,7 +314,12 @@ def workload_cfg(args, rank, world):
     from sample_factory_amd.cfg.arguments import default_cfg
     from sample_factory_amd.envs.synthetic import make_synthetic_continuous_env, make_synthetic_env
     B, T = args.envs, args.rollout
-    common = dict(rollout=T, batch_size=B * T // args.num_batches, num_batches_per_epoch=args.num_batches,
+    # the runner writes config.json (and would resume from a checkpoint) under train_dir: a private, empty directory
+    # per run keeps the repository untouched (it may be read-only) and every run starting from the same seeded weights
+    train_dir = tempfile.mkdtemp(prefix="sf_bench_")
+    atexit.register(shutil.rmtree, train_dir, True)
+    common = dict(train_dir=train_dir,
+                  rollout=T, batch_size=B * T // args.num_batches, num_batches_per_epoch=args.num_batches,
                   num_epochs=args.num_epochs, async_rl=args.async_rl, serial_mode=not args.async_rl, batched_sampling=True,
                   num_workers=1, num_envs_per_worker=args.env_instances, worker_num_splits=args.env_instances,
                   env_gpu_observations=True, env_gpu_actions=True, actor_worker_gpus=[0], seed=0,
@@ -382,6 +388,66 @@ def workload_cfg(args, rank, world):
     raise SystemExit(f"unknown workload {args.workload}")
 
 
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: all files together
+DUMP_ARRAY_CAP = 8 << 20       # one array above this is a fixed, seeded sample of its rows (first dimension)
+DUMP_TRAIN_KEYS = ("lr", "actual_lr", "env_steps", "policy_loss", "exploration_loss", "kl_loss", "value_loss",
+                   "kl_divergence", "kl_divergence_max", "adv_mean", "adv_std", "entropy", "loss", "num_sgd_steps")
+
+
+def dump_outputs(runner, stats, out_dir):
+    """--dump-outputs DIR: what the timed path computed in its LAST step, as a caller of Runner.iteration() receives it —
+    the trained model (state_dict, the checkpoint layout), the trajectory slab the rollout wrote and the learner trained
+    on (every leaf of runner.traj) and the loss / KL / advantage scalars of the train statistics — one DIR/<name>.npy
+    each, float64 where the source is 64-bit, float32 otherwise.  Arrays larger than the per-array cap are sampled along their first dimension
+    with numpy's default_rng(0) (the same rows for the same shape, sorted), the cap halving until all files fit the
+    64 MB budget; rows are selected on the device, so a multi-GB observation slab is never copied whole."""
+    import numpy as np
+    import torch
+    from sample_factory_amd.algo.learning.learner import TRAIN_STATS
+
+    arrays = [("model." + k, v) for k, v in runner.learner.actor_critic.state_dict().items()]
+
+    def leaves(prefix, d):
+        for k, v in d.items():
+            if isinstance(v, dict):
+                yield from leaves(f"{prefix}{k}.", v)
+            else:
+                yield prefix + k, v
+
+    arrays += list(leaves("traj.", runner.traj))
+    # the scalars every Learner.train returns (the summary statistics join them on a wall-clock schedule: left out)
+    train = (stats or {}).get(TRAIN_STATS) or {}
+    arrays += [("train." + k, torch.tensor(float(train[k]), dtype=torch.float64)) for k in DUMP_TRAIN_KEYS if k in train]
+
+    def out_dtype(t):
+        return torch.float64 if t.dtype in (torch.float64, torch.int64) else torch.float32
+
+    def nbytes(t, cap):
+        full = t.numel() * out_dtype(t).itemsize
+        if full <= cap or t.dim() == 0 or t.shape[0] < 2:
+            return full
+        row = full // t.shape[0]
+        return max(1, cap // row) * row
+
+    cap = DUMP_ARRAY_CAP
+    while sum(nbytes(t, cap) for _, t in arrays) > DUMP_BUDGET_BYTES:
+        cap //= 2
+        if cap < 4096:
+            raise SystemExit("--dump-outputs: the outputs do not fit the 64 MB budget")
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays:
+        t = t.detach()
+        if nbytes(t, cap) < t.numel() * out_dtype(t).itemsize:
+            keep = nbytes(t, cap) // (t.numel() // t.shape[0] * out_dtype(t).itemsize)
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        a = t.to(out_dtype(t)).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    return {"dir": out_dir, "files": len(arrays), "bytes": total}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="c2", choices=["c2", "c5", "c3"])
@@ -423,7 +489,11 @@ def main():
     ap.add_argument("--async_rl", action="store_true", help="overlap rollout k+1 with train(k) (policy lag of one dataset)")
     ap.add_argument("--normalize_input", action="store_true",
                     help="c2 with cfg.normalize_input=True (the reference's default; BASELINE configs[1] / NS-2 runs with False)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.envs is None:
         args.envs = dict(c2=4096, c5=2048, c3=1024)[args.workload]
     if args.num_epochs is None:
@@ -530,7 +600,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        runner.iteration()
+        last_stats = runner.iteration()
     barrier()
     dt = time.perf_counter() - t0
     clock = clk.stop() if clk is not None else None
@@ -560,6 +630,7 @@ def main():
                   "dma_share_of_wall_clock": round(dma_ms * 1e-3 / dt, 4)}
     prof, lib.PROFILE, lib.PROFILE_ONLY = lib.PROFILE, None, None
     seen, lib.PROFILE_STRIDE, lib.PROFILE_SEEN = dict(lib.PROFILE_SEEN), 1, {}
+    dumped = dump_outputs(runner, last_stats, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
     collectives = None
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
@@ -603,7 +674,8 @@ def main():
                               "ms_per_step": round(dt / args.steps * 1e3, 2), "n_gpus": world, "rccl_ranks": rccl_ranks,
                               "rank_devices": rank_devices, "config": {"workload": workload_desc},
                               **({"collectives": collectives} if collectives else {}),
-                              **({"ingest": ingest} if ingest is not None else {})}))
+                              **({"ingest": ingest} if ingest is not None else {}),
+                              **({"dumped_outputs": dumped} if dumped else {})}))
         if world > 1:
             torch.distributed.destroy_process_group()
         return
@@ -702,6 +774,7 @@ def main():
                                     "replayed_steps": int(sum(getattr(sm, "program_replays", 0) for sm in runner.samplers))},
         **({"collectives": collectives} if collectives else {}),
         **({"ingest": ingest} if ingest is not None else {}),
+        **({"dumped_outputs": dumped} if dumped else {}),
         "network_kernels": {"source": "instrumented warm-up step (every launch timed in isolation; not the timed region)",
                             "ms_per_step": round(net_ms, 2), "tflops_avg": round(net_flops / (net_ms * 1e-3) / 1e12, 2),
                             "top": breakdown},

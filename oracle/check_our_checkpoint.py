@@ -1,8 +1,10 @@
 """Feed a checkpoint written by THIS engine (tests/golden/ours_checkpoint_mlp.pth) to the REFERENCE's Learner
-(build container only; TEST INFRASTRUCTURE).   python -m oracle.check_our_checkpoint"""
+(TEST INFRASTRUCTURE; the reference is imported as oracle/ref_import.py resolves it, SF_REFERENCE_ROOT first).
+python -m oracle.check_our_checkpoint"""
 import os
 import shutil
 import sys
+import tempfile
 
 import numpy as np
 import torch
@@ -10,18 +12,24 @@ import torch
 from oracle import ref_import  # noqa: F401
 import gymnasium as gym  # the stub
 from oracle.gen_golden import MLP_OBS, make_learner
+import sample_factory.cfg.arguments as ref_arguments
 from sample_factory.cfg.arguments import parse_full_cfg, parse_sf_args
+
+# parse_full_cfg tags the config with the git revision of the working directory, found by listing every directory above
+# it (utils.git_root): that fails where an ancestor may not be listed and has nothing to do with loading a checkpoint,
+# so the check answers it the way the reference does outside a git checkout
+ref_arguments.get_git_commit_hash = lambda: ("unknown", "not a git repository")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def main():
     g = np.load(os.path.join(ROOT, "tests", "golden", "ours_checkpoint_mlp.npz"))
-    shutil.rmtree("/tmp/sf_golden/ours_ckpt", ignore_errors=True)
-    d = "/tmp/sf_golden/ours_ckpt/checkpoint_p0"
+    train_dir = tempfile.mkdtemp(prefix="sf_ours_ckpt_")
+    d = os.path.join(train_dir, "ours_ckpt", "checkpoint_p0")
     os.makedirs(d)
     shutil.copy(os.path.join(ROOT, "tests", "golden", "ours_checkpoint_mlp.pth"), os.path.join(d, str(g["file_name"])))
-    argv = ["--algo=APPO", "--env=synthetic", "--experiment=ours_ckpt", "--train_dir=/tmp/sf_golden", "--device=cpu",
+    argv = ["--algo=APPO", "--env=synthetic", "--experiment=ours_ckpt", f"--train_dir={train_dir}", "--device=cpu",
             "--serial_mode=True", "--seed=0", "--use_rnn=False", "--recurrence=1", "--rollout=8", "--batch_size=64",
             "--num_batches_per_epoch=2", "--num_epochs=2"] + str(g["argv"]).split()
     parser, _ = parse_sf_args(argv)
@@ -39,6 +47,7 @@ def main():
     np.testing.assert_allclose(res["action_logits"].numpy(), g["logits"], atol=2e-5, rtol=1e-4)
     np.testing.assert_allclose(res["values"].numpy(), g["values"], atol=2e-5, rtol=1e-4)
     print("INTEROP OK", learner.train_step, learner.env_steps)
+    shutil.rmtree(train_dir, ignore_errors=True)
 
 
 if __name__ == "__main__":

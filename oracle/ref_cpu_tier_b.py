@@ -18,9 +18,12 @@ with `--device=gpu`, i.e. its stock PyTorch-ROCm / MIOpen path on the MI355X of 
 """
 from __future__ import annotations
 
+import atexit
 import json
 import os
+import shutil
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -32,6 +35,15 @@ from oracle.gen_golden import C2_MODEL_ARGS, fill_batch, make_cfg, make_learner
 from sample_factory.algo.utils.rl_utils import prepare_and_normalize_obs
 from sample_factory.algo.utils.shared_buffers import alloc_trajectory_tensors
 from sample_factory.model.model_utils import get_rnn_size
+import sample_factory.cfg.arguments as ref_arguments
+
+# parse_full_cfg tags the config with the git revision of the working directory, found by listing every directory above
+# it (utils.git_root): that fails where an ancestor may not be listed and has nothing to do with the timing, so the
+# baseline answers it the way the reference does outside a git checkout
+ref_arguments.get_git_commit_hash = lambda: ("unknown", "not a git repository")
+# the reference's Learner.init creates its checkpoint directory: a private one per run, removed at exit
+TRAIN_DIR = tempfile.mkdtemp(prefix="sf_ref_baseline_")
+atexit.register(shutil.rmtree, TRAIN_DIR, True)
 
 
 def main_cuda(argv):
@@ -42,7 +54,8 @@ def main_cuda(argv):
     T, nb = 32, 4
     obs_space = gym.spaces.Dict({"obs": gym.spaces.Box(0, 255, (4, 84, 84), np.uint8)})
     cfg = make_cfg(C2_MODEL_ARGS + [f"--rollout={T}", f"--batch_size={E * T // nb}", f"--num_batches_per_epoch={nb}",
-                                    "--num_epochs=1", "--exploration_loss_coeff=0.01", "--device=gpu"])
+                                    "--num_epochs=1", "--exploration_loss_coeff=0.01", "--device=gpu",
+                                    f"--train_dir={TRAIN_DIR}"])
     assert cfg.device == "gpu"
     t_setup = time.perf_counter()
     learner, env_info = make_learner(cfg, obs_space, gym.spaces.Discrete(6), E)
@@ -122,7 +135,7 @@ def main():
     T, nb, full_envs = 32, 4, 4096
     obs_space = gym.spaces.Dict({"obs": gym.spaces.Box(0, 255, (4, 84, 84), np.uint8)})
     cfg = make_cfg(C2_MODEL_ARGS + [f"--rollout={T}", f"--batch_size={E * T // nb}", f"--num_batches_per_epoch={nb}",
-                                    "--num_epochs=1", "--exploration_loss_coeff=0.01"])
+                                    "--num_epochs=1", "--exploration_loss_coeff=0.01", f"--train_dir={TRAIN_DIR}"])
     learner, env_info = make_learner(cfg, obs_space, gym.spaces.Discrete(6), E)
     ac = learner.actor_critic
     g = torch.Generator().manual_seed(0)

@@ -150,20 +150,50 @@ def test_masked_categorical_matches_reference(golden):
     assert np.abs(freq[~ok] - 1.0 / A).max() < 0.12                           # all-masked rows: uniform fallback
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/sample_factory"), reason="the reference only exists in the build container")
-def test_reference_loads_a_checkpoint_written_here():
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+REF_ZIP = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref",
+                       "sample_factory_ref.zip")
+
+
+def test_checkpoint_written_here_has_the_reference_layout():
+    """tests/golden/ours_checkpoint_mlp.pth (this engine's Learner.save()) against tests/golden/ref_checkpoint_mlp.pth
+    (the reference's Learner.save(), same configuration): the same top-level entries, the same model state_dict names,
+    shapes and dtypes in the same order, and a torch.optim.Adam state of the same layout — what the reference's strict
+    load_state_dict calls need."""
+    import torch
+    ours = torch.load(os.path.join(GOLDEN_DIR, "ours_checkpoint_mlp.pth"), map_location="cpu", weights_only=False)
+    ref = torch.load(os.path.join(GOLDEN_DIR, "ref_checkpoint_mlp.pth"), map_location="cpu", weights_only=False)
+    assert list(ours) == list(ref)
+    assert [(k, tuple(v.shape), v.dtype) for k, v in ours["model"].items()] == \
+        [(k, tuple(v.shape), v.dtype) for k, v in ref["model"].items()]
+    assert all(torch.isfinite(v).all() for v in ours["model"].values() if v.is_floating_point())
+    po, pr = ours["optimizer"]["param_groups"], ref["optimizer"]["param_groups"]
+    assert [sorted(g) for g in po] == [sorted(g) for g in pr] and [g["params"] for g in po] == [g["params"] for g in pr]
+    so, sr = ours["optimizer"]["state"], ref["optimizer"]["state"]
+    assert sorted(so) == sorted(sr)
+    for i in sr:
+        assert sorted(so[i]) == sorted(sr[i])
+        for k in ("exp_avg", "exp_avg_sq"):
+            assert so[i][k].shape == sr[i][k].shape and so[i][k].dtype == sr[i][k].dtype
+    assert float(so[0]["step"]) == int(ours["train_step"])
+
+
+@pytest.mark.skipif(not os.path.isfile(REF_ZIP), reason="oracle/_ref/sample_factory_ref.zip not staged by build() "
+                                                        "(make -C oracle ref needs the reference sources)")
+def test_reference_loads_a_checkpoint_written_here(tmp_path):
     """tests/golden/ours_checkpoint_mlp.pth was written by THIS engine's Learner.save() on the GPU
     (tests/test_gpu_runner.py::test_write_a_checkpoint_for_the_reference).  The reference's Learner.init() resumes from
     it through its own load_from_checkpoint (strict nn.Module.load_state_dict + torch.optim.Adam.load_state_dict) and
-    its model reproduces the outputs this engine recorded for the probe batch.  Subprocess: this process may already
-    hold this repo's `sample_factory` alias package."""
+    its model reproduces the outputs this engine recorded for the probe batch.  The reference is the archive build()
+    staged under oracle/_ref/.  Subprocess: this process may already hold this repo's `sample_factory` alias package;
+    it runs in a private working directory and writes its train dir to a temporary one."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if not os.path.exists(os.path.join(root, "tests", "golden", "ours_checkpoint_mlp.pth")):
-        pytest.skip("fixture not generated yet")
-    r = subprocess.run([sys.executable, "-m", "oracle.check_our_checkpoint"], cwd=root, capture_output=True, text=True,
-                       timeout=600)
+    env = dict(os.environ, SF_REFERENCE_ROOT=REF_ZIP,
+               PYTHONPATH=os.pathsep.join([root] + [p for p in [os.environ.get("PYTHONPATH")] if p]))
+    r = subprocess.run([sys.executable, "-m", "oracle.check_our_checkpoint"], cwd=tmp_path, env=env, capture_output=True,
+                       text=True, timeout=600)
     assert r.returncode == 0 and "INTEROP OK" in r.stdout, (r.stdout[-1500:], r.stderr[-1500:])
 
 

@@ -19,13 +19,17 @@ SCRIPTS = ["sf_examples/train_gym_env.py", "sf_examples/enjoy_gym_env.py",
            "sf_examples/train_custom_env_custom_model.py", "sf_examples/enjoy_custom_env_custom_model.py"]
 
 
-def test_staged_scripts_are_the_reference_bytes():
-    """where the reference is present (the build container) the staged archive equals it byte for byte"""
-    if not (os.path.isdir("/root/reference/sf_examples") and os.path.isfile(EX_ZIP)):
-        pytest.skip("needs /root/reference and the staged archive")
+def test_staged_scripts_are_the_reference_bytes(golden_json):
+    """the staged archive holds the reference's example scripts byte for byte: their SHA-256 digests, recorded from the
+    reference's sources in tests/golden/reference_example_scripts.json"""
+    import hashlib
+    if not os.path.isfile(EX_ZIP):
+        pytest.skip("oracle/_ref/sf_examples_ref.zip not staged (make -C oracle ref needs the reference sources)")
+    digests = golden_json("reference_example_scripts")["sha256"]
+    assert sorted(digests) == sorted(SCRIPTS)
     with zipfile.ZipFile(EX_ZIP) as z:
         for name in SCRIPTS:
-            assert z.read(name) == open(os.path.join("/root/reference", name), "rb").read(), name
+            assert hashlib.sha256(z.read(name)).hexdigest() == digests[name], name
 
 
 def test_every_sample_factory_import_of_the_reference_scripts_resolves(tmp_path):

@@ -1,6 +1,6 @@
 """`Timing` (utils/timing.py) and `LinearDecay` (utils/decay.py): the reference's profiler / schedule API with this engine's own
-implementation.  Held to known answers here and — where /root/reference is present — to the reference's classes on the same
-scripted clock (identical tree / flat strings, bit-equal schedule values)."""
+implementation.  Held to known answers here and — where build() staged the reference under oracle/_ref/ — to the
+reference's classes on the same scripted clock (identical tree / flat strings, bit-equal schedule values)."""
 import itertools
 import os
 
@@ -60,10 +60,11 @@ def test_linear_decay_known_answers():
 
 _COMPARE = r"""
 import importlib, itertools, sys
-from oracle import ref_import  # noqa: F401  (stand-ins for the reference's third-party imports + /root/reference on sys.path)
+import os
+from oracle import ref_import  # noqa: F401  (stand-ins for the reference's third-party imports + the reference on sys.path)
 ref_t = importlib.import_module("sample_factory.utils.timing")
 ref_d = importlib.import_module("sample_factory.utils.decay")
-assert "/root/reference" in ref_t.__file__, ref_t.__file__
+assert ref_t.__file__.startswith(os.environ["SF_REFERENCE_ROOT"]), ref_t.__file__
 import sample_factory_amd.utils.timing as ours_t
 from sample_factory_amd.utils.decay import LinearDecay
 sys.path.insert(0, "tests")
@@ -77,13 +78,20 @@ print("EQUAL")
 """
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/sample_factory"), reason="needs /root/reference")
+REF_ZIP = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref",
+                       "sample_factory_ref.zip")
+
+
+@pytest.mark.skipif(not os.path.isfile(REF_ZIP), reason="oracle/_ref/sample_factory_ref.zip not staged by build() "
+                                                        "(make -C oracle ref needs the reference sources)")
 def test_equal_to_the_reference_classes():
-    """in a process of its own: importing the reference installs stand-ins for gymnasium & co. into sys.modules"""
+    """in a process of its own: importing the reference (the archive build() staged under oracle/_ref/) installs
+    stand-ins for gymnasium & co. into sys.modules"""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", _COMPARE], cwd=root, capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, "-c", _COMPARE], cwd=root, env=dict(os.environ, SF_REFERENCE_ROOT=REF_ZIP),
+                       capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "EQUAL" in r.stdout, r.stdout[-500:] + r.stderr[-1500:]
 
 
