@@ -542,6 +542,47 @@ int sf_linear_dgrad(const float *dout, const float *w, const float *in_act, floa
 /* elementwise helper for the backward chain: g[i] = (act[i] > 0) ? g[i] : 0 */
 int sf_relu_mask(float *g, const float *act, int64_t n, void *stream);
 
+/* ---- resnet_impala encoder (model/encoder.py:153-221: ResnetEncoder, three stages of conv3x3 -> MaxPool2d(3, 2, 1) ->
+ * two ResBlocks x + conv3x3(act(conv3x3(act(x)))), then act, flatten and encoder_conv_mlp_layers; encoder.py:186-213 is the
+ * residual block, whose activations are NOT in place: the skip carries the un-activated x).  3x3 convs with stride 1 and
+ * padding 1, NHWC activations, weights K-major [9*Cin, Cout], k = (kh*3 + kw)*Cin + c.  The fully connected layers after
+ * the last stage are sf_conv_fwd / sf_conv_wgrad / sf_conv_dgrad as 1x1 layers. */
+typedef struct {
+    int32_t Cin, H, W, Cout; /* input = output feature map (same padding); Cout 16 or 32, Cin <= 32 (16 or 32 for dgrad) */
+    int32_t in_u8;           /* 1: the raw u8 NCHW frames, (x - sub_mean) * inv_scale on load (utils/normalize.py:51-70);
+                                0: f32 NHWC [n, H, W, Cin], dense */
+    int32_t act_in;          /* activation applied to the input on load, 0 none 1 ReLU 2 tanh 3 ELU (model_utils.py:27-35);
+                                sf_res_conv_dgrad: the activation whose derivative at `pre` multiplies the data gradient */
+    int32_t traj_T;          /* u8 frames only: slab addressing as sf_conv_desc.traj_T */
+    float sub_mean, inv_scale;
+} sf_res_desc;
+
+/* Conv2d(Cin, Cout, 3, stride=1, padding=1) forward (encoder.py:162-164 and the two convs of encoder.py:193-197):
+ * out[n,H,W,Cout] = [residual +] (conv(act_in(in)) + bias); out_act (optional) = act_out(out), the activated copy the
+ * next consumer reads (encoder.py:170: the activation after the last stage).  The zero padding is in the normalised,
+ * activated domain, as torch pads the normalised f32 tensor.  Sample i is input row index[i] | offset + i (u8 frames:
+ * slab row through traj_T) times in_sample_stride elements.  w, out, out_act, residual 16-byte aligned. */
+int sf_res_conv_fwd(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *w,
+                    const float *bias, const float *residual, float *out, float *out_act, int act_out, int64_t n,
+                    const sf_res_desc *h_desc, void *stream);
+/* MaxPool2d(3, stride=2, padding=1) (encoder.py:165) on f32 NHWC [n,H,W,C] -> [n,(H-1)/2+1,(W-1)/2+1,C] plus the window
+ * position kh*3 + kw of every maximum (u8); -inf padding, torch's tie rule (first maximum in scan order, NaN wins). */
+int sf_res_pool_fwd(const float *in, float *out, uint8_t *argmax, int64_t n, int H, int W, int C, void *stream);
+/* its backward: every input element gathers dout from the windows whose recorded maximum it is (deterministic). */
+int sf_res_pool_bwd(const float *dout, const uint8_t *argmax, float *din, int64_t n, int H, int W, int C, void *stream);
+/* data gradient of the 3x3 conv: din = [g_add +] conv_transpose(dout, w) * act_in'(pre) (pre: the layer's stored
+ * PRE-activation input, NULL when act_in = 0); g_add lets a residual block finish g_x = g_y + dgrad * act'(x) in one
+ * pass.  f32 layers, Cin and Cout 16 or 32. */
+int sf_res_conv_dgrad(const float *dout, const float *w, const float *pre, const float *g_add, float *din, int64_t n,
+                      const sf_res_desc *h_desc, void *stream);
+/* weight / bias gradient of the 3x3 conv: dw[9*Cin, Cout] = patches(act_in(in))^T dout, db = sum dout (overwritten);
+ * same input addressing as sf_res_conv_fwd; deterministic two-stage reduction (no float atomics) through a workspace of
+ * sf_res_conv_wgrad_workspace(...) bytes. */
+int64_t sf_res_conv_wgrad_workspace(int64_t n, const sf_res_desc *h_desc);
+int sf_res_conv_wgrad(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *dout,
+                      float *dw, float *db, int64_t n, const sf_res_desc *h_desc, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,11 @@ class sf_conv_desc(C.Structure):
                 ("inv_scale", C.c_float)]
 
 
+class sf_res_desc(C.Structure):
+    _fields_ = [("Cin", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cout", C.c_int32), ("in_u8", C.c_int32),
+                ("act_in", C.c_int32), ("traj_T", C.c_int32), ("sub_mean", C.c_float), ("inv_scale", C.c_float)]
+
+
 # every symbol include/sf_hip.h declares (tests/test_abi.py checks the header against this list and the .so)
 SYMBOLS = [
     "sf_last_error", "sf_abi_version", "sf_valid_mask", "sf_gae_returns", "sf_moments", "sf_rms_update",
@@ -50,6 +55,8 @@ SYMBOLS = [
     "sf_dp_unique_id", "sf_dp_comm_create", "sf_dp_comm_destroy", "sf_dp_comm_info", "sf_allreduce_grads",
     "sf_dp_allreduce_f64", "sf_dp_broadcast", "sf_dp_oneshot_create", "sf_dp_oneshot_connect", "sf_dp_oneshot_allreduce_f32",
     "sf_dp_oneshot_allreduce_f64", "sf_dp_oneshot_status", "sf_dp_oneshot_destroy",
+    "sf_res_conv_fwd", "sf_res_pool_fwd", "sf_res_pool_bwd", "sf_res_conv_dgrad", "sf_res_conv_wgrad_workspace",
+    "sf_res_conv_wgrad",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -228,6 +235,7 @@ def load() -> C.CDLL:
         lib.sf_conv_fwd_workspace.restype = C.c_int64
         lib.sf_conv_fwd_t_workspace.restype = C.c_int64
         lib.sf_linear_wgrad_workspace.restype = C.c_int64
+        lib.sf_res_conv_wgrad_workspace.restype = C.c_int64
         _lib = lib
     return _lib
 
@@ -976,3 +984,51 @@ def dp_oneshot_status(ctx) -> None:
 
 def dp_oneshot_destroy(ctx) -> None:
     _check(load().sf_dp_oneshot_destroy(ctx), "sf_dp_oneshot_destroy")
+
+
+# ---- resnet_impala encoder (csrc/sf_resnet.hip)
+def _res_in(t: torch.Tensor, desc: sf_res_desc) -> C.c_void_p:
+    want = torch.uint8 if desc.in_u8 else torch.float32
+    if t.dtype != want:
+        raise SfHipError(f"resnet conv input: expected {want}, got {t.dtype}")
+    if not t.is_cuda:
+        raise SfHipError(f"resnet conv input lives on {t.device}; the hot path only runs on the GPU (no CPU fallback)")
+    return _vp(t)
+
+
+def res_conv_fwd(inp, in_sample_stride, index, offset, w, bias, out, n, desc: sf_res_desc, residual=None, out_act=None,
+                 act_out=0) -> None:
+    """3x3 same conv: out = [residual +] conv(act_in(inp)) + bias, out_act = act_out(out); `inp` may be a strided view
+    (u8 frames: index / offset / traj_T addressing as conv_fwd_raw)"""
+    _check(load().sf_res_conv_fwd(_res_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"), i64(offset),
+                                  ptr(w, "f32", "w"), ptr(bias, "f32", "bias"), ptr(residual, "f32", "residual"),
+                                  ptr(out, "f32", "out"), ptr(out_act, "f32", "out_act"), int(act_out), i64(n),
+                                  C.byref(desc), stream()), "sf_res_conv_fwd")
+
+
+def res_pool_fwd(inp, out, argmax, n, H, W, Cn) -> None:
+    _check(load().sf_res_pool_fwd(ptr(inp, "f32", "in"), ptr(out, "f32", "out"), ptr(argmax, "u8", "argmax"), i64(n),
+                                  int(H), int(W), int(Cn), stream()), "sf_res_pool_fwd")
+
+
+def res_pool_bwd(dout, argmax, din, n, H, W, Cn) -> None:
+    _check(load().sf_res_pool_bwd(ptr(dout, "f32", "dout"), ptr(argmax, "u8", "argmax"), ptr(din, "f32", "din"), i64(n),
+                                  int(H), int(W), int(Cn), stream()), "sf_res_pool_bwd")
+
+
+def res_conv_dgrad(dout, w, pre, din, n, desc: sf_res_desc, g_add=None) -> None:
+    """din = [g_add +] conv_transpose(dout, w) * act_in'(pre)"""
+    _check(load().sf_res_conv_dgrad(ptr(dout, "f32", "dout"), ptr(w, "f32", "w"), ptr(pre, "f32", "pre"),
+                                    ptr(g_add, "f32", "g_add"), ptr(din, "f32", "din"), i64(n), C.byref(desc), stream()),
+           "sf_res_conv_dgrad")
+
+
+def res_conv_wgrad_workspace(n, desc: sf_res_desc) -> int:
+    return int(load().sf_res_conv_wgrad_workspace(i64(n), C.byref(desc)))
+
+
+def res_conv_wgrad(inp, in_sample_stride, index, offset, dout, dw, db, n, desc: sf_res_desc, workspace) -> None:
+    _check(load().sf_res_conv_wgrad(_res_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"), i64(offset),
+                                    ptr(dout, "f32", "dout"), ptr(dw, "f32", "dw"), ptr(db, "f32", "db"), i64(n),
+                                    C.byref(desc), ptr(workspace, "u8", "workspace"), i64(workspace.numel()), stream()),
+           "sf_res_conv_wgrad")

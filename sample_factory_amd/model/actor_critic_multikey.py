@@ -24,6 +24,7 @@ import torch
 from sample_factory_amd import lib
 from sample_factory_amd.envs import spaces
 from sample_factory_amd.model.actor_critic import ActorCritic
+from sample_factory_amd.model.encoder_resnet import ResnetImpalaTower, uses_resnet
 
 
 class _KeyedNormalizers:
@@ -33,24 +34,34 @@ class _KeyedNormalizers:
         self.towers = towers
 
     def update(self, obs, stride: int, n: int, **_):
+        if not isinstance(obs, dict):  # the single-key resnet_impala model is handed its one slab leaf
+            obs = {next(iter(self.towers)): obs}
         for k, t in self.towers.items():
             if t.obs_normalizer is not None:
                 t.obs_normalizer.update(obs[k], t.obs_elems, n)
 
 
 class MultiKeyActorCritic:
-    multi_key = True  # the Learner / rollout runner pass {key: slab view} dicts
 
     def __init__(self, cfg, obs_space, action_space, device="cuda", all_reduce=None):
         self.cfg = cfg
         self.obs_keys = sorted(k for k in obs_space.spaces.keys() if k != "action_mask")
-        if len(self.obs_keys) < 2:
+        # an image key under resnet_impala is a ResnetImpalaTower (model/encoder_resnet.py): that tower + the trunk is also
+        # how the single-key resnet_impala model runs
+        resnet = uses_resnet(cfg, obs_space)
+        if len(self.obs_keys) < 2 and not resnet:
             raise NotImplementedError("MultiKeyActorCritic: an observation dict with at least two keys")
         if not cfg.actor_critic_share_weights:
             raise NotImplementedError("separate actor / critic weights with several observation keys")
-        self.encoders: Dict[str, ActorCritic] = {
-            k: ActorCritic(cfg, obs_space, action_space, device, all_reduce=all_reduce, obs_key=k, part="encoder")
-            for k in self.obs_keys}
+
+        def encoder(k):
+            if resnet and len(obs_space[k].shape) == 3:
+                return ResnetImpalaTower(cfg, obs_space, action_space, device, all_reduce=all_reduce, obs_key=k)
+            return ActorCritic(cfg, obs_space, action_space, device, all_reduce=all_reduce, obs_key=k, part="encoder")
+
+        self.encoders: Dict[str, ActorCritic] = {k: encoder(k) for k in self.obs_keys}
+        # several keys: the Learner / rollout runner pass {key: slab view} dicts; one key: the bare view (see _keyed)
+        self.multi_key = len(self.obs_keys) > 1
         self.feat_of = {k: e.feat for k, e in self.encoders.items()}
         self.col0, F = {}, 0
         for k in self.obs_keys:
@@ -217,6 +228,9 @@ class MultiKeyActorCritic:
         return self.trunk.rnn_pass_aborted()
 
     # ------------------------------------------------------------------------------------------ forward / backward
+    def _keyed(self, obs):
+        return obs if isinstance(obs, dict) else {self.obs_keys[0]: obs}
+
     def _stride_of(self, k, view, traj_T):
         """elements between two samples of key k: the learner addresses whole slab leaves [E, T + 1, ...] by dataset row
         (sf_common.h sample_base: dense frames), a rollout / bootstrap step hands one column view [B, ...] of the slab"""
@@ -226,6 +240,7 @@ class MultiKeyActorCritic:
                       rnn=None) -> List[torch.Tensor]:
         """obs: {key: view}; returns the trunk's layer outputs (last = heads [n, heads_ld])"""
         cat = self._buf((tag, "features"), (n, self.F))
+        obs = self._keyed(obs)
         for k in self.obs_keys:
             e, v = self.encoders[k], obs[k]
             out = e.forward_heads(v, n, sample_stride=self._stride_of(k, v, traj_T), index=index, offset=offset,
@@ -244,6 +259,7 @@ class MultiKeyActorCritic:
         t = self.trunk
         t.backward(acts, g_heads, None, n, sample_stride=self.F)
         gin = t.g_input  # [n, F]
+        obs = self._keyed(obs)
         for k in self.obs_keys:
             e, v, c = self.encoders[k], obs[k], self.col0[k]
             g = e._buf(("g", "out"), (n, e.feat))

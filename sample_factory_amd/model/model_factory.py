@@ -61,19 +61,40 @@ def create_actor_critic(cfg, obs_space, action_space, device, all_reduce=None):
     # them back to the torch path)
     import os
     stacked_rnn = bool(cfg.use_rnn) and int(cfg.rnn_num_layers) > 1 and os.environ.get("SF_NATIVE_STACKED_RNN", "1") == "0"
-    if f.is_default() and len(obs_keys_of(obs_space)) <= 1 and not stacked_rnn and not separate:
+    import torch
+    from sample_factory_amd.model.encoder_resnet import uses_resnet
+    resnet = uses_resnet(cfg, obs_space)
+    multi = len(obs_keys_of(obs_space)) > 1
+    if resnet and f.is_default():
+        # cfg.encoder_conv_architecture = resnet_impala (model/encoder.py:153-221): a native ResnetImpalaTower + the trunk
+        # (model/encoder_resnet.py) on cuda; CPU devices, images the kernels do not take, separate actor / critic weights
+        # and SF_NATIVE_RESNET=0 take the torch path below
+        from sample_factory_amd.utils.utils import log
+        if os.environ.get("SF_NATIVE_RESNET", "1") == "0":
+            log.warning("resnet_impala: torch path (SF_NATIVE_RESNET=0)")
+        elif separate:
+            log.warning("resnet_impala with separate actor / critic weights: torch path")
+        elif stacked_rnn:
+            log.warning("resnet_impala with stacked recurrent layers: torch path (SF_NATIVE_STACKED_RNN=0)")
+        elif multi and os.environ.get("SF_NATIVE_MULTIKEY", "1") == "0":
+            log.warning("resnet_impala with several observation keys: torch path (SF_NATIVE_MULTIKEY=0)")
+        else:
+            from sample_factory_amd.model.actor_critic_multikey import MultiKeyActorCritic
+            try:
+                return MultiKeyActorCritic(cfg, obs_space, action_space, device, all_reduce=all_reduce)
+            except NotImplementedError as e:
+                log.warning("resnet_impala: torch path (%s)", e)
+    if f.is_default() and len(obs_keys_of(obs_space)) <= 1 and not stacked_rnn and not separate and not resnet:
         from sample_factory_amd.model.actor_critic import ActorCritic
         return ActorCritic(cfg, obs_space, action_space, device, all_reduce=all_reduce)
-    import torch
-    multi = len(obs_keys_of(obs_space)) > 1
-    if (f.is_default() and not stacked_rnn and separate and torch.device(device).type == "cuda"
+    if (f.is_default() and not stacked_rnn and separate and not resnet and torch.device(device).type == "cuda"
             and os.environ.get("SF_NATIVE_SEPARATE_WEIGHTS", "1") != "0"
             and (not multi or os.environ.get("SF_NATIVE_MULTIKEY", "1") != "0")):
         # cfg.actor_critic_share_weights=False (ActorCriticSeparateWeights, model/actor_critic.py:198-334) on the native
         # kernels since round 6: two towers on one flat parameter buffer (model/actor_critic_separate.py)
         from sample_factory_amd.model.actor_critic_separate import SeparateActorCritic
         return SeparateActorCritic(cfg, obs_space, action_space, device, all_reduce=all_reduce)
-    if (f.is_default() and len(obs_keys_of(obs_space)) > 1 and not stacked_rnn and not separate
+    if (f.is_default() and len(obs_keys_of(obs_space)) > 1 and not stacked_rnn and not separate and not resnet
             and torch.device(device).type == "cuda" and os.environ.get("SF_NATIVE_MULTIKEY", "1") != "0"):
         # observation dicts of several keys (model/encoder.py:33-69, MultiInputEncoder: one encoder per key, concatenated) on
         # the native kernels since round 6: one encoder tower per key + a trunk on one flat parameter buffer
