@@ -314,7 +314,14 @@ typedef struct {
     int32_t Cin, H, W;        /* input  feature map (per sample) */
     int32_t Cout, KH, KW, stride;
     int32_t OH, OW;           /* output feature map */
-    int32_t in_u8;            /* 1: input is the raw u8 NCHW observation; loader applies (x - sub_mean) * inv_scale */
+    int32_t in_u8;            /* input format: 0 = f32 NHWC activations; 1 = raw u8 NCHW observation frames; 2 = f32
+                                 NCHW observation frames (e.g. Box(0, 1, (C, H, W), float32)).  Frames (1, 2): the
+                                 loader applies (x - sub_mean) * inv_scale, weights use k = (c*KH + kh)*KW + kw, there
+                                 is no data gradient.  Format 2 runs on the f32 matrix instructions only (16-byte loads
+                                 when KW, stride and W are multiples of 4 and the frames 16-byte aligned, scalar loads
+                                 otherwise); no other kernel family and no *_supported query but sf_conv_norm_supported
+                                 takes it.  (Format 2 was added without an ABI version change: the struct layout and
+                                 the meaning of 0 / 1 are unchanged, and a value outside 0..2 is now refused.) */
     int32_t relu;             /* activation kind: 0 none, 1 ReLU, 2 tanh, 3 ELU(alpha=1) (model/model_utils.py:27-35).
                                  forward: fused in the epilogue; sf_conv_dgrad: the kind that PRODUCED in_act, whose
                                  derivative (through the stored output) is fused into the dgrad epilogue */
@@ -324,7 +331,8 @@ typedef struct {
     float sub_mean, inv_scale;
 } sf_conv_desc;
 
-/* forward: in = u8 NCHW [n, Cin,H,W] (in_u8) or f32 NHWC [n,H,W,Cin]; sample i of the batch is input row
+/* forward: in = u8 NCHW [n, Cin,H,W] (in_u8 = 1), f32 NCHW [n, Cin,H,W] (in_u8 = 2) or f32 NHWC [n,H,W,Cin]; sample i of
+ * the batch is input row
  * (index ? index[i] : offset+i) * in_sample_stride (elements).  out f32 NHWC [n,OH,OW,Cout].
  * workspace (optional, >= sf_conv_fwd_workspace bytes, 16-byte aligned): lets small launches (e.g. the 3136->512
  * layer at inference batch 4096: 256 tiles for 256 CUs) split the reduction over gridDim.z and finish with a
@@ -373,8 +381,11 @@ int sf_conv_wgrad_relu_mask(const void *in, int64_t in_sample_stride, const int3
  * aligned).  No normalised copy of the frames exists in HBM (28 KB instead of 28 + 2 x 113 KB per
  * frame and pass).  sf_conv_wgrad_norm = the weight / bias gradient against the same normalised input (dout already
  * masked by the activation derivative; workspace >= sf_conv_wgrad_workspace bytes).  sf_conv_norm_supported: 1 for the
- * launches these take (Nature-CNN conv1 geometry 4x84x84 -> 32, 8x8 stride 4, any n); otherwise sf_obsnorm_apply +
- * sf_conv_fwd on the f32 batch.  Sample addressing (index | offset, traj_T) as sf_conv_fwd. */
+ * launches these take (u8 frames: Nature-CNN conv1 geometry 4x84x84 -> 32, 8x8 stride 4, any n; f32 frames, in_u8 = 2:
+ * every geometry, on the f32 matrix instructions, x' = clamp(((x - sub_mean) * inv_scale - mu[d]) * rstd[d], +-5) formed
+ * in the loader, frames / tables 4-byte aligned, 16-byte vector loads where sf_conv_fwd would use them and the tables
+ * are 16-byte aligned); otherwise sf_obsnorm_apply + sf_conv_fwd on the f32 batch.  Sample addressing (index | offset,
+ * traj_T) as sf_conv_fwd. */
 int sf_conv_norm_supported(int64_t n, const sf_conv_desc *h_desc);
 int sf_conv_fwd_norm(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *mu,
                      const float *rstd, const float *w, const float *bias, float *out, int64_t n,
@@ -528,7 +539,8 @@ int sf_conv_fwd_t(const float *in, int64_t in_sample_stride, const float *wt, co
 int sf_transpose(const float *w, float *wt, int K, int N, void *stream); /* wt[N,K] = w[K,N]^T */
 
 /* Profiling aid (no reference counterpart): the kernel instantiation a conv/linear launch resolves to, spelled as
- * rocprofv3 prints it ("k_conv_fwd<128, 64, 2, 2, 0>").  op: 0 forward, 1 wgrad, 2 dgrad. */
+ * rocprofv3 prints it ("k_conv_fwd<128, 64, 2, 2, 0>").  op: 0 forward, 1 wgrad, 2 dgrad, 3 sf_conv_fwd_t,
+ * 4 sf_conv_fwd_norm, 5 sf_conv_wgrad_norm. */
 int sf_conv_kernel_name(int op, int64_t n, const sf_conv_desc *desc, int split_k_allowed, char *out, int cap);
 /* dense layer: out[M,N] = act(in[M,K] * w[K,N] + bias); wgrad: dw[K,N] = in^T dout, db = colsum(dout);
  * dgrad: din[M,K] = (dout[M,N] * w^T) * relu_mask(in_act). */

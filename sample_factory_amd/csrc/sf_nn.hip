@@ -8,8 +8,8 @@
 // the same precision class as the reference's fp32 MIOpen/rocBLAS path.  No reduced precision anywhere.
 //
 // Data layout: activations NHWC ([sample][oh][ow][c] == row-major [M, C]); weights K-major [K, Cout] with
-// k = (kh*KW + kw)*Cin + c (NHWC input) or k = (c*KH + kh)*KW + kw (raw NCHW u8 observation input, so that four
-// consecutive k are four consecutive bytes).  u8 observations are converted ((x - mean) * 1/scale) inside the
+// k = (kh*KW + kw)*Cin + c (NHWC input) or k = (c*KH + kh)*KW + kw (raw NCHW observation frames, u8 or f32, so that
+// four consecutive k are four consecutive pixels).  Observation frames are converted ((x - mean) * 1/scale) inside the
 // loader: the f32 copy of the observations that the reference materialises (utils/normalize.py:40-70) never exists.
 //
 // Tile: 256 threads = 4 wavefronts (one per SIMD), block tile BM x BN x 32, LDS image As[32][BM+pad], Bs[32][BN+pad]
@@ -61,6 +61,13 @@ extern "C" int sf_selftest_host(void) {  // exercised by the CPU test-suite: the
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------- input formats
+// sf_conv_desc.in_u8: 0 = f32 NHWC activations, 1 = u8 NCHW observation frames, 2 = f32 NCHW observation frames.
+// Every test of the field goes through these two helpers (a plain truth test would take format 2 for u8).
+constexpr int IN_F32_NHWC = 0, IN_U8_FRAME = 1, IN_F32_FRAME = 2;
+__host__ __device__ __forceinline__ bool in_is_u8(int in_u8) { return in_u8 == IN_U8_FRAME; }
+__host__ __device__ __forceinline__ bool in_is_frame(int in_u8) { return in_u8 == IN_U8_FRAME || in_u8 == IN_F32_FRAME; }
+
 // ---------------------------------------------------------------------------------------------- geometry
 struct ConvG {
     int Cin, H, W, Cout, KH, KW, S, OH, OW;
@@ -80,7 +87,9 @@ static ConvG make_geom(const sf_conv_desc *d) {
     g.sub_mean = d->sub_mean; g.inv_scale = d->inv_scale;
     g.nmu = nullptr; g.nrstd = nullptr;
     g.K = d->KH * d->KW * d->Cin;
-    g.vecA = d->in_u8 ? (d->KW % 4 == 0 && d->stride % 4 == 0 && d->W % 4 == 0) : (d->Cin % 4 == 0);
+    // frames: four consecutive k are four consecutive pixels of one row, and every patch origin is a multiple of 4
+    // pixels (4-byte words of u8, 16-byte float4 of f32 frames)
+    g.vecA = in_is_frame(d->in_u8) ? (d->KW % 4 == 0 && d->stride % 4 == 0 && d->W % 4 == 0) : (d->Cin % 4 == 0);
     g.vecB = d->Cout % 4 == 0;
     g.dOHOW = make_fastdiv((uint32_t)(d->OH * d->OW));
     g.dOW = make_fastdiv((uint32_t)d->OW);
@@ -106,6 +115,8 @@ static int check_desc(const sf_conv_desc *d, const char *who) {
                "%s: bad geometry", who);
     SF_REQUIRE(d->OH == (d->H - d->KH) / d->stride + 1 && d->OW == (d->W - d->KW) / d->stride + 1,
                "%s: OH/OW do not match a VALID (no padding) convolution", who);
+    SF_REQUIRE(d->in_u8 >= IN_F32_NHWC && d->in_u8 <= IN_F32_FRAME, "%s: in_u8 = %d is not an input format (0, 1, 2)",
+               who, d->in_u8);
     return SF_OK;
 }
 
@@ -113,6 +124,11 @@ static int check_desc(const sf_conv_desc *d, const char *who) {
 constexpr int MODE_F32 = 0;      // f32 NHWC activations, Cin % 4 == 0, Cout % 4 == 0: 16-byte loads everywhere
 constexpr int MODE_U8 = 1;       // raw u8 NCHW observation, KW/stride/W % 4 == 0: 4-byte loads of 4 pixels
 constexpr int MODE_GENERIC = 2;  // any geometry: scalar, bounds-checked (slow; odd shapes only)
+constexpr int MODE_F32F = 3;     // f32 NCHW observation frames, KW/stride/W % 4 == 0: 16-byte loads of 4 pixels
+constexpr int MODE_F32F_NORM = 4;  // MODE_F32F + the observation normaliser's tables (sf_conv_fwd_norm / _wgrad_norm)
+// frames (u8 or f32): reduction index k = (c*KH + kh)*KW + kw over the NCHW frame, output rows fastest across lanes
+template <int MODE>
+constexpr bool frame_layout() { return MODE == MODE_U8 || MODE == MODE_F32F || MODE == MODE_F32F_NORM; }
 
 // input-sample base offset (elements) of logical sample `smp`: optional index gather, optional dataset->trajectory
 // slab row mapping (flat index e*T+t  ->  slab row e*(T+1)+t, learner.py:1005-1012 drops column T by *copy*; we
@@ -178,14 +194,29 @@ template <>
 struct ARaw<MODE_U8> {
     uint32_t v;
 };
+template <>
+struct ARaw<MODE_F32F_NORM> {
+    float4 v, mu, rs;  // four pixels and their normaliser table entries
+};
 
-// four consecutive im2col columns k..k+3 (k % 4 == 0, k < K) of the patch whose origin is `base`
+// the observation normaliser applied to one converted pixel (running_mean_std.py:108: sub_(mu).mul_(1/sigma).clamp_(-5, 5))
+__device__ __forceinline__ float obs_norm(float x, float mu, float rs) { return fminf(fmaxf((x - mu) * rs, -5.f), 5.f); }
+
+// four consecutive im2col columns k..k+3 (k % 4 == 0, k < K) of the patch whose origin is `base`; po = that origin's
+// offset inside its sample (frames with the normaliser: the index into the [Cin*H*W] tables)
 template <int MODE>
-__device__ __forceinline__ ARaw<MODE> load_act_raw(const ConvG &g, const void *__restrict__ in, int64_t base,
+__device__ __forceinline__ ARaw<MODE> load_act_raw(const ConvG &g, const void *__restrict__ in, int64_t base, int po,
                                                    uint32_t k, bool ok) {
     ARaw<MODE> r;
     if constexpr (MODE == MODE_U8) {
         r.v = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(in) + base + tap_offset<true>(g, k));
+    } else if constexpr (MODE == MODE_F32F || MODE == MODE_F32F_NORM) {
+        const int t = tap_offset<true>(g, k);
+        r.v = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(in) + base + t);
+        if constexpr (MODE == MODE_F32F_NORM) {
+            r.mu = *reinterpret_cast<const float4 *>(g.nmu + po + t);
+            r.rs = *reinterpret_cast<const float4 *>(g.nrstd + po + t);
+        }
     } else if constexpr (MODE == MODE_F32) {
         r.v = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(in) + base + tap_offset<false>(g, k));
     } else {
@@ -194,10 +225,15 @@ __device__ __forceinline__ ARaw<MODE> load_act_raw(const ConvG &g, const void *_
         for (int j = 0; j < 4; ++j) {
             const bool okj = ok && (k + j < (uint32_t)g.K);
             const uint32_t kj = okj ? k + j : 0u;
-            if (g.in_u8)
-                x[j] = ((float)reinterpret_cast<const uint8_t *>(in)[base + tap_offset<true>(g, kj)] - g.sub_mean) * g.inv_scale;
-            else
+            if (in_is_frame(g.in_u8)) {
+                const int t = tap_offset<true>(g, kj);
+                const float raw = in_is_u8(g.in_u8) ? (float)reinterpret_cast<const uint8_t *>(in)[base + t]
+                                                    : reinterpret_cast<const float *>(in)[base + t];
+                x[j] = (raw - g.sub_mean) * g.inv_scale;
+                if (g.nmu) x[j] = obs_norm(x[j], g.nmu[po + t], g.nrstd[po + t]);
+            } else {
                 x[j] = reinterpret_cast<const float *>(in)[base + tap_offset<false>(g, kj)];
+            }
             x[j] = okj ? x[j] : 0.f;
         }
         r.v = make_float4(x[0], x[1], x[2], x[3]);
@@ -214,6 +250,16 @@ __device__ __forceinline__ float4 act_finish(const ConvG &g, const ARaw<MODE> &r
             x[j] = ok ? t : 0.f;
         }
         return make_float4(x[0], x[1], x[2], x[3]);
+    } else if constexpr (MODE == MODE_F32F) {
+        const float s = g.sub_mean, c = g.inv_scale;
+        return make_float4(ok ? (r.v.x - s) * c : 0.f, ok ? (r.v.y - s) * c : 0.f, ok ? (r.v.z - s) * c : 0.f,
+                           ok ? (r.v.w - s) * c : 0.f);
+    } else if constexpr (MODE == MODE_F32F_NORM) {
+        const float s = g.sub_mean, c = g.inv_scale;
+        return make_float4(ok ? obs_norm((r.v.x - s) * c, r.mu.x, r.rs.x) : 0.f,
+                           ok ? obs_norm((r.v.y - s) * c, r.mu.y, r.rs.y) : 0.f,
+                           ok ? obs_norm((r.v.z - s) * c, r.mu.z, r.rs.z) : 0.f,
+                           ok ? obs_norm((r.v.w - s) * c, r.mu.w, r.rs.w) : 0.f);
     } else {
         return make_float4(ok ? r.v.x : 0.f, ok ? r.v.y : 0.f, ok ? r.v.z : 0.f, ok ? r.v.w : 0.f);
     }
@@ -365,7 +411,7 @@ __global__ __launch_bounds__(256) void k_conv_fwd(ConvG g, const void *__restric
                                                   float *__restrict__ out, int64_t Mtot, int k_per_split,
                                                   float *__restrict__ partial) {
     using T = Tile<BM, BN, WM, WN>;
-    constexpr bool U8 = MODE == MODE_U8;
+    constexpr bool FR = frame_layout<MODE>();
     constexpr bool VECB = MODE != MODE_GENERIC;
     constexpr int LDA = BM + 1, LDB = BN + 4;
     __shared__ __attribute__((aligned(16))) float As[32 * LDA];
@@ -380,11 +426,13 @@ __global__ __launch_bounds__(256) void k_conv_fwd(ConvG g, const void *__restric
     const int kend = (kbeg + k_per_split < K) ? kbeg + k_per_split : K;
 
     // A slots.  f32 NHWC input: k-quad fastest across lanes (row = tid/8 + 32*s, k-quad = tid%8): 8 lanes read one
-    // 128-byte run of channels.  Raw u8 NCHW input: row fastest (row = tid%32 + 32*s, k-quad = tid/32): consecutive
-    // output pixels are `stride` bytes apart, so 32 lanes x 4 bytes cover one contiguous 128-byte span of the frame.
-    const int arow = U8 ? (tid & 31) : (tid >> 3);
-    const int kq = (U8 ? (tid >> 5) : (tid & 7)) * 4;
+    // 128-byte run of channels.  Raw NCHW frames: row fastest (row = tid%32 + 32*s, k-quad = tid/32): consecutive
+    // output pixels are `stride` pixels apart, so 32 lanes x 4 bytes cover one contiguous 128-byte span of a u8 frame
+    // (f32 frames: 32 lanes x 16 bytes, `stride` floats apart).
+    const int arow = FR ? (tid & 31) : (tid >> 3);
+    const int kq = (FR ? (tid >> 5) : (tid & 7)) * 4;
     int64_t abase[T::SA];
+    int apo[T::SA];
     bool aval[T::SA];
 #pragma unroll
     for (int s = 0; s < T::SA; ++s) {
@@ -392,9 +440,9 @@ __global__ __launch_bounds__(256) void k_conv_fwd(ConvG g, const void *__restric
         aval[s] = m < Mtot;
         const uint32_t mm = aval[s] ? (uint32_t)m : 0u;
         const uint32_t smp = fdiv(mm, g.dOHOW), pix = mm - smp * (uint32_t)(g.OH * g.OW);
-        const bool u8 = MODE == MODE_GENERIC ? g.in_u8 != 0 : U8;
-        abase[s] = sample_base(g, index, offset, in_stride, smp) +
-                   (u8 ? patch_origin<true>(g, pix) : patch_origin<false>(g, pix));
+        const bool fr = MODE == MODE_GENERIC ? in_is_frame(g.in_u8) : FR;
+        apo[s] = fr ? patch_origin<true>(g, pix) : patch_origin<false>(g, pix);
+        abase[s] = sample_base(g, index, offset, in_stride, smp) + apo[s];
     }
     // B slots: F-major: column quad cg, reduction row kk0 + s*(1024/BN)
     constexpr int BG = BN / 4, BROWS = 256 / BG;
@@ -411,7 +459,7 @@ __global__ __launch_bounds__(256) void k_conv_fwd(ConvG g, const void *__restric
         aok = ka < kend;
         const uint32_t kc = aok ? (uint32_t)ka : (uint32_t)kbeg;
 #pragma unroll
-        for (int s = 0; s < T::SA; ++s) ra[s] = load_act_raw<MODE>(g, in, abase[s], kc, aok && aval[s]);
+        for (int s = 0; s < T::SA; ++s) ra[s] = load_act_raw<MODE>(g, in, abase[s], apo[s], kc, aok && aval[s]);
 #pragma unroll
         for (int s = 0; s < T::SB; ++s) {
             const int k = k0 + bkk0 + s * BROWS;
@@ -488,7 +536,7 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(ConvG g, const void *__restr
                                                     int64_t m_per_split) {
     constexpr int BM = 128;
     using T = Tile<BM, BN, WM, WN>;
-    constexpr bool U8 = MODE == MODE_U8;
+    constexpr bool FR = frame_layout<MODE>();
     constexpr bool VECB = MODE != MODE_GENERIC;
     constexpr int LDA = BM + 4, LDB = BN + 4;
     __shared__ __attribute__((aligned(16))) float As[32 * LDA];
@@ -504,17 +552,18 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(ConvG g, const void *__restr
     // A' slots (free-axis-major): 4 consecutive weight rows k for one reduction index m.
     // f32 NHWC input: k-group fastest across lanes (32 lanes read 512 contiguous bytes of channels); slot s holds
     //   k-group tid%32 of reduction row tid/32 + 8*s.
-    // raw u8 NCHW input: m fastest (32 consecutive output pixels = one contiguous 128-byte span); slot s holds k-group
-    //   tid/32 + 8*s of reduction row tid%32, so the m -> (sample, pixel) decomposition is done once per chunk.
+    // raw NCHW frames: m fastest (32 consecutive output pixels = one contiguous 128-byte span of a u8 frame); slot s
+    //   holds k-group tid/32 + 8*s of reduction row tid%32, so the m -> (sample, pixel) decomposition is done once per
+    //   chunk.
     int kg[T::SA], tapo[T::SA];
     bool kval[T::SA];
 #pragma unroll
     for (int s = 0; s < T::SA; ++s) {
-        kg[s] = (U8 ? (tid >> 5) + 8 * s : (tid & 31)) * 4;
+        kg[s] = (FR ? (tid >> 5) + 8 * s : (tid & 31)) * 4;
         const int k = k0row + kg[s];
         kval[s] = k < K;
         const uint32_t kc = kval[s] ? (uint32_t)k : 0u;
-        tapo[s] = MODE == MODE_GENERIC ? 0 : (U8 ? tap_offset<true>(g, kc) : tap_offset<false>(g, kc));
+        tapo[s] = MODE == MODE_GENERIC ? 0 : (FR ? tap_offset<true>(g, kc) : tap_offset<false>(g, kc));
     }
     constexpr int BG = BN / 4, BROWS = 256 / BG;
     const int bcg = (tid % BG) * 4, bkk0 = tid / BG;
@@ -525,21 +574,31 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(ConvG g, const void *__restr
     ARaw<MODE> ra[T::SA];
     float4 rb[T::SB];
     bool aok[T::SA], bok[T::SB];
-    auto patch_base = [&](int64_t m, bool ok) -> int64_t {
+    // base of the patch of reduction row m (sample base + patch origin); po = the patch origin alone
+    auto patch_base = [&](int64_t m, bool ok, int &po) -> int64_t {
         const uint32_t mm = ok ? (uint32_t)m : (uint32_t)mbeg;
         const uint32_t smp = fdiv(mm, g.dOHOW), pix = mm - smp * (uint32_t)(g.OH * g.OW);
-        const bool u8 = MODE == MODE_GENERIC ? g.in_u8 != 0 : U8;
-        return sample_base(g, index, offset, in_stride, smp) +
-               (u8 ? patch_origin<true>(g, pix) : patch_origin<false>(g, pix));
+        const bool fr = MODE == MODE_GENERIC ? in_is_frame(g.in_u8) : FR;
+        po = fr ? patch_origin<true>(g, pix) : patch_origin<false>(g, pix);
+        return sample_base(g, index, offset, in_stride, smp) + po;
     };
     auto gload = [&](int64_t mc) {
-        if constexpr (U8) {
+        if constexpr (FR) {
             const int64_t m = mc + (tid & 31);
             const bool mok = m < mend;
-            const int64_t base = patch_base(m, mok);
+            int po;
+            const int64_t base = patch_base(m, mok, po);
 #pragma unroll
             for (int s = 0; s < T::SA; ++s) {
-                ra[s].v = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(in) + base + tapo[s]);
+                if constexpr (MODE == MODE_U8) {
+                    ra[s].v = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(in) + base + tapo[s]);
+                } else {
+                    ra[s].v = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(in) + base + tapo[s]);
+                    if constexpr (MODE == MODE_F32F_NORM) {
+                        ra[s].mu = *reinterpret_cast<const float4 *>(g.nmu + po + tapo[s]);
+                        ra[s].rs = *reinterpret_cast<const float4 *>(g.nrstd + po + tapo[s]);
+                    }
+                }
                 aok[s] = mok && kval[s];
             }
         } else {
@@ -548,11 +607,12 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(ConvG g, const void *__restr
                 const int64_t m = mc + (tid >> 5) + 8 * s;
                 const bool mok = m < mend;
                 aok[s] = mok && kval[s];
-                const int64_t base = patch_base(m, mok);
+                int po;
+                const int64_t base = patch_base(m, mok, po);
                 if constexpr (MODE == MODE_F32)
                     ra[s].v = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(in) + base + tapo[s]);
                 else
-                    ra[s] = load_act_raw<MODE_GENERIC>(g, in, base, (uint32_t)(k0row + kg[s]), aok[s]);
+                    ra[s] = load_act_raw<MODE_GENERIC>(g, in, base, po, (uint32_t)(k0row + kg[s]), aok[s]);
             }
         }
 #pragma unroll
@@ -569,7 +629,7 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(ConvG g, const void *__restr
         __syncthreads();
 #pragma unroll
         for (int s = 0; s < T::SA; ++s) {
-            const int lrow = U8 ? (tid & 31) : (tid >> 5) + 8 * s;  // reduction index (m) inside the chunk
+            const int lrow = FR ? (tid & 31) : (tid >> 5) + 8 * s;  // reduction index (m) inside the chunk
             // rows k >= K are never stored and reduction rows >= mend are annihilated by the zeroed dY rows below,
             // so the activation operand is stored unmasked on the vector paths (clamped loads read finite data)
             *reinterpret_cast<float4 *>(&As[lrow * LDA + kg[s]]) =
@@ -803,9 +863,12 @@ static int num_cus() {
     return v;
 }
 
+// (g.nmu set: a launch of sf_conv_fwd_norm / sf_conv_wgrad_norm)
 static int pick_mode(const ConvG &g) {
     if (!g.vecA || !g.vecB) return MODE_GENERIC;
-    return g.in_u8 ? MODE_U8 : MODE_F32;
+    if (in_is_u8(g.in_u8)) return MODE_U8;
+    if (g.in_u8 == IN_F32_FRAME) return g.nmu ? MODE_F32F_NORM : MODE_F32F;
+    return MODE_F32;
 }
 
 // geometry contract of k_conv_u8_img<2, 4, 5, 16, *>
@@ -862,6 +925,8 @@ extern "C" int64_t sf_conv_fwd_workspace(int64_t n, const sf_conv_desc *h_desc) 
     do {                                                               \
         if (mode == MODE_F32) FWD_LAUNCH(BM, BN, WM, WN, MODE_F32);    \
         else if (mode == MODE_U8) FWD_LAUNCH(BM, BN, WM, WN, MODE_U8); \
+        else if (mode == MODE_F32F) FWD_LAUNCH(BM, BN, WM, WN, MODE_F32F); \
+        else if (mode == MODE_F32F_NORM) FWD_LAUNCH(BM, BN, WM, WN, MODE_F32F_NORM); \
         else FWD_LAUNCH(BM, BN, WM, WN, MODE_GENERIC);                 \
     } while (0)
 
@@ -870,7 +935,7 @@ extern "C" int64_t sf_conv_fwd_workspace(int64_t n, const sf_conv_desc *h_desc) 
 // SF_RELU_MASK=0 switches the path off (A/B: the data gradient below reads the activation again).
 static bool relu_mask_ok(const sf_conv_desc *d, int64_t n) {
     static const int on = getenv("SF_RELU_MASK") ? atoi(getenv("SF_RELU_MASK")) : 1;
-    if (!on || !d->in_u8 || d->relu != 1 || d->Cout != 32) return false;
+    if (!on || !in_is_u8(d->in_u8) || d->relu != 1 || d->Cout != 32) return false;
     const ConvG g = make_geom(d);
     return conv1_bf16_ok(g, pick_mode(g), n);
 }
@@ -878,21 +943,30 @@ extern "C" int sf_conv_relu_mask_supported(int64_t n, const sf_conv_desc *h_desc
     return h_desc && n > 0 && check_desc(h_desc, "sf_conv_relu_mask_supported") == 0 && relu_mask_ok(h_desc, n) ? 1 : 0;
 }
 
+// vector loads of the activation operand also need aligned bases (f32: 16 bytes; u8 frames: 4 bytes; the normaliser's
+// tables of f32 frames: 16 bytes)
+static bool act_aligned(const ConvG &g, const void *in, int64_t in_sample_stride) {
+    if (in_is_u8(g.in_u8)) return ((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0;
+    const bool tabs = !g.nmu || (((uintptr_t)g.nmu & 15) == 0 && ((uintptr_t)g.nrstd & 15) == 0);
+    return ((uintptr_t)in & 15) == 0 && in_sample_stride % 4 == 0 && tabs;
+}
+
+// mu / rstd: the observation normaliser's tables (f32 frames through sf_conv_fwd_norm), else NULL
 static int conv_fwd_impl(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *w,
                          const float *bias, float *out, uint32_t *relu_mask, int64_t n, const sf_conv_desc *h_desc,
-                         void *workspace, int64_t workspace_bytes, void *stream) {
+                         void *workspace, int64_t workspace_bytes, void *stream, const float *mu = nullptr,
+                         const float *rstd = nullptr) {
     int rc = check_desc(h_desc, "sf_conv_fwd");
     if (rc) return rc;
     SF_REQUIRE(in && w && out && n > 0, "sf_conv_fwd: bad args");
     SF_REQUIRE(((uintptr_t)workspace & 15) == 0, "sf_conv_fwd: workspace must be 16-byte aligned");
-    const ConvG g = make_geom(h_desc);
+    ConvG g = make_geom(h_desc);
+    g.nmu = mu; g.nrstd = rstd;
     const int64_t Mtot = n * g.OH * g.OW;
     SF_REQUIRE(Mtot < (1LL << 31), "sf_conv_fwd: M=%lld exceeds 2^31 rows; split the batch", (long long)Mtot);
     int mode = pick_mode(g);
-    if (mode != MODE_GENERIC) {  // vector loads also need aligned bases
-        const bool al = h_desc->in_u8 ? (((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0)
-                                      : (((uintptr_t)in & 15) == 0 && in_sample_stride % 4 == 0);
-        if (!al || ((uintptr_t)w & 15) != 0) mode = MODE_GENERIC;
+    if (mode != MODE_GENERIC) {
+        if (!act_aligned(g, in, in_sample_stride) || ((uintptr_t)w & 15) != 0) mode = MODE_GENERIC;
     }
     hipStream_t st = STREAM(stream);
     // Nature-CNN conv1 on raw frames: strip-image kernel (bytes converted once into an f32 LDS image, im2col read
@@ -1028,7 +1102,7 @@ static bool launch_img_fwd(const ConvG &g, const float *in, int64_t in_stride, c
 
 // ---- glds forward (pre-transposed weights)
 static bool glds_fwd_ok(const sf_conv_desc *d) {
-    return !d->in_u8 && d->Cin % 32 == 0 && d->traj_T == 0;
+    return d->in_u8 == IN_F32_NHWC && d->Cin % 32 == 0 && d->traj_T == 0;
 }
 // Launch plan of the LDS-DMA forward.  Grids of >= 768 128x64 tiles run unsplit (tile width by grid quantisation).
 // A wide layer with a long reduction and too few rows to fill the chip (the fc layer of a rollout step: 4096 x 512,
@@ -1119,13 +1193,13 @@ static GldsFwdPlan plan_fwd_t(int64_t Mtot, int N, int K) {
 }
 static bool small_linear_wgrad_ok(const sf_conv_desc *d) {
     static const int on = getenv("SF_LINEAR_NARROW") ? atoi(getenv("SF_LINEAR_NARROW")) : 1;
-    return on && !d->in_u8 && d->traj_T == 0 && d->KH == 1 && d->KW == 1 && d->H == 1 && d->W == 1 && d->Cout <= 64 &&
+    return on && d->in_u8 == IN_F32_NHWC && d->traj_T == 0 && d->KH == 1 && d->KW == 1 && d->H == 1 && d->W == 1 && d->Cout <= 64 &&
            d->Cin <= 64;
 }
 // narrow linear layers (the heads): one wave per 16 rows, operands straight from memory (sf_nn_narrow.h)
 static bool narrow_fwd_ok(const sf_conv_desc *d, int64_t n) {
     static const int on = getenv("SF_LINEAR_NARROW") ? atoi(getenv("SF_LINEAR_NARROW")) : 1;
-    return on && !d->in_u8 && d->traj_T == 0 && d->KH == 1 && d->KW == 1 && d->H == 1 && d->W == 1 && d->Cout <= 32 &&
+    return on && d->in_u8 == IN_F32_NHWC && d->traj_T == 0 && d->KH == 1 && d->KW == 1 && d->H == 1 && d->W == 1 && d->Cout <= 32 &&
            d->Cin % 16 == 0 && n < (1 << 30);
 }
 extern "C" int sf_conv_fwd_t_supported(int64_t n, const sf_conv_desc *h_desc) {
@@ -1384,7 +1458,7 @@ static bool wgrad_glds_wanted(int64_t Mtot, int K, int N) {
 // SF_WGRAD_IMG=0: back on k_wgrad_glds; =1: conv3 only; default 3: both (A/B switch).
 static int wgrad_img_variant(const sf_conv_desc *d, int64_t n) {
     static const int on = getenv("SF_WGRAD_IMG") ? atoi(getenv("SF_WGRAD_IMG")) : 3;
-    if (!on || d->in_u8 || d->traj_T != 0 || d->Cout != 64 || n < 512) return 0;
+    if (!on || d->in_u8 != IN_F32_NHWC || d->traj_T != 0 || d->Cout != 64 || n < 512) return 0;
     if ((on & 1) && d->Cin == 64 && d->H == 9 && d->W == 9 && d->KH == 3 && d->KW == 3 && d->stride == 1) return 1;
     if ((on & 2) && d->Cin == 32 && d->H == 20 && d->W == 20 && d->KH == 4 && d->KW == 4 && d->stride == 2) return 2;
     return 0;
@@ -1405,7 +1479,7 @@ extern "C" int64_t sf_conv_wgrad_workspace(int64_t n, const sf_conv_desc *h_desc
         const int64_t zs = cdiv64(Mtot, 64) < 1024 ? cdiv64(Mtot, 64) : 1024;
         if (zs > Z) Z = (int)zs;
     }
-    if (!h_desc->in_u8) {  // the LDS-DMA kernel may pick other tiles (hence another split count)
+    if (h_desc->in_u8 == IN_F32_NHWC) {  // the LDS-DMA kernel may pick other tiles (hence another split count)
         const WgradGlds q = plan_wgrad_glds(Mtot, K, N);
         if (q.Z > Z) Z = q.Z;
     }
@@ -1420,32 +1494,43 @@ extern "C" int64_t sf_conv_wgrad_workspace(int64_t n, const sf_conv_desc *h_desc
     do {                                                             \
         if (mode == MODE_F32) WGRAD_LAUNCH(BN, WM, WN, MODE_F32);    \
         else if (mode == MODE_U8) WGRAD_LAUNCH(BN, WM, WN, MODE_U8); \
+        else if (mode == MODE_F32F) WGRAD_LAUNCH(BN, WM, WN, MODE_F32F); \
+        else if (mode == MODE_F32F_NORM) WGRAD_LAUNCH(BN, WM, WN, MODE_F32F_NORM); \
         else WGRAD_LAUNCH(BN, WM, WN, MODE_GENERIC);                 \
     } while (0)
 
+// per-mode occupancy of the register-staged weight-gradient kernel
+template <int BN, int WM, int WN>
+static int occ_wgrad_mode(int mode) {
+    switch (mode) {
+        case MODE_F32: return occ_wgrad<BN, WM, WN, MODE_F32>();
+        case MODE_U8: return occ_wgrad<BN, WM, WN, MODE_U8>();
+        case MODE_F32F: return occ_wgrad<BN, WM, WN, MODE_F32F>();
+        case MODE_F32F_NORM: return occ_wgrad<BN, WM, WN, MODE_F32F_NORM>();
+        default: return occ_wgrad<BN, WM, WN, MODE_GENERIC>();
+    }
+}
+
+// mu / rstd: the observation normaliser's tables (f32 frames through sf_conv_wgrad_norm), else NULL
 static int conv_wgrad_impl(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
                            const float *dout, const uint32_t *dmask, float *dw, float *db, int64_t n,
-                           const sf_conv_desc *h_desc, void *workspace, void *stream) {
+                           const sf_conv_desc *h_desc, void *workspace, void *stream, const float *mu = nullptr,
+                           const float *rstd = nullptr) {
     int rc = check_desc(h_desc, "sf_conv_wgrad");
     if (rc) return rc;
     SF_REQUIRE(in && dout && dw && workspace && n > 0, "sf_conv_wgrad: bad args");
     SF_REQUIRE(((uintptr_t)workspace & 15) == 0, "sf_conv_wgrad: workspace must be 16-byte aligned");
-    const ConvG g = make_geom(h_desc);
+    ConvG g = make_geom(h_desc);
+    g.nmu = mu; g.nrstd = rstd;
     const int64_t Mtot = n * g.OH * g.OW;
     SF_REQUIRE(Mtot < (1LL << 31), "sf_conv_wgrad: M=%lld exceeds 2^31 rows; split the batch", (long long)Mtot);
     const int K = g.K, N = g.Cout;
     const int BN = wgrad_bn(N);
     int mode = pick_mode(g);
     if (mode != MODE_GENERIC) {
-        const bool al = h_desc->in_u8 ? (((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0)
-                                      : (((uintptr_t)in & 15) == 0 && in_sample_stride % 4 == 0);
-        if (!al || ((uintptr_t)dout & 15) != 0) mode = MODE_GENERIC;
+        if (!act_aligned(g, in, in_sample_stride) || ((uintptr_t)dout & 15) != 0) mode = MODE_GENERIC;
     }
-    int bpc;
-    if (BN == 32) bpc = mode == MODE_F32 ? occ_wgrad<32, 4, 1, MODE_F32>() : mode == MODE_U8 ? occ_wgrad<32, 4, 1, MODE_U8>()
-                                                                                              : occ_wgrad<32, 4, 1, MODE_GENERIC>();
-    else bpc = mode == MODE_F32 ? occ_wgrad<64, 2, 2, MODE_F32>() : mode == MODE_U8 ? occ_wgrad<64, 2, 2, MODE_U8>()
-                                                                                     : occ_wgrad<64, 2, 2, MODE_GENERIC>();
+    const int bpc = BN == 32 ? occ_wgrad_mode<32, 4, 1>(mode) : occ_wgrad_mode<64, 2, 2>(mode);
     const SplitPlan p = plan_splits(Mtot, K, N, 128, BN, bpc);
     const int Zws = plan_splits(Mtot, K, N, 128, BN).Z;  // what sf_conv_wgrad_workspace promised room for
     float *partial_w = reinterpret_cast<float *>(workspace);
@@ -1576,9 +1661,14 @@ extern "C" int sf_conv_wgrad_relu_mask(const void *in, int64_t in_sample_stride,
 // normalised f32 copy of the frames exists anywhere.  mu / rstd: the normaliser's f32 tables [Cin*H*W] in the frame's NCHW
 // order (sf_obsnorm_update writes them).  Launches sf_conv_norm_supported() accepts: the Nature-CNN conv1 geometry the
 // strip-image kernels are built for, n >= 256, 4-byte aligned frames; everything else goes through sf_obsnorm_apply.
+// f32 frames (in_u8 = 2) take every geometry: the register-staged kernels (k_conv_fwd / k_conv_wgrad) form
+// clamp(((x - sub_mean) * inv_scale - mu[d]) * rstd[d], +-5) in their loaders, with 16-byte loads of pixels and table
+// entries where sf_conv_fwd would use them and the scalar loader otherwise.
 static bool conv_norm_ok(const sf_conv_desc *d, int64_t n) {
     static const int on = getenv("SF_CONV1_NORM") ? atoi(getenv("SF_CONV1_NORM")) : 1;
-    if (!on || !d || n <= 0 || !d->in_u8 || d->Cout != 32) return false;
+    if (!on || !d || n <= 0) return false;
+    if (d->in_u8 == IN_F32_FRAME) return true;
+    if (!in_is_u8(d->in_u8) || d->Cout != 32) return false;
     const ConvG g = make_geom(d);
     // the strip kernels' compile-time geometry; ANY n (their n >= 256 dispatch threshold is a speed heuristic of the plain
     // entry points, the kernels themselves are correct for every n >= 1 and there is no other kernel to fall back to)
@@ -1593,6 +1683,12 @@ extern "C" int sf_conv_fwd_norm(const void *in, int64_t in_sample_stride, const 
     int rc = check_desc(h_desc, "sf_conv_fwd_norm");
     if (rc) return rc;
     SF_REQUIRE(in && mu && rstd && w && out && n > 0, "sf_conv_fwd_norm: bad args");
+    if (h_desc->in_u8 == IN_F32_FRAME) {
+        SF_REQUIRE(conv_norm_ok(h_desc, n) && ((uintptr_t)in & 3) == 0 && ((uintptr_t)mu & 3) == 0 && ((uintptr_t)rstd & 3) == 0,
+                   "sf_conv_fwd_norm: unsupported launch (see sf_conv_norm_supported; f32 frames and tables 4-byte aligned)");
+        return conv_fwd_impl(in, in_sample_stride, index, offset, w, bias, out, nullptr, n, h_desc, nullptr, 0, stream, mu,
+                             rstd);
+    }
     SF_REQUIRE(conv_norm_ok(h_desc, n) && ((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0 &&
                    ((uintptr_t)mu & 15) == 0 && ((uintptr_t)rstd & 15) == 0,
                "sf_conv_fwd_norm: unsupported layer / launch (see sf_conv_norm_supported; frames 4-byte, tables 16-byte aligned)");
@@ -1612,6 +1708,12 @@ extern "C" int sf_conv_wgrad_norm(const void *in, int64_t in_sample_stride, cons
     int rc = check_desc(h_desc, "sf_conv_wgrad_norm");
     if (rc) return rc;
     SF_REQUIRE(in && mu && rstd && dout && dw && workspace && n > 0, "sf_conv_wgrad_norm: bad args");
+    if (h_desc->in_u8 == IN_F32_FRAME) {
+        SF_REQUIRE(conv_norm_ok(h_desc, n) && ((uintptr_t)in & 3) == 0 && ((uintptr_t)mu & 3) == 0 && ((uintptr_t)rstd & 3) == 0,
+                   "sf_conv_wgrad_norm: unsupported launch (see sf_conv_norm_supported; f32 frames and tables 4-byte aligned)");
+        return conv_wgrad_impl(in, in_sample_stride, index, offset, dout, nullptr, dw, db, n, h_desc, workspace, stream, mu,
+                               rstd);
+    }
     SF_REQUIRE(conv_norm_ok(h_desc, n) && ((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0 &&
                    ((uintptr_t)mu & 15) == 0 && ((uintptr_t)rstd & 15) == 0 && ((uintptr_t)dout & 15) == 0 &&
                    ((uintptr_t)workspace & 15) == 0,
@@ -1674,7 +1776,7 @@ extern "C" int sf_conv_dgrad(const float *dout, const float *w, const float *in_
     int rc = check_desc(h_desc, "sf_conv_dgrad");
     if (rc) return rc;
     SF_REQUIRE(dout && w && din && n > 0, "sf_conv_dgrad: bad args");
-    SF_REQUIRE(!h_desc->in_u8, "sf_conv_dgrad: the observation layer has no data gradient");
+    SF_REQUIRE(!in_is_frame(h_desc->in_u8), "sf_conv_dgrad: the observation layer has no data gradient");
     SF_REQUIRE(h_desc->Cout % 4 == 0 || (h_desc->KH == 1 && h_desc->KW == 1),
                "sf_conv_dgrad: Cout must be a multiple of 4 for spatial kernels");
     const ConvG g = make_geom(h_desc);
@@ -1775,9 +1877,28 @@ extern "C" int sf_conv_kernel_name(int op, int64_t n, const sf_conv_desc *h_desc
                                    int cap) {
     int rc = check_desc(h_desc, "sf_conv_kernel_name");
     if (rc) return rc;
-    SF_REQUIRE(out && cap >= 48 && n > 0 && op >= 0 && op <= 3, "sf_conv_kernel_name: bad args");
-    const ConvG g = make_geom(h_desc);
+    SF_REQUIRE(out && cap >= 48 && n > 0 && op >= 0 && op <= 5, "sf_conv_kernel_name: bad args");
+    ConvG g = make_geom(h_desc);
     const int64_t Mtot = n * g.OH * g.OW;
+    if (op >= 4) {  // 4: sf_conv_fwd_norm, 5: sf_conv_wgrad_norm (f32 frames: the register-staged kernels, no split)
+        SF_REQUIRE(conv_norm_ok(h_desc, n), "sf_conv_kernel_name: not a launch sf_conv_norm_supported accepts");
+        if (in_is_u8(g.in_u8)) {
+            snprintf(out, cap, op == 4 ? "k_conv_u8_img_norm<2, 4, 5, 16>" : "k_conv1_wgrad_img_norm<2, 4>");
+            return SF_OK;
+        }
+        static const float tab_probe[4] __attribute__((aligned(16))) = {0.f, 0.f, 0.f, 0.f};
+        g.nmu = tab_probe; g.nrstd = tab_probe;  // aligned tables assumed, as for every operand here
+        const int nmode = pick_mode(g);
+        if (op == 4) {
+            const FwdPlan p = plan_fwd(Mtot, g.Cout, g.K, 0);
+            if (p.cfg == 0) snprintf(out, cap, "k_conv_fwd<%d, 32, 4, 1, %d>", Mtot >= 256 * 2048 ? 256 : 128, nmode);
+            else snprintf(out, cap, "k_conv_fwd<%d, 64, 2, 2, %d>", p.cfg == 1 ? 128 : 64, nmode);
+        } else {
+            if (wgrad_bn(g.Cout) == 32) snprintf(out, cap, "k_conv_wgrad<32, 4, 1, %d>", nmode);
+            else snprintf(out, cap, "k_conv_wgrad<64, 2, 2, %d>", nmode);
+        }
+        return SF_OK;
+    }
     const int mode = pick_mode(g);
     if (op == 0 && conv1_img_ok(g, mode, n)) {
         static const int wide_on = getenv("SF_CONV1_WIDE") ? atoi(getenv("SF_CONV1_WIDE")) : 1;

@@ -30,10 +30,14 @@ class sf_loss_cfg(C.Structure):
 
 
 class sf_conv_desc(C.Structure):
+    """in_u8 is the input format: IN_F32_NHWC (activations), IN_U8_FRAME or IN_F32_FRAME (NCHW observation frames)"""
     _fields_ = [("Cin", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cout", C.c_int32), ("KH", C.c_int32),
                 ("KW", C.c_int32), ("stride", C.c_int32), ("OH", C.c_int32), ("OW", C.c_int32),
                 ("in_u8", C.c_int32), ("relu", C.c_int32), ("traj_T", C.c_int32), ("sub_mean", C.c_float),
                 ("inv_scale", C.c_float)]
+
+
+IN_F32_NHWC, IN_U8_FRAME, IN_F32_FRAME = 0, 1, 2  # sf_conv_desc.in_u8
 
 
 class sf_res_desc(C.Structure):
@@ -197,7 +201,7 @@ class _timed:
         return False
 
 
-_OPS = {"fwd": 0, "wgrad": 1, "dgrad": 2, "fwd_t": 3}
+_OPS = {"fwd": 0, "wgrad": 1, "dgrad": 2, "fwd_t": 3, "fwd_norm": 4, "wgrad_norm": 5}
 _names: dict = {}
 
 
@@ -748,7 +752,7 @@ def synth_step(actions, env0, num_actions, seed, step, rewards, terminated) -> N
 
 # ---- network kernels (csrc/sf_nn.hip)
 def _raw_in(t: torch.Tensor, desc: sf_conv_desc) -> C.c_void_p:
-    want = torch.uint8 if desc.in_u8 else torch.float32
+    want = torch.uint8 if desc.in_u8 == IN_U8_FRAME else torch.float32
     if t.dtype != want:
         raise SfHipError(f"conv input: expected {want}, got {t.dtype}")
     if not t.is_cuda:
@@ -807,14 +811,21 @@ def conv_norm_supported(n, desc: sf_conv_desc) -> bool:
     return bool(load().sf_conv_norm_supported(i64(n), C.byref(desc)))
 
 
-def _nkey(op, n, desc, name):
+def _nkey(op, n, desc, name_op):
+    """profiling key of a normalising launch: grouped under `op` ("fwd" / "wgrad"), named by sf_conv_kernel_name(name_op)"""
     k = _dkey(op, n, desc)
-    return None if k is None else k[:-1] + (name,)
+    if k is None:
+        return None
+    nk = (name_op,) + k[1:-1] + (desc.in_u8,)
+    name = _names.get(nk)
+    if name is None:
+        name = _names[nk] = conv_kernel_name(_OPS[name_op], n, desc)
+    return k[:-1] + (name,)
 
 
 def conv_fwd_norm(inp, in_sample_stride, index, offset, mu, rstd, w, bias, out, n, desc: sf_conv_desc) -> None:
-    """conv1 on raw u8 frames with the observation normaliser's tables applied in the loader (sf_conv_fwd_norm)"""
-    with _timed(_nkey("fwd", n, desc, "k_conv_u8_img_norm<2, 4, 5, 16>")):
+    """conv1 on raw frames (u8 or f32) with the observation normaliser's tables applied in the loader (sf_conv_fwd_norm)"""
+    with _timed(_nkey("fwd", n, desc, "fwd_norm")):
         _check(load().sf_conv_fwd_norm(_raw_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"), i64(offset),
                                        ptr(mu, "f32", "mu"), ptr(rstd, "f32", "rstd"), ptr(w, "f32", "w"),
                                        ptr(bias, "f32", "bias"), ptr(out, "f32", "out"), i64(n), C.byref(desc),
@@ -822,7 +833,7 @@ def conv_fwd_norm(inp, in_sample_stride, index, offset, mu, rstd, w, bias, out, 
 
 
 def conv_wgrad_norm(inp, in_sample_stride, index, offset, mu, rstd, dout, dw, db, n, desc: sf_conv_desc, workspace) -> None:
-    with _timed(_nkey("wgrad", n, desc, "k_conv1_wgrad_img_norm<2, 4>")):
+    with _timed(_nkey("wgrad", n, desc, "wgrad_norm")):
         _check(load().sf_conv_wgrad_norm(_raw_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"),
                                          i64(offset), ptr(mu, "f32", "mu"), ptr(rstd, "f32", "rstd"),
                                          ptr(dout, "f32", "dout"), ptr(dw, "f32", "dw"), ptr(db, "f32", "db"), i64(n),

@@ -8,7 +8,8 @@ with Sample Factory checkpoints; the compute is libsf_hip.so'
    -> one launch for grad-norm, one for Adam, one bucket for the data-parallel all-reduce;
  * activations are NHWC, weights K-major [K, Cout]; conversion from/to the reference's OIHW / [out,in] layouts happens
    only in load_state_dict()/state_dict();
- * the u8 -> f32 observation normalisation (utils/normalize.py:51-70) is fused into the first layer's loader;
+ * the observation normalisation of image frames, u8 or f32 (utils/normalize.py:51-70), is fused into the first layer's
+   loader;
  * critic_linear and distribution_linear are one fused [F, 1+A] GEMM (column 0 = value).
 
 Native: conv or MLP encoder (relu/tanh/elu), optional one-layer GRU / LSTM core (per-step cell kernels; width-512 BPTT
@@ -37,6 +38,8 @@ _CONV1_NORM = os.environ.get("SF_CONV1_NORM", "1") != "0"  # A/B switch: 0 = nor
 _MLP2 = os.environ.get("SF_MLP2", "1") != "0"          # A/B switch: 0 = layer-by-layer encoder in the rollout as well
 
 ACT_KIND = {"relu": 1, "tanh": 2, "elu": 3}  # model/model_utils.py:27-35; fused into the GEMM epilogues
+# first conv layers that read raw NCHW observation frames in place (weights k = (c*KH + kh)*KW + kw): u8 / f32 frames
+FRAME_KINDS = {"conv_u8": lib.IN_U8_FRAME, "conv_f32frame": lib.IN_F32_FRAME}
 
 CONV_ARCHS = {  # model/encoder.py:126-134: [out_channels, kernel, stride]
     "convnet_simple": [[32, 8, 4], [64, 4, 2], [128, 3, 2]],
@@ -71,7 +74,7 @@ class _Layer:
         self.in_act_kind = 0      # activation kind of the tensor feeding this layer (fused into its dgrad epilogue)
         self.rnn_l = 0            # index of the stacked recurrent layer a "rnn_ih" / "rnn_hh" projection belongs to
         self.desc = desc
-        self.kind = kind          # "conv_u8" | "conv" | "linear" | "linear_after_conv" | "heads"
+        self.kind = kind          # "conv_u8" | "conv_f32frame" | "conv" | "linear" | "linear_after_conv" | "heads"
         self.ref_w_shape = ref_w_shape
         self.first_fc_chw = first_fc_chw
         self.K = desc.KH * desc.KW * desc.Cin
@@ -85,7 +88,7 @@ class _Layer:
     # ---- layout conversion (reference <-> native)
     def w_from_ref(self, w_ref: torch.Tensor) -> torch.Tensor:
         d = self.desc
-        if self.kind == "conv_u8":      # k = (c*KH + kh)*KW + kw
+        if self.kind in FRAME_KINDS:    # k = (c*KH + kh)*KW + kw
             return w_ref.reshape(d.Cout, self.K).t().contiguous()
         if self.kind == "conv":         # k = (kh*KW + kw)*Cin + c
             return w_ref.permute(2, 3, 1, 0).reshape(self.K, d.Cout).contiguous()
@@ -96,7 +99,7 @@ class _Layer:
 
     def w_to_ref(self, w: torch.Tensor) -> torch.Tensor:
         d = self.desc
-        if self.kind == "conv_u8":
+        if self.kind in FRAME_KINDS:
             return w.t().reshape(d.Cout, d.Cin, d.KH, d.KW).contiguous()
         if self.kind == "conv":
             return w.reshape(d.KH, d.KW, d.Cin, d.Cout).permute(3, 2, 0, 1).contiguous()
@@ -154,6 +157,7 @@ class ActorCritic:
         space = obs_space[obs_key]
         self.obs_shape = tuple(space.shape)
         self.obs_u8 = np.dtype(space.dtype) == np.uint8
+        self.obs_f32 = np.dtype(space.dtype) == np.float32
         self.num_action_params = calc_num_action_parameters(action_space)
         self.layers: List[_Layer] = []
         sub_mean = float(cfg.obs_subtract_mean)
@@ -166,8 +170,12 @@ class ActorCritic:
         self._fused_norm = False
         if len(self.obs_shape) == 3:
             C, H, W = self.obs_shape
-            if not self.obs_u8:
-                raise NotImplementedError("image observations must be uint8 CHW (pixel_format=CHW)")
+            if not (self.obs_u8 or self.obs_f32):
+                raise NotImplementedError(f"image observations must be uint8 or float32 CHW (pixel_format=CHW), got "
+                                          f"{np.dtype(space.dtype)}")
+            # the first layer reads the frames in place: u8 or f32 NCHW (sf_conv_desc.in_u8 = 1 / 2)
+            frame_kind = "conv_u8" if self.obs_u8 else "conv_f32frame"
+            fmt = FRAME_KINDS[frame_kind]
             pfx = f"encoder.encoders.{obs_key}.enc."
             cin, h, w = C, H, W
             for i, (cout, k, s) in enumerate(CONV_ARCHS[cfg.encoder_conv_architecture]):
@@ -176,15 +184,15 @@ class ActorCritic:
                 # sf_conv_wgrad_norm: frames stay u8, first layer keeps its raw-frame form); any other first layer reads a
                 # materialised normalised f32 NHWC batch (utils/normalize.py)
                 if i == 0 and norm_input and _CONV1_NORM:
-                    probe = lib.sf_conv_desc(Cin=cin, H=h, W=w, Cout=cout, KH=k, KW=k, stride=s, OH=oh, OW=ow, in_u8=1,
+                    probe = lib.sf_conv_desc(Cin=cin, H=h, W=w, Cout=cout, KH=k, KW=k, stride=s, OH=oh, OW=ow, in_u8=fmt,
                                              relu=act, traj_T=0, sub_mean=sub_mean, inv_scale=inv_scale)
                     self._fused_norm = bool(lib.conv_norm_supported(1, probe))
                 first = i == 0 and (not norm_input or self._fused_norm)
                 desc = lib.sf_conv_desc(Cin=cin, H=h, W=w, Cout=cout, KH=k, KW=k, stride=s, OH=oh, OW=ow,
-                                        in_u8=int(first), relu=act, traj_T=0,
+                                        in_u8=fmt if first else lib.IN_F32_NHWC, relu=act, traj_T=0,
                                         sub_mean=sub_mean if first else 0.0, inv_scale=inv_scale if first else 1.0)
                 self.layers.append(_Layer(f"{pfx}conv_head.{2 * i}", desc, (cout, cin, k, k),
-                                          "conv_u8" if first else "conv"))
+                                          frame_kind if first else "conv"))
                 cin, h, w = cout, oh, ow
             feat, chw = cin * h * w, (cin, h, w)
             for j, size in enumerate(cfg.encoder_conv_mlp_layers):
@@ -213,7 +221,7 @@ class ActorCritic:
         # an image encoder WITHOUT fully connected layers ends in a conv layer: its output rows are [pixel][channel] (NHWC)
         # while the reference flattens [channel][pixel] (encoder.py:117: view(-1, conv_head_out_size) of an NCHW tensor) —
         # the composite re-orders the features when it concatenates them (out_chw = (C, OH, OW))
-        self.out_chw = chw if (self.headless and len(self.obs_shape) == 3 and self.layers[-1].kind in ("conv", "conv_u8")) else None
+        self.out_chw = chw if (self.headless and len(self.obs_shape) == 3 and (self.layers[-1].kind == "conv" or self.layers[-1].kind in FRAME_KINDS)) else None
         if use_rnn:  # model/core.py:19-64: nn.GRU / nn.LSTM(input=feat, hidden=rnn_size), torch gate order
             Hs = cfg.rnn_size
             G = 3 if cfg.rnn_type == "gru" else 4
@@ -501,7 +509,7 @@ class ActorCritic:
 
     def _aligned_frames(self, tag, x, stride, idx, off, tT, n):
         """the n frames a launch would read — dataset row d = idx[i] | off + i, slab row d + d // traj_T (sf_common.h
-        sample_base) — gathered into a dense, allocator-aligned u8 [n, obs_elems] buffer"""
+        sample_base) — gathered into a dense, allocator-aligned [n, obs_elems] buffer of the frames' dtype"""
         d = idx.long() if idx is not None else torch.arange(off, off + n, device=x.device)
         pos = d + torch.div(d, int(tT), rounding_mode="floor") if tT else d
         avail = (x.untyped_storage().nbytes() - x.storage_offset() * x.element_size()) // x.element_size()
@@ -511,6 +519,11 @@ class ActorCritic:
         lib.recording_unsafe("frames gathered by a torch op")
         torch.index_select(flat, 0, pos, out=out)
         return out, self.obs_elems, None, 0, 0
+
+    def _frames_vector_geometry(self) -> bool:
+        """the first layer's loader can fetch f32 frames as 16-byte quads (KW, stride and W multiples of 4)"""
+        d = self.layers[0].desc
+        return d.KW % 4 == 0 and d.stride % 4 == 0 and d.W % 4 == 0
 
     def _zbuf(self, key, shape):
         """like _buf but zero-filled on creation (buffers with never-written padding columns)"""
@@ -644,9 +657,13 @@ class ActorCritic:
                 # image frames: (x - mu) * rstd, clamped, happens in conv1's loader (sf_conv_fwd_norm) — the frames stay
                 # u8 in the slab and no normalised f32 copy is written or read
                 norm_tabs = tabs if tabs is not None else (on.mu_tab, on.rstd_tab)
-                if x.data_ptr() % 4 or stride % 4:
+                if self.obs_u8 and (x.data_ptr() % 4 or stride % 4):
                     # the loader fetches the bytes as 32-bit words: a frame view at an odd address (a custom slab offset)
                     # degrades to one aligned u8 copy of the batch's frames instead of failing the launch
+                    x, stride, idx, off, tT = self._aligned_frames(tag, x, stride, idx, off, tT, n)
+                elif not self.obs_u8 and (x.data_ptr() % 16 or stride % 4) and self._frames_vector_geometry():
+                    # f32 frames: a view off the 16-byte grid would drop the loader to its scalar form; one aligned copy
+                    # of the batch's frames keeps the 16-byte loads
                     x, stride, idx, off, tT = self._aligned_frames(tag, x, stride, idx, off, tT, n)
             else:  # any other shape: materialise the normalised f32 batch (NHWC), as the reference does
                 xn = self._buf((tag, "obsn"), (n, self.obs_elems))

@@ -84,18 +84,35 @@ def create_actor_critic(cfg, obs_space, action_space, device, all_reduce=None):
                 return MultiKeyActorCritic(cfg, obs_space, action_space, device, all_reduce=all_reduce)
             except NotImplementedError as e:
                 log.warning("resnet_impala: torch path (%s)", e)
-    if f.is_default() and len(obs_keys_of(obs_space)) <= 1 and not stacked_rnn and not separate and not resnet:
+    # float32 CHW image frames (e.g. Box(0, 1, (C, H, W), float32)): the first conv layer reads them in place on cuda; a
+    # CPU device and SF_NATIVE_F32FRAMES=0 take the torch path, as resnet_impala does
+    import numpy as np
+    f32_frames = any(len(obs_space[k].shape) == 3 and np.dtype(obs_space[k].dtype) == np.float32
+                     for k in obs_keys_of(obs_space))
+    torch_f32_frames = f32_frames and (torch.device(device).type != "cuda" or
+                                       os.environ.get("SF_NATIVE_F32FRAMES", "1") == "0")
+    if (f.is_default() and len(obs_keys_of(obs_space)) <= 1 and not stacked_rnn and not separate and not resnet
+            and not torch_f32_frames):
         from sample_factory_amd.model.actor_critic import ActorCritic
-        return ActorCritic(cfg, obs_space, action_space, device, all_reduce=all_reduce)
+        try:
+            return ActorCritic(cfg, obs_space, action_space, device, all_reduce=all_reduce)
+        except NotImplementedError as e:  # an observation the native model refuses (e.g. float64 frames)
+            from sample_factory_amd.utils.utils import log
+            log.warning("default model: torch path (%s)", e)
     if (f.is_default() and not stacked_rnn and separate and not resnet and torch.device(device).type == "cuda"
+            and not torch_f32_frames
             and os.environ.get("SF_NATIVE_SEPARATE_WEIGHTS", "1") != "0"
             and (not multi or os.environ.get("SF_NATIVE_MULTIKEY", "1") != "0")):
         # cfg.actor_critic_share_weights=False (ActorCriticSeparateWeights, model/actor_critic.py:198-334) on the native
         # kernels since round 6: two towers on one flat parameter buffer (model/actor_critic_separate.py)
         from sample_factory_amd.model.actor_critic_separate import SeparateActorCritic
-        return SeparateActorCritic(cfg, obs_space, action_space, device, all_reduce=all_reduce)
+        try:
+            return SeparateActorCritic(cfg, obs_space, action_space, device, all_reduce=all_reduce)
+        except NotImplementedError as e:
+            from sample_factory_amd.utils.utils import log
+            log.warning("separate actor / critic weights: torch path (%s)", e)
     if (f.is_default() and len(obs_keys_of(obs_space)) > 1 and not stacked_rnn and not separate and not resnet
-            and torch.device(device).type == "cuda" and os.environ.get("SF_NATIVE_MULTIKEY", "1") != "0"):
+            and not torch_f32_frames and torch.device(device).type == "cuda" and os.environ.get("SF_NATIVE_MULTIKEY", "1") != "0"):
         # observation dicts of several keys (model/encoder.py:33-69, MultiInputEncoder: one encoder per key, concatenated) on
         # the native kernels since round 6: one encoder tower per key + a trunk on one flat parameter buffer
         # (model/actor_critic_multikey.py).  A shape the towers refuse keeps the torch path below.
