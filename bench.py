@@ -8,7 +8,12 @@ Nature-CNN actor-critic, 1xMI355X") with the NS-2 learner preset of SURVEY.md §
 torch.distributed.run, one rank per GPU) every rank runs the same per-GPU workload on its own env shard and gradients /
 advantage moments are all-reduced over RCCL: weak scaling, value = whole-job env-steps/s.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c5] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the result line (with the roofline of
+the dominant kernel, which comes from the warm-up and the timed steps themselves).  `--full` adds, after that, the legs
+that take runs of their own: the `secondary` workloads (c5, c3, c2 variants and the reference on this GPU, each a process
+of its own) and the `cpu_baseline` leg (the reference's CPU path on the host cores).
 
 `--workload c5` = BASELINE.json configs[4] on one GPU per rank: Ant-shaped synthetic continuous env (obs f32[27],
 Box(8)), 2048 envs, MLP[64,64] tanh encoder + LSTM-512 core, V-trace, KL loss, rollout = recurrence = 32.
@@ -464,9 +469,12 @@ def main():
     ap.add_argument("--rollout", type=int, default=32)
     ap.add_argument("--num_batches", type=int, default=4)
     ap.add_argument("--num_epochs", type=int, default=None, help="default: 1 for c2, 2 for c5 (mujoco preset)")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="c2, one GPU: after the timed region also measure the secondary workload lines and the "
+                         "cpu_baseline leg (runs of their own; a plain run prints only what the headline needs)")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--no_secondary", action="store_true",
-                    help="c2, one GPU: skip the secondary workload lines (c5, c3) measured after the timed region")
+                    help="--full without the secondary workload lines (c5, c3) measured after the timed region")
     ap.add_argument("--no_kernel_events", action="store_true", help="skip per-launch HIP events (no roofline object)")
     ap.add_argument("--cpu_baseline_envs", type=int, default=256)
     ap.add_argument("--cpu_reference_envs", type=int, default=1024,
@@ -779,7 +787,7 @@ def main():
                             "ms_per_step": round(net_ms, 2), "tflops_avg": round(net_flops / (net_ms * 1e-3) / 1e12, 2),
                             "top": breakdown},
     }
-    if rank == 0 and world == 1 and args.workload == "c2" and not args.no_secondary and not args.async_rl \
+    if args.full and rank == 0 and world == 1 and args.workload == "c2" and not args.no_secondary and not args.async_rl \
             and args.envs == 4096:
         # release this run's slab and activations first: the secondary runs get the whole device
         del runner
@@ -787,7 +795,7 @@ def main():
         gc.collect()
         torch.cuda.empty_cache()
         out["secondary"] = secondary_lines(args)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "c2":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "c2":
         out["cpu_baseline"] = cpu_baseline_leg(args, T)
     if rank == 0:
         print(json.dumps(out))

@@ -26,7 +26,7 @@ K=$(find $O/trace -name "*kernel_stats.csv" | head -1)
 cp $O/trace_bench.json $O/${TAG}_bench_under_rocprof.json 2>/dev/null
 # the bench line with the traffic figure of the pass just taken (same kernel sources -> same hash)
 if [ -s $O/${TAG}_traffic.json ]; then cp $O/${TAG}_traffic.json profiles/${TAG}_traffic.json; fi
-python bench.py --steps 20 > $O/${TAG}_bench.json 2> $O/bench.err
+python bench.py --steps 20 --full > $O/${TAG}_bench.json 2> $O/bench.err
 # drop the bulky per-dispatch tables, keep stats + counter summaries
 find $O -name "*kernel_trace.csv" -size +2M -delete
 find $O -name "*counter_collection.csv" -size +8M -delete
