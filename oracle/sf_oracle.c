@@ -583,11 +583,14 @@ SFO_API void sfo_sample_categorical(const float *logits, long N, int A, uint32_t
         uint32_t w[4];
         philox4x32_10(step, 0u, 2u, 0u, seed, row0 + (uint32_t)i, w);
         const float u = (float)(w[0] >> 8) * (1.0f / 16777216.0f); /* 24-bit uniform in [0,1) */
-        float acc = 0.f; int a = A - 1;
+        float acc = 0.f; int a = -1, last_pos = A - 1;
         for (int k = 0; k < A; ++k) {
-            acc += expf((z[k] - mx) - lse);
+            const float p = expf((z[k] - mx) - lse);
+            acc += p;
+            if (p > 0.f) last_pos = k;
             if (u < acc) { a = k; break; }
         }
+        if (a < 0) a = last_pos; /* u beyond the f32 CDF: the last action with non-zero probability */
         actions[i] = (float)a;
         logp[i] = (z[a] - mx) - lse;
     }
@@ -662,8 +665,14 @@ SFO_API void sfo_sample_tuple(const float *logits, long N, const int *head_n, in
             uint32_t w[4];
             philox4x32_10(step, (uint32_t)h, 2u, 0u, seed, row0 + (uint32_t)i, w);
             const float u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);
-            float acc = 0.f; int a = nh - 1;
-            for (int k = 0; k < nh; ++k) { acc += expf((z[off + k] - mx) - lse); if (u < acc) { a = k; break; } }
+            float acc = 0.f; int a = -1, last_pos = nh - 1;
+            for (int k = 0; k < nh; ++k) {
+                const float p = expf((z[off + k] - mx) - lse);
+                acc += p;
+                if (p > 0.f) last_pos = k;
+                if (u < acc) { a = k; break; }
+            }
+            if (a < 0) a = last_pos;
             actions[i * NA + aoff] = (float)a;
             lps += (z[off + a] - mx) - lse;
             off += nh; aoff += 1;

@@ -1523,12 +1523,18 @@ __global__ __launch_bounds__(256) void k_sample_write(const float *__restrict__ 
         const float u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);
         float acc = 0.f;
         bool found = false;
+        int last_pos = A - 1;  // last action whose probability did not underflow
 #pragma unroll
         for (int k = 0; k < MAXA; ++k)
             if (k < A && !found) {
-                acc += expf((zz[k] - mx) - lse);
+                const float p = expf((zz[k] - mx) - lse);
+                acc += p;
+                if (p > 0.f) last_pos = k;
                 if (u < acc) { a = k; found = true; }
             }
+        // the f32 CDF can end a few ulps below 1 and u can reach 1 - 2^-24: take the last action that has any
+        // probability, never a zero-probability tail action (torch.multinomial never draws a zero weight)
+        if (!found) a = last_pos;
     }
     float lp = 0.f;
 #pragma unroll
@@ -1690,10 +1696,15 @@ __global__ __launch_bounds__(256) void k_sample_write_tuple(const float *__restr
             sf_philox4x32_10(step, (uint32_t)h, 2u, 0u, seed, row0 + (uint32_t)b, w);
             const float u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);
             float acc = 0.f;
+            int last_pos = nh - 1;
+            bool found = false;
             for (int k = 0; k < nh; ++k) {
-                acc += expf((z[off + k] - mx) - lse);
-                if (u < acc) { a = k; break; }
+                const float p = expf((z[off + k] - mx) - lse);
+                acc += p;
+                if (p > 0.f) last_pos = k;
+                if (u < acc) { a = k; found = true; break; }
             }
+            if (!found) a = last_pos;  // rounding left u beyond the CDF: the last action with non-zero probability
         }
         lp_sum += (z[off + a] - mx) - lse;
         t_actions[it * NA + aoff] = (float)a;
