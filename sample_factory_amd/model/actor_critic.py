@@ -12,11 +12,12 @@ with Sample Factory checkpoints; the compute is libsf_hip.so'
    loader;
  * critic_linear and distribution_linear are one fused [F, 1+A] GEMM (column 0 = value).
 
-Native: conv or MLP encoder (relu/tanh/elu), optional one-layer GRU / LSTM core (per-step cell kernels; width-512 BPTT
-passes as ONE persistent launch each, csrc/sf_rnn.hip), MLP decoder, input running-mean-std (normalize_input), Discrete /
-Tuple-of-Discrete / Box action heads.  Separate actor/critic weights and multi-layer RNNs raise; user-registered torch
-modules and multi-key observation dicts go through model/torch_policy.py (the network under autograd, everything around
-it native) — there is no silent fallback.
+Native: conv or MLP encoder (relu/tanh/elu), optional GRU / LSTM core of cfg.rnn_num_layers stacked layers (per-step cell
+kernels; width-512 BPTT passes as ONE persistent launch each, csrc/sf_rnn.hip), MLP decoder, input running-mean-std
+(normalize_input), Discrete / Tuple-of-Discrete / Box action heads.  This class is the single-key shared-weights model and a
+tower of the composites (model/composite.py): separate actor / critic weights, observation dicts with several keys and the
+resnet_impala encoder.  What the native models refuse raises NotImplementedError; model_factory.py then builds the network
+in torch (model/torch_policy.py: the network under autograd, everything around it native).
 """
 from __future__ import annotations
 
@@ -114,7 +115,108 @@ def _linear_desc(K, N, relu) -> lib.sf_conv_desc:
                             traj_T=0, sub_mean=0.0, inv_scale=1.0)
 
 
-class ActorCritic:
+class NativeModel:
+    """What every native model, a single tower or a composite of towers (model/composite.py), answers the same way."""
+
+    def eval(self):
+        return self.train(False)
+
+    def model_to_device(self, device):
+        assert torch.device(device).type == "cuda", "the native model only lives on the GPU"
+
+    def normalize_obs(self, obs):
+        """Identity: normalisation is fused into the first layer (the f32 copy is never materialised)."""
+        return obs
+
+
+class NativeTower(NativeModel):
+    """The scratch, normaliser and initialisation plumbing of a single tower (`ActorCritic`, `ResnetImpalaTower`): device
+    buffers keyed by name, per-stream-role workspaces, the launch key of recorded launch programs and the observation
+    normaliser of key `obs_key` under the reference's state-dict names."""
+
+    def _init_scratch(self) -> None:
+        self._bufs: Dict = {}
+        self._layout_gen = 0  # bumped whenever a buffer, workspace or parameter view is (re)allocated: launch_key()
+        self._wss: Dict = {}
+        self._tls = threading.local()  # per-thread "which scratch am I using": a sampler thread may run beside the learner
+        self._snap = None
+        self._snap_tabs = None
+        self.snap_read = 0
+
+    def _buf(self, key, shape, dtype=torch.float32):
+        t = self._bufs.get(key)
+        if t is None or t.shape != torch.Size(shape) or t.dtype != dtype:
+            t = torch.empty(shape, dtype=dtype, device=self.device)
+            self._bufs[key] = t
+            self._layout_gen += 1
+        return t
+
+    def _zbuf(self, key, shape):
+        """like _buf but zero-filled on creation (buffers with never-written padding columns)"""
+        t = self._bufs.get(key)
+        if t is None or t.shape != torch.Size(shape):
+            t = torch.zeros(shape, dtype=torch.float32, device=self.device)
+            self._bufs[key] = t
+            self._layout_gen += 1
+        return t
+
+    def _workspace(self, nbytes: int) -> torch.Tensor:
+        """split-K / wgrad scratch; one per stream role so that the rollout and learner streams never share it"""
+        key = getattr(self._tls, "role", "learner")
+        ws = self._wss.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=self.device)
+            self._wss[key] = ws
+            self._layout_gen += 1
+        return ws
+
+    def launch_key(self, tag: str = "inf"):
+        """identity of every address a one-step forward under `tag` hands the library (weights or the published snapshot
+        it reads, activation buffers, workspaces): a recorded launch program (lib.LaunchProgram) of that forward is valid
+        exactly as long as this value does not change"""
+        return (self._layout_gen, self.snap_read if self._snap is not None else -1)
+
+    @property
+    def _norm_prefix(self) -> str:
+        return f"obs_normalizer.running_mean_std.running_mean_std.{self.obs_key}."
+
+    def normalizer_state(self) -> Dict[str, torch.Tensor]:
+        return self.obs_normalizer.state_dict(self._norm_prefix) if self.obs_normalizer is not None else {}
+
+    def load_normalizer_state(self, sd) -> None:
+        if self.obs_normalizer is not None and self._norm_prefix + "count" in sd:
+            self.obs_normalizer.load_state_dict(sd, self._norm_prefix)
+
+    def initialize_weights(self):
+        """actor_critic.py:73-96: orthogonal (gain) / xavier_uniform / torch_default on the REFERENCE layout; bias 0."""
+        cfg = self.cfg
+        gain = cfg.policy_init_gain
+        sd = {}
+        for name, shape in self.ref_param_shapes():
+            t = torch.empty(shape, dtype=torch.float32)
+            if name.endswith("learned_stddev"):  # action_parameterization.py:58-60
+                t.fill_(math.log(cfg.initial_stddev))
+            elif name.startswith("core.core."):  # nn.GRU/nn.LSTM keep torch's default init (initialize_weights skips them)
+                bound = 1.0 / math.sqrt(self.rnn_H)
+                t.uniform_(-bound, bound)
+            elif name.endswith(".bias"):
+                if cfg.policy_initialization == "torch_default":
+                    fan_in = int(np.prod(dict(self.ref_param_shapes())[name[:-4] + "weight"][1:]))
+                    bound = 1 / math.sqrt(fan_in)
+                    t.uniform_(-bound, bound)
+                else:
+                    t.zero_()
+            elif cfg.policy_initialization == "orthogonal":
+                torch.nn.init.orthogonal_(t, gain=gain)
+            elif cfg.policy_initialization == "xavier_uniform":
+                torch.nn.init.xavier_uniform_(t, gain=gain)
+            else:
+                torch.nn.init.kaiming_uniform_(t, a=math.sqrt(5))
+            sd[name] = t
+        self.load_state_dict(sd, strict=False)
+
+
+class ActorCritic(NativeTower):
     """Shared-weights feed-forward actor-critic (reference: ActorCriticSharedWeights)."""
 
     def __init__(self, cfg, obs_space, action_space, device="cuda", all_reduce=None, obs_key: str = "obs", part: str = "full"):
@@ -135,7 +237,7 @@ class ActorCritic:
         if cfg.use_rnn and (cfg.rnn_num_layers < 1 or cfg.rnn_type not in ("gru", "lstm")):
             raise NotImplementedError("native recurrent core: GRU or LSTM, rnn_num_layers >= 1")
         if not cfg.actor_critic_share_weights:
-            raise NotImplementedError("separate actor/critic weights are outside the hot-path scope (SURVEY.md §2.1)")
+            raise NotImplementedError("separate actor/critic weights: model/actor_critic_separate.py composes two towers")
         if cfg.nonlinearity not in ACT_KIND:
             raise NotImplementedError(f"Unknown nonlinearity {cfg.nonlinearity}")
         act = ACT_KIND[cfg.nonlinearity]
@@ -279,16 +381,11 @@ class ActorCritic:
                                                         all_reduce=all_reduce, world=getattr(cfg, "dp_world", 1))
             if obs_key != "obs":  # mean shift / scale: the key named "obs" only (normalize.py:38-47)
                 self.obs_normalizer.sub_mean, self.obs_normalizer.inv_scale = 0.0, 1.0
-        self._norm_prefix = f"obs_normalizer.running_mean_std.running_mean_std.{obs_key}."
         self._xn: Dict = {}
         self.returns_normalizer: Optional[RunningMeanStdInPlace] = None
         if cfg.normalize_returns and not self.headless:
             self.returns_normalizer = RunningMeanStdInPlace((1,), self.device, all_reduce=all_reduce)
-        self._bufs: Dict = {}
-        self._layout_gen = 0  # bumped whenever a buffer, workspace or parameter view is (re)allocated: launch_key()
-        self._wss: Dict = {}
-        self._tls = threading.local()  # per-thread "which scratch am I using": a sampler thread may run beside the learner
-        self._snap = None
+        self._init_scratch()
         # per-tag results of the last forward: a sampler thread ("inf*" tags) and the learner thread ("boot", "train")
         # call forward_heads concurrently, so nothing a forward leaves behind may live in an untagged attribute
         self._ctx: Dict = {}
@@ -299,9 +396,8 @@ class ActorCritic:
     def seat_flat(self, flat_params: torch.Tensor, flat_grads: torch.Tensor, flat_params_t: torch.Tensor) -> None:
         """(re)build every layer's views on the given flat buffers [num_flat] — parameters, gradients and the Cout-major
         copies [N, K] of the weights of the layers the gfx950 LDS-DMA forward can take (sf_conv_fwd_t; refreshed by
-        params_changed() after every parameter update).  A model composed of several of these (separate actor / critic
-        weights) seats its towers on slices of ONE buffer, so that the optimiser, the gradient exchange and the snapshots
-        see a single flat parameter vector.  Current values are carried over."""
+        params_changed() after every parameter update).  Current values are carried over (a composite seats its towers on
+        slices of its own buffers, model/composite.py)."""
         old = getattr(self, "flat_params", None)
         if old is not None:
             flat_params.copy_(old)
@@ -326,7 +422,7 @@ class ActorCritic:
         """every layer but the fused heads (an encoder tower has none)"""
         return self.layers if self.headless else self.layers[:-1]
 
-    # ---- what a composite (model/actor_critic_separate.py) needs from a tower, whatever the tower is made of
+    # ---- what a separate-weights composite needs from its towers (model/composite.py)
     @property
     def heads_layer(self):
         return self.layers[-1]
@@ -342,56 +438,11 @@ class ActorCritic:
     def share_snapshot_tables_from(self, other) -> None:
         self._snap_tabs = other._snap_tabs
 
-    def normalizer_state(self) -> Dict[str, torch.Tensor]:
-        return self.obs_normalizer.state_dict(self._norm_prefix) if self.obs_normalizer is not None else {}
-
-    def load_normalizer_state(self, sd) -> None:
-        if self.obs_normalizer is not None and self._norm_prefix + "count" in sd:
-            self.obs_normalizer.load_state_dict(sd, self._norm_prefix)
-
     def train(self, mode=True):
         self.training = mode
         if self.returns_normalizer is not None:
             self.returns_normalizer.train(mode)
         return self
-
-    def eval(self):
-        return self.train(False)
-
-    def model_to_device(self, device):
-        assert torch.device(device).type == "cuda", "the native model only lives on the GPU"
-
-    def normalize_obs(self, obs):
-        """Identity: normalisation is fused into the first layer (the f32 copy is never materialised)."""
-        return obs
-
-    def initialize_weights(self):
-        """actor_critic.py:73-96: orthogonal (gain) / xavier_uniform / torch_default on the REFERENCE layout; bias 0."""
-        cfg = self.cfg
-        gain = cfg.policy_init_gain
-        sd = {}
-        for name, shape in self.ref_param_shapes():
-            t = torch.empty(shape, dtype=torch.float32)
-            if name.endswith("learned_stddev"):  # action_parameterization.py:58-60
-                t.fill_(math.log(cfg.initial_stddev))
-            elif name.startswith("core.core."):  # nn.GRU/nn.LSTM keep torch's default init (initialize_weights skips them)
-                bound = 1.0 / math.sqrt(self.rnn_H)
-                t.uniform_(-bound, bound)
-            elif name.endswith(".bias"):
-                if cfg.policy_initialization == "torch_default":
-                    fan_in = int(np.prod(dict(self.ref_param_shapes())[name[:-4] + "weight"][1:]))
-                    bound = 1 / math.sqrt(fan_in)
-                    t.uniform_(-bound, bound)
-                else:
-                    t.zero_()
-            elif cfg.policy_initialization == "orthogonal":
-                torch.nn.init.orthogonal_(t, gain=gain)
-            elif cfg.policy_initialization == "xavier_uniform":
-                torch.nn.init.xavier_uniform_(t, gain=gain)
-            else:
-                torch.nn.init.kaiming_uniform_(t, a=math.sqrt(5))
-            sd[name] = t
-        self.load_state_dict(sd, strict=False)
 
     def ref_param_shapes(self):
         """(name, shape) of every trainable parameter under the reference's names, in the reference's order."""
@@ -420,9 +471,7 @@ class ActorCritic:
         return out
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
-        sd = {}
-        if self.obs_normalizer is not None:
-            sd.update(self.obs_normalizer.state_dict(self._norm_prefix))
+        sd = self.normalizer_state()
         if self.returns_normalizer is not None:
             sd.update(self.returns_normalizer.state_dict("returns_normalizer."))
         for L in self._body():
@@ -448,8 +497,7 @@ class ActorCritic:
                 L.b.copy_(torch.as_tensor(sd[L.bname], dtype=torch.float32))
             if self.headless:
                 self.params_changed()
-                if self.obs_normalizer is not None and self._norm_prefix + "count" in sd:
-                    self.obs_normalizer.load_state_dict(sd, self._norm_prefix)
+                self.load_normalizer_state(sd)
                 return
             H, A = self.layers[-1], self.num_action_params
             cw = torch.as_tensor(sd["critic_linear.weight"], dtype=torch.float32)
@@ -464,8 +512,7 @@ class ActorCritic:
             H.b.copy_(torch.cat([torch.as_tensor(sd["critic_linear.bias"], dtype=torch.float32).reshape(1), ab,
                                  torch.zeros(pad)]))
             self.params_changed()
-            if self.obs_normalizer is not None and self._norm_prefix + "count" in sd:
-                self.obs_normalizer.load_state_dict(sd, self._norm_prefix)
+            self.load_normalizer_state(sd)
             if self.returns_normalizer is not None and "returns_normalizer.running_mean" in sd:
                 self.returns_normalizer.load_state_dict(sd, "returns_normalizer.")
             elif strict and self.returns_normalizer is not None:
@@ -493,20 +540,6 @@ class ActorCritic:
         return out
 
     # ------------------------------------------------------------------------------------------ compute
-    def _buf(self, key, shape, dtype=torch.float32):
-        t = self._bufs.get(key)
-        if t is None or t.shape != torch.Size(shape) or t.dtype != dtype:
-            t = torch.empty(shape, dtype=dtype, device=self.device)
-            self._bufs[key] = t
-            self._layout_gen += 1
-        return t
-
-    def launch_key(self, tag: str = "inf"):
-        """identity of every address a one-step forward under `tag` hands the library (weights or the published snapshot
-        it reads, activation buffers, workspaces): a recorded launch program (lib.LaunchProgram) of that forward is valid
-        exactly as long as this value does not change"""
-        return (self._layout_gen, self.snap_read if self._snap is not None else -1)
-
     def _aligned_frames(self, tag, x, stride, idx, off, tT, n):
         """the n frames a launch would read — dataset row d = idx[i] | off + i, slab row d + d // traj_T (sf_common.h
         sample_base) — gathered into a dense, allocator-aligned [n, obs_elems] buffer of the frames' dtype"""
@@ -524,15 +557,6 @@ class ActorCritic:
         """the first layer's loader can fetch f32 frames as 16-byte quads (KW, stride and W multiples of 4)"""
         d = self.layers[0].desc
         return d.KW % 4 == 0 and d.stride % 4 == 0 and d.W % 4 == 0
-
-    def _zbuf(self, key, shape):
-        """like _buf but zero-filled on creation (buffers with never-written padding columns)"""
-        t = self._bufs.get(key)
-        if t is None or t.shape != torch.Size(shape):
-            t = torch.zeros(shape, dtype=torch.float32, device=self.device)
-            self._bufs[key] = t
-            self._layout_gen += 1
-        return t
 
     def tensor_segment_ids(self):
         """(seg_id u8 [num_flat], num_segments): which REFERENCE parameter tensor every flat element belongs to
@@ -565,16 +589,6 @@ class ActorCritic:
         for L in self.layers:
             if L.wt is not None:
                 lib.transpose(L.w, L.wt, L.K, L.N)
-
-    def _workspace(self, nbytes: int) -> torch.Tensor:
-        """split-K / wgrad scratch; one per stream role so that the rollout and learner streams never share it"""
-        key = getattr(self._tls, "role", "learner")
-        ws = self._wss.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
-            self._wss[key] = ws
-            self._layout_gen += 1
-        return ws
 
     # ---- async mode (cfg.async_rl): inference reads a published SNAPSHOT of the weights (K20).  The reference copies
     # the state_dict into every inference worker under policy_lock (model_sharing.py:128-143); here the learner

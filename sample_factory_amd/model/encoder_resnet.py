@@ -10,14 +10,13 @@ flatten here, NCHW in the reference).  Every launch of the forward is a C-ABI ca
 programs."""
 from __future__ import annotations
 
-import threading
 from typing import Dict, List
 
 import numpy as np
 import torch
 
 from sample_factory_amd import lib
-from sample_factory_amd.model.actor_critic import ACT_KIND, ActorCritic, _Layer, _linear_desc, _pad
+from sample_factory_amd.model.actor_critic import ACT_KIND, NativeTower, _Layer, _linear_desc, _pad
 
 RESNET_STAGES = ((16, 2), (32, 2), (32, 2))  # encoder.py:180-182 (configuration from the IMPALA paper)
 
@@ -49,7 +48,7 @@ class _Conv3:
         return w.reshape(3, 3, self.Cin, self.N).permute(3, 2, 0, 1).contiguous()
 
 
-class ResnetImpalaTower:
+class ResnetImpalaTower(NativeTower):
     """encoder tower of observation key `obs_key` (an image, u8 CHW) for cfg.encoder_conv_architecture = resnet_impala"""
 
     def __init__(self, cfg, obs_space, action_space, device="cuda", all_reduce=None, obs_key: str = "obs"):
@@ -122,14 +121,7 @@ class ResnetImpalaTower:
                                                         all_reduce=all_reduce, world=getattr(cfg, "dp_world", 1))
             if obs_key != "obs":
                 self.obs_normalizer.sub_mean, self.obs_normalizer.inv_scale = 0.0, 1.0
-        self._norm_prefix = f"obs_normalizer.running_mean_std.running_mean_std.{obs_key}."
-        self._bufs: Dict = {}
-        self._layout_gen = 0
-        self._wss: Dict = {}
-        self._tls = threading.local()
-        self._snap = None
-        self._snap_tabs = None
-        self.snap_read = 0
+        self._init_scratch()
         self._ctx: Dict = {}
         self.seat_flat(torch.zeros(off, dtype=torch.float32, device=self.device),
                        torch.zeros(off, dtype=torch.float32, device=self.device),
@@ -159,14 +151,8 @@ class ResnetImpalaTower:
             out += [(L.wname, tuple(L.ref_w_shape)), (L.bname, (L.N,))]
         return out
 
-    def initialize_weights(self):
-        """actor_critic.py:73-96 on the reference layout (the same rule as the other towers)"""
-        ActorCritic.initialize_weights(self)
-
     def state_dict(self) -> Dict[str, torch.Tensor]:
-        sd = {}
-        if self.obs_normalizer is not None:
-            sd.update(self.obs_normalizer.state_dict(self._norm_prefix))
+        sd = self.normalizer_state()
         for L in self.params:
             sd[L.wname] = L.w_to_ref(L.w.detach()).cpu()
             sd[L.bname] = L.b.detach().cpu().clone()
@@ -197,41 +183,11 @@ class ResnetImpalaTower:
     def params_changed(self) -> None:
         """nothing derived from the parameters is cached (no transposed weight copies)"""
 
-    def normalizer_state(self) -> Dict[str, torch.Tensor]:
-        return self.obs_normalizer.state_dict(self._norm_prefix) if self.obs_normalizer is not None else {}
-
-    def load_normalizer_state(self, sd) -> None:
-        if self.obs_normalizer is not None and self._norm_prefix + "count" in sd:
-            self.obs_normalizer.load_state_dict(sd, self._norm_prefix)
-
     def train(self, mode=True):
         self.training = mode
         return self
 
-    def eval(self):
-        return self.train(False)
-
-    # ------------------------------------------------------------------------------------------ plumbing
-    def _buf(self, key, shape, dtype=torch.float32):
-        t = self._bufs.get(key)
-        if t is None or t.shape != torch.Size(shape) or t.dtype != dtype:
-            t = torch.empty(shape, dtype=dtype, device=self.device)
-            self._bufs[key] = t
-            self._layout_gen += 1
-        return t
-
-    def _workspace(self, nbytes: int) -> torch.Tensor:
-        key = getattr(self._tls, "role", "learner")
-        ws = self._wss.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=self.device)
-            self._wss[key] = ws
-            self._layout_gen += 1
-        return ws
-
-    def launch_key(self, tag: str = "inf"):
-        return (self._layout_gen, self.snap_read if self._snap is not None else -1)
-
+    # ------------------------------------------------------------------------------------------ weight snapshots
     def enable_weight_snapshots(self) -> None:
         self._snap = [self.flat_params.clone(), self.flat_params.clone()]
         self.snap_read = 0

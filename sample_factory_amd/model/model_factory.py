@@ -4,16 +4,25 @@
     global_model_factory().register_encoder_factory(make_encoder_func)             # (cfg, obs_space) -> Encoder module
     global_model_factory().register_model_core_factory / register_decoder_factory  # (cfg, in_size) -> module
 
-The DEFAULT models (Nature-CNN / MLP encoders, GRU/LSTM core, MLP decoder) run on the native HIP path
-(`model/actor_critic.py`).  A user-registered torch module keeps working: `create_actor_critic` wraps it in
-`TorchPolicyAdapter` (model/torch_policy.py), which drives the user's module through torch autograd on the GPU while
-everything around the network — rollout sampling, slab protocol, GAE, returns normaliser, PPO loss forward/backward,
-gradient clipping, Adam/Lamb on one flat buffer, data-parallel all-reduce — stays on the native kernels (SURVEY.md §8b:
-"native fast-path only when the factory is the default, otherwise fall back to autograd through the user module").
+The DEFAULT models run on the native HIP path: `ActorCritic` (model/actor_critic.py) for one observation key,
+`MultiKeyActorCritic` (model/actor_critic_multikey.py) for several keys and for cfg.encoder_conv_architecture =
+resnet_impala, `SeparateActorCritic` (model/actor_critic_separate.py) for cfg.actor_critic_share_weights=False; every
+recurrent depth and u8 or f32 image frames included.  `create_actor_critic` decides which one to try in one place
+(`_native_candidate`).  A user-registered part, a configuration the native models do not take (a CPU device for all but the
+single-key model, float64 frames, resnet_impala with separate weights, ...) and the SF_NATIVE_RESNET / _MULTIKEY /
+_SEPARATE_WEIGHTS / _F32FRAMES=0 switches get the network in torch instead: `TorchPolicyAdapter` (model/torch_policy.py)
+drives the module through torch autograd on the GPU while everything around the network — rollout sampling, slab protocol,
+GAE, returns normaliser, PPO loss forward/backward, gradient clipping, Adam/Lamb on one flat buffer, data-parallel
+all-reduce — stays on the native kernels ("native fast-path only when the factory is the default, otherwise
+fall back to autograd through the user module").
 """
 from __future__ import annotations
 
+import os
 from typing import Callable, Optional
+
+import numpy as np
+import torch
 
 
 class ModelFactory:
@@ -52,79 +61,62 @@ def global_model_factory() -> ModelFactory:
     return _FACTORY
 
 
-def create_actor_critic(cfg, obs_space, action_space, device, all_reduce=None):
-    """model/actor_critic.py:337-342 create_actor_critic: the native model unless the user registered something"""
-    f = global_model_factory()
-    from sample_factory_amd.model.torch_policy import TorchPolicyAdapter, build_torch_actor_critic, obs_keys_of
-    separate = not bool(cfg.actor_critic_share_weights)
-    # (stacked recurrent layers, cfg.rnn_num_layers > 1, run on the native model since round 6: SF_NATIVE_STACKED_RNN=0 sends
-    # them back to the torch path)
-    import os
-    stacked_rnn = bool(cfg.use_rnn) and int(cfg.rnn_num_layers) > 1 and os.environ.get("SF_NATIVE_STACKED_RNN", "1") == "0"
-    import torch
+def _native_candidate(cfg, obs_space, device):
+    """(the native model class to try for this configuration, None), or (None, why not: None for user-registered parts)"""
+    if not global_model_factory().is_default():
+        return None, None
+    from sample_factory_amd.model.actor_critic import ActorCritic
+    from sample_factory_amd.model.actor_critic_multikey import MultiKeyActorCritic
+    from sample_factory_amd.model.actor_critic_separate import SeparateActorCritic
     from sample_factory_amd.model.encoder_resnet import uses_resnet
-    resnet = uses_resnet(cfg, obs_space)
-    multi = len(obs_keys_of(obs_space)) > 1
-    if resnet and f.is_default():
-        # cfg.encoder_conv_architecture = resnet_impala (model/encoder.py:153-221): a native ResnetImpalaTower + the trunk
-        # (model/encoder_resnet.py) on cuda; CPU devices, images the kernels do not take, separate actor / critic weights
-        # and SF_NATIVE_RESNET=0 take the torch path below
-        from sample_factory_amd.utils.utils import log
-        if os.environ.get("SF_NATIVE_RESNET", "1") == "0":
-            log.warning("resnet_impala: torch path (SF_NATIVE_RESNET=0)")
-        elif separate:
-            log.warning("resnet_impala with separate actor / critic weights: torch path")
-        elif stacked_rnn:
-            log.warning("resnet_impala with stacked recurrent layers: torch path (SF_NATIVE_STACKED_RNN=0)")
-        elif multi and os.environ.get("SF_NATIVE_MULTIKEY", "1") == "0":
-            log.warning("resnet_impala with several observation keys: torch path (SF_NATIVE_MULTIKEY=0)")
-        else:
-            from sample_factory_amd.model.actor_critic_multikey import MultiKeyActorCritic
-            try:
-                return MultiKeyActorCritic(cfg, obs_space, action_space, device, all_reduce=all_reduce)
-            except NotImplementedError as e:
-                log.warning("resnet_impala: torch path (%s)", e)
-    # float32 CHW image frames (e.g. Box(0, 1, (C, H, W), float32)): the first conv layer reads them in place on cuda; a
-    # CPU device and SF_NATIVE_F32FRAMES=0 take the torch path, as resnet_impala does
-    import numpy as np
-    f32_frames = any(len(obs_space[k].shape) == 3 and np.dtype(obs_space[k].dtype) == np.float32
-                     for k in obs_keys_of(obs_space))
-    torch_f32_frames = f32_frames and (torch.device(device).type != "cuda" or
-                                       os.environ.get("SF_NATIVE_F32FRAMES", "1") == "0")
-    if (f.is_default() and len(obs_keys_of(obs_space)) <= 1 and not stacked_rnn and not separate and not resnet
-            and not torch_f32_frames):
-        from sample_factory_amd.model.actor_critic import ActorCritic
+    from sample_factory_amd.model.torch_policy import obs_keys_of
+
+    def off(switch):
+        return os.environ.get(switch, "1") == "0"
+
+    keys = obs_keys_of(obs_space)
+    multi, separate = len(keys) > 1, not cfg.actor_critic_share_weights
+    cuda = torch.device(device).type == "cuda"
+    if uses_resnet(cfg, obs_space):  # on any device and frame dtype: the resnet tower refuses what it cannot run
+        if off("SF_NATIVE_RESNET"):
+            return None, "resnet_impala with SF_NATIVE_RESNET=0"
+        if separate:
+            return None, "resnet_impala with separate actor / critic weights"
+        if multi and off("SF_NATIVE_MULTIKEY"):
+            return None, "resnet_impala with several observation keys and SF_NATIVE_MULTIKEY=0"
+        return MultiKeyActorCritic, None
+    if any(len(obs_space[k].shape) == 3 and np.dtype(obs_space[k].dtype) == np.float32 for k in keys):
+        if not cuda:
+            return None, "float32 image frames on a CPU device"
+        if off("SF_NATIVE_F32FRAMES"):
+            return None, "float32 image frames with SF_NATIVE_F32FRAMES=0"
+    if not separate and not multi:
+        return ActorCritic, None  # on any device
+    if not cuda:
+        return None, "separate actor / critic weights or several observation keys on a CPU device"
+    if multi and off("SF_NATIVE_MULTIKEY"):
+        return None, "several observation keys with SF_NATIVE_MULTIKEY=0"
+    if separate:
+        if off("SF_NATIVE_SEPARATE_WEIGHTS"):
+            return None, "separate actor / critic weights with SF_NATIVE_SEPARATE_WEIGHTS=0"
+        return SeparateActorCritic, None
+    return MultiKeyActorCritic, None
+
+
+def create_actor_critic(cfg, obs_space, action_space, device, all_reduce=None):
+    """model/actor_critic.py:337-342 create_actor_critic: the native model unless the user registered something or the
+    native kernels do not take this configuration; then the network in torch (everything around it stays native)"""
+    from sample_factory_amd.model.torch_policy import TorchPolicyAdapter, build_torch_actor_critic
+    from sample_factory_amd.utils.utils import log
+    cls, why_not = _native_candidate(cfg, obs_space, device)
+    if cls is not None:
         try:
-            return ActorCritic(cfg, obs_space, action_space, device, all_reduce=all_reduce)
-        except NotImplementedError as e:  # an observation the native model refuses (e.g. float64 frames)
-            from sample_factory_amd.utils.utils import log
-            log.warning("default model: torch path (%s)", e)
-    if (f.is_default() and not stacked_rnn and separate and not resnet and torch.device(device).type == "cuda"
-            and not torch_f32_frames
-            and os.environ.get("SF_NATIVE_SEPARATE_WEIGHTS", "1") != "0"
-            and (not multi or os.environ.get("SF_NATIVE_MULTIKEY", "1") != "0")):
-        # cfg.actor_critic_share_weights=False (ActorCriticSeparateWeights, model/actor_critic.py:198-334) on the native
-        # kernels since round 6: two towers on one flat parameter buffer (model/actor_critic_separate.py)
-        from sample_factory_amd.model.actor_critic_separate import SeparateActorCritic
-        try:
-            return SeparateActorCritic(cfg, obs_space, action_space, device, all_reduce=all_reduce)
-        except NotImplementedError as e:
-            from sample_factory_amd.utils.utils import log
-            log.warning("separate actor / critic weights: torch path (%s)", e)
-    if (f.is_default() and len(obs_keys_of(obs_space)) > 1 and not stacked_rnn and not separate and not resnet
-            and not torch_f32_frames and torch.device(device).type == "cuda" and os.environ.get("SF_NATIVE_MULTIKEY", "1") != "0"):
-        # observation dicts of several keys (model/encoder.py:33-69, MultiInputEncoder: one encoder per key, concatenated) on
-        # the native kernels since round 6: one encoder tower per key + a trunk on one flat parameter buffer
-        # (model/actor_critic_multikey.py).  A shape the towers refuse keeps the torch path below.
-        from sample_factory_amd.model.actor_critic_multikey import MultiKeyActorCritic
-        try:
-            return MultiKeyActorCritic(cfg, obs_space, action_space, device, all_reduce=all_reduce)
-        except NotImplementedError as e:
-            from sample_factory_amd.utils.utils import log
-            log.warning("multi-key observations: torch path (%s)", e)
-    # cfg.actor_critic_share_weights=False with several keys, CPU devices, user-registered parts:
-    # the default architecture in torch: same fallback as a user-registered model, everything around the network
-    # stays native
+            return cls(cfg, obs_space, action_space, device, all_reduce=all_reduce)
+        except NotImplementedError as e:  # a shape the native model refuses (e.g. float64 frames)
+            why_not = f"{cls.__name__}: {e}"
+    if why_not is not None:
+        log.warning("the network runs in torch: %s", why_not)
+    f = global_model_factory()
     if f.make_actor_critic_func is not None:
         module = f.make_actor_critic_func(cfg, obs_space, action_space)
     else:
