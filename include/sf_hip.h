@@ -381,11 +381,14 @@ int sf_conv_wgrad_relu_mask(const void *in, int64_t in_sample_stride, const int3
  * aligned).  No normalised copy of the frames exists in HBM (28 KB instead of 28 + 2 x 113 KB per
  * frame and pass).  sf_conv_wgrad_norm = the weight / bias gradient against the same normalised input (dout already
  * masked by the activation derivative; workspace >= sf_conv_wgrad_workspace bytes).  sf_conv_norm_supported: 1 for the
- * launches these take (u8 frames: Nature-CNN conv1 geometry 4x84x84 -> 32, 8x8 stride 4, any n; f32 frames, in_u8 = 2:
- * every geometry, on the f32 matrix instructions, x' = clamp(((x - sub_mean) * inv_scale - mu[d]) * rstd[d], +-5) formed
- * in the loader, frames / tables 4-byte aligned, 16-byte vector loads where sf_conv_fwd would use them and the tables
- * are 16-byte aligned); otherwise sf_obsnorm_apply + sf_conv_fwd on the f32 batch.  Sample addressing (index | offset,
- * traj_T) as sf_conv_fwd. */
+ * launches these take: every valid descriptor of u8 frames (in_u8 = 1) or f32 frames (in_u8 = 2), any geometry, any n.
+ * They run on the f32 matrix instructions with x' formed in the loader of the register-staged kernels: vector loads
+ * (4 u8 pixels per 4-byte word / 4 f32 pixels per 16 bytes, and 16 bytes of each table) when KW, stride, W and Cout are
+ * multiples of 4, the frames and their sample stride 4-byte (u8) / 16-byte (f32) aligned and the tables 16-byte aligned;
+ * the scalar loader otherwise (tables and f32 frames 4-byte aligned).  The Nature-CNN conv1 on u8 frames (4x84x84 -> 32,
+ * 8x8 stride 4, aligned operands) runs on the strip-image kernels instead.  It answers 0 for f32 NHWC activations
+ * (in_u8 = 0) and under SF_CONV1_NORM=0: then sf_obsnorm_apply + sf_conv_fwd on the f32 batch.  Sample addressing
+ * (index | offset, traj_T) as sf_conv_fwd. */
 int sf_conv_norm_supported(int64_t n, const sf_conv_desc *h_desc);
 int sf_conv_fwd_norm(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *mu,
                      const float *rstd, const float *w, const float *bias, float *out, int64_t n,
@@ -577,6 +580,14 @@ typedef struct {
 int sf_res_conv_fwd(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *w,
                     const float *bias, const float *residual, float *out, float *out_act, int act_out, int64_t n,
                     const sf_res_desc *h_desc, void *stream);
+/* The raw-frame first layer (in_u8 = 1) WITH the observation normaliser applied in the loader (cfg.normalize_input=True):
+ * every in-image pixel becomes clamp(((float(u8) - sub_mean) * inv_scale - mu[d]) * rstd[d], +-5), d = its offset inside
+ * the NCHW frame, mu / rstd = the f32 tables [Cin*H*W] sf_obsnorm_update maintains (4-byte aligned); the zero padding
+ * stays zero, as torch pads the normalised tensor.  No residual, no activated copy; everything else as
+ * sf_res_conv_fwd.  Replaces sf_obsnorm_apply + sf_res_conv_fwd on the f32 NHWC batch. */
+int sf_res_conv_fwd_norm(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *mu,
+                         const float *rstd, const float *w, const float *bias, float *out, int64_t n,
+                         const sf_res_desc *h_desc, void *stream);
 /* MaxPool2d(3, stride=2, padding=1) (encoder.py:165) on f32 NHWC [n,H,W,C] -> [n,(H-1)/2+1,(W-1)/2+1,C] plus the window
  * position kh*3 + kw of every maximum (u8); -inf padding, torch's tie rule (first maximum in scan order, NaN wins). */
 int sf_res_pool_fwd(const float *in, float *out, uint8_t *argmax, int64_t n, int H, int W, int C, void *stream);
@@ -594,6 +605,10 @@ int64_t sf_res_conv_wgrad_workspace(int64_t n, const sf_res_desc *h_desc);
 int sf_res_conv_wgrad(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *dout,
                       float *dw, float *db, int64_t n, const sf_res_desc *h_desc, void *workspace,
                       int64_t workspace_bytes, void *stream);
+/* ... of the raw-frame first layer against the input sf_res_conv_fwd_norm forms (same tables, same workspace size). */
+int sf_res_conv_wgrad_norm(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *mu,
+                           const float *rstd, const float *dout, float *dw, float *db, int64_t n,
+                           const sf_res_desc *h_desc, void *workspace, int64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -126,9 +126,12 @@ constexpr int MODE_U8 = 1;       // raw u8 NCHW observation, KW/stride/W % 4 == 
 constexpr int MODE_GENERIC = 2;  // any geometry: scalar, bounds-checked (slow; odd shapes only)
 constexpr int MODE_F32F = 3;     // f32 NCHW observation frames, KW/stride/W % 4 == 0: 16-byte loads of 4 pixels
 constexpr int MODE_F32F_NORM = 4;  // MODE_F32F + the observation normaliser's tables (sf_conv_fwd_norm / _wgrad_norm)
+constexpr int MODE_U8_NORM = 5;    // MODE_U8 + the observation normaliser's tables: 4-byte load of 4 pixels, 16-byte loads of mu / rstd
 // frames (u8 or f32): reduction index k = (c*KH + kh)*KW + kw over the NCHW frame, output rows fastest across lanes
 template <int MODE>
-constexpr bool frame_layout() { return MODE == MODE_U8 || MODE == MODE_F32F || MODE == MODE_F32F_NORM; }
+constexpr bool frame_layout() {
+    return MODE == MODE_U8 || MODE == MODE_F32F || MODE == MODE_F32F_NORM || MODE == MODE_U8_NORM;
+}
 
 // input-sample base offset (elements) of logical sample `smp`: optional index gather, optional dataset->trajectory
 // slab row mapping (flat index e*T+t  ->  slab row e*(T+1)+t, learner.py:1005-1012 drops column T by *copy*; we
@@ -198,6 +201,11 @@ template <>
 struct ARaw<MODE_F32F_NORM> {
     float4 v, mu, rs;  // four pixels and their normaliser table entries
 };
+template <>
+struct ARaw<MODE_U8_NORM> {
+    uint32_t v;     // four u8 pixels
+    float4 mu, rs;  // their normaliser table entries
+};
 
 // the observation normaliser applied to one converted pixel (running_mean_std.py:108: sub_(mu).mul_(1/sigma).clamp_(-5, 5))
 __device__ __forceinline__ float obs_norm(float x, float mu, float rs) { return fminf(fmaxf((x - mu) * rs, -5.f), 5.f); }
@@ -210,6 +218,11 @@ __device__ __forceinline__ ARaw<MODE> load_act_raw(const ConvG &g, const void *_
     ARaw<MODE> r;
     if constexpr (MODE == MODE_U8) {
         r.v = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(in) + base + tap_offset<true>(g, k));
+    } else if constexpr (MODE == MODE_U8_NORM) {
+        const int t = tap_offset<true>(g, k);
+        r.v = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(in) + base + t);
+        r.mu = *reinterpret_cast<const float4 *>(g.nmu + po + t);
+        r.rs = *reinterpret_cast<const float4 *>(g.nrstd + po + t);
     } else if constexpr (MODE == MODE_F32F || MODE == MODE_F32F_NORM) {
         const int t = tap_offset<true>(g, k);
         r.v = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(in) + base + t);
@@ -250,6 +263,12 @@ __device__ __forceinline__ float4 act_finish(const ConvG &g, const ARaw<MODE> &r
             x[j] = ok ? t : 0.f;
         }
         return make_float4(x[0], x[1], x[2], x[3]);
+    } else if constexpr (MODE == MODE_U8_NORM) {
+        const float s = g.sub_mean, c = g.inv_scale;
+        return make_float4(ok ? obs_norm(((float)(r.v & 0xFFu) - s) * c, r.mu.x, r.rs.x) : 0.f,
+                           ok ? obs_norm(((float)((r.v >> 8) & 0xFFu) - s) * c, r.mu.y, r.rs.y) : 0.f,
+                           ok ? obs_norm(((float)((r.v >> 16) & 0xFFu) - s) * c, r.mu.z, r.rs.z) : 0.f,
+                           ok ? obs_norm(((float)(r.v >> 24) - s) * c, r.mu.w, r.rs.w) : 0.f);
     } else if constexpr (MODE == MODE_F32F) {
         const float s = g.sub_mean, c = g.inv_scale;
         return make_float4(ok ? (r.v.x - s) * c : 0.f, ok ? (r.v.y - s) * c : 0.f, ok ? (r.v.z - s) * c : 0.f,
@@ -590,8 +609,12 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(ConvG g, const void *__restr
             const int64_t base = patch_base(m, mok, po);
 #pragma unroll
             for (int s = 0; s < T::SA; ++s) {
-                if constexpr (MODE == MODE_U8) {
+                if constexpr (MODE == MODE_U8 || MODE == MODE_U8_NORM) {
                     ra[s].v = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(in) + base + tapo[s]);
+                    if constexpr (MODE == MODE_U8_NORM) {
+                        ra[s].mu = *reinterpret_cast<const float4 *>(g.nmu + po + tapo[s]);
+                        ra[s].rs = *reinterpret_cast<const float4 *>(g.nrstd + po + tapo[s]);
+                    }
                 } else {
                     ra[s].v = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(in) + base + tapo[s]);
                     if constexpr (MODE == MODE_F32F_NORM) {
@@ -866,7 +889,7 @@ static int num_cus() {
 // (g.nmu set: a launch of sf_conv_fwd_norm / sf_conv_wgrad_norm)
 static int pick_mode(const ConvG &g) {
     if (!g.vecA || !g.vecB) return MODE_GENERIC;
-    if (in_is_u8(g.in_u8)) return MODE_U8;
+    if (in_is_u8(g.in_u8)) return g.nmu ? MODE_U8_NORM : MODE_U8;
     if (g.in_u8 == IN_F32_FRAME) return g.nmu ? MODE_F32F_NORM : MODE_F32F;
     return MODE_F32;
 }
@@ -927,6 +950,7 @@ extern "C" int64_t sf_conv_fwd_workspace(int64_t n, const sf_conv_desc *h_desc) 
         else if (mode == MODE_U8) FWD_LAUNCH(BM, BN, WM, WN, MODE_U8); \
         else if (mode == MODE_F32F) FWD_LAUNCH(BM, BN, WM, WN, MODE_F32F); \
         else if (mode == MODE_F32F_NORM) FWD_LAUNCH(BM, BN, WM, WN, MODE_F32F_NORM); \
+        else if (mode == MODE_U8_NORM) FWD_LAUNCH(BM, BN, WM, WN, MODE_U8_NORM); \
         else FWD_LAUNCH(BM, BN, WM, WN, MODE_GENERIC);                 \
     } while (0)
 
@@ -944,14 +968,14 @@ extern "C" int sf_conv_relu_mask_supported(int64_t n, const sf_conv_desc *h_desc
 }
 
 // vector loads of the activation operand also need aligned bases (f32: 16 bytes; u8 frames: 4 bytes; the normaliser's
-// tables of f32 frames: 16 bytes)
+// tables of either frame format: 16 bytes)
 static bool act_aligned(const ConvG &g, const void *in, int64_t in_sample_stride) {
-    if (in_is_u8(g.in_u8)) return ((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0;
     const bool tabs = !g.nmu || (((uintptr_t)g.nmu & 15) == 0 && ((uintptr_t)g.nrstd & 15) == 0);
+    if (in_is_u8(g.in_u8)) return ((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0 && tabs;
     return ((uintptr_t)in & 15) == 0 && in_sample_stride % 4 == 0 && tabs;
 }
 
-// mu / rstd: the observation normaliser's tables (f32 frames through sf_conv_fwd_norm), else NULL
+// mu / rstd: the observation normaliser's tables (u8 / f32 frames through sf_conv_fwd_norm), else NULL
 static int conv_fwd_impl(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *w,
                          const float *bias, float *out, uint32_t *relu_mask, int64_t n, const sf_conv_desc *h_desc,
                          void *workspace, int64_t workspace_bytes, void *stream, const float *mu = nullptr,
@@ -1496,6 +1520,7 @@ extern "C" int64_t sf_conv_wgrad_workspace(int64_t n, const sf_conv_desc *h_desc
         else if (mode == MODE_U8) WGRAD_LAUNCH(BN, WM, WN, MODE_U8); \
         else if (mode == MODE_F32F) WGRAD_LAUNCH(BN, WM, WN, MODE_F32F); \
         else if (mode == MODE_F32F_NORM) WGRAD_LAUNCH(BN, WM, WN, MODE_F32F_NORM); \
+        else if (mode == MODE_U8_NORM) WGRAD_LAUNCH(BN, WM, WN, MODE_U8_NORM); \
         else WGRAD_LAUNCH(BN, WM, WN, MODE_GENERIC);                 \
     } while (0)
 
@@ -1507,11 +1532,12 @@ static int occ_wgrad_mode(int mode) {
         case MODE_U8: return occ_wgrad<BN, WM, WN, MODE_U8>();
         case MODE_F32F: return occ_wgrad<BN, WM, WN, MODE_F32F>();
         case MODE_F32F_NORM: return occ_wgrad<BN, WM, WN, MODE_F32F_NORM>();
+        case MODE_U8_NORM: return occ_wgrad<BN, WM, WN, MODE_U8_NORM>();
         default: return occ_wgrad<BN, WM, WN, MODE_GENERIC>();
     }
 }
 
-// mu / rstd: the observation normaliser's tables (f32 frames through sf_conv_wgrad_norm), else NULL
+// mu / rstd: the observation normaliser's tables (u8 / f32 frames through sf_conv_wgrad_norm), else NULL
 static int conv_wgrad_impl(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
                            const float *dout, const uint32_t *dmask, float *dw, float *db, int64_t n,
                            const sf_conv_desc *h_desc, void *workspace, void *stream, const float *mu = nullptr,
@@ -1659,19 +1685,20 @@ extern "C" int sf_conv_wgrad_relu_mask(const void *in, int64_t in_sample_stride,
 // ---- conv1 on raw u8 frames WITH the observation normaliser's running statistics applied in the loader (cfg.normalize_input
 // on image observations: utils/normalize.py:51-70, running_mean_std.py:79-110, cfg/cfg.py:337-341 default True): no
 // normalised f32 copy of the frames exists anywhere.  mu / rstd: the normaliser's f32 tables [Cin*H*W] in the frame's NCHW
-// order (sf_obsnorm_update writes them).  Launches sf_conv_norm_supported() accepts: the Nature-CNN conv1 geometry the
-// strip-image kernels are built for, n >= 256, 4-byte aligned frames; everything else goes through sf_obsnorm_apply.
-// f32 frames (in_u8 = 2) take every geometry: the register-staged kernels (k_conv_fwd / k_conv_wgrad) form
-// clamp(((x - sub_mean) * inv_scale - mu[d]) * rstd[d], +-5) in their loaders, with 16-byte loads of pixels and table
-// entries where sf_conv_fwd would use them and the scalar loader otherwise.
+// order (sf_obsnorm_update writes them).  sf_conv_norm_supported() accepts every frame descriptor (in_u8 = 1 or 2) that
+// check_desc accepts.  Both frame formats take every geometry: the register-staged kernels (k_conv_fwd / k_conv_wgrad)
+// form clamp(((x - sub_mean) * inv_scale - mu[d]) * rstd[d], +-5) in their loaders (MODE_U8_NORM / MODE_F32F_NORM), with
+// vector loads of pixels and table entries where sf_conv_fwd would use them and the scalar loader otherwise.  The
+// Nature-CNN conv1 on u8 frames (32 output channels, aligned operands) keeps the strip-image kernels it always had.
 static bool conv_norm_ok(const sf_conv_desc *d, int64_t n) {
     static const int on = getenv("SF_CONV1_NORM") ? atoi(getenv("SF_CONV1_NORM")) : 1;
-    if (!on || !d || n <= 0) return false;
-    if (d->in_u8 == IN_F32_FRAME) return true;
+    return on && d && n > 0 && in_is_frame(d->in_u8);
+}
+// the strip kernels' compile-time geometry; ANY n (their n >= 256 dispatch threshold is a speed heuristic of the plain
+// entry points, the kernels themselves are correct for every n >= 1)
+static bool conv_norm_strip(const sf_conv_desc *d) {
     if (!in_is_u8(d->in_u8) || d->Cout != 32) return false;
     const ConvG g = make_geom(d);
-    // the strip kernels' compile-time geometry; ANY n (their n >= 256 dispatch threshold is a speed heuristic of the plain
-    // entry points, the kernels themselves are correct for every n >= 1 and there is no other kernel to fall back to)
     return pick_mode(g) == MODE_U8 && g.Cin == 4 && g.H == 84 && g.W == 84 && g.KH == 8 && g.KW == 8 && g.S == 4;
 }
 extern "C" int sf_conv_norm_supported(int64_t n, const sf_conv_desc *h_desc) {
@@ -1683,15 +1710,14 @@ extern "C" int sf_conv_fwd_norm(const void *in, int64_t in_sample_stride, const 
     int rc = check_desc(h_desc, "sf_conv_fwd_norm");
     if (rc) return rc;
     SF_REQUIRE(in && mu && rstd && w && out && n > 0, "sf_conv_fwd_norm: bad args");
-    if (h_desc->in_u8 == IN_F32_FRAME) {
-        SF_REQUIRE(conv_norm_ok(h_desc, n) && ((uintptr_t)in & 3) == 0 && ((uintptr_t)mu & 3) == 0 && ((uintptr_t)rstd & 3) == 0,
-                   "sf_conv_fwd_norm: unsupported launch (see sf_conv_norm_supported; f32 frames and tables 4-byte aligned)");
+    SF_REQUIRE(conv_norm_ok(h_desc, n) && ((uintptr_t)mu & 3) == 0 && ((uintptr_t)rstd & 3) == 0 &&
+                   (in_is_u8(h_desc->in_u8) || ((uintptr_t)in & 3) == 0),
+               "sf_conv_fwd_norm: unsupported launch (see sf_conv_norm_supported; f32 frames and tables 4-byte aligned)");
+    // every launch but the Nature-CNN conv1 on aligned u8 frames: the register-staged kernel with a normalising loader
+    if (!conv_norm_strip(h_desc) || ((uintptr_t)in & 3) != 0 || in_sample_stride % 4 != 0 || ((uintptr_t)mu & 15) != 0 ||
+        ((uintptr_t)rstd & 15) != 0)
         return conv_fwd_impl(in, in_sample_stride, index, offset, w, bias, out, nullptr, n, h_desc, nullptr, 0, stream, mu,
                              rstd);
-    }
-    SF_REQUIRE(conv_norm_ok(h_desc, n) && ((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0 &&
-                   ((uintptr_t)mu & 15) == 0 && ((uintptr_t)rstd & 15) == 0,
-               "sf_conv_fwd_norm: unsupported layer / launch (see sf_conv_norm_supported; frames 4-byte, tables 16-byte aligned)");
     ConvG g = make_geom(h_desc);
     g.nmu = mu; g.nrstd = rstd;
     SF_REQUIRE(n * g.OH * g.OW < (1LL << 31), "sf_conv_fwd_norm: M exceeds 2^31 rows; split the batch");
@@ -1708,16 +1734,14 @@ extern "C" int sf_conv_wgrad_norm(const void *in, int64_t in_sample_stride, cons
     int rc = check_desc(h_desc, "sf_conv_wgrad_norm");
     if (rc) return rc;
     SF_REQUIRE(in && mu && rstd && dout && dw && workspace && n > 0, "sf_conv_wgrad_norm: bad args");
-    if (h_desc->in_u8 == IN_F32_FRAME) {
-        SF_REQUIRE(conv_norm_ok(h_desc, n) && ((uintptr_t)in & 3) == 0 && ((uintptr_t)mu & 3) == 0 && ((uintptr_t)rstd & 3) == 0,
-                   "sf_conv_wgrad_norm: unsupported launch (see sf_conv_norm_supported; f32 frames and tables 4-byte aligned)");
+    SF_REQUIRE(conv_norm_ok(h_desc, n) && ((uintptr_t)mu & 3) == 0 && ((uintptr_t)rstd & 3) == 0 &&
+                   (in_is_u8(h_desc->in_u8) || ((uintptr_t)in & 3) == 0),
+               "sf_conv_wgrad_norm: unsupported launch (see sf_conv_norm_supported; f32 frames and tables 4-byte aligned)");
+    if (!conv_norm_strip(h_desc) || ((uintptr_t)in & 3) != 0 || in_sample_stride % 4 != 0 || ((uintptr_t)mu & 15) != 0 ||
+        ((uintptr_t)rstd & 15) != 0 || ((uintptr_t)dout & 15) != 0)
         return conv_wgrad_impl(in, in_sample_stride, index, offset, dout, nullptr, dw, db, n, h_desc, workspace, stream, mu,
                                rstd);
-    }
-    SF_REQUIRE(conv_norm_ok(h_desc, n) && ((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0 &&
-                   ((uintptr_t)mu & 15) == 0 && ((uintptr_t)rstd & 15) == 0 && ((uintptr_t)dout & 15) == 0 &&
-                   ((uintptr_t)workspace & 15) == 0,
-               "sf_conv_wgrad_norm: unsupported layer / launch (see sf_conv_norm_supported)");
+    SF_REQUIRE(((uintptr_t)workspace & 15) == 0, "sf_conv_wgrad_norm: workspace must be 16-byte aligned");
     ConvG g = make_geom(h_desc);
     g.nmu = mu; g.nrstd = rstd;
     const int K = g.K, N = g.Cout;
@@ -1880,9 +1904,9 @@ extern "C" int sf_conv_kernel_name(int op, int64_t n, const sf_conv_desc *h_desc
     SF_REQUIRE(out && cap >= 48 && n > 0 && op >= 0 && op <= 5, "sf_conv_kernel_name: bad args");
     ConvG g = make_geom(h_desc);
     const int64_t Mtot = n * g.OH * g.OW;
-    if (op >= 4) {  // 4: sf_conv_fwd_norm, 5: sf_conv_wgrad_norm (f32 frames: the register-staged kernels, no split)
+    if (op >= 4) {  // 4: sf_conv_fwd_norm, 5: sf_conv_wgrad_norm (but for one geometry the register-staged kernels, no split)
         SF_REQUIRE(conv_norm_ok(h_desc, n), "sf_conv_kernel_name: not a launch sf_conv_norm_supported accepts");
-        if (in_is_u8(g.in_u8)) {
+        if (conv_norm_strip(h_desc)) {
             snprintf(out, cap, op == 4 ? "k_conv_u8_img_norm<2, 4, 5, 16>" : "k_conv1_wgrad_img_norm<2, 4>");
             return SF_OK;
         }

@@ -23,6 +23,7 @@ struct ResG {
     int Cin, H, W, Cout, act_in, traj_T;
     int64_t stride, offset;
     float sub_mean, inv_scale;
+    const float *nmu, *nrstd;  // sf_res_conv_fwd_norm / _wgrad_norm: the observation normaliser's f32 tables [Cin*H*W], else NULL
 };
 
 __device__ __forceinline__ float act_fwd(int kind, float z) {
@@ -52,14 +53,17 @@ __device__ __forceinline__ int64_t res_sample_base(const ResG &g, const int32_t 
 }
 
 // one input value in the NORMALISED, ACTIVATED domain; the zero padding belongs to that domain (torch pads the
-// normalised f32 tensor), so an out-of-image tap is exactly 0
+// normalised f32 tensor), so an out-of-image tap is exactly 0 — also under the observation normaliser, whose
+// clamp((v - mu) * rstd, +-5) (running_mean_std.py:108) is applied to in-image pixels only
 template <bool U8>
 __device__ __forceinline__ float res_load(const void *__restrict__ x, const ResG &g, int64_t base, int h, int w, int c) {
     if (h < 0 || h >= g.H || w < 0 || w >= g.W) return 0.0f;
     float v;
     if (U8) {
-        const float raw = (float)((const uint8_t *)x)[base + ((int64_t)c * g.H + h) * g.W + w];
+        const int e = (c * g.H + h) * g.W + w;
+        const float raw = (float)((const uint8_t *)x)[base + e];
         v = (raw - g.sub_mean) * g.inv_scale;
+        if (g.nmu) v = fminf(fmaxf((v - g.nmu[e]) * g.nrstd[e], -5.0f), 5.0f);
     } else {
         v = ((const float *)x)[base + ((int64_t)h * g.W + w) * g.Cin + c];
     }
@@ -321,6 +325,7 @@ ResG res_geom(const sf_res_desc *d, int64_t stride, int64_t offset) {
     ResG g;
     g.Cin = d->Cin; g.H = d->H; g.W = d->W; g.Cout = d->Cout; g.act_in = d->act_in; g.traj_T = d->traj_T;
     g.stride = stride; g.offset = offset; g.sub_mean = d->sub_mean; g.inv_scale = d->inv_scale;
+    g.nmu = nullptr; g.nrstd = nullptr;
     return g;
 }
 
@@ -336,9 +341,11 @@ bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
-extern "C" int sf_res_conv_fwd(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
-                               const float *w, const float *bias, const float *residual, float *out, float *out_act,
-                               int act_out, int64_t n, const sf_res_desc *h_desc, void *stream) {
+// mu / rstd: the observation normaliser's tables (sf_res_conv_fwd_norm), else NULL
+static int res_conv_fwd_impl(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
+                             const float *w, const float *bias, const float *residual, float *out, float *out_act,
+                             int act_out, int64_t n, const sf_res_desc *h_desc, void *stream, const float *mu,
+                             const float *rstd) {
     int rc = res_check(h_desc, false);
     if (rc) return rc;
     SF_REQUIRE(in && w && bias && out, "sf_res_conv_fwd: NULL operand");
@@ -353,7 +360,8 @@ extern "C" int sf_res_conv_fwd(const void *in, int64_t in_sample_stride, const i
     SF_REQUIRE(aligned16(w) && aligned16(out) && (!out_act || aligned16(out_act)) && (!residual || aligned16(residual)),
                "sf_res_conv_fwd: w, out, out_act and residual must be 16-byte aligned");
     if (n == 0) return SF_OK;
-    const ResG g = res_geom(h_desc, in_sample_stride, offset);
+    ResG g = res_geom(h_desc, in_sample_stride, offset);
+    g.nmu = mu; g.nrstd = rstd;
     const dim3 grid((unsigned)((n * d.H * d.W + RES_BLOCK - 1) / RES_BLOCK));
     hipStream_t s = STREAM(stream);
 #define RES_FWD(CO, U8)                                                                                             \
@@ -366,6 +374,24 @@ extern "C" int sf_res_conv_fwd(const void *in, int64_t in_sample_stride, const i
     }
 #undef RES_FWD
     return sf_launch_status("sf_res_conv_fwd");
+}
+
+extern "C" int sf_res_conv_fwd(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
+                               const float *w, const float *bias, const float *residual, float *out, float *out_act,
+                               int act_out, int64_t n, const sf_res_desc *h_desc, void *stream) {
+    return res_conv_fwd_impl(in, in_sample_stride, index, offset, w, bias, residual, out, out_act, act_out, n, h_desc,
+                             stream, nullptr, nullptr);
+}
+
+// the raw-frame first layer with cfg.normalize_input: the u8 frames are normalised in the loader (res_load), the zero
+// padding stays zero; mu / rstd: the normaliser's f32 tables [Cin*H*W] in the frame's NCHW order
+extern "C" int sf_res_conv_fwd_norm(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
+                                    const float *mu, const float *rstd, const float *w, const float *bias, float *out,
+                                    int64_t n, const sf_res_desc *h_desc, void *stream) {
+    SF_REQUIRE(h_desc && h_desc->in_u8 && mu && rstd, "sf_res_conv_fwd_norm: the raw u8 frame layer and both tables are needed");
+    SF_REQUIRE(((uintptr_t)mu & 3) == 0 && ((uintptr_t)rstd & 3) == 0, "sf_res_conv_fwd_norm: tables must be 4-byte aligned");
+    return res_conv_fwd_impl(in, in_sample_stride, index, offset, w, bias, nullptr, out, nullptr, 0, n, h_desc, stream, mu,
+                             rstd);
 }
 
 extern "C" int sf_res_pool_fwd(const float *in, float *out, uint8_t *argmax, int64_t n, int H, int W, int C,
@@ -421,9 +447,11 @@ extern "C" int64_t sf_res_conv_wgrad_workspace(int64_t n, const sf_res_desc *h_d
     return res_wgrad_parts(n * h_desc->H * h_desc->W) * E * (int64_t)sizeof(float);
 }
 
-extern "C" int sf_res_conv_wgrad(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
-                                 const float *dout, float *dw, float *db, int64_t n, const sf_res_desc *h_desc,
-                                 void *workspace, int64_t workspace_bytes, void *stream) {
+// mu / rstd: the observation normaliser's tables (sf_res_conv_wgrad_norm), else NULL
+static int res_conv_wgrad_impl(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
+                               const float *dout, float *dw, float *db, int64_t n, const sf_res_desc *h_desc,
+                               void *workspace, int64_t workspace_bytes, void *stream, const float *mu,
+                               const float *rstd) {
     int rc = res_check(h_desc, false);
     if (rc) return rc;
     SF_REQUIRE(in && dout && dw && db, "sf_res_conv_wgrad: NULL operand");
@@ -443,7 +471,8 @@ extern "C" int sf_res_conv_wgrad(const void *in, int64_t in_sample_stride, const
     const int64_t parts = res_wgrad_parts(NP);
     const int64_t rows = NP > 0 ? (NP + parts - 1) / parts : 0;
     float *part = static_cast<float *>(workspace);
-    const ResG g = res_geom(h_desc, in_sample_stride, offset);
+    ResG g = res_geom(h_desc, in_sample_stride, offset);
+    g.nmu = mu; g.nrstd = rstd;
 #define RES_WG(CO, U8)                                                                                          \
     hipLaunchKernelGGL((k_res_conv_wgrad_part<CO, U8>), dim3((unsigned)parts), dim3(RES_BLOCK), 0, s, in, index, dout, \
                        part, n, rows, g)
@@ -458,4 +487,21 @@ extern "C" int sf_res_conv_wgrad(const void *in, int64_t in_sample_stride, const
     hipLaunchKernelGGL(k_res_conv_wgrad_sum, dim3((unsigned)((E + RES_BLOCK - 1) / RES_BLOCK)), dim3(RES_BLOCK), 0, s,
                        part, (int)parts, KC, d.Cout, dw, db);
     return sf_launch_status("sf_res_conv_wgrad");
+}
+
+extern "C" int sf_res_conv_wgrad(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
+                                 const float *dout, float *dw, float *db, int64_t n, const sf_res_desc *h_desc,
+                                 void *workspace, int64_t workspace_bytes, void *stream) {
+    return res_conv_wgrad_impl(in, in_sample_stride, index, offset, dout, dw, db, n, h_desc, workspace, workspace_bytes,
+                               stream, nullptr, nullptr);
+}
+
+extern "C" int sf_res_conv_wgrad_norm(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
+                                      const float *mu, const float *rstd, const float *dout, float *dw, float *db,
+                                      int64_t n, const sf_res_desc *h_desc, void *workspace, int64_t workspace_bytes,
+                                      void *stream) {
+    SF_REQUIRE(h_desc && h_desc->in_u8 && mu && rstd, "sf_res_conv_wgrad_norm: the raw u8 frame layer and both tables are needed");
+    SF_REQUIRE(((uintptr_t)mu & 3) == 0 && ((uintptr_t)rstd & 3) == 0, "sf_res_conv_wgrad_norm: tables must be 4-byte aligned");
+    return res_conv_wgrad_impl(in, in_sample_stride, index, offset, dout, dw, db, n, h_desc, workspace, workspace_bytes,
+                               stream, mu, rstd);
 }

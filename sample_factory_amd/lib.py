@@ -60,7 +60,7 @@ SYMBOLS = [
     "sf_dp_allreduce_f64", "sf_dp_broadcast", "sf_dp_oneshot_create", "sf_dp_oneshot_connect", "sf_dp_oneshot_allreduce_f32",
     "sf_dp_oneshot_allreduce_f64", "sf_dp_oneshot_status", "sf_dp_oneshot_destroy",
     "sf_res_conv_fwd", "sf_res_pool_fwd", "sf_res_pool_bwd", "sf_res_conv_dgrad", "sf_res_conv_wgrad_workspace",
-    "sf_res_conv_wgrad",
+    "sf_res_conv_wgrad", "sf_res_conv_fwd_norm", "sf_res_conv_wgrad_norm",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -1043,3 +1043,20 @@ def res_conv_wgrad(inp, in_sample_stride, index, offset, dout, dw, db, n, desc: 
                                     ptr(dout, "f32", "dout"), ptr(dw, "f32", "dw"), ptr(db, "f32", "db"), i64(n),
                                     C.byref(desc), ptr(workspace, "u8", "workspace"), i64(workspace.numel()), stream()),
            "sf_res_conv_wgrad")
+
+
+def res_conv_fwd_norm(inp, in_sample_stride, index, offset, mu, rstd, w, bias, out, n, desc: sf_res_desc) -> None:
+    """the raw-frame first layer with the observation normaliser's tables applied in the loader (sf_res_conv_fwd_norm)"""
+    _check(load().sf_res_conv_fwd_norm(_res_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"), i64(offset),
+                                       ptr(mu, "f32", "mu"), ptr(rstd, "f32", "rstd"), ptr(w, "f32", "w"),
+                                       ptr(bias, "f32", "bias"), ptr(out, "f32", "out"), i64(n), C.byref(desc), stream()),
+           "sf_res_conv_fwd_norm")
+
+
+def res_conv_wgrad_norm(inp, in_sample_stride, index, offset, mu, rstd, dout, dw, db, n, desc: sf_res_desc,
+                        workspace) -> None:
+    _check(load().sf_res_conv_wgrad_norm(_res_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"),
+                                         i64(offset), ptr(mu, "f32", "mu"), ptr(rstd, "f32", "rstd"),
+                                         ptr(dout, "f32", "dout"), ptr(dw, "f32", "dw"), ptr(db, "f32", "db"), i64(n),
+                                         C.byref(desc), ptr(workspace, "u8", "workspace"), i64(workspace.numel()),
+                                         stream()), "sf_res_conv_wgrad_norm")

@@ -282,9 +282,9 @@ class ActorCritic(NativeTower):
             cin, h, w = C, H, W
             for i, (cout, k, s) in enumerate(CONV_ARCHS[cfg.encoder_conv_architecture]):
                 oh, ow = (h - k) // s + 1, (w - k) // s + 1
-                # normalize_input=True: the Nature-CNN conv1 geometry normalises INSIDE conv1's loader (sf_conv_fwd_norm /
-                # sf_conv_wgrad_norm: frames stay u8, first layer keeps its raw-frame form); any other first layer reads a
-                # materialised normalised f32 NHWC batch (utils/normalize.py)
+                # normalize_input=True: the first layer normalises INSIDE its loader (sf_conv_fwd_norm / sf_conv_wgrad_norm:
+                # the frames stay u8 / f32 NCHW in the slab, the layer keeps its raw-frame form) for every geometry; only
+                # with SF_CONV1_NORM=0 it reads a materialised normalised f32 NHWC batch (utils/normalize.py)
                 if i == 0 and norm_input and _CONV1_NORM:
                     probe = lib.sf_conv_desc(Cin=cin, H=h, W=w, Cout=cout, KH=k, KW=k, stride=s, OH=oh, OW=ow, in_u8=fmt,
                                              relu=act, traj_T=0, sub_mean=sub_mean, inv_scale=inv_scale)
@@ -554,7 +554,7 @@ class ActorCritic(NativeTower):
         return out, self.obs_elems, None, 0, 0
 
     def _frames_vector_geometry(self) -> bool:
-        """the first layer's loader can fetch f32 frames as 16-byte quads (KW, stride and W multiples of 4)"""
+        """the first layer's loader can fetch four pixels of a frame at once (KW, stride and W multiples of 4)"""
         d = self.layers[0].desc
         return d.KW % 4 == 0 and d.stride % 4 == 0 and d.W % 4 == 0
 
@@ -671,15 +671,16 @@ class ActorCritic(NativeTower):
                 # image frames: (x - mu) * rstd, clamped, happens in conv1's loader (sf_conv_fwd_norm) — the frames stay
                 # u8 in the slab and no normalised f32 copy is written or read
                 norm_tabs = tabs if tabs is not None else (on.mu_tab, on.rstd_tab)
-                if self.obs_u8 and (x.data_ptr() % 4 or stride % 4):
+                if self.obs_u8 and (x.data_ptr() % 4 or stride % 4) and self._frames_vector_geometry():
                     # the loader fetches the bytes as 32-bit words: a frame view at an odd address (a custom slab offset)
-                    # degrades to one aligned u8 copy of the batch's frames instead of failing the launch
+                    # would drop it to its scalar form; one aligned u8 copy of the batch's frames keeps the word loads
+                    # (geometries that are scalar anyway, e.g. an odd width, are read where they are)
                     x, stride, idx, off, tT = self._aligned_frames(tag, x, stride, idx, off, tT, n)
                 elif not self.obs_u8 and (x.data_ptr() % 16 or stride % 4) and self._frames_vector_geometry():
                     # f32 frames: a view off the 16-byte grid would drop the loader to its scalar form; one aligned copy
                     # of the batch's frames keeps the 16-byte loads
                     x, stride, idx, off, tT = self._aligned_frames(tag, x, stride, idx, off, tT, n)
-            else:  # any other shape: materialise the normalised f32 batch (NHWC), as the reference does
+            else:  # SF_CONV1_NORM=0 (and vector observations): materialise the normalised f32 batch, as the reference does
                 xn = self._buf((tag, "obsn"), (n, self.obs_elems))
                 on.apply(obs, sample_stride, n, xn, index=index, offset=offset, traj_T=traj_T, tabs=tabs)
                 x, stride, idx, off, tT = xn, self.obs_elems, None, 0, 0

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from sample_factory_amd import lib
+from sample_factory_amd.model import actor_critic as _ac
 from sample_factory_amd.model.actor_critic import ACT_KIND, NativeTower, _Layer, _linear_desc, _pad
 
 RESNET_STAGES = ((16, 2), (32, 2), (32, 2))  # encoder.py:180-182 (configuration from the IMPALA paper)
@@ -81,9 +82,12 @@ class ResnetImpalaTower(NativeTower):
         pfx = f"encoder.encoders.{obs_key}."
         self.stages = []  # (stage conv, [(conv1, conv2) per block], (H, W) before the pool, (OH, OW) after)
         self.convs: List[_Conv3] = []
+        # normalize_input: the first conv stays the raw-frame layer and normalises in its loader (sf_res_conv_fwd_norm /
+        # sf_res_conv_wgrad_norm); only with SF_CONV1_NORM=0 it reads on.apply's f32 NHWC batch
+        self._fused_norm = norm_input and _ac._CONV1_NORM
         cin, h, w, i = C, H, W, 0
         for cout, blocks in RESNET_STAGES:
-            first = i == 0 and not norm_input  # normalize_input: the first conv reads on.apply's f32 NHWC batch
+            first = i == 0 and (not norm_input or self._fused_norm)
             conv = _Conv3(f"{pfx}conv_head.{i}", cin, cout, h, w, 0, u8=first, sub_mean=sub_mean if first else 0.0,
                           inv_scale=inv_scale if first else 1.0)
             oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
@@ -218,12 +222,16 @@ class ResnetImpalaTower(NativeTower):
         self._tls.role = "rollout" + tag[3:] if tag.startswith("inf") else "learner"
         act = self.act_kind
         x, stride, idx, off, tT = obs, sample_stride, index, offset, traj_T
-        if self.obs_normalizer is not None:  # normalize_input=True: the normalised f32 NHWC batch (utils/normalize.py)
+        norm_tabs = None
+        if self.obs_normalizer is not None:  # normalize_input=True
             on = self.obs_normalizer
             tabs = self._snap_tabs[self.snap_read] if (tag.startswith("inf") and self._snap is not None) else None
-            xn = self._buf((tag, "obsn"), (n, self.obs_elems))
-            on.apply(obs, sample_stride, n, xn, index=index, offset=offset, traj_T=traj_T, tabs=tabs)
-            x, stride, idx, off, tT = xn, self.obs_elems, None, 0, 0
+            if self._fused_norm:  # in the first conv's loader: the frames stay u8 in the slab, no f32 copy is written
+                norm_tabs = tabs if tabs is not None else (on.mu_tab, on.rstd_tab)
+            else:  # SF_CONV1_NORM=0: the normalised f32 NHWC batch (utils/normalize.py)
+                xn = self._buf((tag, "obsn"), (n, self.obs_elems))
+                on.apply(obs, sample_stride, n, xn, index=index, offset=offset, traj_T=traj_T, tabs=tabs)
+                x, stride, idx, off, tT = xn, self.obs_elems, None, 0, 0
         first_in = (x, stride, idx, off, tT)
         saved = []  # per stage: (stage input, conv output, pooled, pool argmax, [(block input, t, y)])
         li = 0
@@ -236,7 +244,10 @@ class ResnetImpalaTower(NativeTower):
                 d.traj_T = int(tT)
             wt, bs = self._wb(li, tag)
             full = self._buf((tag, "s", s, "conv"), (n, h, w, conv.N))
-            lib.res_conv_fwd(x, stride, idx, off, wt, bs, full, n, d)
+            if s == 0 and norm_tabs is not None:
+                lib.res_conv_fwd_norm(x, stride, idx, off, norm_tabs[0], norm_tabs[1], wt, bs, full, n, d)
+            else:
+                lib.res_conv_fwd(x, stride, idx, off, wt, bs, full, n, d)
             li += 1
             pooled = self._buf((tag, "s", s, "pool"), (n, oh, ow, conv.N))
             arg = self._buf((tag, "s", s, "arg"), (n, oh, ow, conv.N), dtype=torch.uint8)
@@ -270,7 +281,7 @@ class ResnetImpalaTower(NativeTower):
             lib.conv_fwd_raw(xin, L.K, None, 0, wt, bs, out, n, L.desc, self._workspace(wsb) if wsb else None)
             acts.append(out)
             xin = out
-        self._ctx[tag] = dict(first_in=first_in, saved=saved, acts=acts)
+        self._ctx[tag] = dict(first_in=first_in, saved=saved, acts=acts, norm_tabs=norm_tabs)
         return acts
 
     def backward(self, acts, g_out: torch.Tensor, obs, n: int, *, sample_stride: int = 0, index=None, offset: int = 0,
@@ -312,7 +323,11 @@ class ResnetImpalaTower(NativeTower):
                 d = lib.sf_res_desc.from_buffer_copy(conv.desc)
                 d.traj_T = int(tT)
             ws = self._workspace(lib.res_conv_wgrad_workspace(n, d))
-            lib.res_conv_wgrad(x, stride, idx, off, g_full, conv.gw, conv.gb, n, d, ws)
+            if s == 0 and ctx.get("norm_tabs") is not None:  # the forward normalised in the loader: so does the gradient
+                mu_, rstd_ = ctx["norm_tabs"]
+                lib.res_conv_wgrad_norm(x, stride, idx, off, mu_, rstd_, g_full, conv.gw, conv.gb, n, d, ws)
+            else:
+                lib.res_conv_wgrad(x, stride, idx, off, g_full, conv.gw, conv.gb, n, d, ws)
             if s > 0:
                 g_in = self._buf(("g", "s", s, "in"), (n, h, w, conv.Cin))
                 lib.res_conv_dgrad(g_full, conv.w, None, g_in, n, conv.desc)
