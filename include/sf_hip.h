@@ -109,7 +109,8 @@ int sf_rows_add_scale(const float *a, const float *b, const float *keep, int64_t
  * n/recurrence trajectories; sample i of the minibatch is dataset row (index ? index[i] : offset+i).
  * params [n,A] (row stride ld_params) / values [n] (stride ld_values): CURRENT policy outputs (minibatch order; the
  * strides let both be columns of the fused heads GEMM output [n, 1+A]); actions/old_logp/rewards/dones: dataset
- * arrays; dones u8.  Outputs vs, adv [n] in minibatch order.  action_kind as in sf_ppo_loss. */
+ * arrays; dones u8.  Outputs vs, adv [n] in minibatch order.  action_kind as in sf_ppo_loss.  Any A > 0: up to 128
+ * parameters the ratio pass keeps a row in one lane's registers, above that one wave walks a row (k_vtrace_ratio_wide). */
 int sf_vtrace(const float *params, int ld_params, const float *values, int ld_values, const float *actions,
               const float *old_logp, const float *rewards, const uint8_t *dones, const int32_t *index, int64_t offset,
               int64_t n, int A, int action_kind, int recurrence, float gamma, float rho_hat, float c_hat, float *vs,
@@ -151,6 +152,9 @@ typedef struct {
     int32_t old_values_T;
 } sf_loss_cfg;
 
+/* Any A > 0.  A <= 128: one lane per sample, the distribution in registers.  A > 128 (one wide Discrete / Box, or a
+ * head list whose parameters add up to more): k_ppo_loss_wide, one wave64 per sample row, lanes striding the columns,
+ * same formulas, same sums[0..7]; rows only need 4-byte alignment (they start at column 1 of the heads matrix). */
 int sf_ppo_loss(const float *params, int ld_params, const float *values, int ld_values, const float *actions,
                 const float *old_logp, const float *old_params, const float *old_values, const float *adv,
                 const float *targets, const uint8_t *valids, const int32_t *index, int64_t offset, int64_t n, int A,
@@ -234,7 +238,10 @@ int sf_lamb_step(float *p, const float *g, float *m, float *v, float *scratch, c
  * (A floats) and the int32 action for the env.  `deterministic` != 0 takes argmax (enjoy.py:177-182).
  * action_kind 1 = Box(A/2): params are [means | log_std] (action_distributions.py:290-310); the action
  * mu + clamp(exp(log_std),1e-4,1e4)*eps (eps: Box-Muller on Philox stream 3) is written as A/2 floats into
- * traj_actions[b*T+t] (the env reads it from there; env_actions may be NULL); deterministic takes the mean. */
+ * traj_actions[b*T+t] (the env reads it from there; env_actions may be NULL); deterministic takes the mean.
+ * Any A > 0.  The three samplers hand rows of more than 128 parameters to k_sample_write_wide (one wave64 per env row;
+ * the CDF is walked 64 columns at a time: wave scan + carry, a ballot finds the first crossing) — same Philox counters,
+ * uniforms and draw rule: first index with u < cdf, else the last action of non-zero probability; arg-max = first maximum. */
 int sf_sample_write_step(const float *logits, int ld_logits, const float *values, int ld_values, int B, int A, int T,
                          int t, uint32_t seed, uint32_t step, uint32_t row0, float policy_version, int deterministic,
                          int action_kind, float *traj_actions,

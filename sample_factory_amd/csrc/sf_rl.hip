@@ -350,6 +350,101 @@ __device__ __forceinline__ float tuple_logp(const float *__restrict__ z, const f
     return lp;
 }
 
+// ------------------------------------------------------------------------------------------- wide family (A > 128)
+// One wave64 per sample row, four rows per 256-thread block; the lanes stride the columns of a head, so one load
+// instruction covers 256 contiguous bytes and nothing per-column is kept in a lane.  A row is read from HBM once (the
+// statistics pass); the terms and gradient passes read it again from cache.  Rows start at column 1 of the heads
+// matrix, so only 4-byte alignment is assumed: every access is a dword.  Reductions are xor butterflies, which leave
+// the same bits in every lane (a + b == b + a), so the branches taken on them are wave-uniform.
+constexpr int WIDE_MIN_A = 129;   // A <= 128: the lane-per-sample kernels, untouched
+constexpr int WIDE_ROWS = 4;      // waves (= rows) per block
+
+__device__ __forceinline__ float wide_allsum(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ float wide_allmax(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+__device__ __forceinline__ int wide_allmin(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
+    return v;
+}
+// one step of a lane's running (max, sum of exp(x - max)): one expf per element
+__device__ __forceinline__ void wide_push(float &m, float &s, float x) {
+    const float e = expf(-fabsf(x - m));  // m = -inf before the first element: e = 0, s = 0 * 0 + 1
+    s = x > m ? s * e + 1.f : s + e;
+    m = fmaxf(m, x);
+}
+// the lanes' running pairs -> max and log-sum-exp of the head, in every lane (a lane that saw no column has m = -inf,
+// s = 0 and adds 0)
+__device__ __forceinline__ void wide_finish(float m, float s, float &mx, float &lse) {
+    mx = wide_allmax(m);
+    lse = logf(wide_allsum(s * expf(m - mx)));
+}
+// max and log-sum-exp over nh columns of z (masked-out columns count as z - 1e9, the rule above k_sample_write_masked)
+__device__ __forceinline__ void wide_lse(const float *__restrict__ z, int nh, int lane, const uint8_t *__restrict__ mk,
+                                         float &mx, float &lse) {
+    float m = -INFINITY, s = 0.f;
+    // (unroll 4: four independent loads in flight per lane; these loops wait on memory, not on the ALU)
+    if (mk) {
+#pragma unroll 4
+        for (int k = lane; k < nh; k += 64) wide_push(m, s, z[k] + (mk[k] ? 0.f : -1e9f));
+    } else {
+#pragma unroll 4
+        for (int k = lane; k < nh; k += 64) wide_push(m, s, z[k]);
+    }
+    wide_finish(m, s, mx, lse);
+}
+// a single Discrete(A) / Box(A / 2) as a one-member head list
+static HeadsDev wide_single_head(int A, int action_kind) {
+    HeadsDev hd = {};
+    hd.num_heads = 1;
+    hd.head_n[0] = action_kind == 0 ? A : -(A / 2);
+    return hd;
+}
+
+// k_vtrace_ratio for A > 128: log-prob of the taken action, one wave per row
+__global__ __launch_bounds__(256) void k_vtrace_ratio_wide(const float *__restrict__ params, int ldp,
+                                                           const float *__restrict__ actions,
+                                                           const float *__restrict__ old_logp,
+                                                           const int32_t *__restrict__ index, int64_t offset, int64_t n,
+                                                           float *__restrict__ ratio_out, HeadsDev hd) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t k = (int64_t)blockIdx.x * WIDE_ROWS + wave;
+    if (k >= n) return;
+    const int nact = heads_action_cols(hd.head_n, hd.num_heads);
+    const int64_t d = index ? (int64_t)index[k] : offset + k;
+    const float *z = params + k * ldp, *act = actions + d * nact;
+    float lp = 0.f;
+    int off = 0, aoff = 0;
+    for (int h = 0; h < hd.num_heads; ++h) {
+        const int nh = hd.head_n[h];
+        if (nh < 0) {
+            const int D = -nh;
+            float r = 0.f;
+            for (int j = lane; j < D; j += 64) {
+                const float mu = z[off + j], sd = clampf(expf(z[off + D + j]), 1e-4f, 1e4f);
+                const float a = act[aoff + j];
+                r += -((a - mu) * (a - mu)) / (2.f * (sd * sd)) - logf(sd) - 0.91893853320467274178f;
+            }
+            lp += wide_allsum(r);
+            off += 2 * D; aoff += D;
+            continue;
+        }
+        float mx, lse;
+        wide_lse(z + off, nh, lane, nullptr, mx, lse);
+        const int a = min(max((int)act[aoff], 0), nh - 1);  // (a recorded action is in range; never read past the row)
+        lp += (z[off + a] - mx) - lse;
+        off += nh; aoff += 1;
+    }
+    if (lane == 0) ratio_out[k] = clampf(expf(lp - old_logp[d]), 0.05f, 20.0f);
+}
+
 // phase 1 (parallel over samples): clamped importance ratio pi/pi_old of every step -> ratio_out[k]
 template <int MAXA>
 __global__ __launch_bounds__(256) void k_vtrace_ratio(const float *__restrict__ params, int ldp,
@@ -420,11 +515,21 @@ extern "C" int sf_vtrace(const float *params, int ld_params, const float *values
     SF_REQUIRE(params && values && actions && old_logp && rewards && dones && vs && adv, "sf_vtrace: null pointer");
     SF_REQUIRE(recurrence > 0 && n % recurrence == 0, "sf_vtrace: n=%lld not a multiple of recurrence=%d",
                (long long)n, recurrence);
-    SF_REQUIRE(A > 0 && A <= 128 && (action_kind == 0 || (action_kind == 1 && A % 2 == 0)),
+    SF_REQUIRE(A > 0 && (action_kind == 0 || (action_kind == 1 && A % 2 == 0)),
                "sf_vtrace: unsupported action params A=%d kind=%d", A, action_kind);
     const int64_t ntraj = n / recurrence;
     if (ntraj == 0) return SF_OK;
     const dim3 grid((unsigned)((ntraj + 63) / 64)), block(64), rgrid((unsigned)((n + 255) / 256));
+    if (A >= WIDE_MIN_A) {  // wave-per-row ratio; the recursion does not depend on A
+        SF_REQUIRE((n + WIDE_ROWS - 1) / WIDE_ROWS <= 0x7fffffffLL, "sf_vtrace: n=%lld too large", (long long)n);
+        const HeadsDev whd = hd.num_heads > 1 ? hd : wide_single_head(A, action_kind);
+        k_vtrace_ratio_wide<<<dim3((unsigned)((n + WIDE_ROWS - 1) / WIDE_ROWS)), dim3(256), 0, STREAM(stream)>>>(
+            params, ld_params, actions, old_logp, index, offset, n, vs, whd);
+        k_vtrace<128><<<grid, block, 0, STREAM(stream)>>>(params, ld_params, values, ld_values, actions, old_logp, rewards,
+                                                          dones, index, offset, ntraj, A, action_kind, recurrence, gamma,
+                                                          rho_hat, c_hat, vs, adv, hd);
+        return sf_launch_status("sf_vtrace");
+    }
 #define VT_LAUNCH(M)                                                                                             \
     k_vtrace_ratio<M><<<rgrid, dim3(256), 0, STREAM(stream)>>>(params, ld_params, actions, old_logp, index, offset, n, A,   \
                                                                action_kind, vs, hd);                              \
@@ -846,6 +951,219 @@ __global__ __launch_bounds__(256) void k_symkl_sum(const float *__restrict__ par
     if (threadIdx.x == 0) atomicAdd(out, acc[0]);
 }
 
+// k_ppo_loss / k_ppo_loss_md for A > 128 (any head list of up to 8 members): the same formulas, one wave per row.
+// Pass 1 per head: max / log-sum-exp of the current and the old logits in one read; pass 2: the head's log-prob,
+// entropy, KL and symmetric-KL terms (kept per head in LDS: the gradient needs them and the row's total log-prob);
+// pass 3: the gradient row, written 256 contiguous bytes per store.  The block's waves walk the rows with a grid
+// stride and add their sums in double, so a launch issues a few thousand atomics whatever n is.
+// sym_pass != 0: only the symmetric-KL sum of the valid rows (pre-pass for its mean gate) into sums[7].
+__global__ __launch_bounds__(256) void k_ppo_loss_wide(const float *__restrict__ params, int ldp,
+                                                       const float *__restrict__ values, int ldv,
+                                                       const float *__restrict__ actions,
+                                                       const float *__restrict__ old_logp,
+                                                       const float *__restrict__ old_params,
+                                                       const float *__restrict__ old_values,
+                                                       const float *__restrict__ adv, const float *__restrict__ targets,
+                                                       const uint8_t *__restrict__ valids,
+                                                       const int32_t *__restrict__ index, int64_t offset, int64_t n, int A,
+                                                       LossDev h, const double *__restrict__ moments,
+                                                       double *__restrict__ sums, float *__restrict__ g_params,
+                                                       float *__restrict__ g_values, float *__restrict__ ratio_out,
+                                                       int sym_pass) {
+    __shared__ double lds[4 * 4];
+    __shared__ float lds_max[4];
+    __shared__ float hstat[WIDE_ROWS][8][8];  // per wave and head: mx, lse, mxo, lseo, entropy, KL, KL(p || uniform)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double mn = moments[2];
+    const double mean64 = moments[0] / mn;
+    const double var64 = (moments[1] - moments[0] * mean64) / (mn - 1.0);
+    const float adv_mean = (float)mean64;
+    const float adv_std = (float)sqrt(var64 > 0.0 ? var64 : (mn > 1.0 ? 0.0 : NAN));
+    const float denom = fmaxf(adv_std, 1e-7f);
+    const float inv_n = 1.0f / (float)mn;
+    const float symkl_gate = (h.expl_kind == 2 && !sym_pass) ? (float)sums[6] : 1.0f;
+    const int H = h.num_heads;
+    const int NA = heads_action_cols(h.head_n, H);
+    float (*st)[8] = hstat[wave];
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    float kl_max = -1.0f;
+    for (int64_t i = (int64_t)blockIdx.x * WIDE_ROWS + wave; i < n; i += (int64_t)gridDim.x * WIDE_ROWS) {
+        const int64_t d = index ? (int64_t)index[i] : offset + i;
+        const bool valid = valids[d] != 0;
+        const float *z = params + i * ldp, *zo = old_params + d * A;
+        if (sym_pass) {
+            if (!valid) continue;
+            float symkl = 0.f;
+            int off = 0;
+            for (int hd = 0; hd < H; ++hd) {
+                const int nh = h.head_n[hd];  // categorical heads only (the launcher checks)
+                float m1, l1;
+                wide_lse(z + off, nh, lane, nullptr, m1, l1);
+                const float u = 1.0f / (float)nh, lu = logf(u);
+                float a1 = 0.f, a2 = 0.f;
+#pragma unroll 4
+                for (int k = lane; k < nh; k += 64) {
+                    const float lp = (z[off + k] - m1) - l1;
+                    a1 += expf(lp) * (lp - lu);
+                    a2 += u * (lu - lp);
+                }
+                symkl += 0.5f * (wide_allsum(a1) + wide_allsum(a2));
+                off += nh;
+            }
+            if (lane == 0) acc[0] += symkl;
+            continue;
+        }
+        float *gz = g_params + i * ldp;
+        float logp_a = 0.f, ent = 0.f, kl = 0.f, symkl = 0.f;
+        int off = 0, aoff = 0;
+        for (int hd = 0; hd < H; ++hd) {
+            const int nh = h.head_n[hd];
+            if (nh < 0) {  // Box(D) member: [means | log_std], the formulas of k_ppo_loss's continuous branch
+                const int Dh = -nh;
+                float lpp = 0.f, e = 0.f, kk = 0.f;
+                for (int k = lane; k < Dh; k += 64) {
+                    const float mu = z[off + k], sd = clampf(expf(z[off + Dh + k]), 1e-4f, 1e4f);
+                    const float a = actions[d * NA + aoff + k];
+                    lpp += -((a - mu) * (a - mu)) / (2.f * (sd * sd)) - logf(sd) - 0.91893853320467274178f;
+                    e += 0.5f + 0.91893853320467274178f + logf(sd);
+                    const float muo = zo[off + k], sdo = clampf(expf(zo[off + Dh + k]), 1e-4f, 1e4f);
+                    const float vr = (sd / sdo) * (sd / sdo);
+                    const float t1 = ((mu - muo) / sdo) * ((mu - muo) / sdo);
+                    kk += 0.5f * (vr + t1 - 1.f - logf(vr));
+                }
+                logp_a += wide_allsum(lpp);
+                ent += wide_allsum(e);
+                kl += wide_allsum(kk);
+                off += 2 * Dh; aoff += Dh;
+                continue;
+            }
+            float m1 = -INFINITY, s1 = 0.f, m2 = -INFINITY, s2 = 0.f;
+#pragma unroll 4
+            for (int k = lane; k < nh; k += 64) { wide_push(m1, s1, z[off + k]); wide_push(m2, s2, zo[off + k]); }
+            float mx, lse, mxo, lseo;
+            wide_finish(m1, s1, mx, lse);
+            wide_finish(m2, s2, mxo, lseo);
+            const int act = (int)actions[d * NA + aoff];
+            const float u = 1.0f / (float)nh, lu = logf(u);
+            float lpa = 0.f, e = 0.f, kk = 0.f, a1 = 0.f, a2 = 0.f;
+#pragma unroll 4
+            for (int k = lane; k < nh; k += 64) {
+                const float lp = (z[off + k] - mx) - lse, p = expf(lp), q = (zo[off + k] - mxo) - lseo;
+                if (k == act) lpa = lp;
+                e -= p * lp;
+                kk += p * (lp - q);
+                a1 += p * (lp - lu);
+                a2 += u * (lu - lp);
+            }
+            lpa = wide_allsum(lpa); e = wide_allsum(e); kk = wide_allsum(kk);
+            a1 = wide_allsum(a1); a2 = wide_allsum(a2);
+            // every lane stores the same bits and reads back its own store: no barrier
+            st[hd][0] = mx; st[hd][1] = lse; st[hd][2] = mxo; st[hd][3] = lseo;
+            st[hd][4] = e; st[hd][5] = kk; st[hd][6] = a1;
+            logp_a += lpa; ent += e; kl += kk; symkl += 0.5f * (a1 + a2);
+            off += nh; aoff += 1;
+        }
+        const float raw_ratio = expf(logp_a - old_logp[d]);
+        const float ratio = clampf(raw_ratio, 0.05f, 20.0f);
+        if (ratio_out && lane == 0) ratio_out[i] = ratio;
+        if (!valid) {  // no loss, zero gradient
+            for (int k = lane; k < A; k += 64) gz[k] = 0.f;
+            if (lane == 0) g_values[i * ldv] = 0.f;
+            continue;
+        }
+        const int64_t da = h.dense_adv ? i : d;
+        const float advn = (adv[da] - adv_mean) / denom;
+        const float clipped = clampf(ratio, h.clip_lo, h.clip_hi);
+        const float lu_ = ratio * advn, lc_ = clipped * advn;
+        const float pl = fminf(lu_, lc_);
+        const float v = values[i * ldv], vo = old_values[ov_row(h, d)], R = targets[da];
+        const float vclip = vo + clampf(v - vo, -h.clip_value, h.clip_value);
+        const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
+        const float vl = fmaxf(l1, l2);
+        if (lane == 0) {
+            acc[0] += pl;
+            acc[1] += (h.expl_kind == 2) ? symkl : ent;
+            acc[2] += kl;
+            acc[3] += vl;
+            kl_max = fmaxf(kl_max, kl);
+        }
+        // ---------------- backward (autograd semantics of min/max ties and clamp boundaries), as k_ppo_loss
+        float dpl_dr;
+        const bool in_clip = ratio >= h.clip_lo && ratio <= h.clip_hi;
+        if (lu_ < lc_) dpl_dr = advn;
+        else if (lu_ > lc_) dpl_dr = in_clip ? advn : 0.f;
+        else dpl_dr = 0.5f * advn + (in_clip ? 0.5f * advn : 0.f);
+        const bool in_hard = raw_ratio >= 0.05f && raw_ratio <= 20.0f;
+        const float dL_dlogp = in_hard ? (-inv_n) * dpl_dr * raw_ratio : 0.f;
+        off = 0;
+        aoff = 0;
+        for (int hd = 0; hd < H; ++hd) {
+            const int nh = h.head_n[hd];
+            if (nh < 0) {  // Box(D) member
+                const int Dh = -nh;
+                for (int k = lane; k < Dh; k += 64) {
+                    const float mu = z[off + k], e = expf(z[off + Dh + k]);
+                    const float sd = clampf(e, 1e-4f, 1e4f);
+                    const float dsd = (e >= 1e-4f && e <= 1e4f) ? e : 0.f;
+                    const float a = actions[d * NA + aoff + k];
+                    const float var = sd * sd;
+                    float gmu = dL_dlogp * ((a - mu) / var);
+                    float gsd = dL_dlogp * (((a - mu) * (a - mu)) / (var * sd) - 1.f / sd);
+                    if (h.expl_kind == 1) gsd += -h.expl_coeff * inv_n * (1.f / sd);
+                    if (h.kl_coeff != 0.f) {
+                        const float muo = zo[off + k], sdo = clampf(expf(zo[off + Dh + k]), 1e-4f, 1e4f);
+                        gmu += h.kl_coeff * inv_n * ((mu - muo) / (sdo * sdo));
+                        gsd += h.kl_coeff * inv_n * (sd / (sdo * sdo) - 1.f / sd);
+                    }
+                    gz[off + k] = gmu;
+                    gz[off + Dh + k] = gsd * dsd;
+                }
+                off += 2 * Dh; aoff += Dh;
+                continue;
+            }
+            const int act = (int)actions[d * NA + aoff];
+            aoff += 1;
+            const float mx = st[hd][0], lse = st[hd][1], mxo = st[hd][2], lseo = st[hd][3];
+            const float ent_h = st[hd][4], kl_h = st[hd][5], klpu_h = st[hd][6];
+            const float u = 1.0f / (float)nh, lu = logf(u);
+#pragma unroll 4
+            for (int k = lane; k < nh; k += 64) {
+                const float lp = (z[off + k] - mx) - lse, p = expf(lp);
+                float gk = dL_dlogp * ((k == act ? 1.f : 0.f) - p);
+                if (h.expl_kind == 1) gk += h.expl_coeff * inv_n * (p * (lp + ent_h));
+                if (h.expl_kind == 2)
+                    gk += symkl_gate * h.expl_coeff * inv_n * 0.5f * (p * ((lp - lu) - klpu_h) + p - u);
+                if (h.kl_coeff != 0.f) {
+                    const float q = (zo[off + k] - mxo) - lseo;
+                    gk += h.kl_coeff * inv_n * (p * ((lp - q) - kl_h));
+                }
+                gz[off + k] = gk;
+            }
+            off += nh;
+        }
+        if (lane == 0) {
+            const bool in_v = (v - vo) >= -h.clip_value && (v - vo) <= h.clip_value;
+            float dvl;
+            if (l1 > l2) dvl = 2.f * (v - R);
+            else if (l2 > l1) dvl = in_v ? 2.f * (vclip - R) : 0.f;
+            else dvl = (v - R) + (in_v ? (vclip - R) : 0.f);
+            g_values[i * ldv] = h.value_coeff * inv_n * dvl;
+        }
+    }
+    kl_max = sf_wave_max(kl_max);
+    if (lane == 0) lds_max[wave] = kl_max;
+    sf_block_sum<4>(acc, lds);
+    if (threadIdx.x == 0) {
+        if (sym_pass) { atomicAdd(&sums[7], acc[0]); return; }
+        atomicAdd(&sums[0], acc[0]);
+        atomicAdd(&sums[1], acc[1]);
+        atomicAdd(&sums[2], acc[2]);
+        atomicAdd(&sums[3], acc[3]);
+        const float m = fmaxf(fmaxf(lds_max[0], lds_max[1]), fmaxf(lds_max[2], lds_max[3]));
+        if (m > -1.0f) atomic_max_float(&sums[4], m);
+    }
+}
+
 __global__ void k_symkl_gate(double *__restrict__ sums, const double *__restrict__ moments) {
     if (threadIdx.x || blockIdx.x) return;
     const float m = (float)(sums[7] / moments[2]);
@@ -869,6 +1187,26 @@ static LossDev make_loss_dev(const sf_loss_cfg *c) {
     return h;
 }
 
+static int ppo_loss_wide_launch(const float *params, int ld_params, const float *values, int ld_values,
+                                const float *actions, const float *old_logp, const float *old_params,
+                                const float *old_values, const float *adv, const float *targets, const uint8_t *valids,
+                                const int32_t *index, int64_t offset, int64_t n, int A, const LossDev &h,
+                                const double *moments, double *sums, float *g_params, float *g_values, float *ratio_out,
+                                void *stream) {
+    const int64_t want = (n + WIDE_ROWS - 1) / WIDE_ROWS;
+    const dim3 grid((unsigned)(want < 2048 ? want : 2048)), block(256);  // 256 CUs x 8 blocks; the rows are grid-strided
+    if (h.expl_kind == 2) {
+        k_ppo_loss_wide<<<grid, block, 0, STREAM(stream)>>>(params, ld_params, values, ld_values, actions, old_logp,
+                                                            old_params, old_values, adv, targets, valids, index, offset,
+                                                            n, A, h, moments, sums, g_params, g_values, nullptr, 1);
+        k_symkl_gate<<<dim3(1), dim3(64), 0, STREAM(stream)>>>(sums, moments);
+    }
+    k_ppo_loss_wide<<<grid, block, 0, STREAM(stream)>>>(params, ld_params, values, ld_values, actions, old_logp, old_params,
+                                                        old_values, adv, targets, valids, index, offset, n, A, h, moments,
+                                                        sums, g_params, g_values, ratio_out, 0);
+    return sf_launch_status("sf_ppo_loss");
+}
+
 extern "C" int sf_ppo_loss(const float *params, int ld_params, const float *values, int ld_values,
                            const float *actions, const float *old_logp, const float *old_params,
                            const float *old_values, const float *adv, const float *targets, const uint8_t *valids,
@@ -879,7 +1217,7 @@ extern "C" int sf_ppo_loss(const float *params, int ld_params, const float *valu
     SF_REQUIRE(params && values && actions && old_logp && old_params && old_values && adv && targets && valids &&
                    h_cfg && moments && sums && g_params && g_values,
                "sf_ppo_loss: null pointer");
-    SF_REQUIRE(n > 0 && A > 0 && A <= 128, "sf_ppo_loss: bad shape n=%lld A=%d", (long long)n, A);
+    SF_REQUIRE(n > 0 && A > 0, "sf_ppo_loss: bad shape n=%lld A=%d", (long long)n, A);
     SF_REQUIRE(h_cfg->action_kind == 0 || (h_cfg->action_kind == 1 && A % 2 == 0), "sf_ppo_loss: bad action_kind");
     SF_REQUIRE(!(h_cfg->exploration_kind == 2 && h_cfg->action_kind != 0 && h_cfg->exploration_coeff != 0.f),
                "sf_ppo_loss: symmetric_kl exploration loss needs a categorical distribution");
@@ -906,6 +1244,9 @@ extern "C" int sf_ppo_loss(const float *params, int ld_params, const float *valu
         SF_REQUIRE(!(any_box && h.expl_kind == 2),
                    "sf_ppo_loss: symmetric_kl exploration loss needs categorical heads only (the reference's "
                    "ContinuousActionDistribution has no symmetric_kl_with_uniform_prior)");
+        if (A >= WIDE_MIN_A) return ppo_loss_wide_launch(params, ld_params, values, ld_values, actions, old_logp,
+                                                         old_params, old_values, adv, targets, valids, index, offset, n,
+                                                         A, h, moments, sums, g_params, g_values, ratio_out, stream);
         if (h.expl_kind == 2) {
             k_ppo_loss_md<<<grid, block, 0, STREAM(stream)>>>(params, ld_params, values, ld_values, actions, old_logp, old_params,
                                                               old_values, adv, targets, valids, index, offset, n, A, h, moments,
@@ -916,6 +1257,13 @@ extern "C" int sf_ppo_loss(const float *params, int ld_params, const float *valu
                                                           old_values, adv, targets, valids, index, offset, n, A, h, moments, sums,
                                                           g_params, g_values, ratio_out, 0);
         return sf_launch_status("sf_ppo_loss");
+    }
+    if (A >= WIDE_MIN_A) {  // a single Discrete(A) / Box(A / 2) as a one-member head list
+        LossDev hw = h;
+        hw.head_n[0] = h.action_kind == 0 ? A : -(A / 2);
+        return ppo_loss_wide_launch(params, ld_params, values, ld_values, actions, old_logp, old_params, old_values, adv,
+                                    targets, valids, index, offset, n, A, hw, moments, sums, g_params, g_values,
+                                    ratio_out, stream);
     }
     if (h.expl_kind == 2) {
         PL_DISPATCH(k_symkl_sum, params, ld_params, valids, index, offset, n, A, sums + 7);
@@ -1549,6 +1897,141 @@ __global__ __launch_bounds__(256) void k_sample_write(const float *__restrict__ 
     if (env_actions) env_actions[b] = a;
 }
 
+// The three samplers for A > 128, one wave per env row: any head list of up to 8 members, or one Discrete(A) with an
+// action mask (mask != nullptr, the rule above k_sample_write_masked).  Same Philox counters, uniforms and draw rule
+// as the lane-per-row samplers.  The CDF is walked 64 columns at a time: an inclusive wave scan of the chunk's
+// probabilities plus the carry of the chunks before it, a ballot for the first lane with u < cdf.
+__global__ __launch_bounds__(256) void k_sample_write_wide(const float *__restrict__ logits, int ldl,
+                                                           const float *__restrict__ values, int ldv,
+                                                           const uint8_t *__restrict__ mask, int64_t ldm, int B, int A,
+                                                           int T, int t, uint32_t seed, uint32_t step, uint32_t row0,
+                                                           float version, int deterministic, HeadsDev hd,
+                                                           float *__restrict__ t_actions, float *__restrict__ t_logits,
+                                                           float *__restrict__ t_logp, float *__restrict__ t_values,
+                                                           float *__restrict__ t_version,
+                                                           int32_t *__restrict__ env_actions) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.x * WIDE_ROWS + wave;
+    if (b >= B) return;
+    const float *z = logits + (int64_t)b * ldl;
+    const uint8_t *mk = mask ? mask + (int64_t)b * ldm : nullptr;
+    const int64_t it = (int64_t)b * T + t;
+    const int H = hd.num_heads;
+    const int NA = heads_action_cols(hd.head_n, H);
+    float lp_sum = 0.f;
+    int off = 0, aoff = 0;
+    for (int h = 0; h < H; ++h) {
+        const int nh = hd.head_n[h];
+        if (nh < 0) {  // Box(D) member: a = mu + sd * eps, eps from Box-Muller on Philox counter (step, k / 2, 3, h)
+            const int D = -nh;
+            float lpp = 0.f;
+            for (int k = lane; k < D; k += 64) {
+                uint32_t w[4];
+                sf_philox4x32_10(step, (uint32_t)(k >> 1), 3u, (uint32_t)h, seed, row0 + (uint32_t)b, w);
+                const uint32_t w1 = (k & 1) ? w[2] : w[0], w2 = (k & 1) ? w[3] : w[1];
+                const float u1 = ((float)(w1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+                const float u2 = (float)(w2 >> 8) * (1.0f / 16777216.0f);
+                const float eps = sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+                const float mu = z[off + k];
+                const float sd = clampf(expf(z[off + D + k]), 1e-4f, 1e4f);
+                const float a = deterministic ? mu : mu + sd * eps;
+                t_actions[it * NA + aoff + k] = a;
+                lpp += -((a - mu) * (a - mu)) / (2.f * (sd * sd)) - logf(sd) - 0.91893853320467274178f;
+            }
+            lp_sum += wide_allsum(lpp);
+            off += 2 * D; aoff += D;
+            continue;
+        }
+        const float *zh = z + off;
+        float mx, lse;
+        wide_lse(zh, nh, lane, mk, mx, lse);
+        // masked: probs = softmax * mask / (sum + 1e-13), an all-masked row draws from nh weights of 1e-6
+        bool all_zero = false;
+        float inv = 1.f, tot = 1.f;
+        if (mk) {
+            float ps = 0.f;
+            for (int k = lane; k < nh; k += 64) ps += mk[k] ? expf((zh[k] - mx) - lse) : 0.f;
+            const float psum = wide_allsum(ps);
+            all_zero = psum == 0.f;
+            inv = 1.0f / (psum + 1e-13f);
+            tot = all_zero ? (float)nh * 1e-6f : psum * inv;  // multinomial normalises its weights
+        }
+        int a;
+        if (deterministic) {
+            int first = 0x7fffffff;
+            if (!mk) {  // first maximum, as torch.argmax
+                for (int k = lane; k < nh; k += 64) if (zh[k] == mx) first = min(first, k);
+            } else if (all_zero) {
+                first = 0;
+            } else {  // first maximum of the masked probabilities
+                float best = -1.f;
+                for (int k = lane; k < nh; k += 64) best = fmaxf(best, mk[k] ? expf((zh[k] - mx) - lse) * inv : 0.f);
+                best = wide_allmax(best);
+                for (int k = lane; k < nh; k += 64)
+                    if ((mk[k] ? expf((zh[k] - mx) - lse) * inv : 0.f) == best) first = min(first, k);
+            }
+            a = min(wide_allmin(first), nh - 1);  // (no maximum found: NaN logits, out of scope; stay inside the row)
+        } else {
+            uint32_t w[4];
+            sf_philox4x32_10(step, (uint32_t)h, 2u, 0u, seed, row0 + (uint32_t)b, w);
+            const float u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);
+            float carry = 0.f;
+            int last_pos = -1;  // last action whose probability did not underflow
+            a = -1;
+            for (int base = 0; base < nh; base += 64) {
+                const int k = base + lane;
+                float p = 0.f;
+                if (k < nh) {
+                    if (!mk) p = expf((zh[k] - mx) - lse);
+                    else p = (all_zero ? 1e-6f : (mk[k] ? expf((zh[k] - mx) - lse) * inv : 0.f)) / tot;
+                }
+                float c = p;
+#pragma unroll
+                for (int s = 1; s < 64; s <<= 1) {
+                    const float up = __shfl_up(c, s, 64);
+                    if (lane >= s) c += up;
+                }
+                c += carry;
+                // (the scan adds in a different order per lane: behind a zero p the f32 cdf may sit an ulp ABOVE its
+                // neighbour's, so a crossing only counts where there is probability)
+                const unsigned long long hit = __ballot(p > 0.f && u < c);
+                const unsigned long long pos = __ballot(p > 0.f);
+                if (pos) last_pos = base + 63 - __clzll((long long)pos);
+                if (hit) { a = base + __ffsll((long long)hit) - 1; break; }
+                carry = __shfl(c, 63, 64);
+            }
+            // the f32 CDF can end a few ulps below 1 and u can reach 1 - 2^-24: take the last action that has any
+            // probability, never a zero-probability (underflowed or masked-out) one
+            if (a < 0) a = last_pos >= 0 ? last_pos : nh - 1;
+        }
+        lp_sum += ((mk ? zh[a] + (mk[a] ? 0.f : -1e9f) : zh[a]) - mx) - lse;
+        if (lane == 0) {
+            t_actions[it * NA + aoff] = (float)a;
+            if (env_actions) env_actions[(int64_t)b * H + h] = a;  // all-Discrete head lists only (the launchers check)
+        }
+        off += nh; aoff += 1;
+    }
+#pragma unroll 4
+    for (int k = lane; k < A; k += 64) t_logits[it * A + k] = z[k];
+    if (lane == 0) {
+        t_logp[it] = lp_sum;
+        t_version[it] = version;
+        t_values[(int64_t)b * (T + 1) + t] = values[(int64_t)b * ldv];
+    }
+}
+
+static int sample_write_wide_launch(const char *what, const float *logits, int ld_logits, const float *values,
+                                    int ld_values, const uint8_t *mask, int64_t ld_mask, int B, int A, int T, int t,
+                                    uint32_t seed, uint32_t step, uint32_t row0, float policy_version, int deterministic,
+                                    const HeadsDev &hd, float *traj_actions, float *traj_logits, float *traj_logp,
+                                    float *traj_values, float *traj_policy_version, int32_t *env_actions, void *stream) {
+    SF_REQUIRE(ld_logits >= A && ld_values >= 1 && (!mask || ld_mask >= A), "%s: bad strides", what);
+    k_sample_write_wide<<<dim3((unsigned)((B + WIDE_ROWS - 1) / WIDE_ROWS)), dim3(256), 0, STREAM(stream)>>>(
+        logits, ld_logits, values, ld_values, mask, ld_mask, B, A, T, t, seed, step, row0, policy_version, deterministic,
+        hd, traj_actions, traj_logits, traj_logp, traj_values, traj_policy_version, env_actions);
+    return sf_launch_status(what);
+}
+
 extern "C" int sf_sample_write_step(const float *logits, int ld_logits, const float *values, int ld_values, int B,
                                     int A, int T, int t, uint32_t seed, uint32_t step, uint32_t row0, float policy_version,
                                     int deterministic, int action_kind, float *traj_actions, float *traj_logits, float *traj_logp,
@@ -1558,8 +2041,13 @@ extern "C" int sf_sample_write_step(const float *logits, int ld_logits, const fl
                "sf_sample_write_step: null pointer");
     SF_REQUIRE(action_kind == 1 || env_actions, "sf_sample_write_step: discrete actions need the int32 env_actions");
     SF_REQUIRE(action_kind == 0 || (action_kind == 1 && A % 2 == 0), "sf_sample_write_step: bad action_kind");
-    SF_REQUIRE(B > 0 && A > 0 && A <= 128 && T > 0 && t >= 0 && t < T, "sf_sample_write_step: bad shape B=%d A=%d T=%d t=%d",
+    SF_REQUIRE(B > 0 && A > 0 && T > 0 && t >= 0 && t < T, "sf_sample_write_step: bad shape B=%d A=%d T=%d t=%d",
                B, A, T, t);
+    if (A >= WIDE_MIN_A)
+        return sample_write_wide_launch("sf_sample_write_step", logits, ld_logits, values, ld_values, nullptr, 0, B, A, T,
+                                        t, seed, step, row0, policy_version, deterministic,
+                                        wide_single_head(A, action_kind), traj_actions, traj_logits, traj_logp,
+                                        traj_values, traj_policy_version, env_actions, stream);
     const dim3 grid((unsigned)((B + 255) / 256)), block(256);
 #define SW_LAUNCH(M)                                                                                               \
     k_sample_write<M><<<grid, block, 0, STREAM(stream)>>>(logits, ld_logits, values, ld_values, B, A, T, t, seed, step, row0,            \
@@ -1640,6 +2128,11 @@ extern "C" int sf_sample_write_step_masked(const float *logits, int ld_logits, c
                    traj_policy_version, "sf_sample_write_step_masked: null pointer");
     SF_REQUIRE(B > 0 && A > 0 && T > 0 && t >= 0 && t < T && ld_logits >= A && ld_values >= 1 && ld_mask >= A,
                "sf_sample_write_step_masked: bad shape B=%d A=%d T=%d t=%d", B, A, T, t);
+    if (A >= WIDE_MIN_A)
+        return sample_write_wide_launch("sf_sample_write_step_masked", logits, ld_logits, values, ld_values, action_mask,
+                                        ld_mask, B, A, T, t, seed, step, row0, policy_version, deterministic,
+                                        wide_single_head(A, 0), traj_actions, traj_logits, traj_logp, traj_values,
+                                        traj_policy_version, env_actions, stream);
     k_sample_write_masked<<<dim3((unsigned)((B + 255) / 256)), dim3(256), 0, STREAM(stream)>>>(
         logits, ld_logits, values, ld_values, action_mask, ld_mask, B, A, T, t, seed, step, row0, policy_version,
         deterministic, traj_actions, traj_logits, traj_logp, traj_values, traj_policy_version, env_actions);
@@ -1738,6 +2231,14 @@ extern "C" int sf_sample_write_step_tuple(const float *logits, int ld_logits, co
         A += head_n[i] > 0 ? head_n[i] : -2 * head_n[i];
     }
     SF_REQUIRE(ld_logits >= A && ld_values >= 1, "sf_sample_write_step_tuple: bad strides");
+    if (A >= WIDE_MIN_A) {
+        HeadsDev whd = {};
+        whd.num_heads = num_heads;
+        for (int i = 0; i < num_heads; ++i) whd.head_n[i] = head_n[i];
+        return sample_write_wide_launch("sf_sample_write_step_tuple", logits, ld_logits, values, ld_values, nullptr, 0, B,
+                                        A, T, t, seed, step, row0, policy_version, deterministic, whd, traj_actions,
+                                        traj_logits, traj_logp, traj_values, traj_policy_version, env_actions, stream);
+    }
     k_sample_write_tuple<<<dim3((unsigned)((B + 255) / 256)), dim3(256), 0, STREAM(stream)>>>(
         logits, ld_logits, values, ld_values, B, A, T, t, seed, step, row0, policy_version, deterministic, hd,
         traj_actions, traj_logits, traj_logp, traj_values, traj_policy_version, env_actions);

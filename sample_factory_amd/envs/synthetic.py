@@ -261,7 +261,8 @@ def make_dict_obs_bandit_env(full_env_name, cfg=None, env_config=None, render_mo
 
 def make_masked_bandit_env(full_env_name, cfg=None, env_config=None, render_mode=None):
     n = getattr(cfg, "synthetic_num_agents", 64) if cfg is not None else 64
-    return MaskedBanditEnv(num_agents=n, seed=(getattr(cfg, "seed", None) or 0) if cfg is not None else 0)
+    a = int(getattr(cfg, "synthetic_num_actions", 6) or 6) if cfg is not None else 6
+    return MaskedBanditEnv(num_agents=n, num_actions=a, seed=(getattr(cfg, "seed", None) or 0) if cfg is not None else 0)
 
 
 def make_synthetic_tuple_env(full_env_name, cfg=None, env_config=None, render_mode=None):
