@@ -20,7 +20,9 @@
 // from a clamped, always-valid address and are zeroed with a select, so the compiler issues every global load of a
 // chunk back-to-back and waits once (the first version branched per load and hipcc serialised them with vmcnt(0)).
 #include "sf_common.h"
+#include <stdarg.h>
 #include <stdlib.h>
+#include <string.h>
 #ifndef SF_GLDS_ABLATE
 #define SF_GLDS_ABLATE 0  // timing experiments only (sf_nn_glds.h)
 #endif
@@ -726,9 +728,46 @@ __global__ __launch_bounds__(256) void k_reduce_partials_tree(const float *__res
     if (zg == 0 && i < n)
         out[i] = ((sm[0][li] + sm[1][li]) + (sm[2][li] + sm[3][li])) + ((sm[4][li] + sm[5][li]) + (sm[6][li] + sm[7][li]));
 }
+// ============================================================================================== A/B switches
+// Every SF_* environment variable this file reads, once per process; what each one does stands at the decision it steers.
+#define SF_SWITCHES(X)                                                                                                  \
+    X(reduce_tree, "SF_REDUCE_TREE", 1) X(conv1_bf16, "SF_CONV1_BF16", 1) X(conv1_img, "SF_CONV1_IMG", 1)              \
+    X(conv1_wgs, "SF_CONV1_WGS", 2) X(conv1_wide, "SF_CONV1_WIDE", 1) X(conv1_norm, "SF_CONV1_NORM", 1)                \
+    X(relu_mask, "SF_RELU_MASK", 1) X(fwd_img, "SF_FWD_IMG", 1) X(linear_narrow, "SF_LINEAR_NARROW", 1)                \
+    X(linear_dual, "SF_LINEAR_DUAL", 1) X(glds_cfg, "SF_GLDS_CFG", 0) X(glds_splitk, "SF_GLDS_SPLITK", 1)              \
+    X(glds_fc64, "SF_GLDS_FC64", 1) X(glds_wide_min, "SF_GLDS_WIDE_MIN", 384) X(glds_min_tiles, "SF_GLDS_MIN_TILES", 768) \
+    X(glds_small64, "SF_GLDS_SMALL64", 256) X(glds_force64, "SF_GLDS_FORCE64", 0) X(glds_split64, "SF_GLDS_SPLIT64", 32) \
+    X(glds_zl, "SF_GLDS_ZL", 2) X(glds_tailsplit, "SF_GLDS_TAILSPLIT", 1) X(glds_tall, "SF_GLDS_TALL", 0)              \
+    X(glds_persist, "SF_GLDS_PERSIST", 0) X(xcd_raster, "SF_XCD_RASTER", 1) X(xcd_rows, "SF_XCD_ROWS", 0)              \
+    X(tap_perm, "SF_TAP_PERM", 0) X(wgrad_glds, "SF_WGRAD_GLDS", 1) X(wgrad_glds_min, "SF_WGRAD_GLDS_MIN", -1)         \
+    X(wgrad_glds_k64, "SF_WGRAD_GLDS_K64", 1) X(wgrad_img, "SF_WGRAD_IMG", 3) X(wgrad_zl, "SF_WGRAD_ZL", 1)            \
+    X(dgrad_linear, "SF_DGRAD_LINEAR", 1) X(dgrad_linear64, "SF_DGRAD_LINEAR64", 1) X(dgrad_lpt, "SF_DGRAD_LPT", 1)    \
+    X(dgrad_zl, "SF_DGRAD_ZL", 3) X(dgrad_pix, "SF_DGRAD_PIX", 1) X(debug_occ, "SF_DEBUG_OCC", 0)
+struct Switches {
+#define X(field, name, dflt) int64_t field;
+    SF_SWITCHES(X)
+#undef X
+    bool debug_img;  // SF_DEBUG_IMG set at all
+};
+static int64_t env_num(const char *name, int64_t dflt) {
+    const char *v = getenv(name);
+    return v ? atoll(v) : dflt;
+}
+static Switches read_switches() {
+    Switches s;
+#define X(field, name, dflt) s.field = env_num(name, dflt);
+    SF_SWITCHES(X)
+#undef X
+    s.debug_img = getenv("SF_DEBUG_IMG") != nullptr;
+    return s;
+}
+static const Switches &sw() {
+    static const Switches s = read_switches();
+    return s;
+}
+
 static void launch_reduce_partials(const float *partial, float *out, int64_t n, int Z, hipStream_t st) {
-    static const int tree_on = getenv("SF_REDUCE_TREE") ? atoi(getenv("SF_REDUCE_TREE")) : 1;
-    if (tree_on && Z >= 64 && (n + 255) / 256 < 256)  // fewer loop work-groups than CUs and a long walk each
+    if (sw().reduce_tree && Z >= 64 && (n + 255) / 256 < 256)  // fewer loop work-groups than CUs and a long walk each
         k_reduce_partials_tree<<<dim3((unsigned)((n + 31) / 32)), dim3(256), 0, st>>>(partial, out, n, Z);
     else
         k_reduce_partials<<<dim3((unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0, st>>>(partial, out, n, Z);
@@ -886,6 +925,73 @@ static int num_cus() {
     return v;
 }
 
+// ---------------------------------------------------------------------------------------------- launch plans
+// One plan per operation: plan_conv_fwd (sf_conv_fwd, sf_conv_fwd_norm), plan_conv_fwd_t, plan_conv_wgrad (sf_conv_wgrad,
+// sf_conv_wgrad_norm) and plan_conv_dgrad decide WHICH kernel a launch runs and everything its <<<>>> needs.  The launchers
+// validate their arguments and switch on plan.kernel; sf_conv_kernel_name, the workspace queries and the *_supported
+// queries call the same functions, so a threshold or a switch lives in exactly one place.
+enum ConvKernel {
+    K_NONE,  // not a launch the entry point accepts
+    K_CONV_FWD, K_CONV1_U8_BF16, K_CONV1_U8_BF16_W, K_CONV_U8_IMG, K_CONV_U8_IMG_NORM,
+    K_LINEAR_NARROW, K_FWD_IMG, K_FWD_GLDS, K_FWD_GLDS_Z, K_FWD_GLDS_ZT, K_FWD_GLDS_ZP,
+    K_CONV_WGRAD, K_CONV1_WGRAD_BF16, K_CONV1_WGRAD_IMG, K_CONV1_WGRAD_IMG_NORM, K_LINEAR_WGRAD_SMALL, K_WGRAD_IMG,
+    K_WGRAD_GLDS, K_WGRAD_GLDS_Z,
+    K_CONV_DGRAD, K_DGRAD_PIX, K_DGRAD_PIX_Z, K_DGRAD_QUADROW, K_DGRAD_QUADROW_Z,
+};
+struct TileArgs { int BM, BN, WM, WN; };  // the <BM, BN, WM, WN> of a tiled kernel (weight gradients: BM = reduction-free K rows)
+struct ConvPlan {
+    int kernel;           // ConvKernel
+    char name[64];        // the instantiation as rocprofv3 spells it
+    TileArgs t;
+    int variant;          // the remaining template argument: loader MODE, bool (mean subtracted / vector loads), index into
+                          // IMG_FWD_GEOMS, k_linear_narrow<1|2>, k_wgrad_img variant 1|2
+    dim3 grid, block;
+    unsigned lds;         // dynamic LDS bytes
+    int splits;           // slices of the reduction (gridDim.z before rastering), 1 = unsplit
+    int64_t per_split;    // k_per_split (forward) / m_per_split (weight gradient)
+    int partials;         // weight gradient: partial results in the workspace; partial_b starts partials * K * N floats in
+    int rx, ry, rtot;     // XCD-aware block order (sf_nn_glds.h): tiles per row / column, total (0 = plain grid)
+    int main_tiles;       // k_fwd_glds_zt: 128-row tiles in front of the split last round
+    bool recommended;     // sf_conv_fwd_t_supported's answer
+};
+static ConvPlan plan_init() {
+    ConvPlan p{};  // K_NONE, a grid of one work-group, no name
+    p.block = dim3(256); p.splits = p.partials = 1;
+    return p;
+}
+static void plan_kernel(ConvPlan &p, int kernel, const char *fmt, ...) {
+    p.kernel = kernel;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(p.name, sizeof(p.name), fmt, ap);
+    va_end(ap);
+}
+static void plan_tile(ConvPlan &p, int kernel, const char *base, TileArgs t, const char *tail = "") {
+    p.t = t;
+    plan_kernel(p, kernel, "%s<%d, %d, %d, %d%s>", base, t.BM, t.BN, t.WM, t.WN, tail);
+}
+// 1-D launch whose block ids are re-mapped so that every XCD owns a contiguous run of tiles (sf_nn_glds.h)
+static void plan_raster(ConvPlan &p, bool on) {
+    p.rx = (int)p.grid.x; p.ry = (int)p.grid.y;
+    p.rtot = on ? (int)(p.grid.x * p.grid.y * p.grid.z) : 0;
+    if (p.rtot > 0) p.grid = dim3((unsigned)(8 * ((p.rtot + 7) / 8)), 1, 1);
+}
+
+// What a launcher knows about its operands beyond the descriptor; the plans test the alignments.  sf_conv_kernel_name and
+// the queries ask for query_operands(): everything aligned (a null pointer is), dense samples, no index.
+struct Operands {
+    const void *in;
+    int64_t stride;     // in_sample_stride
+    bool index;         // samples gathered through an index
+    const void *w, *dout, *out;
+    int64_t ws_floats;  // sf_conv_fwd: floats of split-K workspace
+};
+static Operands query_operands(const sf_conv_desc *d, bool split_k_workspace) {
+    return Operands{nullptr, (int64_t)d->H * d->W * d->Cin, false, nullptr, nullptr, nullptr, split_k_workspace ? (int64_t)1 << 60 : 0};
+}
+static bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+static const float TABLE_PROBE[4] __attribute__((aligned(16))) = {0.f, 0.f, 0.f, 0.f};  // stands for mu / rstd in the queries
+
 // (g.nmu set: a launch of sf_conv_fwd_norm / sf_conv_wgrad_norm)
 static int pick_mode(const ConvG &g) {
     if (!g.vecA || !g.vecB) return MODE_GENERIC;
@@ -894,16 +1000,45 @@ static int pick_mode(const ConvG &g) {
     return MODE_F32;
 }
 
+// vector loads of the activation operand also need aligned bases (f32: 16 bytes; u8 frames: 4 bytes; the normaliser's
+// tables of either frame format: 16 bytes)
+static bool act_aligned(const ConvG &g, const void *in, int64_t in_sample_stride) {
+    return aligned(in, in_is_u8(g.in_u8) ? 4 : 16) && in_sample_stride % 4 == 0 && aligned(g.nmu, 16) && aligned(g.nrstd, 16);
+}
+
+// frame base 4-byte aligned, sample stride a multiple of 4: what the Nature-CNN conv1 strip kernels ask of their input
+static bool in4(const Operands &o) { return aligned(o.in, 4) && o.stride % 4 == 0; }
+static bool tabs16(const ConvG &g) { return aligned(g.nmu, 16) && aligned(g.nrstd, 16); }
+
+static bool nature_conv1_geom(const ConvG &g) {
+    return g.Cin == 4 && g.H == 84 && g.W == 84 && g.KH == 8 && g.KW == 8 && g.S == 4;
+}
 // geometry contract of k_conv_u8_img<2, 4, 5, 16, *>
 static bool conv1_img_ok(const ConvG &g, int mode, int64_t n) {
-    return mode == MODE_U8 && n >= 256 && g.Cin == 4 && g.H == 84 && g.W == 84 && g.KH == 8 && g.KW == 8 && g.S == 4 &&
-           g.Cout <= 32;
+    return mode == MODE_U8 && n >= 256 && nature_conv1_geom(g) && g.Cout <= 32;
 }
 
 // k_conv1_u8_bf16: same geometry; the A operand must be exact in bf16: pixel - mean an integer of at most 8 bits
 static bool conv1_bf16_ok(const ConvG &g, int mode, int64_t n) {
-    static const int on = getenv("SF_CONV1_BF16") ? atoi(getenv("SF_CONV1_BF16")) : 1;
-    return on && conv1_img_ok(g, mode, n) && g.sub_mean == floorf(g.sub_mean) && g.sub_mean >= 0.f && g.sub_mean <= 255.f;
+    return sw().conv1_bf16 && conv1_img_ok(g, mode, n) && g.sub_mean == floorf(g.sub_mean) && g.sub_mean >= 0.f &&
+           g.sub_mean <= 255.f;
+}
+
+// ---- conv1 on raw u8 frames WITH the observation normaliser's running statistics applied in the loader (cfg.normalize_input
+// on image observations: utils/normalize.py:51-70, running_mean_std.py:79-110, cfg/cfg.py:337-341 default True): no
+// normalised f32 copy of the frames exists anywhere.  mu / rstd: the normaliser's f32 tables [Cin*H*W] in the frame's NCHW
+// order (sf_obsnorm_update writes them).  sf_conv_norm_supported() accepts every frame descriptor (in_u8 = 1 or 2) that
+// check_desc accepts.  Both frame formats take every geometry: the register-staged kernels (k_conv_fwd / k_conv_wgrad)
+// form clamp(((x - sub_mean) * inv_scale - mu[d]) * rstd[d], +-5) in their loaders (MODE_U8_NORM / MODE_F32F_NORM), with
+// vector loads of pixels and table entries where sf_conv_fwd would use them and the scalar loader otherwise.  The
+// Nature-CNN conv1 on u8 frames (32 output channels, aligned operands) keeps the strip-image kernels it always had.
+static bool conv_norm_ok(const sf_conv_desc *d, int64_t n) {
+    return sw().conv1_norm && d && n > 0 && in_is_frame(d->in_u8);
+}
+// the strip kernels' compile-time geometry; ANY n (their n >= 256 dispatch threshold is a speed heuristic of the plain
+// entry points, the kernels themselves are correct for every n >= 1)
+static bool conv_norm_strip(const ConvG &g) {
+    return in_is_u8(g.in_u8) && g.Cout == 32 && g.vecA && g.vecB && nature_conv1_geom(g);
 }
 
 // forward launch plan: tile config + optional split-K when the natural grid cannot fill 256 CUs several times over
@@ -933,6 +1068,61 @@ static FwdPlan plan_fwd(int64_t Mtot, int N, int K, int64_t ws_floats) {
     return p;
 }
 
+// sf_conv_fwd and (g.nmu set) sf_conv_fwd_norm
+static ConvPlan plan_conv_fwd(const sf_conv_desc *d, const ConvG &g, int64_t n, const Operands &o) {
+    ConvPlan p = plan_init();
+    const bool norm = g.nmu != nullptr;
+    if (norm && !conv_norm_ok(d, n)) return p;
+    const int64_t Mtot = n * g.OH * g.OW, npairs = cdiv64(n, 2);
+    if (norm && conv_norm_strip(g) && in4(o) && tabs16(g)) {
+        // the Nature-CNN conv1 on aligned u8 frames; every other normalising launch: the register-staged kernel below
+        p.lds = (unsigned)(2 * 4 * 20 * 84 * sizeof(float));
+        static const int bpc = occupancy_of(k_conv_u8_img_norm<2, 4, 5, 16>, 256, 2 * 4 * 20 * 84 * sizeof(float));
+        const int64_t resident = (int64_t)num_cus() * (bpc > 0 ? bpc : 1);
+        p.grid = dim3((unsigned)(npairs < resident ? npairs : resident));
+        plan_kernel(p, K_CONV_U8_IMG_NORM, "k_conv_u8_img_norm<2, 4, 5, 16>");
+        return p;
+    }
+    int mode = pick_mode(g);
+    if (mode != MODE_GENERIC && (!act_aligned(g, o.in, o.stride) || !aligned(o.w, 16))) mode = MODE_GENERIC;
+    p.variant = g.sub_mean != 0.f;
+    // Nature-CNN conv1 on raw frames: strip-image kernel (bytes converted once into an f32 LDS image, im2col read
+    // out of LDS).  Geometry contract of the <2,4,5,16> instantiation: K = 256, 2*4*OW rows = 10 fragments.
+    // ... and on the bf16 matrix pipe with exact products (sf_nn_u8.h) when (pixel - mean) is an integer of <= 8 bits
+    if (conv1_bf16_ok(g, mode, n) && in4(o)) {
+        // [SMP][Cin][RS][WP] bf16 strip image + (whole-line stores) the staging tile [SMP][80][36] f32
+        const unsigned img_bytes = 2u * 4u * 20u * (unsigned)SF_CONV1_WP * (unsigned)sizeof(uint16_t);
+        // persistent grid: SF_CONV1_WGS work-groups per CU (default 2 = what the register budget of __launch_bounds__(256, 2) admits)
+        const int64_t resident = (int64_t)num_cus() * sw().conv1_wgs;
+        p.grid = dim3((unsigned)(npairs < resident ? npairs : resident));
+        // SF_CONV1_WIDE (default 1): whole-line output stores through an LDS staging tile (sf_nn_u8.h) — N == 32, aligned output
+        const bool wide = sw().conv1_wide && g.Cout == 32 && aligned(o.out, 16);
+        p.lds = img_bytes + (wide ? 2u * 80u * 36u * (unsigned)sizeof(float) : 0u);
+        plan_kernel(p, wide ? K_CONV1_U8_BF16_W : K_CONV1_U8_BF16, "k_conv1_u8_bf16%s<%s>", wide ? "_w" : "",
+                    p.variant ? "true" : "false");
+        return p;
+    }
+    if (sw().conv1_img && conv1_img_ok(g, mode, n) && in4(o)) {
+        p.lds = (unsigned)(2 * 4 * 20 * 84 * sizeof(float));  // [SMP][Cin][RS][W] f32
+        // persistent work-groups: as many as are resident at once (two per CU: 53.8 KB of LDS each), each walks the
+        // sample pairs b, b + grid, ...
+        static const int bpc = occupancy_of(k_conv_u8_img<2, 4, 5, 16, false>, 256, 2 * 4 * 20 * 84 * sizeof(float));
+        const int64_t resident = (int64_t)num_cus() * bpc;
+        p.grid = dim3((unsigned)(npairs < resident ? npairs : resident));
+        plan_kernel(p, K_CONV_U8_IMG, "k_conv_u8_img<2, 4, 5, 16, %s>", p.variant ? "true" : "false");
+        return p;
+    }
+    const FwdPlan f = plan_fwd(Mtot, g.Cout, g.K, norm ? 0 : o.ws_floats);  // (sf_conv_fwd_norm takes no workspace)
+    // 256-row tiles: measured +5 % for N = 32 (conv1: twice the MFMAs per barrier), -3..-15 % for N = 64 (occupancy)
+    const bool big32 = f.splits == 1 && Mtot >= 256 * 2048;
+    const TileArgs t = f.cfg == 0 ? TileArgs{big32 ? 256 : 128, 32, 4, 1} : TileArgs{f.cfg == 1 ? 128 : 64, 64, 2, 2};
+    p.variant = mode; p.splits = f.splits; p.per_split = f.k_per_split;
+    p.grid = dim3(cdiv64(Mtot, t.BM), cdiv64(g.Cout, t.BN), (unsigned)f.splits);
+    p.t = t;
+    plan_kernel(p, K_CONV_FWD, "k_conv_fwd<%d, %d, %d, %d, %d>", t.BM, t.BN, t.WM, t.WN, mode);
+    return p;
+}
+
 extern "C" int64_t sf_conv_fwd_workspace(int64_t n, const sf_conv_desc *h_desc) {
     if (!h_desc || n <= 0) return 0;
     const int K = h_desc->KH * h_desc->KW * h_desc->Cin, N = h_desc->Cout;
@@ -941,38 +1131,34 @@ extern "C" int64_t sf_conv_fwd_workspace(int64_t n, const sf_conv_desc *h_desc) 
     return p.splits > 1 ? (int64_t)sizeof(float) * p.splits * Mtot * N + 256 : 0;
 }
 
-#define FWD_LAUNCH(BM, BN, WM, WN, MODE)                                                                   \
-    k_conv_fwd<BM, BN, WM, WN, MODE><<<dim3(cdiv64(Mtot, BM), cdiv64(g.Cout, BN), Z), dim3(256), 0, st>>>( \
-        g, in, in_sample_stride, index, offset, w, bias, out, Mtot, p.k_per_split, partial)
-#define FWD_BY_MODE(BM, BN, WM, WN)                                    \
-    do {                                                               \
-        if (mode == MODE_F32) FWD_LAUNCH(BM, BN, WM, WN, MODE_F32);    \
-        else if (mode == MODE_U8) FWD_LAUNCH(BM, BN, WM, WN, MODE_U8); \
-        else if (mode == MODE_F32F) FWD_LAUNCH(BM, BN, WM, WN, MODE_F32F); \
-        else if (mode == MODE_F32F_NORM) FWD_LAUNCH(BM, BN, WM, WN, MODE_F32F_NORM); \
-        else if (mode == MODE_U8_NORM) FWD_LAUNCH(BM, BN, WM, WN, MODE_U8_NORM); \
-        else FWD_LAUNCH(BM, BN, WM, WN, MODE_GENERIC);                 \
-    } while (0)
+#define TILE_IS(BM_, BN_) (p.t.BM == BM_ && p.t.BN == BN_)
+static void launch_splitk_finish(const float *partial, const float *bias, float *out, int64_t MN, const ConvG &g, int Z, hipStream_t st) {
+    k_splitk_finish<<<dim3(cdiv64(MN, 256) < 4096 ? cdiv64(MN, 256) : 4096), dim3(256), 0, st>>>(partial, bias, out, MN, g.Cout, Z, g.relu);
+}
+// the loader MODE of a plan as a template argument: L(..., MODE)
+#define BY_MODE(L, ...)                                                          \
+    switch (p.variant) {                                                         \
+        case MODE_F32: L(__VA_ARGS__, MODE_F32); break;                          \
+        case MODE_U8: L(__VA_ARGS__, MODE_U8); break;                            \
+        case MODE_F32F: L(__VA_ARGS__, MODE_F32F); break;                        \
+        case MODE_F32F_NORM: L(__VA_ARGS__, MODE_F32F_NORM); break;              \
+        case MODE_U8_NORM: L(__VA_ARGS__, MODE_U8_NORM); break;                  \
+        default: L(__VA_ARGS__, MODE_GENERIC);                                   \
+    }
+#define FWD_LAUNCH(BM, BN, WM, WN, MODE)                          \
+    k_conv_fwd<BM, BN, WM, WN, MODE><<<p.grid, p.block, 0, st>>>( \
+        g, in, in_sample_stride, index, offset, w, bias, out, Mtot, (int)p.per_split, partial)
 
 // ReLU sign-bit masks (sf_conv_fwd_relu_mask / sf_conv_wgrad_relu_mask): the layers whose forward AND weight-gradient
 // kernels can record / consume them — conv1 on raw u8 frames on the exact-product bf16 kernels, 32 output channels, ReLU.
 // SF_RELU_MASK=0 switches the path off (A/B: the data gradient below reads the activation again).
 static bool relu_mask_ok(const sf_conv_desc *d, int64_t n) {
-    static const int on = getenv("SF_RELU_MASK") ? atoi(getenv("SF_RELU_MASK")) : 1;
-    if (!on || !in_is_u8(d->in_u8) || d->relu != 1 || d->Cout != 32) return false;
-    const ConvG g = make_geom(d);
-    return conv1_bf16_ok(g, pick_mode(g), n);
+    if (!sw().relu_mask || !in_is_u8(d->in_u8) || d->relu != 1 || d->Cout != 32) return false;
+    const int k = plan_conv_fwd(d, make_geom(d), n, query_operands(d, false)).kernel;
+    return k == K_CONV1_U8_BF16 || k == K_CONV1_U8_BF16_W;
 }
 extern "C" int sf_conv_relu_mask_supported(int64_t n, const sf_conv_desc *h_desc) {
     return h_desc && n > 0 && check_desc(h_desc, "sf_conv_relu_mask_supported") == 0 && relu_mask_ok(h_desc, n) ? 1 : 0;
-}
-
-// vector loads of the activation operand also need aligned bases (f32: 16 bytes; u8 frames: 4 bytes; the normaliser's
-// tables of either frame format: 16 bytes)
-static bool act_aligned(const ConvG &g, const void *in, int64_t in_sample_stride) {
-    const bool tabs = !g.nmu || (((uintptr_t)g.nmu & 15) == 0 && ((uintptr_t)g.nrstd & 15) == 0);
-    if (in_is_u8(g.in_u8)) return ((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0 && tabs;
-    return ((uintptr_t)in & 15) == 0 && in_sample_stride % 4 == 0 && tabs;
 }
 
 // mu / rstd: the observation normaliser's tables (u8 / f32 frames through sf_conv_fwd_norm), else NULL
@@ -988,83 +1174,43 @@ static int conv_fwd_impl(const void *in, int64_t in_sample_stride, const int32_t
     g.nmu = mu; g.nrstd = rstd;
     const int64_t Mtot = n * g.OH * g.OW;
     SF_REQUIRE(Mtot < (1LL << 31), "sf_conv_fwd: M=%lld exceeds 2^31 rows; split the batch", (long long)Mtot);
-    int mode = pick_mode(g);
-    if (mode != MODE_GENERIC) {
-        if (!act_aligned(g, in, in_sample_stride) || ((uintptr_t)w & 15) != 0) mode = MODE_GENERIC;
-    }
+    const Operands o = {in, in_sample_stride, index != nullptr, w, nullptr, out, workspace ? workspace_bytes / (int64_t)sizeof(float) : 0};
+    const ConvPlan p = plan_conv_fwd(h_desc, g, n, o);
     hipStream_t st = STREAM(stream);
-    // Nature-CNN conv1 on raw frames: strip-image kernel (bytes converted once into an f32 LDS image, im2col read
-    // out of LDS).  Geometry contract of the <2,4,5,16> instantiation: K = 256, 2*4*OW rows = 10 fragments.
-    static const int img_on = getenv("SF_CONV1_IMG") ? atoi(getenv("SF_CONV1_IMG")) : 1;
-    // ... and on the bf16 matrix pipe with exact products (sf_nn_u8.h) when (pixel - mean) is an integer of <= 8 bits
-    if (conv1_bf16_ok(g, mode, n) && ((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0) {
-        // [SMP][Cin][RS][WP] bf16 strip image + (whole-line stores) the staging tile [SMP][80][36] f32
-        const unsigned img_bytes = 2u * 4u * 20u * (unsigned)SF_CONV1_WP * (unsigned)sizeof(uint16_t);
-        // persistent grid: SF_CONV1_WGS work-groups per CU (default 2 = what the register budget of __launch_bounds__(256, 2) admits)
-        static const int wgs_per_cu = getenv("SF_CONV1_WGS") ? atoi(getenv("SF_CONV1_WGS")) : 2;
-        static const int occ_dbg = getenv("SF_DEBUG_OCC") ? atoi(getenv("SF_DEBUG_OCC")) : 0;
-        if (occ_dbg)
-            fprintf(stderr, "k_conv1_u8_bf16 occupancy: %d (dword stores, %u B LDS) / %d (whole-line stores, %u B LDS) work-groups per CU\n",
-                    occupancy_of(k_conv1_u8_bf16<false>, 256, img_bytes), img_bytes,
-                    occupancy_of(k_conv1_u8_bf16_w<false>, 256, img_bytes + 2u * 80u * 36u * 4u), img_bytes + 2u * 80u * 36u * 4u);
-        const int64_t npairs = cdiv64(n, 2), resident = (int64_t)num_cus() * wgs_per_cu;
-        const unsigned grid_q = (unsigned)(npairs < resident ? npairs : resident);
-        // SF_CONV1_WIDE (default 1): whole-line output stores through an LDS staging tile (sf_nn_u8.h) — N == 32, aligned output
-        static const int wide_on = getenv("SF_CONV1_WIDE") ? atoi(getenv("SF_CONV1_WIDE")) : 1;
-        const bool wide = wide_on && g.Cout == 32 && ((uintptr_t)out & 15) == 0;
-        const unsigned lds_bytes = img_bytes + (wide ? 2u * 80u * 36u * (unsigned)sizeof(float) : 0u);
-#define CONV1_BF16_LAUNCH(KERN)                                                                                       \
-    KERN<<<dim3(grid_q), dim3(256), lds_bytes, st>>>(g, reinterpret_cast<const uint8_t *>(in), in_sample_stride, index, \
-                                                    offset, w, bias, out, relu_mask, (int)n)
-        if (g.sub_mean != 0.f) {
-            if (wide) CONV1_BF16_LAUNCH(k_conv1_u8_bf16_w<true>);
-            else CONV1_BF16_LAUNCH(k_conv1_u8_bf16<true>);
-        } else {
-            if (wide) CONV1_BF16_LAUNCH(k_conv1_u8_bf16_w<false>);
-            else CONV1_BF16_LAUNCH(k_conv1_u8_bf16<false>);
-        }
-#undef CONV1_BF16_LAUNCH
-        return sf_launch_status("sf_conv_fwd");
-    }
-    // only the kernel above records ReLU sign bits: every other path would leave the mask unwritten for the
+    const bool bf16 = p.kernel == K_CONV1_U8_BF16 || p.kernel == K_CONV1_U8_BF16_W;
+    // only the bf16 kernels record ReLU sign bits: every other path would leave the mask unwritten for the
     // weight-gradient kernel to consume (misaligned operands drop to MODE_GENERIC without it)
-    SF_REQUIRE(relu_mask == nullptr,
+    SF_REQUIRE(relu_mask == nullptr || bf16,
                "sf_conv_fwd_relu_mask: operands not eligible for the sign-bit kernel (sf_conv_relu_mask_supported, 4-byte "
                "aligned frames and sample stride, 16-byte aligned weights)");
-    if (img_on && conv1_img_ok(g, mode, n) && ((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0) {
-        const unsigned lds_bytes = (unsigned)(2 * 4 * 20 * 84 * sizeof(float));  // [SMP][Cin][RS][W] f32
-        // persistent work-groups: as many as are resident at once (two per CU: 53.8 KB of LDS each), each walks the
-        // sample pairs b, b + grid, ...
-        static int bpc = 0;
-        if (!bpc) {
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_conv_u8_img<2, 4, 5, 16, false>, 256, lds_bytes) !=
-                    hipSuccess || bpc < 1)
-                bpc = 2;
-            (void)hipGetLastError();
-        }
-        const int64_t npairs = cdiv64(n, 2);
-        const unsigned grid_img = (unsigned)(npairs < (int64_t)num_cus() * bpc ? npairs : (int64_t)num_cus() * bpc);
-        if (g.sub_mean != 0.f)
-            k_conv_u8_img<2, 4, 5, 16, true><<<dim3(grid_img), dim3(256), lds_bytes, st>>>(
-                g, reinterpret_cast<const uint8_t *>(in), in_sample_stride, index, offset, w, bias, out, (int)n);
-        else
-            k_conv_u8_img<2, 4, 5, 16, false><<<dim3(grid_img), dim3(256), lds_bytes, st>>>(
-                g, reinterpret_cast<const uint8_t *>(in), in_sample_stride, index, offset, w, bias, out, (int)n);
-        return sf_launch_status("sf_conv_fwd");
+    if (bf16 && sw().debug_occ) {
+        const unsigned img_bytes = 2u * 4u * 20u * (unsigned)SF_CONV1_WP * (unsigned)sizeof(uint16_t);
+        fprintf(stderr, "k_conv1_u8_bf16 occupancy: %d (dword stores, %u B LDS) / %d (whole-line stores, %u B LDS) work-groups per CU\n",
+                occupancy_of(k_conv1_u8_bf16<false>, 256, img_bytes), img_bytes,
+                occupancy_of(k_conv1_u8_bf16_w<false>, 256, img_bytes + 2u * 80u * 36u * 4u), img_bytes + 2u * 80u * 36u * 4u);
     }
-    const FwdPlan p = plan_fwd(Mtot, g.Cout, g.K, workspace ? workspace_bytes / (int64_t)sizeof(float) : 0);
+    const uint8_t *in8 = reinterpret_cast<const uint8_t *>(in);
     float *partial = p.splits > 1 ? reinterpret_cast<float *>(workspace) : nullptr;
-    const unsigned Z = (unsigned)p.splits;
-    // 256-row tiles: measured +5 % for N = 32 (conv1: twice the MFMAs per barrier), -3..-15 % for N = 64 (occupancy)
-    const bool big32 = p.splits == 1 && Mtot >= 256 * 2048;
-    if (p.cfg == 0) { if (big32) FWD_BY_MODE(256, 32, 4, 1); else FWD_BY_MODE(128, 32, 4, 1); }
-    else if (p.cfg == 1) FWD_BY_MODE(128, 64, 2, 2);
-    else FWD_BY_MODE(64, 64, 2, 2);
-    if (partial) {
-        const int64_t MN = Mtot * g.Cout;
-        k_splitk_finish<<<dim3(cdiv64(MN, 256) < 4096 ? cdiv64(MN, 256) : 4096), dim3(256), 0, st>>>(
-            partial, bias, out, MN, g.Cout, p.splits, g.relu);
+#define CONV1_LAUNCH(KERN, ...) \
+    KERN<<<p.grid, p.block, p.lds, st>>>(g, in8, in_sample_stride, index, offset, w, bias, out, ##__VA_ARGS__, (int)n)
+    switch (p.kernel) {
+        case K_CONV1_U8_BF16_W:
+            if (p.variant) CONV1_LAUNCH(k_conv1_u8_bf16_w<true>, relu_mask); else CONV1_LAUNCH(k_conv1_u8_bf16_w<false>, relu_mask);
+            break;
+        case K_CONV1_U8_BF16:
+            if (p.variant) CONV1_LAUNCH(k_conv1_u8_bf16<true>, relu_mask); else CONV1_LAUNCH(k_conv1_u8_bf16<false>, relu_mask);
+            break;
+        case K_CONV_U8_IMG:
+            if (p.variant) CONV1_LAUNCH((k_conv_u8_img<2, 4, 5, 16, true>)); else CONV1_LAUNCH((k_conv_u8_img<2, 4, 5, 16, false>));
+            break;
+        default:  // K_CONV_FWD
+            if (TILE_IS(256, 32)) { BY_MODE(FWD_LAUNCH, 256, 32, 4, 1) }
+            else if (TILE_IS(128, 32)) { BY_MODE(FWD_LAUNCH, 128, 32, 4, 1) }
+            else if (TILE_IS(128, 64)) { BY_MODE(FWD_LAUNCH, 128, 64, 2, 2) }
+            else { BY_MODE(FWD_LAUNCH, 64, 64, 2, 2) }
+            if (partial) launch_splitk_finish(partial, bias, out, Mtot * g.Cout, g, p.splits, st);
     }
+#undef CONV1_LAUNCH
     return sf_launch_status("sf_conv_fwd");
 }
 
@@ -1094,34 +1240,21 @@ extern "C" int sf_conv_fwd_relu_mask(const void *in, int64_t in_sample_stride, c
 #define SF_IMG_TMF 2  // 16-row fragments per wave and block step of the conv3 LDS-image forward (experiment switch)
 #endif
 #define IMG_FWD_GEOMS(X) X(64, 9, 9, 3, 1, SF_IMG_TMF, 1, 7)
-static int img_fwd_index(const ConvG &g, int64_t n) {
-    static const int on = getenv("SF_FWD_IMG") ? atoi(getenv("SF_FWD_IMG")) : 1;
-    if (!on || g.Cout != 64 || g.KH != g.KW || n < 512) return -1;
+// index into IMG_FWD_GEOMS (-1: none); fills the plan's grid (persistent: as many work-groups as fit on the chip at once)
+static int plan_img_fwd(ConvPlan &p, const ConvG &g, int64_t n) {
+    if (!sw().fwd_img || g.Cout != 64 || g.KH != g.KW || n < 512) return -1;
     int idx = 0;
-#define X(CIN, HH, WW, KS, ST, TMF, WS, R)                                                       \
-    if (g.Cin == CIN && g.H == HH && g.W == WW && g.KH == KS && g.S == ST) return idx;           \
+#define X(CIN, HH, WW, KS, ST, TMF, WS, R)                                                                         \
+    if (g.Cin == CIN && g.H == HH && g.W == WW && g.KH == KS && g.S == ST) {                                       \
+        static const int bpc = occupancy_of(k_fwd_img<CIN, HH, WW, KS, ST, TMF, WS, R>, 256 * WS);                 \
+        p.variant = idx; p.grid = dim3(num_cus() * (bpc > 0 ? bpc : 1)); p.block = dim3(256 * WS);                 \
+        plan_kernel(p, K_FWD_IMG, "k_fwd_img<%d, %d, %d, %d, %d, %d, %d, %d>", CIN, HH, WW, KS, ST, TMF, WS, R);   \
+        return idx;                                                                                                \
+    }                                                                                                              \
     ++idx;
     IMG_FWD_GEOMS(X)
 #undef X
     return -1;
-}
-static bool launch_img_fwd(const ConvG &g, const float *in, int64_t in_stride, const float *wt, const float *bias,
-                           float *out, int64_t n, hipStream_t st) {
-    const int which = img_fwd_index(g, n);
-    if (which < 0) return false;
-    int idx = 0;
-#define X(CIN, HH, WW, KS, ST, TMF, WS, R)                                                                           \
-    if (which == idx) {                                                                                              \
-        /* persistent: as many work-groups as fit on the chip at once */                                            \
-        static const int bpc = occupancy_of(k_fwd_img<CIN, HH, WW, KS, ST, TMF, WS, R>, 256 * WS);                      \
-        if (getenv("SF_DEBUG_IMG")) fprintf(stderr, "k_fwd_img R=%d: %d work-groups per CU\n", R, bpc);                 \
-        k_fwd_img<CIN, HH, WW, KS, ST, TMF, WS, R><<<dim3(num_cus() * (bpc > 0 ? bpc : 1)), dim3(256 * WS), 0, st>>>(   \
-            in, in_stride, wt, bias, out, (int)n, g.relu);                                                           \
-    }                                                                                                                \
-    ++idx;
-    IMG_FWD_GEOMS(X)
-#undef X
-    return true;
 }
 
 // ---- glds forward (pre-transposed weights)
@@ -1139,168 +1272,167 @@ struct GldsFwdPlan {
     bool ok, wide, sq64;  // sq64: 64x64 tiles, unsplit
     int Z, k_per_split;
 };
+// slices of a reduction of K >= 1024 that turn `tiles` work-groups into about `want`: at least 8 chunks of 32 per slice, at
+// most 16 slices (so more than one slice asked for is more than one slice made); returns Z and sets k_per_split
+static int split_k(int K, int64_t want, int64_t tiles, int *k_per_split) {
+    int z = (int)((want + tiles - 1) / tiles);
+    z = z > K / 256 ? K / 256 : z;
+    z = z > 16 ? 16 : z;
+    if (z <= 1) return 1;
+    *k_per_split = (((K + 31) / 32 + z - 1) / z) * 32;
+    return (K + *k_per_split - 1) / *k_per_split;
+}
 static GldsFwdPlan plan_fwd_t(int64_t Mtot, int N, int K) {
-    static const int cfg = getenv("SF_GLDS_CFG") ? atoi(getenv("SF_GLDS_CFG")) : 0;
-    static const int split_on = getenv("SF_GLDS_SPLITK") ? atoi(getenv("SF_GLDS_SPLITK")) : 1;
+    const Switches &s = sw();
     static const int occ64 = occupancy_of(k_fwd_glds<128, 64, 2, 2, 2>), occ128 = occupancy_of(k_fwd_glds<128, 128, 2, 2, 2>);
     GldsFwdPlan p;
     p.ok = false; p.wide = false; p.sq64 = false; p.Z = 1; p.k_per_split = (K + 31) / 32 * 32;
-    static const int fc64 = getenv("SF_GLDS_FC64") ? atoi(getenv("SF_GLDS_FC64")) : 1;
     const int64_t t64 = cdiv64(Mtot, 128) * (int64_t)cdiv64(N, 64), t128 = cdiv64(Mtot, 128) * (int64_t)cdiv64(N, 128);
-    // (wide outputs of moderate height — the recurrent projection of one rollout step, 2048 x 512 x 2048: 512 tiles,
-    //  two per CU — also beat the register-staged kernel: 75 -> measured in profiles/r02_c5_*; the GRU's 2048 x 512 x
-    //  1536 is 384 tiles)
-    static const int wide_min = getenv("SF_GLDS_WIDE_MIN") ? atoi(getenv("SF_GLDS_WIDE_MIN")) : 384;
+    // SF_GLDS_WIDE_MIN (default 384): wide outputs of moderate height — the recurrent projection of one rollout step,
+    // 2048 x 512 x 2048: 512 tiles, two per CU — also beat the register-staged kernel: 75 -> measured in
+    // profiles/r02_c5_*; the GRU's 2048 x 512 x 1536 is 384 tiles.
     // Launches of a few hundred tiles — the per-split inference launches of a host-env run: conv2 at n = 512 is 324 tiles
     // of 128 x 64, the fc layer 4 x 8 tiles of 64 x 64 — used to fall to the register-staged kernel.  Measured at
     // n = 512 / 1024 (profiles/r05_b_kbench_small_n.log): conv2 47.6 / 84.3 us there, 40.1 / 61.4 us on 128 x 64 LDS-DMA
     // tiles, 34.4 / 61.7 us on 64 x 64 tiles (SF_GLDS_SMALL64 = rows/64 from which they are used; 0 = off); the fc layer
     // 170 / 52 us -> 26 / 39 us on 64 x 64 tiles split along K (SF_GLDS_SPLIT64 below).  SF_GLDS_MIN_TILES: 128 x 64
-    // tiles from which the unsplit 128-row plan is used (unchanged: 768).
-    static const int min_tiles = getenv("SF_GLDS_MIN_TILES") ? atoi(getenv("SF_GLDS_MIN_TILES")) : 768;
-    static const int small64 = getenv("SF_GLDS_SMALL64") ? atoi(getenv("SF_GLDS_SMALL64")) : 256;
-    static const int force64 = getenv("SF_GLDS_FORCE64") ? atoi(getenv("SF_GLDS_FORCE64")) : 0;  // experiment switch
-    if (force64 && N == 64 && t64 <= force64) { p.ok = true; p.sq64 = true; return p; }
-    if (small64 && t64 < 768 && N == 64 && K >= 256 && cdiv64(Mtot, 64) >= small64) {
+    // tiles from which the unsplit 128-row plan is used (unchanged: 768).  SF_GLDS_FORCE64: experiment switch.
+    if (s.glds_force64 && N == 64 && t64 <= s.glds_force64) { p.ok = true; p.sq64 = true; return p; }
+    if (s.glds_small64 && t64 < 768 && N == 64 && K >= 256 && cdiv64(Mtot, 64) >= s.glds_small64) {
         p.ok = true; p.sq64 = true;  // narrow layer, few rows: 64-row tiles double the work-groups on the chip
         return p;
     }
-    if (t64 >= min_tiles || (t64 >= wide_min && N >= 512 && K >= 256)) {
+    if (t64 >= s.glds_min_tiles || (t64 >= s.glds_wide_min && N >= 512 && K >= 256)) {
         p.ok = true;
-        if (N >= 128 && cfg == 0) {  // efficiency = rounds / ceil(rounds) with the kernel's own occupancy
+        if (N >= 128 && s.glds_cfg == 0) {  // efficiency = rounds / ceil(rounds) with the kernel's own occupancy
             const double u64 = (double)t64 / (256.0 * occ64), u128 = (double)t128 / (256.0 * occ128);
             const double e64 = u64 / (double)(int64_t)(u64 + 0.999999), e128 = u128 / (double)(int64_t)(u128 + 0.999999);
             p.wide = e128 * 1.03 >= e64;  // 64x64 wave tiles: fewer LDS reads and DMA instructions per MFMA
         }
-        if (cfg == 2) p.wide = true;
+        if (s.glds_cfg == 2) p.wide = true;
         return p;
     }
-    if (fc64 == 1 && N >= 128 && K >= 1024 && cdiv64(Mtot, 64) * (int64_t)cdiv64(N, 64) >= 512) {
+    if (s.glds_fc64 == 1 && N >= 128 && K >= 1024 && cdiv64(Mtot, 64) * (int64_t)cdiv64(N, 64) >= 512) {
         p.ok = true; p.sq64 = true;  // two 64x64 work-groups per CU, the whole reduction in one pass, no partial sums
         return p;
     }
     // a wide layer on very few rows (the fc layer of a 512-sample inference launch: 4 x 8 tiles of 64 x 64): 64 x 64
     // tiles split along K until ~2 work-groups per CU exist.  SF_GLDS_SPLIT64=<min 64x64 tiles> (0 = off)
-    static const int split64 = getenv("SF_GLDS_SPLIT64") ? atoi(getenv("SF_GLDS_SPLIT64")) : 32;
     const int64_t t6464 = cdiv64(Mtot, 64) * (int64_t)cdiv64(N, 64);
-    if (split64 && split_on && N >= 128 && K >= 1024 && t6464 >= split64 && t6464 < 512) {
-        int z = (int)((512 + t6464 - 1) / t6464);
-        const int zmax = K / 256;
-        z = z > zmax ? zmax : z;
-        z = z > 16 ? 16 : z;
-        if (z > 1) {
-            const int chunks = (K + 31) / 32;
-            p.k_per_split = ((chunks + z - 1) / z) * 32;
-            p.Z = (K + p.k_per_split - 1) / p.k_per_split;
-            if (p.Z > 1) {
-                p.ok = true; p.sq64 = true;
-                return p;
-            }
-            p.Z = 1; p.k_per_split = (K + 31) / 32 * 32;
-        }
+    if (s.glds_split64 && s.glds_splitk && N >= 128 && K >= 1024 && t6464 >= s.glds_split64 && t6464 < 512) {
+        p.Z = split_k(K, 512, t6464, &p.k_per_split);
+        if (p.Z > 1) { p.ok = true; p.sq64 = true; return p; }
     }
-    if (split_on && N >= 128 && K >= 1024 && t128 >= 32) {
-        const int slots = 256 * occ128;
-        int z = (int)((slots + t128 - 1) / t128);
-        const int zmax = K / 256;  // >= 8 chunks per slice
-        z = z > zmax ? zmax : z;
-        z = z > 16 ? 16 : z;
-        if (z > 1) {
-            const int chunks = (K + 31) / 32;
-            p.k_per_split = ((chunks + z - 1) / z) * 32;
-            p.Z = (K + p.k_per_split - 1) / p.k_per_split;
-            p.ok = p.Z > 1;
-            p.wide = true;
-        }
+    if (s.glds_splitk && N >= 128 && K >= 1024 && t128 >= 32) {
+        p.Z = split_k(K, 256 * occ128, t128, &p.k_per_split);
+        p.ok = p.wide = p.Z > 1;
     }
     return p;
 }
+static bool linear_1x1(const sf_conv_desc *d) {
+    return d->in_u8 == IN_F32_NHWC && d->traj_T == 0 && d->KH == 1 && d->KW == 1 && d->H == 1 && d->W == 1;
+}
 static bool small_linear_wgrad_ok(const sf_conv_desc *d) {
-    static const int on = getenv("SF_LINEAR_NARROW") ? atoi(getenv("SF_LINEAR_NARROW")) : 1;
-    return on && d->in_u8 == IN_F32_NHWC && d->traj_T == 0 && d->KH == 1 && d->KW == 1 && d->H == 1 && d->W == 1 && d->Cout <= 64 &&
-           d->Cin <= 64;
+    return sw().linear_narrow && linear_1x1(d) && d->Cout <= 64 && d->Cin <= 64;
 }
 // narrow linear layers (the heads): one wave per 16 rows, operands straight from memory (sf_nn_narrow.h)
 static bool narrow_fwd_ok(const sf_conv_desc *d, int64_t n) {
-    static const int on = getenv("SF_LINEAR_NARROW") ? atoi(getenv("SF_LINEAR_NARROW")) : 1;
-    return on && d->in_u8 == IN_F32_NHWC && d->traj_T == 0 && d->KH == 1 && d->KW == 1 && d->H == 1 && d->W == 1 && d->Cout <= 32 &&
-           d->Cin % 16 == 0 && n < (1 << 30);
+    return sw().linear_narrow && linear_1x1(d) && d->Cout <= 32 && d->Cin % 16 == 0 && n < (1 << 30);
 }
-extern "C" int sf_conv_fwd_t_supported(int64_t n, const sf_conv_desc *h_desc) {
-    if (h_desc && n > 0 && narrow_fwd_ok(h_desc, n)) return 1;
-    if (!h_desc || n <= 0 || !glds_fwd_ok(h_desc)) return 0;
-    // small grids keep the split-K register-staged kernel (a 128-row tile grid must fill 256 CUs a few times over)
-    const int64_t Mtot = n * h_desc->OH * h_desc->OW;
-    if (img_fwd_index(make_geom(h_desc), n) >= 0) return 1;
-    return plan_fwd_t(Mtot, h_desc->Cout, h_desc->KH * h_desc->KW * h_desc->Cin).ok ? 1 : 0;
+// SF_GLDS_TAILSPLIT (default 1): single-column unsplit 128 x 64 launches go through k_fwd_glds_zt, which runs a last round of
+// work-groups that is at most half full as 64-row tiles.  Returns the number of 128-row tiles in front of that round (all of
+// them when there is nothing to split), 0 = not such a launch (k_fwd_glds_z / k_fwd_glds).
+static int fwd_tail_split(const ConvG &g, int64_t Mtot, int Z, bool zl_ok) {
+    if (!sw().glds_tailsplit || !zl_ok || sw().glds_zl < 1 || Z != 1 || g.Cout > 64 || sw().xcd_rows) return 0;
+    static const int occ = occupancy_of(k_fwd_glds_zt<128, 64, 2, 2>, 256, (128 + 64) * 32 * 2 * sizeof(float));
+    const int64_t tiles = cdiv64(Mtot, 128), resident = (int64_t)num_cus() * occ, tail = tiles % resident;
+    if (tiles <= resident || tail == 0 || 2 * tail > resident) return (int)tiles;
+    return (int)(tiles - tail);
 }
-extern "C" int64_t sf_conv_fwd_t_workspace(int64_t n, const sf_conv_desc *h_desc) {
-    if (!h_desc || n <= 0 || narrow_fwd_ok(h_desc, n) || !glds_fwd_ok(h_desc)) return 0;
-    const int64_t Mtot = n * h_desc->OH * h_desc->OW;
-    if (img_fwd_index(make_geom(h_desc), n) >= 0) return 0;
-    const GldsFwdPlan p = plan_fwd_t(Mtot, h_desc->Cout, h_desc->KH * h_desc->KW * h_desc->Cin);
-    return p.ok && p.Z > 1 ? (int64_t)sizeof(float) * p.Z * Mtot * h_desc->Cout + 256 : 0;
-}
-// (XCD-aware block order of the launches with more than one column tile: sf_nn_glds.h; SF_XCD_RASTER=0 switches it off)
-static int xcd_raster_on() {
-    static const int on = getenv("SF_XCD_RASTER") ? atoi(getenv("SF_XCD_RASTER")) : 1;
-    return on;
-}
+// Switches of the LDS-DMA forward launch:
+// SF_XCD_RASTER (default 1; 0 = off): XCD-aware block order of the launches with more than one column tile (sf_nn_glds.h).
 // SF_XCD_ROWS=1: the same re-mapping for launches with ONE column tile (conv2's forward): XCD c then owns a contiguous run
 // of row tiles, so the image rows two neighbouring tiles share (a sample straddling a tile boundary, the 2-row halo of the
-// 4x4 stride-2 window) are fetched into one L2 instead of two
-static int xcd_rows_on() {
-    static const int on = getenv("SF_XCD_ROWS") ? atoi(getenv("SF_XCD_ROWS")) : 0;
-    return on;
-}
+// 4x4 stride-2 window) are fetched into one L2 instead of two.
 // SF_GLDS_ZL (default 2; 1 = wave tiles of at most two 32x32 blocks only, 0 = off): the LDS-DMA forward with no vector-ALU
 // instruction in its k-loop (k_fwd_glds_z, sf_nn_glds.h).  Measured (profiles/r05_k_zl_ab.log, r05_k_zl128_ab.log, same box,
 // alternating): conv2 forward 213 / 218 -> 192 / 195 us at n = 4096, 1491 / 1507 -> 1413 / 1406 us at n = 32768; fc forward
 // of a rollout step (64 x 64 tiles) 110 / 113 -> 105 / 104 us; fc forward at n = 32768 (128 x 128 tiles) 832 / 837 -> 802 / 811 us.
-static int glds_zl_on() {
-    static const int on = getenv("SF_GLDS_ZL") ? atoi(getenv("SF_GLDS_ZL")) : 2;
-    return on;
-}
 // SF_TAP_PERM=1 (default 0): conv2's forward visits its 16 filter taps in groups of the four taps that read the same input
 // elements (k_fwd_glds, sf_nn_glds.h).  Measured (profiles/r05_h_*): counter traffic of the dominant kernel 805.6 -> 544.1 MB
 // per launch (1.56 -> 1.05 x algorithmic), launch time 1573 / 1591 vs 1591 / 1597 us at n = 32768 — the re-reads were being
 // served by the Infinity Cache, so the time does not move.  It is a different fp32 summation order, though, and the
 // normalised-input replay (train_cnn84_norm: inputs up to +-5, two SGD steps) lands on other ReLU flips with it and leaves the
 // tolerance the replays are held to (profiles/r05_m_norm_bisect.log); with no time to gain, the natural order stays.
-static int tap_perm_on() {
-    static const int on = getenv("SF_TAP_PERM") ? atoi(getenv("SF_TAP_PERM")) : 0;
-    return on;
+// SF_GLDS_TALL=<min 256-row tiles> (experiment): 256 x 64 tiles (waves 4 x 1, 64 x 64 wave tiles) for 64-column layers with
+// many rows — half the per-tile fixed cost and a sixth less DMA per flop, at two work-groups per CU instead of three.
+// SF_GLDS_PERSIST=1 (experiment): persistent row-tile walk (k_fwd_glds_zp).
+static ConvPlan plan_conv_fwd_t(const sf_conv_desc *d, int64_t n, int64_t in_sample_stride, ConvG *g_out = nullptr) {
+    ConvPlan p = plan_init();
+    if (narrow_fwd_ok(d, n)) {
+        p.recommended = true; p.variant = d->Cout <= 16 ? 1 : 2;
+        p.grid = dim3((unsigned)cdiv64(n, 16)); p.block = dim3(64);
+        plan_kernel(p, K_LINEAR_NARROW, "k_linear_narrow<%d>", p.variant);
+        return p;
+    }
+    if (!glds_fwd_ok(d)) return p;
+    const ConvG g = make_geom(d);
+    if (g_out) *g_out = g;
+    const int64_t Mtot = n * g.OH * g.OW;
+    if (n * in_sample_stride < ((int64_t)1 << 40) && plan_img_fwd(p, g, n) >= 0) { p.recommended = true; return p; }
+    // small grids keep the split-K register-staged kernel (a 128-row tile grid must fill 256 CUs a few times over)
+    GldsFwdPlan q = plan_fwd_t(Mtot, g.Cout, g.K);
+    p.recommended = q.ok;
+    if (!q.ok) { q.Z = 1; q.k_per_split = (g.K + 31) / 32 * 32; }  // not a grid sf_conv_fwd_t_supported recommends: still correct, one unsplit launch
+    p.splits = q.Z; p.per_split = q.k_per_split;
+    // zero-VALU k-loop form (k_fwd_glds_z): every per-lane operand offset must fit 32 bits
+    const bool zl_ok = sw().glds_zl && (n - 1) * in_sample_stride + (int64_t)g.H * g.W * g.Cin < (1LL << 30) &&
+                       (int64_t)g.Cout * g.K < (1LL << 30);
+    const bool col64 = !q.sq64 && !q.wide && q.Z == 1 && g.Cout <= 64 && zl_ok;
+    if (sw().glds_persist && col64) {
+        static const int occp = occupancy_of(k_fwd_glds_zp<128, 64, 2, 2>);
+        const int64_t tiles = cdiv64(Mtot, 128), slots = (int64_t)num_cus() * occp;
+        p.grid = dim3((unsigned)(tiles < slots ? tiles : slots));
+        plan_tile(p, K_FWD_GLDS_ZP, "k_fwd_glds_zp", TileArgs{128, 64, 2, 2});
+        return p;
+    }
+    if (sw().glds_tall && col64 && cdiv64(Mtot, 256) >= (unsigned)sw().glds_tall) {
+        p.grid = dim3(cdiv64(Mtot, 256), 1, 1);
+        plan_tile(p, K_FWD_GLDS_Z, "k_fwd_glds_z", TileArgs{256, 64, 4, 1});
+        return p;
+    }
+    if (!q.sq64 && !q.wide) {
+        p.main_tiles = fwd_tail_split(g, Mtot, q.Z, zl_ok);
+        if (p.main_tiles > 0) {
+            const int tail = (int)cdiv64(Mtot, 128) - p.main_tiles;
+            p.grid = dim3((unsigned)(p.main_tiles + 2 * tail));
+            p.lds = (128 + 64) * 32 * 2 * sizeof(float);
+            plan_tile(p, K_FWD_GLDS_ZT, "k_fwd_glds_zt", TileArgs{128, 64, 2, 2});
+            return p;
+        }
+    }
+    const TileArgs t = q.sq64 ? TileArgs{64, 64, 2, 2} : q.wide ? TileArgs{128, 128, 2, 2} : TileArgs{128, 64, 2, 2};
+    p.grid = dim3(cdiv64(Mtot, t.BM), cdiv64(g.Cout, t.BN), (unsigned)q.Z);
+    plan_raster(p, sw().xcd_raster && (p.grid.y > 1 || (sw().xcd_rows && p.grid.x >= 64)));
+    // wave tiles of more than two 32x32 blocks (128 x 128) take the _z form from SF_GLDS_ZL=2 on
+    if (zl_ok && ((t.BM / t.WM / 32) * (t.BN / t.WN / 32) <= 2 || sw().glds_zl >= 2)) plan_tile(p, K_FWD_GLDS_Z, "k_fwd_glds_z", t);
+    else plan_tile(p, K_FWD_GLDS, "k_fwd_glds", t, ", 2");
+    return p;
 }
-// SF_GLDS_TAILSPLIT (default 1): single-column unsplit 128 x 64 launches go through k_fwd_glds_zt, which runs a last round of
-// work-groups that is at most half full as 64-row tiles.  Returns the number of 128-row tiles in front of that round (all of
-// them when there is nothing to split), 0 = not such a launch (k_fwd_glds_z / k_fwd_glds).
-static int fwd_tail_split(const ConvG &g, int64_t Mtot, int Z, bool zl_ok) {
-    static const int on = getenv("SF_GLDS_TAILSPLIT") ? atoi(getenv("SF_GLDS_TAILSPLIT")) : 1;
-    if (!on || !zl_ok || glds_zl_on() < 1 || Z != 1 || g.Cout > 64 || xcd_rows_on()) return 0;
-    static const int occ = occupancy_of(k_fwd_glds_zt<128, 64, 2, 2>, 256, (128 + 64) * 32 * 2 * sizeof(float));
-    const int64_t tiles = cdiv64(Mtot, 128), resident = (int64_t)num_cus() * occ, tail = tiles % resident;
-    if (tiles <= resident || tail == 0 || 2 * tail > resident) return (int)tiles;
-    return (int)(tiles - tail);
+extern "C" int sf_conv_fwd_t_supported(int64_t n, const sf_conv_desc *h_desc) {
+    return h_desc && n > 0 && plan_conv_fwd_t(h_desc, n, query_operands(h_desc, false).stride).recommended ? 1 : 0;
 }
-#define GLDS_FWD(BM, BN, WM, WN, NS)                                                                           \
-    do {                                                                                                       \
-        dim3 gq(cdiv64(Mtot, BM), cdiv64(g.Cout, BN), p.Z);                                                    \
-        const int rx = (int)gq.x, ry = (int)gq.y,                                                               \
-                  rtot = (xcd_raster_on() && (gq.y > 1 || (xcd_rows_on() && gq.x >= 64))) ? (int)(gq.x * gq.y * gq.z) : 0; \
-        if (rtot > 0) gq = dim3((unsigned)(8 * ((rtot + 7) / 8)), 1, 1);                                        \
-        bool launched_z = false;                                                                               \
-        {                                                                                                      \
-            if (zl_ok && ((BM / WM / 32) * (BN / WN / 32) <= 2 || glds_zl_on() >= 2)) {                        \
-                k_fwd_glds_z<BM, BN, WM, WN><<<gq, dim3(256), 0, st>>>(                                        \
-                    g, in, in_sample_stride, wt, bias, out, Mtot, p.k_per_split, partial, nullptr, 0, rx, ry,  \
-                    rtot, tap_perm_on());                                                                      \
-                launched_z = true;                                                                             \
-            }                                                                                                  \
-        }                                                                                                      \
-        if (!launched_z)                                                                                       \
-        k_fwd_glds<BM, BN, WM, WN, NS><<<gq, dim3(256), 0, st>>>(                                              \
-            g, in, in_sample_stride, wt, bias, out, Mtot, p.k_per_split, partial, nullptr, 0, rx, ry, rtot,    \
-            tap_perm_on());                                                                                    \
+extern "C" int64_t sf_conv_fwd_t_workspace(int64_t n, const sf_conv_desc *h_desc) {
+    if (!h_desc || n <= 0) return 0;
+    const ConvPlan p = plan_conv_fwd_t(h_desc, n, query_operands(h_desc, false).stride);
+    return p.splits > 1 ? (int64_t)sizeof(float) * p.splits * n * h_desc->OH * h_desc->OW * h_desc->Cout + 256 : 0;
+}
+#define GLDS_FWD_ARGS \
+    g, in, in_sample_stride, wt, bias, out, Mtot, (int)p.per_split, partial, nullptr, 0, p.rx, p.ry, p.rtot, sw().tap_perm
+#define GLDS_FWD(BM, BN, WM, WN)                                                                            \
+    do {                                                                                                    \
+        if (p.kernel == K_FWD_GLDS_Z) k_fwd_glds_z<BM, BN, WM, WN><<<p.grid, p.block, 0, st>>>(GLDS_FWD_ARGS); \
+        else k_fwd_glds<BM, BN, WM, WN, 2><<<p.grid, p.block, 0, st>>>(GLDS_FWD_ARGS);                      \
     } while (0)
 extern "C" int sf_conv_fwd_t(const float *in, int64_t in_sample_stride, const float *wt, const float *bias, float *out,
                              int64_t n, const sf_conv_desc *h_desc, void *workspace, int64_t workspace_bytes,
@@ -1310,71 +1442,57 @@ extern "C" int sf_conv_fwd_t(const float *in, int64_t in_sample_stride, const fl
     SF_REQUIRE(in && wt && out && n > 0, "sf_conv_fwd_t: bad args");
     SF_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)wt & 15) == 0 && in_sample_stride % 4 == 0,
                "sf_conv_fwd_t: operands must be 16-byte aligned");
-    if (narrow_fwd_ok(h_desc, n)) {
-        const dim3 grid((unsigned)cdiv64(n, 16)), block(64);
-        if (h_desc->Cout <= 16)
-            k_linear_narrow<1><<<grid, block, 0, STREAM(stream)>>>(in, in_sample_stride, wt, bias, out, (int)n, h_desc->Cout,
-                                                                    h_desc->Cin, h_desc->relu);
-        else
-            k_linear_narrow<2><<<grid, block, 0, STREAM(stream)>>>(in, in_sample_stride, wt, bias, out, (int)n, h_desc->Cout,
-                                                                    h_desc->Cin, h_desc->relu);
+    ConvG g;
+    const ConvPlan p = plan_conv_fwd_t(h_desc, n, in_sample_stride, &g);
+    hipStream_t st = STREAM(stream);
+    if (p.kernel == K_LINEAR_NARROW) {
+#define NARROW_ARGS in, in_sample_stride, wt, bias, out, (int)n, h_desc->Cout, h_desc->Cin, h_desc->relu
+        if (p.variant == 1) k_linear_narrow<1><<<p.grid, p.block, 0, st>>>(NARROW_ARGS);
+        else k_linear_narrow<2><<<p.grid, p.block, 0, st>>>(NARROW_ARGS);
+#undef NARROW_ARGS
         return sf_launch_status("sf_conv_fwd_t");
     }
     SF_REQUIRE(glds_fwd_ok(h_desc), "sf_conv_fwd_t: needs f32 NHWC input with Cin %% 32 == 0 (use sf_conv_fwd)");
-    const ConvG g = make_geom(h_desc);
     const int64_t Mtot = n * g.OH * g.OW;
     SF_REQUIRE(Mtot < (1LL << 31), "sf_conv_fwd_t: M=%lld exceeds 2^31 rows; split the batch", (long long)Mtot);
-    if (n * in_sample_stride < ((int64_t)1 << 40) && launch_img_fwd(g, in, in_sample_stride, wt, bias, out, n, STREAM(stream)))
-        return sf_launch_status("sf_conv_fwd_t");
-    GldsFwdPlan p = plan_fwd_t(Mtot, g.Cout, g.K);
-    if (!p.ok) {  // not a grid sf_conv_fwd_t_supported recommends: still correct, one unsplit launch
-        p.Z = 1;
-        p.k_per_split = (g.K + 31) / 32 * 32;
-    }
     float *partial = nullptr;
-    if (p.Z > 1) {
+    if (p.splits > 1) {
         SF_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 &&
-                       workspace_bytes >= (int64_t)sizeof(float) * p.Z * Mtot * g.Cout,
+                       workspace_bytes >= (int64_t)sizeof(float) * p.splits * Mtot * g.Cout,
                    "sf_conv_fwd_t: this launch is split along K and needs sf_conv_fwd_t_workspace() bytes of workspace");
         partial = reinterpret_cast<float *>(workspace);
     }
-    hipStream_t st = STREAM(stream);
-    // zero-VALU k-loop form (k_fwd_glds_z): every per-lane operand offset must fit 32 bits
-    const bool zl_ok = glds_zl_on() && (n - 1) * in_sample_stride + (int64_t)g.H * g.W * g.Cin < (1LL << 30) &&
-                       (int64_t)g.Cout * g.K < (1LL << 30);
-    // SF_GLDS_TALL=<min 256-row tiles> (experiment): 256 x 64 tiles (waves 4 x 1, 64 x 64 wave tiles) for 64-column layers with
-    // many rows — half the per-tile fixed cost and a sixth less DMA per flop, at two work-groups per CU instead of three
-    static const int tall = getenv("SF_GLDS_TALL") ? atoi(getenv("SF_GLDS_TALL")) : 0;
-    static const int persist = getenv("SF_GLDS_PERSIST") ? atoi(getenv("SF_GLDS_PERSIST")) : 0;
-    if (persist && !p.sq64 && !p.wide && p.Z == 1 && g.Cout <= 64 && zl_ok) {  // experiment: persistent row-tile walk
-        static const int occp = occupancy_of(k_fwd_glds_zp<128, 64, 2, 2>);
-        const int64_t tiles = cdiv64(Mtot, 128), slots = (int64_t)num_cus() * occp;
-        k_fwd_glds_zp<128, 64, 2, 2><<<dim3((unsigned)(tiles < slots ? tiles : slots)), dim3(256), 0, st>>>(
-            g, in, in_sample_stride, wt, bias, out, Mtot, p.k_per_split);
-    } else
-    if (tall && !p.sq64 && !p.wide && p.Z == 1 && g.Cout <= 64 && cdiv64(Mtot, 256) >= tall && zl_ok) {
-        dim3 gq(cdiv64(Mtot, 256), 1, 1);
-        k_fwd_glds_z<256, 64, 4, 1><<<gq, dim3(256), 0, st>>>(g, in, in_sample_stride, wt, bias, out, Mtot, p.k_per_split,
-                                                                nullptr, nullptr, 0, 0, 0, 0, tap_perm_on());
-    } else
-    if (p.sq64) GLDS_FWD(64, 64, 2, 2, 2);
-    else if (p.wide) GLDS_FWD(128, 128, 2, 2, 2);
-    else if (const int main_tiles = fwd_tail_split(g, Mtot, p.Z, zl_ok); main_tiles > 0) {
-        const int tail = (int)cdiv64(Mtot, 128) - main_tiles;
-        k_fwd_glds_zt<128, 64, 2, 2><<<dim3((unsigned)(main_tiles + 2 * tail)), dim3(256), (128 + 64) * 32 * 2 * sizeof(float), st>>>(
-            g, in, in_sample_stride, wt, bias, out, Mtot, p.k_per_split, main_tiles, tap_perm_on());
-    } else GLDS_FWD(128, 64, 2, 2, 2);
-    if (partial) {
-        const int64_t MN = Mtot * g.Cout;
-        k_splitk_finish<<<dim3(cdiv64(MN, 256) < 4096 ? cdiv64(MN, 256) : 4096), dim3(256), 0, st>>>(
-            partial, bias, out, MN, g.Cout, p.Z, g.relu);
+    switch (p.kernel) {
+        case K_FWD_IMG: {
+            int idx = 0;
+#define X(CIN, HH, WW, KS, ST, TMF, WS, R)                                                                           \
+    if (p.variant == idx++) {                                                                                        \
+        if (sw().debug_img) fprintf(stderr, "k_fwd_img R=%d: %d work-groups per CU\n", R, (int)p.grid.x / num_cus()); \
+        k_fwd_img<CIN, HH, WW, KS, ST, TMF, WS, R><<<p.grid, p.block, 0, st>>>(in, in_sample_stride, wt, bias, out, (int)n, g.relu); \
     }
+            IMG_FWD_GEOMS(X)
+#undef X
+            break;
+        }
+        case K_FWD_GLDS_ZP:
+            k_fwd_glds_zp<128, 64, 2, 2><<<p.grid, p.block, 0, st>>>(g, in, in_sample_stride, wt, bias, out, Mtot, (int)p.per_split);
+            break;
+        case K_FWD_GLDS_ZT:
+            k_fwd_glds_zt<128, 64, 2, 2><<<p.grid, p.block, p.lds, st>>>(g, in, in_sample_stride, wt, bias, out, Mtot, (int)p.per_split,
+                                                                          p.main_tiles, sw().tap_perm);
+            break;
+        default:  // K_FWD_GLDS_Z / K_FWD_GLDS
+            if (TILE_IS(256, 64)) k_fwd_glds_z<256, 64, 4, 1><<<p.grid, p.block, 0, st>>>(GLDS_FWD_ARGS);  // (_z form only)
+            else if (TILE_IS(64, 64)) GLDS_FWD(64, 64, 2, 2);
+            else if (TILE_IS(128, 128)) GLDS_FWD(128, 128, 2, 2);
+            else GLDS_FWD(128, 64, 2, 2);
+    }
+    if (partial) launch_splitk_finish(partial, bias, out, Mtot * g.Cout, g, p.splits, st);
     return sf_launch_status("sf_conv_fwd_t");
 }
 // two linear layers into one accumulator (k_fwd_glds2): out = a1 w1t^T + a2 w2t^T + bias1 + bias2
 extern "C" int sf_linear_fwd_dual_supported(int64_t n, int N, int K1, int K2) {
-    static const int on = getenv("SF_LINEAR_DUAL") ? atoi(getenv("SF_LINEAR_DUAL")) : 1;
-    return on && n > 0 && N >= 64 && K1 > 0 && K2 > 0 && K1 % 32 == 0 && K2 % 32 == 0 && n < (1LL << 31) &&
+    return sw().linear_dual && n > 0 && N >= 64 && K1 > 0 && K2 > 0 && K1 % 32 == 0 && K2 % 32 == 0 && n < (1LL << 31) &&
            cdiv64(n, 128) * (int64_t)cdiv64(N, 64) >= 256;
 }
 extern "C" int sf_linear_fwd_dual(const float *a1, int64_t lda1, const float *w1t, const float *bias1, int K1,
@@ -1429,29 +1547,26 @@ static SplitPlan plan_splits(int64_t Mtot, int K, int N, int BM, int BN, int bpc
     p.Z = (int)((Mtot + p.m_per_split - 1) / p.m_per_split);
     return p;
 }
-template <int BN, int WM, int WN, int MODE>
-static int occ_wgrad() {
-    static const int v = occupancy_of(k_conv_wgrad<BN, WM, WN, MODE>);
-    return v;
-}
 template <int BK, int BN, int WM, int WN>
 static int occ_wgrad_glds() {
     static const int v = occupancy_of(k_wgrad_glds<BK, BN, WM, WN>);
     return v;
 }
 static inline int wgrad_bn(int N) { return N <= 32 ? 32 : 64; }
+// partials sf_conv_wgrad_workspace always has room for: the register-staged kernel's largest split count
+static int wgrad_ws_partials(int64_t Mtot, int K, int N) { return plan_splits(Mtot, K, N, 128, wgrad_bn(N)).Z; }
 struct WgradGlds {
     int cfg;  // 0: 256x64 (waves 4x1), 1: 128x128 (2x2), 2: 128x64 (2x2), 3: 64x128 (2x2; K = 64: the recurrent input projection)
     int BK, BN, Z;
     int64_t m_per_split;
 };
+// SF_WGRAD_GLDS: 0 = the register-staged kernel instead, 1 = default, 2 + cfg = that tile config for every launch
 static WgradGlds plan_wgrad_glds(int64_t Mtot, int K, int N, bool query_occupancy = false) {
-    static const int force = getenv("SF_WGRAD_GLDS") ? atoi(getenv("SF_WGRAD_GLDS")) : 1;
     WgradGlds q;
     // 256-row weight tiles only when they do not add padded rows over 128-row tiles (K = 576: 768 vs 640 rows)
     const bool k256 = K >= 256 && (K + 255) / 256 * 256 <= (K + 127) / 128 * 128;
     q.cfg = N >= 128 ? 1 : (k256 ? 0 : 2);
-    if (force >= 2) q.cfg = force - 2;
+    if (sw().wgrad_glds >= 2) q.cfg = sw().wgrad_glds - 2;
     if (K == 64 && N >= 128) q.cfg = 3;  // a 128-row weight tile would be half padding
     q.BK = q.cfg == 0 ? 256 : q.cfg == 3 ? 64 : 128;
     q.BN = (q.cfg == 1 || q.cfg == 3) ? 128 : 64;
@@ -1470,10 +1585,8 @@ static WgradGlds plan_wgrad_glds(int64_t Mtot, int K, int N, bool query_occupanc
 // stay on the register-staged kernel).  SF_WGRAD_GLDS_MIN
 // overrides the row threshold (A/B switch).
 static bool wgrad_glds_wanted(int64_t Mtot, int K, int N) {
-    static const int64_t v = getenv("SF_WGRAD_GLDS_MIN") ? atoll(getenv("SF_WGRAD_GLDS_MIN")) : -1;
-    if (v >= 0) return Mtot >= v;
-    static const int k64 = getenv("SF_WGRAD_GLDS_K64") ? atoi(getenv("SF_WGRAD_GLDS_K64")) : 1;
-    if (k64 && Mtot >= 16384 && K == 64 && N >= 512) return true;  // W_ih of a recurrent core behind a 64-wide encoder
+    if (sw().wgrad_glds_min >= 0) return Mtot >= sw().wgrad_glds_min;
+    if (sw().wgrad_glds_k64 && Mtot >= 16384 && K == 64 && N >= 512) return true;  // W_ih of a recurrent core behind a 64-wide encoder
     return Mtot >= 65536 || (Mtot >= 16384 && N >= 64 && (K >= 1024 || (int64_t)K * N >= 512 * 1024));
 }
 
@@ -1481,7 +1594,7 @@ static bool wgrad_glds_wanted(int64_t Mtot, int K, int N) {
 // (variant 2: 8 waves, one work-group per CU) geometries, launches that give every persistent work-group a few samples.
 // SF_WGRAD_IMG=0: back on k_wgrad_glds; =1: conv3 only; default 3: both (A/B switch).
 static int wgrad_img_variant(const sf_conv_desc *d, int64_t n) {
-    static const int on = getenv("SF_WGRAD_IMG") ? atoi(getenv("SF_WGRAD_IMG")) : 3;
+    const int on = sw().wgrad_img;
     if (!on || d->in_u8 != IN_F32_NHWC || d->traj_T != 0 || d->Cout != 64 || n < 512) return 0;
     if ((on & 1) && d->Cin == 64 && d->H == 9 && d->W == 9 && d->KH == 3 && d->KW == 3 && d->stride == 1) return 1;
     if ((on & 2) && d->Cin == 32 && d->H == 20 && d->W == 20 && d->KH == 4 && d->KW == 4 && d->stride == 2) return 2;
@@ -1492,12 +1605,87 @@ static int wgrad_img_blocks(const sf_conv_desc *d, int64_t n) {
     return (int)(n < nb ? n : nb);
 }
 
+// per-mode occupancy of the register-staged weight-gradient kernel
+template <int BN, int WM, int WN>
+static int occ_wgrad_mode(int mode) {
+#define OCC(MODE) { static const int v = occupancy_of(k_conv_wgrad<BN, WM, WN, MODE>); return v; }
+    switch (mode) {
+        case MODE_F32: OCC(MODE_F32) case MODE_U8: OCC(MODE_U8) case MODE_F32F: OCC(MODE_F32F)
+        case MODE_F32F_NORM: OCC(MODE_F32F_NORM) case MODE_U8_NORM: OCC(MODE_U8_NORM) default: OCC(MODE_GENERIC)
+    }
+#undef OCC
+}
+
+// sf_conv_wgrad and (g.nmu set) sf_conv_wgrad_norm.  Every kernel writes plan.partials partial results [K, N] (+ [N] for
+// the bias, plan.partials * K * N floats in) that launch_reduce_partials sums; the strip kernels' persistent grids are
+// cut to the partials sf_conv_wgrad_workspace sized for.
+static ConvPlan plan_conv_wgrad(const sf_conv_desc *d, const ConvG &g, int64_t n, const Operands &o) {
+    ConvPlan p = plan_init();
+    const bool norm = g.nmu != nullptr;
+    if (norm && !conv_norm_ok(d, n)) return p;
+    const int K = g.K, N = g.Cout, BN = wgrad_bn(N);
+    const int64_t Mtot = n * g.OH * g.OW;
+    const int Zws = wgrad_ws_partials(Mtot, K, N), npairs = (int)((n + 1) / 2);
+    int mode = pick_mode(g);
+    if (mode != MODE_GENERIC && (!act_aligned(g, o.in, o.stride) || !aligned(o.dout, 16))) mode = MODE_GENERIC;
+    const bool strip_ops = N == 32 && in4(o) && aligned(o.dout, 16);  // what the Nature-CNN conv1 strip kernels ask of their operands
+    p.variant = g.sub_mean != 0.f;
+    // persistent blocks over sample pairs, one partial per block, never more than the workspace was sized for
+    auto strip = [&](int blocks, size_t lds) { p.partials = min(min(npairs, blocks), Zws); p.lds = (unsigned)lds; };
+    if (norm && conv_norm_strip(g) && strip_ops && tabs16(g)) {
+        strip(512, (160 * 32 + 2 * 4 * 20 * 84) * sizeof(float));
+        plan_kernel(p, K_CONV1_WGRAD_IMG_NORM, "k_conv1_wgrad_img_norm<2, 4>");
+    } else if (conv1_bf16_ok(g, mode, n) && strip_ops) {  // exact products on the bf16 matrix pipe (sf_nn_u8.h)
+        strip(2 * num_cus(), (2 * 4 * 20 * 4 * 36 + 3 * 32 * 168) * sizeof(uint16_t));
+        plan_kernel(p, K_CONV1_WGRAD_BF16, "k_conv1_wgrad_bf16<%s>", p.variant ? "true" : "false");
+    } else if (sw().conv1_img && conv1_img_ok(g, mode, n) && strip_ops) {  // Nature-CNN conv1 on raw frames: strip-image kernel
+        strip(512, (160 * 32 + 2 * 4 * 20 * 84) * sizeof(float));
+        plan_kernel(p, K_CONV1_WGRAD_IMG, "k_conv1_wgrad_img<2, 4, %s>", p.variant ? "true" : "false");
+    } else if (small_linear_wgrad_ok(d) && !o.index) {
+        // 27 -> 64 -> 64 encoder layers: 64-row tiles through LDS, fmaf (sf_nn_narrow.h); one partial per work-group
+        const int nb = (int)(cdiv64(Mtot, 64) < 256 ? cdiv64(Mtot, 64) : 256);  // (<= what sf_conv_wgrad_workspace sized for)
+        p.per_split = cdiv64(cdiv64(Mtot, nb), 64) * 64;
+        p.partials = (int)cdiv64(Mtot, p.per_split);
+        plan_kernel(p, K_LINEAR_WGRAD_SMALL, "k_linear_wgrad_small");
+    } else if (mode == MODE_F32 && !o.index && wgrad_img_variant(d, n)) {
+        // conv2 / conv3: persistent LDS-image kernel, every operand byte fetched once, one partial per work-group
+        p.variant = wgrad_img_variant(d, n); p.partials = wgrad_img_blocks(d, n); p.block = dim3(p.variant == 1 ? 256 : 512);
+        plan_kernel(p, K_WGRAD_IMG, p.variant == 1 ? "k_wgrad_img<64, 9, 9, 3, 1, 1>" : "k_wgrad_img<32, 20, 20, 4, 2, 2>");
+    } else if (sw().wgrad_glds && mode == MODE_F32 && !o.index && g.traj_T == 0 && wgrad_glds_wanted(Mtot, K, N) &&
+               n * max(o.stride, (int64_t)g.H * g.W * g.Cin) < ((int64_t)1 << 30)) {  // 32-bit byte offsets in the kernel
+        // gfx950 LDS-DMA kernel (dense f32 NHWC input): different tiles, so its own split plan and partial layout
+        const WgradGlds q = plan_wgrad_glds(Mtot, K, N, true);
+        p.partials = p.splits = q.Z; p.per_split = q.m_per_split;
+        p.grid = dim3(cdiv64(K, q.BK), cdiv64(N, q.BN), (unsigned)q.Z);
+        // XCD-aware block order (sf_nn_glds.h): a 1-D launch whose ids are re-mapped so that every XCD owns a contiguous
+        // run of (row tile, column tile, slice) — only worth it when tiles share strips (more than one tile per slice)
+        plan_raster(p, sw().xcd_raster && p.grid.x * p.grid.y > 1);
+        // linear layers: the zero-VALU reduction loop (k_wgrad_glds_z); SF_WGRAD_ZL=0 switches it off
+        const bool zl = sw().wgrad_zl && g.KH == 1 && g.KW == 1 && g.H == 1 && g.W == 1 && g.OH == 1 && g.OW == 1 &&
+                        n * o.stride < (1LL << 30) && Mtot * N < (1LL << 30);
+        const TileArgs t = {q.BK, q.BN, q.cfg == 0 ? 4 : 2, q.cfg == 0 ? 1 : 2};
+        if (zl) plan_tile(p, K_WGRAD_GLDS_Z, "k_wgrad_glds_z", t);
+        else plan_tile(p, K_WGRAD_GLDS, "k_wgrad_glds", t);
+        return p;
+    } else {
+        const int bpc = BN == 32 ? occ_wgrad_mode<32, 4, 1>(mode) : occ_wgrad_mode<64, 2, 2>(mode);
+        const SplitPlan s = plan_splits(Mtot, K, N, 128, BN, bpc);
+        p.variant = mode; p.partials = p.splits = s.Z; p.per_split = s.m_per_split;
+        p.grid = dim3(cdiv64(K, 128), cdiv64(N, BN), (unsigned)s.Z);
+        p.t = BN == 32 ? TileArgs{128, 32, 4, 1} : TileArgs{128, 64, 2, 2};
+        plan_kernel(p, K_CONV_WGRAD, "k_conv_wgrad<%d, %d, %d, %d>", BN, p.t.WM, p.t.WN, mode);
+        return p;
+    }
+    p.grid = dim3((unsigned)p.partials);  // one partial per (persistent) work-group
+    return p;
+}
+
+// the maximum over the operand facts the query cannot know (alignment, index, occupancy of the kernel that will run)
 extern "C" int64_t sf_conv_wgrad_workspace(int64_t n, const sf_conv_desc *h_desc) {
     if (!h_desc || n <= 0) return 0;
     const int K = h_desc->KH * h_desc->KW * h_desc->Cin, N = h_desc->Cout;
     const int64_t Mtot = n * h_desc->OH * h_desc->OW;
-    const SplitPlan p = plan_splits(Mtot, K, N, 128, wgrad_bn(N));
-    int Z = p.Z;
+    int Z = wgrad_ws_partials(Mtot, K, N);
     if (wgrad_img_variant(h_desc, n) && wgrad_img_blocks(h_desc, n) > Z) Z = wgrad_img_blocks(h_desc, n);  // one partial per work-group
     if (small_linear_wgrad_ok(h_desc)) {  // one partial per 64-row tile, at most 1024
         const int64_t zs = cdiv64(Mtot, 64) < 1024 ? cdiv64(Mtot, 64) : 1024;
@@ -1510,32 +1698,19 @@ extern "C" int64_t sf_conv_wgrad_workspace(int64_t n, const sf_conv_desc *h_desc
     return (int64_t)sizeof(float) * Z * ((int64_t)K * N + N) + 256;
 }
 
-#define WGRAD_LAUNCH(BN, WM, WN, MODE)                                                                        \
-    k_conv_wgrad<BN, WM, WN, MODE><<<grid, dim3(256), 0, st>>>(g, in, in_sample_stride, index, offset, dout,  \
-                                                              partial_w, db ? partial_b : nullptr, Mtot,     \
-                                                              p.m_per_split)
-#define WGRAD_BY_MODE(BN, WM, WN)                                    \
-    do {                                                             \
-        if (mode == MODE_F32) WGRAD_LAUNCH(BN, WM, WN, MODE_F32);    \
-        else if (mode == MODE_U8) WGRAD_LAUNCH(BN, WM, WN, MODE_U8); \
-        else if (mode == MODE_F32F) WGRAD_LAUNCH(BN, WM, WN, MODE_F32F); \
-        else if (mode == MODE_F32F_NORM) WGRAD_LAUNCH(BN, WM, WN, MODE_F32F_NORM); \
-        else if (mode == MODE_U8_NORM) WGRAD_LAUNCH(BN, WM, WN, MODE_U8_NORM); \
-        else WGRAD_LAUNCH(BN, WM, WN, MODE_GENERIC);                 \
+#define WGRAD_LAUNCH(BN, WM, WN, MODE)                                                                                  \
+    k_conv_wgrad<BN, WM, WN, MODE><<<p.grid, p.block, 0, st>>>(g, in, in_sample_stride, index, offset, dout, partial_w, \
+                                                               partial_b, Mtot, p.per_split)
+#define WGRAD_GLDS_ARGS g, inf, in_sample_stride, dout, partial_w, partial_b, Mtot, p.per_split, p.rx, p.ry, p.rtot
+#define WGRAD_GLDS(BK_, BN_, WM_, WN_)                                                                                    \
+    do {                                                                                                                  \
+        if (p.kernel == K_WGRAD_GLDS_Z) k_wgrad_glds_z<BK_, BN_, WM_, WN_><<<p.grid, p.block, 0, st>>>(WGRAD_GLDS_ARGS);  \
+        else k_wgrad_glds<BK_, BN_, WM_, WN_><<<p.grid, p.block, 0, st>>>(WGRAD_GLDS_ARGS);                               \
     } while (0)
-
-// per-mode occupancy of the register-staged weight-gradient kernel
-template <int BN, int WM, int WN>
-static int occ_wgrad_mode(int mode) {
-    switch (mode) {
-        case MODE_F32: return occ_wgrad<BN, WM, WN, MODE_F32>();
-        case MODE_U8: return occ_wgrad<BN, WM, WN, MODE_U8>();
-        case MODE_F32F: return occ_wgrad<BN, WM, WN, MODE_F32F>();
-        case MODE_F32F_NORM: return occ_wgrad<BN, WM, WN, MODE_F32F_NORM>();
-        case MODE_U8_NORM: return occ_wgrad<BN, WM, WN, MODE_U8_NORM>();
-        default: return occ_wgrad<BN, WM, WN, MODE_GENERIC>();
-    }
-}
+// the Nature-CNN conv1 strip kernels (dmask: the bf16 kernel alone)
+#define WGRAD_STRIP(KERN, ...)                                                                                  \
+    KERN<<<p.grid, p.block, p.lds, st>>>(g, reinterpret_cast<const uint8_t *>(in), in_sample_stride, index, offset, dout, \
+                                         ##__VA_ARGS__, partial_w, partial_b, (int)n, (int)((n + 1) / 2))
 
 // mu / rstd: the observation normaliser's tables (u8 / f32 frames through sf_conv_wgrad_norm), else NULL
 static int conv_wgrad_impl(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
@@ -1551,119 +1726,40 @@ static int conv_wgrad_impl(const void *in, int64_t in_sample_stride, const int32
     const int64_t Mtot = n * g.OH * g.OW;
     SF_REQUIRE(Mtot < (1LL << 31), "sf_conv_wgrad: M=%lld exceeds 2^31 rows; split the batch", (long long)Mtot);
     const int K = g.K, N = g.Cout;
-    const int BN = wgrad_bn(N);
-    int mode = pick_mode(g);
-    if (mode != MODE_GENERIC) {
-        if (!act_aligned(g, in, in_sample_stride) || ((uintptr_t)dout & 15) != 0) mode = MODE_GENERIC;
-    }
-    const int bpc = BN == 32 ? occ_wgrad_mode<32, 4, 1>(mode) : occ_wgrad_mode<64, 2, 2>(mode);
-    const SplitPlan p = plan_splits(Mtot, K, N, 128, BN, bpc);
-    const int Zws = plan_splits(Mtot, K, N, 128, BN).Z;  // what sf_conv_wgrad_workspace promised room for
+    const ConvPlan p = plan_conv_wgrad(h_desc, g, n, Operands{in, in_sample_stride, index != nullptr, nullptr, dout, nullptr, 0});
+    SF_REQUIRE(!dmask || p.kernel == K_CONV1_WGRAD_BF16,
+               "sf_conv_wgrad_relu_mask: this launch does not resolve to the mask-consuming kernel");
     float *partial_w = reinterpret_cast<float *>(workspace);
-    float *partial_b = partial_w + (int64_t)p.Z * K * N;
+    float *partial_b = db ? partial_w + (int64_t)p.partials * K * N : nullptr;
     hipStream_t st = STREAM(stream);
-    static const int glds_on = getenv("SF_WGRAD_GLDS") ? atoi(getenv("SF_WGRAD_GLDS")) : 1;
-    int Zused = p.Z;
-    static const int img_on = getenv("SF_CONV1_IMG") ? atoi(getenv("SF_CONV1_IMG")) : 1;
-    if (conv1_bf16_ok(g, mode, n) && N == 32 && ((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0 &&
-        ((uintptr_t)dout & 15) == 0) {
-        // exact products on the bf16 matrix pipe (sf_nn_u8.h): persistent blocks over sample pairs, one partial per block
-        const int npairs = (int)((n + 1) / 2);
-        int nb = npairs < 2 * num_cus() ? npairs : 2 * num_cus();
-        if (nb > Zws) nb = Zws;  // the workspace was sized for Zws partials
-        partial_b = partial_w + (int64_t)nb * K * N;
-        Zused = nb;
-        const unsigned lds_bytes = (unsigned)((2 * 4 * 20 * 4 * 36 + 3 * 32 * 168) * sizeof(uint16_t));
-        if (g.sub_mean != 0.f)
-            k_conv1_wgrad_bf16<true><<<dim3(nb), dim3(256), lds_bytes, st>>>(
-                g, reinterpret_cast<const uint8_t *>(in), in_sample_stride, index, offset, dout, dmask, partial_w,
-                db ? partial_b : nullptr, (int)n, npairs);
-        else
-            k_conv1_wgrad_bf16<false><<<dim3(nb), dim3(256), lds_bytes, st>>>(
-                g, reinterpret_cast<const uint8_t *>(in), in_sample_stride, index, offset, dout, dmask, partial_w,
-                db ? partial_b : nullptr, (int)n, npairs);
-    } else
-    if (dmask) {
-        SF_REQUIRE(false, "sf_conv_wgrad_relu_mask: this launch does not resolve to the mask-consuming kernel");
-    } else
-    if (img_on && conv1_img_ok(g, mode, n) && N == 32 && ((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0 &&
-        ((uintptr_t)dout & 15) == 0) {
-        // Nature-CNN conv1 on raw frames: strip-image kernel, persistent blocks, one partial per block
-        const int npairs = (int)((n + 1) / 2);
-        int nb = npairs < 512 ? npairs : 512;
-        if (nb > Zws) nb = Zws;  // the workspace was sized for Zws partials
-        partial_b = partial_w + (int64_t)nb * K * N;
-        Zused = nb;
-        const unsigned lds_bytes = (unsigned)((160 * 32 + 2 * 4 * 20 * 84) * sizeof(float));
-        if (g.sub_mean != 0.f)
-            k_conv1_wgrad_img<2, 4, true><<<dim3(nb), dim3(256), lds_bytes, st>>>(
-                g, reinterpret_cast<const uint8_t *>(in), in_sample_stride, index, offset, dout, partial_w,
-                db ? partial_b : nullptr, (int)n, npairs);
-        else
-            k_conv1_wgrad_img<2, 4, false><<<dim3(nb), dim3(256), lds_bytes, st>>>(
-                g, reinterpret_cast<const uint8_t *>(in), in_sample_stride, index, offset, dout, partial_w,
-                db ? partial_b : nullptr, (int)n, npairs);
-    } else
-    if (small_linear_wgrad_ok(h_desc) && !index) {
-        // 27 -> 64 -> 64 encoder layers: 64-row tiles through LDS, fmaf (sf_nn_narrow.h); one partial per work-group
-        int nb = (int)(cdiv64(Mtot, 64) < 256 ? cdiv64(Mtot, 64) : 256);  // (<= what sf_conv_wgrad_workspace sized for)
-        const int64_t mps = cdiv64(cdiv64(Mtot, nb), 64) * 64;
-        nb = (int)cdiv64(Mtot, mps);
-        partial_b = partial_w + (int64_t)nb * K * N;
-        Zused = nb;
-        k_linear_wgrad_small<<<dim3(nb), dim3(256), 0, st>>>(reinterpret_cast<const float *>(in), in_sample_stride, dout,
-                                                             partial_w, db ? partial_b : nullptr, Mtot, mps, K, N);
-    } else
-    if (mode == MODE_F32 && !index && wgrad_img_variant(h_desc, n)) {
-        // conv2 / conv3: persistent LDS-image kernel, every operand byte fetched once, one partial per work-group
-        const int nb = wgrad_img_blocks(h_desc, n);
-        partial_b = partial_w + (int64_t)nb * K * N;
-        Zused = nb;
-        const float *inf = reinterpret_cast<const float *>(in);
-        if (wgrad_img_variant(h_desc, n) == 1)
-            k_wgrad_img<64, 9, 9, 3, 1, 1><<<dim3(nb), dim3(256), 0, st>>>(inf, in_sample_stride, dout, partial_w,
-                                                                            db ? partial_b : nullptr, (int)n);
-        else
-            k_wgrad_img<32, 20, 20, 4, 2, 2><<<dim3(nb), dim3(512), 0, st>>>(inf, in_sample_stride, dout, partial_w,
-                                                                              db ? partial_b : nullptr, (int)n);
-    } else
-    if (glds_on && mode == MODE_F32 && !index && g.traj_T == 0 && wgrad_glds_wanted(Mtot, K, N) &&
-        n * max(in_sample_stride, (int64_t)g.H * g.W * g.Cin) < ((int64_t)1 << 30)) {  // 32-bit byte offsets in the kernel
-        // gfx950 LDS-DMA kernel (dense f32 NHWC input): different tiles, so its own split plan and partial layout
-        const WgradGlds q = plan_wgrad_glds(Mtot, K, N, true);
-        partial_b = partial_w + (int64_t)q.Z * K * N;
-        Zused = q.Z;
-        dim3 gq(cdiv64(K, q.BK), cdiv64(N, q.BN), (unsigned)q.Z);
-        // XCD-aware block order (sf_nn_glds.h): a 1-D launch whose ids are re-mapped so that every XCD owns a contiguous
-        // run of (row tile, column tile, slice) — only worth it when tiles share strips (more than one tile per slice)
-        const int rx = (int)gq.x, ry = (int)gq.y, rtot = (xcd_raster_on() && gq.x * gq.y > 1) ? (int)(gq.x * gq.y * gq.z) : 0;
-        if (rtot > 0) gq = dim3((unsigned)(8 * ((rtot + 7) / 8)), 1, 1);
-        const float *inf = reinterpret_cast<const float *>(in);
-        // linear layers: the zero-VALU reduction loop (k_wgrad_glds_z); SF_WGRAD_ZL=0 switches it off
-        static const int wzl = getenv("SF_WGRAD_ZL") ? atoi(getenv("SF_WGRAD_ZL")) : 1;
-        const bool wgrad_zl = wzl && g.KH == 1 && g.KW == 1 && g.H == 1 && g.W == 1 && g.OH == 1 && g.OW == 1 &&
-                              n * in_sample_stride < (1LL << 30) && Mtot * N < (1LL << 30);
-#define WGRAD_GLDS(BK_, BN_, WM_, WN_)                                                                      \
-    do {                                                                                                    \
-        if (wgrad_zl)                                                                                       \
-            k_wgrad_glds_z<BK_, BN_, WM_, WN_><<<gq, dim3(256), 0, st>>>(g, inf, in_sample_stride, dout, partial_w, \
-                                                                        db ? partial_b : nullptr, Mtot, q.m_per_split, rx, ry, rtot); \
-        else                                                                                                \
-    k_wgrad_glds<BK_, BN_, WM_, WN_><<<gq, dim3(256), 0, st>>>(g, inf, in_sample_stride, dout, partial_w,   \
-                                                              db ? partial_b : nullptr, Mtot, q.m_per_split, rx, ry, rtot); \
-    } while (0)
-        if (q.cfg == 3) WGRAD_GLDS(64, 128, 2, 2);
-        else if (q.cfg == 0) WGRAD_GLDS(256, 64, 4, 1);
-        else if (q.cfg == 1) WGRAD_GLDS(128, 128, 2, 2);
-        else WGRAD_GLDS(128, 64, 2, 2);
-    } else {
-        dim3 grid(cdiv64(K, 128), cdiv64(N, BN), (unsigned)p.Z);
-        if (BN == 32) WGRAD_BY_MODE(32, 4, 1);
-        else WGRAD_BY_MODE(64, 2, 2);
+    const float *inf = reinterpret_cast<const float *>(in);
+    switch (p.kernel) {
+        case K_CONV1_WGRAD_BF16:
+            if (p.variant) WGRAD_STRIP(k_conv1_wgrad_bf16<true>, dmask); else WGRAD_STRIP(k_conv1_wgrad_bf16<false>, dmask);
+            break;
+        case K_CONV1_WGRAD_IMG:
+            if (p.variant) WGRAD_STRIP((k_conv1_wgrad_img<2, 4, true>)); else WGRAD_STRIP((k_conv1_wgrad_img<2, 4, false>));
+            break;
+        case K_LINEAR_WGRAD_SMALL:
+            k_linear_wgrad_small<<<p.grid, p.block, 0, st>>>(inf, in_sample_stride, dout, partial_w, partial_b, Mtot, p.per_split, K, N);
+            break;
+        case K_WGRAD_IMG:
+            if (p.variant == 1) k_wgrad_img<64, 9, 9, 3, 1, 1><<<p.grid, p.block, 0, st>>>(inf, in_sample_stride, dout, partial_w, partial_b, (int)n);
+            else k_wgrad_img<32, 20, 20, 4, 2, 2><<<p.grid, p.block, 0, st>>>(inf, in_sample_stride, dout, partial_w, partial_b, (int)n);
+            break;
+        case K_WGRAD_GLDS:
+        case K_WGRAD_GLDS_Z:
+            if (TILE_IS(64, 128)) WGRAD_GLDS(64, 128, 2, 2);
+            else if (TILE_IS(256, 64)) WGRAD_GLDS(256, 64, 4, 1);
+            else if (TILE_IS(128, 128)) WGRAD_GLDS(128, 128, 2, 2);
+            else WGRAD_GLDS(128, 64, 2, 2);
+            break;
+        default:  // K_CONV_WGRAD
+            if (TILE_IS(128, 32)) { BY_MODE(WGRAD_LAUNCH, 32, 4, 1) }
+            else { BY_MODE(WGRAD_LAUNCH, 64, 2, 2) }
     }
-    const int64_t KN = (int64_t)K * N;
-    launch_reduce_partials(partial_w, dw, KN, Zused, st);
-    if (db) launch_reduce_partials(partial_b, db, N, Zused, st);
+    launch_reduce_partials(partial_w, dw, (int64_t)K * N, p.partials, st);
+    if (db) launch_reduce_partials(partial_b, db, N, p.partials, st);
     return sf_launch_status("sf_conv_wgrad");
 }
 
@@ -1682,25 +1778,6 @@ extern "C" int sf_conv_wgrad_relu_mask(const void *in, int64_t in_sample_stride,
     return conv_wgrad_impl(in, in_sample_stride, index, offset, dout, relu_mask, dw, db, n, h_desc, workspace, stream);
 }
 
-// ---- conv1 on raw u8 frames WITH the observation normaliser's running statistics applied in the loader (cfg.normalize_input
-// on image observations: utils/normalize.py:51-70, running_mean_std.py:79-110, cfg/cfg.py:337-341 default True): no
-// normalised f32 copy of the frames exists anywhere.  mu / rstd: the normaliser's f32 tables [Cin*H*W] in the frame's NCHW
-// order (sf_obsnorm_update writes them).  sf_conv_norm_supported() accepts every frame descriptor (in_u8 = 1 or 2) that
-// check_desc accepts.  Both frame formats take every geometry: the register-staged kernels (k_conv_fwd / k_conv_wgrad)
-// form clamp(((x - sub_mean) * inv_scale - mu[d]) * rstd[d], +-5) in their loaders (MODE_U8_NORM / MODE_F32F_NORM), with
-// vector loads of pixels and table entries where sf_conv_fwd would use them and the scalar loader otherwise.  The
-// Nature-CNN conv1 on u8 frames (32 output channels, aligned operands) keeps the strip-image kernels it always had.
-static bool conv_norm_ok(const sf_conv_desc *d, int64_t n) {
-    static const int on = getenv("SF_CONV1_NORM") ? atoi(getenv("SF_CONV1_NORM")) : 1;
-    return on && d && n > 0 && in_is_frame(d->in_u8);
-}
-// the strip kernels' compile-time geometry; ANY n (their n >= 256 dispatch threshold is a speed heuristic of the plain
-// entry points, the kernels themselves are correct for every n >= 1)
-static bool conv_norm_strip(const sf_conv_desc *d) {
-    if (!in_is_u8(d->in_u8) || d->Cout != 32) return false;
-    const ConvG g = make_geom(d);
-    return pick_mode(g) == MODE_U8 && g.Cin == 4 && g.H == 84 && g.W == 84 && g.KH == 8 && g.KW == 8 && g.S == 4;
-}
 extern "C" int sf_conv_norm_supported(int64_t n, const sf_conv_desc *h_desc) {
     return h_desc && check_desc(h_desc, "sf_conv_norm_supported") == 0 && conv_norm_ok(h_desc, n) ? 1 : 0;
 }
@@ -1713,18 +1790,15 @@ extern "C" int sf_conv_fwd_norm(const void *in, int64_t in_sample_stride, const 
     SF_REQUIRE(conv_norm_ok(h_desc, n) && ((uintptr_t)mu & 3) == 0 && ((uintptr_t)rstd & 3) == 0 &&
                    (in_is_u8(h_desc->in_u8) || ((uintptr_t)in & 3) == 0),
                "sf_conv_fwd_norm: unsupported launch (see sf_conv_norm_supported; f32 frames and tables 4-byte aligned)");
-    // every launch but the Nature-CNN conv1 on aligned u8 frames: the register-staged kernel with a normalising loader
-    if (!conv_norm_strip(h_desc) || ((uintptr_t)in & 3) != 0 || in_sample_stride % 4 != 0 || ((uintptr_t)mu & 15) != 0 ||
-        ((uintptr_t)rstd & 15) != 0)
-        return conv_fwd_impl(in, in_sample_stride, index, offset, w, bias, out, nullptr, n, h_desc, nullptr, 0, stream, mu,
-                             rstd);
     ConvG g = make_geom(h_desc);
     g.nmu = mu; g.nrstd = rstd;
+    const ConvPlan p = plan_conv_fwd(h_desc, g, n, Operands{in, in_sample_stride, index != nullptr, w, nullptr, out, 0});
+    // every launch but the Nature-CNN conv1 on aligned u8 frames: the register-staged kernel with a normalising loader
+    if (p.kernel != K_CONV_U8_IMG_NORM)
+        return conv_fwd_impl(in, in_sample_stride, index, offset, w, bias, out, nullptr, n, h_desc, nullptr, 0, stream, mu,
+                             rstd);
     SF_REQUIRE(n * g.OH * g.OW < (1LL << 31), "sf_conv_fwd_norm: M exceeds 2^31 rows; split the batch");
-    const unsigned lds_bytes = (unsigned)(2 * 4 * 20 * 84 * sizeof(float));
-    static const int bpc = occupancy_of(k_conv_u8_img_norm<2, 4, 5, 16>, 256, lds_bytes);
-    const int64_t npairs = cdiv64(n, 2), resident = (int64_t)num_cus() * (bpc > 0 ? bpc : 1);
-    k_conv_u8_img_norm<2, 4, 5, 16><<<dim3((unsigned)(npairs < resident ? npairs : resident)), dim3(256), lds_bytes, STREAM(stream)>>>(
+    k_conv_u8_img_norm<2, 4, 5, 16><<<p.grid, p.block, p.lds, STREAM(stream)>>>(
         g, reinterpret_cast<const uint8_t *>(in), in_sample_stride, index, offset, w, bias, out, (int)n);
     return sf_launch_status("sf_conv_fwd_norm");
 }
@@ -1737,35 +1811,21 @@ extern "C" int sf_conv_wgrad_norm(const void *in, int64_t in_sample_stride, cons
     SF_REQUIRE(conv_norm_ok(h_desc, n) && ((uintptr_t)mu & 3) == 0 && ((uintptr_t)rstd & 3) == 0 &&
                    (in_is_u8(h_desc->in_u8) || ((uintptr_t)in & 3) == 0),
                "sf_conv_wgrad_norm: unsupported launch (see sf_conv_norm_supported; f32 frames and tables 4-byte aligned)");
-    if (!conv_norm_strip(h_desc) || ((uintptr_t)in & 3) != 0 || in_sample_stride % 4 != 0 || ((uintptr_t)mu & 15) != 0 ||
-        ((uintptr_t)rstd & 15) != 0 || ((uintptr_t)dout & 15) != 0)
+    ConvG g = make_geom(h_desc);
+    g.nmu = mu; g.nrstd = rstd;
+    const ConvPlan p = plan_conv_wgrad(h_desc, g, n, Operands{in, in_sample_stride, index != nullptr, nullptr, dout, nullptr, 0});
+    if (p.kernel != K_CONV1_WGRAD_IMG_NORM)
         return conv_wgrad_impl(in, in_sample_stride, index, offset, dout, nullptr, dw, db, n, h_desc, workspace, stream, mu,
                                rstd);
     SF_REQUIRE(((uintptr_t)workspace & 15) == 0, "sf_conv_wgrad_norm: workspace must be 16-byte aligned");
-    ConvG g = make_geom(h_desc);
-    g.nmu = mu; g.nrstd = rstd;
     const int K = g.K, N = g.Cout;
-    const int Zws = plan_splits(n * g.OH * g.OW, K, N, 128, wgrad_bn(N)).Z;  // what sf_conv_wgrad_workspace promised room for
-    const int npairs = (int)((n + 1) / 2);
-    int nb = npairs < 512 ? npairs : 512;
-    if (nb > Zws) nb = Zws;
-    float *partial_w = reinterpret_cast<float *>(workspace), *partial_b = partial_w + (int64_t)nb * K * N;
-    const unsigned lds_bytes = (unsigned)((160 * 32 + 2 * 4 * 20 * 84) * sizeof(float));
+    float *partial_w = reinterpret_cast<float *>(workspace), *partial_b = db ? partial_w + (int64_t)p.partials * K * N : nullptr;
     hipStream_t st = STREAM(stream);
-    k_conv1_wgrad_img_norm<2, 4><<<dim3(nb), dim3(256), lds_bytes, st>>>(
-        g, reinterpret_cast<const uint8_t *>(in), in_sample_stride, index, offset, dout, partial_w, db ? partial_b : nullptr,
-        (int)n, npairs);
-    launch_reduce_partials(partial_w, dw, (int64_t)K * N, nb, st);
-    if (db) launch_reduce_partials(partial_b, db, N, nb, st);
+    WGRAD_STRIP((k_conv1_wgrad_img_norm<2, 4>));
+    launch_reduce_partials(partial_w, dw, (int64_t)K * N, p.partials, st);
+    if (db) launch_reduce_partials(partial_b, db, N, p.partials, st);
     return sf_launch_status("sf_conv_wgrad_norm");
 }
-
-#define DGRAD_LAUNCH(BM, BN, WM, WN)                                                                          \
-    do {                                                                                                      \
-        dim3 grid(cdiv64(Mc, BM), cdiv64(g.Cin, BN), classes);                                                \
-        if (vec) k_conv_dgrad<BM, BN, WM, WN, true><<<grid, dim3(256), 0, st>>>(g, dout, w, in_act, din, n);  \
-        else k_conv_dgrad<BM, BN, WM, WN, false><<<grid, dim3(256), 0, st>>>(g, dout, w, in_act, din, n);     \
-    } while (0)
 
 static sf_conv_desc linear_desc(int K, int N, int relu);
 static bool linear_dgrad_glds_ok(const ConvG &g, int64_t n) {
@@ -1775,26 +1835,95 @@ static bool linear_dgrad_glds_ok(const ConvG &g, int64_t n) {
 // ... and narrow ones (Cin == 64 behind a deep reduction: the data gradient of a recurrent core's input projection,
 // 16384 x 2048 -> 64): 128-row tiles are 128 work-groups, half the chip; 64 x 64 tiles fill it
 static bool linear_dgrad_glds64_ok(const ConvG &g, int64_t n) {
-    static const int on = getenv("SF_DGRAD_LINEAR64") ? atoi(getenv("SF_DGRAD_LINEAR64")) : 1;
-    return on && g.H == 1 && g.W == 1 && g.KH == 1 && g.KW == 1 && g.Cout % 32 == 0 && g.Cout >= 512 && g.Cin == 64 &&
-           n >= 8192;
-}
-static int dgrad_lpt() {  // longest rows first (k_dgrad_pix block order, sf_nn_glds.h); SF_DGRAD_LPT=0: row-major block ids
-    static const int on = getenv("SF_DGRAD_LPT") ? atoi(getenv("SF_DGRAD_LPT")) : 1;
-    return on;
+    return sw().dgrad_linear64 && g.H == 1 && g.W == 1 && g.KH == 1 && g.KW == 1 && g.Cout % 32 == 0 && g.Cout >= 512 &&
+           g.Cin == 64 && n >= 8192;
 }
 // k_dgrad_pix_z (SF_DGRAD_ZL bit 1): per-lane dY / W offsets of the SADDR-form DMA must fit 32 bits, channels in whole 64s
 static bool dgrad_pix_zl(const ConvG &g, int64_t n) {
-    static const int dzl = getenv("SF_DGRAD_ZL") ? atoi(getenv("SF_DGRAD_ZL")) : 3;
-    return (dzl & 2) && g.Cout % 64 == 0 && n * (int64_t)g.OH * g.OW * g.Cout < (1LL << 30) && (int64_t)g.K * g.Cout < (1LL << 30);
+    return (sw().dgrad_zl & 2) && g.Cout % 64 == 0 && n * (int64_t)g.OH * g.OW * g.Cout < (1LL << 30) &&
+           (int64_t)g.K * g.Cout < (1LL << 30);
 }
 // k_dgrad_quadrow_z addresses dY / W lanes as 32-bit element offsets and the input-gradient / activation elements as
 // 32-bit BYTE offsets from a uniform base: both tensors must stay below 2^30 elements
 static bool dgrad_quadrow_zl(const ConvG &g, int64_t n) {
-    static const int dzl = getenv("SF_DGRAD_ZL") ? atoi(getenv("SF_DGRAD_ZL")) : 3;
-    return (dzl & 1) && g.Cout % 64 == 0 && n * (int64_t)g.OH * g.OW * g.Cout < (1LL << 30) &&
+    return (sw().dgrad_zl & 1) && g.Cout % 64 == 0 && n * (int64_t)g.OH * g.OW * g.Cout < (1LL << 30) &&
            (int64_t)g.K * g.Cout < (1LL << 30) && n * (int64_t)g.H * g.W * g.Cin < (1LL << 30);
 }
+// sf_conv_dgrad.  plan.variant: k_conv_dgrad's VEC argument
+static ConvPlan plan_conv_dgrad(const ConvG &g, int64_t n, const Operands &o) {
+    ConvPlan p = plan_init();
+    const bool al16 = aligned(o.dout, 16) && aligned(o.w, 16), vec = g.vecB && al16;
+    p.per_split = (g.Cout + 31) / 32 * 32;  // the linear forms: the forward GEMM's k_per_split
+    // Linear layer (1x1 on a 1x1 image): din[n, Cin] = dY[n, Cout] * W^T is the forward GEMM of the LDS-DMA kernel with
+    // the canonical [Cin, Cout] weight array AS its Cout-major operand (no transpose needed) and a mask epilogue:
+    // 128x128 tiles, 64x64 per wave (fc layer at n = 32768: 105 -> 120 TFLOP/s against the pixel-major kernel).
+    const bool zl_fits = n * (int64_t)g.Cout < (1LL << 30) && (int64_t)g.Cin * g.Cout < (1LL << 30);
+    if (sw().dgrad_linear && linear_dgrad_glds_ok(g, n) && al16) {
+        p.grid = dim3(cdiv64(n, 128), cdiv64(g.Cin, 128), 1);
+        // (measured slower for this launch — 950 vs 930 us at n = 32768: both orders re-read one operand from the Infinity
+        // Cache, and the row-strip order sweeps the 6.4 MB weight matrix per strip — so only SF_XCD_RASTER=2 enables it here)
+        plan_raster(p, sw().xcd_raster >= 2 && p.grid.y > 1);
+        if (sw().glds_zl >= 2 && zl_fits) plan_tile(p, K_FWD_GLDS_Z, "k_fwd_glds_z", TileArgs{128, 128, 2, 2});
+        else plan_tile(p, K_FWD_GLDS, "k_fwd_glds", TileArgs{128, 128, 2, 2}, ", 2");
+        return p;
+    }
+    if (sw().dgrad_linear && linear_dgrad_glds64_ok(g, n) && al16) {
+        p.grid = dim3(cdiv64(n, 64), 1, 1);
+        if (sw().glds_zl && zl_fits) plan_tile(p, K_FWD_GLDS_Z, "k_fwd_glds_z", TileArgs{64, 64, 2, 2});
+        else plan_tile(p, K_FWD_GLDS, "k_fwd_glds", TileArgs{64, 64, 2, 2}, ", 2");
+        return p;
+    }
+    // pixel-major LDS-DMA kernel: needs enough samples to fill BM-sample row tiles and Cout % 32 == 0
+    // (SF_DGRAD_PIX: 0 = off, 2 = 128-sample tiles for Cin <= 32, 3 = strided convs too instead of the row-walking kernel)
+    const int pix_cfg = sw().dgrad_pix;
+    if (pix_cfg && vec && g.Cout % 32 == 0 && n >= 1024) {
+        // zero-VALU reduction loop (k_dgrad_pix_z / k_dgrad_quadrow_z): per-lane operand offsets must fit 32 bits
+        // SF_DGRAD_ZL (default 3): bit 0 = k_dgrad_quadrow_z (conv2: 1918 / 1921 -> 1877 / 1892 us at n = 32768), bit 1 =
+        // k_dgrad_pix_z with SADDR-form DMA only (conv3: 1308 / 1316 -> 1277 / 1297 us; the full form — pointer fragment reads,
+        // two chunks per trip — costs hipcc 256 + 168 registers against 173 + 32 and the second wave per SIMD with them:
+        // 1214 -> 1316 us, compile-time switch SF_DGRAD_PIX_ZL_LITE=0) — profiles/r05_k_dgrad_zl_ab.log, r05_n_dgrad_pix_lite_ab.log
+        if (g.S > 1 && g.KH % g.S == 0 && g.KW % g.S == 0 && g.W % g.S == 0 && pix_cfg != 3) {
+            // strided conv, row-walking tiles of (sample, group-column) rows: contiguous activation / gradient rows
+            p.grid = dim3(cdiv64(n * (g.W / g.S), 128), cdiv64(g.S * g.S * g.Cin, 128));
+            if (dgrad_quadrow_zl(g, n)) plan_tile(p, K_DGRAD_QUADROW_Z, "k_dgrad_quadrow_z", TileArgs{128, 128, 2, 2});
+            else plan_tile(p, K_DGRAD_QUADROW, "k_dgrad_quadrow", TileArgs{128, 128, 2, 2});
+            return p;
+        }
+        const TileArgs t = g.Cin <= 32 ? TileArgs{pix_cfg == 2 ? 128 : 256, 32, 4, 1} : TileArgs{128, 64, 2, 2};
+        const int ntiles = (int)((n + t.BM - 1) / t.BM), tiles8 = (ntiles + 7) / 8, ctiles = (g.Cin + t.BN - 1) / t.BN;
+        p.rx = ntiles; p.ry = tiles8;  // (kernel arguments of the pixel-major kernel, not a raster)
+        p.grid = dim3((unsigned)(tiles8 * 8 * g.H * ctiles));
+        if (dgrad_pix_zl(g, n)) plan_tile(p, K_DGRAD_PIX_Z, "k_dgrad_pix_z", t);
+        else plan_tile(p, K_DGRAD_PIX, "k_dgrad_pix", t);
+        return p;
+    }
+    const int64_t Mc = n * ((g.H + g.S - 1) / g.S) * ((g.W + g.S - 1) / g.S);  // rows of the largest parity class
+    const TileArgs t = g.Cin <= 32 ? TileArgs{128, 32, 4, 1} : Mc * ((g.Cin + 63) / 64) < 128LL * 1024 ? TileArgs{64, 64, 2, 2} : TileArgs{128, 64, 2, 2};
+    p.variant = vec;
+    p.grid = dim3(cdiv64(Mc, t.BM), cdiv64(g.Cin, t.BN), (unsigned)(g.S * g.S));
+    plan_tile(p, K_CONV_DGRAD, "k_conv_dgrad", t, vec ? ", true" : ", false");
+    return p;
+}
+
+#define DGRAD_LAUNCH(BM, BN, WM, WN)                                                                                \
+    do {                                                                                                            \
+        if (p.variant) k_conv_dgrad<BM, BN, WM, WN, true><<<p.grid, p.block, 0, st>>>(g, dout, w, in_act, din, n);  \
+        else k_conv_dgrad<BM, BN, WM, WN, false><<<p.grid, p.block, 0, st>>>(g, dout, w, in_act, din, n);           \
+    } while (0)
+// SF_DGRAD_LPT (default 1): longest rows first (k_dgrad_pix block order, sf_nn_glds.h); 0: row-major block ids
+#define DGRAD_PIX_ARGS g, dout, w, in_act, din, (int)n, p.rx, p.ry, sw().dgrad_lpt
+#define DGRAD_PIX(BM, BN, WM, WN)                                                                                \
+    do {                                                                                                         \
+        if (p.kernel == K_DGRAD_PIX_Z) k_dgrad_pix_z<BM, BN, WM, WN><<<p.grid, p.block, 0, st>>>(DGRAD_PIX_ARGS); \
+        else k_dgrad_pix<BM, BN, WM, WN><<<p.grid, p.block, 0, st>>>(DGRAD_PIX_ARGS);                            \
+    } while (0)
+// the linear forms: the masked forward GEMM on the transposed problem (reduction = Cout, columns = Cin, relu = kind of in_act)
+#define DGRAD_LIN_ARGS g2, dout, g.Cout, w, nullptr, din, n, (int)p.per_split, nullptr, in_act, 1, p.rx, p.ry, p.rtot
+#define DGRAD_LINEAR(BM, BN)                                                                                      \
+    do {                                                                                                          \
+        if (p.kernel == K_FWD_GLDS_Z) k_fwd_glds_z<BM, BN, 2, 2><<<p.grid, p.block, 0, st>>>(DGRAD_LIN_ARGS);     \
+        else k_fwd_glds<BM, BN, 2, 2, 2><<<p.grid, p.block, 0, st>>>(DGRAD_LIN_ARGS);                             \
+    } while (0)
 extern "C" int sf_conv_dgrad(const float *dout, const float *w, const float *in_act, float *din, int64_t n,
                              const sf_conv_desc *h_desc, void *stream) {
     int rc = check_desc(h_desc, "sf_conv_dgrad");
@@ -1804,90 +1933,37 @@ extern "C" int sf_conv_dgrad(const float *dout, const float *w, const float *in_
     SF_REQUIRE(h_desc->Cout % 4 == 0 || (h_desc->KH == 1 && h_desc->KW == 1),
                "sf_conv_dgrad: Cout must be a multiple of 4 for spatial kernels");
     const ConvG g = make_geom(h_desc);
-    const int Hc = (g.H + g.S - 1) / g.S, Wc = (g.W + g.S - 1) / g.S;  // largest parity class
-    const int64_t Mc = n * Hc * Wc;
     SF_REQUIRE(n * g.H * g.W < (1LL << 31) && n * g.OH * g.OW * (int64_t)g.Cout < (1LL << 31) &&
                    (int64_t)g.K * g.Cout < (1LL << 31),
                "sf_conv_dgrad: operand too large for 32-bit element offsets; split the batch");
     hipStream_t st = STREAM(stream);
-    const unsigned classes = (unsigned)(g.S * g.S);
-    const bool vec = g.vecB && ((uintptr_t)dout & 15) == 0 && ((uintptr_t)w & 15) == 0;
-    // Linear layer (1x1 on a 1x1 image): din[n, Cin] = dY[n, Cout] * W^T is the forward GEMM of the LDS-DMA kernel with
-    // the canonical [Cin, Cout] weight array AS its Cout-major operand (no transpose needed) and a mask epilogue:
-    // 128x128 tiles, 64x64 per wave (fc layer at n = 32768: 105 -> 120 TFLOP/s against the pixel-major kernel).
-    static const int lin_on = getenv("SF_DGRAD_LINEAR") ? atoi(getenv("SF_DGRAD_LINEAR")) : 1;
-    if (lin_on && linear_dgrad_glds_ok(g, n) && ((uintptr_t)dout & 15) == 0 && ((uintptr_t)w & 15) == 0) {
-        sf_conv_desc d2 = linear_desc(g.Cout, g.Cin, g.relu);  // reduction = Cout, columns = Cin, relu = kind of in_act
-        const ConvG g2 = make_geom(&d2);
-        dim3 gq(cdiv64(n, 128), cdiv64(g.Cin, 128), 1);
-        // (measured slower for this launch — 950 vs 930 us at n = 32768: both orders re-read one operand from the Infinity
-        // Cache, and the row-strip order sweeps the 6.4 MB weight matrix per strip — so only SF_XCD_RASTER=2 enables it here)
-        const int rx = (int)gq.x, ry = (int)gq.y, rtot = (xcd_raster_on() >= 2 && gq.y > 1) ? (int)(gq.x * gq.y) : 0;
-        if (rtot > 0) gq = dim3((unsigned)(8 * ((rtot + 7) / 8)), 1, 1);
-        const bool zl = glds_zl_on() >= 2 && n * (int64_t)g.Cout < (1LL << 30) && (int64_t)g.Cin * g.Cout < (1LL << 30);
-        if (zl)
-            k_fwd_glds_z<128, 128, 2, 2><<<gq, dim3(256), 0, st>>>(
-                g2, dout, g.Cout, w, nullptr, din, n, (g.Cout + 31) / 32 * 32, nullptr, in_act, 1, rx, ry, rtot);
-        else
-        k_fwd_glds<128, 128, 2, 2, 2><<<gq, dim3(256), 0, st>>>(
-            g2, dout, g.Cout, w, nullptr, din, n, (g.Cout + 31) / 32 * 32, nullptr, in_act, 1, rx, ry, rtot);
-        return sf_launch_status("sf_conv_dgrad");
-    }
-    if (lin_on && linear_dgrad_glds64_ok(g, n) && ((uintptr_t)dout & 15) == 0 && ((uintptr_t)w & 15) == 0) {
-        sf_conv_desc d2 = linear_desc(g.Cout, g.Cin, g.relu);
-        const ConvG g2 = make_geom(&d2);
-        const bool zl = glds_zl_on() && n * (int64_t)g.Cout < (1LL << 30) && (int64_t)g.Cin * g.Cout < (1LL << 30);
-        if (zl)
-            k_fwd_glds_z<64, 64, 2, 2><<<dim3(cdiv64(n, 64), 1, 1), dim3(256), 0, st>>>(
-                g2, dout, g.Cout, w, nullptr, din, n, (g.Cout + 31) / 32 * 32, nullptr, in_act, 1);
-        else
-        k_fwd_glds<64, 64, 2, 2, 2><<<dim3(cdiv64(n, 64), 1, 1), dim3(256), 0, st>>>(
-            g2, dout, g.Cout, w, nullptr, din, n, (g.Cout + 31) / 32 * 32, nullptr, in_act, 1);
-        return sf_launch_status("sf_conv_dgrad");
-    }
-    // pixel-major LDS-DMA kernel: needs enough samples to fill BM-sample row tiles and Cout % 32 == 0
-    static const int pix_cfg = getenv("SF_DGRAD_PIX") ? atoi(getenv("SF_DGRAD_PIX")) : 1;
-    if (pix_cfg && vec && g.Cout % 32 == 0 && n >= 1024) {
-#define DGRAD_PIX(BM, BN, WM, WN)                                                                          \
-    do {                                                                                                   \
-        const int ntiles = (int)((n + BM - 1) / BM), tiles8 = (ntiles + 7) / 8, ctiles = (g.Cin + BN - 1) / BN; \
-        if (dgrad_zl)                                                                                      \
-            k_dgrad_pix_z<BM, BN, WM, WN><<<dim3((unsigned)(tiles8 * 8 * g.H * ctiles)), dim3(256), 0, st>>>( \
-                g, dout, w, in_act, din, (int)n, ntiles, tiles8, dgrad_lpt());                              \
-        else                                                                                               \
-        k_dgrad_pix<BM, BN, WM, WN><<<dim3((unsigned)(tiles8 * 8 * g.H * ctiles)), dim3(256), 0, st>>>(    \
-            g, dout, w, in_act, din, (int)n, ntiles, tiles8, dgrad_lpt());                                 \
-    } while (0)
-        // zero-VALU reduction loop (k_dgrad_pix_z / k_dgrad_quadrow_z): per-lane operand offsets must fit 32 bits
-        // SF_DGRAD_ZL (default 3): bit 0 = k_dgrad_quadrow_z (conv2: 1918 / 1921 -> 1877 / 1892 us at n = 32768), bit 1 =
-        // k_dgrad_pix_z with SADDR-form DMA only (conv3: 1308 / 1316 -> 1277 / 1297 us; the full form — pointer fragment reads,
-        // two chunks per trip — costs hipcc 256 + 168 registers against 173 + 32 and the second wave per SIMD with them:
-        // 1214 -> 1316 us, compile-time switch SF_DGRAD_PIX_ZL_LITE=0) — profiles/r05_k_dgrad_zl_ab.log, r05_n_dgrad_pix_lite_ab.log
-        const bool dgrad_zl = dgrad_pix_zl(g, n);
-        if (g.S > 1 && g.KH % g.S == 0 && g.KW % g.S == 0 && g.W % g.S == 0 && pix_cfg != 3) {
-            // strided conv, row-walking tiles of (sample, group-column) rows: contiguous activation / gradient rows
-            const int Wg = g.W / g.S;
-            const int64_t Mrows = n * Wg;
-            if (dgrad_quadrow_zl(g, n))
-                k_dgrad_quadrow_z<128, 128, 2, 2><<<dim3(cdiv64(Mrows, 128), cdiv64(g.S * g.S * g.Cin, 128)), dim3(256), 0,
-                                                    st>>>(g, dout, w, in_act, din, Mrows, make_fastdiv((uint32_t)Wg));
-            else
-            k_dgrad_quadrow<128, 128, 2, 2><<<dim3(cdiv64(Mrows, 128), cdiv64(g.S * g.S * g.Cin, 128)), dim3(256), 0,
-                                              st>>>(g, dout, w, in_act, din, Mrows, make_fastdiv((uint32_t)Wg));
-            return sf_launch_status("sf_conv_dgrad");
+    const ConvPlan p = plan_conv_dgrad(g, n, Operands{nullptr, 0, false, w, dout, nullptr, 0});
+    switch (p.kernel) {
+        case K_FWD_GLDS:
+        case K_FWD_GLDS_Z: {
+            const sf_conv_desc d2 = linear_desc(g.Cout, g.Cin, g.relu);
+            const ConvG g2 = make_geom(&d2);
+            if (TILE_IS(128, 128)) DGRAD_LINEAR(128, 128); else DGRAD_LINEAR(64, 64);
+            break;
         }
-        if (g.Cin <= 32) { if (pix_cfg == 2) DGRAD_PIX(128, 32, 4, 1); else DGRAD_PIX(256, 32, 4, 1); }
-        else DGRAD_PIX(128, 64, 2, 2);
-        return sf_launch_status("sf_conv_dgrad");
+#define QUADROW_ARGS g, dout, w, in_act, din, n * (g.W / g.S), make_fastdiv((uint32_t)(g.W / g.S))
+        case K_DGRAD_QUADROW_Z: k_dgrad_quadrow_z<128, 128, 2, 2><<<p.grid, p.block, 0, st>>>(QUADROW_ARGS); break;
+        case K_DGRAD_QUADROW: k_dgrad_quadrow<128, 128, 2, 2><<<p.grid, p.block, 0, st>>>(QUADROW_ARGS); break;
+#undef QUADROW_ARGS
+        case K_DGRAD_PIX:
+        case K_DGRAD_PIX_Z:
+            if (TILE_IS(128, 32)) DGRAD_PIX(128, 32, 4, 1);
+            else if (TILE_IS(256, 32)) DGRAD_PIX(256, 32, 4, 1);
+            else DGRAD_PIX(128, 64, 2, 2);
+            break;
+        default:  // K_CONV_DGRAD
+            if (TILE_IS(128, 32)) DGRAD_LAUNCH(128, 32, 4, 1);
+            else if (TILE_IS(64, 64)) DGRAD_LAUNCH(64, 64, 2, 2);
+            else DGRAD_LAUNCH(128, 64, 2, 2);
     }
-    if (g.Cin <= 32) DGRAD_LAUNCH(128, 32, 4, 1);
-    else if (Mc * ((g.Cin + 63) / 64) < 128LL * 1024) DGRAD_LAUNCH(64, 64, 2, 2);
-    else DGRAD_LAUNCH(128, 64, 2, 2);
     return sf_launch_status("sf_conv_dgrad");
 }
 
-// Name of the kernel instantiation a launch with these arguments resolves to (aligned operands assumed), spelled the
-// way rocprofv3 prints it, so that bench.py can group its HIP-event timings exactly like the rocprof kernel stats.
 #if SF_CONV1_TRACE
 // experiment builds only (tools/conv1_trace.py): read and clear the per-phase cycle sums of k_conv1_u8_bf16
 extern "C" int sf_debug_conv1_trace(unsigned long long *host_out12) {
@@ -1897,86 +1973,24 @@ extern "C" int sf_debug_conv1_trace(unsigned long long *host_out12) {
     return hipMemcpyToSymbol(HIP_SYMBOL(sf_conv1_trace_acc), z, sizeof(z)) == hipSuccess ? 0 : 1;
 }
 #endif
+// Name of the kernel instantiation a launch with these arguments resolves to, spelled the way rocprofv3 prints it, so that
+// bench.py can group its HIP-event timings exactly like the rocprof kernel stats: the name of the plan the launcher itself
+// would run for query_operands() (aligned operands and tables, dense samples, no index; a split-K workspace if allowed).
+// op: 0 sf_conv_fwd, 1 sf_conv_wgrad, 2 sf_conv_dgrad, 3 sf_conv_fwd_t, 4 sf_conv_fwd_norm, 5 sf_conv_wgrad_norm
 extern "C" int sf_conv_kernel_name(int op, int64_t n, const sf_conv_desc *h_desc, int split_k_allowed, char *out,
                                    int cap) {
     int rc = check_desc(h_desc, "sf_conv_kernel_name");
     if (rc) return rc;
     SF_REQUIRE(out && cap >= 48 && n > 0 && op >= 0 && op <= 5, "sf_conv_kernel_name: bad args");
+    const Operands o = query_operands(h_desc, split_k_allowed != 0);
     ConvG g = make_geom(h_desc);
-    const int64_t Mtot = n * g.OH * g.OW;
-    if (op >= 4) {  // 4: sf_conv_fwd_norm, 5: sf_conv_wgrad_norm (but for one geometry the register-staged kernels, no split)
-        SF_REQUIRE(conv_norm_ok(h_desc, n), "sf_conv_kernel_name: not a launch sf_conv_norm_supported accepts");
-        if (conv_norm_strip(h_desc)) {
-            snprintf(out, cap, op == 4 ? "k_conv_u8_img_norm<2, 4, 5, 16>" : "k_conv1_wgrad_img_norm<2, 4>");
-            return SF_OK;
-        }
-        static const float tab_probe[4] __attribute__((aligned(16))) = {0.f, 0.f, 0.f, 0.f};
-        g.nmu = tab_probe; g.nrstd = tab_probe;  // aligned tables assumed, as for every operand here
-        const int nmode = pick_mode(g);
-        if (op == 4) {
-            const FwdPlan p = plan_fwd(Mtot, g.Cout, g.K, 0);
-            if (p.cfg == 0) snprintf(out, cap, "k_conv_fwd<%d, 32, 4, 1, %d>", Mtot >= 256 * 2048 ? 256 : 128, nmode);
-            else snprintf(out, cap, "k_conv_fwd<%d, 64, 2, 2, %d>", p.cfg == 1 ? 128 : 64, nmode);
-        } else {
-            if (wgrad_bn(g.Cout) == 32) snprintf(out, cap, "k_conv_wgrad<32, 4, 1, %d>", nmode);
-            else snprintf(out, cap, "k_conv_wgrad<64, 2, 2, %d>", nmode);
-        }
-        return SF_OK;
-    }
-    const int mode = pick_mode(g);
-    if (op == 0 && conv1_img_ok(g, mode, n)) {
-        static const int wide_on = getenv("SF_CONV1_WIDE") ? atoi(getenv("SF_CONV1_WIDE")) : 1;
-        if (conv1_bf16_ok(g, MODE_U8, n))
-            snprintf(out, cap, "k_conv1_u8_bf16%s<%s>", wide_on && g.Cout == 32 ? "_w" : "", g.sub_mean != 0.f ? "true" : "false");
-        else snprintf(out, cap, g.sub_mean != 0.f ? "k_conv_u8_img<2, 4, 5, 16, true>" : "k_conv_u8_img<2, 4, 5, 16, false>");
-    } else if (op == 0) {
-        const FwdPlan p = plan_fwd(Mtot, g.Cout, g.K, split_k_allowed ? (int64_t)1 << 60 : 0);
-        const bool big32 = p.splits == 1 && Mtot >= 256 * 2048;
-        if (p.cfg == 0) snprintf(out, cap, "k_conv_fwd<%d, 32, 4, 1, %d>", big32 ? 256 : 128, mode);
-        else snprintf(out, cap, "k_conv_fwd<%d, 64, 2, 2, %d>", p.cfg == 1 ? 128 : 64, mode);
-    } else if (op == 3) {
-        if (narrow_fwd_ok(h_desc, n)) snprintf(out, cap, "k_linear_narrow<%d>", g.Cout <= 16 ? 1 : 2);
-        else if (img_fwd_index(g, n) >= 0) snprintf(out, cap, "k_fwd_img<%d, %d, %d, %d, %d, 2, 1, %d>", g.Cin, g.H, g.W, g.KH, g.S, g.OH);
-        else {
-            const GldsFwdPlan q = plan_fwd_t(Mtot, g.Cout, g.K);
-            const bool zl = glds_zl_on() && (!q.wide || glds_zl_on() >= 2) && (n - 1) * (int64_t)(g.H * g.W * g.Cin) + (int64_t)g.H * g.W * g.Cin < (1LL << 30) &&
-                            (int64_t)g.Cout * g.K < (1LL << 30);  // (dense samples: the stride the model launches with)
-            const int qz = q.ok ? q.Z : 1;
-            if (zl && !q.sq64 && !q.wide && fwd_tail_split(g, Mtot, qz, true) > 0) snprintf(out, cap, "k_fwd_glds_zt<128, 64, 2, 2>");
-            else if (zl) snprintf(out, cap, q.sq64 ? "k_fwd_glds_z<64, 64, 2, 2>" : q.wide ? "k_fwd_glds_z<128, 128, 2, 2>" : "k_fwd_glds_z<128, 64, 2, 2>");
-            else
-            snprintf(out, cap, q.sq64 ? "k_fwd_glds<64, 64, 2, 2, 2>" : q.wide ? "k_fwd_glds<128, 128, 2, 2, 2>" : "k_fwd_glds<128, 64, 2, 2, 2>");
-        }
-    } else if (op == 1 && small_linear_wgrad_ok(h_desc)) {
-        snprintf(out, cap, "k_linear_wgrad_small");
-    } else if (op == 1 && conv1_img_ok(g, mode, n) && g.Cout == 32) {
-        if (conv1_bf16_ok(g, MODE_U8, n)) snprintf(out, cap, g.sub_mean != 0.f ? "k_conv1_wgrad_bf16<true>" : "k_conv1_wgrad_bf16<false>");
-        else snprintf(out, cap, g.sub_mean != 0.f ? "k_conv1_wgrad_img<2, 4, true>" : "k_conv1_wgrad_img<2, 4, false>");
-    } else if (op == 1 && mode == MODE_F32 && wgrad_img_variant(h_desc, n)) {
-        snprintf(out, cap, wgrad_img_variant(h_desc, n) == 1 ? "k_wgrad_img<64, 9, 9, 3, 1, 1>" : "k_wgrad_img<32, 20, 20, 4, 2, 2>");
-    } else if (op == 1 && mode == MODE_F32 && wgrad_glds_wanted(Mtot, g.K, g.Cout) && (int64_t)n * g.H * g.W * g.Cin < ((int64_t)1 << 30)) {
-        const WgradGlds q = plan_wgrad_glds(Mtot, g.K, g.Cout);
-        static const int wzl = getenv("SF_WGRAD_ZL") ? atoi(getenv("SF_WGRAD_ZL")) : 1;
-        const bool z = wzl && g.KH == 1 && g.KW == 1 && g.H == 1 && g.W == 1 && n * (int64_t)g.Cin < (1LL << 30) && Mtot * g.Cout < (1LL << 30);
-        snprintf(out, cap, "k_wgrad_glds%s<%s>", z ? "_z" : "", q.cfg == 3 ? "64, 128, 2, 2" : q.cfg == 0 ? "256, 64, 4, 1" : q.cfg == 1 ? "128, 128, 2, 2" : "128, 64, 2, 2");
-    } else if (op == 1) {
-        if (wgrad_bn(g.Cout) == 32) snprintf(out, cap, "k_conv_wgrad<32, 4, 1, %d>", mode);
-        else snprintf(out, cap, "k_conv_wgrad<64, 2, 2, %d>", mode);
-    } else {
-        const int Hc = (g.H + g.S - 1) / g.S, Wc = (g.W + g.S - 1) / g.S;
-        const int64_t Mc = n * Hc * Wc;
-        const char *v = g.vecB ? "true" : "false";
-        const bool zlf = n * (int64_t)g.Cout < (1LL << 30) && (int64_t)g.Cin * g.Cout < (1LL << 30);
-        if (g.vecB && linear_dgrad_glds_ok(g, n)) snprintf(out, cap, glds_zl_on() >= 2 && zlf ? "k_fwd_glds_z<128, 128, 2, 2>" : "k_fwd_glds<128, 128, 2, 2, 2>");
-        else if (g.vecB && linear_dgrad_glds64_ok(g, n)) snprintf(out, cap, glds_zl_on() && zlf ? "k_fwd_glds_z<64, 64, 2, 2>" : "k_fwd_glds<64, 64, 2, 2, 2>");
-        else if (g.vecB && g.Cout % 32 == 0 && n >= 1024 && g.S > 1 && g.KH % g.S == 0 && g.KW % g.S == 0 && g.W % g.S == 0)
-            snprintf(out, cap, dgrad_quadrow_zl(g, n) ? "k_dgrad_quadrow_z<128, 128, 2, 2>" : "k_dgrad_quadrow<128, 128, 2, 2>");
-        else if (g.vecB && g.Cout % 32 == 0 && n >= 1024)
-            snprintf(out, cap, "k_dgrad_pix%s<%s>", dgrad_pix_zl(g, n) ? "_z" : "", g.Cin <= 32 ? "256, 32, 4, 1" : "128, 64, 2, 2");
-        else if (g.Cin <= 32) snprintf(out, cap, "k_conv_dgrad<128, 32, 4, 1, %s>", v);
-        else if (Mc * ((g.Cin + 63) / 64) < 128LL * 1024) snprintf(out, cap, "k_conv_dgrad<64, 64, 2, 2, %s>", v);
-        else snprintf(out, cap, "k_conv_dgrad<128, 64, 2, 2, %s>", v);
-    }
+    if (op >= 4) g.nmu = g.nrstd = TABLE_PROBE;
+    const ConvPlan p = op == 3 ? plan_conv_fwd_t(h_desc, n, o.stride) : op == 2 ? plan_conv_dgrad(g, n, o)
+                       : (op == 0 || op == 4) ? plan_conv_fwd(h_desc, g, n, o) : plan_conv_wgrad(h_desc, g, n, o);
+    SF_REQUIRE(p.kernel != K_NONE, "sf_conv_kernel_name: not a launch %s accepts",
+               op >= 4 ? "sf_conv_norm_supported" : "sf_conv_fwd_t");
+    strncpy(out, p.name, (size_t)cap - 1);
+    out[cap - 1] = 0;
     return SF_OK;
 }
 

@@ -3,8 +3,9 @@ sf_conv_fwd_norm, sf_conv_wgrad_norm: about 70 compiled instantiations chosen by
 occupancy and row thresholds).  Every row pins the kernel by the name sf_conv_kernel_name reports, then checks the
 operation against float64 on the CPU (max-norm AND an element-wise a-priori bound), guard bands around every output and
 bit reproducibility.  The roster test sweeps a grid of launches through sf_conv_kernel_name and fails on a selectable
-kernel that has neither a row nor a written reason; the last test repeats both under the A/B switch groups of
-tests/test_gpu_switches.py.  DESIGN.md 4.1 holds the measured figures."""
+kernel that has neither a row nor a written reason; the next test repeats both under the A/B switch groups of
+tests/test_gpu_switches.py, and the last checks that the reported name follows a switch the way the launch does.
+DESIGN.md 4.1 holds the measured figures."""
 import functools
 import os
 import subprocess
@@ -470,3 +471,31 @@ def test_ledger_and_roster_under_non_default_switches(switches):
                        text=True, timeout=900)
     tail = r.stdout[-2500:]
     assert r.returncode == 0 and " passed" in tail and "failed" not in tail, f"{switches}:\n{tail}\n{r.stderr[-500:]}"
+
+
+# ------------------------------------------------------------------------------------------------ names under a switch
+# Launches whose kernel a switch changes.  sf_conv_kernel_name answers from the plan the launcher runs, so the name
+# follows the switch (the hand-kept query this replaced reported the default kernel in each of these cases); the expected
+# names were checked against a rocprofv3 kernel trace of the rows under the switch groups (profiles/conv_plan_same_launches.log).
+SWITCHED_NAMES = [
+    ("SF_DGRAD_PIX=2", [(DGRAD, F32, (16, 9, 9, 32, 3, 1), 1025, 0.0, "k_dgrad_pix<128, 32, 4, 1>")]),
+    ("SF_CONV1_BF16=0 SF_CONV1_IMG=0", [(FWD, U8, NATURE1, 257, 3.0, "k_conv_fwd<128, 32, 4, 1, 1>"),
+                                        (WGRAD, U8, NATURE1, 257, 3.0, "k_conv_wgrad<32, 4, 1, 1>")]),
+    ("SF_WGRAD_GLDS=0", [(WGRAD, F32, (96, 1, 1, 72, 1, 1), 70001, 0.0, "k_conv_wgrad<64, 2, 2, 0>")]),
+]
+_NAME_QUERIES = """
+import json, sys
+from tests.test_gpu_kernel_ledger import lib, make_desc
+print(json.dumps([lib.conv_kernel_name(op, n, make_desc(fmt, tuple(geom), mean)) for op, fmt, geom, n, mean in json.loads(sys.argv[1])]))
+"""
+
+
+@pytest.mark.parametrize("switches,cases", SWITCHED_NAMES, ids=[s.replace(" ", ",") for s, _ in SWITCHED_NAMES])
+def test_kernel_name_follows_the_switches(switches, cases):
+    """name queries only, in a fresh process (the switches are read once per process)"""
+    import json
+    env = dict(os.environ, **dict(kv.split("=") for kv in switches.split()))
+    r = subprocess.run([sys.executable, "-c", _NAME_QUERIES, json.dumps([c[:5] for c in cases])], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-1500:]
+    assert json.loads(r.stdout.strip().splitlines()[-1]) == [c[5] for c in cases]
