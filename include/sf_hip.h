@@ -440,7 +440,7 @@ int sf_rnn_chunk_setup(const uint8_t *dones, const uint8_t *valids, const float 
  * cleared by the library (the caller zeroes it once, e.g. at the start of Learner.train, and hands the same word to
  * sf_adam_step / sf_lamb_step as `skip_flag`, so that the garbage gradients of an aborted pass never reach the weights).  sf_lstm_seq_supported: 1 when (Cn, H) can
  * take this path on the current device (H in {256, 512}: 16 hidden units per work-group with their W_hh slice resident in
- * LDS; grid <= #CUs), else use sf_rnn_cell_fwd/bwd per step.
+ * LDS; grid <= #CUs), else use the row-owned passes below (H <= 128) or sf_rnn_cell_fwd/bwd per step.
  * sf_lstm_seq_bwd: dout [R][Cn][H] = dL/d hout; writes dgx [R][Cn][4H] = dL/d(gate pre-activations) (= the gradient of
  * both gx and h W_hh^T + b_hh); the carries of dL/dh and dL/dc live in registers.  Cn <= 8 * 256 rows. */
 int sf_lstm_seq_supported(int Cn, int H);
@@ -478,6 +478,30 @@ int sf_lstm_seq_fwd_x(const float *x, const float *wih_t, const float *bih, int 
 int sf_gru_seq_fwd_x(const float *x, const float *wih_t, const float *bih, int Kx, const float *whh, const float *bhh,
                      const float *keep, float *gates, float *hprev, float *hout, uint32_t *sync, int R, int Cn, int H,
                      int env_major, void *stream);
+
+/* ---- row-owned sequence passes for narrow cores (H in {32, 64, 128}; kind 0 = GRU, 1 = LSTM) ------------------------
+ * The same two BPTT passes as above for the widths at which the whole W_hh fits one work-group (GRU-64: 48 KB): instead
+ * of splitting the hidden units across work-groups that hand h_t to each other through L2, ONE work-group owns a tile of
+ * chunk rows (16; 32 at H = 32) and walks all R steps of them alone, grid = ceil(Cn / tile).  No `sync` argument: no
+ * counters, no polling, no abort word; any Cn > 0.  W_hh stays in LDS for the whole pass (H <= 64; streamed from L2 at
+ * H = 128), h / c and the dL/dh, dL/dc carries stay in registers, the recurrent products run on v_mfma_f32_16x16x4_f32
+ * in one fixed order over k, so a row's results are bit-identical whatever Cn and whatever else is in the batch; the
+ * cell arithmetic is the device code of sf_rnn_cell_fwd / sf_rnn_cell_bwd.
+ * Buffers and layouts are exactly those of sf_lstm_seq_* / sf_gru_seq_*: gx [R][Cn][G*H], whh [H][G*H], bhh [G*H],
+ * keep [R][Cn], gates [R][Cn][4H] (GRU {r, z, n, hn}), hprev / cprev [R+1][Cn][H] (slot 0 given on entry, slot t+1 =
+ * state_t * keep[t]; written, never read back), hout / cout [R][Cn][H] (hout / dout [Cn][R][H] when env_major); cprev /
+ * cout are NULL for a GRU.  Backward: writes dgx [R][Cn][G*H] and, GRU only, dgh [R][Cn][3H] = {dr, dz, dn * r} (LSTM:
+ * dgh may be NULL, both gradients are dgx; hprev may be NULL); the W_hh / b_hh gradient is sf_conv_wgrad over
+ * (hprev[0..R), dgh) as for the other passes.  whh must be 16-byte aligned.
+ * sf_rnn_rowseq_supported: 1 for the (kind, Cn, H) these passes take; they are offered where they measured faster than
+ * the per-step launches (tools/rowseq_bench.py).  An unsupported shape or a bad operand returns an
+ * error before anything is launched. */
+int sf_rnn_rowseq_supported(int kind, int Cn, int H);
+int sf_rnn_rowseq_fwd(int kind, const float *gx, const float *whh, const float *bhh, const float *keep, float *gates,
+                      float *hprev, float *hout, float *cprev, float *cout, int R, int Cn, int H, int env_major, void *stream);
+int sf_rnn_rowseq_bwd(int kind, const float *dout, const float *gates, const float *hprev, const float *cprev,
+                      const float *cout, const float *keep, const float *whh, float *dgx, float *dgh,
+                      int R, int Cn, int H, int env_major, void *stream);
 
 /* ---- data-parallel learner replicas (SURVEY.md §8(b) "DP -> sf_allreduce_grads", §8(e)) ----------------------------
  * New capability: the reference runs ONE learner per policy (algo/utils/shared_buffers.py:26-32), so these replace no

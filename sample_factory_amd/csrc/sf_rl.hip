@@ -2640,7 +2640,8 @@ extern "C" int sf_mlp2_fwd(const float *x, int64_t x_stride, int64_t n, int D, f
 // time loop over recurrence-length chunks with the state zeroed after a done/invalid step — the loop form that the
 // reference's own test (tests/algo/test_rnn.py) proves equal to its PackedSequence path (rnn_utils.py:114-158).
 // kind 0 = GRU (gates r,z,n), 1 = LSTM (gates i,f,g,o).  All matrices row-major; h_prev/c_prev may be strided rows.
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+// The cell expressions themselves live in sf_rnn_cell.h, shared with the row-owned sequence passes of sf_rnn.hip.
+#include "sf_rnn_cell.h"
 
 // gates_out [C, 4H]: GRU stores {r, z, n, hn = (W_hn h + b_hn)}; LSTM stores {i, f, g, o}.
 // h_out/c_out: the new state (core output); h_next/c_next = state * keep[c] (keep = 1 - done_or_invalid; NULL = 1).
@@ -2658,22 +2659,22 @@ __global__ __launch_bounds__(256) void k_rnn_cell_fwd(int kind, const float *__r
     const float k = keep ? keep[c] : 1.0f;
     if (kind == 0) {
         const float hp = h_prev[c * ld_h + j];
-        float r, z, hn, xn;
+        float r_pre, z_pre, hn, xn;
         if (gh) {
             const float *x = gx + c * 3 * H, *g = gh + c * 3 * H;
-            r = sigmoidf_(x[j] + g[j]);
-            z = sigmoidf_(x[H + j] + g[H + j]);
+            r_pre = x[j] + g[j];
+            z_pre = x[H + j] + g[H + j];
             hn = g[2 * H + j];
             xn = x[2 * H + j];
         } else {  // gx [C, 4H] = {r_pre, z_pre (x and h parts summed), x W_in^T + b_in, h W_hn^T + b_hn} (sf_linear_fwd_dual)
             const float *x = gx + c * 4 * H;
-            r = sigmoidf_(x[j]);
-            z = sigmoidf_(x[H + j]);
+            r_pre = x[j];
+            z_pre = x[H + j];
             xn = x[2 * H + j];
             hn = x[3 * H + j];
         }
-        const float n = tanhf(xn + r * hn);
-        const float h = (1.0f - z) * n + z * hp;
+        float r, z, n, h;
+        sf_gru_cell_fwd(r_pre, z_pre, xn, hn, hp, r, z, n, h);
         if (gates_out) {
             float *go = gates_out + c * 4 * H;
             go[j] = r; go[H + j] = z; go[2 * H + j] = n; go[3 * H + j] = hn;
@@ -2683,21 +2684,17 @@ __global__ __launch_bounds__(256) void k_rnn_cell_fwd(int kind, const float *__r
     } else {
         const float *x = gx + c * 4 * H;
         const float cp = c_prev[c * ld_c + j];
-        float ig, fg, gg, og;
+        float pre[4];
         if (gh) {
             const float *g = gh + c * 4 * H;
-            ig = sigmoidf_(x[j] + g[j]);
-            fg = sigmoidf_(x[H + j] + g[H + j]);
-            gg = tanhf(x[2 * H + j] + g[2 * H + j]);
-            og = sigmoidf_(x[3 * H + j] + g[3 * H + j]);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) pre[q] = x[q * H + j] + g[q * H + j];
         } else {  // gx already holds x W_ih^T + b_ih + h W_hh^T + b_hh (sf_linear_fwd_dual)
-            ig = sigmoidf_(x[j]);
-            fg = sigmoidf_(x[H + j]);
-            gg = tanhf(x[2 * H + j]);
-            og = sigmoidf_(x[3 * H + j]);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) pre[q] = x[q * H + j];
         }
-        const float cn = fg * cp + ig * gg;
-        const float h = og * tanhf(cn);
+        float ig, fg, gg, og, cn, h;
+        sf_lstm_cell_fwd(pre[0], pre[1], pre[2], pre[3], cp, ig, fg, gg, og, cn, h);
         if (gates_out) {
             float *go = gates_out + c * 4 * H;
             go[j] = ig; go[H + j] = fg; go[2 * H + j] = gg; go[3 * H + j] = og;
@@ -2740,26 +2737,23 @@ __global__ __launch_bounds__(256) void k_rnn_cell_bwd(int kind, const float *__r
     if (kind == 0) {
         const float r = go[j], z = go[H + j], n = go[2 * H + j], hn = go[3 * H + j];
         const float hp = h_prev[c * ld_h + j];
-        const float dn_pre = (d * (1.0f - z)) * (1.0f - n * n);
-        const float dz_pre = (d * (hp - n)) * (z * (1.0f - z));
-        const float dr_pre = (dn_pre * hn) * (r * (1.0f - r));
+        float dr_pre, dz_pre, dn_pre, dnr, dhd;
+        sf_gru_cell_bwd(d, r, z, n, hn, hp, dr_pre, dz_pre, dn_pre, dnr, dhd);
         float *x = dgx + c * 3 * H, *g = dgh + c * 3 * H;
         x[j] = dr_pre; x[H + j] = dz_pre; x[2 * H + j] = dn_pre;
-        g[j] = dr_pre; g[H + j] = dz_pre; g[2 * H + j] = dn_pre * r;
-        dh_direct[i] = d * z;
+        g[j] = dr_pre; g[H + j] = dz_pre; g[2 * H + j] = dnr;
+        dh_direct[i] = dhd;
     } else {
         const float ig = go[j], fg = go[H + j], gg = go[2 * H + j], og = go[3 * H + j];
-        const float tc = tanhf(c_out[i]);
-        const float dc = d * og * (1.0f - tc * tc) + (dc_in ? dc_in[i] : 0.0f);
         float *x = dgx + c * 4 * H;
-        const float di = (dc * gg) * (ig * (1.0f - ig)), df = (dc * c_prev[c * ld_c + j]) * (fg * (1.0f - fg));
-        const float dg = (dc * ig) * (1.0f - gg * gg), dob = (d * tc) * (og * (1.0f - og));
+        float di, df, dg, dob, dcp;
+        sf_lstm_cell_bwd(d, dc_in ? dc_in[i] : 0.0f, ig, fg, gg, og, c_out[i], c_prev[c * ld_c + j], di, df, dg, dob, dcp);
         x[j] = di; x[H + j] = df; x[2 * H + j] = dg; x[3 * H + j] = dob;
         if (dgh && dgh != dgx) {
             float *g = dgh + c * 4 * H;
             g[j] = di; g[H + j] = df; g[2 * H + j] = dg; g[3 * H + j] = dob;
         }
-        dc_prev[i] = dc * fg;
+        dc_prev[i] = dcp;
     }
 }
 

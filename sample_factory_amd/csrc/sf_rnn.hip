@@ -23,6 +23,7 @@
 #include <stdlib.h>
 
 #include "sf_common.h"
+#include "sf_rnn_cell.h"
 
 #define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
@@ -859,7 +860,8 @@ __global__ __launch_bounds__(256, 1) void k_gru_seq_bwd(GruSeqBwd p) {
 
 int seq_plan(int Cn, int H, int *ngroups, int *rows_per_group, int *jb) {
     // widths with a compiled instantiation (JB = 16; the k-blocking needs H % 128 == 0 forward, an even number of
-    // 128-column blocks backward: 256 and 512 satisfy both for LSTM and GRU); other widths take the per-step path
+    // 128-column blocks backward: 256 and 512 satisfy both for LSTM and GRU); 32 / 64 / 128 take the row-owned passes
+    // (sf_rnn_rowseq.h), every other width the per-step path
     if (H != 512 && H != 256) return 0;
     *jb = 16;
     int dev = 0, cus = 0;
@@ -877,6 +879,7 @@ int seq_plan(int Cn, int H, int *ngroups, int *rows_per_group, int *jb) {
 }
 
 #include "sf_rnn_regw.h"
+#include "sf_rnn_rowseq.h"
 
 }  // namespace
 
@@ -1051,4 +1054,55 @@ extern "C" int sf_gru_seq_bwd(const float *dout, const float *gates, const float
     const int nsub = (rpg + 63) / 64;
     SEQ_DISPATCH(k_gru_seq_bwd);
     return sf_launch_status("sf_gru_seq_bwd");
+}
+
+// ---- row-owned sequence passes (sf_rnn_rowseq.h): a work-group owns a tile of chunk rows for all R steps
+// grid = ceil(Cn / tile rows of the instantiation)
+#define ROWSEQ_LAUNCH(KERN, K, W) \
+    KERN<K, W><<<dim3((unsigned)((Cn + RowSeqCfg<K, W>::ROWS - 1) / RowSeqCfg<K, W>::ROWS)), dim3(256), 0, STREAM(stream)>>>(p)
+#define ROWSEQ_DISPATCH(KERN)                              \
+    do {                                                   \
+        if (kind == 0 && H == 32) ROWSEQ_LAUNCH(KERN, 0, 32);        \
+        else if (kind == 0 && H == 64) ROWSEQ_LAUNCH(KERN, 0, 64);   \
+        else if (kind == 0) ROWSEQ_LAUNCH(KERN, 0, 128);             \
+        else if (H == 32) ROWSEQ_LAUNCH(KERN, 1, 32);                \
+        else if (H == 64) ROWSEQ_LAUNCH(KERN, 1, 64);                \
+        else ROWSEQ_LAUNCH(KERN, 1, 128);                            \
+    } while (0)
+
+extern "C" int sf_rnn_rowseq_supported(int kind, int Cn, int H) {
+    return (kind == 0 || kind == 1) && Cn > 0 && rowseq_width_ok(H);
+}
+
+extern "C" int sf_rnn_rowseq_fwd(int kind, const float *gx, const float *whh, const float *bhh, const float *keep, float *gates,
+                                 float *hprev, float *hout, float *cprev, float *cout, int R, int Cn, int H, int env_major,
+                                 void *stream) {
+    SF_REQUIRE(sf_rnn_rowseq_supported(kind, Cn, H), "sf_rnn_rowseq_fwd: unsupported kind=%d Cn=%d H=%d (see sf_rnn_rowseq_supported)",
+               kind, Cn, H);
+    SF_REQUIRE(gx && whh && bhh && keep && gates && hprev && hout && R > 0, "sf_rnn_rowseq_fwd: bad args");
+    SF_REQUIRE(kind == 0 || (cprev && cout), "sf_rnn_rowseq_fwd: LSTM needs cprev and cout");
+    SF_REQUIRE(((uintptr_t)whh & 15) == 0 && (((uintptr_t)gx | (uintptr_t)bhh | (uintptr_t)keep | (uintptr_t)gates | (uintptr_t)hprev |
+                                                (uintptr_t)hout | (uintptr_t)cprev | (uintptr_t)cout) & 3) == 0,
+               "sf_rnn_rowseq_fwd: whh must be 16-byte aligned, every other operand 4-byte aligned");
+    RowSeqFwd p{gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, R, Cn,
+                env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H};
+    ROWSEQ_DISPATCH(k_rowseq_fwd);
+    return sf_launch_status("sf_rnn_rowseq_fwd");
+}
+
+extern "C" int sf_rnn_rowseq_bwd(int kind, const float *dout, const float *gates, const float *hprev, const float *cprev,
+                                 const float *cout, const float *keep, const float *whh, float *dgx, float *dgh, int R, int Cn,
+                                 int H, int env_major, void *stream) {
+    SF_REQUIRE(sf_rnn_rowseq_supported(kind, Cn, H), "sf_rnn_rowseq_bwd: unsupported kind=%d Cn=%d H=%d (see sf_rnn_rowseq_supported)",
+               kind, Cn, H);
+    SF_REQUIRE(dout && gates && keep && whh && dgx && R > 0, "sf_rnn_rowseq_bwd: bad args");
+    SF_REQUIRE(kind == 1 || (hprev && dgh), "sf_rnn_rowseq_bwd: GRU needs hprev and dgh");
+    SF_REQUIRE(kind == 0 || (cprev && cout), "sf_rnn_rowseq_bwd: LSTM needs cprev and cout");
+    SF_REQUIRE(((uintptr_t)whh & 15) == 0 && (((uintptr_t)dout | (uintptr_t)gates | (uintptr_t)hprev | (uintptr_t)cprev | (uintptr_t)cout |
+                                                (uintptr_t)keep | (uintptr_t)dgx | (uintptr_t)dgh) & 3) == 0,
+               "sf_rnn_rowseq_bwd: whh must be 16-byte aligned, every other operand 4-byte aligned");
+    RowSeqBwd p{dout, gates, hprev, cprev, cout, keep, whh, dgx, dgh, R, Cn,
+                env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H};
+    ROWSEQ_DISPATCH(k_rowseq_bwd);
+    return sf_launch_status("sf_rnn_rowseq_bwd");
 }

@@ -49,7 +49,7 @@ class sf_res_desc(C.Structure):
 SYMBOLS = [
     "sf_last_error", "sf_abi_version", "sf_valid_mask", "sf_gae_returns", "sf_moments", "sf_rms_update",
     "sf_rms_apply", "sf_vtrace", "sf_ppo_loss", "sf_loss_scalars", "sf_train_summaries", "sf_minibatch_indices", "sf_minibatch_expand", "sf_grad_sumsq",
-    "sf_adam_step", "sf_adam_step_dlr", "sf_lr_kl_adaptive", "sf_clock_probe", "sf_lamb_step", "sf_rnn_cell_fwd", "sf_rnn_cell_bwd", "sf_rows_add_scale", "sf_mlp2_fwd", "sf_rnn_store_state", "sf_rnn_chunk_setup", "sf_lstm_seq_supported", "sf_lstm_seq_fwd", "sf_lstm_seq_bwd", "sf_gru_seq_fwd", "sf_gru_seq_bwd", "sf_seq_fwd_x_supported", "sf_lstm_seq_fwd_x", "sf_gru_seq_fwd_x", "sf_linear_fwd_dual_supported", "sf_linear_fwd_dual",
+    "sf_adam_step", "sf_adam_step_dlr", "sf_lr_kl_adaptive", "sf_clock_probe", "sf_lamb_step", "sf_rnn_cell_fwd", "sf_rnn_cell_bwd", "sf_rows_add_scale", "sf_mlp2_fwd", "sf_rnn_store_state", "sf_rnn_chunk_setup", "sf_lstm_seq_supported", "sf_lstm_seq_fwd", "sf_lstm_seq_bwd", "sf_gru_seq_fwd", "sf_gru_seq_bwd", "sf_seq_fwd_x_supported", "sf_lstm_seq_fwd_x", "sf_gru_seq_fwd_x", "sf_rnn_rowseq_supported", "sf_rnn_rowseq_fwd", "sf_rnn_rowseq_bwd", "sf_linear_fwd_dual_supported", "sf_linear_fwd_dual",
     "sf_obsnorm_moments", "sf_obsnorm_update", "sf_obsnorm_apply", "sf_sample_write_step",
     "sf_sample_write_step_tuple", "sf_sample_write_step_masked", "sf_traj_write_env_step", "sf_synth_obs",
     "sf_synth_step", "sf_synth_vec_step", "sf_h2d_rows", "sf_copy_rows", "sf_conv_fwd", "sf_conv_fwd_workspace", "sf_conv_wgrad_workspace", "sf_conv_wgrad",
@@ -520,6 +520,38 @@ def gru_seq_bwd(dout, gates, hprev, keep, whh, dgx, dgh, sync, R, Cn, H, env_maj
                                      ptr(keep, "f32", "keep"), ptr(whh, "f32", "whh"), ptr(dgx, "f32", "dgx"),
                                      ptr(dgh, "f32", "dgh"), ptr(sync, "i32", "sync"), int(R), int(Cn), int(H),
                                      int(bool(env_major)), stream()), "sf_gru_seq_bwd")
+
+
+def rnn_rowseq_supported(kind: int, Cn: int, H: int) -> bool:
+    return bool(load().sf_rnn_rowseq_supported(int(kind), int(Cn), int(H)))
+
+
+def _rowseq_key(direction, kind, R, Cn, H, steps):
+    """profiling key of a row-owned pass, in _seq_key's layout"""
+    if not _keys_wanted():
+        return None
+    G = 4 if kind else 3
+    return (f"rowseq_{direction}", int(steps * Cn), int(H), 1, 1, int(G * H), 1, 1, 1, 1, f"k_rowseq_{direction}<{int(kind)}, {int(H)}>")
+
+
+def rnn_rowseq_fwd(kind, gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, R, Cn, H, env_major=False) -> None:
+    """sf_rnn_rowseq_fwd: the forward time loop of a narrow GRU (kind 0) / LSTM (1) core in one launch, no sync buffer"""
+    with _timed(_rowseq_key("fwd", kind, R, Cn, H, R)):
+        _check(load().sf_rnn_rowseq_fwd(int(kind), ptr(gx, "f32", "gx"), ptr(whh, "f32", "whh"), ptr(bhh, "f32", "bhh"),
+                                        ptr(keep, "f32", "keep"), ptr(gates, "f32", "gates"), ptr(hprev, "f32", "hprev"),
+                                        ptr(hout, "f32", "hout"), ptr(cprev, "f32", "cprev"), ptr(cout, "f32", "cout"),
+                                        int(R), int(Cn), int(H), int(bool(env_major)), stream()), "sf_rnn_rowseq_fwd")
+
+
+def rnn_rowseq_bwd(kind, dout, gates, hprev, cprev, cout, keep, whh, dgx, dgh, R, Cn, H, env_major=False) -> None:
+    """sf_rnn_rowseq_bwd: the backward time loop of the same pass; writes dgx and, for a GRU, dgh (None for an LSTM, whose two
+    gradients are equal); hprev may be None for an LSTM, cprev / cout for a GRU"""
+    with _timed(_rowseq_key("bwd", kind, R, Cn, H, R - 1)):
+        _check(load().sf_rnn_rowseq_bwd(int(kind), ptr(dout, "f32", "dout"), ptr(gates, "f32", "gates"),
+                                        ptr(hprev, "f32", "hprev"), ptr(cprev, "f32", "cprev"), ptr(cout, "f32", "cout"),
+                                        ptr(keep, "f32", "keep"), ptr(whh, "f32", "whh"), ptr(dgx, "f32", "dgx"),
+                                        ptr(dgh, "f32", "dgh"), int(R), int(Cn), int(H), int(bool(env_major)), stream()),
+               "sf_rnn_rowseq_bwd")
 
 
 def rows_add_scale(a, b, keep, Cn, H, y) -> None:

@@ -13,7 +13,7 @@ with Sample Factory checkpoints; the compute is libsf_hip.so'
  * critic_linear and distribution_linear are one fused [F, 1+A] GEMM (column 0 = value).
 
 Native: conv or MLP encoder (relu/tanh/elu), optional GRU / LSTM core of cfg.rnn_num_layers stacked layers (per-step cell
-kernels; width-512 BPTT passes as ONE persistent launch each, csrc/sf_rnn.hip), MLP decoder, input running-mean-std
+kernels; BPTT passes of widths 256 / 512 and 32 / 64 / 128 as ONE launch each, csrc/sf_rnn.hip), MLP decoder, input running-mean-std
 (normalize_input), Discrete / Tuple-of-Discrete / Box action heads.  This class is the single-key shared-weights model and a
 tower of the composites (model/composite.py): separate actor / critic weights, observation dicts with several keys and the
 resnet_impala encoder.  What the native models refuse raises NotImplementedError; model_factory.py then builds the network
@@ -809,7 +809,14 @@ class ActorCritic(NativeTower):
                 lib.lstm_seq_fwd(GX, Lh.w, Lh.b, keep, gates, Hprev, out, Cprev, Cout, sync, R, Cn, H, env_major=True)
             else:
                 lib.gru_seq_fwd(GX, Lh.w, Lh.b, keep, gates, Hprev, out, sync, R, Cn, H, env_major=True)
-            self._rnn_saved_l[li] = self._rnn_saved = dict(gates=gates, Hprev=Hprev, Cprev=Cprev, Cout=Cout, keep=keep, R=R, Cn=Cn, fused=True)
+            self._rnn_saved_l[li] = self._rnn_saved = dict(gates=gates, Hprev=Hprev, Cprev=Cprev, Cout=Cout, keep=keep, R=R, Cn=Cn,
+                                                           fused=True, family="persistent")
+            return out
+        if _LSTM_SEQ and lib.rnn_rowseq_supported(kind, Cn, H):  # narrow cores: one launch, a work-group owns a tile of chunk
+            # rows for all R steps (csrc/sf_rnn_rowseq.h); no hand-off between work-groups, so no sync buffer and no abort
+            lib.rnn_rowseq_fwd(kind, GX, Lh.w, Lh.b, keep, gates, Hprev, out, Cprev, Cout, R, Cn, H, env_major=True)
+            self._rnn_saved_l[li] = self._rnn_saved = dict(gates=gates, Hprev=Hprev, Cprev=Cprev, Cout=Cout, keep=keep, R=R, Cn=Cn,
+                                                           fused=True, family="row_owned")
             return out
         Hout = self._buf((tag, "Hout", li), (R, Cn, H))
         gh = self._buf((tag, "gh_seq", li), (Cn, GH))
@@ -820,7 +827,8 @@ class ActorCritic(NativeTower):
                              gates[t], Hout[t], Cout[t] if kind == 1 else None, Hprev[t + 1],
                              Cprev[t + 1] if kind == 1 else None)
         out.view(Cn, R, H).copy_(Hout.transpose(0, 1))
-        self._rnn_saved_l[li] = self._rnn_saved = dict(gates=gates, Hprev=Hprev, Cprev=Cprev, Cout=Cout, keep=keep, R=R, Cn=Cn, fused=False)
+        self._rnn_saved_l[li] = self._rnn_saved = dict(gates=gates, Hprev=Hprev, Cprev=Cprev, Cout=Cout, keep=keep, R=R, Cn=Cn,
+                                                       fused=False, family="per_step")
         return out
 
     def _rnn_sequence_bwd(self, li, d_core, n):
@@ -831,12 +839,18 @@ class ActorCritic(NativeTower):
         GH = Lh.N
         dGX = self._buf(("g", "dGX", li), (R, Cn, GH))
         if sv.get("fused"):  # the whole backward time loop in one persistent launch (cell backward + W_hh^T product + carries)
-            sync = self._seq_sync_buf()
             dGH = dGX
             dOut = d_core if d_core.is_contiguous() else d_core.contiguous()  # read in the minibatch's row order
-            if kind == 1:
+            if sv["family"] == "row_owned":
+                if kind == 0:
+                    dGH = self._buf(("g", "dGH", li), (R, Cn, GH))
+                lib.rnn_rowseq_bwd(kind, dOut, sv["gates"], sv["Hprev"], sv["Cprev"], sv["Cout"], keep, Lh.w, dGX,
+                                   dGH if kind == 0 else None, R, Cn, H, env_major=True)
+            elif kind == 1:
+                sync = self._seq_sync_buf()
                 lib.lstm_seq_bwd(dOut, sv["gates"], sv["Cprev"], sv["Cout"], keep, Lh.w, dGX, sync, R, Cn, H, env_major=True)
             else:  # GRU: the candidate gate's recurrent part is scaled by r -> W_hh sees its own gate gradients
+                sync = self._seq_sync_buf()
                 dGH = self._buf(("g", "dGH", li), (R, Cn, GH))
                 lib.gru_seq_bwd(dOut, sv["gates"], sv["Hprev"], keep, Lh.w, dGX, dGH, sync, R, Cn, H, env_major=True)
             ws = self._workspace(lib.conv_wgrad_workspace(n, Lh.desc))
