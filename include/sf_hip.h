@@ -439,10 +439,21 @@ int sf_rnn_chunk_setup(const uint8_t *dones, const uint8_t *valids, const float 
  * (zeroed by the call), word 128 is the STICKY abort word: set by a pass that gave up waiting for a work-group, never
  * cleared by the library (the caller zeroes it once, e.g. at the start of Learner.train, and hands the same word to
  * sf_adam_step / sf_lamb_step as `skip_flag`, so that the garbage gradients of an aborted pass never reach the weights).  sf_lstm_seq_supported: 1 when (Cn, H) can
- * take this path on the current device (H in {256, 512}: 16 hidden units per work-group with their W_hh slice resident in
- * LDS; grid <= #CUs), else use the row-owned passes below (H <= 128) or sf_rnn_cell_fwd/bwd per step.
+ * take this path on the current device AND is offered it (H in {256, 512}, Cn up to the rows of one launch: 16 hidden units
+ * per work-group with their W_hh slice resident in LDS; grid <= #CUs.  The passes run more chunks as row slabs, below, but
+ * there the per-step launches measured 9 - 55 % faster, DESIGN.md 3.4, so the query answers 0 and only a direct call takes
+ * them), else use the row-owned passes below (H <= 128), the wide passes (H = 1024) or
+ * sf_rnn_cell_fwd/bwd per step.
  * sf_lstm_seq_bwd: dout [R][Cn][H] = dL/d hout; writes dgx [R][Cn][4H] = dL/d(gate pre-activations) (= the gradient of
- * both gx and h W_hh^T + b_hh); the carries of dL/dh and dL/dc live in registers.  Cn <= 8 * 256 rows. */
+ * both gx and h W_hh^T + b_hh); the carries of dL/dh and dL/dc live in registers.
+ * Row slabs: one launch serves at most 8 * 256 rows (fewer row groups on a device with fewer CUs:
+ * sf_rnn_seq_slab_rows).  A call with more chunks runs as consecutive launches on `stream`, each over a slab of rows
+ * [r0, r1) of the same dense buffers (Cn stays the row pitch); the counters are zeroed before every launch, the abort
+ * word never; once it is set the remaining slabs are still enqueued and return at their first wait.  Every slab is launched
+ * with the plan a stand-alone call on r1 - r0 rows gets, so its rows are bit-identical to that call's, and a call that fits
+ * one launch is exactly that launch.  Whatever the slabs, a hand-off tensor is addressed as a whole through 32-bit offsets:
+ * (R+1) Cn H 4 and R Cn G H 4 bytes must stay below 2 GiB, and the FORWARD pass refuses a shape whose backward pass would be
+ * refused, so a pass pair fails before anything runs. */
 int sf_lstm_seq_supported(int Cn, int H);
 int sf_lstm_seq_fwd(const float *gx, const float *whh, const float *bhh, const float *keep, float *gates, float *hprev,
                     float *hout, float *cprev, float *cout, uint32_t *sync, int R, int Cn, int H, int env_major,
@@ -470,7 +481,7 @@ int sf_gru_seq_bwd(const float *dout, const float *gates, const float *hprev, co
  * bih [G*H]; every work-group multiplies its own gate columns, the products of step t+1 run while it waits for the
  * other work-groups' h_t.  gx_t = x_t W_ih^T + b_ih is formed in f32 exactly as the GEMM's epilogue does (MFMA sum, then
  * + b_ih), then used as in sf_lstm_seq_fwd / sf_gru_seq_fwd.  sf_seq_fwd_x_supported: Kx == 64 and row groups of at
- * most 128 rows (Cn <= 1024 on 256 CUs), else project with sf_conv_fwd_t and call the gx form. */
+ * most 128 rows (Cn <= 1024 on 256 CUs; one launch, never slabs), else project with sf_conv_fwd_t and call the gx form. */
 int sf_seq_fwd_x_supported(int Cn, int H, int Kx);
 int sf_lstm_seq_fwd_x(const float *x, const float *wih_t, const float *bih, int Kx, const float *whh, const float *bhh,
                       const float *keep, float *gates, float *hprev, float *hout, float *cprev, float *cout,
@@ -502,6 +513,30 @@ int sf_rnn_rowseq_fwd(int kind, const float *gx, const float *whh, const float *
 int sf_rnn_rowseq_bwd(int kind, const float *dout, const float *gates, const float *hprev, const float *cprev,
                       const float *cout, const float *keep, const float *whh, float *dgx, float *dgh,
                       int R, int Cn, int H, int env_major, void *stream);
+
+/* ---- persistent sequence passes at H = 1024 (kind 0 = GRU, 1 = LSTM) ---------------------------------------------------
+ * The scheme of sf_lstm_seq_* / sf_gru_seq_* with 8 hidden units per work-group, at which both W_hh slices fit LDS
+ * (forward 32 gate columns x 1028 floats, backward 8 rows x (G*H + 4) floats); 128 work-groups form a row group, a launch
+ * serves min(8, #CUs / 128) row groups of at most 256 rows (512 rows on 256 CUs) and more rows run as slabs, exactly as
+ * above.  Operands, layouts, `sync` (counters + sticky abort word) and env_major are those of sf_lstm_seq_* /
+ * sf_gru_seq_*; cprev / cout are NULL for a GRU; backward: hprev and dgh may be NULL for an LSTM (both gradients are dgx).
+ * Exact-f32 MFMA products in one k-order per output element (it depends on the hidden unit only), so a row's results are
+ * bit-identical whatever Cn, slab or row group it lands in; the cell arithmetic is the device code of sf_rnn_cell_fwd /
+ * sf_rnn_cell_bwd.  hprev, whh and the gate-gradient payload (dgx for an LSTM, dgh for a GRU) must be 16-byte aligned.
+ * sf_rnn_wideseq_supported: 1 for H == 1024, kind 0 / 1, 0 < Cn <= 64 (GRU) / 512 (LSTM) on a device with at least 128
+ * CUs: the chunk range in which Learner.train was shown faster than on the per-step launches by more than the spread
+ * (the GRU is level with them at 512 chunks, and at 2048 the per-step GEMMs win by 1.8 - 1.9 x).  The two passes themselves run any Cn > 0 at this width; any other kind or
+ * width, or a bad operand, returns an error before anything is launched.
+ * sf_rnn_seq_slab_rows(kind, H, pass): the largest number of rows ONE launch of the forward (pass 0) / backward (pass 1)
+ * pass serves on the current device, for every width with a persistent pass (256, 512, 1024); 0 for any other width. */
+int sf_rnn_wideseq_supported(int kind, int Cn, int H);
+int sf_rnn_seq_slab_rows(int kind, int H, int pass);
+int sf_rnn_wideseq_fwd(int kind, const float *gx, const float *whh, const float *bhh, const float *keep, float *gates,
+                       float *hprev, float *hout, float *cprev, float *cout, uint32_t *sync, int R, int Cn, int H,
+                       int env_major, void *stream);
+int sf_rnn_wideseq_bwd(int kind, const float *dout, const float *gates, const float *hprev, const float *cprev,
+                       const float *cout, const float *keep, const float *whh, float *dgx, float *dgh, uint32_t *sync,
+                       int R, int Cn, int H, int env_major, void *stream);
 
 /* ---- data-parallel learner replicas (SURVEY.md §8(b) "DP -> sf_allreduce_grads", §8(e)) ----------------------------
  * New capability: the reference runs ONE learner per policy (algo/utils/shared_buffers.py:26-32), so these replace no

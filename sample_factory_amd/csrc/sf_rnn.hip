@@ -104,10 +104,12 @@ struct LstmSeqFwd {
     // KXB > 0 (sf_lstm_seq_fwd_x): gx is not given but computed here, x [R][Cn][16*KXB] (time-major), wih_t [4H][16*KXB]
     // (gate-column-major copy of W_ih), bih [4H]
     const float *x, *wih_t, *bih;
+    int row0, row_end;  // this launch covers rows [row0, row_end) of the Cn-row buffers (Cn stays the row pitch)
 };
 
 // H hidden units, JB of them per work-group (JB = 16: the W_hh slice is 64 x (H + 4) floats of LDS — 129 KB at H = 512,
-// 66.5 KB at H = 256; H = 1024 would need 263 KB, i.e. JB = 8 and a different accumulator-to-lane mapping: not built).
+// 66.5 KB at H = 256; H = 1024 would need 263 KB: that width runs with JB = 8 and its own accumulator-to-lane mapping,
+// k_wideseq_fwd in sf_rnn_wideseq.h).
 // KXB > 0: the input projection gx_t = x_t W_ih^T + b_ih (KXB 16-column blocks of x) is computed HERE instead of by a GEMM
 // launch that writes [R][Cn][4H] floats for this kernel to read back: the W_ih fragments of the work-group's 64 gate
 // columns live in registers, the x fragments of step t+1 are fetched behind step t's hand-off, and the 16*KXB MFMAs run
@@ -150,8 +152,8 @@ __global__ __launch_bounds__(256, 1) void k_lstm_seq_fwd(LstmSeqFwd p) {
         }
     __syncthreads();
     const auto h_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)p.hprev, 0, (int)((int64_t)(R + 1) * Cn * H * 4), 0x00020000);
-    const int g_row0 = group * p.rows_per_group;
-    const int g_rows_end = min(Cn, g_row0 + p.rows_per_group);
+    const int g_row0 = p.row0 + group * p.rows_per_group;  // [row0, row_end): the slab of rows this launch covers
+    const int g_rows_end = min(p.row_end, g_row0 + p.rows_per_group);
 
     // the cell state of this lane's (row, unit) elements stays in registers across the steps (the masked copy is also
     // stored to cprev[t+1] for the backward pass); sub-tiles are unrolled so that the register arrays index statically
@@ -329,6 +331,7 @@ struct LstmSeqBwd {
     int64_t do_rs, do_ts;  // dout element (row, t) lives at row*do_rs + t*do_ts (+ unit)
     int ablate;  // timing experiments only (SF_LSTM_ABLATE, tools/lstm_bench.py): 1 no hand-off wait, 2 no phase-B loads,
                  // 4 no phase-B MFMAs, 8 no phase A — results are wrong with any bit set
+    int row0, row_end;  // (see LstmSeqFwd)
 };
 
 template <int H, int JB, int NSUB>
@@ -355,8 +358,8 @@ __global__ __launch_bounds__(256, 1) void k_lstm_seq_bwd(LstmSeqBwd p) {
     }
     __syncthreads();
     const auto d_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)p.dgx, 0, (int)((int64_t)R * Cn * G4 * 4), 0x00020000);
-    const int g_row0 = group * p.rows_per_group;
-    const int g_rows_end = min(Cn, g_row0 + p.rows_per_group);
+    const int g_row0 = p.row0 + group * p.rows_per_group;  // [row0, row_end): the slab of rows this launch covers
+    const int g_rows_end = min(p.row_end, g_row0 + p.rows_per_group);
 
     // dL/dh and dL/dc carried from step t+1 to step t for this lane's (row, unit) elements: registers
     float car_h[NSUB][4][NU], car_c[NSUB][4][NU];
@@ -503,6 +506,7 @@ struct GruSeqFwd {
     int R, Cn, ngroups, rows_per_group;
     int64_t ho_rs, ho_ts;
     const float *x, *wih_t, *bih;  // KXB > 0 (sf_gru_seq_fwd_x): see LstmSeqFwd
+    int row0, row_end;
 };
 
 template <int H, int JB, int NSUB, int KXB>
@@ -541,8 +545,8 @@ __global__ __launch_bounds__(256, 1) void k_gru_seq_fwd(GruSeqFwd p) {
         }
     __syncthreads();
     const auto h_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)p.hprev, 0, (int)((int64_t)(R + 1) * Cn * H * 4), 0x00020000);
-    const int g_row0 = group * p.rows_per_group;
-    const int g_rows_end = min(Cn, g_row0 + p.rows_per_group);
+    const int g_row0 = p.row0 + group * p.rows_per_group;  // [row0, row_end): the slab of rows this launch covers
+    const int g_rows_end = min(p.row_end, g_row0 + p.rows_per_group);
     float hst[NSUB][4][NU];  // masked state entering the step, for this lane's (row, unit) elements
 #pragma unroll
     for (int sub = 0; sub < NSUB; ++sub) {
@@ -702,6 +706,7 @@ struct GruSeqBwd {
     unsigned *sync;
     int R, Cn, ngroups, rows_per_group;
     int64_t do_rs, do_ts;
+    int row0, row_end;
 };
 
 template <int H, int JB, int NSUB>
@@ -727,8 +732,8 @@ __global__ __launch_bounds__(256, 1) void k_gru_seq_bwd(GruSeqBwd p) {
     }
     __syncthreads();
     const auto d_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)p.dgh, 0, (int)((int64_t)R * Cn * G3 * 4), 0x00020000);
-    const int g_row0 = group * p.rows_per_group;
-    const int g_rows_end = min(Cn, g_row0 + p.rows_per_group);
+    const int g_row0 = p.row0 + group * p.rows_per_group;  // [row0, row_end): the slab of rows this launch covers
+    const int g_rows_end = min(p.row_end, g_row0 + p.rows_per_group);
     float car_h[NSUB][4][NU];
 #pragma unroll
     for (int sub = 0; sub < NSUB; ++sub)
@@ -858,10 +863,14 @@ __global__ __launch_bounds__(256, 1) void k_gru_seq_bwd(GruSeqBwd p) {
     }
 }
 
+// The plan of ONE launch over Cn rows: row groups (at most 8, at most #CUs / (H / JB)) of at most 64 * SEQ_MAX_SUB rows.
+// Rows of a pass are independent, so a call with more rows than one launch serves runs as consecutive launches over row
+// slabs [r0, r1) of the same buffers (seq_slab_rows rows each, the last one shorter); every slab gets the plan of a
+// stand-alone call on r1 - r0 rows, which makes its results those of that call bit for bit.
 int seq_plan(int Cn, int H, int *ngroups, int *rows_per_group, int *jb) {
     // widths with a compiled instantiation (JB = 16; the k-blocking needs H % 128 == 0 forward, an even number of
     // 128-column blocks backward: 256 and 512 satisfy both for LSTM and GRU); 32 / 64 / 128 take the row-owned passes
-    // (sf_rnn_rowseq.h), every other width the per-step path
+    // (sf_rnn_rowseq.h), 1024 the 8-unit passes of sf_rnn_wideseq.h, every other width the per-step path
     if (H != 512 && H != 256) return 0;
     *jb = 16;
     int dev = 0, cus = 0;
@@ -878,8 +887,26 @@ int seq_plan(int Cn, int H, int *ngroups, int *rows_per_group, int *jb) {
     return *rows_per_group <= 64 * SEQ_MAX_SUB;
 }
 
+// rows of one slab = the largest Cn seq_plan accepts on this device (2048 on 256 CUs); 0: no fused pass at this width.
+// Both passes use it: a backward slab of this height runs k_*_seq_bwd (LDS), a shorter tail whatever seq_plan_r /
+// seq_plan give a call of its size.  (1024-row slabs on the register-resident backward would make a 1025..2048-row call,
+// one LDS launch today, differ from its own first slab; DESIGN.md 3.4 has the timing of both heights, taken with
+// tools/experiments/sf_rnn_bwd_slab_regw_not_kept.patch.)
+// The kernels address a whole [slot][Cn][width] tensor through ONE 32-bit buffer resource, so a call is limited to 2 GiB per
+// hand-off tensor whatever the slabs; the forward entry points check the backward pass's tensor as well.
+int seq_slab_rows(int H) {
+    if (H != 512 && H != 256) return 0;
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        return 0;
+    int ng = cus / (H / 16);
+    if (ng > 8) ng = 8;
+    return ng < 1 ? 0 : ng * 64 * SEQ_MAX_SUB;
+}
+
 #include "sf_rnn_regw.h"
 #include "sf_rnn_rowseq.h"
+#include "sf_rnn_wideseq.h"
 
 }  // namespace
 
@@ -921,8 +948,10 @@ int seq_plan(int Cn, int H, int *ngroups, int *rows_per_group, int *jb) {
     } while (0)
 
 extern "C" int sf_lstm_seq_supported(int Cn, int H) {
-    int a, b, c;
-    return Cn > 0 && seq_plan(Cn, H, &a, &b, &c);
+    // the OFFER ends at one launch, as before row slabs: on them Learner.train measured 1.09 - 1.55 x the per-step time at
+    // 4096 / 8192 chunks (tools/wideseq_bench.py; nothing was measured in between).  The passes themselves run
+    // any Cn > 0 as slabs; a caller that wants them beyond the offer calls the entry points.
+    return Cn > 0 && Cn <= seq_slab_rows(H);
 }
 
 static int lstm_seq_fwd_impl(const float *gx, const float *x, const float *wih_t, const float *bih, int Kx,
@@ -930,22 +959,33 @@ static int lstm_seq_fwd_impl(const float *gx, const float *x, const float *wih_t
                              float *cprev, float *cout, uint32_t *sync, int R, int Cn, int H, int env_major, void *stream) {
     SF_REQUIRE((gx || (x && wih_t && bih)) && whh && bhh && keep && gates && hprev && hout && cprev && cout && sync && R > 0 && Cn > 0,
                "sf_lstm_seq_fwd: bad args");
-    int ng, rpg, jb;
-    SF_REQUIRE(seq_plan(Cn, H, &ng, &rpg, &jb), "sf_lstm_seq_fwd: unsupported shape Cn=%d H=%d (see sf_lstm_seq_supported)", Cn, H);
+    const int slab = seq_slab_rows(H);
+    SF_REQUIRE(slab > 0, "sf_lstm_seq_fwd: unsupported shape Cn=%d H=%d (see sf_lstm_seq_supported)", Cn, H);
     SF_REQUIRE((int64_t)(R + 1) * Cn * H * 4 < 0x7FFFFFF0LL, "sf_lstm_seq_fwd: state buffer exceeds 2 GiB");
-    const int nsub = (rpg + 63) / 64;  // 64-row sub-tiles per work-group, unrolled at compile time (register-resident state)
-    if (!gx)
-        SF_REQUIRE(Kx == 64 && nsub <= 2 && (((uintptr_t)x | (uintptr_t)wih_t) & 15) == 0,
+    // (the backward pass's limit, checked HERE too: a pass pair is refused before its forward half runs)
+    SF_REQUIRE((int64_t)R * Cn * 4 * H * 4 < 0x7FFFFFF0LL, "sf_lstm_seq_fwd: the backward pass's gate-gradient buffer would exceed 2 GiB");
+    if (!gx) {  // the fused input projection is a one-launch feature
+        int ng, rpg, jb;
+        SF_REQUIRE(Kx == 64 && seq_plan(Cn, H, &ng, &rpg, &jb) && (rpg + 63) / 64 <= 2 && (((uintptr_t)x | (uintptr_t)wih_t) & 15) == 0,
                    "sf_lstm_seq_fwd_x: unsupported shape Cn=%d H=%d Kx=%d (see sf_seq_fwd_x_supported)", Cn, H, Kx);
-    int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_lstm_seq_fwd memset");
-    if (rc) return rc;
-    // hout [R][Cn][H] (time-major) or, env_major, [Cn][R][H] = the row order of the minibatch itself (no transpose copy)
-    LstmSeqFwd p{gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, ng, rpg,
-                 env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, x, wih_t, bih};
-    const dim3 grid((unsigned)(ng * (H / jb))), block(256);
-    if (gx) SEQ_DISPATCH(k_lstm_seq_fwd, , 0);
-    else SEQ_DISPATCH_X(k_lstm_seq_fwd);
-    return sf_launch_status("sf_lstm_seq_fwd");
+    }
+    for (int r0 = 0; r0 < Cn; r0 += slab) {  // one launch per row slab (a single one up to `slab` rows)
+        const int r1 = Cn - r0 < slab ? Cn : r0 + slab;
+        int ng, rpg, jb;
+        SF_REQUIRE(seq_plan(r1 - r0, H, &ng, &rpg, &jb), "sf_lstm_seq_fwd: no plan for %d rows at H=%d", r1 - r0, H);
+        const int nsub = (rpg + 63) / 64;  // 64-row sub-tiles per work-group, unrolled at compile time (register-resident state)
+        int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_lstm_seq_fwd memset");
+        if (rc) return rc;
+        // hout [R][Cn][H] (time-major) or, env_major, [Cn][R][H] = the row order of the minibatch itself (no transpose copy)
+        LstmSeqFwd p{gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, ng, rpg,
+                     env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, x, wih_t, bih, r0, r1};
+        const dim3 grid((unsigned)(ng * (H / jb))), block(256);
+        if (gx) SEQ_DISPATCH(k_lstm_seq_fwd, , 0);
+        else SEQ_DISPATCH_X(k_lstm_seq_fwd);
+        rc = sf_launch_status("sf_lstm_seq_fwd");
+        if (rc) return rc;
+    }
+    return 0;
 }
 extern "C" int sf_lstm_seq_fwd(const float *gx, const float *whh, const float *bhh, const float *keep, float *gates,
                                float *hprev, float *hout, float *cprev, float *cout, uint32_t *sync, int R, int Cn, int H,
@@ -972,27 +1012,34 @@ extern "C" int sf_lstm_seq_bwd(const float *dout, const float *gates, const floa
                                int env_major, void *stream) {
     SF_REQUIRE(dout && gates && cprev && cout && keep && whh && dgx && sync && R > 0 && Cn > 0,
                "sf_lstm_seq_bwd: bad args");
-    int ng, rpg, jb;
-    SF_REQUIRE(seq_plan(Cn, H, &ng, &rpg, &jb), "sf_lstm_seq_bwd: unsupported shape Cn=%d H=%d (see sf_lstm_seq_supported)", Cn, H);
+    const int slab = seq_slab_rows(H);
+    SF_REQUIRE(slab > 0, "sf_lstm_seq_bwd: unsupported shape Cn=%d H=%d (see sf_lstm_seq_supported)", Cn, H);
     SF_REQUIRE((int64_t)R * Cn * 4 * H * 4 < 0x7FFFFFF0LL, "sf_lstm_seq_bwd: gate-gradient buffer exceeds 2 GiB");
-    int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_lstm_seq_bwd memset");
-    if (rc) return rc;
     static const int ablate = getenv("SF_LSTM_ABLATE") ? atoi(getenv("SF_LSTM_ABLATE")) : 0;
-    int ngr, rpgr;
-    if (seq_plan_r(Cn, H, &ngr, &rpgr)) {  // 32 hidden units per work-group, W_hh slice in registers
-        const int rpg = rpgr;
-        LstmSeqBwd p{dout, gates, cprev, cout, keep, whh, dgx, sync, R, Cn, ngr, rpg,
-                     env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, ablate};
-        const dim3 grid((unsigned)(ngr * (H / 32))), block(256);
-        SEQ_DISPATCH_R(k_lstm_seq_bwd_r);
-        return sf_launch_status("sf_lstm_seq_bwd");
+    for (int r0 = 0; r0 < Cn; r0 += slab) {  // one launch per row slab (a single one up to `slab` rows)
+        const int r1 = Cn - r0 < slab ? Cn : r0 + slab;
+        int ng, rpg, jb;
+        SF_REQUIRE(seq_plan(r1 - r0, H, &ng, &rpg, &jb), "sf_lstm_seq_bwd: no plan for %d rows at H=%d", r1 - r0, H);
+        int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_lstm_seq_bwd memset");
+        if (rc) return rc;
+        int ngr, rpgr;
+        if (seq_plan_r(r1 - r0, H, &ngr, &rpgr)) {  // 32 hidden units per work-group, W_hh slice in registers
+            const int rpg = rpgr;
+            LstmSeqBwd p{dout, gates, cprev, cout, keep, whh, dgx, sync, R, Cn, ngr, rpg,
+                         env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, ablate, r0, r1};
+            const dim3 grid((unsigned)(ngr * (H / 32))), block(256);
+            SEQ_DISPATCH_R(k_lstm_seq_bwd_r);
+        } else {
+            LstmSeqBwd p{dout, gates, cprev, cout, keep, whh, dgx, sync, R, Cn, ng, rpg,
+                         env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, ablate, r0, r1};
+            const dim3 grid((unsigned)(ng * (H / jb))), block(256);
+            const int nsub = (rpg + 63) / 64;
+            SEQ_DISPATCH(k_lstm_seq_bwd);
+        }
+        rc = sf_launch_status("sf_lstm_seq_bwd");
+        if (rc) return rc;
     }
-    LstmSeqBwd p{dout, gates, cprev, cout, keep, whh, dgx, sync, R, Cn, ng, rpg,
-                 env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, ablate};
-    const dim3 grid((unsigned)(ng * (H / jb))), block(256);
-    const int nsub = (rpg + 63) / 64;
-    SEQ_DISPATCH(k_lstm_seq_bwd);
-    return sf_launch_status("sf_lstm_seq_bwd");
+    return 0;
 }
 
 static int gru_seq_fwd_impl(const float *gx, const float *x, const float *wih_t, const float *bih, int Kx, const float *whh,
@@ -1000,21 +1047,31 @@ static int gru_seq_fwd_impl(const float *gx, const float *x, const float *wih_t,
                             int R, int Cn, int H, int env_major, void *stream) {
     SF_REQUIRE((gx || (x && wih_t && bih)) && whh && bhh && keep && gates && hprev && hout && sync && R > 0 && Cn > 0,
                "sf_gru_seq_fwd: bad args");
-    int ng, rpg, jb;
-    SF_REQUIRE(seq_plan(Cn, H, &ng, &rpg, &jb), "sf_gru_seq_fwd: unsupported shape Cn=%d H=%d (see sf_lstm_seq_supported)", Cn, H);
+    const int slab = seq_slab_rows(H);
+    SF_REQUIRE(slab > 0, "sf_gru_seq_fwd: unsupported shape Cn=%d H=%d (see sf_lstm_seq_supported)", Cn, H);
     SF_REQUIRE((int64_t)(R + 1) * Cn * H * 4 < 0x7FFFFFF0LL, "sf_gru_seq_fwd: state buffer exceeds 2 GiB");
-    const int nsub = (rpg + 63) / 64;
-    if (!gx)
-        SF_REQUIRE(Kx == 64 && nsub <= 2 && (((uintptr_t)x | (uintptr_t)wih_t) & 15) == 0,
+    SF_REQUIRE((int64_t)R * Cn * 3 * H * 4 < 0x7FFFFFF0LL, "sf_gru_seq_fwd: the backward pass's gate-gradient buffer would exceed 2 GiB");
+    if (!gx) {  // the fused input projection is a one-launch feature
+        int ng, rpg, jb;
+        SF_REQUIRE(Kx == 64 && seq_plan(Cn, H, &ng, &rpg, &jb) && (rpg + 63) / 64 <= 2 && (((uintptr_t)x | (uintptr_t)wih_t) & 15) == 0,
                    "sf_gru_seq_fwd_x: unsupported shape Cn=%d H=%d Kx=%d (see sf_seq_fwd_x_supported)", Cn, H, Kx);
-    int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_gru_seq_fwd memset");
-    if (rc) return rc;
-    GruSeqFwd p{gx, whh, bhh, keep, gates, hprev, hout, sync, R, Cn, ng, rpg,
-                env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, x, wih_t, bih};
-    const dim3 grid((unsigned)(ng * (H / jb))), block(256);
-    if (gx) SEQ_DISPATCH(k_gru_seq_fwd, , 0);
-    else SEQ_DISPATCH_X(k_gru_seq_fwd);
-    return sf_launch_status("sf_gru_seq_fwd");
+    }
+    for (int r0 = 0; r0 < Cn; r0 += slab) {  // one launch per row slab (a single one up to `slab` rows)
+        const int r1 = Cn - r0 < slab ? Cn : r0 + slab;
+        int ng, rpg, jb;
+        SF_REQUIRE(seq_plan(r1 - r0, H, &ng, &rpg, &jb), "sf_gru_seq_fwd: no plan for %d rows at H=%d", r1 - r0, H);
+        const int nsub = (rpg + 63) / 64;
+        int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_gru_seq_fwd memset");
+        if (rc) return rc;
+        GruSeqFwd p{gx, whh, bhh, keep, gates, hprev, hout, sync, R, Cn, ng, rpg,
+                    env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, x, wih_t, bih, r0, r1};
+        const dim3 grid((unsigned)(ng * (H / jb))), block(256);
+        if (gx) SEQ_DISPATCH(k_gru_seq_fwd, , 0);
+        else SEQ_DISPATCH_X(k_gru_seq_fwd);
+        rc = sf_launch_status("sf_gru_seq_fwd");
+        if (rc) return rc;
+    }
+    return 0;
 }
 extern "C" int sf_gru_seq_fwd(const float *gx, const float *whh, const float *bhh, const float *keep, float *gates,
                               float *hprev, float *hout, uint32_t *sync, int R, int Cn, int H, int env_major,
@@ -1034,26 +1091,33 @@ extern "C" int sf_gru_seq_bwd(const float *dout, const float *gates, const float
                               const float *whh, float *dgx, float *dgh, uint32_t *sync, int R, int Cn, int H,
                               int env_major, void *stream) {
     SF_REQUIRE(dout && gates && hprev && keep && whh && dgx && dgh && sync && R > 0 && Cn > 0, "sf_gru_seq_bwd: bad args");
-    int ng, rpg, jb;
-    SF_REQUIRE(seq_plan(Cn, H, &ng, &rpg, &jb), "sf_gru_seq_bwd: unsupported shape Cn=%d H=%d (see sf_lstm_seq_supported)", Cn, H);
+    const int slab = seq_slab_rows(H);
+    SF_REQUIRE(slab > 0, "sf_gru_seq_bwd: unsupported shape Cn=%d H=%d (see sf_lstm_seq_supported)", Cn, H);
     SF_REQUIRE((int64_t)R * Cn * 3 * H * 4 < 0x7FFFFFF0LL, "sf_gru_seq_bwd: gate-gradient buffer exceeds 2 GiB");
-    int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_gru_seq_bwd memset");
-    if (rc) return rc;
-    int ngr, rpgr;
-    if (seq_plan_r(Cn, H, &ngr, &rpgr)) {
-        const int rpg = rpgr;
-        GruSeqBwd p{dout, gates, hprev, keep, whh, dgx, dgh, sync, R, Cn, ngr, rpg,
-                    env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H};
-        const dim3 grid((unsigned)(ngr * (H / 32))), block(256);
-        SEQ_DISPATCH_R(k_gru_seq_bwd_r);
-        return sf_launch_status("sf_gru_seq_bwd");
+    for (int r0 = 0; r0 < Cn; r0 += slab) {  // one launch per row slab (a single one up to `slab` rows)
+        const int r1 = Cn - r0 < slab ? Cn : r0 + slab;
+        int ng, rpg, jb;
+        SF_REQUIRE(seq_plan(r1 - r0, H, &ng, &rpg, &jb), "sf_gru_seq_bwd: no plan for %d rows at H=%d", r1 - r0, H);
+        int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_gru_seq_bwd memset");
+        if (rc) return rc;
+        int ngr, rpgr;
+        if (seq_plan_r(r1 - r0, H, &ngr, &rpgr)) {
+            const int rpg = rpgr;
+            GruSeqBwd p{dout, gates, hprev, keep, whh, dgx, dgh, sync, R, Cn, ngr, rpg,
+                        env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, r0, r1};
+            const dim3 grid((unsigned)(ngr * (H / 32))), block(256);
+            SEQ_DISPATCH_R(k_gru_seq_bwd_r);
+        } else {
+            GruSeqBwd p{dout, gates, hprev, keep, whh, dgx, dgh, sync, R, Cn, ng, rpg,
+                        env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, r0, r1};
+            const dim3 grid((unsigned)(ng * (H / jb))), block(256);
+            const int nsub = (rpg + 63) / 64;
+            SEQ_DISPATCH(k_gru_seq_bwd);
+        }
+        rc = sf_launch_status("sf_gru_seq_bwd");
+        if (rc) return rc;
     }
-    GruSeqBwd p{dout, gates, hprev, keep, whh, dgx, dgh, sync, R, Cn, ng, rpg,
-                env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H};
-    const dim3 grid((unsigned)(ng * (H / jb))), block(256);
-    const int nsub = (rpg + 63) / 64;
-    SEQ_DISPATCH(k_gru_seq_bwd);
-    return sf_launch_status("sf_gru_seq_bwd");
+    return 0;
 }
 
 // ---- row-owned sequence passes (sf_rnn_rowseq.h): a work-group owns a tile of chunk rows for all R steps
@@ -1105,4 +1169,102 @@ extern "C" int sf_rnn_rowseq_bwd(int kind, const float *dout, const float *gates
                 env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H};
     ROWSEQ_DISPATCH(k_rowseq_bwd);
     return sf_launch_status("sf_rnn_rowseq_bwd");
+}
+
+// ---- persistent passes at H = 1024 (sf_rnn_wideseq.h): 8 hidden units per work-group, row slabs as above
+#define WIDESEQ_DISPATCH(KERN)                                                                    \
+    do {                                                                                          \
+        if (kind == 0) {                                                                          \
+            if (nsub == 1) KERN<0, 1><<<grid, block, 0, STREAM(stream)>>>(p);                     \
+            else if (nsub == 2) KERN<0, 2><<<grid, block, 0, STREAM(stream)>>>(p);                \
+            else KERN<0, 4><<<grid, block, 0, STREAM(stream)>>>(p);                               \
+        } else {                                                                                  \
+            if (nsub == 1) KERN<1, 1><<<grid, block, 0, STREAM(stream)>>>(p);                     \
+            else if (nsub == 2) KERN<1, 2><<<grid, block, 0, STREAM(stream)>>>(p);                \
+            else KERN<1, 4><<<grid, block, 0, STREAM(stream)>>>(p);                               \
+        }                                                                                         \
+    } while (0)
+
+// what the wide kernels can run: any Cn > 0 (row slabs beyond one launch)
+static int wideseq_shape_ok(int kind, int Cn, int H) {
+    return (kind == 0 || kind == 1) && Cn > 0 && H == WIDE_H && wide_groups_max() >= 1;
+}
+// what they are OFFERED for: the chunk range in which Learner.train measured faster than on the per-step launches
+// by more than the spread (tools/wideseq_bench.py).  Measured at 64 / 512 / 2048 chunks: 0.40 / 0.99 / 1.91 of
+// the per-step time for the GRU, 0.41 / 0.96 / 1.77 for the LSTM — the pass pulls rows x 1024 floats of h per work-group and
+// step through L2 whatever the batch, the per-step GEMMs gain with it.  The GRU's 1 % at 512 chunks is inside the spread (it
+// was outside in an earlier run), so the GRU is offered up to the largest chunk count that was SHOWN faster, 64; nothing
+// between 64 and 512 was measured.
+constexpr int WIDE_OFFER_MAX_CN[2] = {64, 512};  // GRU, LSTM
+extern "C" int sf_rnn_wideseq_supported(int kind, int Cn, int H) {
+    return wideseq_shape_ok(kind, Cn, H) && Cn <= WIDE_OFFER_MAX_CN[kind];
+}
+
+extern "C" int sf_rnn_seq_slab_rows(int kind, int H, int pass) {
+    if ((kind != 0 && kind != 1) || (pass != 0 && pass != 1)) return 0;
+    if (H == WIDE_H) return wide_groups_max() * 64 * SEQ_MAX_SUB;
+    return seq_slab_rows(H);
+}
+
+extern "C" int sf_rnn_wideseq_fwd(int kind, const float *gx, const float *whh, const float *bhh, const float *keep, float *gates,
+                                  float *hprev, float *hout, float *cprev, float *cout, uint32_t *sync, int R, int Cn, int H,
+                                  int env_major, void *stream) {
+    SF_REQUIRE(wideseq_shape_ok(kind, Cn, H), "sf_rnn_wideseq_fwd: unsupported kind=%d Cn=%d H=%d (see sf_rnn_wideseq_supported)",
+               kind, Cn, H);
+    SF_REQUIRE(gx && whh && bhh && keep && gates && hprev && hout && sync && R > 0, "sf_rnn_wideseq_fwd: bad args");
+    SF_REQUIRE(kind == 0 || (cprev && cout), "sf_rnn_wideseq_fwd: LSTM needs cprev and cout");
+    SF_REQUIRE(((uintptr_t)hprev & 15) == 0 && (((uintptr_t)gx | (uintptr_t)whh | (uintptr_t)bhh | (uintptr_t)keep | (uintptr_t)gates |
+                                                  (uintptr_t)hout | (uintptr_t)cprev | (uintptr_t)cout | (uintptr_t)sync) & 3) == 0,
+               "sf_rnn_wideseq_fwd: hprev must be 16-byte aligned, every other operand 4-byte aligned");
+    SF_REQUIRE((int64_t)(R + 1) * Cn * H * 4 < 0x7FFFFFF0LL, "sf_rnn_wideseq_fwd: state buffer exceeds 2 GiB");
+    SF_REQUIRE((int64_t)R * Cn * (kind ? 4 : 3) * H * 4 < 0x7FFFFFF0LL,
+               "sf_rnn_wideseq_fwd: the backward pass's gate-gradient buffer would exceed 2 GiB");
+    const int slab = sf_rnn_seq_slab_rows(kind, H, 0);
+    for (int r0 = 0; r0 < Cn; r0 += slab) {
+        const int r1 = Cn - r0 < slab ? Cn : r0 + slab;
+        int ng, rpg;
+        SF_REQUIRE(wide_plan(r1 - r0, &ng, &rpg), "sf_rnn_wideseq_fwd: no plan for %d rows", r1 - r0);
+        const int nsub = (rpg + 63) / 64;
+        int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_rnn_wideseq_fwd memset");
+        if (rc) return rc;
+        WideSeqFwd p{gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, ng, rpg, r0, r1,
+                     env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H};
+        const dim3 grid((unsigned)(ng * WIDE_NCOL)), block(256);
+        WIDESEQ_DISPATCH(k_wideseq_fwd);
+        rc = sf_launch_status("sf_rnn_wideseq_fwd");
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+extern "C" int sf_rnn_wideseq_bwd(int kind, const float *dout, const float *gates, const float *hprev, const float *cprev,
+                                  const float *cout, const float *keep, const float *whh, float *dgx, float *dgh, uint32_t *sync,
+                                  int R, int Cn, int H, int env_major, void *stream) {
+    SF_REQUIRE(wideseq_shape_ok(kind, Cn, H), "sf_rnn_wideseq_bwd: unsupported kind=%d Cn=%d H=%d (see sf_rnn_wideseq_supported)",
+               kind, Cn, H);
+    SF_REQUIRE(dout && gates && keep && whh && dgx && sync && R > 0, "sf_rnn_wideseq_bwd: bad args");
+    SF_REQUIRE(kind == 1 || (hprev && dgh), "sf_rnn_wideseq_bwd: GRU needs hprev and dgh");
+    SF_REQUIRE(kind == 0 || (cprev && cout), "sf_rnn_wideseq_bwd: LSTM needs cprev and cout");
+    float *pay = kind == 0 ? dgh : dgx;  // the hand-off payload: 16-byte stores and loads
+    SF_REQUIRE((((uintptr_t)pay | (uintptr_t)whh) & 15) == 0 &&
+                   (((uintptr_t)dout | (uintptr_t)gates | (uintptr_t)hprev | (uintptr_t)cprev | (uintptr_t)cout | (uintptr_t)keep |
+                     (uintptr_t)dgx | (uintptr_t)sync) & 3) == 0,
+               "sf_rnn_wideseq_bwd: whh and the gate-gradient payload must be 16-byte aligned, every other operand 4-byte aligned");
+    SF_REQUIRE((int64_t)R * Cn * (kind ? 4 : 3) * H * 4 < 0x7FFFFFF0LL, "sf_rnn_wideseq_bwd: gate-gradient buffer exceeds 2 GiB");
+    const int slab = sf_rnn_seq_slab_rows(kind, H, 1);
+    for (int r0 = 0; r0 < Cn; r0 += slab) {
+        const int r1 = Cn - r0 < slab ? Cn : r0 + slab;
+        int ng, rpg;
+        SF_REQUIRE(wide_plan(r1 - r0, &ng, &rpg), "sf_rnn_wideseq_bwd: no plan for %d rows", r1 - r0);
+        const int nsub = (rpg + 63) / 64;
+        int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_rnn_wideseq_bwd memset");
+        if (rc) return rc;
+        WideSeqBwd p{dout, gates, hprev, cprev, cout, keep, whh, dgx, pay, sync, R, Cn, ng, rpg, r0, r1,
+                     env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H};
+        const dim3 grid((unsigned)(ng * WIDE_NCOL)), block(256);
+        WIDESEQ_DISPATCH(k_wideseq_bwd);
+        rc = sf_launch_status("sf_rnn_wideseq_bwd");
+        if (rc) return rc;
+    }
+    return 0;
 }

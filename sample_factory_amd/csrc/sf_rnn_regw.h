@@ -59,8 +59,8 @@ __global__ __launch_bounds__(256, 1) void k_lstm_seq_bwd_r(LstmSeqBwd p) {
             else breg[blk][ut] = wv;
         }
     const auto d_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)p.dgx, 0, (int)((int64_t)R * Cn * G4 * 4), 0x00020000);
-    const int g_row0 = group * p.rows_per_group;
-    const int g_rows_end = min(Cn, g_row0 + p.rows_per_group);
+    const int g_row0 = p.row0 + group * p.rows_per_group;  // [row0, row_end): the slab of rows this launch covers
+    const int g_rows_end = min(p.row_end, g_row0 + p.rows_per_group);
 
     // this wave's tiles: ti = wave + 4*q -> row tile rt = ti >> 1, unit tile ut = ti & 1; elements (row 4g+i, unit c)
     float car_h[TPW][4], car_c[TPW][4];
@@ -211,8 +211,8 @@ __global__ __launch_bounds__(256, 1) void k_gru_seq_bwd_r(GruSeqBwd p) {
         for (int ut = 0; ut < 2; ++ut)
             breg[blk][ut] = *reinterpret_cast<const f32x4 *>(p.whh + (int64_t)(j0 + 16 * ut + c) * G3 + wave * KW + 16 * blk + 4 * g);
     const auto d_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)p.dgh, 0, (int)((int64_t)R * Cn * G3 * 4), 0x00020000);
-    const int g_row0 = group * p.rows_per_group;
-    const int g_rows_end = min(Cn, g_row0 + p.rows_per_group);
+    const int g_row0 = p.row0 + group * p.rows_per_group;  // [row0, row_end): the slab of rows this launch covers
+    const int g_rows_end = min(p.row_end, g_row0 + p.rows_per_group);
 
     float car_h[TPW][4];
 #pragma unroll

@@ -49,7 +49,7 @@ class sf_res_desc(C.Structure):
 SYMBOLS = [
     "sf_last_error", "sf_abi_version", "sf_valid_mask", "sf_gae_returns", "sf_moments", "sf_rms_update",
     "sf_rms_apply", "sf_vtrace", "sf_ppo_loss", "sf_loss_scalars", "sf_train_summaries", "sf_minibatch_indices", "sf_minibatch_expand", "sf_grad_sumsq",
-    "sf_adam_step", "sf_adam_step_dlr", "sf_lr_kl_adaptive", "sf_clock_probe", "sf_lamb_step", "sf_rnn_cell_fwd", "sf_rnn_cell_bwd", "sf_rows_add_scale", "sf_mlp2_fwd", "sf_rnn_store_state", "sf_rnn_chunk_setup", "sf_lstm_seq_supported", "sf_lstm_seq_fwd", "sf_lstm_seq_bwd", "sf_gru_seq_fwd", "sf_gru_seq_bwd", "sf_seq_fwd_x_supported", "sf_lstm_seq_fwd_x", "sf_gru_seq_fwd_x", "sf_rnn_rowseq_supported", "sf_rnn_rowseq_fwd", "sf_rnn_rowseq_bwd", "sf_linear_fwd_dual_supported", "sf_linear_fwd_dual",
+    "sf_adam_step", "sf_adam_step_dlr", "sf_lr_kl_adaptive", "sf_clock_probe", "sf_lamb_step", "sf_rnn_cell_fwd", "sf_rnn_cell_bwd", "sf_rows_add_scale", "sf_mlp2_fwd", "sf_rnn_store_state", "sf_rnn_chunk_setup", "sf_lstm_seq_supported", "sf_lstm_seq_fwd", "sf_lstm_seq_bwd", "sf_gru_seq_fwd", "sf_gru_seq_bwd", "sf_seq_fwd_x_supported", "sf_lstm_seq_fwd_x", "sf_gru_seq_fwd_x", "sf_rnn_rowseq_supported", "sf_rnn_rowseq_fwd", "sf_rnn_rowseq_bwd", "sf_rnn_wideseq_supported", "sf_rnn_seq_slab_rows", "sf_rnn_wideseq_fwd", "sf_rnn_wideseq_bwd", "sf_linear_fwd_dual_supported", "sf_linear_fwd_dual",
     "sf_obsnorm_moments", "sf_obsnorm_update", "sf_obsnorm_apply", "sf_sample_write_step",
     "sf_sample_write_step_tuple", "sf_sample_write_step_masked", "sf_traj_write_env_step", "sf_synth_obs",
     "sf_synth_step", "sf_synth_vec_step", "sf_h2d_rows", "sf_copy_rows", "sf_conv_fwd", "sf_conv_fwd_workspace", "sf_conv_wgrad_workspace", "sf_conv_wgrad",
@@ -426,11 +426,14 @@ def lstm_seq_supported(Cn: int, H: int) -> bool:
 
 def _seq_key(op, R, Cn, H, steps, G=4, x_cols=0):
     """profiling key of a fused LSTM pass in bench.py's layout: 2 * (steps*Cn) * 4H * H algorithmic FLOPs of the
-    recurrent products (forward: R steps; backward: R-1, the first step has no state in front of it)"""
+    recurrent products (forward: R steps; backward: R-1, the first step has no state in front of it).  A call beyond one
+    launch (row slabs: several launches, a shorter tail possibly on another instantiation) is keyed by the instantiation of
+    its FULL slabs; the timed region is the whole call."""
     if not _keys_wanted():
         return None
     kind, direction = op.split("_")
     name = None
+    Cn_all, Cn = Cn, min(int(Cn), rnn_seq_slab_rows(0 if kind == "gru" else 1, H, 0 if direction == "fwd" else 1) or int(Cn))
     if direction == "bwd" and int(os.environ.get("SF_SEQ_BWD_REGW", "1")) and H in (256, 512):
         # csrc/sf_rnn_regw.h seq_plan_r: 32 hidden units per work-group, row groups of 32 / 64 rows
         cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
@@ -444,7 +447,7 @@ def _seq_key(op, R, Cn, H, steps, G=4, x_cols=0):
         nsub = {1: 1, 2: 2}.get((rpg + 63) // 64, 4)
         name = f"k_{kind}_seq_{direction}<{int(H)}, 16, {nsub}" + (f", {x_cols // 16}>" if direction == "fwd" else ">")
     # (K = H + x_cols: the fused input projection's FLOPs count as the pass's own)
-    return (op, int(steps * Cn), int(H + x_cols), 1, 1, int(G * H), 1, 1, 1, 1, name)
+    return (op, int(steps * Cn_all), int(H + x_cols), 1, 1, int(G * H), 1, 1, 1, 1, name)
 
 
 def lstm_seq_fwd(gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, H, env_major=False) -> None:
@@ -552,6 +555,48 @@ def rnn_rowseq_bwd(kind, dout, gates, hprev, cprev, cout, keep, whh, dgx, dgh, R
                                         ptr(keep, "f32", "keep"), ptr(whh, "f32", "whh"), ptr(dgx, "f32", "dgx"),
                                         ptr(dgh, "f32", "dgh"), int(R), int(Cn), int(H), int(bool(env_major)), stream()),
                "sf_rnn_rowseq_bwd")
+
+
+def rnn_wideseq_supported(kind: int, Cn: int, H: int) -> bool:
+    return bool(load().sf_rnn_wideseq_supported(int(kind), int(Cn), int(H)))
+
+
+def rnn_seq_slab_rows(kind: int, H: int, pass_: int) -> int:
+    """rows one launch of the persistent forward (pass_ 0) / backward (1) pass serves on this device; 0: no such pass at H"""
+    return int(load().sf_rnn_seq_slab_rows(int(kind), int(H), int(pass_)))
+
+
+def _wideseq_key(direction, kind, R, Cn, H, steps):
+    """profiling key of a wide pass, in _seq_key's layout (the instantiation of a full slab, or of the whole call if smaller)"""
+    if not _keys_wanted():
+        return None
+    G = 4 if kind else 3
+    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    n = min(int(Cn), rnn_seq_slab_rows(kind, H, 0 if direction == "fwd" else 1))
+    ng = max(1, min(cus // 128, 8, (n + 15) // 16))
+    rpg = ((n + ng - 1) // ng + 15) // 16 * 16
+    nsub = {1: 1, 2: 2}.get((rpg + 63) // 64, 4)
+    return (f"wideseq_{direction}", int(steps * Cn), int(H), 1, 1, int(G * H), 1, 1, 1, 1, f"k_wideseq_{direction}<{int(kind)}, {nsub}>")
+
+
+def rnn_wideseq_fwd(kind, gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, H, env_major=False) -> None:
+    """sf_rnn_wideseq_fwd: the forward time loop of a GRU (kind 0) / LSTM (1) core of width 1024 as persistent launches"""
+    with _timed(_wideseq_key("fwd", kind, R, Cn, H, R)):
+        _check(load().sf_rnn_wideseq_fwd(int(kind), ptr(gx, "f32", "gx"), ptr(whh, "f32", "whh"), ptr(bhh, "f32", "bhh"),
+                                         ptr(keep, "f32", "keep"), ptr(gates, "f32", "gates"), ptr(hprev, "f32", "hprev"),
+                                         ptr(hout, "f32", "hout"), ptr(cprev, "f32", "cprev"), ptr(cout, "f32", "cout"),
+                                         ptr(sync, "i32", "sync"), int(R), int(Cn), int(H), int(bool(env_major)), stream()),
+               "sf_rnn_wideseq_fwd")
+
+
+def rnn_wideseq_bwd(kind, dout, gates, hprev, cprev, cout, keep, whh, dgx, dgh, sync, R, Cn, H, env_major=False) -> None:
+    """sf_rnn_wideseq_bwd: the backward time loop of the same pass; operands as rnn_rowseq_bwd, plus the sync buffer"""
+    with _timed(_wideseq_key("bwd", kind, R, Cn, H, R - 1)):
+        _check(load().sf_rnn_wideseq_bwd(int(kind), ptr(dout, "f32", "dout"), ptr(gates, "f32", "gates"),
+                                         ptr(hprev, "f32", "hprev"), ptr(cprev, "f32", "cprev"), ptr(cout, "f32", "cout"),
+                                         ptr(keep, "f32", "keep"), ptr(whh, "f32", "whh"), ptr(dgx, "f32", "dgx"),
+                                         ptr(dgh, "f32", "dgh"), ptr(sync, "i32", "sync"), int(R), int(Cn), int(H),
+                                         int(bool(env_major)), stream()), "sf_rnn_wideseq_bwd")
 
 
 def rows_add_scale(a, b, keep, Cn, H, y) -> None:

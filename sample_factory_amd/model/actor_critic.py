@@ -818,6 +818,13 @@ class ActorCritic(NativeTower):
             self._rnn_saved_l[li] = self._rnn_saved = dict(gates=gates, Hprev=Hprev, Cprev=Cprev, Cout=Cout, keep=keep, R=R, Cn=Cn,
                                                            fused=True, family="row_owned")
             return out
+        if _LSTM_SEQ and lib.rnn_wideseq_supported(kind, Cn, H):  # width 1024: persistent launches with 8 hidden units per
+            # work-group (csrc/sf_rnn_wideseq.h); same sync buffer and abort word as the persistent family
+            lib.rnn_wideseq_fwd(kind, GX, Lh.w, Lh.b, keep, gates, Hprev, out, Cprev, Cout, self._seq_sync_buf(), R, Cn, H,
+                                env_major=True)
+            self._rnn_saved_l[li] = self._rnn_saved = dict(gates=gates, Hprev=Hprev, Cprev=Cprev, Cout=Cout, keep=keep, R=R, Cn=Cn,
+                                                           fused=True, family="persistent_wide")
+            return out
         Hout = self._buf((tag, "Hout", li), (R, Cn, H))
         gh = self._buf((tag, "gh_seq", li), (Cn, GH))
         GXv = GX.view(R, Cn, GH)
@@ -846,6 +853,11 @@ class ActorCritic(NativeTower):
                     dGH = self._buf(("g", "dGH", li), (R, Cn, GH))
                 lib.rnn_rowseq_bwd(kind, dOut, sv["gates"], sv["Hprev"], sv["Cprev"], sv["Cout"], keep, Lh.w, dGX,
                                    dGH if kind == 0 else None, R, Cn, H, env_major=True)
+            elif sv["family"] == "persistent_wide":
+                if kind == 0:
+                    dGH = self._buf(("g", "dGH", li), (R, Cn, GH))
+                lib.rnn_wideseq_bwd(kind, dOut, sv["gates"], sv["Hprev"], sv["Cprev"], sv["Cout"], keep, Lh.w, dGX,
+                                    dGH if kind == 0 else None, self._seq_sync_buf(), R, Cn, H, env_major=True)
             elif kind == 1:
                 sync = self._seq_sync_buf()
                 lib.lstm_seq_bwd(dOut, sv["gates"], sv["Cprev"], sv["Cout"], keep, Lh.w, dGX, sync, R, Cn, H, env_major=True)

@@ -11,7 +11,7 @@ obj=build/variants/${src%.hip}_$tag.o
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Iinclude -Isample_factory_amd/csrc $fp "$@" \
     -c sample_factory_amd/csrc/$src -o $obj
 objs=""
-for s in sf_rl sf_nn sf_rnn sf_dp; do
+for s in sf_rl sf_nn sf_rnn sf_dp sf_resnet; do
     if [ "$s.hip" == "$src" ]; then objs="$objs $obj"; else objs="$objs sample_factory_amd/csrc/$s.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/variants/libsf_hip_$tag.so $objs -ldl
