@@ -28,6 +28,9 @@ extern "C" {
 #define SF_ERR_ARG (-1)
 #define SF_ERR_LAUNCH (-2)
 #define SF_ERR_UNSUPPORTED (-3)
+/* members of a Tuple action space (action_distributions.py:197-287 composes any number; Humanoid discretised is 17,
+ * ShadowHand 20 to 24).  Every entry point that takes a head list refuses a longer one before it launches anything. */
+#define SF_MAX_ACTION_HEADS 64
 
 const char *sf_last_error(void);
 int sf_abi_version(void);
@@ -114,8 +117,8 @@ int sf_rows_add_scale(const float *a, const float *b, const float *keep, int64_t
 int sf_vtrace(const float *params, int ld_params, const float *values, int ld_values, const float *actions,
               const float *old_logp, const float *rewards, const uint8_t *dones, const int32_t *index, int64_t offset,
               int64_t n, int A, int action_kind, int recurrence, float gamma, float rho_hat, float c_hat, float *vs,
-              float *adv, const int32_t *head_n /* host; Tuple members as in sf_loss_cfg.head_n, or NULL */, int num_heads,
-              void *stream);
+              float *adv, const int32_t *head_n /* host; Tuple members as in sf_loss_cfg.head_n, or NULL */,
+              int num_heads /* <= SF_MAX_ACTION_HEADS */, void *stream);
 
 /* ---- K16: PPO loss head, forward + backward ----------------------------------------------------------------
  * learner.py:586-669 (ratio, clamp [0.05,20], per-minibatch advantage normalisation, clipped surrogate, entropy /
@@ -143,7 +146,8 @@ typedef struct {
      * head_n[h] = n > 0 for Discrete(n) (n logits, one action column) or head_n[h] = -D < 0 for Box(D) (2 D parameters
      * [means | log_std], D action columns; symmetric-KL exploration is refused for it, as the reference's
      * ContinuousActionDistribution has no symmetric_kl_with_uniform_prior).  Parameters sum to A; `actions` holds the
-     * members' columns side by side per sample.  num_heads <= 1: one Discrete(A). */
+     * members' columns side by side per sample.  num_heads <= 1: one Discrete(A).  The struct holds 8 members and its
+     * size is part of the ABI; a longer list (up to SF_MAX_ACTION_HEADS) goes to sf_ppo_loss_heads as an argument. */
     int32_t num_heads;
     int32_t head_n[8];
     /* > 0: `old_values` is the trajectory slab's values array [E, old_values_T + 1] read IN PLACE — dataset row
@@ -161,6 +165,19 @@ int sf_ppo_loss(const float *params, int ld_params, const float *values, int ld_
                 const sf_loss_cfg *h_cfg, const double *moments, double *sums, float *g_params, float *g_values,
                 float *ratio_out /* [n] clamped pi/pi_old per sample for the summaries (learner.py:886-903), or NULL */,
                 void *stream);
+/* sf_ppo_loss for a Tuple of 1 .. SF_MAX_ACTION_HEADS members (TupleActionDistribution, action_distributions.py:197-287:
+ * log_prob :258, entropy :265, kl_divergence :271 and symmetric_kl_with_uniform_prior :278 are sums over the
+ * members): head_n (host array of num_heads entries, as sf_loss_cfg.head_n) replaces the struct's num_heads / head_n,
+ * which are not read; everything else as sf_ppo_loss, same launcher.  Up to 8 members run the kernels sf_ppo_loss runs,
+ * with the same results; more run k_ppo_loss_mh (A <= 128: one lane per sample, the members' statistics recomputed in the
+ * gradient loop, not kept) or k_ppo_loss_wide (A > 128), and add the row's log-prob — up to 64 terms — up in double.
+ * A bad list (num_heads outside 1 .. SF_MAX_ACTION_HEADS, an empty member, sizes that do not sum to A, a Box member with
+ * symmetric-KL exploration) returns SF_ERR_ARG before any launch. */
+int sf_ppo_loss_heads(const float *params, int ld_params, const float *values, int ld_values, const float *actions,
+                      const float *old_logp, const float *old_params, const float *old_values, const float *adv,
+                      const float *targets, const uint8_t *valids, const int32_t *index, int64_t offset, int64_t n, int A,
+                      const sf_loss_cfg *h_cfg, const double *moments, double *sums, float *g_params, float *g_values,
+                      float *ratio_out, const int32_t *head_n /* host */, int num_heads, void *stream);
 /* out[0..3] = policy, exploration, kl, value losses; [4] kl mean; [5] kl max; [6] adv mean; [7] adv std;
  * [8] n_valid; [9] entropy (or symkl) mean — device float[16]. */
 int sf_loss_scalars(const double *sums, const double *moments, const sf_loss_cfg *h_cfg, float *out, void *stream);
@@ -257,7 +274,7 @@ int sf_sample_write_step_masked(const float *logits, int ld_logits, const float 
                                 float *traj_policy_version, int32_t *env_actions, void *stream);
 
 /* Tuple variant of sf_sample_write_step (TupleActionDistribution.sample_actions_log_probs,
- * action_distributions.py:241-245): member h (head_n[h] as in sf_loss_cfg, host array of num_heads <= 8 entries) is
+ * action_distributions.py:241-245): member h (head_n[h] as in sf_loss_cfg, host array of num_heads <= SF_MAX_ACTION_HEADS entries) is
  * sampled by inverse CDF from its own Philox uniform (counter (step, h, 2, 0)) if Discrete, as mu + sd * eps with
  * Box-Muller normals from counter (step, dim / 2, 3, h) if Box(D) (deterministic: arg-max / the mean); traj_actions
  * gets the members' columns side by side, traj_logp the SUM of the members' log-probs.  env_actions [B, num_heads]

@@ -345,7 +345,8 @@ class Learner:
             action_kind=1 if is_box(self.env_info.action_space) else 0, dense_adv=int(bool(cfg.with_vtrace)))
         heads = action_head_sizes(self.env_info.action_space)
         self._head_sizes = heads
-        if len(heads) > 1:  # Tuple of Discrete spaces: independent categorical heads
+        # Tuple space: independent members.  The struct holds 8; a longer list travels as lib.ppo_loss's head_sizes
+        if 1 < len(heads) <= len(self.loss_cfg.head_n):
             self.loss_cfg.num_heads = len(heads)
             for i, nh in enumerate(heads):
                 self.loss_cfg.head_n[i] = nh
@@ -542,7 +543,7 @@ class Learner:
         self.loss_cfg.old_values_T = buff.T  # buff["values"] is the slab's [E, T+1] array
         lib.ppo_loss(params, ld, values, ld, buff.actions, buff.log_prob_actions, buff.action_logits, buff["values"],
                      adv_arr, tgt_arr, buff.valids, index, offset, n, A, self.loss_cfg, moments, self._sums,
-                     g_heads[:, 1:], g_heads[:, 0], ratio_out=self._ratio)
+                     g_heads[:, 1:], g_heads[:, 0], ratio_out=self._ratio, head_sizes=self._head_sizes)
         self._last_mb = (index, offset, n, values, adv_arr)  # for _record_summaries
         if self.dp and self._dp_reduce_each_mb:  # only the per-minibatch KL-adaptive LR needs global values NOW
             self.group.loss_sums(self._sums)

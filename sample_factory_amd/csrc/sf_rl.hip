@@ -316,8 +316,32 @@ __device__ __forceinline__ float action_logp(const float *__restrict__ z, int A,
 
 // =========================================================================================== K17 V-trace
 struct HeadsDev {
-    int num_heads, head_n[8];
+    int num_heads, head_n[SF_MAX_ACTION_HEADS];  // a kernel argument (260 bytes); the launchers check num_heads
 };
+// A head list as the entry points receive it (host array): 1 .. cap members, none empty.  Fills `out`, returns the number
+// of parameters the members read, or -1 with the reason in sf_err_buf (`what` names the entry point).  Nothing is
+// launched with a list this has not passed: the kernels index head_n with num_heads unchecked.
+static int heads_from_host(const char *what, const int32_t *head_n, int num_heads, int cap, int *out_n, bool *any_box) {
+    if (!head_n || num_heads < 1 || num_heads > cap) {
+        snprintf(sf_err_buf, sizeof(sf_err_buf), "%s: %d action heads, the limit is %d%s", what, num_heads, cap,
+                 cap < SF_MAX_ACTION_HEADS ? " members in sf_loss_cfg (sf_ppo_loss_heads takes a longer list)"
+                                          : " (SF_MAX_ACTION_HEADS)");
+        return -1;
+    }
+    int tot = 0;
+    *any_box = false;
+    for (int i = 0; i < num_heads; ++i) {  // head_n > 0: Discrete(n), n logits; < 0: Box(-n), 2 * (-n) parameters
+        if (head_n[i] == 0) {
+            snprintf(sf_err_buf, sizeof(sf_err_buf), "%s: empty action head (member %d of %d)", what, i, num_heads);
+            return -1;
+        }
+        out_n[i] = head_n[i];
+        tot += head_n[i] > 0 ? head_n[i] : -2 * head_n[i];
+        *any_box = *any_box || head_n[i] < 0;
+    }
+    for (int i = num_heads; i < SF_MAX_ACTION_HEADS; ++i) out_n[i] = 0;
+    return tot;
+}
 // action columns of a Tuple space: one per Discrete member (head_n > 0), D per Box(D) member (head_n = -D)
 __device__ __host__ __forceinline__ int heads_action_cols(const int *head_n, int num_heads) {
     int c = 0;
@@ -502,14 +526,11 @@ extern "C" int sf_vtrace(const float *params, int ld_params, const float *values
     SF_REQUIRE(ld_params >= A && ld_values >= 1, "sf_vtrace: bad strides");
     HeadsDev hd = {};
     if (head_n && num_heads > 1) {
-        SF_REQUIRE(num_heads <= 8 && action_kind == 0, "sf_vtrace: at most 8 heads (action_kind 0 with a head list)");
-        int tot = 0;
+        SF_REQUIRE(action_kind == 0, "sf_vtrace: a head list needs action_kind 0");
+        bool any_box;
+        const int tot = heads_from_host("sf_vtrace", head_n, num_heads, SF_MAX_ACTION_HEADS, hd.head_n, &any_box);
+        if (tot < 0) return SF_ERR_ARG;
         hd.num_heads = num_heads;
-        for (int i = 0; i < num_heads; ++i) {  // head_n > 0: Discrete(n), n logits; < 0: Box(-n), 2 * (-n) parameters
-            SF_REQUIRE(head_n[i] != 0, "sf_vtrace: empty action head");
-            hd.head_n[i] = head_n[i];
-            tot += head_n[i] > 0 ? head_n[i] : -2 * head_n[i];
-        }
         SF_REQUIRE(tot == A, "sf_vtrace: head sizes sum to %d, A = %d", tot, A);
     }
     SF_REQUIRE(params && values && actions && old_logp && rewards && dones && vs && adv, "sf_vtrace: null pointer");
@@ -549,7 +570,7 @@ extern "C" int sf_vtrace(const float *params, int ld_params, const float *values
 struct LossDev {
     float clip_lo, clip_hi, clip_value, value_coeff, expl_coeff, kl_coeff;
     int expl_kind, action_kind, dense_adv;
-    int num_heads, head_n[8];
+    int num_heads, head_n[SF_MAX_ACTION_HEADS];
     int ov_T;  // > 0: old_values is the slab's [E, ov_T + 1] array read in place (dataset row e*T+t -> e*(T+1)+t)
 };
 __device__ __forceinline__ int64_t ov_row(const LossDev &h, int64_t d) {
@@ -919,6 +940,193 @@ __global__ __launch_bounds__(256) void k_ppo_loss_md(const float *__restrict__ p
     }
 }
 
+// k_ppo_loss_md for head lists of more than 8 members (A <= 128; up to SF_MAX_ACTION_HEADS): the same per-member formulas
+// in the same order (the row's log-prob alone is added up in double), but no per-member state in the lane: seven float[64] arrays would be 448 registers, i.e. scratch.  The
+// first member loop keeps only the row's totals; the gradient loop recomputes a member's max, log-sum-exp, entropy, KL
+// and KL(p || uniform) with the same expressions (cat_terms), which costs a second pass of expf over a row that is in
+// cache.  sym_pass as in k_ppo_loss_md.
+struct CatTerms {
+    float mx, lse, mxo, lseo, ent, kl, klpu, a2, lpa;
+};
+__device__ __forceinline__ CatTerms cat_terms(const float *__restrict__ z, const float *__restrict__ zo, int nh, int act) {
+    CatTerms t;
+    float m1 = -INFINITY, m2 = -INFINITY;
+    for (int k = 0; k < nh; ++k) { m1 = fmaxf(m1, z[k]); m2 = fmaxf(m2, zo[k]); }
+    float s1 = 0.f, s2 = 0.f;
+    for (int k = 0; k < nh; ++k) { s1 += expf(z[k] - m1); s2 += expf(zo[k] - m2); }
+    t.mx = m1; t.lse = logf(s1); t.mxo = m2; t.lseo = logf(s2);
+    const float u = 1.0f / (float)nh, lu = logf(u);
+    float lpa = 0.f, e = 0.f, kk = 0.f, a1 = 0.f, a2 = 0.f;
+    for (int k = 0; k < nh; ++k) {
+        const float lp = (z[k] - m1) - t.lse, p = expf(lp), q = (zo[k] - m2) - t.lseo;
+        if (k == act) lpa = lp;
+        e -= p * lp;
+        kk += p * (lp - q);
+        a1 += p * (lp - lu);
+        a2 += u * (lu - lp);
+    }
+    t.ent = e; t.kl = kk; t.klpu = a1; t.a2 = a2; t.lpa = lpa;
+    return t;
+}
+__global__ __launch_bounds__(256) void k_ppo_loss_mh(const float *__restrict__ params, int ldp,
+                                                     const float *__restrict__ values, int ldv,
+                                                     const float *__restrict__ actions,
+                                                     const float *__restrict__ old_logp,
+                                                     const float *__restrict__ old_params,
+                                                     const float *__restrict__ old_values, const float *__restrict__ adv,
+                                                     const float *__restrict__ targets,
+                                                     const uint8_t *__restrict__ valids,
+                                                     const int32_t *__restrict__ index, int64_t offset, int64_t n, int A,
+                                                     LossDev h, const double *__restrict__ moments,
+                                                     double *__restrict__ sums, float *__restrict__ g_params,
+                                                     float *__restrict__ g_values, float *__restrict__ ratio_out,
+                                                     int sym_pass) {
+    __shared__ double lds[4 * 4];
+    __shared__ float lds_max[4];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const double mn = moments[2];
+    const double mean64 = moments[0] / mn;
+    const double var64 = (moments[1] - moments[0] * mean64) / (mn - 1.0);
+    const float adv_mean = (float)mean64;
+    const float adv_std = (float)sqrt(var64 > 0.0 ? var64 : (mn > 1.0 ? 0.0 : NAN));
+    const float denom = fmaxf(adv_std, 1e-7f);
+    const float inv_n = 1.0f / (float)mn;
+    const float symkl_gate = (h.expl_kind == 2 && !sym_pass) ? (float)sums[6] : 1.0f;
+    const int H = h.num_heads;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    float kl_max = -1.0f;
+    if (i < n) {
+        const int64_t d = index ? (int64_t)index[i] : offset + i;
+        const bool valid = valids[d] != 0;
+        const float *z = params + i * ldp, *zo = old_params + d * A;
+        float *gz = g_params + i * ldp;
+        // the row's log-prob is a sum of up to 64 members' (|lp| can pass 100 each): added up in double, so that the
+        // ratio exp(logp - old_logp) does not inherit the rounding of a float running sum of that size
+        double logp_a = 0.0;
+        float ent = 0.f, kl = 0.f, symkl = 0.f;
+        int off = 0, aoff = 0;
+        const int NA = heads_action_cols(h.head_n, H);
+        const float *arow = actions + d * NA;
+        for (int hd = 0; hd < H; ++hd) {
+            const int nh = h.head_n[hd];
+            if (nh < 0) {  // Box(D) member: [means | log_std], the formulas of k_ppo_loss's continuous branch
+                const int Dh = -nh;
+                float lpp = 0.f, e = 0.f, kk = 0.f;
+                for (int k = 0; k < Dh; ++k) {
+                    const float mu = z[off + k], sd = clampf(expf(z[off + Dh + k]), 1e-4f, 1e4f);
+                    const float a = arow[aoff + k];
+                    lpp += -((a - mu) * (a - mu)) / (2.f * (sd * sd)) - logf(sd) - 0.91893853320467274178f;
+                    e += 0.5f + 0.91893853320467274178f + logf(sd);
+                    const float muo = zo[off + k], sdo = clampf(expf(zo[off + Dh + k]), 1e-4f, 1e4f);
+                    const float vr = (sd / sdo) * (sd / sdo);
+                    const float t1 = ((mu - muo) / sdo) * ((mu - muo) / sdo);
+                    kk += 0.5f * (vr + t1 - 1.f - logf(vr));
+                }
+                logp_a += (double)lpp; ent += e; kl += kk;
+                off += 2 * Dh; aoff += Dh;
+                continue;
+            }
+            const CatTerms t = cat_terms(z + off, zo + off, nh, (int)arow[aoff]);
+            logp_a += (double)t.lpa; ent += t.ent; kl += t.kl; symkl += 0.5f * (t.klpu + t.a2);
+            off += nh; aoff += 1;
+        }
+        if (sym_pass) {
+            if (valid) acc[0] = symkl;
+        } else {
+            const float raw_ratio = expf((float)(logp_a - (double)old_logp[d]));
+            const float ratio = clampf(raw_ratio, 0.05f, 20.0f);
+            if (ratio_out) ratio_out[i] = ratio;
+            const int64_t da = h.dense_adv ? i : d;
+            const float advn = (adv[da] - adv_mean) / denom;
+            const float clipped = clampf(ratio, h.clip_lo, h.clip_hi);
+            const float lu_ = ratio * advn, lc_ = clipped * advn;
+            const float pl = fminf(lu_, lc_);
+            const float v = values[i * ldv], vo = old_values[ov_row(h, d)], R = targets[da];
+            const float vclip = vo + clampf(v - vo, -h.clip_value, h.clip_value);
+            const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
+            const float vl = fmaxf(l1, l2);
+            if (valid) {
+                acc[0] = pl;
+                acc[1] = (h.expl_kind == 2) ? symkl : ent;
+                acc[2] = kl;
+                acc[3] = vl;
+                kl_max = kl;
+                float dpl_dr;
+                const bool in_clip = ratio >= h.clip_lo && ratio <= h.clip_hi;
+                if (lu_ < lc_) dpl_dr = advn;
+                else if (lu_ > lc_) dpl_dr = in_clip ? advn : 0.f;
+                else dpl_dr = 0.5f * advn + (in_clip ? 0.5f * advn : 0.f);
+                const bool in_hard = raw_ratio >= 0.05f && raw_ratio <= 20.0f;
+                const float dL_dlogp = in_hard ? (-inv_n) * dpl_dr * raw_ratio : 0.f;
+                off = 0;
+                aoff = 0;
+                for (int hd = 0; hd < H; ++hd) {
+                    const int nh = h.head_n[hd];
+                    if (nh < 0) {  // Box(D) member
+                        const int Dh = -nh;
+                        for (int k = 0; k < Dh; ++k) {
+                            const float mu = z[off + k], e = expf(z[off + Dh + k]);
+                            const float sd = clampf(e, 1e-4f, 1e4f);
+                            const float dsd = (e >= 1e-4f && e <= 1e4f) ? e : 0.f;
+                            const float a = arow[aoff + k];
+                            const float var = sd * sd;
+                            float gmu = dL_dlogp * ((a - mu) / var);
+                            float gsd = dL_dlogp * (((a - mu) * (a - mu)) / (var * sd) - 1.f / sd);
+                            if (h.expl_kind == 1) gsd += -h.expl_coeff * inv_n * (1.f / sd);
+                            if (h.kl_coeff != 0.f) {
+                                const float muo = zo[off + k], sdo = clampf(expf(zo[off + Dh + k]), 1e-4f, 1e4f);
+                                gmu += h.kl_coeff * inv_n * ((mu - muo) / (sdo * sdo));
+                                gsd += h.kl_coeff * inv_n * (sd / (sdo * sdo) - 1.f / sd);
+                            }
+                            gz[off + k] = gmu;
+                            gz[off + Dh + k] = gsd * dsd;
+                        }
+                        off += 2 * Dh; aoff += Dh;
+                        continue;
+                    }
+                    const int act = (int)arow[aoff];
+                    aoff += 1;
+                    const CatTerms t = cat_terms(z + off, zo + off, nh, act);  // the first loop's values, bit for bit
+                    const float u = 1.0f / (float)nh, lu = logf(u);
+                    for (int k = 0; k < nh; ++k) {
+                        const float lp = (z[off + k] - t.mx) - t.lse, p = expf(lp);
+                        const float q = (zo[off + k] - t.mxo) - t.lseo;
+                        float gk = dL_dlogp * ((k == act ? 1.f : 0.f) - p);
+                        if (h.expl_kind == 1) gk += h.expl_coeff * inv_n * (p * (lp + t.ent));
+                        if (h.expl_kind == 2)
+                            gk += symkl_gate * h.expl_coeff * inv_n * 0.5f * (p * ((lp - lu) - t.klpu) + p - u);
+                        if (h.kl_coeff != 0.f) gk += h.kl_coeff * inv_n * (p * ((lp - q) - t.kl));
+                        gz[off + k] = gk;
+                    }
+                    off += nh;
+                }
+                const bool in_v = (v - vo) >= -h.clip_value && (v - vo) <= h.clip_value;
+                float dvl;
+                if (l1 > l2) dvl = 2.f * (v - R);
+                else if (l2 > l1) dvl = in_v ? 2.f * (vclip - R) : 0.f;
+                else dvl = (v - R) + (in_v ? (vclip - R) : 0.f);
+                g_values[i * ldv] = h.value_coeff * inv_n * dvl;
+            } else {
+                for (int k = 0; k < A; ++k) gz[k] = 0.f;
+                g_values[i * ldv] = 0.f;
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    kl_max = sf_wave_max(kl_max);
+    if (lane == 0) lds_max[wave] = kl_max;
+    sf_block_sum<4>(acc, lds);
+    if (threadIdx.x == 0) {
+        if (sym_pass) { atomicAdd(&sums[7], acc[0]); return; }
+        atomicAdd(&sums[0], acc[0]);
+        atomicAdd(&sums[1], acc[1]);
+        atomicAdd(&sums[2], acc[2]);
+        atomicAdd(&sums[3], acc[3]);
+        const float m = fmaxf(fmaxf(lds_max[0], lds_max[1]), fmaxf(lds_max[2], lds_max[3]));
+        if (m > -1.0f) atomic_max_float(&sums[4], m);
+    }
+}
+
 // pre-pass for the symmetric-KL exploration loss: mean over valid samples decides clamp(max=30) / isfinite gate
 template <int MAXA>
 __global__ __launch_bounds__(256) void k_symkl_sum(const float *__restrict__ params, int ldp,
@@ -951,7 +1159,7 @@ __global__ __launch_bounds__(256) void k_symkl_sum(const float *__restrict__ par
     if (threadIdx.x == 0) atomicAdd(out, acc[0]);
 }
 
-// k_ppo_loss / k_ppo_loss_md for A > 128 (any head list of up to 8 members): the same formulas, one wave per row.
+// k_ppo_loss / k_ppo_loss_md for A > 128 (any head list of up to SF_MAX_ACTION_HEADS members): the same formulas, one wave per row.
 // Pass 1 per head: max / log-sum-exp of the current and the old logits in one read; pass 2: the head's log-prob,
 // entropy, KL and symmetric-KL terms (kept per head in LDS: the gradient needs them and the row's total log-prob);
 // pass 3: the gradient row, written 256 contiguous bytes per store.  The block's waves walk the rows with a grid
@@ -972,7 +1180,8 @@ __global__ __launch_bounds__(256) void k_ppo_loss_wide(const float *__restrict__
                                                        int sym_pass) {
     __shared__ double lds[4 * 4];
     __shared__ float lds_max[4];
-    __shared__ float hstat[WIDE_ROWS][8][8];  // per wave and head: mx, lse, mxo, lseo, entropy, KL, KL(p || uniform)
+    // per wave and head: mx, lse, mxo, lseo, entropy, KL, KL(p || uniform); 8 KB for the longest list
+    __shared__ float hstat[WIDE_ROWS][SF_MAX_ACTION_HEADS][8];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const double mn = moments[2];
     const double mean64 = moments[0] / mn;
@@ -1015,6 +1224,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss_wide(const float *__restrict__
         }
         float *gz = g_params + i * ldp;
         float logp_a = 0.f, ent = 0.f, kl = 0.f, symkl = 0.f;
+        double logp_d = 0.0;  // the same sum in double: what a list of more than 8 members takes its ratio from
         int off = 0, aoff = 0;
         for (int hd = 0; hd < H; ++hd) {
             const int nh = h.head_n[hd];
@@ -1031,7 +1241,8 @@ __global__ __launch_bounds__(256) void k_ppo_loss_wide(const float *__restrict__
                     const float t1 = ((mu - muo) / sdo) * ((mu - muo) / sdo);
                     kk += 0.5f * (vr + t1 - 1.f - logf(vr));
                 }
-                logp_a += wide_allsum(lpp);
+                lpp = wide_allsum(lpp);
+                logp_a += lpp; logp_d += (double)lpp;
                 ent += wide_allsum(e);
                 kl += wide_allsum(kk);
                 off += 2 * Dh; aoff += Dh;
@@ -1060,10 +1271,11 @@ __global__ __launch_bounds__(256) void k_ppo_loss_wide(const float *__restrict__
             // every lane stores the same bits and reads back its own store: no barrier
             st[hd][0] = mx; st[hd][1] = lse; st[hd][2] = mxo; st[hd][3] = lseo;
             st[hd][4] = e; st[hd][5] = kk; st[hd][6] = a1;
-            logp_a += lpa; ent += e; kl += kk; symkl += 0.5f * (a1 + a2);
+            logp_a += lpa; logp_d += (double)lpa; ent += e; kl += kk; symkl += 0.5f * (a1 + a2);
             off += nh; aoff += 1;
         }
-        const float raw_ratio = expf(logp_a - old_logp[d]);
+        // up to 8 members: the float sum, as ever; more (|logp| can reach several hundred): the double one, see k_ppo_loss_mh
+        const float raw_ratio = expf(H > 8 ? (float)(logp_d - (double)old_logp[d]) : logp_a - old_logp[d]);
         const float ratio = clampf(raw_ratio, 0.05f, 20.0f);
         if (ratio_out && lane == 0) ratio_out[i] = ratio;
         if (!valid) {  // no loss, zero gradient
@@ -1170,7 +1382,8 @@ __global__ void k_symkl_gate(double *__restrict__ sums, const double *__restrict
     sums[6] = (isfinite(m) && m <= 30.0f) ? 1.0 : 0.0;
 }
 
-static LossDev make_loss_dev(const sf_loss_cfg *c) {
+// head_n: the categorical / Box members to copy (num_heads checked entries), or nullptr for one Discrete(A) / Box(A / 2)
+static LossDev make_loss_dev(const sf_loss_cfg *c, const int32_t *head_n, int num_heads) {
     LossDev h;
     h.clip_hi = (float)(1.0 + (double)c->clip_ratio);
     h.clip_lo = (float)(1.0 / (1.0 + (double)c->clip_ratio));
@@ -1181,8 +1394,8 @@ static LossDev make_loss_dev(const sf_loss_cfg *c) {
     h.expl_kind = c->exploration_coeff == 0.f ? 0 : c->exploration_kind;
     h.action_kind = c->action_kind;
     h.dense_adv = c->dense_adv;
-    h.num_heads = c->num_heads > 1 ? c->num_heads : 1;
-    for (int i = 0; i < 8; ++i) h.head_n[i] = c->num_heads > 1 ? c->head_n[i] : 0;
+    h.num_heads = head_n ? num_heads : 1;
+    for (int i = 0; i < SF_MAX_ACTION_HEADS; ++i) h.head_n[i] = head_n && i < num_heads ? head_n[i] : 0;
     h.ov_T = c->old_values_T > 0 ? c->old_values_T : 0;
     return h;
 }
@@ -1207,21 +1420,34 @@ static int ppo_loss_wide_launch(const float *params, int ld_params, const float 
     return sf_launch_status("sf_ppo_loss");
 }
 
-extern "C" int sf_ppo_loss(const float *params, int ld_params, const float *values, int ld_values,
+// sf_ppo_loss and sf_ppo_loss_heads: `what` names the entry point in the messages; head_n / num_heads is the struct's list
+// (cap 8) or the argument's (cap SF_MAX_ACTION_HEADS).  num_heads <= 1: one Discrete(A) / Box(A / 2).
+static int ppo_loss_launch(const char *what, const float *params, int ld_params, const float *values, int ld_values,
                            const float *actions, const float *old_logp, const float *old_params,
                            const float *old_values, const float *adv, const float *targets, const uint8_t *valids,
                            const int32_t *index, int64_t offset, int64_t n, int A, const sf_loss_cfg *h_cfg,
-                           const double *moments, double *sums, float *g_params, float *g_values, float *ratio_out,
-                           void *stream) {
-    SF_REQUIRE(ld_params >= A && ld_values >= 1, "sf_ppo_loss: bad strides");
+                           const int32_t *head_n, int num_heads, int cap, const double *moments, double *sums,
+                           float *g_params, float *g_values, float *ratio_out, void *stream) {
+    SF_REQUIRE(ld_params >= A && ld_values >= 1, "%s: bad strides", what);
     SF_REQUIRE(params && values && actions && old_logp && old_params && old_values && adv && targets && valids &&
                    h_cfg && moments && sums && g_params && g_values,
-               "sf_ppo_loss: null pointer");
-    SF_REQUIRE(n > 0 && A > 0, "sf_ppo_loss: bad shape n=%lld A=%d", (long long)n, A);
-    SF_REQUIRE(h_cfg->action_kind == 0 || (h_cfg->action_kind == 1 && A % 2 == 0), "sf_ppo_loss: bad action_kind");
+               "%s: null pointer", what);
+    SF_REQUIRE(n > 0 && A > 0, "%s: bad shape n=%lld A=%d", what, (long long)n, A);
+    SF_REQUIRE(h_cfg->action_kind == 0 || (h_cfg->action_kind == 1 && A % 2 == 0), "%s: bad action_kind", what);
     SF_REQUIRE(!(h_cfg->exploration_kind == 2 && h_cfg->action_kind != 0 && h_cfg->exploration_coeff != 0.f),
-               "sf_ppo_loss: symmetric_kl exploration loss needs a categorical distribution");
-    const LossDev h = make_loss_dev(h_cfg);
+               "%s: symmetric_kl exploration loss needs a categorical distribution", what);
+    const bool tuple = h_cfg->action_kind == 0 && num_heads > 1;
+    if (tuple) {  // every check of the list comes before the first launch (the memset included)
+        int32_t checked[SF_MAX_ACTION_HEADS];
+        bool any_box;
+        const int tot = heads_from_host(what, head_n, num_heads, cap, checked, &any_box);
+        if (tot < 0) return SF_ERR_ARG;
+        SF_REQUIRE(tot == A, "%s: head sizes sum to %d, A = %d", what, tot, A);
+        SF_REQUIRE(!(any_box && h_cfg->exploration_kind == 2 && h_cfg->exploration_coeff != 0.f),
+                   "%s: symmetric_kl exploration loss needs categorical heads only (the reference's "
+                   "ContinuousActionDistribution has no symmetric_kl_with_uniform_prior)", what);
+    }
+    const LossDev h = make_loss_dev(h_cfg, tuple ? head_n : nullptr, num_heads);
     int rc = sf_hip_status(hipMemsetAsync(sums, 0, 8 * sizeof(double), STREAM(stream)), "sf_ppo_loss memset");
     if (rc) return rc;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
@@ -1231,32 +1457,22 @@ extern "C" int sf_ppo_loss(const float *params, int ld_params, const float *valu
         else if (A <= 32) KERNEL<32><<<grid, block, 0, STREAM(stream)>>>(__VA_ARGS__);  \
         else KERNEL<128><<<grid, block, 0, STREAM(stream)>>>(__VA_ARGS__);              \
     } while (0)
-    if (h.action_kind == 0 && h.num_heads > 1) {
-        int tot = 0;
-        SF_REQUIRE(h.num_heads <= 8, "sf_ppo_loss: at most 8 action heads");
-        bool any_box = false;  // head_n > 0: Discrete(n); head_n < 0: Box(-n) member with 2 * (-n) parameters
-        for (int i = 0; i < h.num_heads; ++i) {
-            SF_REQUIRE(h.head_n[i] != 0, "sf_ppo_loss: empty action head");
-            tot += h.head_n[i] > 0 ? h.head_n[i] : -2 * h.head_n[i];
-            any_box = any_box || h.head_n[i] < 0;
-        }
-        SF_REQUIRE(tot == A, "sf_ppo_loss: head sizes sum to %d, A = %d", tot, A);
-        SF_REQUIRE(!(any_box && h.expl_kind == 2),
-                   "sf_ppo_loss: symmetric_kl exploration loss needs categorical heads only (the reference's "
-                   "ContinuousActionDistribution has no symmetric_kl_with_uniform_prior)");
+    if (tuple) {
         if (A >= WIDE_MIN_A) return ppo_loss_wide_launch(params, ld_params, values, ld_values, actions, old_logp,
                                                          old_params, old_values, adv, targets, valids, index, offset, n,
                                                          A, h, moments, sums, g_params, g_values, ratio_out, stream);
+        // up to 8 members: their statistics stay in the lane (k_ppo_loss_md); more: recomputed (k_ppo_loss_mh)
+        auto kern = h.num_heads <= 8 ? k_ppo_loss_md : k_ppo_loss_mh;
         if (h.expl_kind == 2) {
-            k_ppo_loss_md<<<grid, block, 0, STREAM(stream)>>>(params, ld_params, values, ld_values, actions, old_logp, old_params,
-                                                              old_values, adv, targets, valids, index, offset, n, A, h, moments,
-                                                              sums, g_params, g_values, nullptr, 1);
+            kern<<<grid, block, 0, STREAM(stream)>>>(params, ld_params, values, ld_values, actions, old_logp, old_params,
+                                                     old_values, adv, targets, valids, index, offset, n, A, h, moments,
+                                                     sums, g_params, g_values, nullptr, 1);
             k_symkl_gate<<<dim3(1), dim3(64), 0, STREAM(stream)>>>(sums, moments);
         }
-        k_ppo_loss_md<<<grid, block, 0, STREAM(stream)>>>(params, ld_params, values, ld_values, actions, old_logp, old_params,
-                                                          old_values, adv, targets, valids, index, offset, n, A, h, moments, sums,
-                                                          g_params, g_values, ratio_out, 0);
-        return sf_launch_status("sf_ppo_loss");
+        kern<<<grid, block, 0, STREAM(stream)>>>(params, ld_params, values, ld_values, actions, old_logp, old_params,
+                                                 old_values, adv, targets, valids, index, offset, n, A, h, moments, sums,
+                                                 g_params, g_values, ratio_out, 0);
+        return sf_launch_status(what);
     }
     if (A >= WIDE_MIN_A) {  // a single Discrete(A) / Box(A / 2) as a one-member head list
         LossDev hw = h;
@@ -1272,7 +1488,38 @@ extern "C" int sf_ppo_loss(const float *params, int ld_params, const float *valu
     PL_DISPATCH(k_ppo_loss, params, ld_params, values, ld_values, actions, old_logp, old_params, old_values, adv, targets, valids, index,
                 offset, n, A, h, moments, sums, g_params, g_values, ratio_out);
 #undef PL_DISPATCH
-    return sf_launch_status("sf_ppo_loss");
+    return sf_launch_status(what);
+}
+
+extern "C" int sf_ppo_loss(const float *params, int ld_params, const float *values, int ld_values,
+                           const float *actions, const float *old_logp, const float *old_params,
+                           const float *old_values, const float *adv, const float *targets, const uint8_t *valids,
+                           const int32_t *index, int64_t offset, int64_t n, int A, const sf_loss_cfg *h_cfg,
+                           const double *moments, double *sums, float *g_params, float *g_values, float *ratio_out,
+                           void *stream) {
+    return ppo_loss_launch("sf_ppo_loss", params, ld_params, values, ld_values, actions, old_logp, old_params, old_values,
+                           adv, targets, valids, index, offset, n, A, h_cfg, h_cfg ? h_cfg->head_n : nullptr,
+                           h_cfg ? h_cfg->num_heads : 0, 8, moments, sums, g_params, g_values, ratio_out, stream);
+}
+
+extern "C" int sf_ppo_loss_heads(const float *params, int ld_params, const float *values, int ld_values,
+                                 const float *actions, const float *old_logp, const float *old_params,
+                                 const float *old_values, const float *adv, const float *targets, const uint8_t *valids,
+                                 const int32_t *index, int64_t offset, int64_t n, int A, const sf_loss_cfg *h_cfg,
+                                 const double *moments, double *sums, float *g_params, float *g_values, float *ratio_out,
+                                 const int32_t *head_n, int num_heads, void *stream) {
+    // the list is the argument's, whatever the struct says; one member is that member alone, as num_heads <= 1 there
+    SF_REQUIRE(head_n && num_heads >= 1 && num_heads <= SF_MAX_ACTION_HEADS,
+               "sf_ppo_loss_heads: %d action heads, the limit is %d (SF_MAX_ACTION_HEADS)", num_heads,
+               SF_MAX_ACTION_HEADS);
+    if (num_heads == 1)
+        SF_REQUIRE(h_cfg && head_n[0] == (h_cfg->action_kind == 0 ? A : -(A / 2)),
+                   "sf_ppo_loss_heads: a one-member list must be Discrete(A) with action_kind 0 or Box(A / 2) with 1");
+    else
+        SF_REQUIRE(h_cfg && h_cfg->action_kind == 0, "sf_ppo_loss_heads: a head list needs action_kind 0");
+    return ppo_loss_launch("sf_ppo_loss_heads", params, ld_params, values, ld_values, actions, old_logp, old_params,
+                           old_values, adv, targets, valids, index, offset, n, A, h_cfg, head_n, num_heads,
+                           SF_MAX_ACTION_HEADS, moments, sums, g_params, g_values, ratio_out, stream);
 }
 
 __global__ void k_loss_scalars(const double *__restrict__ sums, const double *__restrict__ moments, LossDev h,
@@ -1301,7 +1548,7 @@ __global__ void k_loss_scalars(const double *__restrict__ sums, const double *__
 extern "C" int sf_loss_scalars(const double *sums, const double *moments, const sf_loss_cfg *h_cfg, float *out,
                                void *stream) {
     SF_REQUIRE(sums && moments && h_cfg && out, "sf_loss_scalars: null pointer");
-    k_loss_scalars<<<dim3(1), dim3(64), 0, STREAM(stream)>>>(sums, moments, make_loss_dev(h_cfg), out);
+    k_loss_scalars<<<dim3(1), dim3(64), 0, STREAM(stream)>>>(sums, moments, make_loss_dev(h_cfg, nullptr, 0), out);
     return sf_launch_status("sf_loss_scalars");
 }
 
@@ -1897,7 +2144,7 @@ __global__ __launch_bounds__(256) void k_sample_write(const float *__restrict__ 
     if (env_actions) env_actions[b] = a;
 }
 
-// The three samplers for A > 128, one wave per env row: any head list of up to 8 members, or one Discrete(A) with an
+// The three samplers for A > 128, one wave per env row: any head list of up to SF_MAX_ACTION_HEADS members, or one Discrete(A) with an
 // action mask (mask != nullptr, the rule above k_sample_write_masked).  Same Philox counters, uniforms and draw rule
 // as the lane-per-row samplers.  The CDF is walked 64 columns at a time: an inclusive wave scan of the chunk's
 // probabilities plus the carry of the chunks before it, a ballot for the first lane with u < cdf.
@@ -2217,19 +2464,17 @@ extern "C" int sf_sample_write_step_tuple(const float *logits, int ld_logits, co
                                           float *traj_policy_version, int32_t *env_actions, void *stream) {
     SF_REQUIRE(logits && values && head_n && traj_actions && traj_logits && traj_logp && traj_values &&
                    traj_policy_version, "sf_sample_write_step_tuple: null pointer");
-    SF_REQUIRE(num_heads >= 1 && num_heads <= 8 && B > 0 && T > 0 && t >= 0 && t < T,
-               "sf_sample_write_step_tuple: bad shape heads=%d B=%d T=%d t=%d", num_heads, B, T, t);
+    SF_REQUIRE(B > 0 && T > 0 && t >= 0 && t < T, "sf_sample_write_step_tuple: bad shape heads=%d B=%d T=%d t=%d",
+               num_heads, B, T, t);
     LossDev hd = {};
+    bool any_box;
+    const int A = heads_from_host("sf_sample_write_step_tuple", head_n, num_heads, SF_MAX_ACTION_HEADS, hd.head_n,
+                                  &any_box);
+    if (A < 0) return SF_ERR_ARG;
     hd.num_heads = num_heads;
-    int A = 0;
-    for (int i = 0; i < num_heads; ++i) {  // head_n > 0: Discrete(n); head_n < 0: Box(-n) member, 2 * (-n) parameters
-        SF_REQUIRE(head_n[i] != 0, "sf_sample_write_step_tuple: empty action head");
-        SF_REQUIRE(head_n[i] > 0 || !env_actions,
-                   "sf_sample_write_step_tuple: a tuple with a Box member has no int32 env_actions (the env reads the "
-                   "trajectory's f32 action row)");
-        hd.head_n[i] = head_n[i];
-        A += head_n[i] > 0 ? head_n[i] : -2 * head_n[i];
-    }
+    SF_REQUIRE(!any_box || !env_actions,
+               "sf_sample_write_step_tuple: a tuple with a Box member has no int32 env_actions (the env reads the "
+               "trajectory's f32 action row)");
     SF_REQUIRE(ld_logits >= A && ld_values >= 1, "sf_sample_write_step_tuple: bad strides");
     if (A >= WIDE_MIN_A) {
         HeadsDev whd = {};

@@ -69,6 +69,9 @@ def is_discrete(space) -> bool:
     return hasattr(space, "n")
 
 
+MAX_ACTION_HEADS = 64  # SF_MAX_ACTION_HEADS of include/sf_hip.h: the members of a Tuple the native kernels take
+
+
 def is_tuple(space) -> bool:
     return hasattr(space, "spaces") and not hasattr(space, "keys")
 
@@ -76,12 +79,12 @@ def is_tuple(space) -> bool:
 def action_head_sizes(action_space):
     """members of the action distribution as the native loss / sampler kernels take them: [n] for Discrete(n); one entry
     per member of a Tuple — n for Discrete(n), -D for Box(D) (2 D parameters [means | log_std], D action columns;
-    action_distributions.py:197-287 composes any members) — at most 8; [] for a bare Box"""
+    action_distributions.py:197-287 composes any members) — at most MAX_ACTION_HEADS; [] for a bare Box"""
     if is_discrete(action_space):
         return [int(action_space.n)]
     if is_tuple(action_space):
-        if len(action_space.spaces) > 8:
-            raise NotImplementedError("at most 8 action heads")
+        if len(action_space.spaces) > MAX_ACTION_HEADS:
+            raise NotImplementedError(f"at most {MAX_ACTION_HEADS} action heads, got {len(action_space.spaces)}")
         out = []
         for sp in action_space.spaces:
             if is_discrete(sp):

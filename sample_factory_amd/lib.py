@@ -48,7 +48,7 @@ class sf_res_desc(C.Structure):
 # every symbol include/sf_hip.h declares (tests/test_abi.py checks the header against this list and the .so)
 SYMBOLS = [
     "sf_last_error", "sf_abi_version", "sf_valid_mask", "sf_gae_returns", "sf_moments", "sf_rms_update",
-    "sf_rms_apply", "sf_vtrace", "sf_ppo_loss", "sf_loss_scalars", "sf_train_summaries", "sf_minibatch_indices", "sf_minibatch_expand", "sf_grad_sumsq",
+    "sf_rms_apply", "sf_vtrace", "sf_ppo_loss", "sf_ppo_loss_heads", "sf_loss_scalars", "sf_train_summaries", "sf_minibatch_indices", "sf_minibatch_expand", "sf_grad_sumsq",
     "sf_adam_step", "sf_adam_step_dlr", "sf_lr_kl_adaptive", "sf_clock_probe", "sf_lamb_step", "sf_rnn_cell_fwd", "sf_rnn_cell_bwd", "sf_rows_add_scale", "sf_mlp2_fwd", "sf_rnn_store_state", "sf_rnn_chunk_setup", "sf_lstm_seq_supported", "sf_lstm_seq_fwd", "sf_lstm_seq_bwd", "sf_gru_seq_fwd", "sf_gru_seq_bwd", "sf_seq_fwd_x_supported", "sf_lstm_seq_fwd_x", "sf_gru_seq_fwd_x", "sf_rnn_rowseq_supported", "sf_rnn_rowseq_fwd", "sf_rnn_rowseq_bwd", "sf_rnn_wideseq_supported", "sf_rnn_seq_slab_rows", "sf_rnn_wideseq_fwd", "sf_rnn_wideseq_bwd", "sf_linear_fwd_dual_supported", "sf_linear_fwd_dual",
     "sf_obsnorm_moments", "sf_obsnorm_update", "sf_obsnorm_apply", "sf_sample_write_step",
     "sf_sample_write_step_tuple", "sf_sample_write_step_masked", "sf_traj_write_env_step", "sf_synth_obs",
@@ -604,9 +604,18 @@ def rows_add_scale(a, b, keep, Cn, H, y) -> None:
                                     ptr(y, "f32", "y"), stream()), "sf_rows_add_scale")
 
 
+MAX_ACTION_HEADS = 64  # SF_MAX_ACTION_HEADS (include/sf_hip.h)
+
+
+def _head_array(head_sizes):
+    """host int32 array of a head list, sized by the list (the library copies it during the call; a recorded launch
+    program keeps the array alive in its argument tuple).  The library refuses more than MAX_ACTION_HEADS members."""
+    return (C.c_int32 * len(head_sizes))(*[int(x) for x in head_sizes])
+
+
 def vtrace(params, ld_params, values, ld_values, actions, old_logp, rewards, dones, index, offset, n, A, action_kind,
            recurrence, gamma, rho_hat, c_hat, vs, adv, head_sizes=None) -> None:
-    hn = (C.c_int32 * 8)(*[int(x) for x in head_sizes]) if head_sizes and len(head_sizes) > 1 else None
+    hn = _head_array(head_sizes) if head_sizes and len(head_sizes) > 1 else None
     _check(load().sf_vtrace(_raw(params, "f32", "params"), int(ld_params), _raw(values, "f32", "values"),
                             int(ld_values), ptr(actions, "f32", "actions"),
                             ptr(old_logp, "f32", "old_logp"), ptr(rewards, "f32", "rewards"), ptr(dones, "u8", "dones"),
@@ -617,16 +626,22 @@ def vtrace(params, ld_params, values, ld_values, actions, old_logp, rewards, don
 
 
 def ppo_loss(params, ld_params, values, ld_values, actions, old_logp, old_params, old_values, adv, targets, valids,
-             index, offset, n, A, cfg: sf_loss_cfg, mom, sums, g_params, g_values, ratio_out=None) -> None:
-    """params/values (and g_params/g_values) may be strided column views of one [n, ld] matrix."""
-    _check(load().sf_ppo_loss(_raw(params, "f32", "params"), int(ld_params), _raw(values, "f32", "values"),
-                              int(ld_values), ptr(actions, "f32", "actions"), ptr(old_logp, "f32", "old_logp"),
-                              ptr(old_params, "f32", "old_params"), ptr(old_values, "f32", "old_values"),
-                              ptr(adv, "f32", "adv"), ptr(targets, "f32", "targets"), ptr(valids, "u8", "valids"),
-                              ptr(index, "i32", "index"), i64(offset), i64(n), int(A), C.byref(cfg),
-                              ptr(mom, "f64", "moments"), ptr(sums, "f64", "sums"), _raw(g_params, "f32", "g_params"),
-                              _raw(g_values, "f32", "g_values"), ptr(ratio_out, "f32", "ratio_out"), stream()),
-           "sf_ppo_loss")
+             index, offset, n, A, cfg: sf_loss_cfg, mom, sums, g_params, g_values, ratio_out=None,
+             head_sizes=None) -> None:
+    """params/values (and g_params/g_values) may be strided column views of one [n, ld] matrix.  head_sizes: the Tuple's
+    member list; up to 8 members it must already be in cfg (num_heads / head_n) and sf_ppo_loss runs as ever, a longer
+    one goes to sf_ppo_loss_heads as an argument and cfg's list is neither read nor written."""
+    args = (_raw(params, "f32", "params"), int(ld_params), _raw(values, "f32", "values"),
+            int(ld_values), ptr(actions, "f32", "actions"), ptr(old_logp, "f32", "old_logp"),
+            ptr(old_params, "f32", "old_params"), ptr(old_values, "f32", "old_values"),
+            ptr(adv, "f32", "adv"), ptr(targets, "f32", "targets"), ptr(valids, "u8", "valids"),
+            ptr(index, "i32", "index"), i64(offset), i64(n), int(A), C.byref(cfg),
+            ptr(mom, "f64", "moments"), ptr(sums, "f64", "sums"), _raw(g_params, "f32", "g_params"),
+            _raw(g_values, "f32", "g_values"), ptr(ratio_out, "f32", "ratio_out"))
+    if head_sizes is not None and len(head_sizes) > len(cfg.head_n):
+        _check(load().sf_ppo_loss_heads(*args, _head_array(head_sizes), len(head_sizes), stream()), "sf_ppo_loss_heads")
+    else:
+        _check(load().sf_ppo_loss(*args, stream()), "sf_ppo_loss")
 
 
 def loss_scalars(sums, mom, cfg: sf_loss_cfg, out) -> None:
@@ -738,7 +753,7 @@ def sample_write_step_tuple(logits, ld_logits, values, ld_values, B, head_n, T, 
                             deterministic, traj_actions, traj_logits, traj_logp, traj_values, traj_policy_version,
                             env_actions) -> None:
     """Tuple of Discrete heads; env_actions int32 [B, len(head_n)]"""
-    hn = (C.c_int32 * 8)(*[int(x) for x in head_n])
+    hn = _head_array(head_n)
     _check(load().sf_sample_write_step_tuple(_raw(logits, "f32", "logits"), int(ld_logits),
                                              _raw(values, "f32", "values"), int(ld_values), int(B), len(head_n), hn,
                                              int(T), int(t), u32(seed), u32(step), u32(row0), f(policy_version),
