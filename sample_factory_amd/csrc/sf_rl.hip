@@ -267,10 +267,10 @@ __global__ __launch_bounds__(256) void k_rms_apply(float *__restrict__ x, int64_
     const float sigma = sqrtf((float)stats[1] + 1e-5f);
     const float inv = 1.0f / sigma;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float v = x[i];
-        if (denormalize) v = clampf(v, -5.0f, 5.0f) * sigma + mu;
-        else v = clampf((v - mu) * inv, -5.0f, 5.0f);
-        x[i] = v;
+        // torch.clamp hands a NaN on (a one-sample batch has no unbiased variance: NaN statistics); fminf / fmaxf drop it
+        const float u = denormalize ? x[i] : (x[i] - mu) * inv;
+        const float c = (u != u) ? u : clampf(u, -5.0f, 5.0f);
+        x[i] = denormalize ? c * sigma + mu : c;
     }
 }
 
