@@ -27,6 +27,7 @@
 #define SF_GLDS_ABLATE 0  // timing experiments only (sf_nn_glds.h)
 #endif
 #include <type_traits>
+#include <algorithm>
 
 #define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
@@ -952,6 +953,7 @@ struct ConvPlan {
     int partials;         // weight gradient: partial results in the workspace; partial_b starts partials * K * N floats in
     int rx, ry, rtot;     // XCD-aware block order (sf_nn_glds.h): tiles per row / column, total (0 = plain grid)
     int main_tiles;       // k_fwd_glds_zt: 128-row tiles in front of the split last round
+    QuadrowClasses qr;    // k_dgrad_quadrow / _z: the column classes and their tiles (sf_nn_glds.h)
     bool recommended;     // sf_conv_fwd_t_supported's answer
 };
 static ConvPlan plan_init() {
@@ -1849,6 +1851,32 @@ static bool dgrad_quadrow_zl(const ConvG &g, int64_t n) {
     return (sw().dgrad_zl & 1) && g.Cout % 64 == 0 && n * (int64_t)g.OH * g.OW * g.Cout < (1LL << 30) &&
            (int64_t)g.K * g.Cout < (1LL << 30) && n * (int64_t)g.H * g.W * g.Cin < (1LL << 30);
 }
+// Column classes of the row-walking strided data gradient (sf_nn_glds.h): runs of group columns iwc with the same tap
+// columns b in [max(0, iwc - OW + 1), min(KW/S - 1, iwc)] inside dY, each padded to whole BM-row tiles.  Launch order:
+// the classes with the most tap columns first (conv2 at n = 32768: 2048 interior tiles = four full rounds of the 512
+// resident work-groups, then the 2 x 256 border tiles with half the chunks).  Returns the tile count.
+static unsigned plan_quadrow_classes(QuadrowClasses &q, const ConvG &g, int64_t n, int BM) {
+    const int Wg = g.W / g.S, KWs = g.KW / g.S;
+    q.ncls = 0;
+    q.n = (uint32_t)n;
+    for (int iwc = 0; iwc < Wg; ++iwc) {
+        const int lo = std::max(0, iwc - g.OW + 1), nb = std::max(0, std::min(KWs - 1, iwc) - lo + 1);
+        QuadrowClass *last = q.ncls ? &q.c[q.ncls - 1] : nullptr;
+        if (last && last->nb == nb && (nb == 0 || last->b_lo == lo)) { ++last->dw.d; continue; }
+        QuadrowClass &c = q.c[q.ncls++];
+        c.col0 = iwc; c.b_lo = lo; c.nb = nb; c.dw.d = 1;
+    }
+    std::stable_sort(q.c, q.c + q.ncls, [](const QuadrowClass &a, const QuadrowClass &b) {
+        return a.nb != b.nb ? a.nb > b.nb : a.dw.d > b.dw.d;  // most chunks per step first
+    });
+    unsigned tiles = 0;
+    for (int i = 0; i < q.ncls; ++i) {
+        q.c[i].tile0 = tiles;
+        tiles += cdiv64(n * (int64_t)q.c[i].dw.d, BM);
+        q.c[i].dw = make_fastdiv(q.c[i].dw.d);
+    }
+    return tiles;
+}
 // sf_conv_dgrad.  plan.variant: k_conv_dgrad's VEC argument
 static ConvPlan plan_conv_dgrad(const ConvG &g, int64_t n, const Operands &o) {
     ConvPlan p = plan_init();
@@ -1882,9 +1910,10 @@ static ConvPlan plan_conv_dgrad(const ConvG &g, int64_t n, const Operands &o) {
         // k_dgrad_pix_z with SADDR-form DMA only (conv3: 1308 / 1316 -> 1277 / 1297 us; the full form — pointer fragment reads,
         // two chunks per trip — costs hipcc 256 + 168 registers against 173 + 32 and the second wave per SIMD with them:
         // 1214 -> 1316 us, compile-time switch SF_DGRAD_PIX_ZL_LITE=0) — profiles/r05_k_dgrad_zl_ab.log, r05_n_dgrad_pix_lite_ab.log
-        if (g.S > 1 && g.KH % g.S == 0 && g.KW % g.S == 0 && g.W % g.S == 0 && pix_cfg != 3) {
+        if (g.S > 1 && g.KH % g.S == 0 && g.KW % g.S == 0 && g.W % g.S == 0 && pix_cfg != 3 &&
+            2 * (g.KW / g.S) - 1 <= SF_QUADROW_MAX_CLASSES) {
             // strided conv, row-walking tiles of (sample, group-column) rows: contiguous activation / gradient rows
-            p.grid = dim3(cdiv64(n * (g.W / g.S), 128), cdiv64(g.S * g.S * g.Cin, 128));
+            p.grid = dim3(plan_quadrow_classes(p.qr, g, n, 128), cdiv64(g.S * g.S * g.Cin, 128));
             if (dgrad_quadrow_zl(g, n)) plan_tile(p, K_DGRAD_QUADROW_Z, "k_dgrad_quadrow_z", TileArgs{128, 128, 2, 2});
             else plan_tile(p, K_DGRAD_QUADROW, "k_dgrad_quadrow", TileArgs{128, 128, 2, 2});
             return p;
@@ -1946,7 +1975,7 @@ extern "C" int sf_conv_dgrad(const float *dout, const float *w, const float *in_
             if (TILE_IS(128, 128)) DGRAD_LINEAR(128, 128); else DGRAD_LINEAR(64, 64);
             break;
         }
-#define QUADROW_ARGS g, dout, w, in_act, din, n * (g.W / g.S), make_fastdiv((uint32_t)(g.W / g.S))
+#define QUADROW_ARGS g, dout, w, in_act, din, p.qr
         case K_DGRAD_QUADROW_Z: k_dgrad_quadrow_z<128, 128, 2, 2><<<p.grid, p.block, 0, st>>>(QUADROW_ARGS); break;
         case K_DGRAD_QUADROW: k_dgrad_quadrow<128, 128, 2, 2><<<p.grid, p.block, 0, st>>>(QUADROW_ARGS); break;
 #undef QUADROW_ARGS

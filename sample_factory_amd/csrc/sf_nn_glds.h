@@ -1532,21 +1532,46 @@ __global__ __launch_bounds__(256) void k_conv_u8_img_norm(ConvG g, const uint8_t
 // m = (sample, iwc) — about 13 whole image rows of groups — and the block walks DOWN the image (ihc = 0..Hg-1): per
 // step every sample of the tile reads/writes two complete contiguous image rows (2 x 2.5 KB for conv2), dY rows are
 // contiguous 256-byte neighbours, and the per-row (sample, iwc) decode is done once per block (row offsets parked in
-// LDS).  (a, b) blocks outside dY: a is uniform per step and skipped; b depends on iwc, i.e. on the row, so a row whose
-// tap column falls outside dY takes its DMA from the zero page (10 % of the rows x taps for conv2 — the only
-// structural-zero work left).  Measured (n = 32768, conv2): class-decomposed im2col kernel 2.98 ms, pixel-major
-// 2.51 ms, this kernel 2.33 ms; with all memory traffic removed 1.65 ms — the epilogue's 64 loads + 64 stores per lane
-// and step, not the matrix pipe, are what is left.
+// LDS).  Measured (n = 32768, conv2): class-decomposed im2col kernel 2.98 ms, pixel-major 2.51 ms, this kernel
+// 2.33 ms; with all memory traffic removed 1.65 ms — the epilogue's 64 loads + 64 stores per lane and step, not the
+// matrix pipe, are what is left.
+//
+// (a, b) blocks outside dY.  a is uniform per step and skipped.  b depends on iwc: the tap columns inside dY are
+// b in [max(0, iwc - OW + 1), min(KW/S - 1, iwc)].  The group columns with the same range form a COLUMN CLASS, a
+// contiguous run of iwc (conv2: {0} with b = 0, {1..8} with b = 0, 1 and {9} with b = 1; at most 2*KW/S - 1 classes).
+// The rows are numbered per class — sample-major, iwc inner — and every class is padded to whole tiles, so a tile
+// belongs to one class and its steps run exactly the chunks (a of the step) x (b of the class) x (channel chunk): every
+// lane's dY address is inside dY for every chunk, no structural zero is multiplied (the border columns' missing tap
+// column was 10 % of conv2's MFMAs and DMA), and the dY operand of the ZL form is uniform base + one constant 32-bit
+// lane offset like the weight operand.  The skipped products were exact zeros added to sums that start at +0: results
+// are bit-identical to multiplying them.  plan_conv_dgrad (sf_nn.hip) builds the class table, the classes with the most
+// tap columns first, so that the short border tiles fill the last round of the launch (conv2 at n = 32768: 2048 interior
+// tiles = four rounds of the 512 resident work-groups, then 512 border tiles of half the length).  A border tile's rows
+// are 128 different samples: its epilogue writes one 256-byte piece per sample and image row, the pattern that was no
+// faster as a whole kernel (above) — here it is a fifth of the rows, and the launch is 13 % shorter with it than with
+// the zero columns.
+constexpr int SF_QUADROW_MAX_CLASSES = 7;  // KW / S <= 4
+struct QuadrowClass {
+    uint32_t tile0;    // first tile (blockIdx.x) of the class
+    int col0;          // first group column; the class holds dw.d columns
+    int b_lo, nb;      // tap columns inside dY: b_lo .. b_lo + nb - 1
+    FastDiv dw;
+};
+struct QuadrowClasses {
+    int ncls;
+    uint32_t n;        // samples
+    QuadrowClass c[SF_QUADROW_MAX_CLASSES];  // in launch order
+};
 template <int BM, int BN, int WM, int WN, bool ZL>
 __device__ __forceinline__ void dgrad_quadrow_body(ConvG g, const float *__restrict__ dy,
                                                    const float *__restrict__ w, const float *__restrict__ in_act,
-                                                   float *__restrict__ din, int64_t Mrows, FastDiv dWg) {
+                                                   float *__restrict__ din, const QuadrowClasses &qc) {
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     constexpr int AI = BM / 32, BI = BN / 32;
     constexpr int STAGE = (BM + BN) * 32;
     static_assert(WM * WN == 4 && TM >= 1 && TN >= 1, "4 waves per block");
     __shared__ __attribute__((aligned(1024))) float lds[2 * STAGE];
-    __shared__ uint32_t rowoff[BM];  // element offset of (sample, iwc) inside din / in_act, 0xFFFFFFFF = row past M
+    __shared__ uint32_t rowoff[BM];  // element offset of (sample, iwc) inside din / in_act, 0xFFFFFFFF = row past the class's end
     __shared__ int rot_s;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // uniform: LDS-DMA bases (M0) stay on the scalar unit
     const int wm = wave / WN, wn = wave % WN;
@@ -1557,32 +1582,42 @@ __device__ __forceinline__ void dgrad_quadrow_body(ConvG g, const float *__restr
     // work-group that replaces a finished one inherits its slot) -- a key from blockIdx cannot know who shares a CU.
     if (ZL && SF_QUADROW_ROT && tid == 0) rot_s = (int)(__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4) & 1u);
     const int Cin = g.Cin, Cout = g.Cout, S = g.S, OH = g.OH, OW = g.OW, H = g.H, W = g.W;
-    const int Hg = (H + S - 1) / S, Wg = (int)dWg.d, N = S * S * Cin;
-    const int KHs = g.KH / S, KWs = g.KW / S, CC = Cout >> 5;
-    const int64_t m0 = (int64_t)blockIdx.x * BM;
+    const int Hg = (H + S - 1) / S, N = S * S * Cin;
+    const int KHs = g.KH / S, CC = Cout >> 5;
+    // the column class of this tile (constant indices only: the table stays in the kernel-argument segment)
+    QuadrowClass k = qc.c[0];
+#pragma unroll
+    for (int c = 1; c < SF_QUADROW_MAX_CLASSES; ++c)
+        if (c < qc.ncls && blockIdx.x >= qc.c[c].tile0) k = qc.c[c];
+    const FastDiv dWc = k.dw;
+    const int Wc = (int)dWc.d, col0 = k.col0, b_lo = k.b_lo, nb = k.nb;
+    const uint32_t Mrows = qc.n * (uint32_t)Wc;  // rows of the class
+    const uint32_t m0 = (blockIdx.x - k.tile0) * (uint32_t)BM;
     const int n0 = blockIdx.y * BN;
     const uint32_t sstride = (uint32_t)(H * W * Cin);
     if (tid < BM) {
-        const int64_t m = m0 + tid;
-        const uint32_t mm = m < Mrows ? (uint32_t)m : 0u;
-        const uint32_t s = fdiv(mm, dWg), iwc = mm - s * (uint32_t)Wg;
+        const uint32_t m = m0 + tid;
+        const uint32_t mm = m < Mrows ? m : 0u;
+        const uint32_t s = fdiv(mm, dWc), iwc = (uint32_t)col0 + mm - s * (uint32_t)Wc;
         // ZL: BYTE offsets (the launcher guarantees n*H*W*Cin*4 < 2^32), so that "uniform base + 32-bit lane offset" stores and
         // loads need one v_add_u32 per element instead of a 64-bit address build-up
         rowoff[tid] = m < Mrows ? (s * sstride + iwc * (uint32_t)(S * Cin)) * (ZL ? 4u : 1u) : 0xFFFFFFFFu;
     }
     const int lrow = lane >> 3, lpos = lane & 7;
+    // dY lane addresses (rows past the class's end repeat its last row): ZL as 32-bit byte offsets from dy (the launcher
+    // guarantees n*OH*OW*Cout < 2^30), else as pointers
     const float *asrc[AI], *bsrc[BI];
-    int aiwc[AI];
+    uint32_t avoff[AI];
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
         const int row = (i * 4 + wave) * 8 + lrow;
-        int64_t m = m0 + row;
+        uint32_t m = m0 + row;
         m = m < Mrows ? m : Mrows - 1;
-        const uint32_t s = fdiv((uint32_t)m, dWg);
-        aiwc[i] = (int)((uint32_t)m - s * (uint32_t)Wg);
-        asrc[i] = dy + ((int64_t)s * (OH * OW) + aiwc[i]) * Cout + ((lpos ^ ((row >> 1) & 7)) << 2);
+        const uint32_t s = fdiv(m, dWc), iwc = (uint32_t)col0 + m - s * (uint32_t)Wc;
+        const int64_t e = ((int64_t)s * (OH * OW) + iwc) * Cout + ((lpos ^ ((row >> 1) & 7)) << 2);
+        if constexpr (ZL) avoff[i] = (uint32_t)e * 4u;
+        else asrc[i] = dy + e;
     }
-    const int zpos = lpos << 2;  // any 16 bytes of the zero page
 #pragma unroll
     for (int i = 0; i < BI; ++i) {
         const int row = (i * 4 + wave) * 8 + lrow;
@@ -1611,7 +1646,7 @@ __device__ __forceinline__ void dgrad_quadrow_body(ConvG g, const float *__restr
     __syncthreads();  // rowoff visible
     // Complete tiles (all rows real, all columns real, no group row hanging over the image) skip the per-element
     // predicates; the activation kind is hoisted out of the element loops.
-    const bool full = m0 + BM <= Mrows && n0 + BN <= N && H % S == 0;
+    const bool full = m0 + (uint32_t)BM <= Mrows && n0 + BN <= N && H % S == 0;
     auto ld32 = [&](const float *base, uint32_t off) {  // ZL: off in bytes; else in elements
         if constexpr (ZL) return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + (size_t)off);
         else return base[off];
@@ -1701,7 +1736,7 @@ __device__ __forceinline__ void dgrad_quadrow_body(ConvG g, const float *__restr
         const int a_hi = ihc < KHs - 1 ? ihc : KHs - 1;
         p.na = a_hi - p.a_lo + 1;
         p.na = p.na > 0 ? p.na : 0;
-        p.total = p.na * KWs * CC;
+        p.total = p.na * nb * CC;
         return p;
     };
     auto next_step = [&](int v) {  // first position >= v with work (v = Hg: none)
@@ -1711,8 +1746,7 @@ __device__ __forceinline__ void dgrad_quadrow_body(ConvG g, const float *__restr
     };
     auto row_at = [&](int v) { return v + rot < Hg ? v + rot : v + rot - Hg; };
     // ZL (k_dgrad_quadrow_z): fragments through per-lane LDS pointers with the stage as an immediate, the weight operand's
-    // DMA as uniform base + 32-bit lane offset.  (The dY operand keeps 64-bit lane addresses: a lane whose tap column is
-    // outside dY reads the zero page, which no 32-bit offset from dY can name.)
+    // and the dY operand's DMA as uniform base + 32-bit lane offset (avoff above).
     uint32_t bvoff[BI];
     const float *apl[4], *bpl[4];
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float *)lds;
@@ -1730,57 +1764,50 @@ __device__ __forceinline__ void dgrad_quadrow_body(ConvG g, const float *__restr
     auto issue = [&](const St &p, int q, int stage) {
         if (ZL && (SF_GLDS_ABLATE & 16)) return;
         const int blk = q / CC, cc = q - blk * CC;
-        const int a = p.a_lo + blk / KWs, b = blk % KWs;
+        const int a = p.a_lo + blk / nb, b = b_lo + blk % nb;
         const int64_t aoff = (int64_t)((p.ihc - a) * OW - b) * Cout + cc * 32;
         const int64_t boff = (int64_t)((S * a * g.KW + S * b) * Cin) * Cout + cc * 32;
         float *sa = lds + stage * STAGE, *sb = sa + BM * 32;
-#pragma unroll
-        for (int i = 0; i < AI; ++i) {
-            const int ow = aiwc[i] - b;
-            const float *src = (ow >= 0 && ow < OW) ? asrc[i] + aoff : sf_zero_page + zpos;
-            GLDS16(src, sa + (i * 4 + wave) * 256);
-        }
         if constexpr (ZL) {
-            const float *bb = w + boff;
+            const float *ab = dy + aoff, *bb = w + boff;
+#pragma unroll
+            for (int i = 0; i < AI; ++i) glds16_s(ab, avoff[i], lds0 + (uint32_t)((stage * STAGE + (i * 4 + wave) * 256) * 4));
 #pragma unroll
             for (int i = 0; i < BI; ++i)
                 glds16_s(bb, bvoff[i], lds0 + (uint32_t)((stage * STAGE + BM * 32 + (i * 4 + wave) * 256) * 4));
             return;
         }
 #pragma unroll
+        for (int i = 0; i < AI; ++i) GLDS16(asrc[i] + aoff, sa + (i * 4 + wave) * 256);
+#pragma unroll
         for (int i = 0; i < BI; ++i) GLDS16(bsrc[i] + boff, sb + (i * 4 + wave) * 256);
     };
-    // ZL + SF_QUADROW_PREP: the addresses of a chunk's DMA are worked out ONE CHUNK AHEAD (scalar divisions of the chunk
-    // index, the per-row zero-page select and its 64-bit adds: ~40 scalar + ~30 vector instructions that otherwise sit
-    // between the barrier and the DMA with no MFMA of this wave in flight), so that after the barrier only the 8 DMA
-    // instructions are left; the work for the chunk after next is placed behind them, among the MFMAs.
+    // ZL + SF_QUADROW_PREP: the two uniform bases of a chunk's DMA are worked out ONE CHUNK AHEAD (scalar divisions of the
+    // chunk index and 64-bit adds: ~40 scalar instructions that otherwise sit between the barrier and the DMA with no MFMA of
+    // this wave in flight), so that after the barrier only the 8 DMA instructions are left; the work for the chunk after
+    // next is placed behind them, among the MFMAs.
     struct It { St st; int q; };
     auto advance = [&](It &it) {
         if (it.q + 1 < it.st.total) ++it.q;
         else { it.st = next_step(it.st.v + 1); it.q = 0; }
     };
-    struct Prep { const float *bb; const float *as[AI]; bool valid; };
+    struct Prep { const float *ab, *bb; bool valid; };
     auto prep = [&](const It &it) {
         Prep r;
         r.valid = it.st.v < Hg;
         const int q = r.valid ? it.q : 0;
         const int blk = q / CC, cc = q - blk * CC;
-        const int a = it.st.a_lo + blk / KWs, b = blk % KWs;
-        const int64_t aoff = (int64_t)((it.st.ihc - a) * OW - b) * Cout + cc * 32;
+        const int a = it.st.a_lo + blk / nb, b = b_lo + blk % nb;
+        r.ab = dy + ((int64_t)((it.st.ihc - a) * OW - b) * Cout + cc * 32);
         r.bb = w + (int64_t)((S * a * g.KW + S * b) * Cin) * Cout + cc * 32;
-#pragma unroll
-        for (int i = 0; i < AI; ++i) {
-            const int ow = aiwc[i] - b;
-            r.as[i] = (ow >= 0 && ow < OW) ? asrc[i] + aoff : sf_zero_page + zpos;
-        }
         return r;
     };
     auto fire = [&](const Prep &r, int stage, int part = 3) {  // part: 1 = the dY rows, 2 = the weight rows, 3 = both
         if (!r.valid || (SF_GLDS_ABLATE & 16)) return;
-        float *sa = lds + stage * STAGE;
         if (part & 1) {
 #pragma unroll
-            for (int i = 0; i < AI; ++i) GLDS16(r.as[i], sa + (i * 4 + wave) * 256);
+            for (int i = 0; i < AI; ++i)
+                glds16_s(r.ab, avoff[i], lds0 + (uint32_t)((stage * STAGE + (i * 4 + wave) * 256) * 4));
         }
         if (part & 2) {
 #pragma unroll
@@ -1884,14 +1911,14 @@ __device__ __forceinline__ void dgrad_quadrow_body(ConvG g, const float *__restr
 template <int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256, 2) void k_dgrad_quadrow(ConvG g, const float *__restrict__ dy,
                                                          const float *__restrict__ w, const float *__restrict__ in_act,
-                                                         float *__restrict__ din, int64_t Mrows, FastDiv dWg) {
-    dgrad_quadrow_body<BM, BN, WM, WN, false>(g, dy, w, in_act, din, Mrows, dWg);
+                                                         float *__restrict__ din, QuadrowClasses qc) {
+    dgrad_quadrow_body<BM, BN, WM, WN, false>(g, dy, w, in_act, din, qc);
 }
 template <int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256, 2) void k_dgrad_quadrow_z(ConvG g, const float *__restrict__ dy,
                                                            const float *__restrict__ w, const float *__restrict__ in_act,
-                                                           float *__restrict__ din, int64_t Mrows, FastDiv dWg) {
-    dgrad_quadrow_body<BM, BN, WM, WN, true>(g, dy, w, in_act, din, Mrows, dWg);
+                                                           float *__restrict__ din, QuadrowClasses qc) {
+    dgrad_quadrow_body<BM, BN, WM, WN, true>(g, dy, w, in_act, din, qc);
 }
 
 // ============================================================================================== WEIGHT GRADIENT, raw u8 frames

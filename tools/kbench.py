@@ -30,6 +30,7 @@ def main():
     if HASH: torch.manual_seed(0)
     ns = [int(v) for v in os.environ["KBENCH_NS"].split(",")] if os.environ.get("KBENCH_NS") else [4096, 32768]
     only = os.environ.get("KBENCH_LAYERS", "").split(",") if os.environ.get("KBENCH_LAYERS") else None
+    grads_at = set(ns) if os.environ.get("KBENCH_NS") else {32768}  # gradients: the training batch, or every n asked for
     for n in ns:
         for name, d in LAYERS:
             if only and name not in only: continue
@@ -55,14 +56,14 @@ def main():
                     t = timeit(lambda: lib.conv_fwd_t(x, stride, wt, b, out, n, d, wst), reps)
                     err = (out - ref).abs().max().item() / ref.abs().max().item()
                     res.append(f"fwd_t {t*1e3:8.1f}us {flops/t/1e9:6.1f}TF relerr {err:.1e}" + (f" #{digest(out)}" if HASH else ""))
-            if "wgrad" in which and n == 32768:
+            if "wgrad" in which and n in grads_at:
                 dw = torch.empty_like(w); db = torch.empty_like(b)
                 ws = torch.empty(lib.conv_wgrad_workspace(n, d),dtype=torch.uint8,device="cuda")
                 t = timeit(lambda: lib.conv_wgrad(x, stride, None, 0, dy, dw, db, n, d, ws), reps); res.append(f"wgrad {t*1e3:8.1f}us {flops/t/1e9:6.1f}TF" + (f" #{digest(dw)}" if HASH else ""))
-            if "dgrad" in which and n == 32768 and not d.in_u8:
+            if "dgrad" in which and n in grads_at and not d.in_u8:
                 din = torch.empty((n,d.H,d.W,d.Cin),device="cuda")
                 t = timeit(lambda: lib.conv_dgrad(dy, w, x, din, n, d), reps); res.append(f"dgrad {t*1e3:8.1f}us {flops/t/1e9:6.1f}TF" + (f" #{digest(din)}" if HASH else ""))
-            if "dgrad_noact" in which and n == 32768 and not d.in_u8:  # upper bound of what a mask-free epilogue could win
+            if "dgrad_noact" in which and n in grads_at and not d.in_u8:  # upper bound of what a mask-free epilogue could win
                 din = torch.empty((n,d.H,d.W,d.Cin),device="cuda")
                 t = timeit(lambda: lib.conv_dgrad(dy, w, None, din, n, d), reps); res.append(f"dgrad(no act read) {t*1e3:8.1f}us {flops/t/1e9:6.1f}TF" + (f" #{digest(din)}" if HASH else ""))
             print(f"n={n:6d} {name:6s} " + " | ".join(res), flush=True)
