@@ -624,9 +624,26 @@ int sf_conv_fwd_t(const float *in, int64_t in_sample_stride, const float *wt, co
                   int64_t n, const sf_conv_desc *desc, void *workspace, int64_t workspace_bytes, void *stream);
 int sf_transpose(const float *w, float *wt, int K, int N, void *stream); /* wt[N,K] = w[K,N]^T */
 
+/* The same forwards with an OUTPUT sample stride (floats; sign-bit words: mask_sample_stride u32 words): sample s, pixel p
+ * is written to out + s * out_sample_stride + p * Cout, with the arithmetic and the stores of the dense entry point.  One
+ * rollout step can so write slot t of an activation buffer laid out [E, T, OH*OW, Cout]; the next layer reads that slot
+ * through its input stride, and the learner reads rows [e*T + t] of the buffer as the dense activation of its dataset
+ * rows.  Only the launches whose dense kernel has a strided twin are taken: sf_conv_fwd_os_supported(op, ...) with op = 0
+ * for sf_conv_fwd_relu_mask_os (k_conv1_u8_bf16_w_os) and op = 3 for sf_conv_fwd_t_os (k_fwd_glds_zt_os, k_fwd_img_os; never
+ * split along K, so no workspace).  The strides must be multiples of 4 floats and at least one sample long, out 16-byte
+ * aligned. */
+int sf_conv_fwd_os_supported(int op, int64_t n, const sf_conv_desc *desc, int64_t in_sample_stride,
+                             int64_t out_sample_stride);
+int sf_conv_fwd_relu_mask_os(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
+                             const float *w, const float *bias, float *out, int64_t out_sample_stride,
+                             uint32_t *relu_mask, int64_t mask_sample_stride, int64_t n, const sf_conv_desc *h_desc,
+                             void *stream);
+int sf_conv_fwd_t_os(const float *in, int64_t in_sample_stride, const float *wt, const float *bias, float *out,
+                     int64_t out_sample_stride, int64_t n, const sf_conv_desc *desc, void *stream);
+
 /* Profiling aid (no reference counterpart): the kernel instantiation a conv/linear launch resolves to, spelled as
  * rocprofv3 prints it ("k_conv_fwd<128, 64, 2, 2, 0>").  op: 0 forward, 1 wgrad, 2 dgrad, 3 sf_conv_fwd_t,
- * 4 sf_conv_fwd_norm, 5 sf_conv_wgrad_norm. */
+ * 4 sf_conv_fwd_norm, 5 sf_conv_wgrad_norm, 6 sf_conv_fwd_relu_mask_os, 7 sf_conv_fwd_t_os. */
 int sf_conv_kernel_name(int op, int64_t n, const sf_conv_desc *desc, int split_k_allowed, char *out, int cap);
 /* dense layer: out[M,N] = act(in[M,K] * w[K,N] + bias); wgrad: dw[K,N] = in^T dout, db = colsum(dout);
  * dgrad: din[M,K] = (dout[M,N] * w^T) * relu_mask(in_act). */

@@ -163,6 +163,8 @@ class Learner:
         self.world = self.group.world if self.group is not None else 1
         self.dp = self.group is not None and self.group.on  # collectives are issued (world > 1, or forced for tests)
         self._grad_norms: List[float] = []
+        # first-minibatch forwards that resumed behind the rollout's kept conv activations / that ran the whole stack
+        self.reuse_stats = dict(reused=0, plain=0, last_prefix=0, last_reason="")
 
     # ------------------------------------------------------------------------------------------ init / checkpoints
     def _all_reduce(self, t: torch.Tensor) -> None:
@@ -500,7 +502,7 @@ class Learner:
         return dist, sc[0].clone(), sc[1].clone(), kl_old, sc[2].clone(), sc[3].clone(), summaries
 
     def _losses_native(self, buff: AttrDict, mb, num_invalids: int, scalars_out: Optional[torch.Tensor] = None,
-                       moments: Optional[torch.Tensor] = None):
+                       moments: Optional[torch.Tensor] = None, first_of: Optional[Tuple[int, int]] = None):
         """learner.py:537-669 for one minibatch mb=(index, offset, n): forward, (v-trace), advantage moments,
         fused loss forward+backward.  Returns (acts, g_heads, scalars[16] device tensor) — scalars follow
         sf_loss_scalars: policy, exploration, kl, value losses, kl mean/max, adv mean/std, n_valid, entropy."""
@@ -514,8 +516,18 @@ class Learner:
             h0 = ac._buf(("rnn", "h0"), (Cn, buff.rnn_states.shape[-1]))
             lib.rnn_chunk_setup(buff.dones, buff.valids, buff.rnn_states, index, offset, Cn, R, keep_tm, h0, traj_T=buff.T)
             rnn = dict(R=R, h0=h0, keep_tm=keep_tm)
+        kw = {}
+        if first_of == (0, 0):
+            # the first minibatch of the first epoch, still on the rollout's weights: the conv activations the rollout kept
+            # for exactly these rows stand in for conv1..conv3 (ActorCritic.kept_resume holds the guard); reuse_stats counts
+            resume, why = ac.kept_resume(buff.obs, index, offset, n, buff.T, 0, 0) if hasattr(ac, "kept_resume") else (None, "model")
+            st = self.reuse_stats
+            st["reused" if resume is not None else "plain"] += 1
+            st["last_prefix"], st["last_reason"] = (resume["prefix"] if resume is not None else 0), why
+            if resume is not None:
+                kw["resume_from"] = resume
         acts = ac.forward_heads(buff.obs, n, sample_stride=ac.obs_elems, index=index, offset=offset,
-                                traj_T=buff.T, tag="train", rnn=rnn)
+                                traj_T=buff.T, tag="train", rnn=rnn, **kw)
         heads = acts[-1]
         ld = ac.heads_ld  # 1 + A padded to a multiple of 4; padding columns of g_heads stay zero
         params, values = heads[:, 1:], heads[:, 0]
@@ -600,7 +612,8 @@ class Learner:
             for batch_num, mb in enumerate(minibatches):
                 row = self._scalars[epoch * n_mb + batch_num]
                 acts, g_heads, _ = self._losses_native(buff, mb, num_invalids, row,
-                                                       moments=None if mom_tab is None else mom_tab[batch_num])
+                                                       moments=None if mom_tab is None else mom_tab[batch_num],
+                                                       first_of=(epoch, batch_num))
                 index, offset, n = mb
                 # C1: every replica's gradient already carries the GLOBAL 1/n_valid -> SUM over replicas
                 if self._dp_split is not None:

@@ -79,6 +79,7 @@ class BatchedVectorEnvRunner:
         self._progs_layout = None
         self.program_replays = 0
         self._launch_key = getattr(actor_critic, "launch_key", None) if lib.LAUNCH_PROGRAMS else None
+        self.keep_on, self.keep_row0 = False, 0  # the model keeps the conv activations of this runner's steps (Runner.init)
         self.masked = "action_mask" in traj["obs"]
         if self.masked and (self.continuous or len(self.heads) != 1):
             raise NotImplementedError("action masks are supported for a single Discrete action space")
@@ -220,6 +221,8 @@ class BatchedVectorEnvRunner:
             self._progs[rec_key] = prog
         else:
             self._policy_and_sample(t)
+        if self.keep_on:  # (after a replay as well: the program wrote the same slot with the current weights)
+            self.ac.keep_note(t, self.keep_row0, self.B, self.obs[:, t].data_ptr())
         tr = self.traj
         # Box: f32 [B, D] view of the slab; Tuple with a Box member: f32 [B, columns] view, split per member for the env
         env_actions = tr["actions"][:, t] if (self.continuous or self.mixed) else self.env_actions
@@ -234,7 +237,8 @@ class BatchedVectorEnvRunner:
         ver, deterministic, cfg, step = self._c_ver, self._deterministic, self.cfg, self._c_step
         rnn = dict(states=tr["rnn_states"][:, t]) if self.rnn else None  # the state INPUT of step t (parity trap 13)
         x = {k: tr["obs"][k][:, t] for k in self.obs_keys} if self.multi_key else self.obs[:, t]
-        heads = self.ac.forward_heads(x, B, sample_stride=self.obs.stride(0), tag=self.tag, rnn=rnn)[-1]
+        kw = dict(keep=(t, self.keep_row0)) if self.keep_on else {}
+        heads = self.ac.forward_heads(x, B, sample_stride=self.obs.stride(0), tag=self.tag, rnn=rnn, **kw)[-1]
         if self.masked:
             mk = tr["obs"]["action_mask"][:, t]
             lib.sample_write_step_masked(heads[:, 1:], self.ld, heads[:, 0], self.ld, mk, mk.stride(0), B, A, T, t,

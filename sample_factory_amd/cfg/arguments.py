@@ -72,6 +72,7 @@ ENGINE_FLAGS = [
     ("dp_oneshot_bytes", int, 0),            # > 0: f32 / f64 SUM buckets up to this size (the 0.31 MB conv bucket, the moment / invalid-count scalars) go through the one-shot mailbox exchange (sf_dp_oneshot_*) instead of a ring all-reduce
     ("dp_native_rccl", _bool, False),        # gradient buckets through the C-ABI (sf_allreduce_grads) instead of torch.distributed
     ("dp_force_collectives", _bool, False),  # issue the collectives in a group of one rank (tests)
+    ("reuse_rollout_activations", str, "auto"),  # auto: the first minibatch reuses the rollout's conv activations (sync mode); off
     ("device_shuffle", _bool, False),        # shuffle_minibatches with the stateless on-device permutation
     ("sampler_thread", _bool, None),         # None: a sampler thread iff async_rl with a host env
     ("record_grad_norm", _bool, False),
@@ -164,6 +165,8 @@ def verify_cfg(cfg, env_info) -> bool:
         err(f"{cfg.batch_size=} must be a multiple of {cfg.rollout=}")
     if cfg.use_rnn and cfg.recurrence <= 1:
         err("RNN policies need recurrence > 1")
+    if str(getattr(cfg, "reuse_rollout_activations", "auto")) not in ("auto", "off"):
+        err(f"{cfg.reuse_rollout_activations=} must be 'auto' or 'off'")
     total_agents = cfg.num_workers * cfg.num_envs_per_worker * env_info.num_agents
     per_iter = cfg.num_batches_per_epoch * cfg.batch_size
     per_rollout = total_agents * cfg.rollout // cfg.num_policies

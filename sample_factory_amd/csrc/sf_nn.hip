@@ -383,6 +383,44 @@ __device__ __forceinline__ void store_fwd_tile(const f32x16 (&acc)[TM][TN], floa
     }
 }
 
+// store_fwd_tile with an output SAMPLE stride: row m of the flat row space belongs to sample m / OHOW, pixel m % OHOW, and goes
+// to out + sample * out_ss + pixel * N (k_fwd_glds_zt_os).  mrow0 = this lane's first row, col = its column of tile 0.
+template <int TM, int TN, int KIND>
+__device__ __forceinline__ void store_fwd_tile_os(const f32x16 (&acc)[TM][TN], float *__restrict__ out, int64_t mrow0,
+                                                  int64_t Mtot, const ConvG &g, int64_t out_ss, int col,
+                                                  const float *__restrict__ bias, int kind) {
+    const int N = g.Cout;
+    const uint32_t OHOW = (uint32_t)(g.OH * g.OW);
+    bool cok[TN];
+    float bv[TN];
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) {
+        cok[tn] = col + tn * 32 < N;
+        bv[tn] = (bias && cok[tn]) ? bias[col + tn * 32] : 0.f;
+    }
+    // a lane's rows come in groups of four consecutive ones (r & 3): the (sample, pixel) split and the 64-bit address are
+    // worked out once per group, a row that crosses into the next sample adds the distance between the two samples' ends
+    // (OHOW >= 4: at most one boundary inside a group; the launcher keeps out_ss below 2^30)
+    const int hop = (int)out_ss - (int)OHOW * N;
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t m0 = mrow0 + tm * 32 + 8 * q;
+            const uint32_t smp = fdiv((uint32_t)(m0 < Mtot ? m0 : 0), g.dOHOW), pix = (uint32_t)m0 - smp * OHOW;
+            float *p0 = out + (int64_t)smp * out_ss + (int64_t)pix * N + col;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int o = j * N + (pix + (uint32_t)j >= OHOW ? hop : 0);
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn) {
+                    const float v = act_fwd_c<KIND>(acc[tm][tn][4 * q + j] + bv[tn], kind);
+                    if (cok[tn] && m0 + j < Mtot) p0[o + tn * 32] = v;
+                }
+            }
+        }
+}
+
 // The same tile as v * act'(y): the data gradient of a linear layer is this forward GEMM on dY with the (untransposed)
 // weight matrix, finished with the derivative of the activation that produced the layer's input y (mk: pointer to the
 // tile's (0, 0) inside y, same [rows][N] layout).  KIND 0: no mask, 1: ReLU, < 0: run-time kind.
@@ -972,6 +1010,14 @@ static void plan_tile(ConvPlan &p, int kernel, const char *base, TileArgs t, con
     p.t = t;
     plan_kernel(p, kernel, "%s<%d, %d, %d, %d%s>", base, t.BM, t.BN, t.WM, t.WN, tail);
 }
+// the strided-output twin of a planned kernel (sf_conv_fwd_relu_mask_os / sf_conv_fwd_t_os): "k_name<...>" -> "k_name_os<...>"
+static void plan_os_name(ConvPlan &p) {
+    char tmp[64];
+    const char *lt = strchr(p.name, '<');
+    if (!lt) return;
+    snprintf(tmp, sizeof(tmp), "%.*s_os%s", (int)(lt - p.name), p.name, lt);
+    memcpy(p.name, tmp, sizeof(tmp));
+}
 // 1-D launch whose block ids are re-mapped so that every XCD owns a contiguous run of tiles (sf_nn_glds.h)
 static void plan_raster(ConvPlan &p, bool on) {
     p.rx = (int)p.grid.x; p.ry = (int)p.grid.y;
@@ -1167,7 +1213,7 @@ extern "C" int sf_conv_relu_mask_supported(int64_t n, const sf_conv_desc *h_desc
 static int conv_fwd_impl(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *w,
                          const float *bias, float *out, uint32_t *relu_mask, int64_t n, const sf_conv_desc *h_desc,
                          void *workspace, int64_t workspace_bytes, void *stream, const float *mu = nullptr,
-                         const float *rstd = nullptr) {
+                         const float *rstd = nullptr, bool os = false, int64_t out_ss = 0, int64_t mask_ss = 0) {
     int rc = check_desc(h_desc, "sf_conv_fwd");
     if (rc) return rc;
     SF_REQUIRE(in && w && out && n > 0, "sf_conv_fwd: bad args");
@@ -1185,6 +1231,8 @@ static int conv_fwd_impl(const void *in, int64_t in_sample_stride, const int32_t
     SF_REQUIRE(relu_mask == nullptr || bf16,
                "sf_conv_fwd_relu_mask: operands not eligible for the sign-bit kernel (sf_conv_relu_mask_supported, 4-byte "
                "aligned frames and sample stride, 16-byte aligned weights)");
+    SF_REQUIRE(!os || p.kernel == K_CONV1_U8_BF16_W,
+               "sf_conv_fwd_relu_mask_os: not a launch of the whole-line-store conv1 kernel (sf_conv_fwd_os_supported)");
     if (bf16 && sw().debug_occ) {
         const unsigned img_bytes = 2u * 4u * 20u * (unsigned)SF_CONV1_WP * (unsigned)sizeof(uint16_t);
         fprintf(stderr, "k_conv1_u8_bf16 occupancy: %d (dword stores, %u B LDS) / %d (whole-line stores, %u B LDS) work-groups per CU\n",
@@ -1197,6 +1245,11 @@ static int conv_fwd_impl(const void *in, int64_t in_sample_stride, const int32_t
     KERN<<<p.grid, p.block, p.lds, st>>>(g, in8, in_sample_stride, index, offset, w, bias, out, ##__VA_ARGS__, (int)n)
     switch (p.kernel) {
         case K_CONV1_U8_BF16_W:
+            if (os) {
+                if (p.variant) k_conv1_u8_bf16_w_os<true><<<p.grid, p.block, p.lds, st>>>(g, in8, in_sample_stride, index, offset, w, bias, out, relu_mask, (int)n, out_ss, mask_ss);
+                else k_conv1_u8_bf16_w_os<false><<<p.grid, p.block, p.lds, st>>>(g, in8, in_sample_stride, index, offset, w, bias, out, relu_mask, (int)n, out_ss, mask_ss);
+                break;
+            }
             if (p.variant) CONV1_LAUNCH(k_conv1_u8_bf16_w<true>, relu_mask); else CONV1_LAUNCH(k_conv1_u8_bf16_w<false>, relu_mask);
             break;
         case K_CONV1_U8_BF16:
@@ -1231,6 +1284,26 @@ extern "C" int sf_conv_fwd_relu_mask(const void *in, int64_t in_sample_stride, c
     return conv_fwd_impl(in, in_sample_stride, index, offset, w, bias, out, relu_mask, n, h_desc, nullptr, 0, stream);
 }
 
+// ---- forwards with an OUTPUT sample stride (floats; the sign-bit words: mask_sample_stride u32 words): sample s, pixel p goes
+// to out + s * out_sample_stride + p * Cout.  A rollout step writes slot t of a buffer laid out [E, T, OH * OW, Cout] this way;
+// the next layer reads it through its input stride, and rows [e * T + t] of that buffer are the dense activation of dataset
+// rows e * T + t.  Only the launches whose dense kernel has a strided twin are accepted (sf_conv_fwd_os_supported).
+static bool out_stride_ok(const sf_conv_desc *d, const void *out, int64_t out_ss) {
+    return out_ss >= (int64_t)d->OH * d->OW * d->Cout && out_ss < (1LL << 30) && out_ss % 4 == 0 && aligned(out, 16);
+}
+extern "C" int sf_conv_fwd_relu_mask_os(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
+                                        const float *w, const float *bias, float *out, int64_t out_sample_stride,
+                                        uint32_t *relu_mask, int64_t mask_sample_stride, int64_t n, const sf_conv_desc *h_desc,
+                                        void *stream) {
+    SF_REQUIRE(relu_mask && ((uintptr_t)relu_mask & 3) == 0, "sf_conv_fwd_relu_mask_os: relu_mask must be a 4-byte aligned device buffer");
+    SF_REQUIRE(h_desc && n > 0 && relu_mask_ok(h_desc, n) && ((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0,
+               "sf_conv_fwd_relu_mask_os: unsupported layer / launch (see sf_conv_relu_mask_supported)");
+    SF_REQUIRE(out_stride_ok(h_desc, out, out_sample_stride) && mask_sample_stride >= (int64_t)h_desc->OH * h_desc->OW,
+               "sf_conv_fwd_relu_mask_os: output / mask sample stride shorter than a sample, or unaligned output");
+    return conv_fwd_impl(in, in_sample_stride, index, offset, w, bias, out, relu_mask, n, h_desc, nullptr, 0, stream, nullptr,
+                         nullptr, true, out_sample_stride, mask_sample_stride);
+}
+
 // ---- LDS-image forward (sf_nn_img.h): compile-time geometries (Cin, H, W, K, S, fragments per step, wave sets, output
 // rows per unit).  Nature-CNN conv3 (64 x 9 x 9, 3x3 stride 1, whole images): two independent persistent work-groups
 // per CU, +5 % (n = 32768) / +8 % (n = 4096) over k_fwd_glds.  conv2 (32 x 20 x 20, 4x4 stride 2) was measured in two
@@ -1243,8 +1316,8 @@ extern "C" int sf_conv_fwd_relu_mask(const void *in, int64_t in_sample_stride, c
 #endif
 #define IMG_FWD_GEOMS(X) X(64, 9, 9, 3, 1, SF_IMG_TMF, 1, 7)
 // index into IMG_FWD_GEOMS (-1: none); fills the plan's grid (persistent: as many work-groups as fit on the chip at once)
-static int plan_img_fwd(ConvPlan &p, const ConvG &g, int64_t n) {
-    if (!sw().fwd_img || g.Cout != 64 || g.KH != g.KW || n < 512) return -1;
+static int plan_img_fwd(ConvPlan &p, const ConvG &g, int64_t n, bool any_n = false) {
+    if (!sw().fwd_img || g.Cout != 64 || g.KH != g.KW || (n < 512 && !any_n)) return -1;
     int idx = 0;
 #define X(CIN, HH, WW, KS, ST, TMF, WS, R)                                                                         \
     if (g.Cin == CIN && g.H == HH && g.W == WW && g.KH == KS && g.S == ST) {                                       \
@@ -1369,7 +1442,12 @@ static int fwd_tail_split(const ConvG &g, int64_t Mtot, int Z, bool zl_ok) {
 // SF_GLDS_TALL=<min 256-row tiles> (experiment): 256 x 64 tiles (waves 4 x 1, 64 x 64 wave tiles) for 64-column layers with
 // many rows — half the per-tile fixed cost and a sixth less DMA per flop, at two work-groups per CU instead of three.
 // SF_GLDS_PERSIST=1 (experiment): persistent row-tile walk (k_fwd_glds_zp).
-static ConvPlan plan_conv_fwd_t(const sf_conv_desc *d, int64_t n, int64_t in_sample_stride, ConvG *g_out = nullptr) {
+// os: the plan of sf_conv_fwd_t_os — the twin of k_fwd_img (its geometries) or of k_fwd_glds_zt (one column tile, unsplit) at
+// ANY n: the size thresholds of the dense dispatch are speed heuristics, the kernels are correct for every n, and whether a
+// strided launch may stand in for a dense one is the caller's comparison of the two names.  The twins take their lane
+// offsets from the tile's first sample, so only a TILE's span of the input has to fit 32 bits.  K_NONE: no twin.
+static ConvPlan plan_conv_fwd_t(const sf_conv_desc *d, int64_t n, int64_t in_sample_stride, ConvG *g_out = nullptr,
+                                bool os = false) {
     ConvPlan p = plan_init();
     if (narrow_fwd_ok(d, n)) {
         p.recommended = true; p.variant = d->Cout <= 16 ? 1 : 2;
@@ -1381,16 +1459,32 @@ static ConvPlan plan_conv_fwd_t(const sf_conv_desc *d, int64_t n, int64_t in_sam
     const ConvG g = make_geom(d);
     if (g_out) *g_out = g;
     const int64_t Mtot = n * g.OH * g.OW;
-    if (n * in_sample_stride < ((int64_t)1 << 40) && plan_img_fwd(p, g, n) >= 0) { p.recommended = true; return p; }
+    if (n * in_sample_stride < ((int64_t)1 << 40) && plan_img_fwd(p, g, n, os) >= 0) {
+        p.recommended = true;
+        if (os) plan_os_name(p);
+        return p;
+    }
     // small grids keep the split-K register-staged kernel (a 128-row tile grid must fill 256 CUs a few times over)
     GldsFwdPlan q = plan_fwd_t(Mtot, g.Cout, g.K);
     p.recommended = q.ok;
     if (!q.ok) { q.Z = 1; q.k_per_split = (g.K + 31) / 32 * 32; }  // not a grid sf_conv_fwd_t_supported recommends: still correct, one unsplit launch
     p.splits = q.Z; p.per_split = q.k_per_split;
     // zero-VALU k-loop form (k_fwd_glds_z): every per-lane operand offset must fit 32 bits
-    const bool zl_ok = sw().glds_zl && (n - 1) * in_sample_stride + (int64_t)g.H * g.W * g.Cin < (1LL << 30) &&
+    const int64_t lane_span = os ? 127 / (g.OH * g.OW) + 1 : n - 1;  // samples between a lane's row and the DMA base
+    const bool zl_ok = sw().glds_zl && lane_span * in_sample_stride + (int64_t)g.H * g.W * g.Cin < (1LL << 30) &&
                        (int64_t)g.Cout * g.K < (1LL << 30);
     const bool col64 = !q.sq64 && !q.wide && q.Z == 1 && g.Cout <= 64 && zl_ok;
+    if (os) {
+        p.splits = 1; p.per_split = (g.K + 31) / 32 * 32;
+        p.main_tiles = g.K % 32 == 0 && g.OH * g.OW >= 4 ? fwd_tail_split(g, Mtot, 1, zl_ok) : 0;  // (>= 4 pixels: store_fwd_tile_os)
+        if (p.main_tiles <= 0) return plan_init();
+        const int tail = (int)cdiv64(Mtot, 128) - p.main_tiles;
+        p.grid = dim3((unsigned)(p.main_tiles + 2 * tail));
+        p.lds = (128 + 64) * 32 * 2 * sizeof(float);
+        plan_tile(p, K_FWD_GLDS_ZT, "k_fwd_glds_zt", TileArgs{128, 64, 2, 2});
+        plan_os_name(p);
+        return p;
+    }
     if (sw().glds_persist && col64) {
         static const int occp = occupancy_of(k_fwd_glds_zp<128, 64, 2, 2>);
         const int64_t tiles = cdiv64(Mtot, 128), slots = (int64_t)num_cus() * occp;
@@ -1493,6 +1587,54 @@ extern "C" int sf_conv_fwd_t(const float *in, int64_t in_sample_stride, const fl
     return sf_launch_status("sf_conv_fwd_t");
 }
 // two linear layers into one accumulator (k_fwd_glds2): out = a1 w1t^T + a2 w2t^T + bias1 + bias2
+// sf_conv_fwd_t with an output sample stride: the launches that resolve to k_fwd_glds_zt (conv2) or k_fwd_img (conv3)
+extern "C" int sf_conv_fwd_t_os(const float *in, int64_t in_sample_stride, const float *wt, const float *bias, float *out,
+                                int64_t out_sample_stride, int64_t n, const sf_conv_desc *h_desc, void *stream) {
+    int rc = check_desc(h_desc, "sf_conv_fwd_t_os");
+    if (rc) return rc;
+    SF_REQUIRE(in && wt && out && n > 0, "sf_conv_fwd_t_os: bad args");
+    SF_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)wt & 15) == 0 && in_sample_stride % 4 == 0,
+               "sf_conv_fwd_t_os: operands must be 16-byte aligned");
+    SF_REQUIRE(out_stride_ok(h_desc, out, out_sample_stride),
+               "sf_conv_fwd_t_os: output sample stride shorter than a sample, or unaligned output");
+    ConvG g;
+    const ConvPlan p = plan_conv_fwd_t(h_desc, n, in_sample_stride, &g, true);
+    SF_REQUIRE((p.kernel == K_FWD_IMG || p.kernel == K_FWD_GLDS_ZT) && p.splits == 1,
+               "sf_conv_fwd_t_os: this launch has no strided-output kernel (sf_conv_fwd_os_supported)");
+    const int64_t Mtot = n * g.OH * g.OW;
+    SF_REQUIRE(Mtot < (1LL << 31), "sf_conv_fwd_t_os: M=%lld exceeds 2^31 rows; split the batch", (long long)Mtot);
+    hipStream_t st = STREAM(stream);
+    if (p.kernel == K_FWD_IMG) {
+        int idx = 0;
+#define X(CIN, HH, WW, KS, ST, TMF, WS, R)                                                                              \
+    if (p.variant == idx++)                                                                                             \
+        k_fwd_img_os<CIN, HH, WW, KS, ST, TMF, WS, R><<<p.grid, p.block, 0, st>>>(in, in_sample_stride, wt, bias, out, (int)n, \
+                                                                                  g.relu, out_sample_stride);
+        IMG_FWD_GEOMS(X)
+#undef X
+    } else {
+        k_fwd_glds_zt_os<128, 64, 2, 2><<<p.grid, p.block, p.lds, st>>>(g, in, in_sample_stride, wt, bias, out, Mtot, (int)p.per_split,
+                                                                         p.main_tiles, sw().tap_perm, out_sample_stride);
+    }
+    return sf_launch_status("sf_conv_fwd_t_os");
+}
+// op: 0 sf_conv_fwd_relu_mask_os, 3 sf_conv_fwd_t_os (the numbers of their dense entry points in sf_conv_kernel_name)
+extern "C" int sf_conv_fwd_os_supported(int op, int64_t n, const sf_conv_desc *h_desc, int64_t in_sample_stride,
+                                        int64_t out_sample_stride) {
+    if (!h_desc || n <= 0 || check_desc(h_desc, "sf_conv_fwd_os_supported") != 0 || in_sample_stride % 4 != 0 ||
+        !out_stride_ok(h_desc, nullptr, out_sample_stride) || n * (int64_t)h_desc->OH * h_desc->OW >= (1LL << 31))
+        return 0;
+    if (op == 0) {
+        if (!relu_mask_ok(h_desc, n)) return 0;
+        Operands o = query_operands(h_desc, false);
+        o.stride = in_sample_stride;
+        return plan_conv_fwd(h_desc, make_geom(h_desc), n, o).kernel == K_CONV1_U8_BF16_W ? 1 : 0;
+    }
+    if (op != 3) return 0;
+    const ConvPlan p = plan_conv_fwd_t(h_desc, n, in_sample_stride, nullptr, true);
+    return (p.kernel == K_FWD_IMG || p.kernel == K_FWD_GLDS_ZT) && p.splits == 1 ? 1 : 0;
+}
+
 extern "C" int sf_linear_fwd_dual_supported(int64_t n, int N, int K1, int K2) {
     return sw().linear_dual && n > 0 && N >= 64 && K1 > 0 && K2 > 0 && K1 % 32 == 0 && K2 % 32 == 0 && n < (1LL << 31) &&
            cdiv64(n, 128) * (int64_t)cdiv64(N, 64) >= 256;
@@ -2005,19 +2147,26 @@ extern "C" int sf_debug_conv1_trace(unsigned long long *host_out12) {
 // Name of the kernel instantiation a launch with these arguments resolves to, spelled the way rocprofv3 prints it, so that
 // bench.py can group its HIP-event timings exactly like the rocprof kernel stats: the name of the plan the launcher itself
 // would run for query_operands() (aligned operands and tables, dense samples, no index; a split-K workspace if allowed).
-// op: 0 sf_conv_fwd, 1 sf_conv_wgrad, 2 sf_conv_dgrad, 3 sf_conv_fwd_t, 4 sf_conv_fwd_norm, 5 sf_conv_wgrad_norm
+// op: 0 sf_conv_fwd, 1 sf_conv_wgrad, 2 sf_conv_dgrad, 3 sf_conv_fwd_t, 4 sf_conv_fwd_norm, 5 sf_conv_wgrad_norm,
+// 6 sf_conv_fwd_relu_mask_os, 7 sf_conv_fwd_t_os (the strided-output twins)
 extern "C" int sf_conv_kernel_name(int op, int64_t n, const sf_conv_desc *h_desc, int split_k_allowed, char *out,
                                    int cap) {
     int rc = check_desc(h_desc, "sf_conv_kernel_name");
     if (rc) return rc;
-    SF_REQUIRE(out && cap >= 48 && n > 0 && op >= 0 && op <= 5, "sf_conv_kernel_name: bad args");
+    SF_REQUIRE(out && cap >= 48 && n > 0 && op >= 0 && op <= 7, "sf_conv_kernel_name: bad args");
     const Operands o = query_operands(h_desc, split_k_allowed != 0);
     ConvG g = make_geom(h_desc);
-    if (op >= 4) g.nmu = g.nrstd = TABLE_PROBE;
-    const ConvPlan p = op == 3 ? plan_conv_fwd_t(h_desc, n, o.stride) : op == 2 ? plan_conv_dgrad(g, n, o)
-                       : (op == 0 || op == 4) ? plan_conv_fwd(h_desc, g, n, o) : plan_conv_wgrad(h_desc, g, n, o);
+    if (op == 4 || op == 5) g.nmu = g.nrstd = TABLE_PROBE;
+    ConvPlan p = op == 3 ? plan_conv_fwd_t(h_desc, n, o.stride) : op == 2 ? plan_conv_dgrad(g, n, o)
+                 : op == 7 ? plan_conv_fwd_t(h_desc, n, o.stride, nullptr, true)
+                 : (op == 0 || op == 4 || op == 6) ? plan_conv_fwd(h_desc, g, n, o) : plan_conv_wgrad(h_desc, g, n, o);
+    if (op == 6) {
+        if (p.kernel == K_CONV1_U8_BF16_W && relu_mask_ok(h_desc, n)) plan_os_name(p);
+        else p.kernel = K_NONE;
+    }
+    if (op == 7 && (p.kernel == K_LINEAR_NARROW || p.splits != 1)) p.kernel = K_NONE;
     SF_REQUIRE(p.kernel != K_NONE, "sf_conv_kernel_name: not a launch %s accepts",
-               op >= 4 ? "sf_conv_norm_supported" : "sf_conv_fwd_t");
+               op >= 6 ? "sf_conv_fwd_os_supported" : op >= 4 ? "sf_conv_norm_supported" : "sf_conv_fwd_t");
     strncpy(out, p.name, (size_t)cap - 1);
     out[cap - 1] = 0;
     return SF_OK;

@@ -305,12 +305,18 @@ __device__ __forceinline__ void mma_chunk_stage(const float *const (&ap)[4], con
 // every per-lane operand offset < 4 GiB (the launcher checks).
 // DYNLDS: the pipeline stages live in the launch's dynamic LDS (k_fwd_glds_zt runs two instantiations in one kernel: two
 // static arrays would both be allocated); bx_shift: added to the row-tile index (the 64-row tail tiles of that kernel)
-template <int BM, int BN, int WM, int WN, int NS, bool ZL, bool PERSIST = false, bool DYNLDS = false>
+// OS (k_fwd_glds_zt_os: forward with bias and activation only): output sample s starts out_ss floats behind sample s - 1 — row
+// m goes to out + (m / OHOW) * out_ss + (m % OHOW) * N (a rollout step writing its slot of a kept [E, T, OHOW, N] buffer) — and
+// the per-lane DMA offsets of the ZL form are taken from the TILE's first sample instead of from `in`, so that an input
+// with the same kind of sample stride (several GB from end to end) keeps 32-bit lane offsets.  Same products, same order.
+template <int BM, int BN, int WM, int WN, int NS, bool ZL, bool PERSIST = false, bool DYNLDS = false, bool OS = false>
 __device__ __forceinline__ void fwd_glds_body(ConvG g, const float *__restrict__ in, int64_t in_stride,
                                               const float *__restrict__ wt, const float *__restrict__ bias,
                                               float *__restrict__ out, int64_t Mtot, int k_per_split,
                                               float *__restrict__ partial, const float *__restrict__ dmask,
-                                              int dmask_on, int rx, int ry, int rtot, int tap_perm, int bx_shift = 0) {
+                                              int dmask_on, int rx, int ry, int rtot, int tap_perm, int bx_shift = 0,
+                                              int64_t out_ss = 0) {
+    static_assert(!OS || (ZL && !PERSIST), "the strided output form exists for the zero-VALU forward only");
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     constexpr int AI = BM / 32, BI = BN / 32;  // DMA instructions per wave and chunk (8 rows x 128 B each)
     constexpr int STAGE = (BM + BN) * 32;      // floats per pipeline stage
@@ -424,8 +430,10 @@ __device__ __forceinline__ void fwd_glds_body(ConvG g, const float *__restrict__
 
         // ---- per-lane 32-bit byte offsets of the DMA sources (relative to `in` / `wt`), LDS fragment pointers of stage 0
         uint32_t avoff[AI], bvoff[BI];
+        const float *inb = in;  // uniform base of the activation DMA
+        if constexpr (OS) inb = in + (int64_t)fdiv((uint32_t)(m0 < Mtot ? m0 : Mtot - 1), g.dOHOW) * in_stride;
 #pragma unroll
-        for (int i = 0; i < AI; ++i) avoff[i] = (uint32_t)((asrc[i] - in) * (int64_t)sizeof(float));
+        for (int i = 0; i < AI; ++i) avoff[i] = (uint32_t)((asrc[i] - inb) * (int64_t)sizeof(float));
 #pragma unroll
         for (int i = 0; i < BI; ++i) bvoff[i] = (uint32_t)((bsrc[i] - wt) * (int64_t)sizeof(float));
         const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float *)lds;
@@ -448,7 +456,7 @@ __device__ __forceinline__ void fwd_glds_body(ConvG g, const float *__restrict__
         };
         {
             const int kf = kord(kbeg);
-            const float *ab = in + chunk_off(kf), *bb = wt + kf;
+            const float *ab = inb + chunk_off(kf), *bb = wt + kf;
 #pragma unroll
             for (int q = 0; q < AI + BI; ++q) dma(q, ab, bb, 0);
         }
@@ -457,7 +465,7 @@ __device__ __forceinline__ void fwd_glds_body(ConvG g, const float *__restrict__
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             BARRIER_NOFENCE();
             const int kn = prefetch ? kord(k0 + 32) : 0;
-            const float *ab = in + chunk_off(kn), *bb = wt + kn;
+            const float *ab = inb + chunk_off(kn), *bb = wt + kn;
             if (!prefetch) prefetch_mask();  // (last chunk of the tile)
             if constexpr (TM * TN <= 2) {  // DMA instructions spread over the first three MFMA groups
                 mma_chunk_ptrs_mid<TM, TN, ST * STAGE>(apl, bpl, acc, [&](int c) {
@@ -556,6 +564,12 @@ __device__ __forceinline__ void fwd_glds_body(ConvG g, const float *__restrict__
     const int cols_left = N - (n0 + wn * TN * 32) - (lane & 31);
     const uint32_t voff = (uint32_t)(4 * (lane >> 5)) * (uint32_t)N + (uint32_t)(lane & 31);
     const bool full = m0 + BM <= Mtot && n0 + BN <= N;
+    if constexpr (OS) {
+        const int64_t mrow0 = m0 + wm * TM * 32 + 4 * (lane >> 5);
+        const int col = n0 + wn * TN * 32 + (lane & 31);
+        if (g.relu == 1) store_fwd_tile_os<TM, TN, 1>(acc, out, mrow0, Mtot, g, out_ss, col, bias, 1);
+        else store_fwd_tile_os<TM, TN, -1>(acc, out, mrow0, Mtot, g, out_ss, col, bias, g.relu);
+    } else
     if (dmask_on) {  // data gradient of a linear layer (sf_conv_dgrad): out = acc * act'(dmask), no bias
         const float *mk = dmask ? dmask + (m0 + wm * TM * 32) * N + (n0 + wn * TN * 32) : nullptr;
         if (!dmask) {
@@ -624,6 +638,19 @@ __global__ __launch_bounds__(256, 2) void k_fwd_glds_zt(ConvG g, const float *__
     else
         fwd_glds_body<BM / 2, BN, WM, WN, 2, true, false, true>(g, in, in_stride, wt, bias, out, Mtot, k_per_split, nullptr,
                                                                 nullptr, 0, 0, 0, 0, tap_perm, main_tiles);
+}
+// ... with an output sample stride (fwd_glds_body, OS)
+template <int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(256, 2) void k_fwd_glds_zt_os(ConvG g, const float *__restrict__ in, int64_t in_stride,
+                                                          const float *__restrict__ wt, const float *__restrict__ bias,
+                                                          float *__restrict__ out, int64_t Mtot, int k_per_split,
+                                                          int main_tiles, int tap_perm, int64_t out_ss) {
+    if ((int)blockIdx.x < main_tiles)
+        fwd_glds_body<BM, BN, WM, WN, 2, true, false, true, true>(g, in, in_stride, wt, bias, out, Mtot, k_per_split, nullptr,
+                                                                  nullptr, 0, 0, 0, 0, tap_perm, 0, out_ss);
+    else
+        fwd_glds_body<BM / 2, BN, WM, WN, 2, true, false, true, true>(g, in, in_stride, wt, bias, out, Mtot, k_per_split, nullptr,
+                                                                      nullptr, 0, 0, 0, 0, tap_perm, main_tiles, out_ss);
 }
 // the same kernel with the zero-VALU k-loop (see fwd_glds_body, ZL)
 template <int BM, int BN, int WM, int WN>

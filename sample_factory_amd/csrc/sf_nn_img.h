@@ -57,10 +57,12 @@ struct ImgFwdGeom {
     static_assert(RING * IMG_B <= 160 * 1024, "LDS");
 };
 
-template <int CIN, int H, int W, int KS, int ST, int TMF, int WSETS, int R>
-__global__ __launch_bounds__(256 * WSETS, 1) void k_fwd_img(const float *__restrict__ in, int64_t in_stride,
-                                                    const float *__restrict__ wt, const float *__restrict__ bias,
-                                                    float *__restrict__ out, int nsamples, int act) {
+// OS (k_fwd_img_os, whole-image units only): output sample s starts out_ss floats behind sample s - 1 — row m goes to
+// out + (m / OHW) * out_ss + (m % OHW) * 64 (a rollout step writing its slot of a kept [E, T, OHW, 64] buffer).
+template <int CIN, int H, int W, int KS, int ST, int TMF, int WSETS, int R, bool OS>
+__device__ __forceinline__ void fwd_img_body(const float *__restrict__ in, int64_t in_stride,
+                                             const float *__restrict__ wt, const float *__restrict__ bias,
+                                             float *__restrict__ out, int nsamples, int act, int64_t out_ss) {
     typedef ImgFwdGeom<CIN, H, W, KS, ST, TMF, WSETS, R> G;
     constexpr int NW = 4 * WSETS, TB = TMF * WSETS;  // waves per block, fragments per block step
     constexpr int OW = G::OW, OHW = G::OHW, K = G::K, KG = G::KG, WQ = G::WQ, PLANE = G::PLANE, RING = G::RING;
@@ -128,6 +130,21 @@ __global__ __launch_bounds__(256 * WSETS, 1) void k_fwd_img(const float *__restr
     f32x4 pend[TMF];
     int pend_fb = -1, pend_nf = 0;
     auto store_pend = [&]() {
+        if constexpr (OS) {
+            static_assert(!OS || G::U == 1, "strided output: one unit per sample");
+            const uint32_t mb = (uint32_t)pend_fb * 16u + 4u * (uint32_t)kg;
+#pragma unroll
+            for (int f = 0; f < TMF; ++f) {
+                const uint32_t m = mb + (uint32_t)f * 16u, s = m / (uint32_t)OHW, p = m - s * (uint32_t)OHW;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const uint32_t wrap = p + (uint32_t)r >= (uint32_t)OHW ? 1u : 0u;  // (OHW >= 4: at most one sample boundary)
+                    float *o = out + (int64_t)(s + wrap) * out_ss + (int64_t)(p + (uint32_t)r - wrap * (uint32_t)OHW) * N + n;
+                    if (f < pend_nf && m + (uint32_t)r < M32) *o = pend[f][r];
+                }
+            }
+            return;
+        }
         float *ob = out + ((int64_t)pend_fb * 16 + 4 * kg) * N + n;
         const int rows_left = (int)(M32 - ((uint32_t)pend_fb * 16u + 4u * (uint32_t)kg));
 #pragma unroll
@@ -218,4 +235,17 @@ __global__ __launch_bounds__(256 * WSETS, 1) void k_fwd_img(const float *__restr
         pend_nf = nf;
     }
     if (pend_fb >= 0) store_pend();
+}
+
+template <int CIN, int H, int W, int KS, int ST, int TMF, int WSETS, int R>
+__global__ __launch_bounds__(256 * WSETS, 1) void k_fwd_img(const float *__restrict__ in, int64_t in_stride,
+                                                    const float *__restrict__ wt, const float *__restrict__ bias,
+                                                    float *__restrict__ out, int nsamples, int act) {
+    fwd_img_body<CIN, H, W, KS, ST, TMF, WSETS, R, false>(in, in_stride, wt, bias, out, nsamples, act, 0);
+}
+template <int CIN, int H, int W, int KS, int ST, int TMF, int WSETS, int R>
+__global__ __launch_bounds__(256 * WSETS, 1) void k_fwd_img_os(const float *__restrict__ in, int64_t in_stride,
+                                                       const float *__restrict__ wt, const float *__restrict__ bias,
+                                                       float *__restrict__ out, int nsamples, int act, int64_t out_ss) {
+    fwd_img_body<CIN, H, W, KS, ST, TMF, WSETS, R, true>(in, in_stride, wt, bias, out, nsamples, act, out_ss);
 }

@@ -71,12 +71,16 @@ __device__ __forceinline__ void split3_bf16(float w, uint32_t &hi, uint32_t &mid
 // 16 bytes back in output order and stores them with global_store_dwordx4: a wave instruction is 1 KB of contiguous
 // output.  No extra barrier: the next strip's staging writes come after its leading barrier.  The ReLU sign bits are
 // taken there too (4 channels per lane, OR over the 8 lanes of a pixel by DPP): one u32 store per pixel.
-template <bool SUB, int NCT, bool WIDE>
+// OS (WIDE only, k_conv1_u8_bf16_w_os): sample s of the output starts out_ss floats, its sign-bit words mask_ss words, behind
+// sample s - 1 (a rollout step writing slot t of a kept [E, T, 400, 32] buffer); the dense form is out_ss = 400 * 32,
+// mask_ss = 400.  Same products, same order, same stores per sample.
+template <bool SUB, int NCT, bool WIDE, bool OS = false>
 __device__ __forceinline__ void conv1_u8_bf16_body(ConvG g, const uint8_t *__restrict__ in, int64_t in_stride,
                                                    const int32_t *__restrict__ index, int64_t offset,
                                                    const float *__restrict__ w, const float *__restrict__ bias,
                                                    float *__restrict__ out, uint32_t *__restrict__ mask_out,
-                                                   int nsamples) {
+                                                   int nsamples, int64_t out_ss = 0, int64_t mask_ss = 0) {
+    static_assert(!OS || WIDE, "the strided output form exists for the whole-line store path only");
     constexpr int SMP = 2 * NCT, R = 4, TMF = 5, KB = 8;
     constexpr int H = 84, W = 84, WP = SF_CONV1_WP, Cin = 4, KH = 8, S = 4, OH = 20, OW = 20, OHOW = OH * OW;
     constexpr int RS = (R - 1) * S + KH;  // 20 input rows per strip
@@ -282,14 +286,22 @@ __device__ __forceinline__ void conv1_u8_bf16_body(ConvG g, const uint8_t *__res
                 const float4 v = *reinterpret_cast<const float4 *>(stg + (z * (R * OW) + px) * SP + ch * 4);
                 const bool sok = s0 + z < nsamples;
                 const int64_t pix0 = (int64_t)(s0 + z) * OHOW + st * (R * OW);
-                if (sok) *reinterpret_cast<float4 *>(out + pix0 * 32 + qq * 4) = v;
+                if constexpr (OS) {
+                    if (sok) *reinterpret_cast<float4 *>(out + (int64_t)(s0 + z) * out_ss + st * (R * OW) * 32 + qq * 4) = v;
+                } else {
+                    if (sok) *reinterpret_cast<float4 *>(out + pix0 * 32 + qq * 4) = v;
+                }
                 if (g.relu == 1 && mask_out) {  // (uniform) sign bits of the pixel: 4 per lane, OR over its 8 lanes
                     int nib = (v.x > 0.f ? 1 : 0) | (v.y > 0.f ? 2 : 0) | (v.z > 0.f ? 4 : 0) | (v.w > 0.f ? 8 : 0);
                     nib <<= 4 * ch;
                     nib |= __builtin_amdgcn_update_dpp(0, nib, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
                     nib |= __builtin_amdgcn_update_dpp(0, nib, 0x4E /* quad_perm [2,3,0,1] */, 0xF, 0xF, true);
                     nib |= __builtin_amdgcn_update_dpp(0, nib, 0x141 /* row_half_mirror */, 0xF, 0xF, true);
-                    if (ch == 0 && sok) mask_out[pix0 + px] = (uint32_t)nib;
+                    if constexpr (OS) {
+                        if (ch == 0 && sok) mask_out[(int64_t)(s0 + z) * mask_ss + st * (R * OW) + px] = (uint32_t)nib;
+                    } else {
+                        if (ch == 0 && sok) mask_out[pix0 + px] = (uint32_t)nib;
+                    }
                 }
             }
             SF_C1T(6);  // staged tile -> global
@@ -320,6 +332,14 @@ void k_conv1_u8_bf16_w(ConvG g, const uint8_t *__restrict__ in, int64_t in_strid
                        int64_t offset, const float *__restrict__ w, const float *__restrict__ bias,
                        float *__restrict__ out, uint32_t *__restrict__ mask_out, int nsamples) {
     conv1_u8_bf16_body<SUB, 1, true>(g, in, in_stride, index, offset, w, bias, out, mask_out, nsamples);
+}
+template <bool SUB>
+__global__ __launch_bounds__(256, 2)
+void k_conv1_u8_bf16_w_os(ConvG g, const uint8_t *__restrict__ in, int64_t in_stride, const int32_t *__restrict__ index,
+                          int64_t offset, const float *__restrict__ w, const float *__restrict__ bias,
+                          float *__restrict__ out, uint32_t *__restrict__ mask_out, int nsamples, int64_t out_ss,
+                          int64_t mask_ss) {
+    conv1_u8_bf16_body<SUB, 1, true, true>(g, in, in_stride, index, offset, w, bias, out, mask_out, nsamples, out_ss, mask_ss);
 }
 
 // ============================================================================================== WEIGHT GRADIENT, raw u8 frames

@@ -54,6 +54,7 @@ SYMBOLS = [
     "sf_sample_write_step_tuple", "sf_sample_write_step_masked", "sf_traj_write_env_step", "sf_synth_obs",
     "sf_synth_step", "sf_synth_vec_step", "sf_h2d_rows", "sf_copy_rows", "sf_conv_fwd", "sf_conv_fwd_workspace", "sf_conv_wgrad_workspace", "sf_conv_wgrad",
     "sf_conv_dgrad", "sf_conv_norm_supported", "sf_conv_fwd_norm", "sf_conv_wgrad_norm", "sf_conv_relu_mask_supported", "sf_conv_fwd_relu_mask", "sf_conv_wgrad_relu_mask", "sf_conv_kernel_name", "sf_conv_fwd_t_supported", "sf_conv_fwd_t_workspace", "sf_conv_fwd_t", "sf_transpose",
+    "sf_conv_fwd_os_supported", "sf_conv_fwd_relu_mask_os", "sf_conv_fwd_t_os",
     "sf_tanh_scale_fwd", "sf_tanh_scale_bwd",
     "sf_linear_fwd", "sf_linear_wgrad_workspace", "sf_linear_wgrad", "sf_linear_dgrad", "sf_relu_mask",
     "sf_dp_unique_id", "sf_dp_comm_create", "sf_dp_comm_destroy", "sf_dp_comm_info", "sf_allreduce_grads",
@@ -201,7 +202,7 @@ class _timed:
         return False
 
 
-_OPS = {"fwd": 0, "wgrad": 1, "dgrad": 2, "fwd_t": 3, "fwd_norm": 4, "wgrad_norm": 5}
+_OPS = {"fwd": 0, "wgrad": 1, "dgrad": 2, "fwd_t": 3, "fwd_norm": 4, "wgrad_norm": 5, "fwd_os": 6, "fwd_t_os": 7}
 _names: dict = {}
 
 
@@ -955,6 +956,32 @@ def conv_fwd_t(inp, in_sample_stride, wt, bias, out, n, desc: sf_conv_desc, work
                                     ptr(workspace, "u8", "workspace"),
                                     i64(workspace.numel() if workspace is not None else 0), stream()),
                "sf_conv_fwd_t")
+
+
+def conv_fwd_os_supported(op: str, n, desc: sf_conv_desc, in_sample_stride, out_sample_stride) -> bool:
+    """op: "fwd" (conv_fwd_relu_mask_os) | "fwd_t" (conv_fwd_t_os)"""
+    return bool(load().sf_conv_fwd_os_supported(_OPS[op], i64(n), C.byref(desc), i64(in_sample_stride),
+                                                i64(out_sample_stride)))
+
+
+def conv_fwd_relu_mask_os(inp, in_sample_stride, index, offset, w, bias, out, out_sample_stride, relu_mask,
+                          mask_sample_stride, n, desc: sf_conv_desc) -> None:
+    """conv_fwd_relu_mask writing sample s at out + s * out_sample_stride floats / relu_mask + s * mask_sample_stride words
+    (`out`, `relu_mask`: possibly strided views whose data_ptr is sample 0)"""
+    with _timed(_nkey("fwd", n, desc, "fwd_os")):
+        _check(load().sf_conv_fwd_relu_mask_os(_raw_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"),
+                                               i64(offset), ptr(w, "f32", "w"), ptr(bias, "f32", "bias"),
+                                               _raw(out, "f32", "out"), i64(out_sample_stride),
+                                               _raw(relu_mask, "i32", "relu_mask"), i64(mask_sample_stride), i64(n),
+                                               C.byref(desc), stream()), "sf_conv_fwd_relu_mask_os")
+
+
+def conv_fwd_t_os(inp, in_sample_stride, wt, bias, out, out_sample_stride, n, desc: sf_conv_desc) -> None:
+    """conv_fwd_t writing sample s at out + s * out_sample_stride floats (`out`: possibly strided view, data_ptr = sample 0)"""
+    with _timed(_nkey("fwd_t", n, desc, "fwd_t_os")):
+        _check(load().sf_conv_fwd_t_os(_raw_in(inp, desc), i64(in_sample_stride), ptr(wt, "f32", "wt"),
+                                       ptr(bias, "f32", "bias"), _raw(out, "f32", "out"), i64(out_sample_stride), i64(n),
+                                       C.byref(desc), stream()), "sf_conv_fwd_t_os")
 
 
 def tanh_scale_fwd(x, ld, n, col0, ncols, scale) -> None:

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from sample_factory_amd import lib
+from sample_factory_amd.algo.learning.rollout_reuse import SlotRecord, reuse_prefix, twin_name
 from sample_factory_amd.algo.utils.running_mean_std import RunningMeanStdInPlace
 from sample_factory_amd.envs.spaces import is_box, calc_num_action_parameters
 
@@ -37,6 +38,12 @@ import os
 _LSTM_SEQ = os.environ.get("SF_LSTM_SEQ", "1") != "0"  # A/B switch: 0 = per-step launches instead of the fused passes
 _CONV1_NORM = os.environ.get("SF_CONV1_NORM", "1") != "0"  # A/B switch: 0 = normalised f32 copy of the frames + f32 conv1
 _MLP2 = os.environ.get("SF_MLP2", "1") != "0"          # A/B switch: 0 = layer-by-layer encoder in the rollout as well
+_REUSE = os.environ.get("SF_REUSE_ROLLOUT_ACTS", "1") != "0"  # A/B switch: 0 = the first minibatch recomputes conv1..conv3
+# the kept activation buffers of cfg.reuse_rollout_activations=auto may take at most this share of the device memory that
+# is free when the runner is set up, AFTER the learner's own training-size buffers (activations, their gradients, the
+# first layer's sign bits: allocated lazily at the first train(), estimated here from the layer shapes) are taken off;
+# beyond it nothing is kept (logged once) and training runs the plain forward
+KEEP_MEM_SHARE = 0.5
 
 ACT_KIND = {"relu": 1, "tanh": 2, "elu": 3}  # model/model_utils.py:27-35; fused into the GEMM epilogues
 # first conv layers that read raw NCHW observation frames in place (weights k = (c*KH + kh)*KW + kw): u8 / f32 frames
@@ -391,6 +398,8 @@ class ActorCritic(NativeTower):
         self._ctx: Dict = {}
         self._rnn_out: Dict = {}   # tag -> [(h_out, c_out | None) per recurrent layer] of the last ONE-STEP forward under that tag
         self._rnn_saved_l: Dict = {}  # layer index -> what the last training pass of that recurrent layer left for its BPTT
+        self._keep: Optional[Dict] = None  # kept rollout activations (configure_keep), None: nothing is kept
+        self._keep_same: Dict = {}
         self.initialize_weights()
 
     def seat_flat(self, flat_params: torch.Tensor, flat_grads: torch.Tensor, flat_params_t: torch.Tensor) -> None:
@@ -403,6 +412,7 @@ class ActorCritic(NativeTower):
             flat_params.copy_(old)
             flat_params_t.copy_(self.flat_params_t)
         self.flat_params, self.flat_grads, self.flat_params_t = flat_params, flat_grads, flat_params_t
+        self.weights_gen = getattr(self, "weights_gen", 0) + 1
         self._layout_gen = getattr(self, "_layout_gen", 0) + 1
         for L, (o, ob) in zip(self.layers, self._segs):
             L.w = flat_params[o:o + L.K * L.N].view(L.K, L.N)
@@ -491,6 +501,7 @@ class ActorCritic(NativeTower):
         return sd
 
     def load_state_dict(self, sd, strict=True):
+        self.weights_gen += 1
         with torch.no_grad():
             for L in self._body():
                 L.w.copy_(L.w_from_ref(torch.as_tensor(sd[L.wname], dtype=torch.float32)))
@@ -586,6 +597,7 @@ class ActorCritic(NativeTower):
 
     def params_changed(self) -> None:
         """call after ANY write to flat_params (optimiser step, load_state_dict, broadcast): refresh derived copies"""
+        self.weights_gen += 1  # activations kept by a rollout before this point no longer belong to these weights
         for L in self.layers:
             if L.wt is not None:
                 lib.transpose(L.w, L.wt, L.K, L.N)
@@ -607,6 +619,7 @@ class ActorCritic(NativeTower):
         self._snap_tabs = [(on.mu_tab.clone(), on.rstd_tab.clone()) for _ in range(2)] if on is not None else None
 
     def publish_weights(self, slot: int) -> None:
+        self.weights_gen += 1
         self._snap[slot].copy_(self.flat_params)
         self._snap_t[slot].copy_(self.flat_params_t)
         if self._snap_tabs is not None:
@@ -634,8 +647,11 @@ class ActorCritic(NativeTower):
         lib.conv_fwd_raw(x, stride, index, offset, w, b, out, n, d, self._workspace(wsb) if wsb else None)
 
     def forward_heads(self, obs: torch.Tensor, n: int, *, sample_stride: int, index=None, offset: int = 0,
-                      traj_T: int = 0, tag="inf", rnn=None) -> List[torch.Tensor]:
+                      traj_T: int = 0, tag="inf", rnn=None, keep=None, resume_from=None) -> List[torch.Tensor]:
         """Run the whole stack on `n` samples; returns the list of layer outputs (last = heads [n, heads_ld]).
+        keep=(t, row0) (rollout tags, after configure_keep): the leading conv layers write slot t of rows [row0, row0 + n) of
+        the kept buffers.  resume_from (tag "train"): what kept_resume returned — those layers are not run, the forward
+        continues behind them.
 
         obs: any (possibly strided) view whose data_ptr is sample 0; logical sample i lives at row
         (index[i] | offset+i) [-> slab row if traj_T] * sample_stride elements.
@@ -686,8 +702,33 @@ class ActorCritic(NativeTower):
                 x, stride, idx, off, tT = xn, self.obs_elems, None, 0, 0
         first_in = (x, stride, idx, off, tT)
         seq = rnn is not None and "R" in rnn
+        kp = self._keep if keep is not None else None
+        if kp is not None:
+            assert tag.startswith("inf") and first_layer == 0 and norm_tabs is None and idx is None and not tT
+            assert n == kp["n_roll"] and stride == kp["obs_stride"] and keep[1] + n <= kp["rows"] and self._snap is None
+        if resume_from is not None:  # the first minibatch behind the rollout: conv layers [0, prefix) were kept, bit for bit
+            assert tag == "train" and first_layer == 0 and norm_tabs is None
+            first_layer = resume_from["prefix"]
+            for li in range(first_layer):
+                inputs[li] = x if li == 0 else acts[li - 1]
+                acts[li] = resume_from["acts"][li]
+            relu_mask0 = resume_from["mask"]
+            x, stride, idx, off, tT = acts[first_layer - 1], acts[first_layer - 1].numel() // n, None, 0, 0
         for li, L in enumerate(self.layers):
             if L.role == "rnn_hh" or li < first_layer:
+                continue
+            if kp is not None and li < kp["prefix"]:
+                t_, r0 = keep
+                kb = self._bufs[("keep", li)]  # [rows, T, pixels * channels]: this launch writes slot t_ of its rows
+                out, w_b = kb[r0:r0 + n, t_], self._wb(li, tag)
+                if li == 0:
+                    mk = self._bufs[("keep", "relu_mask0")]
+                    lib.conv_fwd_relu_mask_os(x, stride, None, 0, w_b[0], w_b[1], out, kb.stride(0), mk[r0:r0 + n, t_],
+                                              mk.stride(0), n, L.desc)
+                else:
+                    lib.conv_fwd_t_os(x, stride, w_b[2], w_b[1], out, kb.stride(0), n, L.desc)
+                inputs[li], acts[li], x = x, out, out
+                stride, idx, off, tT = kb.stride(0), None, 0, 0
                 continue
             if L.role == "rnn_ih" and seq:  # BPTT pass: the recurrent block works time-major ([R, C, .])
                 R, Cn = rnn["R"], n // rnn["R"]
@@ -749,6 +790,114 @@ class ActorCritic(NativeTower):
         self._ctx[tag] = dict(acts=acts, inputs=inputs, first_in=first_in, rnn=rnn, relu_mask0=relu_mask0,
                               norm_tabs=norm_tabs)
         return acts
+
+    # ------------------------------------------------------------------------------------------ kept rollout activations
+    # (the decision itself: algo/learning/rollout_reuse.py)
+    def _keep_rollout_ok(self, li, n, in_stride, out_stride) -> bool:
+        """layer li's rollout launch has a strided-output twin of the kernel the dense launch of that size runs"""
+        L = self.layers[li]
+        d = L.desc
+        if li == 0:
+            if L.kind != "conv_u8" or d.relu != 1 or self.layers[1].role != "chain":
+                return False
+            if not lib.conv_relu_mask_supported(n, d) or not lib.conv_fwd_os_supported("fwd", n, d, in_stride, out_stride):
+                return False
+            return lib.conv_kernel_name(6, n, d) == twin_name(lib.conv_kernel_name(0, n, d))
+        if L.kind != "conv" or L.wt is None or not lib.conv_fwd_t_supported(n, d) or lib.conv_fwd_t_workspace(n, d):
+            return False
+        if not lib.conv_fwd_os_supported("fwd_t", n, d, in_stride, out_stride):
+            return False
+        return lib.conv_kernel_name(7, n, d) == twin_name(lib.conv_kernel_name(3, n, d))
+
+    def _keep_same_kernel(self, li, n_roll, n_train) -> bool:
+        """layer li's training launch runs the kernel of its rollout launch, unsplit: the kept bytes are the bytes it would write"""
+        key = (li, n_roll, n_train)
+        ok = self._keep_same.get(key)
+        if ok is None:
+            d, op = self.layers[li].desc, 0 if li == 0 else 3
+            ok = lib.conv_kernel_name(op, n_roll, d) == lib.conv_kernel_name(op, n_train, d)
+            if li == 0:
+                ok = ok and lib.conv_relu_mask_supported(n_train, d)
+            else:
+                ok = ok and lib.conv_fwd_t_supported(n_train, d) and not lib.conv_fwd_t_workspace(n_train, d)
+            self._keep_same[key] = bool(ok)
+        return self._keep_same[key]
+
+    def configure_keep(self, rows: int, T: int, n_roll: int, obs_stride: int) -> int:
+        """Set up (or switch off) the kept activation buffers for rollouts of `n_roll` samples per launch into `rows`
+        trajectories of length T whose frames are obs_stride elements apart; returns the number of leading conv layers kept.
+        cfg.reuse_rollout_activations: "auto" keeps them where the learner's guard can ever hold and the buffers fit,
+        "off" never."""
+        self._keep, cfg = None, self.cfg
+        if str(getattr(cfg, "reuse_rollout_activations", "auto")) != "auto" or not _REUSE:
+            return 0
+        # the learner's dataset must be exactly ONE sampling round: with k rounds per dataset every round overwrites the same
+        # kept rows and minibatch 0 comes from the first one — the guard could never hold, the strided launches and the
+        # buffers would be pure cost
+        if int(cfg.batch_size) * int(cfg.num_batches_per_epoch) != int(rows) * int(T) or int(cfg.batch_size) % int(T):
+            return 0
+        if (self.part != "full" or self.obs_normalizer is not None or self.rnn_kind is not None or self._snap is not None or
+                getattr(cfg, "async_rl", False) or getattr(cfg, "shuffle_minibatches", False) or len(self.obs_shape) != 3):
+            return 0
+        nconv = sum(1 for L in self.layers if L.kind in FRAME_KINDS or L.kind == "conv")
+        prefix, in_stride = 0, int(obs_stride)
+        for li in range(min(3, nconv, len(self.layers) - 1)):
+            L = self.layers[li]
+            if not self._keep_rollout_ok(li, n_roll, in_stride, T * L.out_pixels * L.N):
+                break
+            prefix, in_stride = prefix + 1, T * L.out_pixels * L.N
+        if prefix == 0:
+            return 0
+        need = sum(rows * T * self.layers[li].out_pixels * (self.layers[li].N + (1 if li == 0 else 0)) * 4 for li in range(prefix))
+        free = torch.cuda.mem_get_info(self.device)[0] + sum(t.numel() * t.element_size() for k, t in self._bufs.items()
+                                                             if isinstance(k, tuple) and k and k[0] == "keep")
+        if ("train", 0) not in self._bufs:  # the training-size buffers do not exist yet: an activation and a gradient per layer
+            free -= 2 * 4 * int(cfg.batch_size) * sum(L.out_pixels * L.N for L in self.layers if L.role != "rnn_hh")
+        if need > KEEP_MEM_SHARE * free:
+            if not getattr(self, "_keep_refused", False):
+                self._keep_refused = True
+                print(f"reuse_rollout_activations: {need / 2**30:.1f} GiB of kept activations exceed {KEEP_MEM_SHARE:.0%} of "
+                      f"the {free / 2**30:.1f} GiB of free device memory; the first minibatch recomputes them", flush=True)
+            return 0
+        for li in range(prefix):
+            L = self.layers[li]
+            self._buf(("keep", li), (rows, T, L.out_pixels * L.N))
+        self._buf(("keep", "relu_mask0"), (rows, T, self.layers[0].out_pixels), dtype=torch.int32)
+        self._keep = dict(rows=int(rows), T=int(T), prefix=prefix, n_roll=int(n_roll), obs_stride=int(obs_stride), records={})
+        return prefix
+
+    def keep_note(self, t: int, row0: int, n: int, obs_ptr: int) -> None:
+        """a rollout step (run plainly or replayed from its launch program) has written slot t of kept rows [row0, row0 + n)
+        from the frames starting at obs_ptr, with the weights as they are now"""
+        if self._keep is not None:
+            self._keep["records"][(int(row0), int(t))] = SlotRecord(int(row0), int(row0) + int(n), int(t), self.weights_gen,
+                                                                   int(obs_ptr))
+
+    def kept_resume(self, obs, index, offset: int, n: int, T: int, epoch: int, batch_num: int):
+        """(resume_from for forward_heads | None, reason): the kept activations of dataset rows [offset, offset + n) of `obs`
+        (the slab's [E, T + 1, ...] frames) if the guard of algo/learning/rollout_reuse.py holds for this minibatch"""
+        kp = self._keep
+        if kp is None:
+            return None, "nothing is kept"
+        if not isinstance(obs, torch.Tensor) or obs.dim() < 2 or obs.data_ptr() % 4:
+            return None, "frames not in one aligned slab array"
+        es = obs.element_size()
+        layer_ok = [self._keep_same_kernel(li, kp["n_roll"], n) for li in range(kp["prefix"])]
+        prefix, why = reuse_prefix(epoch=epoch, batch_num=batch_num, indexed=index is not None, offset=int(offset), n=int(n),
+                                   T=int(T), keep_T=kp["T"], keep_rows=kp["rows"], records=kp["records"],
+                                   generation=self.weights_gen, obs_ptr=obs.data_ptr(), obs_row_bytes=obs.stride(0) * es,
+                                   obs_step_bytes=obs.stride(1) * es, has_normalizer=self.obs_normalizer is not None,
+                                   has_rnn=self.rnn_kind is not None, async_rl=bool(getattr(self.cfg, "async_rl", False)),
+                                   snapshot_reads=self._snap is not None, layer_ok=layer_ok)
+        if prefix == 0:
+            return None, why
+        acts = []
+        for li in range(prefix):
+            L = self.layers[li]
+            acts.append(self._bufs[("keep", li)].view(-1, L.out_pixels * L.N)[offset:offset + n].view(n * L.out_pixels, L.N))
+        P0 = self.layers[0].out_pixels
+        mask = self._bufs[("keep", "relu_mask0")].view(-1)[offset * P0:(offset + n) * P0]
+        return dict(prefix=prefix, acts=acts, mask=mask), why
 
     # ------------------------------------------------------------------------------------------ recurrent core
     def _rnn_step(self, li, gx, n, rnn, tag, x_in=None, x_stride=0):

@@ -285,6 +285,12 @@ class Runner:
                                                 tag="inf" if e == 0 else f"inf{e}")
                          for e, env in enumerate(self.envs)]
         self.sampler = self.samplers[0]
+        # synchronous mode: the rollout keeps its conv activations for the learner's first minibatch
+        ac = self.learner.actor_critic
+        if not cfg.async_rl and hasattr(ac, "configure_keep") and not self.sampler.multi_key:
+            kept = ac.configure_keep(self.num_rows, int(cfg.rollout), n, self.sampler.obs.stride(0))
+            for e, sm in enumerate(self.samplers):
+                sm.keep_on, sm.keep_row0 = kept > 0, e * n
         self._prev_rows: List = [None] * E          # slab view each env instance wrote its previous rollout into
         S = max(1, min(int(cfg.worker_num_splits), E))
         # SF_ROLLOUT_PRIORITY=1 (async mode): sampling streams on the HIGH hardware-queue priority.  Off by default: over

@@ -56,6 +56,28 @@ def main():
                     t = timeit(lambda: lib.conv_fwd_t(x, stride, wt, b, out, n, d, wst), reps)
                     err = (out - ref).abs().max().item() / ref.abs().max().item()
                     res.append(f"fwd_t {t*1e3:8.1f}us {flops/t/1e9:6.1f}TF relerr {err:.1e}" + (f" #{digest(out)}" if HASH else ""))
+            if "fwd_os" in which and name in ("conv1", "conv2", "conv3"):
+                # the rollout-size launch into slot t of a kept [n, T, pixels * channels] buffer (t walks the slots), reading its
+                # input from such a buffer as well (conv2, conv3), against the dense launch of the same kernel; KBENCH_T slots
+                T = int(os.environ.get("KBENCH_T", "32"))
+                L_out, L_in = d.OH*d.OW*d.Cout, d.H*d.W*d.Cin
+                kept = torch.empty((n, T, L_out), device="cuda"); step = [0]
+                if d.in_u8:
+                    mk = torch.empty((n, T, d.OH*d.OW), dtype=torch.int32, device="cuda"); mkd = torch.empty((M,), dtype=torch.int32, device="cuda")
+                    def strided():
+                        t_ = step[0] % T; step[0] += 1
+                        lib.conv_fwd_relu_mask_os(x, stride, None, 0, w, b, kept[:, t_], T*L_out, mk[:, t_], T*d.OH*d.OW, n, d)
+                    dense = lambda: lib.conv_fwd_relu_mask(x, stride, None, 0, w, b, out, mkd, n, d)
+                else:
+                    wt = torch.empty((d.Cout, K), device="cuda"); lib.transpose(w, wt, K, d.Cout)
+                    xin = torch.randn((n, T, L_in), device="cuda")
+                    def strided():
+                        t_ = step[0] % T; step[0] += 1
+                        lib.conv_fwd_t_os(xin[:, t_], T*L_in, wt, b, kept[:, t_], T*L_out, n, d)
+                    dense = lambda: lib.conv_fwd_t(x, stride, wt, b, out, n, d)
+                for rnd in range(2):
+                    td, ts = timeit(dense, reps), timeit(strided, max(reps, T))
+                    res.append(f"dense {td*1e3:8.1f}us strided(T={T}) {ts*1e3:8.1f}us")
             if "wgrad" in which and n in grads_at:
                 dw = torch.empty_like(w); db = torch.empty_like(b)
                 ws = torch.empty(lib.conv_wgrad_workspace(n, d),dtype=torch.uint8,device="cuda")
