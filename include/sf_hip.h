@@ -640,10 +640,31 @@ int sf_conv_fwd_relu_mask_os(const void *in, int64_t in_sample_stride, const int
                              void *stream);
 int sf_conv_fwd_t_os(const float *in, int64_t in_sample_stride, const float *wt, const float *bias, float *out,
                      int64_t out_sample_stride, int64_t n, const sf_conv_desc *desc, void *stream);
+/* ... in TWO SEGMENTS of samples: a rollout launch of n trajectories of which only the first keep_n belong to the learner's
+ * first minibatch (0 <= keep_n <= n).  Samples s < keep_n are read and written exactly as above (in / in_sample_stride, out /
+ * out_sample_stride, relu_mask / mask_sample_stride).  Samples s >= keep_n are read from in2 + (s - keep_n) * H*W*Cin and written
+ * to out2 + (s - keep_n) * OH*OW*Cout, both dense (the ordinary activation buffer), and their sign-bit words are not stored.
+ * in2 / out2 16-byte aligned; the pointers of an empty segment are not looked at.  Same kernels (the entry points above are
+ * their keep_n = n case), same bytes as the dense entry point in both segments: k_conv1_u8_bf16_w_os and k_fwd_img_os select
+ * the bases per sample, k_fwd_glds_zt_os cuts its row tiles per segment and runs the dense segment's tiles through the body
+ * of k_fwd_glds_zt.  The frames of sf_conv_fwd_relu_mask_os2 have one segment.  sf_conv_fwd_t_os2 also takes a linear layer
+ * (H = W = 1: the fc layer behind conv3, whose input then has the two segments): k_fwd_glds_z_os<64, 64, 2, 2>, the unsplit
+ * 64 x 64 form of k_fwd_glds_z with the same tile cut, at any n; out_sample_stride is then the row pitch of the first segment
+ * (Cout for one dense output, with out2 = out + keep_n * Cout).  sf_conv_kernel_name op 7 names it. */
+int sf_conv_fwd_os2_supported(int op, int64_t n, int64_t keep_n, const sf_conv_desc *desc, int64_t in_sample_stride,
+                              int64_t out_sample_stride);
+int sf_conv_fwd_relu_mask_os2(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
+                              const float *w, const float *bias, float *out, int64_t out_sample_stride,
+                              uint32_t *relu_mask, int64_t mask_sample_stride, float *out2, int64_t keep_n, int64_t n,
+                              const sf_conv_desc *h_desc, void *stream);
+int sf_conv_fwd_t_os2(const float *in, int64_t in_sample_stride, const float *in2, const float *wt, const float *bias,
+                      float *out, int64_t out_sample_stride, float *out2, int64_t keep_n, int64_t n,
+                      const sf_conv_desc *desc, void *stream);
 
 /* Profiling aid (no reference counterpart): the kernel instantiation a conv/linear launch resolves to, spelled as
  * rocprofv3 prints it ("k_conv_fwd<128, 64, 2, 2, 0>").  op: 0 forward, 1 wgrad, 2 dgrad, 3 sf_conv_fwd_t,
- * 4 sf_conv_fwd_norm, 5 sf_conv_wgrad_norm, 6 sf_conv_fwd_relu_mask_os, 7 sf_conv_fwd_t_os. */
+ * 4 sf_conv_fwd_norm, 5 sf_conv_wgrad_norm, 6 sf_conv_fwd_relu_mask_os, 7 sf_conv_fwd_t_os
+ * (also the names of the two-segment entry points _os2; for a linear layer op 7 names k_fwd_glds_z_os). */
 int sf_conv_kernel_name(int op, int64_t n, const sf_conv_desc *desc, int split_k_allowed, char *out, int cap);
 /* dense layer: out[M,N] = act(in[M,K] * w[K,N] + bias); wgrad: dw[K,N] = in^T dout, db = colsum(dout);
  * dgrad: din[M,K] = (dout[M,N] * w^T) * relu_mask(in_act). */

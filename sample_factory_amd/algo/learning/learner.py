@@ -164,7 +164,7 @@ class Learner:
         self.dp = self.group is not None and self.group.on  # collectives are issued (world > 1, or forced for tests)
         self._grad_norms: List[float] = []
         # first-minibatch forwards that resumed behind the rollout's kept conv activations / that ran the whole stack
-        self.reuse_stats = dict(reused=0, plain=0, last_prefix=0, last_reason="")
+        self.reuse_stats = dict(reused=0, plain=0, last_prefix=0, last_reason="", fc_reused=0)
 
     # ------------------------------------------------------------------------------------------ init / checkpoints
     def _all_reduce(self, t: torch.Tensor) -> None:
@@ -524,6 +524,7 @@ class Learner:
             st = self.reuse_stats
             st["reused" if resume is not None else "plain"] += 1
             st["last_prefix"], st["last_reason"] = (resume["prefix"] if resume is not None else 0), why
+            st["fc_reused"] += 1 if resume is not None and resume.get("fc") is not None else 0  # (the fc layer too)
             if resume is not None:
                 kw["resume_from"] = resume
         acts = ac.forward_heads(buff.obs, n, sample_stride=ac.obs_elems, index=index, offset=offset,

@@ -3,8 +3,8 @@
 In synchronous mode the rollout runs conv1 -> conv2 -> conv3 on obs[:, t] with the learner's own weights, and the first
 minibatch of the first epoch — dataset rows [0, batch_size) when minibatches are not shuffled — runs the same layers on the
 same frames with the same weights before the first optimiser step.  The rollout therefore writes those activations into
-kept buffers laid out [E, T, pixels, channels] (row e * T + t = dataset row e * T + t) and the training forward resumes
-behind them.  Everything here is host bookkeeping; nothing in this module touches the device.
+kept buffers laid out [keep_rows, T, pixels, channels] (row e * T + t = dataset row e * T + t; keep_rows = the trajectories
+of minibatch 0, the others are written densely as without reuse) and the training forward resumes behind them.  Everything here is host bookkeeping; nothing in this module touches the device.
 """
 from __future__ import annotations
 
@@ -20,9 +20,38 @@ class SlotRecord(NamedTuple):
     obs_ptr: int      # address of the frame of kept row `row0` at step t (the slab row the step read)
 
 
+def keep_rows(batch_size: int, T: int, rows: int) -> int:
+    """trajectories whose activations are kept: the whole trajectories of minibatch 0 = dataset rows [0, batch_size), at most
+    the `rows` trajectories there are.  Nothing beyond them is ever read back, so nothing beyond them is kept."""
+    if T <= 0 or batch_size <= 0 or rows <= 0:
+        return 0
+    return min(int(batch_size) // int(T), int(rows))
+
+
+def keep_n(kept_rows: int, row0: int, n: int) -> int:
+    """of a rollout launch over trajectories [row0, row0 + n): how many of its leading samples belong to the kept rows
+    [0, kept_rows) — the split point of the two-segment forward (0: the launch keeps nothing and runs the plain forward)"""
+    return max(0, min(int(n), int(kept_rows) - int(row0)))
+
+
 def twin_name(dense: str) -> str:
     """name of the strided-output twin of a dense kernel instantiation: k_x<...> -> k_x_os<...>"""
     return dense.replace("<", "_os<", 1)
+
+
+# tile forms of fwd_glds_body whose unsplit launches were shown to give the same bytes (tests/test_gpu_fwd_two_segment.py::
+# test_fc_tile_shapes_give_the_same_bytes): one accumulator chain per output element, k in ascending 32-deep chunks
+FC_SAME_BYTES_FORMS = ("k_fwd_glds_z<64, 64, 2, 2>", "k_fwd_glds_z<128, 128, 2, 2>")
+
+
+def fc_reusable(name_roll: str, name_train: str, workspace_roll: int, workspace_train: int) -> bool:
+    """may the fc output the rollout computed stand in for the training launch's?  The conv layers ask for the SAME kernel;
+    the fc layer runs 64 x 64 tiles at the rollout size and 128 x 128 tiles at the training size, so for it the rule is: both
+    launches are k_fwd_glds_z instantiations whose bytes were shown to agree, and neither is split along K (a split launch
+    adds partial sums in another order; it is the launch that asks for a workspace)."""
+    if workspace_roll or workspace_train:
+        return False
+    return name_roll in FC_SAME_BYTES_FORMS and name_train in FC_SAME_BYTES_FORMS
 
 
 def reuse_prefix(*, epoch: int, batch_num: int, indexed: bool, offset: int, n: int, T: int, keep_T: int, keep_rows: int,

@@ -1213,7 +1213,8 @@ extern "C" int sf_conv_relu_mask_supported(int64_t n, const sf_conv_desc *h_desc
 static int conv_fwd_impl(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *w,
                          const float *bias, float *out, uint32_t *relu_mask, int64_t n, const sf_conv_desc *h_desc,
                          void *workspace, int64_t workspace_bytes, void *stream, const float *mu = nullptr,
-                         const float *rstd = nullptr, bool os = false, int64_t out_ss = 0, int64_t mask_ss = 0) {
+                         const float *rstd = nullptr, bool os = false, int64_t out_ss = 0, int64_t mask_ss = 0,
+                         float *out2 = nullptr, int64_t keep_n = -1) {
     int rc = check_desc(h_desc, "sf_conv_fwd");
     if (rc) return rc;
     SF_REQUIRE(in && w && out && n > 0, "sf_conv_fwd: bad args");
@@ -1246,8 +1247,9 @@ static int conv_fwd_impl(const void *in, int64_t in_sample_stride, const int32_t
     switch (p.kernel) {
         case K_CONV1_U8_BF16_W:
             if (os) {
-                if (p.variant) k_conv1_u8_bf16_w_os<true><<<p.grid, p.block, p.lds, st>>>(g, in8, in_sample_stride, index, offset, w, bias, out, relu_mask, (int)n, out_ss, mask_ss);
-                else k_conv1_u8_bf16_w_os<false><<<p.grid, p.block, p.lds, st>>>(g, in8, in_sample_stride, index, offset, w, bias, out, relu_mask, (int)n, out_ss, mask_ss);
+                const int kn = (int)(keep_n < 0 ? n : keep_n);  // samples of the strided segment (all of them: one segment)
+                if (p.variant) k_conv1_u8_bf16_w_os<true><<<p.grid, p.block, p.lds, st>>>(g, in8, in_sample_stride, index, offset, w, bias, out, relu_mask, (int)n, out_ss, mask_ss, out2, kn);
+                else k_conv1_u8_bf16_w_os<false><<<p.grid, p.block, p.lds, st>>>(g, in8, in_sample_stride, index, offset, w, bias, out, relu_mask, (int)n, out_ss, mask_ss, out2, kn);
                 break;
             }
             if (p.variant) CONV1_LAUNCH(k_conv1_u8_bf16_w<true>, relu_mask); else CONV1_LAUNCH(k_conv1_u8_bf16_w<false>, relu_mask);
@@ -1302,6 +1304,31 @@ extern "C" int sf_conv_fwd_relu_mask_os(const void *in, int64_t in_sample_stride
                "sf_conv_fwd_relu_mask_os: output / mask sample stride shorter than a sample, or unaligned output");
     return conv_fwd_impl(in, in_sample_stride, index, offset, w, bias, out, relu_mask, n, h_desc, nullptr, 0, stream, nullptr,
                          nullptr, true, out_sample_stride, mask_sample_stride);
+}
+// ---- ... in TWO SEGMENTS of samples (a rollout launch of which only the first keep_n trajectories belong to the learner's
+// first minibatch): samples s < keep_n are read and written as by the _os entry points (in / in_sample_stride, out /
+// out_sample_stride, relu_mask / mask_sample_stride); samples s >= keep_n are read from in2 + (s - keep_n) * H*W*Cin and written
+// to out2 + (s - keep_n) * OH*OW*Cout, both dense, and their sign-bit words are not stored.  0 <= keep_n <= n; the pointers of
+// an empty segment are not looked at.  The same kernels as the _os entry points, which are their keep_n = n case.
+static bool seg2_ok(const sf_conv_desc *d, const void *out, int64_t out_ss, const void *out2, int64_t keep_n, int64_t n) {
+    if (keep_n < 0 || keep_n > n) return false;
+    if (keep_n > 0 && !(out && out_stride_ok(d, out, out_ss))) return false;
+    if (keep_n == 0 && !(out_ss >= 0 && out_ss < (1LL << 30) && out_ss % 4 == 0)) return false;
+    return keep_n == n || (out2 && aligned(out2, 16));
+}
+extern "C" int sf_conv_fwd_relu_mask_os2(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
+                                         const float *w, const float *bias, float *out, int64_t out_sample_stride,
+                                         uint32_t *relu_mask, int64_t mask_sample_stride, float *out2, int64_t keep_n,
+                                         int64_t n, const sf_conv_desc *h_desc, void *stream) {
+    SF_REQUIRE(h_desc && n > 0 && relu_mask_ok(h_desc, n) && ((uintptr_t)in & 3) == 0 && in_sample_stride % 4 == 0,
+               "sf_conv_fwd_relu_mask_os2: unsupported layer / launch (see sf_conv_relu_mask_supported)");
+    SF_REQUIRE(seg2_ok(h_desc, out, out_sample_stride, out2, keep_n, n),
+               "sf_conv_fwd_relu_mask_os2: keep_n outside [0, n], output sample stride shorter than a sample, or unaligned output");
+    SF_REQUIRE(keep_n == 0 || (relu_mask && ((uintptr_t)relu_mask & 3) == 0 && mask_sample_stride >= (int64_t)h_desc->OH * h_desc->OW),
+               "sf_conv_fwd_relu_mask_os2: relu_mask must be a 4-byte aligned device buffer, its sample stride a sample long");
+    float *o1 = keep_n > 0 ? out : out2;  // (an empty first segment: any valid pointer, never written through)
+    return conv_fwd_impl(in, in_sample_stride, index, offset, w, bias, o1, keep_n > 0 ? relu_mask : nullptr, n, h_desc, nullptr, 0,
+                         stream, nullptr, nullptr, true, out_sample_stride, mask_sample_stride, out2, keep_n);
 }
 
 // ---- LDS-image forward (sf_nn_img.h): compile-time geometries (Cin, H, W, K, S, fragments per step, wave sets, output
@@ -1446,8 +1473,9 @@ static int fwd_tail_split(const ConvG &g, int64_t Mtot, int Z, bool zl_ok) {
 // ANY n: the size thresholds of the dense dispatch are speed heuristics, the kernels are correct for every n, and whether a
 // strided launch may stand in for a dense one is the caller's comparison of the two names.  The twins take their lane
 // offsets from the tile's first sample, so only a TILE's span of the input has to fit 32 bits.  K_NONE: no twin.
+// keep_n (os): samples of the strided segment, < 0 = all n; k_fwd_glds_zt_os cuts its row tiles per segment.
 static ConvPlan plan_conv_fwd_t(const sf_conv_desc *d, int64_t n, int64_t in_sample_stride, ConvG *g_out = nullptr,
-                                bool os = false) {
+                                bool os = false, int64_t keep_n = -1) {
     ConvPlan p = plan_init();
     if (narrow_fwd_ok(d, n)) {
         p.recommended = true; p.variant = d->Cout <= 16 ? 1 : 2;
@@ -1474,11 +1502,30 @@ static ConvPlan plan_conv_fwd_t(const sf_conv_desc *d, int64_t n, int64_t in_sam
     const bool zl_ok = sw().glds_zl && lane_span * in_sample_stride + (int64_t)g.H * g.W * g.Cin < (1LL << 30) &&
                        (int64_t)g.Cout * g.K < (1LL << 30);
     const bool col64 = !q.sq64 && !q.wide && q.Z == 1 && g.Cout <= 64 && zl_ok;
+    if (os && linear_1x1(d)) {
+        // a linear layer (the fc behind conv3, whose output has the two segments): the twin of the unsplit 64 x 64 launch, at
+        // any n like the conv twins (whether it may stand in for the dense launch of this n is the caller's comparison of the
+        // names and of the workspace); its row tiles are cut per segment, each segment's lane offsets are taken from its base
+        const int64_t nk = keep_n < 0 || keep_n > n ? n : keep_n;
+        const bool zl2 = sw().glds_zl && (nk == 0 || (nk - 1) * in_sample_stride + g.K < (1LL << 30)) &&
+                         (n - nk) * (int64_t)g.K < (1LL << 30) && (int64_t)g.Cout * g.K < (1LL << 30);
+        if (!zl2 || g.K % 32 != 0 || g.Cout < 64) return plan_init();
+        p.splits = 1; p.per_split = g.K;
+        p.grid = dim3((unsigned)(cdiv64(nk, 64) + cdiv64(n - nk, 64)), cdiv64(g.Cout, 64), 1);
+        plan_raster(p, sw().xcd_raster && p.grid.y > 1);
+        plan_tile(p, K_FWD_GLDS_Z, "k_fwd_glds_z", TileArgs{64, 64, 2, 2});
+        plan_os_name(p);
+        return p;
+    }
     if (os) {
         p.splits = 1; p.per_split = (g.K + 31) / 32 * 32;
-        p.main_tiles = g.K % 32 == 0 && g.OH * g.OW >= 4 ? fwd_tail_split(g, Mtot, 1, zl_ok) : 0;  // (>= 4 pixels: store_fwd_tile_os)
+        const int64_t Mkeep = (keep_n < 0 || keep_n > n ? n : keep_n) * g.OH * g.OW;
+        const int64_t tiles = cdiv64(Mkeep, 128) + cdiv64(Mtot - Mkeep, 128);  // (one more than the flat count where the split is inside a tile)
+        // the dense segment runs the body of k_fwd_glds_zt: its lane offsets are taken from in2, over the whole segment
+        const bool seg2_zl = Mkeep == Mtot || (n - Mkeep / (g.OH * g.OW)) * (int64_t)g.H * g.W * g.Cin < (1LL << 30);
+        p.main_tiles = g.K % 32 == 0 && g.OH * g.OW >= 4 && seg2_zl ? fwd_tail_split(g, tiles * 128, 1, zl_ok) : 0;  // (>= 4 pixels: store_fwd_tile_os)
         if (p.main_tiles <= 0) return plan_init();
-        const int tail = (int)cdiv64(Mtot, 128) - p.main_tiles;
+        const int tail = (int)tiles - p.main_tiles;
         p.grid = dim3((unsigned)(p.main_tiles + 2 * tail));
         p.lds = (128 + 64) * 32 * 2 * sizeof(float);
         plan_tile(p, K_FWD_GLDS_ZT, "k_fwd_glds_zt", TileArgs{128, 64, 2, 2});
@@ -1588,41 +1635,59 @@ extern "C" int sf_conv_fwd_t(const float *in, int64_t in_sample_stride, const fl
 }
 // two linear layers into one accumulator (k_fwd_glds2): out = a1 w1t^T + a2 w2t^T + bias1 + bias2
 // sf_conv_fwd_t with an output sample stride: the launches that resolve to k_fwd_glds_zt (conv2) or k_fwd_img (conv3)
-extern "C" int sf_conv_fwd_t_os(const float *in, int64_t in_sample_stride, const float *wt, const float *bias, float *out,
-                                int64_t out_sample_stride, int64_t n, const sf_conv_desc *h_desc, void *stream) {
-    int rc = check_desc(h_desc, "sf_conv_fwd_t_os");
+static int conv_fwd_t_os_impl(const char *who, const float *in, int64_t in_sample_stride, const float *in2, const float *wt,
+                              const float *bias, float *out, int64_t out_sample_stride, float *out2, int64_t keep_n, int64_t n,
+                              const sf_conv_desc *h_desc, void *stream) {
+    int rc = check_desc(h_desc, who);
     if (rc) return rc;
-    SF_REQUIRE(in && wt && out && n > 0, "sf_conv_fwd_t_os: bad args");
-    SF_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)wt & 15) == 0 && in_sample_stride % 4 == 0,
-               "sf_conv_fwd_t_os: operands must be 16-byte aligned");
-    SF_REQUIRE(out_stride_ok(h_desc, out, out_sample_stride),
-               "sf_conv_fwd_t_os: output sample stride shorter than a sample, or unaligned output");
+    SF_REQUIRE(wt && n > 0 && ((uintptr_t)wt & 15) == 0 && in_sample_stride % 4 == 0, "%s: bad args", who);
+    SF_REQUIRE(seg2_ok(h_desc, out, out_sample_stride, out2, keep_n, n),
+               "%s: keep_n outside [0, n], output sample stride shorter than a sample, or unaligned output", who);
+    SF_REQUIRE((keep_n == 0 || (in && ((uintptr_t)in & 15) == 0)) && (keep_n == n || (in2 && ((uintptr_t)in2 & 15) == 0)),
+               "%s: operands must be 16-byte aligned", who);
     ConvG g;
-    const ConvPlan p = plan_conv_fwd_t(h_desc, n, in_sample_stride, &g, true);
-    SF_REQUIRE((p.kernel == K_FWD_IMG || p.kernel == K_FWD_GLDS_ZT) && p.splits == 1,
-               "sf_conv_fwd_t_os: this launch has no strided-output kernel (sf_conv_fwd_os_supported)");
+    const ConvPlan p = plan_conv_fwd_t(h_desc, n, in_sample_stride, &g, true, keep_n);
+    SF_REQUIRE((p.kernel == K_FWD_IMG || p.kernel == K_FWD_GLDS_ZT || p.kernel == K_FWD_GLDS_Z) && p.splits == 1,
+               "%s: this launch has no strided-output kernel (sf_conv_fwd_os_supported)", who);
     const int64_t Mtot = n * g.OH * g.OW;
-    SF_REQUIRE(Mtot < (1LL << 31), "sf_conv_fwd_t_os: M=%lld exceeds 2^31 rows; split the batch", (long long)Mtot);
+    SF_REQUIRE(Mtot < (1LL << 31), "%s: M=%lld exceeds 2^31 rows; split the batch", who, (long long)Mtot);
     hipStream_t st = STREAM(stream);
     if (p.kernel == K_FWD_IMG) {
         int idx = 0;
 #define X(CIN, HH, WW, KS, ST, TMF, WS, R)                                                                              \
     if (p.variant == idx++)                                                                                             \
         k_fwd_img_os<CIN, HH, WW, KS, ST, TMF, WS, R><<<p.grid, p.block, 0, st>>>(in, in_sample_stride, wt, bias, out, (int)n, \
-                                                                                  g.relu, out_sample_stride);
+                                                                                  g.relu, out_sample_stride, in2, out2, (int)keep_n);
         IMG_FWD_GEOMS(X)
 #undef X
+    } else if (p.kernel == K_FWD_GLDS_Z) {
+        k_fwd_glds_z_os<64, 64, 2, 2><<<p.grid, p.block, 0, st>>>(g, in, in_sample_stride, wt, bias, out, Mtot, (int)p.per_split, p.rx,
+                                                                   p.ry, p.rtot, out_sample_stride, in2, out2, keep_n);
     } else {
         k_fwd_glds_zt_os<128, 64, 2, 2><<<p.grid, p.block, p.lds, st>>>(g, in, in_sample_stride, wt, bias, out, Mtot, (int)p.per_split,
-                                                                         p.main_tiles, sw().tap_perm, out_sample_stride);
+                                                                         p.main_tiles, sw().tap_perm, out_sample_stride, in2, out2,
+                                                                         keep_n * g.OH * g.OW);
     }
-    return sf_launch_status("sf_conv_fwd_t_os");
+    return sf_launch_status(who);
+}
+extern "C" int sf_conv_fwd_t_os(const float *in, int64_t in_sample_stride, const float *wt, const float *bias, float *out,
+                                int64_t out_sample_stride, int64_t n, const sf_conv_desc *h_desc, void *stream) {
+    SF_REQUIRE(in && out, "sf_conv_fwd_t_os: bad args");
+    return conv_fwd_t_os_impl("sf_conv_fwd_t_os", in, in_sample_stride, nullptr, wt, bias, out, out_sample_stride, nullptr, n, n,
+                              h_desc, stream);
+}
+extern "C" int sf_conv_fwd_t_os2(const float *in, int64_t in_sample_stride, const float *in2, const float *wt, const float *bias,
+                                 float *out, int64_t out_sample_stride, float *out2, int64_t keep_n, int64_t n,
+                                 const sf_conv_desc *h_desc, void *stream) {
+    return conv_fwd_t_os_impl("sf_conv_fwd_t_os2", in, in_sample_stride, in2, wt, bias, out, out_sample_stride, out2, keep_n, n,
+                              h_desc, stream);
 }
 // op: 0 sf_conv_fwd_relu_mask_os, 3 sf_conv_fwd_t_os (the numbers of their dense entry points in sf_conv_kernel_name)
-extern "C" int sf_conv_fwd_os_supported(int op, int64_t n, const sf_conv_desc *h_desc, int64_t in_sample_stride,
-                                        int64_t out_sample_stride) {
-    if (!h_desc || n <= 0 || check_desc(h_desc, "sf_conv_fwd_os_supported") != 0 || in_sample_stride % 4 != 0 ||
-        !out_stride_ok(h_desc, nullptr, out_sample_stride) || n * (int64_t)h_desc->OH * h_desc->OW >= (1LL << 31))
+static int conv_fwd_os_supported_impl(int op, int64_t n, int64_t keep_n, const sf_conv_desc *h_desc, int64_t in_sample_stride,
+                                      int64_t out_sample_stride) {
+    if (!h_desc || n <= 0 || keep_n < 0 || keep_n > n || check_desc(h_desc, "sf_conv_fwd_os_supported") != 0 ||
+        in_sample_stride % 4 != 0 || !out_stride_ok(h_desc, nullptr, out_sample_stride) ||
+        n * (int64_t)h_desc->OH * h_desc->OW >= (1LL << 31))
         return 0;
     if (op == 0) {
         if (!relu_mask_ok(h_desc, n)) return 0;
@@ -1631,8 +1696,17 @@ extern "C" int sf_conv_fwd_os_supported(int op, int64_t n, const sf_conv_desc *h
         return plan_conv_fwd(h_desc, make_geom(h_desc), n, o).kernel == K_CONV1_U8_BF16_W ? 1 : 0;
     }
     if (op != 3) return 0;
-    const ConvPlan p = plan_conv_fwd_t(h_desc, n, in_sample_stride, nullptr, true);
-    return (p.kernel == K_FWD_IMG || p.kernel == K_FWD_GLDS_ZT) && p.splits == 1 ? 1 : 0;
+    const ConvPlan p = plan_conv_fwd_t(h_desc, n, in_sample_stride, nullptr, true, keep_n);
+    return (p.kernel == K_FWD_IMG || p.kernel == K_FWD_GLDS_ZT || p.kernel == K_FWD_GLDS_Z) && p.splits == 1 ? 1 : 0;
+}
+extern "C" int sf_conv_fwd_os_supported(int op, int64_t n, const sf_conv_desc *h_desc, int64_t in_sample_stride,
+                                        int64_t out_sample_stride) {
+    return conv_fwd_os_supported_impl(op, n, n, h_desc, in_sample_stride, out_sample_stride);
+}
+// ... of the two-segment entry points with this split
+extern "C" int sf_conv_fwd_os2_supported(int op, int64_t n, int64_t keep_n, const sf_conv_desc *h_desc, int64_t in_sample_stride,
+                                         int64_t out_sample_stride) {
+    return conv_fwd_os_supported_impl(op, n, keep_n, h_desc, in_sample_stride, out_sample_stride);
 }
 
 extern "C" int sf_linear_fwd_dual_supported(int64_t n, int N, int K1, int K2) {
@@ -2148,7 +2222,8 @@ extern "C" int sf_debug_conv1_trace(unsigned long long *host_out12) {
 // bench.py can group its HIP-event timings exactly like the rocprof kernel stats: the name of the plan the launcher itself
 // would run for query_operands() (aligned operands and tables, dense samples, no index; a split-K workspace if allowed).
 // op: 0 sf_conv_fwd, 1 sf_conv_wgrad, 2 sf_conv_dgrad, 3 sf_conv_fwd_t, 4 sf_conv_fwd_norm, 5 sf_conv_wgrad_norm,
-// 6 sf_conv_fwd_relu_mask_os, 7 sf_conv_fwd_t_os (the strided-output twins)
+// 6 sf_conv_fwd_relu_mask_os, 7 sf_conv_fwd_t_os (the strided-output twins, the same for their two-segment entry points; a
+// linear layer under op 7: k_fwd_glds_z_os<64, 64, 2, 2>)
 extern "C" int sf_conv_kernel_name(int op, int64_t n, const sf_conv_desc *h_desc, int split_k_allowed, char *out,
                                    int cap) {
     int rc = check_desc(h_desc, "sf_conv_kernel_name");

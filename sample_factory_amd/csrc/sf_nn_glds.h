@@ -309,14 +309,20 @@ __device__ __forceinline__ void mma_chunk_stage(const float *const (&ap)[4], con
 // m goes to out + (m / OHOW) * out_ss + (m % OHOW) * N (a rollout step writing its slot of a kept [E, T, OHOW, N] buffer) — and
 // the per-lane DMA offsets of the ZL form are taken from the TILE's first sample instead of from `in`, so that an input
 // with the same kind of sample stride (several GB from end to end) keeps 32-bit lane offsets.  Same products, same order.
-template <int BM, int BN, int WM, int WN, int NS, bool ZL, bool PERSIST = false, bool DYNLDS = false, bool OS = false>
+// SEG (k_fwd_glds_z_os: a linear layer, one row per sample, forward with bias and activation only): two segments of rows with
+// the row tiles cut per segment.  Rows below Mkeep are read from in / in_stride and written at a row pitch of out_ss floats;
+// the rows from Mkeep on are read from in2 (dense, K floats a row) and written to out2 (dense), both counted from Mkeep.
+template <int BM, int BN, int WM, int WN, int NS, bool ZL, bool PERSIST = false, bool DYNLDS = false, bool OS = false,
+          bool SEG = false>
 __device__ __forceinline__ void fwd_glds_body(ConvG g, const float *__restrict__ in, int64_t in_stride,
                                               const float *__restrict__ wt, const float *__restrict__ bias,
                                               float *__restrict__ out, int64_t Mtot, int k_per_split,
                                               float *__restrict__ partial, const float *__restrict__ dmask,
                                               int dmask_on, int rx, int ry, int rtot, int tap_perm, int bx_shift = 0,
-                                              int64_t out_ss = 0) {
+                                              int64_t out_ss = 0, const float *__restrict__ in2 = nullptr,
+                                              float *__restrict__ out2 = nullptr, int64_t Mkeep = 0) {
     static_assert(!OS || (ZL && !PERSIST), "the strided output form exists for the zero-VALU forward only");
+    static_assert(!SEG || (ZL && !PERSIST && !OS), "the two-segment linear form exists for the zero-VALU forward only");
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     constexpr int AI = BM / 32, BI = BN / 32;  // DMA instructions per wave and chunk (8 rows x 128 B each)
     constexpr int STAGE = (BM + BN) * 32;      // floats per pipeline stage
@@ -341,6 +347,17 @@ __device__ __forceinline__ void fwd_glds_body(ConvG g, const float *__restrict__
         const int t = L / ry;
         bx = t % rx;
         bz = t / rx;
+    }
+    int ld = g.Cout;  // (SEG) row pitch of the output
+    if constexpr (SEG) {  // (uniform) the tile's segment: its operands, its rows
+        const int keep_tiles = (int)((Mkeep + BM - 1) / BM);
+        if (bx >= keep_tiles) {
+            bx -= keep_tiles;
+            in = in2; in_stride = (int64_t)g.H * g.W * g.Cin; out = out2; Mtot -= Mkeep;
+        } else {
+            Mtot = Mkeep; ld = (int)out_ss;
+        }
+        if ((int64_t)bx * BM >= Mtot) return;
     }
     const int64_t m0 = (int64_t)bx * BM;
     const int n0 = by * BN;
@@ -564,7 +581,17 @@ __device__ __forceinline__ void fwd_glds_body(ConvG g, const float *__restrict__
     const int cols_left = N - (n0 + wn * TN * 32) - (lane & 31);
     const uint32_t voff = (uint32_t)(4 * (lane >> 5)) * (uint32_t)N + (uint32_t)(lane & 31);
     const bool full = m0 + BM <= Mtot && n0 + BN <= N;
-    if constexpr (OS) {
+    if constexpr (SEG) {
+        float *os = out + (m0 + wm * TM * 32) * ld + (n0 + wn * TN * 32);
+        const uint32_t vo = (uint32_t)(4 * (lane >> 5)) * (uint32_t)ld + (uint32_t)(lane & 31);
+        const float *b0 = bias ? bias + n0 + wn * TN * 32 : nullptr;
+        if (g.relu == 1) {
+            if (full) store_fwd_tile<TM, TN, 1, true>(acc, os, vo, ld, rows_left, cols_left, b0, lane & 31, 1);
+            else store_fwd_tile<TM, TN, 1, false>(acc, os, vo, ld, rows_left, cols_left, b0, lane & 31, 1);
+        } else {
+            store_fwd_tile<TM, TN, -1, false>(acc, os, vo, ld, rows_left, cols_left, b0, lane & 31, g.relu);
+        }
+    } else if constexpr (OS) {
         const int64_t mrow0 = m0 + wm * TM * 32 + 4 * (lane >> 5);
         const int col = n0 + wn * TN * 32 + (lane & 31);
         if (g.relu == 1) store_fwd_tile_os<TM, TN, 1>(acc, out, mrow0, Mtot, g, out_ss, col, bias, 1);
@@ -639,18 +666,60 @@ __global__ __launch_bounds__(256, 2) void k_fwd_glds_zt(ConvG g, const float *__
         fwd_glds_body<BM / 2, BN, WM, WN, 2, true, false, true>(g, in, in_stride, wt, bias, out, Mtot, k_per_split, nullptr,
                                                                 nullptr, 0, 0, 0, 0, tap_perm, main_tiles);
 }
-// ... with an output sample stride (fwd_glds_body, OS)
+// ... with an output sample stride (fwd_glds_body, OS) and TWO SEGMENTS of samples.  Rows below Mkeep (= keep_n * OHOW, whole
+// samples) are read from in / in_stride and written to out / out_ss as above; the rows from Mkeep on are read from in2 and
+// written to out2, both dense and counted from Mkeep (sample s -> in2 + (s - keep_n) * H*W*Cin, row m -> out2 + (m - Mkeep) * N).
+// The row tiles are cut PER SEGMENT — the first tile of the dense segment starts at row Mkeep — so that no tile has rows of
+// both: the zero-VALU loop takes a tile's DMA sources as one uniform base plus 32-bit lane offsets, and two buffers an
+// arbitrary distance apart have no common base.  A work-group of the dense segment then runs the body of k_fwd_glds_zt itself
+// (OS = false: its lane offsets from in2, store_fwd_tile), one of the kept segment the strided body; an output element is one
+// accumulator chain over k whichever tile its row falls into, so the cut does not show in the results.  In 64-row units the
+// kept segment takes [0, 2 * ceil(Mkeep / BM)), the dense one follows; blocks below main_tiles run units (2b, 2b + 1) as one
+// BM-row tile, the others one unit each (the tail round of k_fwd_glds_zt), and a unit that starts behind its segment's end
+// (the second half of a ragged last tile) has nothing to do.  Mkeep = Mtot: the single-segment launch of before.
 template <int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256, 2) void k_fwd_glds_zt_os(ConvG g, const float *__restrict__ in, int64_t in_stride,
                                                           const float *__restrict__ wt, const float *__restrict__ bias,
                                                           float *__restrict__ out, int64_t Mtot, int k_per_split,
-                                                          int main_tiles, int tap_perm, int64_t out_ss) {
-    if ((int)blockIdx.x < main_tiles)
-        fwd_glds_body<BM, BN, WM, WN, 2, true, false, true, true>(g, in, in_stride, wt, bias, out, Mtot, k_per_split, nullptr,
-                                                                  nullptr, 0, 0, 0, 0, tap_perm, 0, out_ss);
-    else
-        fwd_glds_body<BM / 2, BN, WM, WN, 2, true, false, true, true>(g, in, in_stride, wt, bias, out, Mtot, k_per_split, nullptr,
-                                                                      nullptr, 0, 0, 0, 0, tap_perm, main_tiles, out_ss);
+                                                          int main_tiles, int tap_perm, int64_t out_ss,
+                                                          const float *__restrict__ in2, float *__restrict__ out2,
+                                                          int64_t Mkeep) {
+    const int b = (int)blockIdx.x;
+    const bool half = b >= main_tiles;
+    const int keep_units = 2 * (int)((Mkeep + BM - 1) / BM);
+    const int unit = half ? b + main_tiles : 2 * b;
+    const bool dense = unit >= keep_units;
+    const int lu = dense ? unit - keep_units : unit;  // unit inside its segment
+    const int64_t Mseg = dense ? Mtot - Mkeep : Mkeep;
+    if ((int64_t)lu * (BM / 2) >= Mseg) return;
+    const int shift = (half ? lu : lu >> 1) - b;       // blockIdx.x + shift = the tile's index inside its segment
+    if (!dense) {
+        if (!half)
+            fwd_glds_body<BM, BN, WM, WN, 2, true, false, true, true>(g, in, in_stride, wt, bias, out, Mseg, k_per_split, nullptr,
+                                                                      nullptr, 0, 0, 0, 0, tap_perm, shift, out_ss);
+        else
+            fwd_glds_body<BM / 2, BN, WM, WN, 2, true, false, true, true>(g, in, in_stride, wt, bias, out, Mseg, k_per_split,
+                                                                          nullptr, nullptr, 0, 0, 0, 0, tap_perm, shift, out_ss);
+    } else {
+        const int64_t dense_stride = (int64_t)g.H * g.W * g.Cin;
+        if (!half)
+            fwd_glds_body<BM, BN, WM, WN, 2, true, false, true>(g, in2, dense_stride, wt, bias, out2, Mseg, k_per_split, nullptr,
+                                                                nullptr, 0, 0, 0, 0, tap_perm, shift);
+        else
+            fwd_glds_body<BM / 2, BN, WM, WN, 2, true, false, true>(g, in2, dense_stride, wt, bias, out2, Mseg, k_per_split,
+                                                                    nullptr, nullptr, 0, 0, 0, 0, tap_perm, shift);
+    }
+}
+// k_fwd_glds_z for a linear layer whose rows come in two segments (fwd_glds_body, SEG); grid: ceil(Mkeep / BM) +
+// ceil((Mtot - Mkeep) / BM) row tiles, unsplit
+template <int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(256, 2) void k_fwd_glds_z_os(ConvG g, const float *__restrict__ in, int64_t in_stride,
+                                                         const float *__restrict__ wt, const float *__restrict__ bias,
+                                                         float *__restrict__ out, int64_t Mtot, int k_per_split, int rx, int ry,
+                                                         int rtot, int64_t out_ss, const float *__restrict__ in2,
+                                                         float *__restrict__ out2, int64_t Mkeep) {
+    fwd_glds_body<BM, BN, WM, WN, 2, true, false, false, false, true>(g, in, in_stride, wt, bias, out, Mtot, k_per_split, nullptr,
+                                                                      nullptr, 0, rx, ry, rtot, 0, 0, out_ss, in2, out2, Mkeep);
 }
 // the same kernel with the zero-VALU k-loop (see fwd_glds_body, ZL)
 template <int BM, int BN, int WM, int WN>

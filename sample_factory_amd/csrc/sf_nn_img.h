@@ -59,10 +59,16 @@ struct ImgFwdGeom {
 
 // OS (k_fwd_img_os, whole-image units only): output sample s starts out_ss floats behind sample s - 1 — row m goes to
 // out + (m / OHW) * out_ss + (m % OHW) * 64 (a rollout step writing its slot of a kept [E, T, OHW, 64] buffer).
+// Two segments: that holds for the samples below keep_n; sample s >= keep_n is read from in2 + (s - keep_n) * H*W*CIN and
+// written to out2 + (s - keep_n) * OHW * 64, both dense.  The input base is a scalar select per image; a block step whose
+// first row lies at or behind the split stores with the dense code, one wholly below it with the strided code of before, and
+// only the step that holds the split selects the base per row (also where a 4-row group wraps into the next sample).
 template <int CIN, int H, int W, int KS, int ST, int TMF, int WSETS, int R, bool OS>
 __device__ __forceinline__ void fwd_img_body(const float *__restrict__ in, int64_t in_stride,
                                              const float *__restrict__ wt, const float *__restrict__ bias,
-                                             float *__restrict__ out, int nsamples, int act, int64_t out_ss) {
+                                             float *__restrict__ out, int nsamples, int act, int64_t out_ss,
+                                             const float *__restrict__ in2 = nullptr, float *__restrict__ out2 = nullptr,
+                                             int keep_n = 0) {
     typedef ImgFwdGeom<CIN, H, W, KS, ST, TMF, WSETS, R> G;
     constexpr int NW = 4 * WSETS, TB = TMF * WSETS;  // waves per block, fragments per block step
     constexpr int OW = G::OW, OHW = G::OHW, K = G::K, KG = G::KG, WQ = G::WQ, PLANE = G::PLANE, RING = G::RING;
@@ -108,6 +114,9 @@ __device__ __forceinline__ void fwd_img_body(const float *__restrict__ in, int64
     auto load_image = [&](int s) {  // s: unit index
         const int u = s < nunits ? s : nunits - 1, smp = u / U, strip = u - smp * U;
         const float *img = in + (int64_t)smp * in_stride + strip * (R * ST * W * CIN);
+        if constexpr (OS) {
+            if (smp >= keep_n) img = in2 + (int64_t)(smp - keep_n) * (H * W * CIN);
+        }
         char *dst = ring + (s % RING) * IMG_B;
 #pragma unroll
         for (int j = 0; j < NI; ++j)
@@ -132,20 +141,32 @@ __device__ __forceinline__ void fwd_img_body(const float *__restrict__ in, int64
     auto store_pend = [&]() {
         if constexpr (OS) {
             static_assert(!OS || G::U == 1, "strided output: one unit per sample");
-            const uint32_t mb = (uint32_t)pend_fb * 16u + 4u * (uint32_t)kg;
+            const uint32_t mb = (uint32_t)pend_fb * 16u + 4u * (uint32_t)kg, mkeep = (uint32_t)keep_n * (uint32_t)OHW;
+            if ((uint32_t)pend_fb * 16u < mkeep) {  // (wave-uniform) the step has kept rows
+                auto strided = [&](auto selc) {
+                    constexpr bool SEL = decltype(selc)::value;  // the step holds the split: base per row
 #pragma unroll
-            for (int f = 0; f < TMF; ++f) {
-                const uint32_t m = mb + (uint32_t)f * 16u, s = m / (uint32_t)OHW, p = m - s * (uint32_t)OHW;
+                    for (int f = 0; f < TMF; ++f) {
+                        const uint32_t m = mb + (uint32_t)f * 16u, s = m / (uint32_t)OHW, p = m - s * (uint32_t)OHW;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const uint32_t wrap = p + (uint32_t)r >= (uint32_t)OHW ? 1u : 0u;  // (OHW >= 4: at most one sample boundary)
-                    float *o = out + (int64_t)(s + wrap) * out_ss + (int64_t)(p + (uint32_t)r - wrap * (uint32_t)OHW) * N + n;
-                    if (f < pend_nf && m + (uint32_t)r < M32) *o = pend[f][r];
-                }
+                        for (int r = 0; r < 4; ++r) {
+                            const uint32_t wrap = p + (uint32_t)r >= (uint32_t)OHW ? 1u : 0u;  // (OHW >= 4: at most one sample boundary)
+                            const uint32_t sr = s + wrap;
+                            float *ob = out + (int64_t)sr * out_ss;
+                            if constexpr (SEL) {
+                                if (sr >= (uint32_t)keep_n) ob = out2 + (int64_t)(sr - (uint32_t)keep_n) * (OHW * N);
+                            }
+                            float *o = ob + (int64_t)(p + (uint32_t)r - wrap * (uint32_t)OHW) * N + n;
+                            if (f < pend_nf && m + (uint32_t)r < M32) *o = pend[f][r];
+                        }
+                    }
+                };
+                if (((uint32_t)pend_fb + (uint32_t)TMF) * 16u <= mkeep) strided(std::false_type{});
+                else strided(std::true_type{});
+                return;
             }
-            return;
         }
-        float *ob = out + ((int64_t)pend_fb * 16 + 4 * kg) * N + n;
+        float *ob = (OS ? out2 - (int64_t)keep_n * (OHW * N) : out) + ((int64_t)pend_fb * 16 + 4 * kg) * N + n;
         const int rows_left = (int)(M32 - ((uint32_t)pend_fb * 16u + 4u * (uint32_t)kg));
 #pragma unroll
         for (int f = 0; f < TMF; ++f)
@@ -246,6 +267,7 @@ __global__ __launch_bounds__(256 * WSETS, 1) void k_fwd_img(const float *__restr
 template <int CIN, int H, int W, int KS, int ST, int TMF, int WSETS, int R>
 __global__ __launch_bounds__(256 * WSETS, 1) void k_fwd_img_os(const float *__restrict__ in, int64_t in_stride,
                                                        const float *__restrict__ wt, const float *__restrict__ bias,
-                                                       float *__restrict__ out, int nsamples, int act, int64_t out_ss) {
-    fwd_img_body<CIN, H, W, KS, ST, TMF, WSETS, R, true>(in, in_stride, wt, bias, out, nsamples, act, out_ss);
+                                                       float *__restrict__ out, int nsamples, int act, int64_t out_ss,
+                                                       const float *__restrict__ in2, float *__restrict__ out2, int keep_n) {
+    fwd_img_body<CIN, H, W, KS, ST, TMF, WSETS, R, true>(in, in_stride, wt, bias, out, nsamples, act, out_ss, in2, out2, keep_n);
 }

@@ -73,13 +73,16 @@ __device__ __forceinline__ void split3_bf16(float w, uint32_t &hi, uint32_t &mid
 // taken there too (4 channels per lane, OR over the 8 lanes of a pixel by DPP): one u32 store per pixel.
 // OS (WIDE only, k_conv1_u8_bf16_w_os): sample s of the output starts out_ss floats, its sign-bit words mask_ss words, behind
 // sample s - 1 (a rollout step writing slot t of a kept [E, T, 400, 32] buffer); the dense form is out_ss = 400 * 32,
-// mask_ss = 400.  Same products, same order, same stores per sample.
+// mask_ss = 400.  Same products, same order, same stores per sample.  Two segments: that holds for the samples below keep_n;
+// sample s >= keep_n goes to out2 + (s - keep_n) * 400 * 32 (dense) and its sign-bit words are not stored (a pair of samples
+// wholly behind the split does not work them out either).  The frames have one segment: they are the rollout's slab rows.
 template <bool SUB, int NCT, bool WIDE, bool OS = false>
 __device__ __forceinline__ void conv1_u8_bf16_body(ConvG g, const uint8_t *__restrict__ in, int64_t in_stride,
                                                    const int32_t *__restrict__ index, int64_t offset,
                                                    const float *__restrict__ w, const float *__restrict__ bias,
                                                    float *__restrict__ out, uint32_t *__restrict__ mask_out,
-                                                   int nsamples, int64_t out_ss = 0, int64_t mask_ss = 0) {
+                                                   int nsamples, int64_t out_ss = 0, int64_t mask_ss = 0,
+                                                   float *__restrict__ out2 = nullptr, int keep_n = 0) {
     static_assert(!OS || WIDE, "the strided output form exists for the whole-line store path only");
     constexpr int SMP = 2 * NCT, R = 4, TMF = 5, KB = 8;
     constexpr int H = 84, W = 84, WP = SF_CONV1_WP, Cin = 4, KH = 8, S = 4, OH = 20, OW = 20, OHOW = OH * OW;
@@ -287,18 +290,19 @@ __device__ __forceinline__ void conv1_u8_bf16_body(ConvG g, const uint8_t *__res
                 const bool sok = s0 + z < nsamples;
                 const int64_t pix0 = (int64_t)(s0 + z) * OHOW + st * (R * OW);
                 if constexpr (OS) {
-                    if (sok) *reinterpret_cast<float4 *>(out + (int64_t)(s0 + z) * out_ss + st * (R * OW) * 32 + qq * 4) = v;
+                    float *ob = s0 + z < keep_n ? out + (int64_t)(s0 + z) * out_ss : out2 + (int64_t)(s0 + z - keep_n) * (OHOW * 32);
+                    if (sok) *reinterpret_cast<float4 *>(ob + st * (R * OW) * 32 + qq * 4) = v;
                 } else {
                     if (sok) *reinterpret_cast<float4 *>(out + pix0 * 32 + qq * 4) = v;
                 }
-                if (g.relu == 1 && mask_out) {  // (uniform) sign bits of the pixel: 4 per lane, OR over its 8 lanes
+                if (g.relu == 1 && mask_out && (!OS || s0 < keep_n)) {  // (uniform) sign bits of the pixel: 4 per lane, OR over its 8 lanes
                     int nib = (v.x > 0.f ? 1 : 0) | (v.y > 0.f ? 2 : 0) | (v.z > 0.f ? 4 : 0) | (v.w > 0.f ? 8 : 0);
                     nib <<= 4 * ch;
                     nib |= __builtin_amdgcn_update_dpp(0, nib, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
                     nib |= __builtin_amdgcn_update_dpp(0, nib, 0x4E /* quad_perm [2,3,0,1] */, 0xF, 0xF, true);
                     nib |= __builtin_amdgcn_update_dpp(0, nib, 0x141 /* row_half_mirror */, 0xF, 0xF, true);
                     if constexpr (OS) {
-                        if (ch == 0 && sok) mask_out[(int64_t)(s0 + z) * mask_ss + st * (R * OW) + px] = (uint32_t)nib;
+                        if (ch == 0 && sok && s0 + z < keep_n) mask_out[(int64_t)(s0 + z) * mask_ss + st * (R * OW) + px] = (uint32_t)nib;
                     } else {
                         if (ch == 0 && sok) mask_out[pix0 + px] = (uint32_t)nib;
                     }
@@ -338,8 +342,9 @@ __global__ __launch_bounds__(256, 2)
 void k_conv1_u8_bf16_w_os(ConvG g, const uint8_t *__restrict__ in, int64_t in_stride, const int32_t *__restrict__ index,
                           int64_t offset, const float *__restrict__ w, const float *__restrict__ bias,
                           float *__restrict__ out, uint32_t *__restrict__ mask_out, int nsamples, int64_t out_ss,
-                          int64_t mask_ss) {
-    conv1_u8_bf16_body<SUB, 1, true, true>(g, in, in_stride, index, offset, w, bias, out, mask_out, nsamples, out_ss, mask_ss);
+                          int64_t mask_ss, float *__restrict__ out2, int keep_n) {
+    conv1_u8_bf16_body<SUB, 1, true, true>(g, in, in_stride, index, offset, w, bias, out, mask_out, nsamples, out_ss, mask_ss,
+                                           out2, keep_n);
 }
 
 // ============================================================================================== WEIGHT GRADIENT, raw u8 frames

@@ -55,6 +55,7 @@ SYMBOLS = [
     "sf_synth_step", "sf_synth_vec_step", "sf_h2d_rows", "sf_copy_rows", "sf_conv_fwd", "sf_conv_fwd_workspace", "sf_conv_wgrad_workspace", "sf_conv_wgrad",
     "sf_conv_dgrad", "sf_conv_norm_supported", "sf_conv_fwd_norm", "sf_conv_wgrad_norm", "sf_conv_relu_mask_supported", "sf_conv_fwd_relu_mask", "sf_conv_wgrad_relu_mask", "sf_conv_kernel_name", "sf_conv_fwd_t_supported", "sf_conv_fwd_t_workspace", "sf_conv_fwd_t", "sf_transpose",
     "sf_conv_fwd_os_supported", "sf_conv_fwd_relu_mask_os", "sf_conv_fwd_t_os",
+    "sf_conv_fwd_os2_supported", "sf_conv_fwd_relu_mask_os2", "sf_conv_fwd_t_os2",
     "sf_tanh_scale_fwd", "sf_tanh_scale_bwd",
     "sf_linear_fwd", "sf_linear_wgrad_workspace", "sf_linear_wgrad", "sf_linear_dgrad", "sf_relu_mask",
     "sf_dp_unique_id", "sf_dp_comm_create", "sf_dp_comm_destroy", "sf_dp_comm_info", "sf_allreduce_grads",
@@ -982,6 +983,40 @@ def conv_fwd_t_os(inp, in_sample_stride, wt, bias, out, out_sample_stride, n, de
         _check(load().sf_conv_fwd_t_os(_raw_in(inp, desc), i64(in_sample_stride), ptr(wt, "f32", "wt"),
                                        ptr(bias, "f32", "bias"), _raw(out, "f32", "out"), i64(out_sample_stride), i64(n),
                                        C.byref(desc), stream()), "sf_conv_fwd_t_os")
+
+
+def _raw_opt(t, kind, name):
+    return _raw(t, kind, name) if t is not None else C.c_void_p(0)
+
+
+def conv_fwd_os2_supported(op: str, n, keep_n, desc: sf_conv_desc, in_sample_stride, out_sample_stride) -> bool:
+    """conv_fwd_os_supported for the two-segment entry points with the split at sample keep_n"""
+    return bool(load().sf_conv_fwd_os2_supported(_OPS[op], i64(n), i64(keep_n), C.byref(desc), i64(in_sample_stride),
+                                                 i64(out_sample_stride)))
+
+
+def conv_fwd_relu_mask_os2(inp, in_sample_stride, index, offset, w, bias, out, out_sample_stride, relu_mask,
+                           mask_sample_stride, out2, keep_n, n, desc: sf_conv_desc) -> None:
+    """conv_fwd_relu_mask_os for samples [0, keep_n); samples [keep_n, n) go densely to out2 (sample keep_n first) and leave
+    no sign-bit words"""
+    with _timed(_nkey("fwd", n, desc, "fwd_os")):
+        _check(load().sf_conv_fwd_relu_mask_os2(_raw_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"),
+                                                i64(offset), ptr(w, "f32", "w"), ptr(bias, "f32", "bias"),
+                                                _raw(out, "f32", "out"), i64(out_sample_stride),
+                                                _raw(relu_mask, "i32", "relu_mask"), i64(mask_sample_stride),
+                                                _raw_opt(out2, "f32", "out2"), i64(keep_n), i64(n), C.byref(desc), stream()),
+               "sf_conv_fwd_relu_mask_os2")
+
+
+def conv_fwd_t_os2(inp, in_sample_stride, inp2, wt, bias, out, out_sample_stride, out2, keep_n, n,
+                   desc: sf_conv_desc) -> None:
+    """conv_fwd_t_os for samples [0, keep_n); samples [keep_n, n) are read densely from inp2 and written densely to out2"""
+    with _timed(_nkey("fwd_t", n, desc, "fwd_t_os")):
+        _check(load().sf_conv_fwd_t_os2(_raw_in(inp, desc), i64(in_sample_stride),
+                                        _raw_in(inp2, desc) if inp2 is not None else C.c_void_p(0), ptr(wt, "f32", "wt"),
+                                        ptr(bias, "f32", "bias"), _raw(out, "f32", "out"), i64(out_sample_stride),
+                                        _raw_opt(out2, "f32", "out2"), i64(keep_n), i64(n), C.byref(desc), stream()),
+               "sf_conv_fwd_t_os2")
 
 
 def tanh_scale_fwd(x, ld, n, col0, ncols, scale) -> None:

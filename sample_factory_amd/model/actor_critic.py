@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from sample_factory_amd import lib
-from sample_factory_amd.algo.learning.rollout_reuse import SlotRecord, reuse_prefix, twin_name
+from sample_factory_amd.algo.learning.rollout_reuse import SlotRecord, fc_reusable, keep_n, keep_rows, reuse_prefix, twin_name
 from sample_factory_amd.algo.utils.running_mean_std import RunningMeanStdInPlace
 from sample_factory_amd.envs.spaces import is_box, calc_num_action_parameters
 
@@ -649,8 +649,8 @@ class ActorCritic(NativeTower):
     def forward_heads(self, obs: torch.Tensor, n: int, *, sample_stride: int, index=None, offset: int = 0,
                       traj_T: int = 0, tag="inf", rnn=None, keep=None, resume_from=None) -> List[torch.Tensor]:
         """Run the whole stack on `n` samples; returns the list of layer outputs (last = heads [n, heads_ld]).
-        keep=(t, row0) (rollout tags, after configure_keep): the leading conv layers write slot t of rows [row0, row0 + n) of
-        the kept buffers.  resume_from (tag "train"): what kept_resume returned — those layers are not run, the forward
+        keep=(t, row0) (rollout tags, after configure_keep): the leading conv layers write slot t of those of the rows
+        [row0, row0 + n) that are kept, the others go to the ordinary activation buffers (two-segment launches).  resume_from (tag "train"): what kept_resume returned — those layers are not run, the forward
         continues behind them.
 
         obs: any (possibly strided) view whose data_ptr is sample 0; logical sample i lives at row
@@ -703,9 +703,13 @@ class ActorCritic(NativeTower):
         first_in = (x, stride, idx, off, tT)
         seq = rnn is not None and "R" in rnn
         kp = self._keep if keep is not None else None
+        kn, x2 = 0, None  # samples of this launch that are kept; the dense second segment of the current activation
         if kp is not None:
             assert tag.startswith("inf") and first_layer == 0 and norm_tabs is None and idx is None and not tT
-            assert n == kp["n_roll"] and stride == kp["obs_stride"] and keep[1] + n <= kp["rows"] and self._snap is None
+            assert n == kp["n_roll"] and stride == kp["obs_stride"] and keep[1] + n <= kp["total_rows"] and self._snap is None
+            kn = keep_n(kp["rows"], keep[1], n)
+            if kn == 0:  # an env instance whose rows all lie beyond minibatch 0: the plain dense forward
+                kp = None
         if resume_from is not None:  # the first minibatch behind the rollout: conv layers [0, prefix) were kept, bit for bit
             assert tag == "train" and first_layer == 0 and norm_tabs is None
             first_layer = resume_from["prefix"]
@@ -713,22 +717,43 @@ class ActorCritic(NativeTower):
                 inputs[li] = x if li == 0 else acts[li - 1]
                 acts[li] = resume_from["acts"][li]
             relu_mask0 = resume_from["mask"]
+            if resume_from.get("fc") is not None:  # ... and the fc layer behind them: the forward starts at the heads
+                inputs[first_layer], acts[first_layer] = acts[first_layer - 1], resume_from["fc"]
+                first_layer += 1
             x, stride, idx, off, tT = acts[first_layer - 1], acts[first_layer - 1].numel() // n, None, 0, 0
         for li, L in enumerate(self.layers):
             if L.role == "rnn_hh" or li < first_layer:
                 continue
             if kp is not None and li < kp["prefix"]:
                 t_, r0 = keep
-                kb = self._bufs[("keep", li)]  # [rows, T, pixels * channels]: this launch writes slot t_ of its rows
-                out, w_b = kb[r0:r0 + n, t_], self._wb(li, tag)
+                kb = self._bufs[("keep", li)]  # [keep_rows, T, pixels * channels]: this launch writes slot t_ of its kept rows
+                out, w_b, P = kb[r0:r0 + kn, t_], self._wb(li, tag), L.out_pixels * L.N
+                # samples [kn, n) go where the plain forward puts them: rows kn.. of the ordinary activation buffer
+                dense = self._buf((tag, li), (n * L.out_pixels, L.N)).view(n, P)
+                out2 = dense[kn:] if kn < n else None
                 if li == 0:
                     mk = self._bufs[("keep", "relu_mask0")]
-                    lib.conv_fwd_relu_mask_os(x, stride, None, 0, w_b[0], w_b[1], out, kb.stride(0), mk[r0:r0 + n, t_],
-                                              mk.stride(0), n, L.desc)
+                    lib.conv_fwd_relu_mask_os2(x, stride, None, 0, w_b[0], w_b[1], out, kb.stride(0), mk[r0:r0 + kn, t_],
+                                               mk.stride(0), out2, kn, n, L.desc)
                 else:
-                    lib.conv_fwd_t_os(x, stride, w_b[2], w_b[1], out, kb.stride(0), n, L.desc)
-                inputs[li], acts[li], x = x, out, out
+                    lib.conv_fwd_t_os2(x, stride, x2, w_b[2], w_b[1], out, kb.stride(0), out2, kn, n, L.desc)
+                inputs[li], acts[li], x, x2 = x, out, out, out2
                 stride, idx, off, tT = kb.stride(0), None, 0, 0
+                if li == kp["prefix"] - 1 and x2 is not None and kp["junction"] == "copy":
+                    # the next layer has no two-segment form of the kernel its dense launch runs: the kept samples of this
+                    # slot are copied in front of the dense ones (one launch of the row-copy kernel)
+                    lib.copy_rows(dense[:kn], out)
+                    x, x2, stride = dense, None, P
+                continue
+            if x2 is not None:  # the layer behind the kept ones reads the two segments and writes one dense activation
+                inputs[li] = x
+                out = self._buf((tag, li), (n * L.out_pixels, L.N))
+                w_b, P = self._wb(li, tag), L.out_pixels * L.N
+                lib.conv_fwd_t_os2(x, stride, x2, w_b[2], w_b[1], out, P, out.view(n, P)[kn:], kn, n, L.desc)
+                acts[li], x, x2 = out, out, None
+                stride, idx, off, tT = P, None, 0, 0
+                if li == kp["fc"]:
+                    lib.copy_rows(self._bufs[("keep", "fc")][keep[1]:keep[1] + kn, keep[0]], out.view(n, P)[:kn])
                 continue
             if L.role == "rnn_ih" and seq:  # BPTT pass: the recurrent block works time-major ([R, C, .])
                 R, Cn = rnn["R"], n // rnn["R"]
@@ -775,6 +800,10 @@ class ActorCritic(NativeTower):
                 relu_mask0 = mask  # kept in this forward's OWN context (below): nothing a forward leaves behind is untagged
             acts[li] = out
             x = out
+            if kp is not None and li == kp["fc"]:
+                # the heads read the fc output where it is; its kept rows are also filed in slot t of the kept fc buffer (one
+                # launch of the row-copy kernel, 2 KB a row), where the first minibatch finds them as its dense fc activation
+                lib.copy_rows(self._bufs[("keep", "fc")][keep[1]:keep[1] + kn, keep[0]], out.view(n, L.N)[:kn])
             if L.role == "rnn_ih":
                 if fuse_x:
                     acts[li] = None  # gx is never materialised
@@ -793,8 +822,9 @@ class ActorCritic(NativeTower):
 
     # ------------------------------------------------------------------------------------------ kept rollout activations
     # (the decision itself: algo/learning/rollout_reuse.py)
-    def _keep_rollout_ok(self, li, n, in_stride, out_stride) -> bool:
-        """layer li's rollout launch has a strided-output twin of the kernel the dense launch of that size runs"""
+    def _keep_rollout_ok(self, li, n, in_stride, out_stride, splits=(), kinds=("conv",)) -> bool:
+        """layer li's rollout launch has a strided-output twin of the kernel the dense launch of that size runs, for every
+        split point (samples kept of a launch) in `splits`"""
         L = self.layers[li]
         d = L.desc
         if li == 0:
@@ -802,12 +832,17 @@ class ActorCritic(NativeTower):
                 return False
             if not lib.conv_relu_mask_supported(n, d) or not lib.conv_fwd_os_supported("fwd", n, d, in_stride, out_stride):
                 return False
+            if not all(lib.conv_fwd_os2_supported("fwd", n, k, d, in_stride, out_stride) for k in splits):
+                return False
             return lib.conv_kernel_name(6, n, d) == twin_name(lib.conv_kernel_name(0, n, d))
-        if L.kind != "conv" or L.wt is None or not lib.conv_fwd_t_supported(n, d) or lib.conv_fwd_t_workspace(n, d):
+        if L.kind not in kinds or L.wt is None or not lib.conv_fwd_t_supported(n, d) or lib.conv_fwd_t_workspace(n, d):
             return False
-        if not lib.conv_fwd_os_supported("fwd_t", n, d, in_stride, out_stride):
+        if not all(lib.conv_fwd_os2_supported("fwd_t", n, k, d, in_stride, out_stride) for k in (n,) + tuple(splits)):
             return False
-        return lib.conv_kernel_name(7, n, d) == twin_name(lib.conv_kernel_name(3, n, d))
+        try:
+            return lib.conv_kernel_name(7, n, d) == twin_name(lib.conv_kernel_name(3, n, d))
+        except lib.SfHipError:  # (no twin at all for this launch)
+            return False
 
     def _keep_same_kernel(self, li, n_roll, n_train) -> bool:
         """layer li's training launch runs the kernel of its rollout launch, unsplit: the kept bytes are the bytes it would write"""
@@ -820,6 +855,18 @@ class ActorCritic(NativeTower):
                 ok = ok and lib.conv_relu_mask_supported(n_train, d)
             else:
                 ok = ok and lib.conv_fwd_t_supported(n_train, d) and not lib.conv_fwd_t_workspace(n_train, d)
+            self._keep_same[key] = bool(ok)
+        return self._keep_same[key]
+
+    def _keep_fc_ok(self, li, n_roll, n_train) -> bool:
+        """the fc layer's rollout launch and training launch write the same bytes (rollout_reuse.fc_reusable)"""
+        key = ("fc", li, n_roll, n_train)
+        ok = self._keep_same.get(key)
+        if ok is None:
+            d = self.layers[li].desc
+            ok = lib.conv_fwd_t_supported(n_roll, d) and lib.conv_fwd_t_supported(n_train, d) and \
+                fc_reusable(lib.conv_kernel_name(3, n_roll, d), lib.conv_kernel_name(3, n_train, d),
+                            lib.conv_fwd_t_workspace(n_roll, d), lib.conv_fwd_t_workspace(n_train, d))
             self._keep_same[key] = bool(ok)
         return self._keep_same[key]
 
@@ -839,16 +886,38 @@ class ActorCritic(NativeTower):
         if (self.part != "full" or self.obs_normalizer is not None or self.rnn_kind is not None or self._snap is not None or
                 getattr(cfg, "async_rl", False) or getattr(cfg, "shuffle_minibatches", False) or len(self.obs_shape) != 3):
             return 0
+        # only the trajectories of minibatch 0 are ever read back: they alone are kept, an env instance whose rows straddle
+        # their end runs two-segment launches (split at `straddle` samples), one wholly beyond them the plain forward
+        total_rows, rows = int(rows), keep_rows(int(cfg.batch_size), int(T), int(rows))
+        if rows <= 0:
+            return 0
+        straddle = rows % int(n_roll)
+        splits = (straddle,) if straddle else ()
         nconv = sum(1 for L in self.layers if L.kind in FRAME_KINDS or L.kind == "conv")
         prefix, in_stride = 0, int(obs_stride)
         for li in range(min(3, nconv, len(self.layers) - 1)):
             L = self.layers[li]
-            if not self._keep_rollout_ok(li, n_roll, in_stride, T * L.out_pixels * L.N):
+            if not self._keep_rollout_ok(li, n_roll, in_stride, T * L.out_pixels * L.N, splits):
                 break
             prefix, in_stride = prefix + 1, T * L.out_pixels * L.N
         if prefix == 0:
             return 0
+        # the layer behind the kept ones reads a two-segment input where a launch straddles: through the two-segment form of
+        # the kernel its dense launch runs ("twin"), else the kept samples are first copied in front of the dense ones ("copy")
+        junction = None
+        if straddle:
+            Lj = self.layers[prefix]
+            junction = "twin" if Lj.role == "chain" and \
+                self._keep_rollout_ok(prefix, n_roll, in_stride, Lj.out_pixels * Lj.N, splits, kinds=("conv", "linear", "linear_after_conv")) else "copy"
+        # the fc layer behind the last conv layer: its rollout output is kept as well where both of its launches are unsplit
+        # k_fwd_glds_z forms with the same bytes (rollout_reuse.fc_reusable; decided per minibatch size in kept_resume)
+        fc = None
+        Lf = self.layers[prefix] if prefix == nconv and prefix + 1 < len(self.layers) else None
+        if Lf is not None and Lf.kind in ("linear", "linear_after_conv") and Lf.role == "chain" and Lf.wt is not None and Lf.out_pixels == 1 and \
+                self._keep_fc_ok(prefix, n_roll, int(cfg.batch_size)):
+            fc = prefix
         need = sum(rows * T * self.layers[li].out_pixels * (self.layers[li].N + (1 if li == 0 else 0)) * 4 for li in range(prefix))
+        need += rows * T * Lf.N * 4 if fc is not None else 0
         free = torch.cuda.mem_get_info(self.device)[0] + sum(t.numel() * t.element_size() for k, t in self._bufs.items()
                                                              if isinstance(k, tuple) and k and k[0] == "keep")
         if ("train", 0) not in self._bufs:  # the training-size buffers do not exist yet: an activation and a gradient per layer
@@ -863,15 +932,20 @@ class ActorCritic(NativeTower):
             L = self.layers[li]
             self._buf(("keep", li), (rows, T, L.out_pixels * L.N))
         self._buf(("keep", "relu_mask0"), (rows, T, self.layers[0].out_pixels), dtype=torch.int32)
-        self._keep = dict(rows=int(rows), T=int(T), prefix=prefix, n_roll=int(n_roll), obs_stride=int(obs_stride), records={})
+        if fc is not None:
+            self._buf(("keep", "fc"), (rows, T, Lf.N))
+        self._keep = dict(rows=int(rows), total_rows=total_rows, T=int(T), prefix=prefix, n_roll=int(n_roll),
+                          obs_stride=int(obs_stride), junction=junction, fc=fc, records={})
         return prefix
 
     def keep_note(self, t: int, row0: int, n: int, obs_ptr: int) -> None:
-        """a rollout step (run plainly or replayed from its launch program) has written slot t of kept rows [row0, row0 + n)
-        from the frames starting at obs_ptr, with the weights as they are now"""
+        """a rollout step over rows [row0, row0 + n) (run plainly or replayed from its launch program) has written slot t of
+        those of them that are kept, [row0, row0 + keep_n), from the frames starting at obs_ptr, with the weights as they are now"""
         if self._keep is not None:
-            self._keep["records"][(int(row0), int(t))] = SlotRecord(int(row0), int(row0) + int(n), int(t), self.weights_gen,
-                                                                   int(obs_ptr))
+            kn = keep_n(self._keep["rows"], row0, n)
+            if kn > 0:
+                self._keep["records"][(int(row0), int(t))] = SlotRecord(int(row0), int(row0) + kn, int(t), self.weights_gen,
+                                                                       int(obs_ptr))
 
     def kept_resume(self, obs, index, offset: int, n: int, T: int, epoch: int, batch_num: int):
         """(resume_from for forward_heads | None, reason): the kept activations of dataset rows [offset, offset + n) of `obs`
@@ -897,7 +971,10 @@ class ActorCritic(NativeTower):
             acts.append(self._bufs[("keep", li)].view(-1, L.out_pixels * L.N)[offset:offset + n].view(n * L.out_pixels, L.N))
         P0 = self.layers[0].out_pixels
         mask = self._bufs[("keep", "relu_mask0")].view(-1)[offset * P0:(offset + n) * P0]
-        return dict(prefix=prefix, acts=acts, mask=mask), why
+        fc = None
+        if kp["fc"] is not None and prefix == kp["fc"] and self._keep_fc_ok(prefix, kp["n_roll"], n):
+            fc = self._bufs[("keep", "fc")].view(-1, self.layers[prefix].N)[offset:offset + n]
+        return dict(prefix=prefix, acts=acts, mask=mask, fc=fc), why
 
     # ------------------------------------------------------------------------------------------ recurrent core
     def _rnn_step(self, li, gx, n, rnn, tag, x_in=None, x_stride=0):

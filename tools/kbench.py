@@ -78,6 +78,47 @@ def main():
                 for rnd in range(2):
                     td, ts = timeit(dense, reps), timeit(strided, max(reps, T))
                     res.append(f"dense {td*1e3:8.1f}us strided(T={T}) {ts*1e3:8.1f}us")
+            if "fwd_os2" in which and name in ("conv1", "conv2", "conv3", "fc"):
+                # the two-segment twins (sf_conv_fwd_*_os2) at the rollout size, to tell the twin's address work from the scatter of
+                # its kept segment: the dense launch (conv1: without sign-bit words, as the plain rollout runs it) | keep_n = 0 (the
+                # dense segment alone: must time like the dense launch) | keep_n = n into T slots (today's strided launch) |
+                # keep_n = n with T = 1 (the strided code writing contiguous memory: address work alone) | keep_n = n / 4 (the
+                # headline split).  fc writes a dense output in every mode; only its input has the two segments.
+                T = int(os.environ.get("KBENCH_T", "32"))
+                L_out, L_in, P = d.OH*d.OW*d.Cout, d.H*d.W*d.Cin, d.OH*d.OW
+                fc = name == "fc"
+                kept = None if fc else torch.empty((n, T, L_out), device="cuda")
+                step = [0]
+                if d.in_u8:
+                    mk = torch.empty((n, T, P), dtype=torch.int32, device="cuda")
+                    dense = lambda: lib.conv_fwd(x, stride, None, 0, w, b, out, n, d, None)
+                    def twin(kn, Tt):
+                        t_ = step[0] % Tt; step[0] += 1
+                        o1 = kept.view(-1)[:n*Tt*L_out].view(n, Tt, L_out); m1 = mk.view(-1)[:n*Tt*P].view(n, Tt, P)
+                        lib.conv_fwd_relu_mask_os2(x, stride, None, 0, w, b, o1[:max(kn, 1), t_], Tt*L_out, m1[:max(kn, 1), t_], Tt*P,
+                                                   out.view(n, L_out)[kn:] if kn < n else None, kn, n, d)
+                else:
+                    wt = torch.empty((d.Cout, K), device="cuda"); lib.transpose(w, wt, K, d.Cout)
+                    xin = torch.randn((n, T, L_in), device="cuda")
+                    x2 = x.view(n, L_in)
+                    wst = None
+                    if fc:
+                        nb = lib.conv_fwd_t_workspace(n, d); wst = torch.empty(nb, dtype=torch.uint8, device="cuda") if nb else None
+                    dense = lambda: lib.conv_fwd_t(x, stride, wt, b, out, n, d, wst)
+                    def twin(kn, Tt):
+                        t_ = step[0] % Tt; step[0] += 1
+                        i1 = xin.view(-1)[:n*Tt*L_in].view(n, Tt, L_in)
+                        if fc:
+                            o1, oss = out.view(n, L_out), L_out
+                        else:
+                            o1, oss = kept.view(-1)[:n*Tt*L_out].view(n, Tt, L_out)[:, t_], Tt*L_out
+                        lib.conv_fwd_t_os2(i1[:max(kn, 1), t_], Tt*L_in, x2[kn:] if kn < n else None, wt, b, o1[:max(kn, 1)], oss,
+                                           out.view(n, L_out)[kn:] if kn < n else None, kn, n, d)
+                for rnd in range(2):
+                    r = max(reps, T)
+                    res.append(f"dense {timeit(dense, r)*1e3:7.1f}us keep0 {timeit(lambda: twin(0, T), r)*1e3:7.1f}us "
+                               f"keepN(T={T}) {timeit(lambda: twin(n, T), r)*1e3:7.1f}us keepN(T=1) {timeit(lambda: twin(n, 1), r)*1e3:7.1f}us "
+                               f"keepN/4(T={T}) {timeit(lambda: twin(n // 4, T), r)*1e3:7.1f}us")
             if "wgrad" in which and n in grads_at:
                 dw = torch.empty_like(w); db = torch.empty_like(b)
                 ws = torch.empty(lib.conv_wgrad_workspace(n, d),dtype=torch.uint8,device="cuda")
