@@ -285,6 +285,22 @@ int sf_sample_write_step_tuple(const float *logits, int ld_logits, const float *
                                float *traj_logits, float *traj_logp, float *traj_values, float *traj_policy_version,
                                int32_t *env_actions, void *stream);
 
+/* sf_sample_write_step_tuple under obs["action_mask"]: u8 [B, A], A = the members' parameter counts added up, row b at
+ * action_mask + b * ld_mask (ld_mask >= A), mask column c belonging to logits column c.  A Discrete member reads the
+ * slice at its own logits offset and follows the rule of sf_sample_write_step_masked on it: masked-out logits count as
+ * z - 1e9 in the log-sum-exp, p = softmax * mask / (sum + 1e-13), an all-zero slice draws uniformly (arg-max: action 0),
+ * the member's log-prob is the masked log-softmax at the drawn action; the 2 * D columns under a Box(D) member are never
+ * read and the member is sampled as without a mask.  (The reference's Tuple path indexes the mask by member along the
+ * BATCH dimension, action_distributions.py:224; this is the per-parameter layout its Discrete path uses.)  Philox
+ * counters as in sf_sample_write_step_tuple: the mask changes probabilities, never uniforms.  Raw logits are recorded.
+ * Refused before any launch (-1): a null mask, ld_mask < A, and what sf_sample_write_step_tuple refuses. */
+int sf_sample_write_step_tuple_masked(const float *logits, int ld_logits, const float *values, int ld_values,
+                                      const uint8_t *action_mask, int64_t ld_mask, int B, int num_heads,
+                                      const int32_t *head_n, int T, int t, uint32_t seed, uint32_t step, uint32_t row0,
+                                      float policy_version, int deterministic, float *traj_actions, float *traj_logits,
+                                      float *traj_logp, float *traj_values, float *traj_policy_version,
+                                      int32_t *env_actions, void *stream);
+
 /* ---- K1/K6: env outputs -> trajectory step ---------------------------------------------------------------------
  * batched_sampling.py:208-213 (reward*scale, clamp +-clip), :319-335 (rewards/dones/time_outs/policy_id into
  * traj[:, t]) and :215-287 (episode statistics, kept on device: ep_return/ep_len per env, and on `done` the

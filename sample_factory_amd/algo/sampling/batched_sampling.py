@@ -3,7 +3,7 @@
 inference_worker.py:313-341 (InferenceWorker._handle_policy_steps), collapsed into one stream-ordered loop:
 
   per step t:   policy forward on slab obs[:, t] (in place)          K2+K3  sf_conv_fwd stack
-                sample + write policy outputs into traj[:, t]         K4+K5  sf_sample_write_step
+                sample + write policy outputs into traj[:, t]         K4+K5  sf_sample_write_step[_tuple][_masked]
                 env.step -> obs straight into slab obs[:, t+1]        K1     (zero-copy for envs with step_into)
                 rewards/dones/time_outs/policy_id + episode stats     K6     sf_traj_write_env_step
 
@@ -39,6 +39,17 @@ class BatchedVectorEnvRunner:
         assert traj["rewards"].shape == (self.B, self.T), "one slab row per agent (sync mode: one rollout per dataset)"
         self.heads = action_head_sizes(env_info.action_space)  # [n] | [n1, -D2, ...] (Tuple; -D = a Box(D) member) | [] (Box)
         self.mixed = heads_mixed(self.heads)  # Tuple with a Box member: the env reads the slab's f32 action row, split per member
+        # obs["action_mask"]: one u8 column per distribution parameter.  A Discrete member reads the columns under its own
+        # logits; the 2 * D columns under a Box(D) member are ignored (TupleActionDistribution splits the mask the same way)
+        self.masked = "action_mask" in traj["obs"]
+        if self.masked and is_box(env_info.action_space):
+            raise NotImplementedError("action masks are supported for Discrete and Tuple action spaces: a pure Box action "
+                                      "space has nothing to mask")
+        if self.masked and traj["obs"]["action_mask"].shape[-1] != actor_critic.num_action_params:
+            raise ValueError(f"obs['action_mask'] has {traj['obs']['action_mask'].shape[-1]} columns, the action space has "
+                             f"{actor_critic.num_action_params} distribution parameters: the mask holds one column per "
+                             "distribution parameter (a Discrete member reads the columns under its own logits, the columns "
+                             "under a Box member are ignored)")
         self.env_actions = torch.zeros((self.B, len(self.heads)) if len(self.heads) > 1 else self.B, dtype=torch.int32,
                                        device=dev)
         self.ep_return = torch.zeros(self.B, dtype=torch.float32, device=dev)
@@ -80,9 +91,6 @@ class BatchedVectorEnvRunner:
         self.program_replays = 0
         self._launch_key = getattr(actor_critic, "launch_key", None) if lib.LAUNCH_PROGRAMS else None
         self.keep_on, self.keep_row0 = False, 0  # the model keeps the conv activations of this runner's steps (Runner.init)
-        self.masked = "action_mask" in traj["obs"]
-        if self.masked and (self.continuous or len(self.heads) != 1):
-            raise NotImplementedError("action masks are supported for a single Discrete action space")
         if self.masked and self.zero_copy:
             raise NotImplementedError("action masks with a zero-copy (step_into) env")
 
@@ -239,7 +247,13 @@ class BatchedVectorEnvRunner:
         x = {k: tr["obs"][k][:, t] for k in self.obs_keys} if self.multi_key else self.obs[:, t]
         kw = dict(keep=(t, self.keep_row0)) if self.keep_on else {}
         heads = self.ac.forward_heads(x, B, sample_stride=self.obs.stride(0), tag=self.tag, rnn=rnn, **kw)[-1]
-        if self.masked:
+        if self.masked and len(self.heads) > 1:  # Tuple space under a mask: every Discrete member on its own mask columns
+            mk = tr["obs"]["action_mask"][:, t]
+            lib.sample_write_step_tuple_masked(heads[:, 1:], self.ld, heads[:, 0], self.ld, mk, mk.stride(0), B,
+                                               self.heads, T, t, self.sample_seed, step, self.row0, ver, deterministic,
+                                               tr["actions"], tr["action_logits"], tr["log_prob_actions"], tr["values"],
+                                               tr["policy_version"], None if self.mixed else self.env_actions)
+        elif self.masked:
             mk = tr["obs"]["action_mask"][:, t]
             lib.sample_write_step_masked(heads[:, 1:], self.ld, heads[:, 0], self.ld, mk, mk.stride(0), B, A, T, t,
                                          self.sample_seed, step, self.row0, ver, deterministic,

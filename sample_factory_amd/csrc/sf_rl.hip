@@ -2144,9 +2144,9 @@ __global__ __launch_bounds__(256) void k_sample_write(const float *__restrict__ 
     if (env_actions) env_actions[b] = a;
 }
 
-// The three samplers for A > 128, one wave per env row: any head list of up to SF_MAX_ACTION_HEADS members, or one Discrete(A) with an
-// action mask (mask != nullptr, the rule above k_sample_write_masked).  Same Philox counters, uniforms and draw rule
-// as the lane-per-row samplers.  The CDF is walked 64 columns at a time: an inclusive wave scan of the chunk's
+// The four samplers for A > 128, one wave per env row: any head list of up to SF_MAX_ACTION_HEADS members, with or without
+// an action mask (mask != nullptr: the rule above k_sample_write_masked per Discrete member, on the member's own mask
+// columns).  Same Philox counters, uniforms and draw rule as the lane-per-row samplers.  The CDF is walked 64 columns at a time: an inclusive wave scan of the chunk's
 // probabilities plus the carry of the chunks before it, a ballot for the first lane with u < cdf.
 __global__ __launch_bounds__(256) void k_sample_write_wide(const float *__restrict__ logits, int ldl,
                                                            const float *__restrict__ values, int ldv,
@@ -2190,14 +2190,16 @@ __global__ __launch_bounds__(256) void k_sample_write_wide(const float *__restri
             continue;
         }
         const float *zh = z + off;
+        // the member's slice of the row's mask: mask column c belongs to logits column c (one head: off = 0)
+        const uint8_t *mh = mk ? mk + off : nullptr;
         float mx, lse;
-        wide_lse(zh, nh, lane, mk, mx, lse);
-        // masked: probs = softmax * mask / (sum + 1e-13), an all-masked row draws from nh weights of 1e-6
+        wide_lse(zh, nh, lane, mh, mx, lse);
+        // masked: probs = softmax * mask / (sum + 1e-13), an all-masked member draws from nh weights of 1e-6
         bool all_zero = false;
         float inv = 1.f, tot = 1.f;
-        if (mk) {
+        if (mh) {
             float ps = 0.f;
-            for (int k = lane; k < nh; k += 64) ps += mk[k] ? expf((zh[k] - mx) - lse) : 0.f;
+            for (int k = lane; k < nh; k += 64) ps += mh[k] ? expf((zh[k] - mx) - lse) : 0.f;
             const float psum = wide_allsum(ps);
             all_zero = psum == 0.f;
             inv = 1.0f / (psum + 1e-13f);
@@ -2206,16 +2208,16 @@ __global__ __launch_bounds__(256) void k_sample_write_wide(const float *__restri
         int a;
         if (deterministic) {
             int first = 0x7fffffff;
-            if (!mk) {  // first maximum, as torch.argmax
+            if (!mh) {  // first maximum, as torch.argmax
                 for (int k = lane; k < nh; k += 64) if (zh[k] == mx) first = min(first, k);
             } else if (all_zero) {
                 first = 0;
             } else {  // first maximum of the masked probabilities
                 float best = -1.f;
-                for (int k = lane; k < nh; k += 64) best = fmaxf(best, mk[k] ? expf((zh[k] - mx) - lse) * inv : 0.f);
+                for (int k = lane; k < nh; k += 64) best = fmaxf(best, mh[k] ? expf((zh[k] - mx) - lse) * inv : 0.f);
                 best = wide_allmax(best);
                 for (int k = lane; k < nh; k += 64)
-                    if ((mk[k] ? expf((zh[k] - mx) - lse) * inv : 0.f) == best) first = min(first, k);
+                    if ((mh[k] ? expf((zh[k] - mx) - lse) * inv : 0.f) == best) first = min(first, k);
             }
             a = min(wide_allmin(first), nh - 1);  // (no maximum found: NaN logits, out of scope; stay inside the row)
         } else {
@@ -2229,8 +2231,8 @@ __global__ __launch_bounds__(256) void k_sample_write_wide(const float *__restri
                 const int k = base + lane;
                 float p = 0.f;
                 if (k < nh) {
-                    if (!mk) p = expf((zh[k] - mx) - lse);
-                    else p = (all_zero ? 1e-6f : (mk[k] ? expf((zh[k] - mx) - lse) * inv : 0.f)) / tot;
+                    if (!mh) p = expf((zh[k] - mx) - lse);
+                    else p = (all_zero ? 1e-6f : (mh[k] ? expf((zh[k] - mx) - lse) * inv : 0.f)) / tot;
                 }
                 float c = p;
 #pragma unroll
@@ -2251,7 +2253,7 @@ __global__ __launch_bounds__(256) void k_sample_write_wide(const float *__restri
             // probability, never a zero-probability (underflowed or masked-out) one
             if (a < 0) a = last_pos >= 0 ? last_pos : nh - 1;
         }
-        lp_sum += ((mk ? zh[a] + (mk[a] ? 0.f : -1e9f) : zh[a]) - mx) - lse;
+        lp_sum += ((mh ? zh[a] + (mh[a] ? 0.f : -1e9f) : zh[a]) - mx) - lse;
         if (lane == 0) {
             t_actions[it * NA + aoff] = (float)a;
             if (env_actions) env_actions[(int64_t)b * H + h] = a;  // all-Discrete head lists only (the launchers check)
@@ -2386,18 +2388,19 @@ extern "C" int sf_sample_write_step_masked(const float *logits, int ld_logits, c
     return sf_launch_status("sf_sample_write_step_masked");
 }
 
-// Tuple of Discrete heads: every head is sampled from its own Philox uniform (counter lane 1 = head index)
-__global__ __launch_bounds__(256) void k_sample_write_tuple(const float *__restrict__ logits, int ldl,
-                                                            const float *__restrict__ values, int ldv, int B, int A, int T,
-                                                            int t, uint32_t seed, uint32_t step, uint32_t row0,
-                                                            float version, int deterministic, LossDev hd,
-                                                            float *__restrict__ t_actions, float *__restrict__ t_logits,
-                                                            float *__restrict__ t_logp, float *__restrict__ t_values,
-                                                            float *__restrict__ t_version,
-                                                            int32_t *__restrict__ env_actions) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const float *z = logits + (int64_t)b * ldl;
+// Tuple of Discrete / Box heads, one lane per row: every head is sampled from its own Philox uniform (counter lane 1 =
+// head index).  MASKED: the rule above k_sample_write_masked per Discrete member, on the member's slice of the row's
+// mask (mask column c belongs to logits column c; the 2 * D columns under a Box(D) member are never read).  The mask
+// changes the probabilities, never the uniforms.  The unmasked instantiation has no mask code at all.
+template <bool MASKED>
+__device__ __forceinline__ void sample_write_tuple_row(const float *__restrict__ z, const uint8_t *__restrict__ mk,
+                                                       const float *__restrict__ values, int ldv, int b, int A, int T,
+                                                       int t, uint32_t seed, uint32_t step, uint32_t row0, float version,
+                                                       int deterministic, const LossDev &hd,
+                                                       float *__restrict__ t_actions, float *__restrict__ t_logits,
+                                                       float *__restrict__ t_logp, float *__restrict__ t_values,
+                                                       float *__restrict__ t_version,
+                                                       int32_t *__restrict__ env_actions) {
     const int64_t it = (int64_t)b * T + t;
     const int H = hd.num_heads;
     const int NA = heads_action_cols(hd.head_n, H);
@@ -2423,30 +2426,68 @@ __global__ __launch_bounds__(256) void k_sample_write_tuple(const float *__restr
             off += 2 * D; aoff += D;
             continue;
         }
-        float mx = -INFINITY;
-        for (int k = 0; k < nh; ++k) mx = fmaxf(mx, z[off + k]);
-        float se = 0.f;
-        for (int k = 0; k < nh; ++k) se += expf(z[off + k] - mx);
-        const float lse = logf(se);
         int a = nh - 1;
-        if (deterministic) {
-            for (int k = nh - 1; k >= 0; --k) if (z[off + k] == mx) a = k;  // first maximum, as torch.argmax
-        } else {
-            uint32_t w[4];
-            sf_philox4x32_10(step, (uint32_t)h, 2u, 0u, seed, row0 + (uint32_t)b, w);
-            const float u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);
-            float acc = 0.f;
-            int last_pos = nh - 1;
-            bool found = false;
-            for (int k = 0; k < nh; ++k) {
-                const float p = expf((z[off + k] - mx) - lse);
-                acc += p;
-                if (p > 0.f) last_pos = k;
-                if (u < acc) { a = k; found = true; break; }
+        if constexpr (MASKED) {
+            const float *zh = z + off;
+            const uint8_t *mh = mk + off;
+            float mx = -INFINITY;
+            for (int k = 0; k < nh; ++k) mx = fmaxf(mx, zh[k] + (mh[k] ? 0.f : -1e9f));
+            float se = 0.f;
+            for (int k = 0; k < nh; ++k) se += expf((zh[k] + (mh[k] ? 0.f : -1e9f)) - mx);
+            const float lse = logf(se);
+            float psum = 0.f;
+            for (int k = 0; k < nh; ++k) psum += mh[k] ? expf((zh[k] - mx) - lse) : 0.f;
+            const bool all_zero = psum == 0.f;
+            const float inv = 1.0f / (psum + 1e-13f);
+            if (deterministic) {  // first maximum of the masked probabilities (an all-zero slice: nh equal weights, action 0)
+                float best = -1.f;
+                for (int k = 0; k < nh; ++k) {
+                    const float p = all_zero ? 1e-6f : (mh[k] ? expf((zh[k] - mx) - lse) * inv : 0.f);
+                    if (p > best) { best = p; a = k; }
+                }
+            } else {
+                uint32_t w[4];
+                sf_philox4x32_10(step, (uint32_t)h, 2u, 0u, seed, row0 + (uint32_t)b, w);
+                const float u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);
+                const float tot = all_zero ? (float)nh * 1e-6f : psum * inv;  // multinomial normalises its weights
+                float acc = 0.f;
+                int last_pos = -1;  // last action with any probability (allowed, not underflowed)
+                bool found = false;
+                for (int k = 0; k < nh; ++k) {
+                    const float p = (all_zero ? 1e-6f : (mh[k] ? expf((zh[k] - mx) - lse) * inv : 0.f)) / tot;
+                    acc += p;
+                    if (p > 0.f) last_pos = k;
+                    if (u < acc) { a = k; found = true; break; }  // (acc only moves where p > 0: never a masked-out k)
+                }
+                // rounding left u beyond the last allowed action: take the last allowed one
+                if (!found && last_pos >= 0) a = last_pos;
             }
-            if (!found) a = last_pos;  // rounding left u beyond the CDF: the last action with non-zero probability
+            lp_sum += ((zh[a] + (mh[a] ? 0.f : -1e9f)) - mx) - lse;
+        } else {
+            float mx = -INFINITY;
+            for (int k = 0; k < nh; ++k) mx = fmaxf(mx, z[off + k]);
+            float se = 0.f;
+            for (int k = 0; k < nh; ++k) se += expf(z[off + k] - mx);
+            const float lse = logf(se);
+            if (deterministic) {
+                for (int k = nh - 1; k >= 0; --k) if (z[off + k] == mx) a = k;  // first maximum, as torch.argmax
+            } else {
+                uint32_t w[4];
+                sf_philox4x32_10(step, (uint32_t)h, 2u, 0u, seed, row0 + (uint32_t)b, w);
+                const float u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);
+                float acc = 0.f;
+                int last_pos = nh - 1;
+                bool found = false;
+                for (int k = 0; k < nh; ++k) {
+                    const float p = expf((z[off + k] - mx) - lse);
+                    acc += p;
+                    if (p > 0.f) last_pos = k;
+                    if (u < acc) { a = k; found = true; break; }
+                }
+                if (!found) a = last_pos;  // rounding left u beyond the CDF: the last action with non-zero probability
+            }
+            lp_sum += (z[off + a] - mx) - lse;
         }
-        lp_sum += (z[off + a] - mx) - lse;
         t_actions[it * NA + aoff] = (float)a;
         if (env_actions) env_actions[(int64_t)b * H + h] = a;  // all-Discrete tuples only (the launcher checks)
         off += nh; aoff += 1;
@@ -2455,6 +2496,37 @@ __global__ __launch_bounds__(256) void k_sample_write_tuple(const float *__restr
     t_logp[it] = lp_sum;
     t_version[it] = version;
     t_values[(int64_t)b * (T + 1) + t] = values[(int64_t)b * ldv];
+}
+
+__global__ __launch_bounds__(256) void k_sample_write_tuple(const float *__restrict__ logits, int ldl,
+                                                            const float *__restrict__ values, int ldv, int B, int A, int T,
+                                                            int t, uint32_t seed, uint32_t step, uint32_t row0,
+                                                            float version, int deterministic, LossDev hd,
+                                                            float *__restrict__ t_actions, float *__restrict__ t_logits,
+                                                            float *__restrict__ t_logp, float *__restrict__ t_values,
+                                                            float *__restrict__ t_version,
+                                                            int32_t *__restrict__ env_actions) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    sample_write_tuple_row<false>(logits + (int64_t)b * ldl, nullptr, values, ldv, b, A, T, t, seed, step, row0, version,
+                                  deterministic, hd, t_actions, t_logits, t_logp, t_values, t_version, env_actions);
+}
+
+__global__ __launch_bounds__(256) void k_sample_write_masked_tuple(const float *__restrict__ logits, int ldl,
+                                                                   const float *__restrict__ values, int ldv,
+                                                                   const uint8_t *__restrict__ mask, int64_t ldm, int B,
+                                                                   int A, int T, int t, uint32_t seed, uint32_t step,
+                                                                   uint32_t row0, float version, int deterministic,
+                                                                   LossDev hd, float *__restrict__ t_actions,
+                                                                   float *__restrict__ t_logits, float *__restrict__ t_logp,
+                                                                   float *__restrict__ t_values,
+                                                                   float *__restrict__ t_version,
+                                                                   int32_t *__restrict__ env_actions) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    sample_write_tuple_row<true>(logits + (int64_t)b * ldl, mask + (int64_t)b * ldm, values, ldv, b, A, T, t, seed, step,
+                                 row0, version, deterministic, hd, t_actions, t_logits, t_logp, t_values, t_version,
+                                 env_actions);
 }
 
 extern "C" int sf_sample_write_step_tuple(const float *logits, int ld_logits, const float *values, int ld_values, int B,
@@ -2488,6 +2560,46 @@ extern "C" int sf_sample_write_step_tuple(const float *logits, int ld_logits, co
         logits, ld_logits, values, ld_values, B, A, T, t, seed, step, row0, policy_version, deterministic, hd,
         traj_actions, traj_logits, traj_logp, traj_values, traj_policy_version, env_actions);
     return sf_launch_status("sf_sample_write_step_tuple");
+}
+
+// sf_sample_write_step_tuple under obs["action_mask"]: u8 [B, A], one column per distribution parameter
+extern "C" int sf_sample_write_step_tuple_masked(const float *logits, int ld_logits, const float *values, int ld_values,
+                                                 const uint8_t *action_mask, int64_t ld_mask, int B, int num_heads,
+                                                 const int32_t *head_n, int T, int t, uint32_t seed, uint32_t step,
+                                                 uint32_t row0, float policy_version, int deterministic,
+                                                 float *traj_actions, float *traj_logits, float *traj_logp,
+                                                 float *traj_values, float *traj_policy_version, int32_t *env_actions,
+                                                 void *stream) {
+    SF_REQUIRE(action_mask, "sf_sample_write_step_tuple_masked: null action_mask");
+    SF_REQUIRE(logits && values && head_n && traj_actions && traj_logits && traj_logp && traj_values &&
+                   traj_policy_version, "sf_sample_write_step_tuple_masked: null pointer");
+    SF_REQUIRE(B > 0 && T > 0 && t >= 0 && t < T,
+               "sf_sample_write_step_tuple_masked: bad shape heads=%d B=%d T=%d t=%d", num_heads, B, T, t);
+    LossDev hd = {};
+    bool any_box;
+    const int A = heads_from_host("sf_sample_write_step_tuple_masked", head_n, num_heads, SF_MAX_ACTION_HEADS, hd.head_n,
+                                  &any_box);
+    if (A < 0) return SF_ERR_ARG;
+    hd.num_heads = num_heads;
+    SF_REQUIRE(!any_box || !env_actions,
+               "sf_sample_write_step_tuple_masked: a tuple with a Box member has no int32 env_actions (the env reads the "
+               "trajectory's f32 action row)");
+    SF_REQUIRE(ld_mask >= A, "sf_sample_write_step_tuple_masked: ld_mask=%lld, the mask has one column per distribution "
+               "parameter (A=%d)", (long long)ld_mask, A);
+    SF_REQUIRE(ld_logits >= A && ld_values >= 1, "sf_sample_write_step_tuple_masked: bad strides");
+    if (A >= WIDE_MIN_A) {
+        HeadsDev whd = {};
+        whd.num_heads = num_heads;
+        for (int i = 0; i < num_heads; ++i) whd.head_n[i] = head_n[i];
+        return sample_write_wide_launch("sf_sample_write_step_tuple_masked", logits, ld_logits, values, ld_values,
+                                        action_mask, ld_mask, B, A, T, t, seed, step, row0, policy_version, deterministic,
+                                        whd, traj_actions, traj_logits, traj_logp, traj_values, traj_policy_version,
+                                        env_actions, stream);
+    }
+    k_sample_write_masked_tuple<<<dim3((unsigned)((B + 255) / 256)), dim3(256), 0, STREAM(stream)>>>(
+        logits, ld_logits, values, ld_values, action_mask, ld_mask, B, A, T, t, seed, step, row0, policy_version,
+        deterministic, hd, traj_actions, traj_logits, traj_logp, traj_values, traj_policy_version, env_actions);
+    return sf_launch_status("sf_sample_write_step_tuple_masked");
 }
 
 // =========================================================================================== K1/K6 env step -> traj

@@ -265,6 +265,64 @@ def make_masked_bandit_env(full_env_name, cfg=None, env_config=None, render_mode
     return MaskedBanditEnv(num_agents=n, num_actions=a, seed=(getattr(cfg, "seed", None) or 0) if cfg is not None else 0)
 
 
+class MaskedTupleBanditEnv:
+    """MaskedBanditEnv on Tuple(Discrete(n_0), Discrete(n_1), ...): obs = the members' rewarded actions as one-hots side
+    by side, obs["action_mask"] u8 [N, sum n_i] with one column per distribution parameter (member i owns the columns
+    under its own logits).  A member's rewarded action is always allowed and a random half of its other actions is masked
+    out; the reward is the fraction of members that took their rewarded action."""
+
+    def __init__(self, num_agents=64, head_sizes=(4, 3), seed=0, device="cuda"):
+        self.num_agents, self.head_sizes = int(num_agents), tuple(int(n) for n in head_sizes)
+        assert len(self.head_sizes) > 1 and all(n > 0 for n in self.head_sizes), "a Tuple of Discrete members"
+        self.A = sum(self.head_sizes)
+        self.observation_space = spaces.Dict({"obs": spaces.Box(0, 1, (self.A,), np.float32),
+                                              "action_mask": spaces.Box(0, 1, (self.A,), np.uint8)})
+        self.action_space = spaces.Tuple([spaces.Discrete(n) for n in self.head_sizes])
+        self.device = torch.device(device)
+        self.gen = torch.Generator(device=self.device)
+        self.gen.manual_seed(int(seed))
+        self._rows = torch.arange(self.num_agents, device=self.device)
+        self.last_allowed = None  # [N, members] bool: was member i's action of the last step allowed by its mask
+        self._draw()
+
+    def _draw(self):
+        N = self.num_agents
+        self.target = torch.stack([torch.randint(0, n, (N,), generator=self.gen, device=self.device)
+                                   for n in self.head_sizes], 1)
+        self.mask = torch.rand((N, self.A), generator=self.gen, device=self.device) < 0.5
+        obs, off = torch.zeros((N, self.A), device=self.device), 0
+        for i, n in enumerate(self.head_sizes):
+            self.mask[self._rows, off + self.target[:, i]] = True
+            obs[self._rows, off + self.target[:, i]] = 1.0
+            off += n
+        self.obs = obs
+
+    def _out(self):
+        return {"obs": self.obs, "action_mask": self.mask.to(torch.uint8)}
+
+    def reset(self, **kwargs):
+        self._draw()
+        return self._out(), {}
+
+    def step(self, actions):
+        a = torch.as_tensor(actions, device=self.device).reshape(self.num_agents, len(self.head_sizes)).long()
+        offs = torch.tensor([sum(self.head_sizes[:i]) for i in range(len(self.head_sizes))], device=self.device)
+        self.last_allowed = self.mask.gather(1, a + offs).clone()
+        rew = (a == self.target).float().mean(1)
+        term = torch.ones(self.num_agents, dtype=torch.bool, device=self.device)  # one-step episodes, auto-reset
+        self._draw()
+        return self._out(), rew, term, torch.zeros_like(term), {}
+
+    def close(self):
+        pass
+
+
+def make_masked_tuple_bandit_env(full_env_name, cfg=None, env_config=None, render_mode=None):
+    n = getattr(cfg, "synthetic_num_agents", 64) if cfg is not None else 64
+    hs = tuple(getattr(cfg, "synthetic_head_sizes", None) or (4, 3)) if cfg is not None else (4, 3)
+    return MaskedTupleBanditEnv(num_agents=n, head_sizes=hs, seed=(getattr(cfg, "seed", None) or 0) if cfg is not None else 0)
+
+
 def make_synthetic_tuple_env(full_env_name, cfg=None, env_config=None, render_mode=None):
     n = getattr(cfg, "synthetic_num_agents", 4096) if cfg is not None else 4096
     seed = (getattr(cfg, "seed", None) or 0) if cfg is not None else 0

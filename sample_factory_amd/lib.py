@@ -51,7 +51,8 @@ SYMBOLS = [
     "sf_rms_apply", "sf_vtrace", "sf_ppo_loss", "sf_ppo_loss_heads", "sf_loss_scalars", "sf_train_summaries", "sf_minibatch_indices", "sf_minibatch_expand", "sf_grad_sumsq",
     "sf_adam_step", "sf_adam_step_dlr", "sf_lr_kl_adaptive", "sf_clock_probe", "sf_lamb_step", "sf_rnn_cell_fwd", "sf_rnn_cell_bwd", "sf_rows_add_scale", "sf_mlp2_fwd", "sf_rnn_store_state", "sf_rnn_chunk_setup", "sf_lstm_seq_supported", "sf_lstm_seq_fwd", "sf_lstm_seq_bwd", "sf_gru_seq_fwd", "sf_gru_seq_bwd", "sf_seq_fwd_x_supported", "sf_lstm_seq_fwd_x", "sf_gru_seq_fwd_x", "sf_rnn_rowseq_supported", "sf_rnn_rowseq_fwd", "sf_rnn_rowseq_bwd", "sf_rnn_wideseq_supported", "sf_rnn_seq_slab_rows", "sf_rnn_wideseq_fwd", "sf_rnn_wideseq_bwd", "sf_linear_fwd_dual_supported", "sf_linear_fwd_dual",
     "sf_obsnorm_moments", "sf_obsnorm_update", "sf_obsnorm_apply", "sf_sample_write_step",
-    "sf_sample_write_step_tuple", "sf_sample_write_step_masked", "sf_traj_write_env_step", "sf_synth_obs",
+    "sf_sample_write_step_tuple", "sf_sample_write_step_masked", "sf_sample_write_step_tuple_masked",
+    "sf_traj_write_env_step", "sf_synth_obs",
     "sf_synth_step", "sf_synth_vec_step", "sf_h2d_rows", "sf_copy_rows", "sf_conv_fwd", "sf_conv_fwd_workspace", "sf_conv_wgrad_workspace", "sf_conv_wgrad",
     "sf_conv_dgrad", "sf_conv_norm_supported", "sf_conv_fwd_norm", "sf_conv_wgrad_norm", "sf_conv_relu_mask_supported", "sf_conv_fwd_relu_mask", "sf_conv_wgrad_relu_mask", "sf_conv_kernel_name", "sf_conv_fwd_t_supported", "sf_conv_fwd_t_workspace", "sf_conv_fwd_t", "sf_transpose",
     "sf_conv_fwd_os_supported", "sf_conv_fwd_relu_mask_os", "sf_conv_fwd_t_os",
@@ -763,6 +764,26 @@ def sample_write_step_tuple(logits, ld_logits, values, ld_values, B, head_n, T, 
                                              ptr(traj_logp, "f32"), ptr(traj_values, "f32"),
                                              ptr(traj_policy_version, "f32"), ptr(env_actions, "i32"), stream()),
            "sf_sample_write_step_tuple")
+
+
+def sample_write_step_tuple_masked(logits, ld_logits, values, ld_values, mask, ld_mask, B, head_n, T, t, seed, step, row0,
+                                   policy_version, deterministic, traj_actions, traj_logits, traj_logp, traj_values,
+                                   traj_policy_version, env_actions) -> None:
+    """Tuple space under an action mask.  mask: u8/bool [B, A] view with row stride ld_mask, one column per distribution
+    parameter (a Discrete member reads the slice at its own logits offset; the columns under a Box member are ignored);
+    env_actions int32 [B, len(head_n)], None when a member is a Box"""
+    if mask.dtype not in (torch.uint8, torch.bool) or not mask.is_cuda:
+        raise SfHipError(f"action_mask: expected a u8/bool CUDA tensor, got {mask.dtype} on {mask.device}")
+    hn = _head_array(head_n)
+    _check(load().sf_sample_write_step_tuple_masked(_raw(logits, "f32", "logits"), int(ld_logits),
+                                                    _raw(values, "f32", "values"), int(ld_values),
+                                                    _vp(mask), i64(ld_mask), int(B), len(head_n), hn, int(T), int(t),
+                                                    u32(seed), u32(step), u32(row0), f(policy_version),
+                                                    int(bool(deterministic)), ptr(traj_actions, "f32"),
+                                                    ptr(traj_logits, "f32"), ptr(traj_logp, "f32"),
+                                                    ptr(traj_values, "f32"), ptr(traj_policy_version, "f32"),
+                                                    ptr(env_actions, "i32"), stream()),
+           "sf_sample_write_step_tuple_masked")
 
 
 def traj_write_env_step(rewards, terminated, truncated, T, t, reward_scale, reward_clip, policy_id, traj_rewards,
