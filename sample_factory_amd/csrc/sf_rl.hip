@@ -284,19 +284,169 @@ extern "C" int sf_rms_apply(float *x, int64_t n, const double *stats, int denorm
 }
 
 // =========================================================================================== action distributions
+// The arithmetic of one column of a member, shared by V-trace, the PPO loss and the samplers.  Every
+// helper is inlined and keeps one operation order, so all its callers round alike; the column loop stays in the caller:
+// a lane-per-row kernel walks k = 0 .. D, a wave-per-row kernel k = lane, lane + 64, .. and sums over the wave after.
+struct HeadsDev {
+    int num_heads, head_n[SF_MAX_ACTION_HEADS];  // a kernel argument (260 bytes); the launchers check num_heads
+};
+struct LossDev {
+    float clip_lo, clip_hi, clip_value, value_coeff, expl_coeff, kl_coeff;
+    int expl_kind, action_kind, dense_adv;
+    HeadsDev hd;
+    int ov_T;  // > 0: old_values is the slab's [E, ov_T + 1] array read in place (dataset row e*T+t -> e*(T+1)+t)
+};
+constexpr float HALF_LOG_2PI = 0.91893853320467274178f;
+
+// Box(D) member, parameters [means | log_std]: the standard deviation of a column, the Normal log-density of an action
+__device__ __forceinline__ float box_sd(float zlog) { return clampf(expf(zlog), 1e-4f, 1e4f); }
+__device__ __forceinline__ float box_logp(float a, float mu, float sd) {
+    return -((a - mu) * (a - mu)) / (2.f * (sd * sd)) - logf(sd) - HALF_LOG_2PI;
+}
+// column k of a Box(D) member in the loss: adds its log-prob, entropy and KL(current || old) to the three sums
+__device__ __forceinline__ void box_loss_terms(const float *__restrict__ z, const float *__restrict__ zo,
+                                               const float *__restrict__ act, int D, int k, float &lp, float &ent,
+                                               float &kl) {
+    const float mu = z[k], sd = box_sd(z[D + k]);
+    lp += box_logp(act[k], mu, sd);
+    ent += 0.5f + HALF_LOG_2PI + logf(sd);
+    const float muo = zo[k], sdo = box_sd(zo[D + k]);
+    const float vr = (sd / sdo) * (sd / sdo);
+    const float t1 = ((mu - muo) / sdo) * ((mu - muo) / sdo);
+    kl += 0.5f * (vr + t1 - 1.f - logf(vr));
+}
+// ... and its gradient: gz[k] (mean) and gz[D + k] (log_std; zero where exp(log_std) is beyond the clamp)
+__device__ __forceinline__ void box_grad(const float *__restrict__ z, const float *__restrict__ zo,
+                                         const float *__restrict__ act, int D, int k, float dL_dlogp, float inv_n,
+                                         const LossDev &h, float *__restrict__ gz) {
+    const float mu = z[k], e = expf(z[D + k]);
+    const float sd = clampf(e, 1e-4f, 1e4f);
+    const float dsd = (e >= 1e-4f && e <= 1e4f) ? e : 0.f;
+    const float a = act[k];
+    const float var = sd * sd;
+    float gmu = dL_dlogp * ((a - mu) / var);
+    float gsd = dL_dlogp * (((a - mu) * (a - mu)) / (var * sd) - 1.f / sd);
+    if (h.expl_kind == 1) gsd += -h.expl_coeff * inv_n * (1.f / sd);
+    if (h.kl_coeff != 0.f) {
+        const float muo = zo[k], sdo = box_sd(zo[D + k]);
+        gmu += h.kl_coeff * inv_n * ((mu - muo) / (sdo * sdo));
+        gsd += h.kl_coeff * inv_n * (sd / (sdo * sdo) - 1.f / sd);
+    }
+    gz[k] = gmu;
+    gz[D + k] = gsd * dsd;
+}
+// the standard normal a sampler draws for column k of Box member h: Box-Muller on Philox counter (step, k / 2, 3, h),
+// two columns per counter
+__device__ __forceinline__ float box_eps(uint32_t step, int k, int h, uint32_t seed, uint32_t row) {
+    uint32_t w[4];
+    sf_philox4x32_10(step, (uint32_t)(k >> 1), 3u, (uint32_t)h, seed, row, w);
+    const uint32_t w1 = (k & 1) ? w[2] : w[0], w2 = (k & 1) ? w[3] : w[1];
+    const float u1 = ((float)(w1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float u2 = (float)(w2 >> 8) * (1.0f / 16777216.0f);
+    return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+}
+// the uniform in [0, 1) a sampler draws Discrete member h from: Philox counter (step, h, 2, 0)
+__device__ __forceinline__ float cat_uniform(uint32_t step, int h, uint32_t seed, uint32_t row) {
+    uint32_t w[4];
+    sf_philox4x32_10(step, (uint32_t)h, 2u, 0u, seed, row, w);
+    return (float)(w[0] >> 8) * (1.0f / 16777216.0f);
+}
+
+// Discrete(nh) member read in place, one lane per row: maximum and log-sum-exp of its logits
+__device__ __forceinline__ void cat_lse(const float *__restrict__ z, int nh, float &mx, float &lse) {
+    mx = -INFINITY;
+    for (int k = 0; k < nh; ++k) mx = fmaxf(mx, z[k]);
+    float se = 0.f;
+    for (int k = 0; k < nh; ++k) se += expf(z[k] - mx);
+    lse = logf(se);
+}
+// Discrete(nh) member in the loss, one lane per row: softmax statistics of the current and the old logits, entropy, KL,
+// KL(p || uniform) (klpu), its mirror sum u * (lu - lp) (a2) and the log-prob of `act` (lpa)
+struct CatTerms {
+    float mx, lse, mxo, lseo, ent, kl, klpu, a2, lpa;
+};
+__device__ __forceinline__ CatTerms cat_terms(const float *__restrict__ z, const float *__restrict__ zo, int nh, int act) {
+    CatTerms t;
+    float m1 = -INFINITY, m2 = -INFINITY;
+    for (int k = 0; k < nh; ++k) { m1 = fmaxf(m1, z[k]); m2 = fmaxf(m2, zo[k]); }
+    float s1 = 0.f, s2 = 0.f;
+    for (int k = 0; k < nh; ++k) { s1 += expf(z[k] - m1); s2 += expf(zo[k] - m2); }
+    t.mx = m1; t.lse = logf(s1); t.mxo = m2; t.lseo = logf(s2);
+    const float u = 1.0f / (float)nh, lu = logf(u);
+    float lpa = 0.f, e = 0.f, kk = 0.f, a1 = 0.f, a2 = 0.f;
+    for (int k = 0; k < nh; ++k) {
+        const float lp = (z[k] - m1) - t.lse, p = expf(lp), q = (zo[k] - m2) - t.lseo;
+        if (k == act) lpa = lp;
+        e -= p * lp;
+        kk += p * (lp - q);
+        a1 += p * (lp - lu);
+        a2 += u * (lu - lp);
+    }
+    t.ent = e; t.kl = kk; t.klpu = a1; t.a2 = a2; t.lpa = lpa;
+    return t;
+}
+// gradient of one column of a Discrete(nh) member (zk / zok: its current and old logit, the old one read only when the
+// KL term is on; taken: it is the recorded action; u = 1 / nh, lu = log u), from the member's seven statistics
+__device__ __forceinline__ float cat_grad(float zk, float zok, bool taken, float mx, float lse, float mxo, float lseo,
+                                          float ent, float kl, float klpu, float u, float lu, float dL_dlogp, float inv_n,
+                                          float symkl_gate, const LossDev &h) {
+    const float lp = (zk - mx) - lse, p = expf(lp), q = (zok - mxo) - lseo;
+    float gk = dL_dlogp * ((taken ? 1.f : 0.f) - p);
+    if (h.expl_kind == 1) gk += h.expl_coeff * inv_n * (p * (lp + ent));
+    if (h.expl_kind == 2) gk += symkl_gate * h.expl_coeff * inv_n * 0.5f * (p * ((lp - lu) - klpu) + p - u);
+    if (h.kl_coeff != 0.f) gk += h.kl_coeff * inv_n * (p * ((lp - q) - kl));
+    return gk;
+}
+
+// Discrete(A), A <= MAXA, held in registers: the row into zz (-inf beyond A), its maximum and log-sum-exp.  MAXA bounds
+// the unrolled loops, so no array is indexed dynamically.
+template <int MAXA>
+__device__ __forceinline__ void reg_softmax(const float *__restrict__ z, int A, float (&zz)[MAXA], float &mx, float &lse) {
+    mx = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < MAXA; ++k) { zz[k] = k < A ? z[k] : -INFINITY; mx = fmaxf(mx, zz[k]); }
+    float se = 0.f;
+#pragma unroll
+    for (int k = 0; k < MAXA; ++k) if (k < A) se += expf(zz[k] - mx);
+    lse = logf(se);
+}
+
+// Discrete(n) under an action mask (the rule above k_sample_write_masked), one lane per row: softmax statistics of the
+// logits with -1e9 on the masked-out columns, the allowed probability mass, 1 / (mass + 1e-13) and the total of the
+// weights masked_p gives (multinomial normalises its weights)
+struct MaskedStats {
+    float mx, lse, psum, inv, tot;
+    bool all_zero;
+};
+__device__ __forceinline__ MaskedStats masked_stats(const float *__restrict__ z, const uint8_t *__restrict__ mk, int n) {
+    MaskedStats s;
+    s.mx = -INFINITY;
+    for (int k = 0; k < n; ++k) s.mx = fmaxf(s.mx, z[k] + (mk[k] ? 0.f : -1e9f));
+    float se = 0.f;
+    for (int k = 0; k < n; ++k) se += expf((z[k] + (mk[k] ? 0.f : -1e9f)) - s.mx);
+    s.lse = logf(se);
+    s.psum = 0.f;
+    for (int k = 0; k < n; ++k) s.psum += mk[k] ? expf((z[k] - s.mx) - s.lse) : 0.f;
+    s.all_zero = s.psum == 0.f;
+    s.inv = 1.0f / (s.psum + 1e-13f);
+    s.tot = s.all_zero ? (float)n * 1e-6f : s.psum * s.inv;
+    return s;
+}
+// weight of a column before multinomial's normalisation (an all-masked member: n weights of 1e-6), and its log-prob
+__device__ __forceinline__ float masked_p(const MaskedStats &s, float zk, uint8_t allowed) {
+    return s.all_zero ? 1e-6f : (allowed ? expf((zk - s.mx) - s.lse) * s.inv : 0.f);
+}
+__device__ __forceinline__ float masked_logp(const MaskedStats &s, float zk, uint8_t allowed) {
+    return ((zk + (allowed ? 0.f : -1e9f)) - s.mx) - s.lse;
+}
+
 // log-prob of the taken action under the current policy, for one sample (used by v-trace and the loss head).
 template <int MAXA>
 __device__ __forceinline__ float action_logp(const float *__restrict__ z, int A, int action_kind,
                                              const float *__restrict__ act_row) {
     if (action_kind == 0) {
-        float zz[MAXA];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int k = 0; k < MAXA; ++k) { zz[k] = k < A ? z[k] : -INFINITY; mx = fmaxf(mx, zz[k]); }
-        float se = 0.f;
-#pragma unroll
-        for (int k = 0; k < MAXA; ++k) if (k < A) se += expf(zz[k] - mx);
-        const float lse = logf(se);
+        float zz[MAXA], mx, lse;
+        reg_softmax<MAXA>(z, A, zz, mx, lse);
         const int a = (int)act_row[0];
         float r = 0.f;
 #pragma unroll
@@ -305,19 +455,12 @@ __device__ __forceinline__ float action_logp(const float *__restrict__ z, int A,
     } else {
         const int D = A / 2;
         float r = 0.f;
-        for (int k = 0; k < D; ++k) {
-            const float mu = z[k], sd = clampf(expf(z[D + k]), 1e-4f, 1e4f);
-            const float a = act_row[k];
-            r += -((a - mu) * (a - mu)) / (2.f * (sd * sd)) - logf(sd) - 0.91893853320467274178f;
-        }
+        for (int k = 0; k < D; ++k) r += box_logp(act_row[k], z[k], box_sd(z[D + k]));
         return r;
     }
 }
 
 // =========================================================================================== K17 V-trace
-struct HeadsDev {
-    int num_heads, head_n[SF_MAX_ACTION_HEADS];  // a kernel argument (260 bytes); the launchers check num_heads
-};
 // A head list as the entry points receive it (host array): 1 .. cap members, none empty.  Fills `out`, returns the number
 // of parameters the members read, or -1 with the reason in sf_err_buf (`what` names the entry point).  Nothing is
 // launched with a list this has not passed: the kernels index head_n with num_heads unchecked.
@@ -356,19 +499,13 @@ __device__ __forceinline__ float tuple_logp(const float *__restrict__ z, const f
         const int nh = hd.head_n[h];
         if (nh < 0) {
             const int D = -nh;
-            for (int k = 0; k < D; ++k) {
-                const float mu = z[off + k], sd = clampf(expf(z[off + D + k]), 1e-4f, 1e4f);
-                const float a = act[aoff + k];
-                lp += -((a - mu) * (a - mu)) / (2.f * (sd * sd)) - logf(sd) - 0.91893853320467274178f;
-            }
+            for (int k = 0; k < D; ++k) lp += box_logp(act[aoff + k], z[off + k], box_sd(z[off + D + k]));
             off += 2 * D; aoff += D;
             continue;
         }
-        float mx = -INFINITY;
-        for (int k = 0; k < nh; ++k) mx = fmaxf(mx, z[off + k]);
-        float se = 0.f;
-        for (int k = 0; k < nh; ++k) se += expf(z[off + k] - mx);
-        lp += (z[off + (int)act[aoff]] - mx) - logf(se);
+        float mx, lse;
+        cat_lse(z + off, nh, mx, lse);
+        lp += (z[off + (int)act[aoff]] - mx) - lse;
         off += nh; aoff += 1;
     }
     return lp;
@@ -425,7 +562,7 @@ __device__ __forceinline__ void wide_lse(const float *__restrict__ z, int nh, in
     wide_finish(m, s, mx, lse);
 }
 // a single Discrete(A) / Box(A / 2) as a one-member head list
-static HeadsDev wide_single_head(int A, int action_kind) {
+static HeadsDev single_head(int A, int action_kind) {
     HeadsDev hd = {};
     hd.num_heads = 1;
     hd.head_n[0] = action_kind == 0 ? A : -(A / 2);
@@ -451,11 +588,7 @@ __global__ __launch_bounds__(256) void k_vtrace_ratio_wide(const float *__restri
         if (nh < 0) {
             const int D = -nh;
             float r = 0.f;
-            for (int j = lane; j < D; j += 64) {
-                const float mu = z[off + j], sd = clampf(expf(z[off + D + j]), 1e-4f, 1e4f);
-                const float a = act[aoff + j];
-                r += -((a - mu) * (a - mu)) / (2.f * (sd * sd)) - logf(sd) - 0.91893853320467274178f;
-            }
+            for (int j = lane; j < D; j += 64) r += box_logp(act[aoff + j], z[off + j], box_sd(z[off + D + j]));
             lp += wide_allsum(r);
             off += 2 * D; aoff += D;
             continue;
@@ -487,14 +620,11 @@ __global__ __launch_bounds__(256) void k_vtrace_ratio(const float *__restrict__ 
 
 // phase 2 (one lane per trajectory): the reverse recursion of learner.py:618-635; vs[k] holds the ratio of step k on
 // entry (read before it is overwritten with the result)
-template <int MAXA>
-__global__ __launch_bounds__(64) void k_vtrace(const float *__restrict__ params, int ldp,
-                                               const float *__restrict__ values, int ldv,
-                                               const float *__restrict__ actions, const float *__restrict__ old_logp,
+__global__ __launch_bounds__(64) void k_vtrace(const float *__restrict__ values, int ldv,
                                                const float *__restrict__ rewards, const uint8_t *__restrict__ dones,
-                                               const int32_t *__restrict__ index, int64_t offset, int64_t ntraj, int A,
-                                               int action_kind, int rec, float gamma, float rho_hat, float c_hat,
-                                               float *__restrict__ vs, float *__restrict__ adv, HeadsDev hd) {
+                                               const int32_t *__restrict__ index, int64_t offset, int64_t ntraj, int rec,
+                                               float gamma, float rho_hat, float c_hat, float *__restrict__ vs,
+                                               float *__restrict__ adv) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= ntraj) return;
     const int64_t base = j * rec;
@@ -541,38 +671,29 @@ extern "C" int sf_vtrace(const float *params, int ld_params, const float *values
     const int64_t ntraj = n / recurrence;
     if (ntraj == 0) return SF_OK;
     const dim3 grid((unsigned)((ntraj + 63) / 64)), block(64), rgrid((unsigned)((n + 255) / 256));
-    if (A >= WIDE_MIN_A) {  // wave-per-row ratio; the recursion does not depend on A
+#define VT_LAUNCH(M)                                                                                                   \
+    k_vtrace_ratio<M><<<rgrid, dim3(256), 0, STREAM(stream)>>>(params, ld_params, actions, old_logp, index, offset, n, A, \
+                                                               action_kind, vs, hd)
+    if (A >= WIDE_MIN_A) {  // wave-per-row ratio
         SF_REQUIRE((n + WIDE_ROWS - 1) / WIDE_ROWS <= 0x7fffffffLL, "sf_vtrace: n=%lld too large", (long long)n);
-        const HeadsDev whd = hd.num_heads > 1 ? hd : wide_single_head(A, action_kind);
         k_vtrace_ratio_wide<<<dim3((unsigned)((n + WIDE_ROWS - 1) / WIDE_ROWS)), dim3(256), 0, STREAM(stream)>>>(
-            params, ld_params, actions, old_logp, index, offset, n, vs, whd);
-        k_vtrace<128><<<grid, block, 0, STREAM(stream)>>>(params, ld_params, values, ld_values, actions, old_logp, rewards,
-                                                          dones, index, offset, ntraj, A, action_kind, recurrence, gamma,
-                                                          rho_hat, c_hat, vs, adv, hd);
-        return sf_launch_status("sf_vtrace");
-    }
-#define VT_LAUNCH(M)                                                                                             \
-    k_vtrace_ratio<M><<<rgrid, dim3(256), 0, STREAM(stream)>>>(params, ld_params, actions, old_logp, index, offset, n, A,   \
-                                                               action_kind, vs, hd);                              \
-    k_vtrace<M><<<grid, block, 0, STREAM(stream)>>>(params, ld_params, values, ld_values, actions, old_logp, rewards, dones, index,    \
-                                                    offset, ntraj, A, action_kind, recurrence, gamma, rho_hat,   \
-                                                    c_hat, vs, adv, hd)
-    if (A <= 8) { VT_LAUNCH(8); }
-    else if (A <= 32) { VT_LAUNCH(32); }
-    else { VT_LAUNCH(128); }
+            params, ld_params, actions, old_logp, index, offset, n, vs,
+            hd.num_heads > 1 ? hd : single_head(A, action_kind));
+    } else if (A <= 8) VT_LAUNCH(8);
+    else if (A <= 32) VT_LAUNCH(32);
+    else VT_LAUNCH(128);
 #undef VT_LAUNCH
+    // the recursion reads the ratios only: one kernel whatever the distribution is
+    k_vtrace<<<grid, block, 0, STREAM(stream)>>>(values, ld_values, rewards, dones, index, offset, ntraj, recurrence, gamma,
+                                                 rho_hat, c_hat, vs, adv);
     return sf_launch_status("sf_vtrace");
 }
 
 // =========================================================================================== K16 PPO loss fwd+bwd
 // One lane per sample; the per-sample distribution lives in registers (template MAXA bounds the unrolled loops so no
 // array is indexed dynamically).  Loss sums use wave shuffles -> LDS -> one double atomic per block per quantity.
-struct LossDev {
-    float clip_lo, clip_hi, clip_value, value_coeff, expl_coeff, kl_coeff;
-    int expl_kind, action_kind, dense_adv;
-    int num_heads, head_n[SF_MAX_ACTION_HEADS];
-    int ov_T;  // > 0: old_values is the slab's [E, ov_T + 1] array read in place (dataset row e*T+t -> e*(T+1)+t)
-};
+// The four loss kernels differ in how a row's distribution terms are laid out over lanes and registers; what comes
+// before (loss_prologue), between the forward terms and the gradient (loss_row) and after (loss_epilogue) is one code.
 __device__ __forceinline__ int64_t ov_row(const LossDev &h, int64_t d) {
     if (h.ov_T <= 0) return d;
     const int64_t e = d / h.ov_T;
@@ -591,6 +712,82 @@ __device__ __forceinline__ void atomic_max_float(double *addr, float v) {
     } while (assumed != old);
 }
 
+// global (all-reduced) advantage moments {sum, sum of squares, count} -> mean / unbiased variance, learner.py:646-647
+__device__ __forceinline__ void adv_mean_var(const double *__restrict__ moments, double &mean64, double &var64) {
+    const double mn = moments[2];
+    mean64 = moments[0] / mn;
+    var64 = (moments[1] - moments[0] * mean64) / (mn - 1.0);
+}
+struct LossPre {
+    float adv_mean, denom, inv_n, symkl_gate;
+};
+// gated: the symmetric-KL exploration loss is selected and this is not its pre-pass.  Its clamp(max=30) / non-finite
+// gate needs the MEAN, which a pre-pass leaves in sums[6] (see ppo_loss_launch); otherwise the gate is open.
+__device__ __forceinline__ LossPre loss_prologue(const double *__restrict__ moments, const double *__restrict__ sums,
+                                                 bool gated) {
+    double mean64, var64;
+    adv_mean_var(moments, mean64, var64);
+    const double mn = moments[2];
+    LossPre p;
+    p.adv_mean = (float)mean64;
+    const float adv_std = (float)sqrt(var64 > 0.0 ? var64 : (mn > 1.0 ? 0.0 : NAN));
+    p.denom = fmaxf(adv_std, 1e-7f);
+    p.inv_n = 1.0f / (float)mn;
+    p.symkl_gate = gated ? (float)sums[6] : 1.0f;
+    return p;
+}
+
+// Clipped surrogate and clipped value loss of one row with their derivatives (autograd semantics of min / max ties and
+// clamp boundaries).  dlogp = logp - old_logp as the caller formed it (float, or rounded from a double sum).
+struct LossRow {
+    float ratio, raw_ratio, pl, vl, dL_dlogp, dvl;
+};
+__device__ __forceinline__ LossRow loss_row(float dlogp, float adv, float v, float vo, float R, const LossPre &p,
+                                            const LossDev &h) {
+    LossRow r;
+    r.raw_ratio = expf(dlogp);
+    r.ratio = clampf(r.raw_ratio, 0.05f, 20.0f);
+    const float advn = (adv - p.adv_mean) / p.denom;
+    const float clipped = clampf(r.ratio, h.clip_lo, h.clip_hi);
+    const float lu_ = r.ratio * advn, lc_ = clipped * advn;
+    r.pl = fminf(lu_, lc_);
+    const float vclip = vo + clampf(v - vo, -h.clip_value, h.clip_value);
+    const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
+    r.vl = fmaxf(l1, l2);
+    float dpl_dr;
+    const bool in_clip = r.ratio >= h.clip_lo && r.ratio <= h.clip_hi;
+    if (lu_ < lc_) dpl_dr = advn;
+    else if (lu_ > lc_) dpl_dr = in_clip ? advn : 0.f;
+    else dpl_dr = 0.5f * advn + (in_clip ? 0.5f * advn : 0.f);
+    const bool in_hard = r.raw_ratio >= 0.05f && r.raw_ratio <= 20.0f;
+    r.dL_dlogp = in_hard ? (-p.inv_n) * dpl_dr * r.raw_ratio : 0.f;
+    const bool in_v = (v - vo) >= -h.clip_value && (v - vo) <= h.clip_value;
+    if (l1 > l2) r.dvl = 2.f * (v - R);
+    else if (l2 > l1) r.dvl = in_v ? 2.f * (vclip - R) : 0.f;
+    else r.dvl = (v - R) + (in_v ? (vclip - R) : 0.f);
+    return r;
+}
+
+// block reduction of a 256-thread block's sums {policy, exploration, KL, value} and of its largest KL into sums[0..4];
+// sym_pass: acc[0] is the symmetric-KL sum of the pre-pass, into sums[7]
+__device__ __forceinline__ void loss_epilogue(double (&acc)[4], float kl_max, double *__restrict__ sums, int sym_pass) {
+    __shared__ double lds[4 * 4];
+    __shared__ float lds_max[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    kl_max = sf_wave_max(kl_max);
+    if (lane == 0) lds_max[wave] = kl_max;
+    sf_block_sum<4>(acc, lds);  // contains a __syncthreads()
+    if (threadIdx.x == 0) {
+        if (sym_pass) { atomicAdd(&sums[7], acc[0]); return; }
+        atomicAdd(&sums[0], acc[0]);
+        atomicAdd(&sums[1], acc[1]);
+        atomicAdd(&sums[2], acc[2]);
+        atomicAdd(&sums[3], acc[3]);
+        const float m = fmaxf(fmaxf(lds_max[0], lds_max[1]), fmaxf(lds_max[2], lds_max[3]));
+        if (m > -1.0f) atomic_max_float(&sums[4], m);
+    }
+}
+
 template <int MAXA>
 __global__ __launch_bounds__(256) void k_ppo_loss(const float *__restrict__ params, int ldp,
                                                   const float *__restrict__ values, int ldv,
@@ -604,27 +801,14 @@ __global__ __launch_bounds__(256) void k_ppo_loss(const float *__restrict__ para
                                                   LossDev h, const double *__restrict__ moments,
                                                   double *__restrict__ sums, float *__restrict__ g_params,
                                                   float *__restrict__ g_values, float *__restrict__ ratio_out) {
-    __shared__ double lds[4 * 4];
-    __shared__ float lds_max[4];
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    // global (all-reduced) advantage moments -> mean / unbiased std, learner.py:646-647
-    const double mn = moments[2];
-    const double mean64 = moments[0] / mn;
-    const double var64 = (moments[1] - moments[0] * mean64) / (mn - 1.0);
-    const float adv_mean = (float)mean64;
-    const float adv_std = (float)sqrt(var64 > 0.0 ? var64 : (mn > 1.0 ? 0.0 : NAN));
-    const float denom = fmaxf(adv_std, 1e-7f);
-    const float inv_n = 1.0f / (float)mn;
-    // symmetric-KL exploration: clamp(max=30) / non-finite gate need the MEAN; it is passed through moments-like
-    // slot sums[6] by a pre-pass only when that loss is selected (see sf_ppo_loss); gate defaults to open.
-    const float symkl_gate = (h.expl_kind == 2) ? (float)sums[6] : 1.0f;
-
+    const LossPre p = loss_prologue(moments, sums, h.expl_kind == 2);
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     float kl_max = -1.0f;
     if (i < n) {
         const int64_t d = index ? (int64_t)index[i] : offset + i;
         const bool valid = valids[d] != 0;
-        const float *z = params + i * ldp;
+        const float *z = params + i * ldp, *zold = old_params + d * A;
         float *gz = g_params + i * ldp;
         float logp_a = 0.f, ent = 0.f, kl = 0.f, symkl = 0.f;
         const int D = A / 2;
@@ -632,10 +816,11 @@ __global__ __launch_bounds__(256) void k_ppo_loss(const float *__restrict__ para
         float mx = -INFINITY, mxo = -INFINITY, lse = 0.f, lseo = 0.f;
         int act = 0;
         if (h.action_kind == 0) {
+            // (reg_softmax twice, with the two rows' loops fused: two separate passes at MAXA = 128 go to scratch)
 #pragma unroll
             for (int k = 0; k < MAXA; ++k) {
                 zz[k] = k < A ? z[k] : -INFINITY;
-                zo[k] = k < A ? old_params[d * A + k] : -INFINITY;
+                zo[k] = k < A ? zold[k] : -INFINITY;
                 mx = fmaxf(mx, zz[k]);
                 mxo = fmaxf(mxo, zo[k]);
             }
@@ -651,53 +836,27 @@ __global__ __launch_bounds__(256) void k_ppo_loss(const float *__restrict__ para
 #pragma unroll
             for (int k = 0; k < MAXA; ++k)
                 if (k < A) {
-                    const float lp = (zz[k] - mx) - lse, p = expf(lp), q = (zo[k] - mxo) - lseo;
+                    const float lp = (zz[k] - mx) - lse, p_ = expf(lp), q = (zo[k] - mxo) - lseo;
                     if (k == act) logp_a = lp;
-                    ent -= p * lp;
-                    kl += p * (lp - q);
-                    a1 += p * (lp - lu);
+                    ent -= p_ * lp;
+                    kl += p_ * (lp - q);
+                    a1 += p_ * (lp - lu);
                     a2 += u * (lu - lp);
                 }
             symkl = 0.5f * (a1 + a2);
         } else {
-            for (int k = 0; k < D; ++k) {
-                const float mu = z[k], sd = clampf(expf(z[D + k]), 1e-4f, 1e4f);
-                const float a = actions[d * D + k];
-                const float var = sd * sd;
-                logp_a += -((a - mu) * (a - mu)) / (2.f * var) - logf(sd) - 0.91893853320467274178f;
-                ent += 0.5f + 0.91893853320467274178f + logf(sd);
-                const float muo = old_params[d * A + k], sdo = clampf(expf(old_params[d * A + D + k]), 1e-4f, 1e4f);
-                const float vr = (sd / sdo) * (sd / sdo);
-                const float t1 = ((mu - muo) / sdo) * ((mu - muo) / sdo);
-                kl += 0.5f * (vr + t1 - 1.f - logf(vr));
-            }
+            for (int k = 0; k < D; ++k) box_loss_terms(z, zold, actions + d * D, D, k, logp_a, ent, kl);
         }
-        const float raw_ratio = expf(logp_a - old_logp[d]);
-        const float ratio = clampf(raw_ratio, 0.05f, 20.0f);
-        if (ratio_out) ratio_out[i] = ratio;  // summaries (learner.py:886-903)
         const int64_t da = h.dense_adv ? i : d;
-        const float advn = (adv[da] - adv_mean) / denom;
-        const float clipped = clampf(ratio, h.clip_lo, h.clip_hi);
-        const float lu_ = ratio * advn, lc_ = clipped * advn;
-        const float pl = fminf(lu_, lc_);
-        const float v = values[i * ldv], vo = old_values[ov_row(h, d)], R = targets[da];
-        const float vclip = vo + clampf(v - vo, -h.clip_value, h.clip_value);
-        const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
-        const float vl = fmaxf(l1, l2);
+        const LossRow r = loss_row(logp_a - old_logp[d], adv[da], values[i * ldv], old_values[ov_row(h, d)], targets[da],
+                                   p, h);
+        if (ratio_out) ratio_out[i] = r.ratio;  // summaries (learner.py:886-903)
         if (valid) {
-            acc[0] = pl;
+            acc[0] = r.pl;
             acc[1] = (h.expl_kind == 2) ? symkl : ent;
             acc[2] = kl;
-            acc[3] = vl;
+            acc[3] = r.vl;
             kl_max = kl;
-            // ---------------- backward (autograd semantics of min/max ties and clamp boundaries)
-            float dpl_dr;
-            const bool in_clip = ratio >= h.clip_lo && ratio <= h.clip_hi;
-            if (lu_ < lc_) dpl_dr = advn;
-            else if (lu_ > lc_) dpl_dr = in_clip ? advn : 0.f;
-            else dpl_dr = 0.5f * advn + (in_clip ? 0.5f * advn : 0.f);
-            const bool in_hard = raw_ratio >= 0.05f && raw_ratio <= 20.0f;
-            const float dL_dlogp = in_hard ? (-inv_n) * dpl_dr * raw_ratio : 0.f;
             if (h.action_kind == 0) {
                 const float u = 1.0f / (float)A, lu = logf(u);
                 float klpu = 0.f;
@@ -708,66 +867,126 @@ __global__ __launch_bounds__(256) void k_ppo_loss(const float *__restrict__ para
                 }
 #pragma unroll
                 for (int k = 0; k < MAXA; ++k)
-                    if (k < A) {
-                        const float lp = (zz[k] - mx) - lse, p = expf(lp), q = (zo[k] - mxo) - lseo;
-                        float gk = dL_dlogp * ((k == act ? 1.f : 0.f) - p);
-                        if (h.expl_kind == 1) gk += h.expl_coeff * inv_n * (p * (lp + ent));
-                        if (h.expl_kind == 2)
-                            gk += symkl_gate * h.expl_coeff * inv_n * 0.5f * (p * ((lp - lu) - klpu) + p - u);
-                        if (h.kl_coeff != 0.f) gk += h.kl_coeff * inv_n * (p * ((lp - q) - kl));
-                        gz[k] = gk;
-                    }
+                    if (k < A)
+                        gz[k] = cat_grad(zz[k], zo[k], k == act, mx, lse, mxo, lseo, ent, kl, klpu, u, lu, r.dL_dlogp,
+                                         p.inv_n, p.symkl_gate, h);
             } else {
-                for (int k = 0; k < D; ++k) {
-                    const float mu = z[k], e = expf(z[D + k]);
-                    const float sd = clampf(e, 1e-4f, 1e4f);
-                    const float dsd = (e >= 1e-4f && e <= 1e4f) ? e : 0.f;
-                    const float a = actions[d * D + k];
-                    const float var = sd * sd;
-                    float gmu = dL_dlogp * ((a - mu) / var);
-                    float gsd = dL_dlogp * (((a - mu) * (a - mu)) / (var * sd) - 1.f / sd);
-                    if (h.expl_kind == 1) gsd += -h.expl_coeff * inv_n * (1.f / sd);
-                    if (h.kl_coeff != 0.f) {
-                        const float muo = old_params[d * A + k];
-                        const float sdo = clampf(expf(old_params[d * A + D + k]), 1e-4f, 1e4f);
-                        gmu += h.kl_coeff * inv_n * ((mu - muo) / (sdo * sdo));
-                        gsd += h.kl_coeff * inv_n * (sd / (sdo * sdo) - 1.f / sd);
-                    }
-                    gz[k] = gmu;
-                    gz[D + k] = gsd * dsd;
-                }
+                for (int k = 0; k < D; ++k) box_grad(z, zold, actions + d * D, D, k, r.dL_dlogp, p.inv_n, h, gz);
             }
-            const bool in_v = (v - vo) >= -h.clip_value && (v - vo) <= h.clip_value;
-            float dvl;
-            if (l1 > l2) dvl = 2.f * (v - R);
-            else if (l2 > l1) dvl = in_v ? 2.f * (vclip - R) : 0.f;
-            else dvl = (v - R) + (in_v ? (vclip - R) : 0.f);
-            g_values[i * ldv] = h.value_coeff * inv_n * dvl;
+            g_values[i * ldv] = h.value_coeff * p.inv_n * r.dvl;
         } else {
             for (int k = 0; k < A; ++k) gz[k] = 0.f;
             g_values[i * ldv] = 0.f;
         }
     }
-    // block reduction
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    kl_max = sf_wave_max(kl_max);
-    if (lane == 0) lds_max[wave] = kl_max;
-    sf_block_sum<4>(acc, lds);  // contains a __syncthreads()
-    if (threadIdx.x == 0) {
-        atomicAdd(&sums[0], acc[0]);
-        atomicAdd(&sums[1], acc[1]);
-        atomicAdd(&sums[2], acc[2]);
-        atomicAdd(&sums[3], acc[3]);
-        const float m = fmaxf(fmaxf(lds_max[0], lds_max[1]), fmaxf(lds_max[2], lds_max[3]));
-        if (m > -1.0f) atomic_max_float(&sums[4], m);
-    }
+    loss_epilogue(acc, kl_max, sums, 0);
 }
 
+// Tuple of Discrete / Box heads (TupleActionDistribution, action_distributions.py:197-287), A <= 128: independent
+// members whose log-prob / entropy / KL / symmetric-KL add up.  Same loss and backward as k_ppo_loss, per-member softmax
+// statistics; members are read from global memory in place (these kernels are ~0.1 % of a step: clarity over register
+// blocking).  sym_pass != 0: only accumulate the symmetric-KL sum (pre-pass for its mean gate) into sums[7].
+// KEEP (k_ppo_loss_md, up to 8 members): a member's seven statistics stay in the lane between the forward loop and the
+// gradient loop, and the row's log-prob is a float sum.  !KEEP (k_ppo_loss_mh, up to SF_MAX_ACTION_HEADS members): seven
+// float[64] arrays would be 448 registers, i.e. scratch, so the gradient loop calls cat_terms again (the same expressions,
+// hence the same bits, for a second pass of expf over a row that is in cache); the row's log-prob is a sum of up to 64
+// members' (|lp| can pass 100 each) and is added up in double, so that the ratio exp(logp - old_logp) does not inherit the
+// rounding of a float running sum of that size.
+template <bool KEEP>
+__device__ __forceinline__ void ppo_loss_tuple(const float *__restrict__ params, int ldp,
+                                               const float *__restrict__ values, int ldv,
+                                               const float *__restrict__ actions, const float *__restrict__ old_logp,
+                                               const float *__restrict__ old_params,
+                                               const float *__restrict__ old_values, const float *__restrict__ adv,
+                                               const float *__restrict__ targets, const uint8_t *__restrict__ valids,
+                                               const int32_t *__restrict__ index, int64_t offset, int64_t n, int A,
+                                               const LossDev &h, const double *__restrict__ moments,
+                                               double *__restrict__ sums, float *__restrict__ g_params,
+                                               float *__restrict__ g_values, float *__restrict__ ratio_out,
+                                               int sym_pass) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const LossPre p = loss_prologue(moments, sums, h.expl_kind == 2 && !sym_pass);
+    const int H = h.hd.num_heads;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    float kl_max = -1.0f;
+    if (i < n) {
+        const int64_t d = index ? (int64_t)index[i] : offset + i;
+        const bool valid = valids[d] != 0;
+        const float *z = params + i * ldp, *zo = old_params + d * A;
+        const float *arow = actions + d * heads_action_cols(h.hd.head_n, H);
+        float *gz = g_params + i * ldp;
+        float logp_a = 0.f;   // KEEP
+        double logp_d = 0.0;  // !KEEP
+        float ent = 0.f, kl = 0.f, symkl = 0.f;
+        constexpr int NK = KEEP ? 8 : 1;
+        float mx[NK], lse[NK], mxo[NK], lseo[NK], ent_h[NK], kl_h[NK], klpu_h[NK];
+        auto keep = [&](const CatTerms &t, int s) {
+            mx[s] = t.mx; lse[s] = t.lse; mxo[s] = t.mxo; lseo[s] = t.lseo;
+            ent_h[s] = t.ent; kl_h[s] = t.kl; klpu_h[s] = t.klpu;
+        };
+        int off = 0, aoff = 0;
+        for (int hd = 0; hd < H; ++hd) {
+            const int nh = h.hd.head_n[hd];
+            if (nh < 0) {  // Box(D) member
+                const int Dh = -nh;
+                float lpp = KEEP ? logp_a : 0.f, e = 0.f, kk = 0.f;  // (the float sum runs on through the columns)
+                for (int k = 0; k < Dh; ++k) box_loss_terms(z + off, zo + off, arow + aoff, Dh, k, lpp, e, kk);
+                if constexpr (KEEP) logp_a = lpp;
+                else logp_d += (double)lpp;
+                ent += e; kl += kk;
+                off += 2 * Dh; aoff += Dh;
+                continue;
+            }
+            const CatTerms t = cat_terms(z + off, zo + off, nh, (int)arow[aoff]);
+            if constexpr (KEEP) { keep(t, hd); logp_a += t.lpa; }
+            else logp_d += (double)t.lpa;
+            ent += t.ent; kl += t.kl; symkl += 0.5f * (t.klpu + t.a2);
+            off += nh; aoff += 1;
+        }
+        if (sym_pass) {
+            if (valid) acc[0] = symkl;
+        } else {
+            const float dlogp = KEEP ? logp_a - old_logp[d] : (float)(logp_d - (double)old_logp[d]);
+            const int64_t da = h.dense_adv ? i : d;
+            const LossRow r = loss_row(dlogp, adv[da], values[i * ldv], old_values[ov_row(h, d)], targets[da], p, h);
+            if (ratio_out) ratio_out[i] = r.ratio;
+            if (valid) {
+                acc[0] = r.pl;
+                acc[1] = (h.expl_kind == 2) ? symkl : ent;
+                acc[2] = kl;
+                acc[3] = r.vl;
+                kl_max = kl;
+                off = 0;
+                aoff = 0;
+                for (int hd = 0; hd < H; ++hd) {
+                    const int nh = h.hd.head_n[hd];
+                    if (nh < 0) {  // Box(D) member
+                        const int Dh = -nh;
+                        for (int k = 0; k < Dh; ++k)
+                            box_grad(z + off, zo + off, arow + aoff, Dh, k, r.dL_dlogp, p.inv_n, h, gz + off);
+                        off += 2 * Dh; aoff += Dh;
+                        continue;
+                    }
+                    const int act = (int)arow[aoff];
+                    aoff += 1;
+                    const int s = KEEP ? hd : 0;
+                    if constexpr (!KEEP) keep(cat_terms(z + off, zo + off, nh, act), 0);  // the first loop's values, bit for bit
+                    const float u = 1.0f / (float)nh, lu = logf(u);
+                    for (int k = 0; k < nh; ++k)
+                        gz[off + k] = cat_grad(z[off + k], zo[off + k], k == act, mx[s], lse[s], mxo[s], lseo[s], ent_h[s],
+                                               kl_h[s], klpu_h[s], u, lu, r.dL_dlogp, p.inv_n, p.symkl_gate, h);
+                    off += nh;
+                }
+                g_values[i * ldv] = h.value_coeff * p.inv_n * r.dvl;
+            } else {
+                for (int k = 0; k < A; ++k) gz[k] = 0.f;
+                g_values[i * ldv] = 0.f;
+            }
+        }
+    }
+    loss_epilogue(acc, kl_max, sums, sym_pass);
+}
 
-// Tuple of Discrete heads (TupleActionDistribution, action_distributions.py:197-287): independent categoricals whose
-// log-prob / entropy / KL / symmetric-KL add up.  Same loss and backward as k_ppo_loss, per-head softmax statistics;
-// heads are read from global memory in place (this kernel is ~0.1 % of a step: clarity over register blocking).
-// sym_pass != 0: only accumulate the symmetric-KL sum (pre-pass for its mean gate) into sums[7].
 __global__ __launch_bounds__(256) void k_ppo_loss_md(const float *__restrict__ params, int ldp,
                                                      const float *__restrict__ values, int ldv,
                                                      const float *__restrict__ actions,
@@ -781,193 +1000,10 @@ __global__ __launch_bounds__(256) void k_ppo_loss_md(const float *__restrict__ p
                                                      double *__restrict__ sums, float *__restrict__ g_params,
                                                      float *__restrict__ g_values, float *__restrict__ ratio_out,
                                                      int sym_pass) {
-    __shared__ double lds[4 * 4];
-    __shared__ float lds_max[4];
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const double mn = moments[2];
-    const double mean64 = moments[0] / mn;
-    const double var64 = (moments[1] - moments[0] * mean64) / (mn - 1.0);
-    const float adv_mean = (float)mean64;
-    const float adv_std = (float)sqrt(var64 > 0.0 ? var64 : (mn > 1.0 ? 0.0 : NAN));
-    const float denom = fmaxf(adv_std, 1e-7f);
-    const float inv_n = 1.0f / (float)mn;
-    const float symkl_gate = (h.expl_kind == 2 && !sym_pass) ? (float)sums[6] : 1.0f;
-    const int H = h.num_heads;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    float kl_max = -1.0f;
-    if (i < n) {
-        const int64_t d = index ? (int64_t)index[i] : offset + i;
-        const bool valid = valids[d] != 0;
-        const float *z = params + i * ldp, *zo = old_params + d * A;
-        float *gz = g_params + i * ldp;
-        float logp_a = 0.f, ent = 0.f, kl = 0.f, symkl = 0.f;
-        float mx[8], lse[8], mxo[8], lseo[8], ent_h[8], kl_h[8], klpu_h[8];
-        int off = 0, aoff = 0;
-        const int NA = heads_action_cols(h.head_n, H);
-        for (int hd = 0; hd < H; ++hd) {
-            const int nh = h.head_n[hd];
-            if (nh < 0) {  // Box(D) member: [means | log_std], the formulas of k_ppo_loss's continuous branch
-                const int Dh = -nh;
-                float e = 0.f, kk = 0.f;
-                for (int k = 0; k < Dh; ++k) {
-                    const float mu = z[off + k], sd = clampf(expf(z[off + Dh + k]), 1e-4f, 1e4f);
-                    const float a = actions[d * NA + aoff + k];
-                    logp_a += -((a - mu) * (a - mu)) / (2.f * (sd * sd)) - logf(sd) - 0.91893853320467274178f;
-                    e += 0.5f + 0.91893853320467274178f + logf(sd);
-                    const float muo = zo[off + k], sdo = clampf(expf(zo[off + Dh + k]), 1e-4f, 1e4f);
-                    const float vr = (sd / sdo) * (sd / sdo);
-                    const float t1 = ((mu - muo) / sdo) * ((mu - muo) / sdo);
-                    kk += 0.5f * (vr + t1 - 1.f - logf(vr));
-                }
-                ent_h[hd] = e; kl_h[hd] = kk; klpu_h[hd] = 0.f;
-                ent += e; kl += kk;
-                off += 2 * Dh; aoff += Dh;
-                continue;
-            }
-            float m1 = -INFINITY, m2 = -INFINITY;
-            for (int k = 0; k < nh; ++k) { m1 = fmaxf(m1, z[off + k]); m2 = fmaxf(m2, zo[off + k]); }
-            float s1 = 0.f, s2 = 0.f;
-            for (int k = 0; k < nh; ++k) { s1 += expf(z[off + k] - m1); s2 += expf(zo[off + k] - m2); }
-            mx[hd] = m1; lse[hd] = logf(s1); mxo[hd] = m2; lseo[hd] = logf(s2);
-            const int act = (int)actions[d * NA + aoff];
-            const float u = 1.0f / (float)nh, lu = logf(u);
-            float e = 0.f, kk = 0.f, a1 = 0.f, a2 = 0.f;
-            for (int k = 0; k < nh; ++k) {
-                const float lp = (z[off + k] - m1) - lse[hd], p = expf(lp), q = (zo[off + k] - m2) - lseo[hd];
-                if (k == act) logp_a += lp;
-                e -= p * lp;
-                kk += p * (lp - q);
-                a1 += p * (lp - lu);
-                a2 += u * (lu - lp);
-            }
-            ent_h[hd] = e; kl_h[hd] = kk; klpu_h[hd] = a1;
-            ent += e; kl += kk; symkl += 0.5f * (a1 + a2);
-            off += nh; aoff += 1;
-        }
-        if (sym_pass) {
-            if (valid) acc[0] = symkl;
-        } else {
-            const float raw_ratio = expf(logp_a - old_logp[d]);
-            const float ratio = clampf(raw_ratio, 0.05f, 20.0f);
-            if (ratio_out) ratio_out[i] = ratio;
-            const int64_t da = h.dense_adv ? i : d;
-            const float advn = (adv[da] - adv_mean) / denom;
-            const float clipped = clampf(ratio, h.clip_lo, h.clip_hi);
-            const float lu_ = ratio * advn, lc_ = clipped * advn;
-            const float pl = fminf(lu_, lc_);
-            const float v = values[i * ldv], vo = old_values[ov_row(h, d)], R = targets[da];
-            const float vclip = vo + clampf(v - vo, -h.clip_value, h.clip_value);
-            const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
-            const float vl = fmaxf(l1, l2);
-            if (valid) {
-                acc[0] = pl;
-                acc[1] = (h.expl_kind == 2) ? symkl : ent;
-                acc[2] = kl;
-                acc[3] = vl;
-                kl_max = kl;
-                float dpl_dr;
-                const bool in_clip = ratio >= h.clip_lo && ratio <= h.clip_hi;
-                if (lu_ < lc_) dpl_dr = advn;
-                else if (lu_ > lc_) dpl_dr = in_clip ? advn : 0.f;
-                else dpl_dr = 0.5f * advn + (in_clip ? 0.5f * advn : 0.f);
-                const bool in_hard = raw_ratio >= 0.05f && raw_ratio <= 20.0f;
-                const float dL_dlogp = in_hard ? (-inv_n) * dpl_dr * raw_ratio : 0.f;
-                off = 0;
-                aoff = 0;
-                for (int hd = 0; hd < H; ++hd) {
-                    const int nh = h.head_n[hd];
-                    if (nh < 0) {  // Box(D) member
-                        const int Dh = -nh;
-                        for (int k = 0; k < Dh; ++k) {
-                            const float mu = z[off + k], e = expf(z[off + Dh + k]);
-                            const float sd = clampf(e, 1e-4f, 1e4f);
-                            const float dsd = (e >= 1e-4f && e <= 1e4f) ? e : 0.f;
-                            const float a = actions[d * NA + aoff + k];
-                            const float var = sd * sd;
-                            float gmu = dL_dlogp * ((a - mu) / var);
-                            float gsd = dL_dlogp * (((a - mu) * (a - mu)) / (var * sd) - 1.f / sd);
-                            if (h.expl_kind == 1) gsd += -h.expl_coeff * inv_n * (1.f / sd);
-                            if (h.kl_coeff != 0.f) {
-                                const float muo = zo[off + k], sdo = clampf(expf(zo[off + Dh + k]), 1e-4f, 1e4f);
-                                gmu += h.kl_coeff * inv_n * ((mu - muo) / (sdo * sdo));
-                                gsd += h.kl_coeff * inv_n * (sd / (sdo * sdo) - 1.f / sd);
-                            }
-                            gz[off + k] = gmu;
-                            gz[off + Dh + k] = gsd * dsd;
-                        }
-                        off += 2 * Dh; aoff += Dh;
-                        continue;
-                    }
-                    const int act = (int)actions[d * NA + aoff];
-                    aoff += 1;
-                    const float u = 1.0f / (float)nh, lu = logf(u);
-                    for (int k = 0; k < nh; ++k) {
-                        const float lp = (z[off + k] - mx[hd]) - lse[hd], p = expf(lp);
-                        const float q = (zo[off + k] - mxo[hd]) - lseo[hd];
-                        float gk = dL_dlogp * ((k == act ? 1.f : 0.f) - p);
-                        if (h.expl_kind == 1) gk += h.expl_coeff * inv_n * (p * (lp + ent_h[hd]));
-                        if (h.expl_kind == 2)
-                            gk += symkl_gate * h.expl_coeff * inv_n * 0.5f * (p * ((lp - lu) - klpu_h[hd]) + p - u);
-                        if (h.kl_coeff != 0.f) gk += h.kl_coeff * inv_n * (p * ((lp - q) - kl_h[hd]));
-                        gz[off + k] = gk;
-                    }
-                    off += nh;
-                }
-                const bool in_v = (v - vo) >= -h.clip_value && (v - vo) <= h.clip_value;
-                float dvl;
-                if (l1 > l2) dvl = 2.f * (v - R);
-                else if (l2 > l1) dvl = in_v ? 2.f * (vclip - R) : 0.f;
-                else dvl = (v - R) + (in_v ? (vclip - R) : 0.f);
-                g_values[i * ldv] = h.value_coeff * inv_n * dvl;
-            } else {
-                for (int k = 0; k < A; ++k) gz[k] = 0.f;
-                g_values[i * ldv] = 0.f;
-            }
-        }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    kl_max = sf_wave_max(kl_max);
-    if (lane == 0) lds_max[wave] = kl_max;
-    sf_block_sum<4>(acc, lds);
-    if (threadIdx.x == 0) {
-        if (sym_pass) { atomicAdd(&sums[7], acc[0]); return; }
-        atomicAdd(&sums[0], acc[0]);
-        atomicAdd(&sums[1], acc[1]);
-        atomicAdd(&sums[2], acc[2]);
-        atomicAdd(&sums[3], acc[3]);
-        const float m = fmaxf(fmaxf(lds_max[0], lds_max[1]), fmaxf(lds_max[2], lds_max[3]));
-        if (m > -1.0f) atomic_max_float(&sums[4], m);
-    }
+    ppo_loss_tuple<true>(params, ldp, values, ldv, actions, old_logp, old_params, old_values, adv, targets, valids, index,
+                         offset, n, A, h, moments, sums, g_params, g_values, ratio_out, sym_pass);
 }
 
-// k_ppo_loss_md for head lists of more than 8 members (A <= 128; up to SF_MAX_ACTION_HEADS): the same per-member formulas
-// in the same order (the row's log-prob alone is added up in double), but no per-member state in the lane: seven float[64] arrays would be 448 registers, i.e. scratch.  The
-// first member loop keeps only the row's totals; the gradient loop recomputes a member's max, log-sum-exp, entropy, KL
-// and KL(p || uniform) with the same expressions (cat_terms), which costs a second pass of expf over a row that is in
-// cache.  sym_pass as in k_ppo_loss_md.
-struct CatTerms {
-    float mx, lse, mxo, lseo, ent, kl, klpu, a2, lpa;
-};
-__device__ __forceinline__ CatTerms cat_terms(const float *__restrict__ z, const float *__restrict__ zo, int nh, int act) {
-    CatTerms t;
-    float m1 = -INFINITY, m2 = -INFINITY;
-    for (int k = 0; k < nh; ++k) { m1 = fmaxf(m1, z[k]); m2 = fmaxf(m2, zo[k]); }
-    float s1 = 0.f, s2 = 0.f;
-    for (int k = 0; k < nh; ++k) { s1 += expf(z[k] - m1); s2 += expf(zo[k] - m2); }
-    t.mx = m1; t.lse = logf(s1); t.mxo = m2; t.lseo = logf(s2);
-    const float u = 1.0f / (float)nh, lu = logf(u);
-    float lpa = 0.f, e = 0.f, kk = 0.f, a1 = 0.f, a2 = 0.f;
-    for (int k = 0; k < nh; ++k) {
-        const float lp = (z[k] - m1) - t.lse, p = expf(lp), q = (zo[k] - m2) - t.lseo;
-        if (k == act) lpa = lp;
-        e -= p * lp;
-        kk += p * (lp - q);
-        a1 += p * (lp - lu);
-        a2 += u * (lu - lp);
-    }
-    t.ent = e; t.kl = kk; t.klpu = a1; t.a2 = a2; t.lpa = lpa;
-    return t;
-}
 __global__ __launch_bounds__(256) void k_ppo_loss_mh(const float *__restrict__ params, int ldp,
                                                      const float *__restrict__ values, int ldv,
                                                      const float *__restrict__ actions,
@@ -981,150 +1017,8 @@ __global__ __launch_bounds__(256) void k_ppo_loss_mh(const float *__restrict__ p
                                                      double *__restrict__ sums, float *__restrict__ g_params,
                                                      float *__restrict__ g_values, float *__restrict__ ratio_out,
                                                      int sym_pass) {
-    __shared__ double lds[4 * 4];
-    __shared__ float lds_max[4];
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const double mn = moments[2];
-    const double mean64 = moments[0] / mn;
-    const double var64 = (moments[1] - moments[0] * mean64) / (mn - 1.0);
-    const float adv_mean = (float)mean64;
-    const float adv_std = (float)sqrt(var64 > 0.0 ? var64 : (mn > 1.0 ? 0.0 : NAN));
-    const float denom = fmaxf(adv_std, 1e-7f);
-    const float inv_n = 1.0f / (float)mn;
-    const float symkl_gate = (h.expl_kind == 2 && !sym_pass) ? (float)sums[6] : 1.0f;
-    const int H = h.num_heads;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    float kl_max = -1.0f;
-    if (i < n) {
-        const int64_t d = index ? (int64_t)index[i] : offset + i;
-        const bool valid = valids[d] != 0;
-        const float *z = params + i * ldp, *zo = old_params + d * A;
-        float *gz = g_params + i * ldp;
-        // the row's log-prob is a sum of up to 64 members' (|lp| can pass 100 each): added up in double, so that the
-        // ratio exp(logp - old_logp) does not inherit the rounding of a float running sum of that size
-        double logp_a = 0.0;
-        float ent = 0.f, kl = 0.f, symkl = 0.f;
-        int off = 0, aoff = 0;
-        const int NA = heads_action_cols(h.head_n, H);
-        const float *arow = actions + d * NA;
-        for (int hd = 0; hd < H; ++hd) {
-            const int nh = h.head_n[hd];
-            if (nh < 0) {  // Box(D) member: [means | log_std], the formulas of k_ppo_loss's continuous branch
-                const int Dh = -nh;
-                float lpp = 0.f, e = 0.f, kk = 0.f;
-                for (int k = 0; k < Dh; ++k) {
-                    const float mu = z[off + k], sd = clampf(expf(z[off + Dh + k]), 1e-4f, 1e4f);
-                    const float a = arow[aoff + k];
-                    lpp += -((a - mu) * (a - mu)) / (2.f * (sd * sd)) - logf(sd) - 0.91893853320467274178f;
-                    e += 0.5f + 0.91893853320467274178f + logf(sd);
-                    const float muo = zo[off + k], sdo = clampf(expf(zo[off + Dh + k]), 1e-4f, 1e4f);
-                    const float vr = (sd / sdo) * (sd / sdo);
-                    const float t1 = ((mu - muo) / sdo) * ((mu - muo) / sdo);
-                    kk += 0.5f * (vr + t1 - 1.f - logf(vr));
-                }
-                logp_a += (double)lpp; ent += e; kl += kk;
-                off += 2 * Dh; aoff += Dh;
-                continue;
-            }
-            const CatTerms t = cat_terms(z + off, zo + off, nh, (int)arow[aoff]);
-            logp_a += (double)t.lpa; ent += t.ent; kl += t.kl; symkl += 0.5f * (t.klpu + t.a2);
-            off += nh; aoff += 1;
-        }
-        if (sym_pass) {
-            if (valid) acc[0] = symkl;
-        } else {
-            const float raw_ratio = expf((float)(logp_a - (double)old_logp[d]));
-            const float ratio = clampf(raw_ratio, 0.05f, 20.0f);
-            if (ratio_out) ratio_out[i] = ratio;
-            const int64_t da = h.dense_adv ? i : d;
-            const float advn = (adv[da] - adv_mean) / denom;
-            const float clipped = clampf(ratio, h.clip_lo, h.clip_hi);
-            const float lu_ = ratio * advn, lc_ = clipped * advn;
-            const float pl = fminf(lu_, lc_);
-            const float v = values[i * ldv], vo = old_values[ov_row(h, d)], R = targets[da];
-            const float vclip = vo + clampf(v - vo, -h.clip_value, h.clip_value);
-            const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
-            const float vl = fmaxf(l1, l2);
-            if (valid) {
-                acc[0] = pl;
-                acc[1] = (h.expl_kind == 2) ? symkl : ent;
-                acc[2] = kl;
-                acc[3] = vl;
-                kl_max = kl;
-                float dpl_dr;
-                const bool in_clip = ratio >= h.clip_lo && ratio <= h.clip_hi;
-                if (lu_ < lc_) dpl_dr = advn;
-                else if (lu_ > lc_) dpl_dr = in_clip ? advn : 0.f;
-                else dpl_dr = 0.5f * advn + (in_clip ? 0.5f * advn : 0.f);
-                const bool in_hard = raw_ratio >= 0.05f && raw_ratio <= 20.0f;
-                const float dL_dlogp = in_hard ? (-inv_n) * dpl_dr * raw_ratio : 0.f;
-                off = 0;
-                aoff = 0;
-                for (int hd = 0; hd < H; ++hd) {
-                    const int nh = h.head_n[hd];
-                    if (nh < 0) {  // Box(D) member
-                        const int Dh = -nh;
-                        for (int k = 0; k < Dh; ++k) {
-                            const float mu = z[off + k], e = expf(z[off + Dh + k]);
-                            const float sd = clampf(e, 1e-4f, 1e4f);
-                            const float dsd = (e >= 1e-4f && e <= 1e4f) ? e : 0.f;
-                            const float a = arow[aoff + k];
-                            const float var = sd * sd;
-                            float gmu = dL_dlogp * ((a - mu) / var);
-                            float gsd = dL_dlogp * (((a - mu) * (a - mu)) / (var * sd) - 1.f / sd);
-                            if (h.expl_kind == 1) gsd += -h.expl_coeff * inv_n * (1.f / sd);
-                            if (h.kl_coeff != 0.f) {
-                                const float muo = zo[off + k], sdo = clampf(expf(zo[off + Dh + k]), 1e-4f, 1e4f);
-                                gmu += h.kl_coeff * inv_n * ((mu - muo) / (sdo * sdo));
-                                gsd += h.kl_coeff * inv_n * (sd / (sdo * sdo) - 1.f / sd);
-                            }
-                            gz[off + k] = gmu;
-                            gz[off + Dh + k] = gsd * dsd;
-                        }
-                        off += 2 * Dh; aoff += Dh;
-                        continue;
-                    }
-                    const int act = (int)arow[aoff];
-                    aoff += 1;
-                    const CatTerms t = cat_terms(z + off, zo + off, nh, act);  // the first loop's values, bit for bit
-                    const float u = 1.0f / (float)nh, lu = logf(u);
-                    for (int k = 0; k < nh; ++k) {
-                        const float lp = (z[off + k] - t.mx) - t.lse, p = expf(lp);
-                        const float q = (zo[off + k] - t.mxo) - t.lseo;
-                        float gk = dL_dlogp * ((k == act ? 1.f : 0.f) - p);
-                        if (h.expl_kind == 1) gk += h.expl_coeff * inv_n * (p * (lp + t.ent));
-                        if (h.expl_kind == 2)
-                            gk += symkl_gate * h.expl_coeff * inv_n * 0.5f * (p * ((lp - lu) - t.klpu) + p - u);
-                        if (h.kl_coeff != 0.f) gk += h.kl_coeff * inv_n * (p * ((lp - q) - t.kl));
-                        gz[off + k] = gk;
-                    }
-                    off += nh;
-                }
-                const bool in_v = (v - vo) >= -h.clip_value && (v - vo) <= h.clip_value;
-                float dvl;
-                if (l1 > l2) dvl = 2.f * (v - R);
-                else if (l2 > l1) dvl = in_v ? 2.f * (vclip - R) : 0.f;
-                else dvl = (v - R) + (in_v ? (vclip - R) : 0.f);
-                g_values[i * ldv] = h.value_coeff * inv_n * dvl;
-            } else {
-                for (int k = 0; k < A; ++k) gz[k] = 0.f;
-                g_values[i * ldv] = 0.f;
-            }
-        }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    kl_max = sf_wave_max(kl_max);
-    if (lane == 0) lds_max[wave] = kl_max;
-    sf_block_sum<4>(acc, lds);
-    if (threadIdx.x == 0) {
-        if (sym_pass) { atomicAdd(&sums[7], acc[0]); return; }
-        atomicAdd(&sums[0], acc[0]);
-        atomicAdd(&sums[1], acc[1]);
-        atomicAdd(&sums[2], acc[2]);
-        atomicAdd(&sums[3], acc[3]);
-        const float m = fmaxf(fmaxf(lds_max[0], lds_max[1]), fmaxf(lds_max[2], lds_max[3]));
-        if (m > -1.0f) atomic_max_float(&sums[4], m);
-    }
+    ppo_loss_tuple<false>(params, ldp, values, ldv, actions, old_logp, old_params, old_values, adv, targets, valids, index,
+                          offset, n, A, h, moments, sums, g_params, g_values, ratio_out, sym_pass);
 }
 
 // pre-pass for the symmetric-KL exploration loss: mean over valid samples decides clamp(max=30) / isfinite gate
@@ -1139,15 +1033,9 @@ __global__ __launch_bounds__(256) void k_symkl_sum(const float *__restrict__ par
     if (i < n) {
         const int64_t d = index ? (int64_t)index[i] : offset + i;
         if (valids[d]) {
-            const float *z = params + i * ldp;
-            float zz[MAXA];
-            float mx = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < MAXA; ++k) { zz[k] = k < A ? z[k] : -INFINITY; mx = fmaxf(mx, zz[k]); }
-            float se = 0.f;
-#pragma unroll
-            for (int k = 0; k < MAXA; ++k) if (k < A) se += expf(zz[k] - mx);
-            const float lse = logf(se), u = 1.0f / (float)A, lu = logf(u);
+            float zz[MAXA], mx, lse;
+            reg_softmax<MAXA>(params + i * ldp, A, zz, mx, lse);
+            const float u = 1.0f / (float)A, lu = logf(u);
             float a1 = 0.f, a2 = 0.f;
 #pragma unroll
             for (int k = 0; k < MAXA; ++k)
@@ -1178,34 +1066,25 @@ __global__ __launch_bounds__(256) void k_ppo_loss_wide(const float *__restrict__
                                                        double *__restrict__ sums, float *__restrict__ g_params,
                                                        float *__restrict__ g_values, float *__restrict__ ratio_out,
                                                        int sym_pass) {
-    __shared__ double lds[4 * 4];
-    __shared__ float lds_max[4];
     // per wave and head: mx, lse, mxo, lseo, entropy, KL, KL(p || uniform); 8 KB for the longest list
     __shared__ float hstat[WIDE_ROWS][SF_MAX_ACTION_HEADS][8];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double mn = moments[2];
-    const double mean64 = moments[0] / mn;
-    const double var64 = (moments[1] - moments[0] * mean64) / (mn - 1.0);
-    const float adv_mean = (float)mean64;
-    const float adv_std = (float)sqrt(var64 > 0.0 ? var64 : (mn > 1.0 ? 0.0 : NAN));
-    const float denom = fmaxf(adv_std, 1e-7f);
-    const float inv_n = 1.0f / (float)mn;
-    const float symkl_gate = (h.expl_kind == 2 && !sym_pass) ? (float)sums[6] : 1.0f;
-    const int H = h.num_heads;
-    const int NA = heads_action_cols(h.head_n, H);
+    const LossPre p = loss_prologue(moments, sums, h.expl_kind == 2 && !sym_pass);
+    const int H = h.hd.num_heads;
+    const int NA = heads_action_cols(h.hd.head_n, H);
     float (*st)[8] = hstat[wave];
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     float kl_max = -1.0f;
     for (int64_t i = (int64_t)blockIdx.x * WIDE_ROWS + wave; i < n; i += (int64_t)gridDim.x * WIDE_ROWS) {
         const int64_t d = index ? (int64_t)index[i] : offset + i;
         const bool valid = valids[d] != 0;
-        const float *z = params + i * ldp, *zo = old_params + d * A;
+        const float *z = params + i * ldp, *zo = old_params + d * A, *arow = actions + d * NA;
         if (sym_pass) {
             if (!valid) continue;
             float symkl = 0.f;
             int off = 0;
             for (int hd = 0; hd < H; ++hd) {
-                const int nh = h.head_n[hd];  // categorical heads only (the launcher checks)
+                const int nh = h.hd.head_n[hd];  // categorical heads only (the launcher checks)
                 float m1, l1;
                 wide_lse(z + off, nh, lane, nullptr, m1, l1);
                 const float u = 1.0f / (float)nh, lu = logf(u);
@@ -1227,20 +1106,11 @@ __global__ __launch_bounds__(256) void k_ppo_loss_wide(const float *__restrict__
         double logp_d = 0.0;  // the same sum in double: what a list of more than 8 members takes its ratio from
         int off = 0, aoff = 0;
         for (int hd = 0; hd < H; ++hd) {
-            const int nh = h.head_n[hd];
-            if (nh < 0) {  // Box(D) member: [means | log_std], the formulas of k_ppo_loss's continuous branch
+            const int nh = h.hd.head_n[hd];
+            if (nh < 0) {  // Box(D) member
                 const int Dh = -nh;
                 float lpp = 0.f, e = 0.f, kk = 0.f;
-                for (int k = lane; k < Dh; k += 64) {
-                    const float mu = z[off + k], sd = clampf(expf(z[off + Dh + k]), 1e-4f, 1e4f);
-                    const float a = actions[d * NA + aoff + k];
-                    lpp += -((a - mu) * (a - mu)) / (2.f * (sd * sd)) - logf(sd) - 0.91893853320467274178f;
-                    e += 0.5f + 0.91893853320467274178f + logf(sd);
-                    const float muo = zo[off + k], sdo = clampf(expf(zo[off + Dh + k]), 1e-4f, 1e4f);
-                    const float vr = (sd / sdo) * (sd / sdo);
-                    const float t1 = ((mu - muo) / sdo) * ((mu - muo) / sdo);
-                    kk += 0.5f * (vr + t1 - 1.f - logf(vr));
-                }
+                for (int k = lane; k < Dh; k += 64) box_loss_terms(z + off, zo + off, arow + aoff, Dh, k, lpp, e, kk);
                 lpp = wide_allsum(lpp);
                 logp_a += lpp; logp_d += (double)lpp;
                 ent += wide_allsum(e);
@@ -1254,16 +1124,16 @@ __global__ __launch_bounds__(256) void k_ppo_loss_wide(const float *__restrict__
             float mx, lse, mxo, lseo;
             wide_finish(m1, s1, mx, lse);
             wide_finish(m2, s2, mxo, lseo);
-            const int act = (int)actions[d * NA + aoff];
+            const int act = (int)arow[aoff];
             const float u = 1.0f / (float)nh, lu = logf(u);
             float lpa = 0.f, e = 0.f, kk = 0.f, a1 = 0.f, a2 = 0.f;
 #pragma unroll 4
             for (int k = lane; k < nh; k += 64) {
-                const float lp = (z[off + k] - mx) - lse, p = expf(lp), q = (zo[off + k] - mxo) - lseo;
+                const float lp = (z[off + k] - mx) - lse, p_ = expf(lp), q = (zo[off + k] - mxo) - lseo;
                 if (k == act) lpa = lp;
-                e -= p * lp;
-                kk += p * (lp - q);
-                a1 += p * (lp - lu);
+                e -= p_ * lp;
+                kk += p_ * (lp - q);
+                a1 += p_ * (lp - lu);
                 a2 += u * (lu - lp);
             }
             lpa = wide_allsum(lpa); e = wide_allsum(e); kk = wide_allsum(kk);
@@ -1274,106 +1144,48 @@ __global__ __launch_bounds__(256) void k_ppo_loss_wide(const float *__restrict__
             logp_a += lpa; logp_d += (double)lpa; ent += e; kl += kk; symkl += 0.5f * (a1 + a2);
             off += nh; aoff += 1;
         }
-        // up to 8 members: the float sum, as ever; more (|logp| can reach several hundred): the double one, see k_ppo_loss_mh
-        const float raw_ratio = expf(H > 8 ? (float)(logp_d - (double)old_logp[d]) : logp_a - old_logp[d]);
-        const float ratio = clampf(raw_ratio, 0.05f, 20.0f);
-        if (ratio_out && lane == 0) ratio_out[i] = ratio;
+        // up to 8 members: the float sum, as ever; more (|logp| can reach several hundred): the double one, see ppo_loss_tuple
+        const float dlogp = H > 8 ? (float)(logp_d - (double)old_logp[d]) : logp_a - old_logp[d];
+        const int64_t da = h.dense_adv ? i : d;
+        const LossRow r = loss_row(dlogp, adv[da], values[i * ldv], old_values[ov_row(h, d)], targets[da], p, h);
+        if (ratio_out && lane == 0) ratio_out[i] = r.ratio;
         if (!valid) {  // no loss, zero gradient
             for (int k = lane; k < A; k += 64) gz[k] = 0.f;
             if (lane == 0) g_values[i * ldv] = 0.f;
             continue;
         }
-        const int64_t da = h.dense_adv ? i : d;
-        const float advn = (adv[da] - adv_mean) / denom;
-        const float clipped = clampf(ratio, h.clip_lo, h.clip_hi);
-        const float lu_ = ratio * advn, lc_ = clipped * advn;
-        const float pl = fminf(lu_, lc_);
-        const float v = values[i * ldv], vo = old_values[ov_row(h, d)], R = targets[da];
-        const float vclip = vo + clampf(v - vo, -h.clip_value, h.clip_value);
-        const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
-        const float vl = fmaxf(l1, l2);
         if (lane == 0) {
-            acc[0] += pl;
+            acc[0] += r.pl;
             acc[1] += (h.expl_kind == 2) ? symkl : ent;
             acc[2] += kl;
-            acc[3] += vl;
+            acc[3] += r.vl;
             kl_max = fmaxf(kl_max, kl);
         }
-        // ---------------- backward (autograd semantics of min/max ties and clamp boundaries), as k_ppo_loss
-        float dpl_dr;
-        const bool in_clip = ratio >= h.clip_lo && ratio <= h.clip_hi;
-        if (lu_ < lc_) dpl_dr = advn;
-        else if (lu_ > lc_) dpl_dr = in_clip ? advn : 0.f;
-        else dpl_dr = 0.5f * advn + (in_clip ? 0.5f * advn : 0.f);
-        const bool in_hard = raw_ratio >= 0.05f && raw_ratio <= 20.0f;
-        const float dL_dlogp = in_hard ? (-inv_n) * dpl_dr * raw_ratio : 0.f;
         off = 0;
         aoff = 0;
         for (int hd = 0; hd < H; ++hd) {
-            const int nh = h.head_n[hd];
+            const int nh = h.hd.head_n[hd];
             if (nh < 0) {  // Box(D) member
                 const int Dh = -nh;
-                for (int k = lane; k < Dh; k += 64) {
-                    const float mu = z[off + k], e = expf(z[off + Dh + k]);
-                    const float sd = clampf(e, 1e-4f, 1e4f);
-                    const float dsd = (e >= 1e-4f && e <= 1e4f) ? e : 0.f;
-                    const float a = actions[d * NA + aoff + k];
-                    const float var = sd * sd;
-                    float gmu = dL_dlogp * ((a - mu) / var);
-                    float gsd = dL_dlogp * (((a - mu) * (a - mu)) / (var * sd) - 1.f / sd);
-                    if (h.expl_kind == 1) gsd += -h.expl_coeff * inv_n * (1.f / sd);
-                    if (h.kl_coeff != 0.f) {
-                        const float muo = zo[off + k], sdo = clampf(expf(zo[off + Dh + k]), 1e-4f, 1e4f);
-                        gmu += h.kl_coeff * inv_n * ((mu - muo) / (sdo * sdo));
-                        gsd += h.kl_coeff * inv_n * (sd / (sdo * sdo) - 1.f / sd);
-                    }
-                    gz[off + k] = gmu;
-                    gz[off + Dh + k] = gsd * dsd;
-                }
+                for (int k = lane; k < Dh; k += 64)
+                    box_grad(z + off, zo + off, arow + aoff, Dh, k, r.dL_dlogp, p.inv_n, h, gz + off);
                 off += 2 * Dh; aoff += Dh;
                 continue;
             }
-            const int act = (int)actions[d * NA + aoff];
+            const int act = (int)arow[aoff];
             aoff += 1;
             const float mx = st[hd][0], lse = st[hd][1], mxo = st[hd][2], lseo = st[hd][3];
             const float ent_h = st[hd][4], kl_h = st[hd][5], klpu_h = st[hd][6];
             const float u = 1.0f / (float)nh, lu = logf(u);
 #pragma unroll 4
-            for (int k = lane; k < nh; k += 64) {
-                const float lp = (z[off + k] - mx) - lse, p = expf(lp);
-                float gk = dL_dlogp * ((k == act ? 1.f : 0.f) - p);
-                if (h.expl_kind == 1) gk += h.expl_coeff * inv_n * (p * (lp + ent_h));
-                if (h.expl_kind == 2)
-                    gk += symkl_gate * h.expl_coeff * inv_n * 0.5f * (p * ((lp - lu) - klpu_h) + p - u);
-                if (h.kl_coeff != 0.f) {
-                    const float q = (zo[off + k] - mxo) - lseo;
-                    gk += h.kl_coeff * inv_n * (p * ((lp - q) - kl_h));
-                }
-                gz[off + k] = gk;
-            }
+            for (int k = lane; k < nh; k += 64)
+                gz[off + k] = cat_grad(z[off + k], h.kl_coeff != 0.f ? zo[off + k] : 0.f, k == act, mx, lse, mxo, lseo,
+                                       ent_h, kl_h, klpu_h, u, lu, r.dL_dlogp, p.inv_n, p.symkl_gate, h);
             off += nh;
         }
-        if (lane == 0) {
-            const bool in_v = (v - vo) >= -h.clip_value && (v - vo) <= h.clip_value;
-            float dvl;
-            if (l1 > l2) dvl = 2.f * (v - R);
-            else if (l2 > l1) dvl = in_v ? 2.f * (vclip - R) : 0.f;
-            else dvl = (v - R) + (in_v ? (vclip - R) : 0.f);
-            g_values[i * ldv] = h.value_coeff * inv_n * dvl;
-        }
+        if (lane == 0) g_values[i * ldv] = h.value_coeff * p.inv_n * r.dvl;
     }
-    kl_max = sf_wave_max(kl_max);
-    if (lane == 0) lds_max[wave] = kl_max;
-    sf_block_sum<4>(acc, lds);
-    if (threadIdx.x == 0) {
-        if (sym_pass) { atomicAdd(&sums[7], acc[0]); return; }
-        atomicAdd(&sums[0], acc[0]);
-        atomicAdd(&sums[1], acc[1]);
-        atomicAdd(&sums[2], acc[2]);
-        atomicAdd(&sums[3], acc[3]);
-        const float m = fmaxf(fmaxf(lds_max[0], lds_max[1]), fmaxf(lds_max[2], lds_max[3]));
-        if (m > -1.0f) atomic_max_float(&sums[4], m);
-    }
+    loss_epilogue(acc, kl_max, sums, sym_pass);
 }
 
 __global__ void k_symkl_gate(double *__restrict__ sums, const double *__restrict__ moments) {
@@ -1382,8 +1194,8 @@ __global__ void k_symkl_gate(double *__restrict__ sums, const double *__restrict
     sums[6] = (isfinite(m) && m <= 30.0f) ? 1.0 : 0.0;
 }
 
-// head_n: the categorical / Box members to copy (num_heads checked entries), or nullptr for one Discrete(A) / Box(A / 2)
-static LossDev make_loss_dev(const sf_loss_cfg *c, const int32_t *head_n, int num_heads) {
+// hd: the checked member list (one member: Discrete(A) / Box(A / 2))
+static LossDev make_loss_dev(const sf_loss_cfg *c, const HeadsDev &hd) {
     LossDev h;
     h.clip_hi = (float)(1.0 + (double)c->clip_ratio);
     h.clip_lo = (float)(1.0 / (1.0 + (double)c->clip_ratio));
@@ -1394,8 +1206,7 @@ static LossDev make_loss_dev(const sf_loss_cfg *c, const int32_t *head_n, int nu
     h.expl_kind = c->exploration_coeff == 0.f ? 0 : c->exploration_kind;
     h.action_kind = c->action_kind;
     h.dense_adv = c->dense_adv;
-    h.num_heads = head_n ? num_heads : 1;
-    for (int i = 0; i < SF_MAX_ACTION_HEADS; ++i) h.head_n[i] = head_n && i < num_heads ? head_n[i] : 0;
+    h.hd = hd;
     h.ov_T = c->old_values_T > 0 ? c->old_values_T : 0;
     return h;
 }
@@ -1437,17 +1248,18 @@ static int ppo_loss_launch(const char *what, const float *params, int ld_params,
     SF_REQUIRE(!(h_cfg->exploration_kind == 2 && h_cfg->action_kind != 0 && h_cfg->exploration_coeff != 0.f),
                "%s: symmetric_kl exploration loss needs a categorical distribution", what);
     const bool tuple = h_cfg->action_kind == 0 && num_heads > 1;
+    HeadsDev hd = single_head(A, h_cfg->action_kind);
     if (tuple) {  // every check of the list comes before the first launch (the memset included)
-        int32_t checked[SF_MAX_ACTION_HEADS];
         bool any_box;
-        const int tot = heads_from_host(what, head_n, num_heads, cap, checked, &any_box);
+        const int tot = heads_from_host(what, head_n, num_heads, cap, hd.head_n, &any_box);
         if (tot < 0) return SF_ERR_ARG;
+        hd.num_heads = num_heads;
         SF_REQUIRE(tot == A, "%s: head sizes sum to %d, A = %d", what, tot, A);
         SF_REQUIRE(!(any_box && h_cfg->exploration_kind == 2 && h_cfg->exploration_coeff != 0.f),
                    "%s: symmetric_kl exploration loss needs categorical heads only (the reference's "
                    "ContinuousActionDistribution has no symmetric_kl_with_uniform_prior)", what);
     }
-    const LossDev h = make_loss_dev(h_cfg, tuple ? head_n : nullptr, num_heads);
+    const LossDev h = make_loss_dev(h_cfg, hd);
     int rc = sf_hip_status(hipMemsetAsync(sums, 0, 8 * sizeof(double), STREAM(stream)), "sf_ppo_loss memset");
     if (rc) return rc;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
@@ -1462,7 +1274,7 @@ static int ppo_loss_launch(const char *what, const float *params, int ld_params,
                                                          old_params, old_values, adv, targets, valids, index, offset, n,
                                                          A, h, moments, sums, g_params, g_values, ratio_out, stream);
         // up to 8 members: their statistics stay in the lane (k_ppo_loss_md); more: recomputed (k_ppo_loss_mh)
-        auto kern = h.num_heads <= 8 ? k_ppo_loss_md : k_ppo_loss_mh;
+        auto kern = h.hd.num_heads <= 8 ? k_ppo_loss_md : k_ppo_loss_mh;
         if (h.expl_kind == 2) {
             kern<<<grid, block, 0, STREAM(stream)>>>(params, ld_params, values, ld_values, actions, old_logp, old_params,
                                                      old_values, adv, targets, valids, index, offset, n, A, h, moments,
@@ -1474,13 +1286,10 @@ static int ppo_loss_launch(const char *what, const float *params, int ld_params,
                                                  g_params, g_values, ratio_out, 0);
         return sf_launch_status(what);
     }
-    if (A >= WIDE_MIN_A) {  // a single Discrete(A) / Box(A / 2) as a one-member head list
-        LossDev hw = h;
-        hw.head_n[0] = h.action_kind == 0 ? A : -(A / 2);
+    if (A >= WIDE_MIN_A)  // a single Discrete(A) / Box(A / 2) as a one-member head list
         return ppo_loss_wide_launch(params, ld_params, values, ld_values, actions, old_logp, old_params, old_values, adv,
-                                    targets, valids, index, offset, n, A, hw, moments, sums, g_params, g_values,
+                                    targets, valids, index, offset, n, A, h, moments, sums, g_params, g_values,
                                     ratio_out, stream);
-    }
     if (h.expl_kind == 2) {
         PL_DISPATCH(k_symkl_sum, params, ld_params, valids, index, offset, n, A, sums + 7);
         k_symkl_gate<<<dim3(1), dim3(64), 0, STREAM(stream)>>>(sums, moments);
@@ -1526,8 +1335,8 @@ __global__ void k_loss_scalars(const double *__restrict__ sums, const double *__
                                float *__restrict__ out) {
     if (threadIdx.x || blockIdx.x) return;
     const double n = moments[2];
-    const double mean64 = moments[0] / n;
-    const double var64 = (moments[1] - moments[0] * mean64) / (n - 1.0);
+    double mean64, var64;
+    adv_mean_var(moments, mean64, var64);
     out[0] = (float)(-(sums[0] / n));
     if (h.expl_kind == 1) out[1] = (float)(-(double)h.expl_coeff * (sums[1] / n));
     else if (h.expl_kind == 2) {
@@ -1548,7 +1357,7 @@ __global__ void k_loss_scalars(const double *__restrict__ sums, const double *__
 extern "C" int sf_loss_scalars(const double *sums, const double *moments, const sf_loss_cfg *h_cfg, float *out,
                                void *stream) {
     SF_REQUIRE(sums && moments && h_cfg && out, "sf_loss_scalars: null pointer");
-    k_loss_scalars<<<dim3(1), dim3(64), 0, STREAM(stream)>>>(sums, moments, make_loss_dev(h_cfg, nullptr, 0), out);
+    k_loss_scalars<<<dim3(1), dim3(64), 0, STREAM(stream)>>>(sums, moments, make_loss_dev(h_cfg, HeadsDev{}), out);
     return sf_launch_status("sf_loss_scalars");
 }
 
@@ -2081,17 +1890,11 @@ __global__ __launch_bounds__(256) void k_sample_write(const float *__restrict__ 
         const int64_t it = (int64_t)b * T + t;
         float lp = 0.f;
         for (int k = 0; k < D; ++k) {
-            uint32_t w[4];
-            sf_philox4x32_10(step, (uint32_t)(k >> 1), 3u, 0u, seed, row0 + (uint32_t)b, w);
-            const uint32_t w1 = (k & 1) ? w[2] : w[0], w2 = (k & 1) ? w[3] : w[1];
-            const float u1 = ((float)(w1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-            const float u2 = (float)(w2 >> 8) * (1.0f / 16777216.0f);
-            const float eps = sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-            const float mu = z[k];
-            const float sd = clampf(expf(z[D + k]), 1e-4f, 1e4f);
+            const float eps = box_eps(step, k, 0, seed, row0 + (uint32_t)b);
+            const float mu = z[k], sd = box_sd(z[D + k]);
             const float a = deterministic ? mu : mu + sd * eps;  // argmax_actions: the mean (action_distributions.py:78-79)
             t_actions[it * D + k] = a;
-            lp += -((a - mu) * (a - mu)) / (2.f * (sd * sd)) - logf(sd) - 0.91893853320467274178f;
+            lp += box_logp(a, mu, sd);
         }
         for (int k = 0; k < A; ++k) t_logits[it * A + k] = z[k];
         t_logp[it] = lp;
@@ -2099,23 +1902,15 @@ __global__ __launch_bounds__(256) void k_sample_write(const float *__restrict__ 
         t_values[(int64_t)b * (T + 1) + t] = values[(int64_t)b * ldv];
         return;
     }
-    float zz[MAXA];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < MAXA; ++k) { zz[k] = k < A ? z[k] : -INFINITY; mx = fmaxf(mx, zz[k]); }
-    float se = 0.f;
-#pragma unroll
-    for (int k = 0; k < MAXA; ++k) if (k < A) se += expf(zz[k] - mx);
-    const float lse = logf(se);
+    float zz[MAXA], mx, lse;
+    reg_softmax<MAXA>(z, A, zz, mx, lse);
     int a = A - 1;
     if (deterministic) {
         bool found = false;
 #pragma unroll
         for (int k = 0; k < MAXA; ++k) if (k < A && !found && zz[k] == mx) { a = k; found = true; }
     } else {
-        uint32_t w[4];
-        sf_philox4x32_10(step, 0u, 2u, 0u, seed, row0 + (uint32_t)b, w);
-        const float u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);
+        const float u = cat_uniform(step, 0, seed, row0 + (uint32_t)b);
         float acc = 0.f;
         bool found = false;
         int last_pos = A - 1;  // last action whose probability did not underflow
@@ -2173,17 +1968,11 @@ __global__ __launch_bounds__(256) void k_sample_write_wide(const float *__restri
             const int D = -nh;
             float lpp = 0.f;
             for (int k = lane; k < D; k += 64) {
-                uint32_t w[4];
-                sf_philox4x32_10(step, (uint32_t)(k >> 1), 3u, (uint32_t)h, seed, row0 + (uint32_t)b, w);
-                const uint32_t w1 = (k & 1) ? w[2] : w[0], w2 = (k & 1) ? w[3] : w[1];
-                const float u1 = ((float)(w1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-                const float u2 = (float)(w2 >> 8) * (1.0f / 16777216.0f);
-                const float eps = sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-                const float mu = z[off + k];
-                const float sd = clampf(expf(z[off + D + k]), 1e-4f, 1e4f);
+                const float eps = box_eps(step, k, h, seed, row0 + (uint32_t)b);
+                const float mu = z[off + k], sd = box_sd(z[off + D + k]);
                 const float a = deterministic ? mu : mu + sd * eps;
                 t_actions[it * NA + aoff + k] = a;
-                lpp += -((a - mu) * (a - mu)) / (2.f * (sd * sd)) - logf(sd) - 0.91893853320467274178f;
+                lpp += box_logp(a, mu, sd);
             }
             lp_sum += wide_allsum(lpp);
             off += 2 * D; aoff += D;
@@ -2192,38 +1981,35 @@ __global__ __launch_bounds__(256) void k_sample_write_wide(const float *__restri
         const float *zh = z + off;
         // the member's slice of the row's mask: mask column c belongs to logits column c (one head: off = 0)
         const uint8_t *mh = mk ? mk + off : nullptr;
-        float mx, lse;
-        wide_lse(zh, nh, lane, mh, mx, lse);
-        // masked: probs = softmax * mask / (sum + 1e-13), an all-masked member draws from nh weights of 1e-6
-        bool all_zero = false;
-        float inv = 1.f, tot = 1.f;
+        // masked: probs = softmax * mask / (sum + 1e-13), an all-masked member draws from nh weights of 1e-6; the
+        // statistics of masked_stats, reduced over the wave
+        MaskedStats ms = {0.f, 0.f, 1.f, 1.f, 1.f, false};
+        wide_lse(zh, nh, lane, mh, ms.mx, ms.lse);
+        const float mx = ms.mx, lse = ms.lse;
         if (mh) {
             float ps = 0.f;
             for (int k = lane; k < nh; k += 64) ps += mh[k] ? expf((zh[k] - mx) - lse) : 0.f;
-            const float psum = wide_allsum(ps);
-            all_zero = psum == 0.f;
-            inv = 1.0f / (psum + 1e-13f);
-            tot = all_zero ? (float)nh * 1e-6f : psum * inv;  // multinomial normalises its weights
+            ms.psum = wide_allsum(ps);
+            ms.all_zero = ms.psum == 0.f;
+            ms.inv = 1.0f / (ms.psum + 1e-13f);
+            ms.tot = ms.all_zero ? (float)nh * 1e-6f : ms.psum * ms.inv;
         }
         int a;
         if (deterministic) {
             int first = 0x7fffffff;
             if (!mh) {  // first maximum, as torch.argmax
                 for (int k = lane; k < nh; k += 64) if (zh[k] == mx) first = min(first, k);
-            } else if (all_zero) {
+            } else if (ms.all_zero) {
                 first = 0;
             } else {  // first maximum of the masked probabilities
                 float best = -1.f;
-                for (int k = lane; k < nh; k += 64) best = fmaxf(best, mh[k] ? expf((zh[k] - mx) - lse) * inv : 0.f);
+                for (int k = lane; k < nh; k += 64) best = fmaxf(best, masked_p(ms, zh[k], mh[k]));
                 best = wide_allmax(best);
-                for (int k = lane; k < nh; k += 64)
-                    if ((mh[k] ? expf((zh[k] - mx) - lse) * inv : 0.f) == best) first = min(first, k);
+                for (int k = lane; k < nh; k += 64) if (masked_p(ms, zh[k], mh[k]) == best) first = min(first, k);
             }
             a = min(wide_allmin(first), nh - 1);  // (no maximum found: NaN logits, out of scope; stay inside the row)
         } else {
-            uint32_t w[4];
-            sf_philox4x32_10(step, (uint32_t)h, 2u, 0u, seed, row0 + (uint32_t)b, w);
-            const float u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);
+            const float u = cat_uniform(step, h, seed, row0 + (uint32_t)b);
             float carry = 0.f;
             int last_pos = -1;  // last action whose probability did not underflow
             a = -1;
@@ -2232,7 +2018,7 @@ __global__ __launch_bounds__(256) void k_sample_write_wide(const float *__restri
                 float p = 0.f;
                 if (k < nh) {
                     if (!mh) p = expf((zh[k] - mx) - lse);
-                    else p = (all_zero ? 1e-6f : (mh[k] ? expf((zh[k] - mx) - lse) * inv : 0.f)) / tot;
+                    else p = masked_p(ms, zh[k], mh[k]) / ms.tot;
                 }
                 float c = p;
 #pragma unroll
@@ -2253,7 +2039,7 @@ __global__ __launch_bounds__(256) void k_sample_write_wide(const float *__restri
             // probability, never a zero-probability (underflowed or masked-out) one
             if (a < 0) a = last_pos >= 0 ? last_pos : nh - 1;
         }
-        lp_sum += ((mh ? zh[a] + (mh[a] ? 0.f : -1e9f) : zh[a]) - mx) - lse;
+        lp_sum += mh ? masked_logp(ms, zh[a], mh[a]) : (zh[a] - mx) - lse;
         if (lane == 0) {
             t_actions[it * NA + aoff] = (float)a;
             if (env_actions) env_actions[(int64_t)b * H + h] = a;  // all-Discrete head lists only (the launchers check)
@@ -2295,7 +2081,7 @@ extern "C" int sf_sample_write_step(const float *logits, int ld_logits, const fl
     if (A >= WIDE_MIN_A)
         return sample_write_wide_launch("sf_sample_write_step", logits, ld_logits, values, ld_values, nullptr, 0, B, A, T,
                                         t, seed, step, row0, policy_version, deterministic,
-                                        wide_single_head(A, action_kind), traj_actions, traj_logits, traj_logp,
+                                        single_head(A, action_kind), traj_actions, traj_logits, traj_logp,
                                         traj_values, traj_policy_version, env_actions, stream);
     const dim3 grid((unsigned)((B + 255) / 256)), block(256);
 #define SW_LAUNCH(M)                                                                                               \
@@ -2327,40 +2113,28 @@ __global__ __launch_bounds__(256) void k_sample_write_masked(const float *__rest
     if (b >= B) return;
     const float *z = logits + (int64_t)b * ldl;
     const uint8_t *mk = mask + (int64_t)b * ldm;
-    float mx = -INFINITY;
-    for (int k = 0; k < A; ++k) mx = fmaxf(mx, z[k] + (mk[k] ? 0.f : -1e9f));
-    float se = 0.f;
-    for (int k = 0; k < A; ++k) se += expf((z[k] + (mk[k] ? 0.f : -1e9f)) - mx);
-    const float lse = logf(se);
-    float psum = 0.f;
-    for (int k = 0; k < A; ++k) psum += mk[k] ? expf(((z[k]) - mx) - lse) : 0.f;
-    const bool all_zero = psum == 0.f;
-    const float inv = 1.0f / (psum + 1e-13f);
+    const MaskedStats ms = masked_stats(z, mk, A);
     int a = A - 1;
     if (deterministic) {
         float best = -1.f;
         for (int k = 0; k < A; ++k) {
-            const float p = all_zero ? 1e-6f : (mk[k] ? expf((z[k] - mx) - lse) * inv : 0.f);
+            const float p = masked_p(ms, z[k], mk[k]);
             if (p > best) { best = p; a = k; }
         }
     } else {
-        uint32_t w[4];
-        sf_philox4x32_10(step, 0u, 2u, 0u, seed, row0 + (uint32_t)b, w);
-        const float u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);
+        const float u = cat_uniform(step, 0, seed, row0 + (uint32_t)b);
         float acc = 0.f;
-        const float tot = all_zero ? (float)A * 1e-6f : psum * inv;  // multinomial normalises its weights
         for (int k = 0; k < A; ++k) {
-            const float p = all_zero ? 1e-6f : (mk[k] ? expf((z[k] - mx) - lse) * inv : 0.f);
-            acc += p / tot;
+            acc += masked_p(ms, z[k], mk[k]) / ms.tot;
             if (u < acc) { a = k; break; }
         }
-        if (!all_zero && !mk[a]) {  // rounding left u beyond the last allowed action: take the last allowed one
+        if (!ms.all_zero && !mk[a]) {  // rounding left u beyond the last allowed action: take the last allowed one
             for (int k = A - 1; k >= 0; --k) if (mk[k]) { a = k; break; }
         }
     }
     const int64_t it = (int64_t)b * T + t;
     t_actions[it] = (float)a;
-    t_logp[it] = ((z[a] + (mk[a] ? 0.f : -1e9f)) - mx) - lse;
+    t_logp[it] = masked_logp(ms, z[a], mk[a]);
     t_version[it] = version;
     t_values[(int64_t)b * (T + 1) + t] = values[(int64_t)b * ldv];
     for (int k = 0; k < A; ++k) t_logits[it * A + k] = z[k];
@@ -2380,7 +2154,7 @@ extern "C" int sf_sample_write_step_masked(const float *logits, int ld_logits, c
     if (A >= WIDE_MIN_A)
         return sample_write_wide_launch("sf_sample_write_step_masked", logits, ld_logits, values, ld_values, action_mask,
                                         ld_mask, B, A, T, t, seed, step, row0, policy_version, deterministic,
-                                        wide_single_head(A, 0), traj_actions, traj_logits, traj_logp, traj_values,
+                                        single_head(A, 0), traj_actions, traj_logits, traj_logp, traj_values,
                                         traj_policy_version, env_actions, stream);
     k_sample_write_masked<<<dim3((unsigned)((B + 255) / 256)), dim3(256), 0, STREAM(stream)>>>(
         logits, ld_logits, values, ld_values, action_mask, ld_mask, B, A, T, t, seed, step, row0, policy_version,
@@ -2396,7 +2170,7 @@ template <bool MASKED>
 __device__ __forceinline__ void sample_write_tuple_row(const float *__restrict__ z, const uint8_t *__restrict__ mk,
                                                        const float *__restrict__ values, int ldv, int b, int A, int T,
                                                        int t, uint32_t seed, uint32_t step, uint32_t row0, float version,
-                                                       int deterministic, const LossDev &hd,
+                                                       int deterministic, const HeadsDev &hd,
                                                        float *__restrict__ t_actions, float *__restrict__ t_logits,
                                                        float *__restrict__ t_logp, float *__restrict__ t_values,
                                                        float *__restrict__ t_version,
@@ -2408,53 +2182,36 @@ __device__ __forceinline__ void sample_write_tuple_row(const float *__restrict__
     int off = 0, aoff = 0;
     for (int h = 0; h < H; ++h) {
         const int nh = hd.head_n[h];
-        if (nh < 0) {  // Box(D) member: a = mu + sd * eps, eps from Box-Muller on Philox counter (step, k / 2, 3, h)
+        if (nh < 0) {  // Box(D) member: a = mu + sd * eps
             const int D = -nh;
             for (int k = 0; k < D; ++k) {
-                uint32_t w[4];
-                sf_philox4x32_10(step, (uint32_t)(k >> 1), 3u, (uint32_t)h, seed, row0 + (uint32_t)b, w);
-                const uint32_t w1 = (k & 1) ? w[2] : w[0], w2 = (k & 1) ? w[3] : w[1];
-                const float u1 = ((float)(w1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-                const float u2 = (float)(w2 >> 8) * (1.0f / 16777216.0f);
-                const float eps = sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-                const float mu = z[off + k];
-                const float sd = clampf(expf(z[off + D + k]), 1e-4f, 1e4f);
+                const float eps = box_eps(step, k, h, seed, row0 + (uint32_t)b);
+                const float mu = z[off + k], sd = box_sd(z[off + D + k]);
                 const float a = deterministic ? mu : mu + sd * eps;
                 t_actions[it * NA + aoff + k] = a;
-                lp_sum += -((a - mu) * (a - mu)) / (2.f * (sd * sd)) - logf(sd) - 0.91893853320467274178f;
+                lp_sum += box_logp(a, mu, sd);
             }
             off += 2 * D; aoff += D;
             continue;
         }
+        const float *zh = z + off;
         int a = nh - 1;
         if constexpr (MASKED) {
-            const float *zh = z + off;
             const uint8_t *mh = mk + off;
-            float mx = -INFINITY;
-            for (int k = 0; k < nh; ++k) mx = fmaxf(mx, zh[k] + (mh[k] ? 0.f : -1e9f));
-            float se = 0.f;
-            for (int k = 0; k < nh; ++k) se += expf((zh[k] + (mh[k] ? 0.f : -1e9f)) - mx);
-            const float lse = logf(se);
-            float psum = 0.f;
-            for (int k = 0; k < nh; ++k) psum += mh[k] ? expf((zh[k] - mx) - lse) : 0.f;
-            const bool all_zero = psum == 0.f;
-            const float inv = 1.0f / (psum + 1e-13f);
+            const MaskedStats ms = masked_stats(zh, mh, nh);
             if (deterministic) {  // first maximum of the masked probabilities (an all-zero slice: nh equal weights, action 0)
                 float best = -1.f;
                 for (int k = 0; k < nh; ++k) {
-                    const float p = all_zero ? 1e-6f : (mh[k] ? expf((zh[k] - mx) - lse) * inv : 0.f);
+                    const float p = masked_p(ms, zh[k], mh[k]);
                     if (p > best) { best = p; a = k; }
                 }
             } else {
-                uint32_t w[4];
-                sf_philox4x32_10(step, (uint32_t)h, 2u, 0u, seed, row0 + (uint32_t)b, w);
-                const float u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);
-                const float tot = all_zero ? (float)nh * 1e-6f : psum * inv;  // multinomial normalises its weights
+                const float u = cat_uniform(step, h, seed, row0 + (uint32_t)b);
                 float acc = 0.f;
                 int last_pos = -1;  // last action with any probability (allowed, not underflowed)
                 bool found = false;
                 for (int k = 0; k < nh; ++k) {
-                    const float p = (all_zero ? 1e-6f : (mh[k] ? expf((zh[k] - mx) - lse) * inv : 0.f)) / tot;
+                    const float p = masked_p(ms, zh[k], mh[k]) / ms.tot;
                     acc += p;
                     if (p > 0.f) last_pos = k;
                     if (u < acc) { a = k; found = true; break; }  // (acc only moves where p > 0: never a masked-out k)
@@ -2462,31 +2219,26 @@ __device__ __forceinline__ void sample_write_tuple_row(const float *__restrict__
                 // rounding left u beyond the last allowed action: take the last allowed one
                 if (!found && last_pos >= 0) a = last_pos;
             }
-            lp_sum += ((zh[a] + (mh[a] ? 0.f : -1e9f)) - mx) - lse;
+            lp_sum += masked_logp(ms, zh[a], mh[a]);
         } else {
-            float mx = -INFINITY;
-            for (int k = 0; k < nh; ++k) mx = fmaxf(mx, z[off + k]);
-            float se = 0.f;
-            for (int k = 0; k < nh; ++k) se += expf(z[off + k] - mx);
-            const float lse = logf(se);
+            float mx, lse;
+            cat_lse(zh, nh, mx, lse);
             if (deterministic) {
-                for (int k = nh - 1; k >= 0; --k) if (z[off + k] == mx) a = k;  // first maximum, as torch.argmax
+                for (int k = nh - 1; k >= 0; --k) if (zh[k] == mx) a = k;  // first maximum, as torch.argmax
             } else {
-                uint32_t w[4];
-                sf_philox4x32_10(step, (uint32_t)h, 2u, 0u, seed, row0 + (uint32_t)b, w);
-                const float u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);
+                const float u = cat_uniform(step, h, seed, row0 + (uint32_t)b);
                 float acc = 0.f;
                 int last_pos = nh - 1;
                 bool found = false;
                 for (int k = 0; k < nh; ++k) {
-                    const float p = expf((z[off + k] - mx) - lse);
+                    const float p = expf((zh[k] - mx) - lse);
                     acc += p;
                     if (p > 0.f) last_pos = k;
                     if (u < acc) { a = k; found = true; break; }
                 }
                 if (!found) a = last_pos;  // rounding left u beyond the CDF: the last action with non-zero probability
             }
-            lp_sum += (z[off + a] - mx) - lse;
+            lp_sum += (zh[a] - mx) - lse;
         }
         t_actions[it * NA + aoff] = (float)a;
         if (env_actions) env_actions[(int64_t)b * H + h] = a;  // all-Discrete tuples only (the launcher checks)
@@ -2501,7 +2253,7 @@ __device__ __forceinline__ void sample_write_tuple_row(const float *__restrict__
 __global__ __launch_bounds__(256) void k_sample_write_tuple(const float *__restrict__ logits, int ldl,
                                                             const float *__restrict__ values, int ldv, int B, int A, int T,
                                                             int t, uint32_t seed, uint32_t step, uint32_t row0,
-                                                            float version, int deterministic, LossDev hd,
+                                                            float version, int deterministic, HeadsDev hd,
                                                             float *__restrict__ t_actions, float *__restrict__ t_logits,
                                                             float *__restrict__ t_logp, float *__restrict__ t_values,
                                                             float *__restrict__ t_version,
@@ -2517,7 +2269,7 @@ __global__ __launch_bounds__(256) void k_sample_write_masked_tuple(const float *
                                                                    const uint8_t *__restrict__ mask, int64_t ldm, int B,
                                                                    int A, int T, int t, uint32_t seed, uint32_t step,
                                                                    uint32_t row0, float version, int deterministic,
-                                                                   LossDev hd, float *__restrict__ t_actions,
+                                                                   HeadsDev hd, float *__restrict__ t_actions,
                                                                    float *__restrict__ t_logits, float *__restrict__ t_logp,
                                                                    float *__restrict__ t_values,
                                                                    float *__restrict__ t_version,
@@ -2529,37 +2281,52 @@ __global__ __launch_bounds__(256) void k_sample_write_masked_tuple(const float *
                                  env_actions);
 }
 
+// sf_sample_write_step_tuple (action_mask = nullptr) and sf_sample_write_step_tuple_masked: `what` names the entry point
+// in the messages.  Every check comes before the launch.
+static int sample_write_tuple_launch(const char *what, const float *logits, int ld_logits, const float *values,
+                                     int ld_values, const uint8_t *action_mask, int64_t ld_mask, int B, int num_heads,
+                                     const int32_t *head_n, int T, int t, uint32_t seed, uint32_t step, uint32_t row0,
+                                     float policy_version, int deterministic, float *traj_actions, float *traj_logits,
+                                     float *traj_logp, float *traj_values, float *traj_policy_version,
+                                     int32_t *env_actions, void *stream) {
+    SF_REQUIRE(logits && values && head_n && traj_actions && traj_logits && traj_logp && traj_values &&
+                   traj_policy_version, "%s: null pointer", what);
+    SF_REQUIRE(B > 0 && T > 0 && t >= 0 && t < T, "%s: bad shape heads=%d B=%d T=%d t=%d", what, num_heads, B, T, t);
+    HeadsDev hd = {};
+    bool any_box;
+    const int A = heads_from_host(what, head_n, num_heads, SF_MAX_ACTION_HEADS, hd.head_n, &any_box);
+    if (A < 0) return SF_ERR_ARG;
+    hd.num_heads = num_heads;
+    SF_REQUIRE(!any_box || !env_actions,
+               "%s: a tuple with a Box member has no int32 env_actions (the env reads the trajectory's f32 action row)",
+               what);
+    SF_REQUIRE(!action_mask || ld_mask >= A,
+               "%s: ld_mask=%lld, the mask has one column per distribution parameter (A=%d)", what, (long long)ld_mask, A);
+    SF_REQUIRE(ld_logits >= A && ld_values >= 1, "%s: bad strides", what);
+    if (A >= WIDE_MIN_A)
+        return sample_write_wide_launch(what, logits, ld_logits, values, ld_values, action_mask, ld_mask, B, A, T, t, seed,
+                                        step, row0, policy_version, deterministic, hd, traj_actions, traj_logits,
+                                        traj_logp, traj_values, traj_policy_version, env_actions, stream);
+    const dim3 grid((unsigned)((B + 255) / 256)), block(256);
+    if (action_mask)
+        k_sample_write_masked_tuple<<<grid, block, 0, STREAM(stream)>>>(
+            logits, ld_logits, values, ld_values, action_mask, ld_mask, B, A, T, t, seed, step, row0, policy_version,
+            deterministic, hd, traj_actions, traj_logits, traj_logp, traj_values, traj_policy_version, env_actions);
+    else
+        k_sample_write_tuple<<<grid, block, 0, STREAM(stream)>>>(
+            logits, ld_logits, values, ld_values, B, A, T, t, seed, step, row0, policy_version, deterministic, hd,
+            traj_actions, traj_logits, traj_logp, traj_values, traj_policy_version, env_actions);
+    return sf_launch_status(what);
+}
+
 extern "C" int sf_sample_write_step_tuple(const float *logits, int ld_logits, const float *values, int ld_values, int B,
                                           int num_heads, const int32_t *head_n, int T, int t, uint32_t seed,
                                           uint32_t step, uint32_t row0, float policy_version, int deterministic,
                                           float *traj_actions, float *traj_logits, float *traj_logp, float *traj_values,
                                           float *traj_policy_version, int32_t *env_actions, void *stream) {
-    SF_REQUIRE(logits && values && head_n && traj_actions && traj_logits && traj_logp && traj_values &&
-                   traj_policy_version, "sf_sample_write_step_tuple: null pointer");
-    SF_REQUIRE(B > 0 && T > 0 && t >= 0 && t < T, "sf_sample_write_step_tuple: bad shape heads=%d B=%d T=%d t=%d",
-               num_heads, B, T, t);
-    LossDev hd = {};
-    bool any_box;
-    const int A = heads_from_host("sf_sample_write_step_tuple", head_n, num_heads, SF_MAX_ACTION_HEADS, hd.head_n,
-                                  &any_box);
-    if (A < 0) return SF_ERR_ARG;
-    hd.num_heads = num_heads;
-    SF_REQUIRE(!any_box || !env_actions,
-               "sf_sample_write_step_tuple: a tuple with a Box member has no int32 env_actions (the env reads the "
-               "trajectory's f32 action row)");
-    SF_REQUIRE(ld_logits >= A && ld_values >= 1, "sf_sample_write_step_tuple: bad strides");
-    if (A >= WIDE_MIN_A) {
-        HeadsDev whd = {};
-        whd.num_heads = num_heads;
-        for (int i = 0; i < num_heads; ++i) whd.head_n[i] = head_n[i];
-        return sample_write_wide_launch("sf_sample_write_step_tuple", logits, ld_logits, values, ld_values, nullptr, 0, B,
-                                        A, T, t, seed, step, row0, policy_version, deterministic, whd, traj_actions,
-                                        traj_logits, traj_logp, traj_values, traj_policy_version, env_actions, stream);
-    }
-    k_sample_write_tuple<<<dim3((unsigned)((B + 255) / 256)), dim3(256), 0, STREAM(stream)>>>(
-        logits, ld_logits, values, ld_values, B, A, T, t, seed, step, row0, policy_version, deterministic, hd,
-        traj_actions, traj_logits, traj_logp, traj_values, traj_policy_version, env_actions);
-    return sf_launch_status("sf_sample_write_step_tuple");
+    return sample_write_tuple_launch("sf_sample_write_step_tuple", logits, ld_logits, values, ld_values, nullptr, 0, B,
+                                     num_heads, head_n, T, t, seed, step, row0, policy_version, deterministic, traj_actions,
+                                     traj_logits, traj_logp, traj_values, traj_policy_version, env_actions, stream);
 }
 
 // sf_sample_write_step_tuple under obs["action_mask"]: u8 [B, A], one column per distribution parameter
@@ -2571,35 +2338,10 @@ extern "C" int sf_sample_write_step_tuple_masked(const float *logits, int ld_log
                                                  float *traj_values, float *traj_policy_version, int32_t *env_actions,
                                                  void *stream) {
     SF_REQUIRE(action_mask, "sf_sample_write_step_tuple_masked: null action_mask");
-    SF_REQUIRE(logits && values && head_n && traj_actions && traj_logits && traj_logp && traj_values &&
-                   traj_policy_version, "sf_sample_write_step_tuple_masked: null pointer");
-    SF_REQUIRE(B > 0 && T > 0 && t >= 0 && t < T,
-               "sf_sample_write_step_tuple_masked: bad shape heads=%d B=%d T=%d t=%d", num_heads, B, T, t);
-    LossDev hd = {};
-    bool any_box;
-    const int A = heads_from_host("sf_sample_write_step_tuple_masked", head_n, num_heads, SF_MAX_ACTION_HEADS, hd.head_n,
-                                  &any_box);
-    if (A < 0) return SF_ERR_ARG;
-    hd.num_heads = num_heads;
-    SF_REQUIRE(!any_box || !env_actions,
-               "sf_sample_write_step_tuple_masked: a tuple with a Box member has no int32 env_actions (the env reads the "
-               "trajectory's f32 action row)");
-    SF_REQUIRE(ld_mask >= A, "sf_sample_write_step_tuple_masked: ld_mask=%lld, the mask has one column per distribution "
-               "parameter (A=%d)", (long long)ld_mask, A);
-    SF_REQUIRE(ld_logits >= A && ld_values >= 1, "sf_sample_write_step_tuple_masked: bad strides");
-    if (A >= WIDE_MIN_A) {
-        HeadsDev whd = {};
-        whd.num_heads = num_heads;
-        for (int i = 0; i < num_heads; ++i) whd.head_n[i] = head_n[i];
-        return sample_write_wide_launch("sf_sample_write_step_tuple_masked", logits, ld_logits, values, ld_values,
-                                        action_mask, ld_mask, B, A, T, t, seed, step, row0, policy_version, deterministic,
-                                        whd, traj_actions, traj_logits, traj_logp, traj_values, traj_policy_version,
-                                        env_actions, stream);
-    }
-    k_sample_write_masked_tuple<<<dim3((unsigned)((B + 255) / 256)), dim3(256), 0, STREAM(stream)>>>(
-        logits, ld_logits, values, ld_values, action_mask, ld_mask, B, A, T, t, seed, step, row0, policy_version,
-        deterministic, hd, traj_actions, traj_logits, traj_logp, traj_values, traj_policy_version, env_actions);
-    return sf_launch_status("sf_sample_write_step_tuple_masked");
+    return sample_write_tuple_launch("sf_sample_write_step_tuple_masked", logits, ld_logits, values, ld_values, action_mask,
+                                     ld_mask, B, num_heads, head_n, T, t, seed, step, row0, policy_version, deterministic,
+                                     traj_actions, traj_logits, traj_logp, traj_values, traj_policy_version, env_actions,
+                                     stream);
 }
 
 // =========================================================================================== K1/K6 env step -> traj

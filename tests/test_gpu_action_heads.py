@@ -13,12 +13,14 @@ parameters: logits, or 2 * D for Box(D)).  Which case reaches which instantiatio
   k_sample_write    discrete A in {1,2,7,8}        discrete A in {9,31,32}        discrete A in {33,64,127,128}
                     continuous D in {1,4}          continuous D in {5,16}         continuous D = 64
                     zero-probability sweep 2..8    sweep 9..32                    sweep 33..128
-  k_vtrace(_ratio)  discrete A = 8, cont. D in     discrete A = 32, cont. D = 16  discrete A = 128, cont. D = 64
-                    {1,3}                          tuple [3,-2,5] (A = 12)        tuple [100,-3,7,5,1,-1,3] (A = 124)
+  k_vtrace_ratio    discrete A = 8, cont. D in     discrete A = 32, cont. D = 16  discrete A = 128, cont. D = 64
+  (then k_vtrace,   {1,3}                          tuple [3,-2,5] (A = 12)        tuple [100,-3,7,5,1,-1,3] (A = 124)
+  one kernel)
   k_ppo_loss        discrete A in {2,7,8},         discrete A in {9,32},          discrete A in {33,128},
                     cont. D in {1,4}               cont. D in {5,16}              cont. D = 64
-  k_ppo_loss_md     (not templated) tuples [3,-2,5], [7,4,2] (symmetric KL) and an 8-member tuple with Discrete(100)
-  masked / tuple    (not templated) masked A in {2,33,128}; tuples with 2 and 8 heads
+  k_ppo_loss_md     (no MAXA: the members' statistics kept in the lane, ppo_loss_tuple<true>) tuples [3,-2,5], [7,4,2]
+                    (symmetric KL) and an 8-member tuple with Discrete(100)
+  masked / tuple    (no MAXA) masked A in {2,33,128}; tuples with 2 and 8 heads
 
 Out of scope: Discrete spaces wider than 128 (every kernel refuses them with SfHipError) and NaN logits."""
 import math
