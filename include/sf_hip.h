@@ -178,6 +178,35 @@ int sf_ppo_loss_heads(const float *params, int ld_params, const float *values, i
                       const float *targets, const uint8_t *valids, const int32_t *index, int64_t offset, int64_t n, int A,
                       const sf_loss_cfg *h_cfg, const double *moments, double *sums, float *g_params, float *g_values,
                       float *ratio_out, const int32_t *head_n /* host */, int num_heads, void *stream);
+/* Training under the action mask the rows were SAMPLED under (the reference's
+ * CategoricalActionDistribution(raw_logits, action_mask), action_distributions.py:84-180, which its learner never hands
+ * the mask).  Per Discrete member with logits slice z and mask slice m, the rule of sf_sample_write_step_masked:
+ *   logp_k = ((z_k + (m_k ? 0 : -1e9f)) - mx) - lse;   p_k = m_k ? exp((z_k - mx) - lse) / (sum of those + 1e-13) : 0
+ * (the sampler's 1e-6 multinomial weights are no part of the loss); member log-prob logp_a, entropy -sum p_k logp_k,
+ * KL(new || old) = sum p_k (logp_k - logp_old_k) with the OLD distribution built from old_params under the SAME mask row;
+ * row quantities are sums over the members; a Box(D) member never reads the 2 D mask columns under it.  The gradient is
+ * the analytic derivative: d logp_a / dz_k = delta_ak - exp(logp_k), exactly 0 on a masked-out column of a slice that
+ * allows something; an all-zero slice behaves as n equal logits (|z| < 32 is absorbed by z - 1e9 in f32) with p = 0,
+ * entropy 0, KL 0 and gradient delta_ak - 1 / n.
+ * mask: u8, row stride ld_mask >= A, column c belonging to parameter column c.  mask_T > 0: the trajectory slab's
+ * [E, mask_T + 1, A] array read in place, dataset row e * T + t at mask row e * (T + 1) + t (as old_values_T);
+ * mask_T == 0: a flat [N, ld_mask] array.  Rows go through index / offset like every dataset array.
+ * sf_ppo_loss_masked takes the member list as sf_ppo_loss_heads does (one member: Discrete(A)); both refuse, before any
+ * launch or memset (SF_ERR_ARG): a null mask, ld_mask < A, mask_T < 0, a pure Box space, every head list the unmasked
+ * entry refuses, and (the loss) symmetric-KL exploration with a non-zero coefficient, whose uniform-prior term
+ * u (log u - logp_k) has no meaning where logp_k is about -1e9. */
+int sf_ppo_loss_masked(const float *params, int ld_params, const float *values, int ld_values, const float *actions,
+                       const float *old_logp, const float *old_params, const float *old_values, const float *adv,
+                       const float *targets, const uint8_t *valids, const int32_t *index, int64_t offset, int64_t n, int A,
+                       const sf_loss_cfg *h_cfg, const double *moments, double *sums, float *g_params, float *g_values,
+                       float *ratio_out, const int32_t *head_n /* host */, int num_heads, const uint8_t *mask,
+                       int64_t ld_mask, int mask_T, void *stream);
+/* sf_vtrace with the importance ratios taken under the mask (rule and mask addressing above); k_vtrace is unchanged. */
+int sf_vtrace_masked(const float *params, int ld_params, const float *values, int ld_values, const float *actions,
+                     const float *old_logp, const float *rewards, const uint8_t *dones, const int32_t *index,
+                     int64_t offset, int64_t n, int A, int action_kind, int recurrence, float gamma, float rho_hat,
+                     float c_hat, float *vs, float *adv, const int32_t *head_n /* host, or NULL */, int num_heads,
+                     const uint8_t *mask, int64_t ld_mask, int mask_T, void *stream);
 /* out[0..3] = policy, exploration, kl, value losses; [4] kl mean; [5] kl max; [6] adv mean; [7] adv std;
  * [8] n_valid; [9] entropy (or symkl) mean — device float[16]. */
 int sf_loss_scalars(const double *sums, const double *moments, const sf_loss_cfg *h_cfg, float *out, void *stream);

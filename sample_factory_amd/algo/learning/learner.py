@@ -40,6 +40,7 @@ from sample_factory_amd.model.actor_critic import ActorCritic
 from sample_factory_amd.model.model_factory import create_actor_critic
 from sample_factory_amd.utils.attr_dict import AttrDict
 from sample_factory_amd.utils.decay import LinearDecay
+from sample_factory_amd.utils.utils import log
 
 LEARNER_ENV_STEPS, POLICY_ID_KEY, STATS_KEY, TRAIN_STATS = "learner_env_steps", "policy_id", "stats", "train"
 
@@ -175,6 +176,7 @@ class Learner:
         cfg = self.cfg
         if cfg.exploration_loss not in ("entropy", "symmetric_kl"):
             raise NotImplementedError(f"{cfg.exploration_loss} not supported!")
+        self._loss_mask_on = self._mask_in_loss(cfg, self.env_info)
         if cfg.optimizer not in ("adam", "lamb"):
             raise RuntimeError(f"Unknown optimizer {cfg.optimizer}")  # learner.py:228-230
         if cfg.seed is not None:
@@ -229,6 +231,25 @@ class Learner:
         self.is_initialized = True
         state_dict = None if cfg.serial_mode else self.actor_critic.state_dict()
         return self.policy_id, state_dict, self.device, self.train_step
+
+    @staticmethod
+    def _mask_in_loss(cfg, env_info) -> bool:
+        """cfg.mask_actions_in_loss: True when the loss and V-trace run under obs["action_mask"].  The
+        flag without a mask in the observation space is logged once and runs the plain path; with a mask, the
+        symmetric-KL exploration loss is refused: its uniform-prior term u (log u - logp_k) meets logp_k of about -1e9 on
+        the masked-out columns and has no usable meaning there."""
+        if not getattr(cfg, "mask_actions_in_loss", False):
+            return False
+        obs_space = getattr(env_info, "obs_space", None)
+        keys = getattr(obs_space, "spaces", obs_space)
+        if keys is None or "action_mask" not in keys:
+            log.warning("mask_actions_in_loss=True, but the env's observation space has no 'action_mask': "
+                        "training runs the plain (unmasked) loss")
+            return False
+        if cfg.exploration_loss == "symmetric_kl" and cfg.exploration_loss_coeff != 0.0:
+            raise ValueError("mask_actions_in_loss=True does not support exploration_loss=symmetric_kl (the uniform-prior "
+                             "term has no meaning on masked-out actions); use exploration_loss=entropy")
+        return True
 
     @staticmethod
     def checkpoint_dir(cfg, policy_id):
@@ -429,6 +450,8 @@ class Learner:
         buff["values"] = batch["values"]  # [E, T+1], row e*T+t at e*(T+1)+t; NB: item access, AttrDict.values is dict.values
         buff.valids = valids_flat
         buff.E, buff.T = E, T
+        if getattr(self, "_loss_mask_on", False):
+            buff.action_mask = batch["obs"]["action_mask"]  # the slab's [E, T+1, A] view, read in place (mask_T = T)
         if cfg.normalize_returns and not cfg.with_vtrace:
             ac.returns_normalizer(buff.returns)  # in place: update (all-reduced moments under DP) + normalise
         num_invalids = int(self._num_invalid.item())  # the one host sync per dataset (reference: learner.py:1021)
@@ -493,10 +516,12 @@ class Learner:
         heads = acts[-1]
         A = self.num_action_params
         space = self.env_info.action_space
-        dist = get_action_distribution(space, heads[:n, 1:1 + A])
-        dist.raw_logits, dist.values = heads[:n, 1:1 + A], heads[:n, 0]
         rows = index.long() if index is not None else torch.arange(offset, offset + n, device=self.device)
-        kl_old = dist.kl_divergence(get_action_distribution(space, buff.action_logits[rows]))[buff.valids[rows]]
+        mask = buff.get("action_mask")  # cfg.mask_actions_in_loss: the object and the kernel scalars under one mask
+        mrows = None if mask is None else mask[:, :buff.T].reshape(buff.E * buff.T, -1)[rows]
+        dist = get_action_distribution(space, heads[:n, 1:1 + A], mrows)
+        dist.raw_logits, dist.values = heads[:n, 1:1 + A], heads[:n, 0]
+        kl_old = dist.kl_divergence(get_action_distribution(space, buff.action_logits[rows], mrows))[buff.valids[rows]]
         summaries = AttrDict(adv_mean=sc[6], adv_std=sc[7], num_valid=sc[8], entropy=sc[9], kl_divergence_max=sc[5],
                              kl_old_mean=sc[4].clone(), ratio=self._ratio[:n], values=heads[:n, 0], g_heads=g_heads)
         return dist, sc[0].clone(), sc[1].clone(), kl_old, sc[2].clone(), sc[3].clone(), summaries
@@ -533,12 +558,15 @@ class Learner:
         ld = ac.heads_ld  # 1 + A padded to a multiple of 4; padding columns of g_heads stay zero
         params, values = heads[:, 1:], heads[:, 0]
         g_heads = ac._zbuf(("g", "heads"), (n, ld))
+        # cfg.mask_actions_in_loss: V-trace ratios and the loss under the mask the rows were sampled under
+        mask = buff.get("action_mask")
+        mkw = dict(mask=mask, mask_T=buff.T) if mask is not None else {}
         if cfg.with_vtrace:
             vs = ac._buf(("vt", "vs"), (n,))
             adv = ac._buf(("vt", "adv"), (n,))
             lib.vtrace(params, ld, values, ld, buff.actions, buff.log_prob_actions, buff.rewards, buff.dones, index,
                        offset, n, A, self.loss_cfg.action_kind, cfg.recurrence, cfg.gamma, cfg.vtrace_rho,
-                       cfg.vtrace_c, vs, adv, head_sizes=self._head_sizes)
+                       cfg.vtrace_c, vs, adv, head_sizes=self._head_sizes, **mkw)
             lib.moments(adv, buff.valids, index, n, self._moments, offset=offset, dense_x=True)
             adv_arr, tgt_arr = adv, vs
         elif moments is None:
@@ -556,7 +584,7 @@ class Learner:
         self.loss_cfg.old_values_T = buff.T  # buff["values"] is the slab's [E, T+1] array
         lib.ppo_loss(params, ld, values, ld, buff.actions, buff.log_prob_actions, buff.action_logits, buff["values"],
                      adv_arr, tgt_arr, buff.valids, index, offset, n, A, self.loss_cfg, moments, self._sums,
-                     g_heads[:, 1:], g_heads[:, 0], ratio_out=self._ratio, head_sizes=self._head_sizes)
+                     g_heads[:, 1:], g_heads[:, 0], ratio_out=self._ratio, head_sizes=self._head_sizes, **mkw)
         self._last_mb = (index, offset, n, values, adv_arr)  # for _record_summaries
         if self.dp and self._dp_reduce_each_mb:  # only the per-minibatch KL-adaptive LR needs global values NOW
             self.group.loss_sums(self._sums)

@@ -80,6 +80,9 @@ ENGINE_FLAGS = [
     #                                          rollout workers), "inline" = in this process, "auto" = processes iff
     #                                          serial_mode=False and the env is a host env (algo/sampling/parallel_env.py)
     ("env_worker_start_method", str, "spawn"),  # multiprocessing start method of the env workers
+    ("mask_actions_in_loss", _bool, False),  # an env with obs["action_mask"] is TRAINED under the mask too: PPO loss and
+    #                                          V-trace ratios on the distribution the sampler drew from (DESIGN.md 3.10.4;
+    #                                          off: the reference's behaviour, the learner never sees the mask)
 ]
 
 

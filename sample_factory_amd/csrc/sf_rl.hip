@@ -439,6 +439,53 @@ __device__ __forceinline__ float masked_p(const MaskedStats &s, float zk, uint8_
 __device__ __forceinline__ float masked_logp(const MaskedStats &s, float zk, uint8_t allowed) {
     return ((zk + (allowed ? 0.f : -1e9f)) - s.mx) - s.lse;
 }
+// Training under the mask: the reference's `probs` of a column, softmax * mask / (sum + 1e-13).  The
+// 1e-6 weights of masked_p are the sampler's multinomial guard and no part of the loss: an all-zero slice has p = 0.
+__device__ __forceinline__ float masked_prob(const MaskedStats &s, float zk, uint8_t allowed) {
+    return allowed ? expf((zk - s.mx) - s.lse) * s.inv : 0.f;
+}
+// a mask row of dataset row d: the slab's [E, mask_T + 1, A] array read in place (mask_T > 0, the mapping of ov_row),
+// or the flat [N, ldm] array
+__device__ __forceinline__ const uint8_t *mask_row(const uint8_t *__restrict__ mask, int64_t ldm, int mask_T, int64_t d) {
+    return mask + (mask_T > 0 ? d + d / mask_T : d) * ldm;
+}
+// Discrete(nh) member in the masked loss, one lane per row (cat_terms under a mask; no symmetric-KL terms: the masked
+// entry points refuse that loss): statistics of the current and of the old logits under the SAME mask slice, entropy
+// -sum p lp, KL sum p (lp - lp_old) and the log-prob of `act`
+struct MaskedCatTerms {
+    MaskedStats s, so;
+    float ent, kl, lpa;
+};
+__device__ __forceinline__ MaskedCatTerms masked_cat_terms(const float *__restrict__ z, const float *__restrict__ zo,
+                                                           const uint8_t *__restrict__ mk, int nh, int act) {
+    MaskedCatTerms t;
+    t.s = masked_stats(z, mk, nh);
+    t.so = masked_stats(zo, mk, nh);
+    float lpa = 0.f, e = 0.f, kk = 0.f;
+    for (int k = 0; k < nh; ++k) {
+        const float lp = masked_logp(t.s, z[k], mk[k]), p = masked_prob(t.s, z[k], mk[k]);
+        const float q = masked_logp(t.so, zo[k], mk[k]);
+        if (k == act) lpa = lp;
+        e -= p * lp;
+        kk += p * (lp - q);
+    }
+    t.ent = e; t.kl = kk; t.lpa = lpa;
+    return t;
+}
+// gradient of one column of a masked Discrete member: d logp_a / dz_k = delta_ak - exp(lp_k) on every column (exp(-1e9)
+// is 0: exactly zero on a masked-out column of a slice that allows something, delta - 1 / n on an all-zero slice); the
+// entropy and KL terms carry p_k and vanish with it
+__device__ __forceinline__ float masked_cat_grad(float zk, float zok, uint8_t allowed, bool taken, float mx, float lse,
+                                                 float inv, float mxo, float lseo, float ent, float kl, float dL_dlogp,
+                                                 float inv_n, const LossDev &h) {
+    const float off = allowed ? 0.f : -1e9f;
+    const float lp = ((zk + off) - mx) - lse, q = ((zok + off) - mxo) - lseo;
+    const float p = allowed ? expf((zk - mx) - lse) * inv : 0.f;
+    float gk = dL_dlogp * ((taken ? 1.f : 0.f) - expf(lp));
+    if (h.expl_kind == 1) gk += h.expl_coeff * inv_n * (p * (lp + ent));
+    if (h.kl_coeff != 0.f) gk += h.kl_coeff * inv_n * (p * ((lp - q) - kl));
+    return gk;
+}
 
 // log-prob of the taken action under the current policy, for one sample (used by v-trace and the loss head).
 template <int MAXA>
@@ -491,8 +538,15 @@ __device__ __host__ __forceinline__ int heads_action_cols(const int *head_n, int
     for (int h = 0; h < num_heads; ++h) c += head_n[h] > 0 ? 1 : -head_n[h];
     return c;
 }
+static bool heads_any_discrete(const HeadsDev &hd) {
+    for (int h = 0; h < hd.num_heads; ++h) if (hd.head_n[h] > 0) return true;
+    return false;
+}
 // log-prob of a Tuple action: sum over the members of log_softmax(z_h)[a_h] (Discrete) / Normal log-density (Box, head_n = -D)
-__device__ __forceinline__ float tuple_logp(const float *__restrict__ z, const float *__restrict__ act, const HeadsDev &hd) {
+// MASKED: a Discrete member's log-prob is the masked log-softmax on its slice of the mask row mk
+template <bool MASKED>
+__device__ __forceinline__ float tuple_logp(const float *__restrict__ z, const float *__restrict__ act, const HeadsDev &hd,
+                                            const uint8_t *__restrict__ mk) {
     float lp = 0.f;
     int off = 0, aoff = 0;
     for (int h = 0; h < hd.num_heads; ++h) {
@@ -503,9 +557,15 @@ __device__ __forceinline__ float tuple_logp(const float *__restrict__ z, const f
             off += 2 * D; aoff += D;
             continue;
         }
-        float mx, lse;
-        cat_lse(z + off, nh, mx, lse);
-        lp += (z[off + (int)act[aoff]] - mx) - lse;
+        if constexpr (MASKED) {
+            const MaskedStats ms = masked_stats(z + off, mk + off, nh);
+            const int a = min(max((int)act[aoff], 0), nh - 1);  // (a recorded action is in range; never read past the slice)
+            lp += masked_logp(ms, z[off + a], mk[off + a]);
+        } else {
+            float mx, lse;
+            cat_lse(z + off, nh, mx, lse);
+            lp += (z[off + (int)act[aoff]] - mx) - lse;
+        }
         off += nh; aoff += 1;
     }
     return lp;
@@ -569,12 +629,14 @@ static HeadsDev single_head(int A, int action_kind) {
     return hd;
 }
 
-// k_vtrace_ratio for A > 128: log-prob of the taken action, one wave per row
-__global__ __launch_bounds__(256) void k_vtrace_ratio_wide(const float *__restrict__ params, int ldp,
-                                                           const float *__restrict__ actions,
-                                                           const float *__restrict__ old_logp,
-                                                           const int32_t *__restrict__ index, int64_t offset, int64_t n,
-                                                           float *__restrict__ ratio_out, HeadsDev hd) {
+// k_vtrace_ratio for A > 128: log-prob of the taken action, one wave per row.  MASKED: a Discrete member's log-sum-exp
+// runs under its slice of the row's mask (wide_lse's rule), and so does the taken action's log-prob.
+template <bool MASKED>
+__device__ __forceinline__ void vtrace_ratio_wide(const float *__restrict__ params, int ldp,
+                                                  const float *__restrict__ actions, const float *__restrict__ old_logp,
+                                                  const int32_t *__restrict__ index, int64_t offset, int64_t n,
+                                                  float *__restrict__ ratio_out, const HeadsDev &hd,
+                                                  const uint8_t *__restrict__ mask, int64_t ldm, int mask_T) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t k = (int64_t)blockIdx.x * WIDE_ROWS + wave;
     if (k >= n) return;
@@ -594,12 +656,37 @@ __global__ __launch_bounds__(256) void k_vtrace_ratio_wide(const float *__restri
             continue;
         }
         float mx, lse;
-        wide_lse(z + off, nh, lane, nullptr, mx, lse);
-        const int a = min(max((int)act[aoff], 0), nh - 1);  // (a recorded action is in range; never read past the row)
-        lp += (z[off + a] - mx) - lse;
+        if constexpr (MASKED) {
+            const uint8_t *mk = mask_row(mask, ldm, mask_T, d) + off;
+            wide_lse(z + off, nh, lane, mk, mx, lse);
+            const int a = min(max((int)act[aoff], 0), nh - 1);
+            lp += ((z[off + a] + (mk[a] ? 0.f : -1e9f)) - mx) - lse;
+        } else {
+            wide_lse(z + off, nh, lane, nullptr, mx, lse);
+            const int a = min(max((int)act[aoff], 0), nh - 1);  // (a recorded action is in range; never read past the row)
+            lp += (z[off + a] - mx) - lse;
+        }
         off += nh; aoff += 1;
     }
     if (lane == 0) ratio_out[k] = clampf(expf(lp - old_logp[d]), 0.05f, 20.0f);
+}
+
+__global__ __launch_bounds__(256) void k_vtrace_ratio_wide(const float *__restrict__ params, int ldp,
+                                                           const float *__restrict__ actions,
+                                                           const float *__restrict__ old_logp,
+                                                           const int32_t *__restrict__ index, int64_t offset, int64_t n,
+                                                           float *__restrict__ ratio_out, HeadsDev hd) {
+    vtrace_ratio_wide<false>(params, ldp, actions, old_logp, index, offset, n, ratio_out, hd, nullptr, 0, 0);
+}
+
+__global__ __launch_bounds__(256) void k_masked_vtrace_ratio_wide(const float *__restrict__ params, int ldp,
+                                                                  const float *__restrict__ actions,
+                                                                  const float *__restrict__ old_logp,
+                                                                  const int32_t *__restrict__ index, int64_t offset,
+                                                                  int64_t n, float *__restrict__ ratio_out, HeadsDev hd,
+                                                                  const uint8_t *__restrict__ mask, int64_t ldm,
+                                                                  int mask_T) {
+    vtrace_ratio_wide<true>(params, ldp, actions, old_logp, index, offset, n, ratio_out, hd, mask, ldm, mask_T);
 }
 
 // phase 1 (parallel over samples): clamped importance ratio pi/pi_old of every step -> ratio_out[k]
@@ -613,9 +700,24 @@ __global__ __launch_bounds__(256) void k_vtrace_ratio(const float *__restrict__ 
     if (k >= n) return;
     const int nact = hd.num_heads > 1 ? heads_action_cols(hd.head_n, hd.num_heads) : (action_kind == 0 ? 1 : A / 2);
     const int64_t d = index ? (int64_t)index[k] : offset + k;
-    const float lp = hd.num_heads > 1 ? tuple_logp(params + k * ldp, actions + d * nact, hd)
+    const float lp = hd.num_heads > 1 ? tuple_logp<false>(params + k * ldp, actions + d * nact, hd, nullptr)
                                       : action_logp<MAXA>(params + k * ldp, A, action_kind, actions + d * nact);
     ratio_out[k] = clampf(expf(lp - old_logp[d]), 0.05f, 20.0f);  // learner.py:591-594
+}
+
+// k_vtrace_ratio under an action mask, A <= 128: any head list, a plain Discrete(A) as a one-member list
+__global__ __launch_bounds__(256) void k_masked_vtrace_ratio(const float *__restrict__ params, int ldp,
+                                                             const float *__restrict__ actions,
+                                                             const float *__restrict__ old_logp,
+                                                             const int32_t *__restrict__ index, int64_t offset, int64_t n,
+                                                             float *__restrict__ ratio_out, HeadsDev hd,
+                                                             const uint8_t *__restrict__ mask, int64_t ldm, int mask_T) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const int nact = heads_action_cols(hd.head_n, hd.num_heads);
+    const int64_t d = index ? (int64_t)index[k] : offset + k;
+    const float lp = tuple_logp<true>(params + k * ldp, actions + d * nact, hd, mask_row(mask, ldm, mask_T, d));
+    ratio_out[k] = clampf(expf(lp - old_logp[d]), 0.05f, 20.0f);
 }
 
 // phase 2 (one lane per trajectory): the reverse recursion of learner.py:618-635; vs[k] holds the ratio of step k on
@@ -648,34 +750,50 @@ __global__ __launch_bounds__(64) void k_vtrace(const float *__restrict__ values,
     }
 }
 
-extern "C" int sf_vtrace(const float *params, int ld_params, const float *values, int ld_values,
+// sf_vtrace (mask = nullptr) and sf_vtrace_masked: `what` names the entry point in the messages
+static int vtrace_launch(const char *what, const float *params, int ld_params, const float *values, int ld_values,
                          const float *actions, const float *old_logp, const float *rewards, const uint8_t *dones,
                          const int32_t *index, int64_t offset, int64_t n, int A, int action_kind, int recurrence,
                          float gamma, float rho_hat, float c_hat, float *vs, float *adv, const int32_t *head_n,
-                         int num_heads, void *stream) {
-    SF_REQUIRE(ld_params >= A && ld_values >= 1, "sf_vtrace: bad strides");
+                         int num_heads, const uint8_t *mask, int64_t ld_mask, int mask_T, void *stream) {
+    SF_REQUIRE(ld_params >= A && ld_values >= 1, "%s: bad strides", what);
     HeadsDev hd = {};
     if (head_n && num_heads > 1) {
-        SF_REQUIRE(action_kind == 0, "sf_vtrace: a head list needs action_kind 0");
+        SF_REQUIRE(action_kind == 0, "%s: a head list needs action_kind 0", what);
         bool any_box;
-        const int tot = heads_from_host("sf_vtrace", head_n, num_heads, SF_MAX_ACTION_HEADS, hd.head_n, &any_box);
+        const int tot = heads_from_host(what, head_n, num_heads, SF_MAX_ACTION_HEADS, hd.head_n, &any_box);
         if (tot < 0) return SF_ERR_ARG;
         hd.num_heads = num_heads;
-        SF_REQUIRE(tot == A, "sf_vtrace: head sizes sum to %d, A = %d", tot, A);
+        SF_REQUIRE(tot == A, "%s: head sizes sum to %d, A = %d", what, tot, A);
     }
-    SF_REQUIRE(params && values && actions && old_logp && rewards && dones && vs && adv, "sf_vtrace: null pointer");
-    SF_REQUIRE(recurrence > 0 && n % recurrence == 0, "sf_vtrace: n=%lld not a multiple of recurrence=%d",
+    SF_REQUIRE(params && values && actions && old_logp && rewards && dones && vs && adv, "%s: null pointer", what);
+    SF_REQUIRE(recurrence > 0 && n % recurrence == 0, "%s: n=%lld not a multiple of recurrence=%d", what,
                (long long)n, recurrence);
     SF_REQUIRE(A > 0 && (action_kind == 0 || (action_kind == 1 && A % 2 == 0)),
-               "sf_vtrace: unsupported action params A=%d kind=%d", A, action_kind);
+               "%s: unsupported action params A=%d kind=%d", what, A, action_kind);
     const int64_t ntraj = n / recurrence;
     if (ntraj == 0) return SF_OK;
     const dim3 grid((unsigned)((ntraj + 63) / 64)), block(64), rgrid((unsigned)((n + 255) / 256));
+    if (mask) {  // the masked ratio pass: any head list, in place (a plain Discrete(A) is a one-member list)
+        const HeadsDev mh = hd.num_heads > 1 ? hd : single_head(A, action_kind);
+        SF_REQUIRE(heads_any_discrete(mh), "%s: a pure Box space has no action mask", what);
+        if (A >= WIDE_MIN_A) {
+            SF_REQUIRE((n + WIDE_ROWS - 1) / WIDE_ROWS <= 0x7fffffffLL, "%s: n=%lld too large", what, (long long)n);
+            k_masked_vtrace_ratio_wide<<<dim3((unsigned)((n + WIDE_ROWS - 1) / WIDE_ROWS)), dim3(256), 0, STREAM(stream)>>>(
+                params, ld_params, actions, old_logp, index, offset, n, vs, mh, mask, ld_mask, mask_T);
+        } else {
+            k_masked_vtrace_ratio<<<rgrid, dim3(256), 0, STREAM(stream)>>>(params, ld_params, actions, old_logp, index,
+                                                                          offset, n, vs, mh, mask, ld_mask, mask_T);
+        }
+        k_vtrace<<<grid, block, 0, STREAM(stream)>>>(values, ld_values, rewards, dones, index, offset, ntraj, recurrence,
+                                                     gamma, rho_hat, c_hat, vs, adv);
+        return sf_launch_status(what);
+    }
 #define VT_LAUNCH(M)                                                                                                   \
     k_vtrace_ratio<M><<<rgrid, dim3(256), 0, STREAM(stream)>>>(params, ld_params, actions, old_logp, index, offset, n, A, \
                                                                action_kind, vs, hd)
     if (A >= WIDE_MIN_A) {  // wave-per-row ratio
-        SF_REQUIRE((n + WIDE_ROWS - 1) / WIDE_ROWS <= 0x7fffffffLL, "sf_vtrace: n=%lld too large", (long long)n);
+        SF_REQUIRE((n + WIDE_ROWS - 1) / WIDE_ROWS <= 0x7fffffffLL, "%s: n=%lld too large", what, (long long)n);
         k_vtrace_ratio_wide<<<dim3((unsigned)((n + WIDE_ROWS - 1) / WIDE_ROWS)), dim3(256), 0, STREAM(stream)>>>(
             params, ld_params, actions, old_logp, index, offset, n, vs,
             hd.num_heads > 1 ? hd : single_head(A, action_kind));
@@ -686,7 +804,40 @@ extern "C" int sf_vtrace(const float *params, int ld_params, const float *values
     // the recursion reads the ratios only: one kernel whatever the distribution is
     k_vtrace<<<grid, block, 0, STREAM(stream)>>>(values, ld_values, rewards, dones, index, offset, ntraj, recurrence, gamma,
                                                  rho_hat, c_hat, vs, adv);
-    return sf_launch_status("sf_vtrace");
+    return sf_launch_status(what);
+}
+
+extern "C" int sf_vtrace(const float *params, int ld_params, const float *values, int ld_values,
+                         const float *actions, const float *old_logp, const float *rewards, const uint8_t *dones,
+                         const int32_t *index, int64_t offset, int64_t n, int A, int action_kind, int recurrence,
+                         float gamma, float rho_hat, float c_hat, float *vs, float *adv, const int32_t *head_n,
+                         int num_heads, void *stream) {
+    return vtrace_launch("sf_vtrace", params, ld_params, values, ld_values, actions, old_logp, rewards, dones, index, offset,
+                         n, A, action_kind, recurrence, gamma, rho_hat, c_hat, vs, adv, head_n, num_heads, nullptr, 0, 0,
+                         stream);
+}
+
+// the mask arguments of sf_vtrace_masked / sf_ppo_loss_masked, checked before anything else of the call
+static int masked_args_ok(const char *what, const uint8_t *mask, int64_t ld_mask, int mask_T, int A) {
+    SF_REQUIRE(mask, "%s: null mask", what);
+    SF_REQUIRE(ld_mask >= A, "%s: ld_mask=%lld, the mask has one column per distribution parameter (A=%d)", what,
+               (long long)ld_mask, A);
+    SF_REQUIRE(mask_T >= 0, "%s: mask_T=%d is negative (0: a flat [N, ld_mask] mask; T: the slab's [E, T + 1, A])", what,
+               mask_T);
+    return SF_OK;
+}
+
+// sf_vtrace under the action mask the rows were sampled under
+extern "C" int sf_vtrace_masked(const float *params, int ld_params, const float *values, int ld_values,
+                                const float *actions, const float *old_logp, const float *rewards, const uint8_t *dones,
+                                const int32_t *index, int64_t offset, int64_t n, int A, int action_kind, int recurrence,
+                                float gamma, float rho_hat, float c_hat, float *vs, float *adv, const int32_t *head_n,
+                                int num_heads, const uint8_t *mask, int64_t ld_mask, int mask_T, void *stream) {
+    if (int rc = masked_args_ok("sf_vtrace_masked", mask, ld_mask, mask_T, A)) return rc;
+    SF_REQUIRE(action_kind == 0, "sf_vtrace_masked: a pure Box space has no action mask");
+    return vtrace_launch("sf_vtrace_masked", params, ld_params, values, ld_values, actions, old_logp, rewards, dones, index,
+                         offset, n, A, action_kind, recurrence, gamma, rho_hat, c_hat, vs, adv, head_n, num_heads, mask,
+                         ld_mask, mask_T, stream);
 }
 
 // =========================================================================================== K16 PPO loss fwd+bwd
@@ -892,7 +1043,10 @@ __global__ __launch_bounds__(256) void k_ppo_loss(const float *__restrict__ para
 // hence the same bits, for a second pass of expf over a row that is in cache); the row's log-prob is a sum of up to 64
 // members' (|lp| can pass 100 each) and is added up in double, so that the ratio exp(logp - old_logp) does not inherit the
 // rounding of a float running sum of that size.
-template <bool KEEP>
+// MASKED (k_masked_ppo_loss_md / k_masked_ppo_loss_mh): a Discrete member's terms and gradient come from
+// masked_cat_terms / masked_cat_grad on its slice of the row's mask, the kept slot klpu_h holds 1 / (mass + 1e-13); a Box
+// member never reads the mask.  The unmasked instantiations have no mask code at all.
+template <bool KEEP, bool MASKED>
 __device__ __forceinline__ void ppo_loss_tuple(const float *__restrict__ params, int ldp,
                                                const float *__restrict__ values, int ldv,
                                                const float *__restrict__ actions, const float *__restrict__ old_logp,
@@ -903,7 +1057,8 @@ __device__ __forceinline__ void ppo_loss_tuple(const float *__restrict__ params,
                                                const LossDev &h, const double *__restrict__ moments,
                                                double *__restrict__ sums, float *__restrict__ g_params,
                                                float *__restrict__ g_values, float *__restrict__ ratio_out,
-                                               int sym_pass) {
+                                               int sym_pass, const uint8_t *__restrict__ mask, int64_t ldm,
+                                               int mask_T) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const LossPre p = loss_prologue(moments, sums, h.expl_kind == 2 && !sym_pass);
     const int H = h.hd.num_heads;
@@ -915,6 +1070,8 @@ __device__ __forceinline__ void ppo_loss_tuple(const float *__restrict__ params,
         const float *z = params + i * ldp, *zo = old_params + d * A;
         const float *arow = actions + d * heads_action_cols(h.hd.head_n, H);
         float *gz = g_params + i * ldp;
+        const uint8_t *mk = nullptr;
+        if constexpr (MASKED) mk = mask_row(mask, ldm, mask_T, d);
         float logp_a = 0.f;   // KEEP
         double logp_d = 0.0;  // !KEEP
         float ent = 0.f, kl = 0.f, symkl = 0.f;
@@ -923,6 +1080,10 @@ __device__ __forceinline__ void ppo_loss_tuple(const float *__restrict__ params,
         auto keep = [&](const CatTerms &t, int s) {
             mx[s] = t.mx; lse[s] = t.lse; mxo[s] = t.mxo; lseo[s] = t.lseo;
             ent_h[s] = t.ent; kl_h[s] = t.kl; klpu_h[s] = t.klpu;
+        };
+        auto keep_masked = [&](const MaskedCatTerms &t, int s) {
+            mx[s] = t.s.mx; lse[s] = t.s.lse; mxo[s] = t.so.mx; lseo[s] = t.so.lse;
+            ent_h[s] = t.ent; kl_h[s] = t.kl; klpu_h[s] = t.s.inv;
         };
         int off = 0, aoff = 0;
         for (int hd = 0; hd < H; ++hd) {
@@ -937,10 +1098,17 @@ __device__ __forceinline__ void ppo_loss_tuple(const float *__restrict__ params,
                 off += 2 * Dh; aoff += Dh;
                 continue;
             }
-            const CatTerms t = cat_terms(z + off, zo + off, nh, (int)arow[aoff]);
-            if constexpr (KEEP) { keep(t, hd); logp_a += t.lpa; }
-            else logp_d += (double)t.lpa;
-            ent += t.ent; kl += t.kl; symkl += 0.5f * (t.klpu + t.a2);
+            if constexpr (MASKED) {
+                const MaskedCatTerms t = masked_cat_terms(z + off, zo + off, mk + off, nh, (int)arow[aoff]);
+                if constexpr (KEEP) { keep_masked(t, hd); logp_a += t.lpa; }
+                else logp_d += (double)t.lpa;
+                ent += t.ent; kl += t.kl;
+            } else {
+                const CatTerms t = cat_terms(z + off, zo + off, nh, (int)arow[aoff]);
+                if constexpr (KEEP) { keep(t, hd); logp_a += t.lpa; }
+                else logp_d += (double)t.lpa;
+                ent += t.ent; kl += t.kl; symkl += 0.5f * (t.klpu + t.a2);
+            }
             off += nh; aoff += 1;
         }
         if (sym_pass) {
@@ -970,6 +1138,15 @@ __device__ __forceinline__ void ppo_loss_tuple(const float *__restrict__ params,
                     const int act = (int)arow[aoff];
                     aoff += 1;
                     const int s = KEEP ? hd : 0;
+                    if constexpr (MASKED) {
+                        if constexpr (!KEEP) keep_masked(masked_cat_terms(z + off, zo + off, mk + off, nh, act), 0);
+                        for (int k = 0; k < nh; ++k)
+                            gz[off + k] = masked_cat_grad(z[off + k], zo[off + k], mk[off + k], k == act, mx[s], lse[s],
+                                                          klpu_h[s], mxo[s], lseo[s], ent_h[s], kl_h[s], r.dL_dlogp,
+                                                          p.inv_n, h);
+                        off += nh;
+                        continue;
+                    }
                     if constexpr (!KEEP) keep(cat_terms(z + off, zo + off, nh, act), 0);  // the first loop's values, bit for bit
                     const float u = 1.0f / (float)nh, lu = logf(u);
                     for (int k = 0; k < nh; ++k)
@@ -1000,8 +1177,9 @@ __global__ __launch_bounds__(256) void k_ppo_loss_md(const float *__restrict__ p
                                                      double *__restrict__ sums, float *__restrict__ g_params,
                                                      float *__restrict__ g_values, float *__restrict__ ratio_out,
                                                      int sym_pass) {
-    ppo_loss_tuple<true>(params, ldp, values, ldv, actions, old_logp, old_params, old_values, adv, targets, valids, index,
-                         offset, n, A, h, moments, sums, g_params, g_values, ratio_out, sym_pass);
+    ppo_loss_tuple<true, false>(params, ldp, values, ldv, actions, old_logp, old_params, old_values, adv, targets, valids,
+                                index, offset, n, A, h, moments, sums, g_params, g_values, ratio_out, sym_pass, nullptr, 0,
+                                0);
 }
 
 __global__ __launch_bounds__(256) void k_ppo_loss_mh(const float *__restrict__ params, int ldp,
@@ -1017,9 +1195,29 @@ __global__ __launch_bounds__(256) void k_ppo_loss_mh(const float *__restrict__ p
                                                      double *__restrict__ sums, float *__restrict__ g_params,
                                                      float *__restrict__ g_values, float *__restrict__ ratio_out,
                                                      int sym_pass) {
-    ppo_loss_tuple<false>(params, ldp, values, ldv, actions, old_logp, old_params, old_values, adv, targets, valids, index,
-                          offset, n, A, h, moments, sums, g_params, g_values, ratio_out, sym_pass);
+    ppo_loss_tuple<false, false>(params, ldp, values, ldv, actions, old_logp, old_params, old_values, adv, targets, valids,
+                                 index, offset, n, A, h, moments, sums, g_params, g_values, ratio_out, sym_pass, nullptr,
+                                 0, 0);
 }
+
+// k_ppo_loss_md / k_ppo_loss_mh under an action mask; a plain Discrete(A <= 128) runs k_masked_ppo_loss_md as a one-member
+// list (a masked k_ppo_loss<128> would not fit the register file: the unmasked one sits at 256 VGPRs + 53 AGPRs)
+#define SF_MASKED_LOSS_KERNEL(NAME, KEEP)                                                                                \
+    __global__ __launch_bounds__(256) void NAME(                                                                         \
+        const float *__restrict__ params, int ldp, const float *__restrict__ values, int ldv,                            \
+        const float *__restrict__ actions, const float *__restrict__ old_logp, const float *__restrict__ old_params,     \
+        const float *__restrict__ old_values, const float *__restrict__ adv, const float *__restrict__ targets,          \
+        const uint8_t *__restrict__ valids, const int32_t *__restrict__ index, int64_t offset, int64_t n, int A,         \
+        LossDev h, const double *__restrict__ moments, double *__restrict__ sums, float *__restrict__ g_params,          \
+        float *__restrict__ g_values, float *__restrict__ ratio_out, const uint8_t *__restrict__ mask, int64_t ldm,      \
+        int mask_T) {                                                                                                    \
+        ppo_loss_tuple<KEEP, true>(params, ldp, values, ldv, actions, old_logp, old_params, old_values, adv, targets,    \
+                                   valids, index, offset, n, A, h, moments, sums, g_params, g_values, ratio_out, 0, mask, \
+                                   ldm, mask_T);                                                                         \
+    }
+SF_MASKED_LOSS_KERNEL(k_masked_ppo_loss_md, true)
+SF_MASKED_LOSS_KERNEL(k_masked_ppo_loss_mh, false)
+#undef SF_MASKED_LOSS_KERNEL
 
 // pre-pass for the symmetric-KL exploration loss: mean over valid samples decides clamp(max=30) / isfinite gate
 template <int MAXA>
@@ -1053,19 +1251,21 @@ __global__ __launch_bounds__(256) void k_symkl_sum(const float *__restrict__ par
 // pass 3: the gradient row, written 256 contiguous bytes per store.  The block's waves walk the rows with a grid
 // stride and add their sums in double, so a launch issues a few thousand atomics whatever n is.
 // sym_pass != 0: only the symmetric-KL sum of the valid rows (pre-pass for its mean gate) into sums[7].
-__global__ __launch_bounds__(256) void k_ppo_loss_wide(const float *__restrict__ params, int ldp,
-                                                       const float *__restrict__ values, int ldv,
-                                                       const float *__restrict__ actions,
-                                                       const float *__restrict__ old_logp,
-                                                       const float *__restrict__ old_params,
-                                                       const float *__restrict__ old_values,
-                                                       const float *__restrict__ adv, const float *__restrict__ targets,
-                                                       const uint8_t *__restrict__ valids,
-                                                       const int32_t *__restrict__ index, int64_t offset, int64_t n, int A,
-                                                       LossDev h, const double *__restrict__ moments,
-                                                       double *__restrict__ sums, float *__restrict__ g_params,
-                                                       float *__restrict__ g_values, float *__restrict__ ratio_out,
-                                                       int sym_pass) {
+// MASKED (k_masked_ppo_loss_wide): pass 1 pushes z - 1e9 on masked-out columns, for the current and the
+// old logits alike; pass 2 sums the allowed columns' softmax mass, -s lp and s (lp - lp_old) and scales the last two by
+// 1 / (mass + 1e-13), which slot 6 keeps for the gradient pass (no symmetric-KL there: the launcher refuses it).
+template <bool MASKED>
+__device__ __forceinline__ void ppo_loss_wide(const float *__restrict__ params, int ldp,
+                                              const float *__restrict__ values, int ldv,
+                                              const float *__restrict__ actions, const float *__restrict__ old_logp,
+                                              const float *__restrict__ old_params, const float *__restrict__ old_values,
+                                              const float *__restrict__ adv, const float *__restrict__ targets,
+                                              const uint8_t *__restrict__ valids, const int32_t *__restrict__ index,
+                                              int64_t offset, int64_t n, int A, const LossDev &h,
+                                              const double *__restrict__ moments, double *__restrict__ sums,
+                                              float *__restrict__ g_params, float *__restrict__ g_values,
+                                              float *__restrict__ ratio_out, int sym_pass,
+                                              const uint8_t *__restrict__ mask, int64_t ldm, int mask_T) {
     // per wave and head: mx, lse, mxo, lseo, entropy, KL, KL(p || uniform); 8 KB for the longest list
     __shared__ float hstat[WIDE_ROWS][SF_MAX_ACTION_HEADS][8];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1079,6 +1279,8 @@ __global__ __launch_bounds__(256) void k_ppo_loss_wide(const float *__restrict__
         const int64_t d = index ? (int64_t)index[i] : offset + i;
         const bool valid = valids[d] != 0;
         const float *z = params + i * ldp, *zo = old_params + d * A, *arow = actions + d * NA;
+        const uint8_t *mk = nullptr;
+        if constexpr (MASKED) mk = mask_row(mask, ldm, mask_T, d);
         if (sym_pass) {
             if (!valid) continue;
             float symkl = 0.f;
@@ -1119,12 +1321,43 @@ __global__ __launch_bounds__(256) void k_ppo_loss_wide(const float *__restrict__
                 continue;
             }
             float m1 = -INFINITY, s1 = 0.f, m2 = -INFINITY, s2 = 0.f;
+            if constexpr (MASKED) {
 #pragma unroll 4
-            for (int k = lane; k < nh; k += 64) { wide_push(m1, s1, z[off + k]); wide_push(m2, s2, zo[off + k]); }
+                for (int k = lane; k < nh; k += 64) {
+                    const float mo = mk[off + k] ? 0.f : -1e9f;
+                    wide_push(m1, s1, z[off + k] + mo);
+                    wide_push(m2, s2, zo[off + k] + mo);
+                }
+            } else {
+#pragma unroll 4
+                for (int k = lane; k < nh; k += 64) { wide_push(m1, s1, z[off + k]); wide_push(m2, s2, zo[off + k]); }
+            }
             float mx, lse, mxo, lseo;
             wide_finish(m1, s1, mx, lse);
             wide_finish(m2, s2, mxo, lseo);
             const int act = (int)arow[aoff];
+            if constexpr (MASKED) {
+                float lpa = 0.f, e = 0.f, kk = 0.f, ps = 0.f;
+#pragma unroll 4
+                for (int k = lane; k < nh; k += 64) {
+                    const uint8_t ok = mk[off + k];
+                    const float mo = ok ? 0.f : -1e9f;
+                    const float lp = ((z[off + k] + mo) - mx) - lse, q = ((zo[off + k] + mo) - mxo) - lseo;
+                    const float s_ = ok ? expf((z[off + k] - mx) - lse) : 0.f;
+                    if (k == act) lpa = lp;
+                    ps += s_;
+                    e -= s_ * lp;
+                    kk += s_ * (lp - q);
+                }
+                lpa = wide_allsum(lpa);
+                const float inv = 1.0f / (wide_allsum(ps) + 1e-13f);
+                e = wide_allsum(e) * inv; kk = wide_allsum(kk) * inv;
+                st[hd][0] = mx; st[hd][1] = lse; st[hd][2] = mxo; st[hd][3] = lseo;
+                st[hd][4] = e; st[hd][5] = kk; st[hd][6] = inv;
+                logp_a += lpa; logp_d += (double)lpa; ent += e; kl += kk;
+                off += nh; aoff += 1;
+                continue;
+            }
             const float u = 1.0f / (float)nh, lu = logf(u);
             float lpa = 0.f, e = 0.f, kk = 0.f, a1 = 0.f, a2 = 0.f;
 #pragma unroll 4
@@ -1176,6 +1409,14 @@ __global__ __launch_bounds__(256) void k_ppo_loss_wide(const float *__restrict__
             aoff += 1;
             const float mx = st[hd][0], lse = st[hd][1], mxo = st[hd][2], lseo = st[hd][3];
             const float ent_h = st[hd][4], kl_h = st[hd][5], klpu_h = st[hd][6];
+            if constexpr (MASKED) {
+#pragma unroll 4
+                for (int k = lane; k < nh; k += 64)
+                    gz[off + k] = masked_cat_grad(z[off + k], h.kl_coeff != 0.f ? zo[off + k] : 0.f, mk[off + k], k == act,
+                                                  mx, lse, klpu_h, mxo, lseo, ent_h, kl_h, r.dL_dlogp, p.inv_n, h);
+                off += nh;
+                continue;
+            }
             const float u = 1.0f / (float)nh, lu = logf(u);
 #pragma unroll 4
             for (int k = lane; k < nh; k += 64)
@@ -1186,6 +1427,41 @@ __global__ __launch_bounds__(256) void k_ppo_loss_wide(const float *__restrict__
         if (lane == 0) g_values[i * ldv] = h.value_coeff * p.inv_n * r.dvl;
     }
     loss_epilogue(acc, kl_max, sums, sym_pass);
+}
+
+__global__ __launch_bounds__(256) void k_ppo_loss_wide(const float *__restrict__ params, int ldp,
+                                                       const float *__restrict__ values, int ldv,
+                                                       const float *__restrict__ actions,
+                                                       const float *__restrict__ old_logp,
+                                                       const float *__restrict__ old_params,
+                                                       const float *__restrict__ old_values,
+                                                       const float *__restrict__ adv, const float *__restrict__ targets,
+                                                       const uint8_t *__restrict__ valids,
+                                                       const int32_t *__restrict__ index, int64_t offset, int64_t n, int A,
+                                                       LossDev h, const double *__restrict__ moments,
+                                                       double *__restrict__ sums, float *__restrict__ g_params,
+                                                       float *__restrict__ g_values, float *__restrict__ ratio_out,
+                                                       int sym_pass) {
+    ppo_loss_wide<false>(params, ldp, values, ldv, actions, old_logp, old_params, old_values, adv, targets, valids, index,
+                         offset, n, A, h, moments, sums, g_params, g_values, ratio_out, sym_pass, nullptr, 0, 0);
+}
+
+__global__ __launch_bounds__(256) void k_masked_ppo_loss_wide(const float *__restrict__ params, int ldp,
+                                                              const float *__restrict__ values, int ldv,
+                                                              const float *__restrict__ actions,
+                                                              const float *__restrict__ old_logp,
+                                                              const float *__restrict__ old_params,
+                                                              const float *__restrict__ old_values,
+                                                              const float *__restrict__ adv,
+                                                              const float *__restrict__ targets,
+                                                              const uint8_t *__restrict__ valids,
+                                                              const int32_t *__restrict__ index, int64_t offset, int64_t n,
+                                                              int A, LossDev h, const double *__restrict__ moments,
+                                                              double *__restrict__ sums, float *__restrict__ g_params,
+                                                              float *__restrict__ g_values, float *__restrict__ ratio_out,
+                                                              const uint8_t *__restrict__ mask, int64_t ldm, int mask_T) {
+    ppo_loss_wide<true>(params, ldp, values, ldv, actions, old_logp, old_params, old_values, adv, targets, valids, index,
+                        offset, n, A, h, moments, sums, g_params, g_values, ratio_out, 0, mask, ldm, mask_T);
 }
 
 __global__ void k_symkl_gate(double *__restrict__ sums, const double *__restrict__ moments) {
@@ -1216,9 +1492,16 @@ static int ppo_loss_wide_launch(const float *params, int ld_params, const float 
                                 const float *old_values, const float *adv, const float *targets, const uint8_t *valids,
                                 const int32_t *index, int64_t offset, int64_t n, int A, const LossDev &h,
                                 const double *moments, double *sums, float *g_params, float *g_values, float *ratio_out,
-                                void *stream) {
+                                const uint8_t *mask, int64_t ld_mask, int mask_T, void *stream) {
     const int64_t want = (n + WIDE_ROWS - 1) / WIDE_ROWS;
     const dim3 grid((unsigned)(want < 2048 ? want : 2048)), block(256);  // 256 CUs x 8 blocks; the rows are grid-strided
+    if (mask) {
+        k_masked_ppo_loss_wide<<<grid, block, 0, STREAM(stream)>>>(params, ld_params, values, ld_values, actions, old_logp,
+                                                                   old_params, old_values, adv, targets, valids, index,
+                                                                   offset, n, A, h, moments, sums, g_params, g_values,
+                                                                   ratio_out, mask, ld_mask, mask_T);
+        return sf_launch_status("sf_ppo_loss_masked");
+    }
     if (h.expl_kind == 2) {
         k_ppo_loss_wide<<<grid, block, 0, STREAM(stream)>>>(params, ld_params, values, ld_values, actions, old_logp,
                                                             old_params, old_values, adv, targets, valids, index, offset,
@@ -1238,7 +1521,8 @@ static int ppo_loss_launch(const char *what, const float *params, int ld_params,
                            const float *old_values, const float *adv, const float *targets, const uint8_t *valids,
                            const int32_t *index, int64_t offset, int64_t n, int A, const sf_loss_cfg *h_cfg,
                            const int32_t *head_n, int num_heads, int cap, const double *moments, double *sums,
-                           float *g_params, float *g_values, float *ratio_out, void *stream) {
+                           float *g_params, float *g_values, float *ratio_out, const uint8_t *mask, int64_t ld_mask,
+                           int mask_T, void *stream) {
     SF_REQUIRE(ld_params >= A && ld_values >= 1, "%s: bad strides", what);
     SF_REQUIRE(params && values && actions && old_logp && old_params && old_values && adv && targets && valids &&
                    h_cfg && moments && sums && g_params && g_values,
@@ -1259,6 +1543,12 @@ static int ppo_loss_launch(const char *what, const float *params, int ld_params,
                    "%s: symmetric_kl exploration loss needs categorical heads only (the reference's "
                    "ContinuousActionDistribution has no symmetric_kl_with_uniform_prior)", what);
     }
+    if (mask) {  // sf_ppo_loss_masked: the rule is defined per Discrete member, without the uniform-prior term
+        SF_REQUIRE(h_cfg->action_kind == 0 && heads_any_discrete(hd), "%s: a pure Box space has no action mask", what);
+        SF_REQUIRE(!(h_cfg->exploration_kind == 2 && h_cfg->exploration_coeff != 0.f),
+                   "%s: exploration_loss=symmetric_kl has no meaning under an action mask (log-probs of masked-out "
+                   "actions are about -1e9); use exploration_loss=entropy", what);
+    }
     const LossDev h = make_loss_dev(h_cfg, hd);
     int rc = sf_hip_status(hipMemsetAsync(sums, 0, 8 * sizeof(double), STREAM(stream)), "sf_ppo_loss memset");
     if (rc) return rc;
@@ -1269,10 +1559,22 @@ static int ppo_loss_launch(const char *what, const float *params, int ld_params,
         else if (A <= 32) KERNEL<32><<<grid, block, 0, STREAM(stream)>>>(__VA_ARGS__);  \
         else KERNEL<128><<<grid, block, 0, STREAM(stream)>>>(__VA_ARGS__);              \
     } while (0)
+    if (mask) {  // one wave per row from WIDE_MIN_A parameters on, else one lane per row over the member list
+        if (A >= WIDE_MIN_A) return ppo_loss_wide_launch(params, ld_params, values, ld_values, actions, old_logp,
+                                                         old_params, old_values, adv, targets, valids, index, offset, n,
+                                                         A, h, moments, sums, g_params, g_values, ratio_out, mask,
+                                                         ld_mask, mask_T, stream);
+        auto kern = h.hd.num_heads <= 8 ? k_masked_ppo_loss_md : k_masked_ppo_loss_mh;
+        kern<<<grid, block, 0, STREAM(stream)>>>(params, ld_params, values, ld_values, actions, old_logp, old_params,
+                                                 old_values, adv, targets, valids, index, offset, n, A, h, moments, sums,
+                                                 g_params, g_values, ratio_out, mask, ld_mask, mask_T);
+        return sf_launch_status(what);
+    }
     if (tuple) {
         if (A >= WIDE_MIN_A) return ppo_loss_wide_launch(params, ld_params, values, ld_values, actions, old_logp,
                                                          old_params, old_values, adv, targets, valids, index, offset, n,
-                                                         A, h, moments, sums, g_params, g_values, ratio_out, stream);
+                                                         A, h, moments, sums, g_params, g_values, ratio_out, nullptr, 0,
+                                                         0, stream);
         // up to 8 members: their statistics stay in the lane (k_ppo_loss_md); more: recomputed (k_ppo_loss_mh)
         auto kern = h.hd.num_heads <= 8 ? k_ppo_loss_md : k_ppo_loss_mh;
         if (h.expl_kind == 2) {
@@ -1289,7 +1591,7 @@ static int ppo_loss_launch(const char *what, const float *params, int ld_params,
     if (A >= WIDE_MIN_A)  // a single Discrete(A) / Box(A / 2) as a one-member head list
         return ppo_loss_wide_launch(params, ld_params, values, ld_values, actions, old_logp, old_params, old_values, adv,
                                     targets, valids, index, offset, n, A, h, moments, sums, g_params, g_values,
-                                    ratio_out, stream);
+                                    ratio_out, nullptr, 0, 0, stream);
     if (h.expl_kind == 2) {
         PL_DISPATCH(k_symkl_sum, params, ld_params, valids, index, offset, n, A, sums + 7);
         k_symkl_gate<<<dim3(1), dim3(64), 0, STREAM(stream)>>>(sums, moments);
@@ -1308,7 +1610,8 @@ extern "C" int sf_ppo_loss(const float *params, int ld_params, const float *valu
                            void *stream) {
     return ppo_loss_launch("sf_ppo_loss", params, ld_params, values, ld_values, actions, old_logp, old_params, old_values,
                            adv, targets, valids, index, offset, n, A, h_cfg, h_cfg ? h_cfg->head_n : nullptr,
-                           h_cfg ? h_cfg->num_heads : 0, 8, moments, sums, g_params, g_values, ratio_out, stream);
+                           h_cfg ? h_cfg->num_heads : 0, 8, moments, sums, g_params, g_values, ratio_out, nullptr, 0, 0,
+                           stream);
 }
 
 extern "C" int sf_ppo_loss_heads(const float *params, int ld_params, const float *values, int ld_values,
@@ -1328,7 +1631,27 @@ extern "C" int sf_ppo_loss_heads(const float *params, int ld_params, const float
         SF_REQUIRE(h_cfg && h_cfg->action_kind == 0, "sf_ppo_loss_heads: a head list needs action_kind 0");
     return ppo_loss_launch("sf_ppo_loss_heads", params, ld_params, values, ld_values, actions, old_logp, old_params,
                            old_values, adv, targets, valids, index, offset, n, A, h_cfg, head_n, num_heads,
-                           SF_MAX_ACTION_HEADS, moments, sums, g_params, g_values, ratio_out, stream);
+                           SF_MAX_ACTION_HEADS, moments, sums, g_params, g_values, ratio_out, nullptr, 0, 0, stream);
+}
+
+// sf_ppo_loss_heads under the action mask the rows were sampled under
+extern "C" int sf_ppo_loss_masked(const float *params, int ld_params, const float *values, int ld_values,
+                                  const float *actions, const float *old_logp, const float *old_params,
+                                  const float *old_values, const float *adv, const float *targets, const uint8_t *valids,
+                                  const int32_t *index, int64_t offset, int64_t n, int A, const sf_loss_cfg *h_cfg,
+                                  const double *moments, double *sums, float *g_params, float *g_values, float *ratio_out,
+                                  const int32_t *head_n, int num_heads, const uint8_t *mask, int64_t ld_mask, int mask_T,
+                                  void *stream) {
+    if (int rc = masked_args_ok("sf_ppo_loss_masked", mask, ld_mask, mask_T, A)) return rc;
+    SF_REQUIRE(head_n && num_heads >= 1 && num_heads <= SF_MAX_ACTION_HEADS,
+               "sf_ppo_loss_masked: %d action heads, the limit is %d (SF_MAX_ACTION_HEADS)", num_heads,
+               SF_MAX_ACTION_HEADS);
+    SF_REQUIRE(h_cfg && h_cfg->action_kind == 0, "sf_ppo_loss_masked: a pure Box space has no action mask");
+    if (num_heads == 1)
+        SF_REQUIRE(head_n[0] == A, "sf_ppo_loss_masked: a one-member list must be Discrete(A)");
+    return ppo_loss_launch("sf_ppo_loss_masked", params, ld_params, values, ld_values, actions, old_logp, old_params,
+                           old_values, adv, targets, valids, index, offset, n, A, h_cfg, head_n, num_heads,
+                           SF_MAX_ACTION_HEADS, moments, sums, g_params, g_values, ratio_out, mask, ld_mask, mask_T, stream);
 }
 
 __global__ void k_loss_scalars(const double *__restrict__ sums, const double *__restrict__ moments, LossDev h,

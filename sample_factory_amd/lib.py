@@ -48,7 +48,7 @@ class sf_res_desc(C.Structure):
 # every symbol include/sf_hip.h declares (tests/test_abi.py checks the header against this list and the .so)
 SYMBOLS = [
     "sf_last_error", "sf_abi_version", "sf_valid_mask", "sf_gae_returns", "sf_moments", "sf_rms_update",
-    "sf_rms_apply", "sf_vtrace", "sf_ppo_loss", "sf_ppo_loss_heads", "sf_loss_scalars", "sf_train_summaries", "sf_minibatch_indices", "sf_minibatch_expand", "sf_grad_sumsq",
+    "sf_rms_apply", "sf_vtrace", "sf_vtrace_masked", "sf_ppo_loss", "sf_ppo_loss_heads", "sf_ppo_loss_masked", "sf_loss_scalars", "sf_train_summaries", "sf_minibatch_indices", "sf_minibatch_expand", "sf_grad_sumsq",
     "sf_adam_step", "sf_adam_step_dlr", "sf_lr_kl_adaptive", "sf_clock_probe", "sf_lamb_step", "sf_rnn_cell_fwd", "sf_rnn_cell_bwd", "sf_rows_add_scale", "sf_mlp2_fwd", "sf_rnn_store_state", "sf_rnn_chunk_setup", "sf_lstm_seq_supported", "sf_lstm_seq_fwd", "sf_lstm_seq_bwd", "sf_gru_seq_fwd", "sf_gru_seq_bwd", "sf_seq_fwd_x_supported", "sf_lstm_seq_fwd_x", "sf_gru_seq_fwd_x", "sf_rnn_rowseq_supported", "sf_rnn_rowseq_fwd", "sf_rnn_rowseq_bwd", "sf_rnn_wideseq_supported", "sf_rnn_seq_slab_rows", "sf_rnn_wideseq_fwd", "sf_rnn_wideseq_bwd", "sf_linear_fwd_dual_supported", "sf_linear_fwd_dual",
     "sf_obsnorm_moments", "sf_obsnorm_update", "sf_obsnorm_apply", "sf_sample_write_step",
     "sf_sample_write_step_tuple", "sf_sample_write_step_masked", "sf_sample_write_step_tuple_masked",
@@ -616,24 +616,50 @@ def _head_array(head_sizes):
     return (C.c_int32 * len(head_sizes))(*[int(x) for x in head_sizes])
 
 
+def _mask_args(mask, mask_T, A):
+    """(pointer, row stride, mask_T) of an action mask: u8 / bool, the slab's [E, mask_T + 1, >= A] array in place
+    (mask_T > 0) or a flat [N, >= A] one (mask_T == 0); its rows must be contiguous and evenly spaced"""
+    if mask.dtype not in _DT["u8"]:
+        raise SfHipError(f"action mask: expected dtype u8, got {mask.dtype}")
+    if not mask.is_cuda:
+        raise SfHipError(f"action mask lives on {mask.device}; the hot path only runs on the GPU (no CPU fallback)")
+    ok = mask.dim() in (2, 3) and mask.shape[-1] >= int(A) and (mask.stride(-1) == 1 or mask.shape[-1] == 1)
+    ld = mask.stride(-2) if ok and mask.shape[-2] > 1 else mask.shape[-1]
+    if ok and mask.dim() == 3:  # [E, mask_T + 1, A]: env e starts (mask_T + 1) rows after env e - 1
+        ok = int(mask_T) > 0 and mask.shape[1] == int(mask_T) + 1 and (mask.shape[0] == 1 or mask.stride(0) == mask.shape[1] * ld)
+    if not ok or ld < int(A):
+        raise SfHipError(f"action mask: expected evenly spaced rows of >= {A} contiguous columns, [E, mask_T + 1, A] or "
+                         f"[N, A] (shape {tuple(mask.shape)}, strides {mask.stride()}, mask_T {mask_T})")
+    return _vp(mask), i64(ld), int(mask_T)
+
+
 def vtrace(params, ld_params, values, ld_values, actions, old_logp, rewards, dones, index, offset, n, A, action_kind,
-           recurrence, gamma, rho_hat, c_hat, vs, adv, head_sizes=None) -> None:
+           recurrence, gamma, rho_hat, c_hat, vs, adv, head_sizes=None, mask=None, mask_T=0) -> None:
+    """mask (with mask_T): the importance ratios are taken under the action mask the rows were sampled under
+    (sf_vtrace_masked); None: sf_vtrace"""
     hn = _head_array(head_sizes) if head_sizes and len(head_sizes) > 1 else None
-    _check(load().sf_vtrace(_raw(params, "f32", "params"), int(ld_params), _raw(values, "f32", "values"),
-                            int(ld_values), ptr(actions, "f32", "actions"),
-                            ptr(old_logp, "f32", "old_logp"), ptr(rewards, "f32", "rewards"), ptr(dones, "u8", "dones"),
-                            ptr(index, "i32", "index"), i64(offset), i64(n), int(A), int(action_kind),
-                            int(recurrence), f(gamma), f(rho_hat), f(c_hat), ptr(vs, "f32", "vs"),
-                            ptr(adv, "f32", "adv"), hn, len(head_sizes) if hn is not None else 0, stream()),
-           "sf_vtrace")
+    margs = _mask_args(mask, mask_T, A) if mask is not None else None
+    args = (_raw(params, "f32", "params"), int(ld_params), _raw(values, "f32", "values"),
+            int(ld_values), ptr(actions, "f32", "actions"),
+            ptr(old_logp, "f32", "old_logp"), ptr(rewards, "f32", "rewards"), ptr(dones, "u8", "dones"),
+            ptr(index, "i32", "index"), i64(offset), i64(n), int(A), int(action_kind),
+            int(recurrence), f(gamma), f(rho_hat), f(c_hat), ptr(vs, "f32", "vs"),
+            ptr(adv, "f32", "adv"), hn, len(head_sizes) if hn is not None else 0)
+    if mask is not None:
+        _check(load().sf_vtrace_masked(*args, *margs, stream()), "sf_vtrace_masked")
+    else:
+        _check(load().sf_vtrace(*args, stream()), "sf_vtrace")
 
 
 def ppo_loss(params, ld_params, values, ld_values, actions, old_logp, old_params, old_values, adv, targets, valids,
              index, offset, n, A, cfg: sf_loss_cfg, mom, sums, g_params, g_values, ratio_out=None,
-             head_sizes=None) -> None:
+             head_sizes=None, mask=None, mask_T=0) -> None:
     """params/values (and g_params/g_values) may be strided column views of one [n, ld] matrix.  head_sizes: the Tuple's
     member list; up to 8 members it must already be in cfg (num_heads / head_n) and sf_ppo_loss runs as ever, a longer
-    one goes to sf_ppo_loss_heads as an argument and cfg's list is neither read nor written."""
+    one goes to sf_ppo_loss_heads as an argument and cfg's list is neither read nor written.  mask (with mask_T): the
+    loss under the action mask the rows were sampled under (sf_ppo_loss_masked; the member list is
+    head_sizes, cfg's list when that is None, else one Discrete(A))."""
+    margs = _mask_args(mask, mask_T, A) if mask is not None else None
     args = (_raw(params, "f32", "params"), int(ld_params), _raw(values, "f32", "values"),
             int(ld_values), ptr(actions, "f32", "actions"), ptr(old_logp, "f32", "old_logp"),
             ptr(old_params, "f32", "old_params"), ptr(old_values, "f32", "old_values"),
@@ -641,7 +667,11 @@ def ppo_loss(params, ld_params, values, ld_values, actions, old_logp, old_params
             ptr(index, "i32", "index"), i64(offset), i64(n), int(A), C.byref(cfg),
             ptr(mom, "f64", "moments"), ptr(sums, "f64", "sums"), _raw(g_params, "f32", "g_params"),
             _raw(g_values, "f32", "g_values"), ptr(ratio_out, "f32", "ratio_out"))
-    if head_sizes is not None and len(head_sizes) > len(cfg.head_n):
+    if mask is not None:
+        heads = list(head_sizes) if head_sizes else (list(cfg.head_n[:cfg.num_heads]) if cfg.num_heads > 1 else [int(A)])
+        _check(load().sf_ppo_loss_masked(*args, _head_array(heads), len(heads), *margs, stream()),
+               "sf_ppo_loss_masked")
+    elif head_sizes is not None and len(head_sizes) > len(cfg.head_n):
         _check(load().sf_ppo_loss_heads(*args, _head_array(head_sizes), len(head_sizes), stream()), "sf_ppo_loss_heads")
     else:
         _check(load().sf_ppo_loss(*args, stream()), "sf_ppo_loss")
