@@ -359,6 +359,25 @@ int sf_h2d_rows(void *dst, int64_t dst_pitch, const void *src, int64_t src_pitch
  * reference), the bootstrap value -> values[:, T] (learner.py:962-969). */
 int sf_copy_rows(void *dst, int64_t dst_pitch, const void *src, int64_t src_pitch, int64_t row_bytes, int64_t rows,
                  void *stream);
+/* ---- frame stack on the device (csrc/sf_ingest.hip) ----------------------------------------------------------
+ * The reference stacks frames inside the env (sf_examples/atari/atari_utils.py:112, gym.wrappers.FrameStack(env,
+ * cfg.env_framestack)), so a host env ships the whole [k C, H, W] observation every step although (k - 1) / k of it
+ * already sits in the slab column before.  With --device_framestack=k the env delivers ONE frame and the stack is kept
+ * in the slab.  Byte granular (u8 and f32 frames alike): row b of `next` / `prev` is k slots of frame_bytes, oldest
+ * first, rows next_pitch / prev_pitch bytes apart (obs[:, t + 1] / obs[:, t]).  With done = terminated[b] | truncated[b]
+ * (either pointer may be NULL = all zero):
+ *   not done:                          next[b][j] = prev[b][j + 1] for j < k - 1, next[b][k - 1] = frame[b]
+ *   done, or BOTH flag pointers NULL:  next[b][j] = frame[b] for every j   (the auto-reset observation refills the
+ *                                      stack; both NULL is an env reset, prev is then not read)
+ * frame == NULL: the new frame has already been written to next[b][k - 1] (sf_h2d_rows straight into the last slot:
+ * the rows are contiguous, the pitch is the column's); that slot is then read for done rows and never written.
+ * One launch; 16-byte accesses when every address, pitch and frame_bytes allow it, else 4-byte, else single bytes.
+ * Refused before any launch (SF_ERR_ARG): null next / prev, k outside 1 .. 16, frame_bytes <= 0, a pitch below
+ * k * frame_bytes, frame_pitch < frame_bytes, rows < 0, rows of next and prev that share bytes.  rows == 0: SF_OK,
+ * nothing is launched. */
+int sf_framestack_step(void *next, int64_t next_pitch, const void *prev, int64_t prev_pitch, const void *frame,
+                       int64_t frame_pitch, int64_t frame_bytes, int k, const uint8_t *terminated,
+                       const uint8_t *truncated, int rows, void *stream);
 
 /* ---- synthetic vector env (SURVEY.md §8d "C2 synthetic inputs") ------------------------------------------------
  * Device-resident stand-in for a GPU env (the reference's pattern: sf_examples/brax/train_brax.py:160-204).

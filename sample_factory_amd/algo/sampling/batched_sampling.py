@@ -93,6 +93,14 @@ class BatchedVectorEnvRunner:
         self.keep_on, self.keep_row0 = False, 0  # the model keeps the conv activations of this runner's steps (Runner.init)
         if self.masked and self.zero_copy:
             raise NotImplementedError("action masks with a zero-copy (step_into) env")
+        # --device_framestack=k: the env delivers one frame per step; the slab's image keys hold k of them, oldest first.
+        # fs_keys: key -> channels of ONE frame.  The new frame goes into the last slot of obs[:, t + 1], the other slots
+        # are shifted over from obs[:, t] (or refilled where the episode ended) by sf_framestack_step.
+        self.fs_k = int(getattr(cfg, "device_framestack", 1))
+        self.fs_keys = {k: traj["obs"][k].shape[2] // self.fs_k for k in self.obs_keys
+                        if self.fs_k > 1 and traj["obs"][k].dim() == 5}
+        if self.fs_k > 1 and hasattr(env, "step_into"):
+            raise NotImplementedError(f"device_framestack={self.fs_k} with a zero-copy (step_into) env")
 
     def reset(self) -> None:
         """First observation into slab obs[:, 0] (batched_sampling.py:172-206)."""
@@ -103,6 +111,7 @@ class BatchedVectorEnvRunner:
             first = (o["obs"] if "obs" in o else o[self.obs_keys[0]]) if isinstance(o, dict) else o
             self.host_env = not (isinstance(first, torch.Tensor) and first.is_cuda)
             self._store_obs(o, 0)
+            self._framestack(0, None, None)
         self._started = True
 
     # ---- host (CPU) envs: pinned staging, asynchronous H2D straight into the slab slot.  The only
@@ -163,14 +172,29 @@ class BatchedVectorEnvRunner:
             self.ingest_prof["act_wait_s"] = self.ingest_prof.get("act_wait_s", 0.0) + time.perf_counter() - t0
         return stage.numpy()
 
+    def _obs_slot(self, key: str, t: int) -> torch.Tensor:
+        """where the env's observation of `key` goes in slab column t: the column, or — a stacked key — its LAST frame slot
+        (rows stay contiguous blocks at the column's pitch: still one pitched DMA)"""
+        x = self.traj["obs"][key]
+        c1 = self.fs_keys.get(key)
+        return x[:, t] if c1 is None else x[:, t, (self.fs_k - 1) * c1:]
+
     def _store_obs(self, o, t: int) -> None:
         if self.multi_key:
             for k in self.obs_keys:
-                self._to_device("obs." + k, o[k], self.traj["obs"][k][:, t])
+                self._to_device("obs." + k, o[k], self._obs_slot(k, t))
         else:
-            self._to_device("obs", o["obs"] if isinstance(o, dict) else o, self.obs[:, t])
+            key = "obs" if "obs" in self.traj["obs"] else self.obs_keys[0]
+            self._to_device("obs", o["obs"] if isinstance(o, dict) else o, self._obs_slot(key, t))
         if self.masked:
             self._to_device("mask", o["action_mask"], self.traj["obs"]["action_mask"][:, t])
+
+    def _framestack(self, t: int, term, trunc) -> None:
+        """complete the stacked keys of slab column t around the frame _store_obs put into their last slot: one launch per
+        key (term / trunc: the device flags of the step that produced the frame; None, None: a reset)"""
+        for k in self.fs_keys:
+            x = self.traj["obs"][k]
+            lib.framestack_step(x[:, t], x[:, t - 1 if t > 0 else 1], self.fs_k, None, term, trunc)
 
     def policy_version(self) -> float:
         return float(self.policy_versions[self.policy_id].item()) if self.policy_versions is not None else 0.0
@@ -326,6 +350,8 @@ class BatchedVectorEnvRunner:
     def _record_step(self, t: int, rew, term, trunc) -> None:
         """env outputs of step t -> slab (rewards shaped, dones, episode statistics), next-step recurrent state"""
         tr, T, cfg = self.traj, self.T, self.cfg
+        if self.fs_keys:  # (behind the flag transfers: the stack of obs[:, t + 1] needs this step's terminated / truncated)
+            self._framestack(t + 1, term, trunc)
         lib.traj_write_env_step(rew, term, trunc, T, t, cfg.reward_scale, cfg.reward_clip, self.policy_id,
                                 tr["rewards"], tr["dones"], tr["time_outs"], tr["policy_id"], self.ep_return,
                                 self.ep_len, self.ep_stats)

@@ -39,6 +39,33 @@ def extract_env_info(env, cfg) -> EnvInfo:
                    get_default_reward_shaping(env), ENV_INFO_PROTOCOL_VERSION)
 
 
+_framestack_warned = False
+
+
+def with_device_framestack(env_info: EnvInfo, env, cfg) -> EnvInfo:
+    """--device_framestack=k: the EnvInfo the slab, the model and the learner are built from — a copy whose image keys hold
+    k frames (envs/spaces.py stacked_obs_space).  The env's own EnvInfo (the cached / probed one) keeps describing the env.
+    k == 1: `env_info` itself.  Refuses what the device stack cannot serve."""
+    import dataclasses
+
+    from sample_factory_amd.envs.spaces import stacked_obs_space
+    from sample_factory_amd.utils.utils import log
+    global _framestack_warned
+    k = int(getattr(cfg, "device_framestack", 1))
+    stacked = stacked_obs_space(env_info.obs_space, k)  # ValueError: k < 1, or nothing to stack
+    if k == 1:
+        return env_info
+    if hasattr(env, "step_into"):
+        raise NotImplementedError(f"device_framestack={k} with a zero-copy env (step_into writes whole observations into "
+                                  "the slab): stack inside the env, or let it return single frames from step()")
+    if int(getattr(cfg, "env_framestack", 1) or 1) > 1 and not _framestack_warned:
+        _framestack_warned = True
+        log.warning("env_framestack=%d and device_framestack=%d are both set: an env factory that reads env_framestack stacks "
+                    "on its own and the device would stack those stacks; set env_framestack=1 unless the factory ignores it",
+                    int(cfg.env_framestack), k)
+    return dataclasses.replace(env_info, obs_space=stacked)
+
+
 def env_info_cache_filename(cfg) -> str:
     """env_info.py:113-114: one cache entry per env name under the per-user temporary directory"""
     import os

@@ -83,6 +83,9 @@ ENGINE_FLAGS = [
     ("mask_actions_in_loss", _bool, False),  # an env with obs["action_mask"] is TRAINED under the mask too: PPO loss and
     #                                          V-trace ratios on the distribution the sampler drew from (DESIGN.md 3.10.4;
     #                                          off: the reference's behaviour, the learner never sees the mask)
+    ("device_framestack", int, 1),           # k > 1: the env delivers ONE frame per step and the k-frame stack of every CHW
+    #                                          observation key is kept in the slab (sf_framestack_step);
+    #                                          not env_framestack, which reference-style env factories read to stack themselves
 ]
 
 

@@ -136,6 +136,40 @@ def is_box(space) -> bool:
     return not hasattr(space, "n") and hasattr(space, "shape") and getattr(space, "shape", None) is not None and not hasattr(space, "spaces")
 
 
+def framestack_keys(obs_space, k: int = 2):
+    """the observation keys --device_framestack stacks: every key whose space has three dimensions (CHW), never the
+    action mask; [] for k == 1"""
+    items = obs_space.spaces.items() if hasattr(obs_space, "spaces") else [("obs", obs_space)]
+    return [name for name, sp in items if int(k) > 1 and name != "action_mask" and len(getattr(sp, "shape", ()) or ()) == 3]
+
+
+def stacked_obs_space(obs_space, k: int):
+    """the observation space the slab, the model and the learner see under --device_framestack=k: a Dict in which every
+    3-D (CHW) key has become Box(k * C, H, W) — low / high tiled along the channel axis, dtype kept — and every other key
+    (vectors, the action mask) is the env's own space object.  k == 1: the space as it is."""
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"device_framestack={k}: the frame stack holds at least one frame")
+    if k == 1:
+        return obs_space
+    keys = framestack_keys(obs_space, k)
+    if not keys:
+        raise ValueError(f"device_framestack={k}: the observation space {obs_space!r} has no key with three dimensions "
+                         "(CHW) to stack")
+    out = {}
+    for name, sp in (obs_space.spaces.items() if hasattr(obs_space, "spaces") else [("obs", obs_space)]):
+        if name not in keys:
+            out[name] = sp
+            continue
+
+        def tiled(b):
+            b = np.asarray(b)
+            return np.tile(b, (k, 1, 1)) if b.ndim == 3 else (b.item() if b.ndim == 0 else b)  # scalar bounds stay scalar
+        c, h, w = sp.shape
+        out[name] = Box(tiled(sp.low), tiled(sp.high), (k * int(c), int(h), int(w)), sp.dtype)
+    return Dict(out)
+
+
 def calc_num_actions(action_space) -> int:
     """action_distributions.py:14-26"""
     if is_discrete(action_space):

@@ -148,7 +148,10 @@ class HostFrameVecEnv:
 def make_host_frame_env(full_env_name, cfg=None, env_config=None, render_mode=None):
     n = getattr(cfg, "synthetic_num_agents", 1024) if cfg is not None else 1024
     seed = ((getattr(cfg, "seed", None) or 0) if cfg is not None else 0) + int(getattr(env_config, "env_id", 0) or 0)
-    return HostFrameVecEnv(num_agents=n, seed=seed, sim_ms=getattr(cfg, "host_env_sim_ms", 0.0) if cfg is not None else 0.0)
+    # cfg.host_env_obs_shape: e.g. (1, 84, 84) — single frames, stacked on the device with --device_framestack
+    shape = tuple(getattr(cfg, "host_env_obs_shape", None) or (4, 84, 84)) if cfg is not None else (4, 84, 84)
+    return HostFrameVecEnv(num_agents=n, obs_shape=shape, seed=seed,
+                           sim_ms=getattr(cfg, "host_env_sim_ms", 0.0) if cfg is not None else 0.0)
 
 
 class SyntheticTupleEnv(SyntheticVecEnv):

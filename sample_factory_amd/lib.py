@@ -53,7 +53,7 @@ SYMBOLS = [
     "sf_obsnorm_moments", "sf_obsnorm_update", "sf_obsnorm_apply", "sf_sample_write_step",
     "sf_sample_write_step_tuple", "sf_sample_write_step_masked", "sf_sample_write_step_tuple_masked",
     "sf_traj_write_env_step", "sf_synth_obs",
-    "sf_synth_step", "sf_synth_vec_step", "sf_h2d_rows", "sf_copy_rows", "sf_conv_fwd", "sf_conv_fwd_workspace", "sf_conv_wgrad_workspace", "sf_conv_wgrad",
+    "sf_synth_step", "sf_synth_vec_step", "sf_h2d_rows", "sf_copy_rows", "sf_framestack_step", "sf_conv_fwd", "sf_conv_fwd_workspace", "sf_conv_wgrad_workspace", "sf_conv_wgrad",
     "sf_conv_dgrad", "sf_conv_norm_supported", "sf_conv_fwd_norm", "sf_conv_wgrad_norm", "sf_conv_relu_mask_supported", "sf_conv_fwd_relu_mask", "sf_conv_wgrad_relu_mask", "sf_conv_kernel_name", "sf_conv_fwd_t_supported", "sf_conv_fwd_t_workspace", "sf_conv_fwd_t", "sf_transpose",
     "sf_conv_fwd_os_supported", "sf_conv_fwd_relu_mask_os", "sf_conv_fwd_t_os",
     "sf_conv_fwd_os2_supported", "sf_conv_fwd_relu_mask_os2", "sf_conv_fwd_t_os2",
@@ -882,6 +882,44 @@ def copy_rows(dst: torch.Tensor, src: torch.Tensor) -> None:
             rs, bs, ps = rd, bd, bd
     _check(load().sf_copy_rows(_vp(dst), i64(pd), _vp(src), i64(ps), i64(bd),
                                i64(rd), stream()), "sf_copy_rows")
+
+
+def framestack_step(next_: torch.Tensor, prev: torch.Tensor, k: int, frame: Optional[torch.Tensor] = None,
+                    terminated: Optional[torch.Tensor] = None, truncated: Optional[torch.Tensor] = None) -> None:
+    """sf_framestack_step on two columns of an observation slab: next_ / prev are device views [rows, k * C, ...] of one
+    dtype whose rows are contiguous blocks (obs[:, t + 1] / obs[:, t]); frame: [rows, C, ...] with contiguous rows, or None
+    when the new frame already sits in the last slot of next_; terminated / truncated: contiguous bool / u8 [rows], both
+    None = a reset (every slot of every row becomes the new frame)"""
+    if not (next_.is_cuda and prev.is_cuda) or next_.shape != prev.shape or next_.dtype != prev.dtype or next_.dim() < 2:
+        raise SfHipError(f"framestack_step: next / prev must be device views of equal shape and dtype [rows, ...], got "
+                         f"{tuple(next_.shape)} {next_.dtype} on {next_.device} / {tuple(prev.shape)} {prev.dtype} on {prev.device}")
+    rows, es = int(next_.shape[0]), next_.element_size()
+    if rows == 0:
+        return
+    if not (next_[0].is_contiguous() and prev[0].is_contiguous()):
+        raise SfHipError(f"framestack_step: rows must be contiguous blocks (strides {next_.stride()} / {prev.stride()})")
+    row_bytes = next_[0].numel() * es
+    if int(k) < 1 or next_.shape[1] % int(k) or row_bytes % int(k):
+        raise SfHipError(f"framestack_step: dim 1 of {tuple(next_.shape)} is not k = {k} frames")
+    fb = row_bytes // int(k)
+    for name, flags in (("terminated", terminated), ("truncated", truncated)):
+        if flags is not None and flags.numel() != rows:
+            raise SfHipError(f"framestack_step: {name} must hold one flag per row ({rows}), got {flags.numel()}")
+
+    def pitch(t, rb):  # (a one-row view may carry any stride)
+        return int(t.stride(0)) * es if rows > 1 else max(int(t.stride(0)) * es, rb)
+    fptr, fpitch = C.c_void_p(0), 0
+    if frame is not None:
+        if not frame.is_cuda or frame.dtype != next_.dtype or frame.shape[0] != rows or not frame[0].is_contiguous() or \
+                frame[0].numel() * es != fb:
+            raise SfHipError(f"framestack_step: frame must be a device [rows, C, ...] view of {fb} contiguous bytes per "
+                             f"row and dtype {next_.dtype}, got {tuple(frame.shape)} {frame.dtype} on {frame.device}")
+        fptr, fpitch = _vp(frame), pitch(frame, fb)
+    key = ("framestack_step", rows, int(k), fb) if _keys_wanted() else None  # (tools/framestack_bench.py times it)
+    with _timed(key):
+        _check(load().sf_framestack_step(_vp(next_), i64(pitch(next_, row_bytes)), _vp(prev), i64(pitch(prev, row_bytes)),
+                                         fptr, i64(fpitch), i64(fb), int(k), ptr(terminated, "u8", "terminated"),
+                                         ptr(truncated, "u8", "truncated"), rows, stream()), "sf_framestack_step")
 
 
 def synth_obs(obs_slot_ptr: int, env_stride, B, env0, obs_bytes, seed, step) -> None:
