@@ -339,6 +339,18 @@ int sf_traj_write_env_step(const float *rewards, const uint8_t *terminated, cons
                            uint8_t *traj_dones, uint8_t *traj_time_outs, int32_t *traj_policy_id, float *ep_return,
                            int32_t *ep_len, double *ep_stats, void *stream);
 
+/* sf_traj_write_env_step for envs that report info["is_active"] (non_batched_sampling.py:82-84, 197-203; DESIGN.md
+ * 3.13), one launch in its place.  active_state: one persistent u8 per agent row, 1 = the agent acted at this step.
+ * traj_policy_id[b, t] = active_state[b] ? policy_id : -1, and only then active_state[b] = active_in[b] != 0 (what the
+ * env reported WITH this step: it rules the next one).  The thread that owns row b reads and rewrites its byte.  Every
+ * other output holds the bits sf_traj_write_env_step writes.  Refused before any launch (-1): a null active_in or
+ * active_state, an active_in that aliases active_state, and what sf_traj_write_env_step refuses. */
+int sf_traj_write_env_step_active(const float *rewards, const uint8_t *terminated, const uint8_t *truncated, int B, int T,
+                                  int t, float reward_scale, float reward_clip, int policy_id, float *traj_rewards,
+                                  uint8_t *traj_dones, uint8_t *traj_time_outs, int32_t *traj_policy_id, float *ep_return,
+                                  int32_t *ep_len, double *ep_stats, const uint8_t *active_in, uint8_t *active_state,
+                                  void *stream);
+
 /* Ant-shaped continuous stand-in env (config 5): f32 observations [B, D], Box actions [B, A] (row stride act_stride
  * floats, e.g. traj.actions[:, t]).  One launch per env step writes the next observation into `state` (the env's own
  * [B, D] copy) AND into obs_out (row stride out_stride floats = slot t+1 of the slab); reset != 0: fresh observations
@@ -500,6 +512,17 @@ int sf_mlp2_fwd(const float *x, int64_t x_stride, int64_t n, int D, float sub_me
  * [B, H or 2H] view traj.rnn_states[:, t+1] (row stride out_stride floats). */
 int sf_rnn_store_state(const float *h, const float *c, const uint8_t *dones, int64_t done_stride, float *out,
                        int64_t out_stride, int64_t B, int H, void *stream);
+
+/* sf_rnn_store_state for a rollout that tracks inactive agents (non_batched_sampling.py:605-612): a row
+ * whose step was recorded with policy_id < 0 keeps the state it had,
+ *   out[b] = (policy_id[b] < 0 ? prev[b] : [h[b] | c[b]]) * (1 - done[b]).
+ * prev: the [B, H or 2H] view traj.rnn_states[:, t] (this layer's columns, row stride prev_stride floats); policy_id: the
+ * i32 [B] column traj.policy_id[:, t] (element stride pid_stride).  With no negative policy_id the bits of
+ * sf_rnn_store_state.  Refused before any launch (-1): what sf_rnn_store_state refuses, a null prev or policy_id, a
+ * row stride below the row width, an out whose extent overlaps prev's. */
+int sf_rnn_store_state_held(const float *h, const float *c, const uint8_t *dones, int64_t done_stride, const float *prev,
+                            int64_t prev_stride, const int32_t *policy_id, int64_t pid_stride, float *out,
+                            int64_t out_stride, int64_t B, int H, void *stream);
 
 /* training pass of a recurrent model (learner.py:557-569, rnn_utils.py:59-105): minibatch = Cn chunks of R consecutive
  * dataset rows, chunk c starting at row index[c*R] (index != NULL: a permuted minibatch, every chunk's R rows consecutive

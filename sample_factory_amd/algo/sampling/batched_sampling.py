@@ -5,7 +5,7 @@ inference_worker.py:313-341 (InferenceWorker._handle_policy_steps), collapsed in
   per step t:   policy forward on slab obs[:, t] (in place)          K2+K3  sf_conv_fwd stack
                 sample + write policy outputs into traj[:, t]         K4+K5  sf_sample_write_step[_tuple][_masked]
                 env.step -> obs straight into slab obs[:, t+1]        K1     (zero-copy for envs with step_into)
-                rewards/dones/time_outs/policy_id + episode stats     K6     sf_traj_write_env_step
+                rewards/dones/time_outs/policy_id + episode stats     K6     sf_traj_write_env_step[_active]
 
 No host synchronisation happens inside a rollout (the reference syncs the device and round-trips dones/rewards to the
 CPU every step: batched_sampling.py:216,323,390-392; torch_utils.py:58-66).
@@ -20,8 +20,21 @@ import numpy as np
 import torch
 
 from sample_factory_amd import lib
+from sample_factory_amd.algo.sampling.parallel_env import infos_is_active
 from sample_factory_amd.algo.utils.tensor_dict import TensorDict
 from sample_factory_amd.envs.spaces import action_head_sizes, heads_mixed, is_box, split_tuple_actions
+
+
+def tracks_inactive_agents(cfg, env, multi_key: bool = False) -> bool:
+    """is --track_inactive_agents on for a runner of `env`?  Refuses, at set-up, the one kind of env it cannot serve: a
+    zero-copy env (`step_into` writes into the slab and returns rewards and flags, no infos) has nowhere to report
+    is_active.  (A step_into env with several observation keys is stepped through step() and is fine.)"""
+    if not getattr(cfg, "track_inactive_agents", False):
+        return False
+    if hasattr(env, "step_into") and not multi_key:
+        raise NotImplementedError("track_inactive_agents with a zero-copy (step_into) env: step_into returns no infos, the "
+                                  "env cannot report is_active; let it return them from step()")
+    return True
 
 
 class BatchedVectorEnvRunner:
@@ -101,9 +114,21 @@ class BatchedVectorEnvRunner:
                         if self.fs_k > 1 and traj["obs"][k].dim() == 5}
         if self.fs_k > 1 and hasattr(env, "step_into"):
             raise NotImplementedError(f"device_framestack={self.fs_k} with a zero-copy (step_into) env")
+        # --track_inactive_agents: one persistent byte per agent row, 1 = the env's last info did not say
+        # is_active=False.  Step t records policy_id -1 and holds the recurrent state where the byte is 0, then the byte
+        # takes what the env reported with step t.  The bytes belong to the runner: they outlive a rollout, set_slab and
+        # carry_over, and a done does not touch them (non_batched_sampling.py:82-84, 197-203); reset() sets them to 1.
+        # A zero-copy (step_into) env returns no infos: refused here, as masks and the device frame stack are.
+        self.track_active = tracks_inactive_agents(cfg, env, self.multi_key)
+        if self.track_active:
+            self._active = torch.ones(self.B, dtype=torch.uint8, device=dev)
+            self._active_in = torch.ones(self.B, dtype=torch.bool, device=dev)  # this step's report (host envs: H2D target)
+            self._all_active = torch.ones(self.B, dtype=torch.bool, device=dev)  # never written: infos without the key
 
     def reset(self) -> None:
         """First observation into slab obs[:, 0] (batched_sampling.py:172-206)."""
+        if self.track_active:
+            self._active.fill_(1)
         if self.zero_copy:
             self.env.reset_into(self.obs[:, 0])
         else:
@@ -303,6 +328,7 @@ class BatchedVectorEnvRunner:
 
     def _env_step_and_record(self, t: int, env_actions) -> None:
         tr, T, cfg = self.traj, self.T, self.cfg
+        active_in = None
         if self.zero_copy:
             if self.mixed:  # batched_sampling.py:51-59: a list with one (device) array per Tuple member
                 env_actions = split_tuple_actions(env_actions, self.heads)
@@ -312,12 +338,12 @@ class BatchedVectorEnvRunner:
                 self.host_env = False
             t0 = time.perf_counter()
             if self.async_env:
-                o, rew, term, trunc, _ = self.env.step_wait()
+                o, rew, term, trunc, info = self.env.step_wait()
             else:
                 acts_in = self._actions_to_host(env_actions) if self.host_env else env_actions
                 if self.mixed:  # batched_sampling.py:51-59: a list with one array per Tuple member
                     acts_in = split_tuple_actions(acts_in, self.heads)
-                o, rew, term, trunc, _ = self.env.step(acts_in)
+                o, rew, term, trunc, info = self.env.step(acts_in)
             if self.ingest_prof is not None:
                 self.ingest_prof["env_step_s"] = self.ingest_prof.get("env_step_s", 0.0) + time.perf_counter() - t0
             self._store_obs(o, t + 1)
@@ -326,7 +352,14 @@ class BatchedVectorEnvRunner:
                 self._to_device("term", term, self._term)
                 self._to_device("trunc", trunc, self._trunc)
                 rew, term, trunc = self._rew, self._term, self._trunc
+                if self.track_active:  # same pinned route, same fixed device address: the record step stays a program
+                    flags = infos_is_active(info, self.B)
+                    if flags is not None:
+                        self._to_device("active", flags, self._active_in)
+                    active_in = self._all_active if flags is None else self._active_in
             else:
+                if self.track_active:
+                    active_in = self._device_is_active(info)
                 rew = torch.as_tensor(rew, dtype=torch.float32, device=self.device).contiguous()
                 term = torch.as_tensor(term, dtype=torch.bool, device=self.device).contiguous()
                 trunc = torch.as_tensor(trunc, dtype=torch.bool, device=self.device).contiguous()
@@ -335,37 +368,65 @@ class BatchedVectorEnvRunner:
             prog = rec_key = None  # torch model path (the state store is a torch op) / env outputs in fresh tensors every step
         else:
             # (the shaping constants are launch arguments: a cfg update between rollouts must not replay the old ones)
-            prog, rec_key = self._program("record", t, (rew.data_ptr(), term.data_ptr(), trunc.data_ptr(),
-                                                        float(cfg.reward_scale), float(cfg.reward_clip)))
+            extra = (rew.data_ptr(), term.data_ptr(), trunc.data_ptr(), float(cfg.reward_scale), float(cfg.reward_clip))
+            if self.track_active:
+                extra += (active_in.data_ptr(), self._active.data_ptr())
+            prog, rec_key = self._program("record", t, extra)
         if prog is not None:
             prog.replay()
         elif rec_key is not None:
             with lib.record_launches() as prog:
-                self._record_step(t, rew, term, trunc)
+                self._record_step(t, rew, term, trunc, active_in)
             self._progs[rec_key] = prog
         else:
-            self._record_step(t, rew, term, trunc)
+            self._record_step(t, rew, term, trunc, active_in)
         self.global_step += 1
 
-    def _record_step(self, t: int, rew, term, trunc) -> None:
-        """env outputs of step t -> slab (rewards shaped, dones, episode statistics), next-step recurrent state"""
+    def _device_is_active(self, info) -> torch.Tensor:
+        """a device env's is_active report as a contiguous device bool / u8 [B]: a CUDA tensor in the infos dict is used in
+        place, per-agent dicts or a host array are uploaded, infos without the key mean all active"""
+        v = info.get("is_active") if isinstance(info, dict) else None
+        if isinstance(v, torch.Tensor) and v.is_cuda:
+            if v.numel() != self.B:
+                raise ValueError(f"info['is_active'] has {v.numel()} entries for {self.B} agents")
+            v = v.reshape(-1)
+            return v.contiguous() if v.dtype in (torch.bool, torch.uint8) else (v != 0)
+        flags = infos_is_active(info, self.B)
+        return self._all_active if flags is None else torch.as_tensor(flags, device=self.device)
+
+    def _record_step(self, t: int, rew, term, trunc, active_in=None) -> None:
+        """env outputs of step t -> slab (rewards shaped, dones, episode statistics), next-step recurrent state;
+        active_in (--track_inactive_agents): the env's is_active report of this step"""
         tr, T, cfg = self.traj, self.T, self.cfg
         if self.fs_keys:  # (behind the flag transfers: the stack of obs[:, t + 1] needs this step's terminated / truncated)
             self._framestack(t + 1, term, trunc)
-        lib.traj_write_env_step(rew, term, trunc, T, t, cfg.reward_scale, cfg.reward_clip, self.policy_id,
-                                tr["rewards"], tr["dones"], tr["time_outs"], tr["policy_id"], self.ep_return,
-                                self.ep_len, self.ep_stats)
+        if self.track_active:  # policy_id[:, t] = -1 where the agent was told to wait, then the bytes take this step's report
+            lib.traj_write_env_step_active(rew, term, trunc, T, t, cfg.reward_scale, cfg.reward_clip, self.policy_id,
+                                           tr["rewards"], tr["dones"], tr["time_outs"], tr["policy_id"], self.ep_return,
+                                           self.ep_len, self.ep_stats, active_in, self._active)
+        else:
+            lib.traj_write_env_step(rew, term, trunc, T, t, cfg.reward_scale, cfg.reward_clip, self.policy_id,
+                                    tr["rewards"], tr["dones"], tr["time_outs"], tr["policy_id"], self.ep_return,
+                                    self.ep_len, self.ep_stats)
         if self.rnn:  # batched_sampling.py:332-335: next-step state = new_rnn_states * (1 - done)
             # the state THIS runner's forward produced (keyed by its tag: the learner thread may have run its bootstrap
             # forward through the same model object since)
             parts = self.ac.new_rnn_parts_of(self.tag)
             if parts is not None:  # native model: mask + store [h | c] in one launch per recurrent layer
                 dst, SL = tr["rnn_states"][:, t + 1], tr["rnn_states"].shape[-1] // len(parts)
+                src = tr["rnn_states"][:, t]
                 for l, (h_, c_) in enumerate(parts):  # stacked layers: layer l owns columns [l * SL, (l + 1) * SL) (core.py:54-58)
-                    lib.rnn_store_state(h_, c_, tr["dones"][:, t], dst[:, l * SL:(l + 1) * SL])
+                    if self.track_active:  # a row recorded with policy_id -1 keeps its state (non_batched_sampling.py:605-612)
+                        lib.rnn_store_state_held(h_, c_, tr["dones"][:, t], src[:, l * SL:(l + 1) * SL],
+                                                 tr["policy_id"][:, t], dst[:, l * SL:(l + 1) * SL])
+                    else:
+                        lib.rnn_store_state(h_, c_, tr["dones"][:, t], dst[:, l * SL:(l + 1) * SL])
             else:                  # torch model path
                 keep = (~tr["dones"][:, t]).to(torch.float32).unsqueeze(1)
-                torch.mul(self.ac.new_rnn_states_of(self.tag), keep, out=tr["rnn_states"][:, t + 1])
+                new = self.ac.new_rnn_states_of(self.tag)
+                if self.track_active:
+                    new = torch.where((tr["policy_id"][:, t] < 0).unsqueeze(1), tr["rnn_states"][:, t], new)
+                torch.mul(new, keep, out=tr["rnn_states"][:, t + 1])
 
     def set_slab(self, traj: TensorDict, carry_from: Optional[TensorDict] = None) -> None:
         """async mode: switch to another slab; its step 0 continues from the last step of `carry_from`"""

@@ -40,6 +40,23 @@ def _as_obs_dict(obs) -> Dict[str, Any]:
     return obs if isinstance(obs, dict) else {"obs": obs}
 
 
+def infos_is_active(infos, n: int) -> Optional[np.ndarray]:
+    """the `is_active` flags of one env step as bool[n], or None when the infos carry none (= every agent is active).
+    infos: a list / tuple of per-agent dicts (a missing key means active, non_batched_sampling.py:82-84), a dict holding an
+    `is_active` array (or, a single-agent env, one flag), or anything else (no flags)."""
+    if isinstance(infos, dict):
+        v = infos.get("is_active")
+        if v is None:
+            return None
+        v = np.asarray(v.cpu() if hasattr(v, "cpu") else v).reshape(-1)
+        if v.size != n:
+            raise ValueError(f"info['is_active'] has {v.size} entries for {n} agents")
+        return v.astype(np.bool_, copy=False)
+    if isinstance(infos, (list, tuple)) and len(infos) == n and any(isinstance(i, dict) and "is_active" in i for i in infos):
+        return np.fromiter((bool(i.get("is_active", True)) if isinstance(i, dict) else True for i in infos), np.bool_, n)
+    return None
+
+
 def env_is_batched(env) -> bool:
     """make_env.py:30-39: `num_agents` > 1 or an explicit `is_multiagent` -> the env speaks per-agent vectors"""
     n = getattr(env, "num_agents", 1)
@@ -186,7 +203,10 @@ class _InstanceStepper:
                 self._put_obs(a, obs, row0, nrows, batched)
                 continue
             act = _format_actions(a["act"][row0:row0 + nrows], self.heads, self.continuous, batched)
-            obs, rew, term, trunc, _info = env.step(act)
+            obs, rew, term, trunc, info = env.step(act)
+            if "active" in a:  # --track_inactive_agents: the agents' info["is_active"] beside their rewards (a missing key: active)
+                flags = infos_is_active(info, nrows)
+                a["active"][row0:row0 + nrows] = True if flags is None else flags
             if batched:
                 a["rew"][row0:row0 + nrows] = np.asarray(rew.cpu() if hasattr(rew, "cpu") else rew, dtype=np.float32).reshape(-1)
                 a["term"][row0:row0 + nrows] = np.asarray(term.cpu() if hasattr(term, "cpu") else term).reshape(-1)
@@ -281,7 +301,7 @@ class ParallelVecEnvView(RewardShapingInterface):
         self.parent._wait(self.split)
         self._pending = False
         a = self._arrays()
-        return self._obs(), a["rew"], a["term"], a["trunc"], {}
+        return self._obs(), a["rew"], a["term"], a["trunc"], ({"is_active": a["active"]} if "active" in a else {})
 
     def step(self, actions):
         self.step_async(actions)
@@ -361,6 +381,8 @@ class ParallelHostEnvs:
             add("rew", (n,), np.float32)
             add("term", (n,), np.bool_)
             add("trunc", (n,), np.bool_)
+            if getattr(cfg, "track_inactive_agents", False):
+                add("active", (n,), np.bool_)
             if self.continuous:
                 add("act", (n, int(self.action_space.shape[0])), np.float32)
             elif heads_mixed(self.heads):  # Tuple with a Box member: the slab's f32 action rows

@@ -86,6 +86,9 @@ ENGINE_FLAGS = [
     ("device_framestack", int, 1),           # k > 1: the env delivers ONE frame per step and the k-frame stack of every CHW
     #                                          observation key is kept in the slab (sf_framestack_step);
     #                                          not env_framestack, which reference-style env factories read to stack themselves
+    ("track_inactive_agents", _bool, False),  # honour info["is_active"]: the step AFTER an agent reported False is recorded
+    #                                          with policy_id = -1 (the learner's validity mask drops it) and leaves the
+    #                                          agent's recurrent state as it was (off: infos are ignored)
 ]
 
 

@@ -2668,15 +2668,15 @@ extern "C" int sf_sample_write_step_tuple_masked(const float *logits, int ld_log
 }
 
 // =========================================================================================== K1/K6 env step -> traj
-__global__ __launch_bounds__(256) void k_traj_write_env(const float *__restrict__ rewards,
-                                                        const uint8_t *__restrict__ terminated,
-                                                        const uint8_t *__restrict__ truncated, int B, int T, int t,
-                                                        float scale, float clip, int pid,
-                                                        float *__restrict__ t_rewards, uint8_t *__restrict__ t_dones,
-                                                        uint8_t *__restrict__ t_timeouts, int32_t *__restrict__ t_pid,
-                                                        float *__restrict__ ep_ret, int32_t *__restrict__ ep_len,
-                                                        double *__restrict__ ep_stats) {
-    __shared__ double lds[4 * 3];
+// one thread per agent row b; pid: the policy id THIS row records (the is_active kernel below passes -1 for some rows)
+__device__ __forceinline__ void traj_write_env_row(const float *__restrict__ rewards,
+                                                   const uint8_t *__restrict__ terminated,
+                                                   const uint8_t *__restrict__ truncated, int B, int T, int t,
+                                                   float scale, float clip, int pid, float *__restrict__ t_rewards,
+                                                   uint8_t *__restrict__ t_dones, uint8_t *__restrict__ t_timeouts,
+                                                   int32_t *__restrict__ t_pid, float *__restrict__ ep_ret,
+                                                   int32_t *__restrict__ ep_len, double *__restrict__ ep_stats,
+                                                   double *lds) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     double acc[3] = {0.0, 0.0, 0.0};
     if (b < B) {
@@ -2705,6 +2705,38 @@ __global__ __launch_bounds__(256) void k_traj_write_env(const float *__restrict_
     }
 }
 
+__global__ __launch_bounds__(256) void k_traj_write_env(const float *__restrict__ rewards,
+                                                        const uint8_t *__restrict__ terminated,
+                                                        const uint8_t *__restrict__ truncated, int B, int T, int t,
+                                                        float scale, float clip, int pid,
+                                                        float *__restrict__ t_rewards, uint8_t *__restrict__ t_dones,
+                                                        uint8_t *__restrict__ t_timeouts, int32_t *__restrict__ t_pid,
+                                                        float *__restrict__ ep_ret, int32_t *__restrict__ ep_len,
+                                                        double *__restrict__ ep_stats) {
+    __shared__ double lds[4 * 3];
+    traj_write_env_row(rewards, terminated, truncated, B, T, t, scale, clip, pid, t_rewards, t_dones, t_timeouts, t_pid,
+                       ep_ret, ep_len, ep_stats, lds);
+}
+
+// the same step for envs that report info["is_active"]: a row the env declared inactive at its PREVIOUS step records
+// policy_id -1 (the learner's validity mask drops it), then the row's byte takes what the env reported with this step
+// (non_batched_sampling.py:82-84, 197-203).  The thread that owns row b is the only one that touches active[b].
+__global__ __launch_bounds__(256) void k_traj_write_env_active(
+    const float *__restrict__ rewards, const uint8_t *__restrict__ terminated, const uint8_t *__restrict__ truncated, int B,
+    int T, int t, float scale, float clip, int pid, float *__restrict__ t_rewards, uint8_t *__restrict__ t_dones,
+    uint8_t *__restrict__ t_timeouts, int32_t *__restrict__ t_pid, float *__restrict__ ep_ret,
+    int32_t *__restrict__ ep_len, double *__restrict__ ep_stats, const uint8_t *__restrict__ active_in,
+    uint8_t *__restrict__ active) {
+    __shared__ double lds[4 * 3];
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) {
+        if (!active[b]) pid = -1;
+        active[b] = (uint8_t)(active_in[b] != 0);
+    }
+    traj_write_env_row(rewards, terminated, truncated, B, T, t, scale, clip, pid, t_rewards, t_dones, t_timeouts, t_pid,
+                       ep_ret, ep_len, ep_stats, lds);
+}
+
 extern "C" int sf_traj_write_env_step(const float *rewards, const uint8_t *terminated, const uint8_t *truncated, int B,
                                       int T, int t, float reward_scale, float reward_clip, int policy_id,
                                       float *traj_rewards, uint8_t *traj_dones, uint8_t *traj_time_outs,
@@ -2718,6 +2750,25 @@ extern "C" int sf_traj_write_env_step(const float *rewards, const uint8_t *termi
         rewards, terminated, truncated, B, T, t, reward_scale, reward_clip, policy_id, traj_rewards, traj_dones,
         traj_time_outs, traj_policy_id, ep_return, ep_len, ep_stats);
     return sf_launch_status("sf_traj_write_env_step");
+}
+
+extern "C" int sf_traj_write_env_step_active(const float *rewards, const uint8_t *terminated, const uint8_t *truncated,
+                                             int B, int T, int t, float reward_scale, float reward_clip, int policy_id,
+                                             float *traj_rewards, uint8_t *traj_dones, uint8_t *traj_time_outs,
+                                             int32_t *traj_policy_id, float *ep_return, int32_t *ep_len,
+                                             double *ep_stats, const uint8_t *active_in, uint8_t *active_state,
+                                             void *stream) {
+    SF_REQUIRE(rewards && terminated && traj_rewards && traj_dones && traj_time_outs && traj_policy_id,
+               "sf_traj_write_env_step_active: null pointer");
+    SF_REQUIRE(active_in && active_state, "sf_traj_write_env_step_active: null active_in / active_state");
+    SF_REQUIRE(B > 0 && T > 0 && t >= 0 && t < T, "sf_traj_write_env_step_active: bad shape");
+    SF_REQUIRE(active_in + B <= active_state || active_state + B <= active_in,
+               "sf_traj_write_env_step_active: active_in aliases active_state");
+    SF_REQUIRE((ep_return == nullptr) == (ep_len == nullptr), "sf_traj_write_env_step_active: ep_return/ep_len mismatch");
+    k_traj_write_env_active<<<dim3((unsigned)((B + 255) / 256)), dim3(256), 0, STREAM(stream)>>>(
+        rewards, terminated, truncated, B, T, t, reward_scale, reward_clip, policy_id, traj_rewards, traj_dones,
+        traj_time_outs, traj_policy_id, ep_return, ep_len, ep_stats, active_in, active_state);
+    return sf_launch_status("sf_traj_write_env_step_active");
 }
 
 // =========================================================================================== synthetic env

@@ -21,6 +21,7 @@
 // work-group per CU (LDS-limited).  A bounded spin turns a lost work-group (GPU shared with another process) into an
 // error flag instead of a hang.
 #include <stdlib.h>
+#include <type_traits>
 
 #include "sf_common.h"
 #include "sf_rnn_cell.h"
@@ -1267,4 +1268,62 @@ extern "C" int sf_rnn_wideseq_bwd(int kind, const float *dout, const float *gate
         if (rc) return rc;
     }
     return 0;
+}
+
+// ---- rollout state store that honours is_active.  sf_rnn_store_state (sf_rl.hip) with one more choice
+// per row: a step recorded with policy_id < 0 was not the agent's to act on, so the row keeps the state it had
+// (non_batched_sampling.py:605-612); the done mask applies either way.  out row b = [h | c] (c: LSTM)
+// One thread per V floats of a row: V = 4 (one 16-byte load and store) where H, the row strides and the bases allow
+// it, else 1.  A thread's floats lie on one side of the h | c seam because H % V == 0.
+template <int V>
+__global__ __launch_bounds__(256) void k_rnn_store_state_held(const float *__restrict__ h, const float *__restrict__ c,
+                                                              const uint8_t *__restrict__ dones, int64_t done_stride,
+                                                              const float *__restrict__ prev, int64_t prev_stride,
+                                                              const int32_t *__restrict__ pid, int64_t pid_stride,
+                                                              float *__restrict__ out, int64_t out_stride, int64_t B, int H) {
+    using vec = typename std::conditional<V == 4, float4, float>::type;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int WV = (c ? 2 * H : H) / V;
+    if (i >= B * WV) return;
+    const int64_t b = i / WV;
+    const int j = (int)(i - b * WV) * V;
+    // the new state is loaded whatever policy_id says, as in the plain kernel: its load, the flag's and the done's are in
+    // flight together, and only a held row waits for one more (prev)
+    vec v = *reinterpret_cast<const vec *>(j < H ? h + b * H + j : c + b * H + j - H);
+    if (pid[b * pid_stride] < 0) v = *reinterpret_cast<const vec *>(prev + b * prev_stride + j);
+    if (dones[b * done_stride]) v = vec{};
+    *reinterpret_cast<vec *>(out + b * out_stride + j) = v;
+}
+
+// do the row sets {a + b * sa + [0, W)} and {o + b * so + [0, W)}, b < B, share an element?  (units: floats.)  Exact for
+// equal strides — columns t and t + 1 of one slab interleave without touching —, by extent otherwise
+static bool rows_overlap(const float *a, int64_t sa, const float *o, int64_t so, int64_t B, int64_t W) {
+    const intptr_t d = ((intptr_t)o - (intptr_t)a) / (intptr_t)sizeof(float);  // (both 4-byte aligned: checked by the caller)
+    if (sa != so) return d < (B - 1) * sa + W && -d < (B - 1) * so + W;
+    const intptr_t r = ((d % sa) + sa) % sa, k = (d - r) / sa;  // d = k * sa + r, 0 <= r < sa: o's row 0 starts r into a's row k
+    return (r < W && k > -B && k < B) || (sa - r < W && k + 1 > -B && k + 1 < B);
+}
+
+extern "C" int sf_rnn_store_state_held(const float *h, const float *c, const uint8_t *dones, int64_t done_stride,
+                                       const float *prev, int64_t prev_stride, const int32_t *policy_id,
+                                       int64_t pid_stride, float *out, int64_t out_stride, int64_t B, int H,
+                                       void *stream) {
+    SF_REQUIRE(h && dones && out && B > 0 && H > 0, "sf_rnn_store_state_held: bad args");
+    SF_REQUIRE(prev && policy_id, "sf_rnn_store_state_held: null prev / policy_id");
+    const int64_t W = c ? 2 * (int64_t)H : H;
+    SF_REQUIRE(prev_stride >= W && out_stride >= W, "sf_rnn_store_state_held: row stride below the row width %lld",
+               (long long)W);
+    SF_REQUIRE((((uintptr_t)prev | (uintptr_t)out) & 3) == 0, "sf_rnn_store_state_held: prev / out not 4-byte aligned");
+    SF_REQUIRE(!rows_overlap(prev, prev_stride, out, out_stride, B, W), "sf_rnn_store_state_held: out overlaps prev");
+    const bool v4 = H % 4 == 0 && prev_stride % 4 == 0 && out_stride % 4 == 0 &&
+                    (((uintptr_t)h | (uintptr_t)c | (uintptr_t)prev | (uintptr_t)out) & 15) == 0;
+    const int64_t n = B * W / (v4 ? 4 : 1);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (v4)
+        k_rnn_store_state_held<4><<<grid, block, 0, STREAM(stream)>>>(h, c, dones, done_stride, prev, prev_stride, policy_id,
+                                                                     pid_stride, out, out_stride, B, H);
+    else
+        k_rnn_store_state_held<1><<<grid, block, 0, STREAM(stream)>>>(h, c, dones, done_stride, prev, prev_stride, policy_id,
+                                                                     pid_stride, out, out_stride, B, H);
+    return sf_launch_status("sf_rnn_store_state_held");
 }

@@ -268,6 +268,85 @@ def make_masked_bandit_env(full_env_name, cfg=None, env_config=None, render_mode
     return MaskedBanditEnv(num_agents=n, num_actions=a, seed=(getattr(cfg, "seed", None) or 0) if cfg is not None else 0)
 
 
+class TurnBasedMaskedBanditEnv:
+    """HOST vector env of `num_games` two-agent turn-based games (row 2 * g + a = agent a of game g): the masked bandit,
+    played in turns.  The agents of a game alternate; with every step the env reports, per agent, whether the observation
+    it just handed out is that agent's to act on: info["is_active"] = False for the one that now waits (what the
+    reference's PettingZoo adapter reports for every agent but the one to move).  The action of a waiting agent is
+    ignored and the reward is paid to the mover only; observations carry an "action_mask" that always allows the rewarded
+    action.  Episodes last `episode_len` steps, then every row reports `terminated` and the game goes on (auto-reset;
+    whose turn it is does not depend on episode boundaries).
+
+    Step k (0-based, counted from reset) is moved by agent (k + g) % 2 of game g, so the infos returned WITH step k name
+    agent (k + 1 + g) % 2 as active.  `script` (bool [period, 2 * num_games]) replaces that pattern: the infos of step k
+    carry script[k % period].  `dict_infos`: the flags come as one {"is_active": bool array} dict instead of a list of
+    per-agent dicts, and agents whose flag is True leave the key out of their dict in the list form (missing = active)."""
+
+    def __init__(self, num_games=3, num_actions=4, episode_len=5, seed=0, script=None, dict_infos=False):
+        self.num_games, self.A, self.episode_len = int(num_games), int(num_actions), int(episode_len)
+        self.num_agents = 2 * self.num_games
+        self.is_multiagent = True
+        self.observation_space = spaces.Dict({"obs": spaces.Box(0, 1, (self.A,), np.float32),
+                                              "action_mask": spaces.Box(0, 1, (self.A,), np.uint8)})
+        self.action_space = spaces.Discrete(self.A)
+        self.script = None if script is None else np.asarray(script, dtype=np.bool_).reshape(-1, self.num_agents)
+        self.dict_infos = bool(dict_infos)
+        self._seed = int(seed)
+        self._rows = np.arange(self.num_agents)
+        self.reset()
+
+    def _draw(self):
+        self.target = self._rng.integers(0, self.A, self.num_agents)
+        self.mask = self._rng.random((self.num_agents, self.A)) < 0.5
+        self.mask[self._rows, self.target] = True
+
+    def _out(self):
+        obs = np.zeros((self.num_agents, self.A), np.float32)
+        obs[self._rows, self.target] = 1.0
+        return {"obs": obs, "action_mask": self.mask.astype(np.uint8)}
+
+    def movers(self, k: int) -> np.ndarray:
+        """bool [agents]: who moves at step k"""
+        return (self._rows % 2) == ((k + self._rows // 2) % 2)
+
+    def active_after(self, k: int) -> np.ndarray:
+        """bool [agents]: the is_active flags the infos of step k carry"""
+        return self.script[k % len(self.script)] if self.script is not None else self.movers(k + 1)
+
+    def reset(self, **kwargs):
+        self._rng = np.random.default_rng(self._seed)
+        self.k = self.ep_step = 0
+        self._draw()
+        return self._out(), [{} for _ in range(self.num_agents)]
+
+    def step(self, actions):
+        a = np.asarray(actions).reshape(-1)
+        rew = ((a == self.target) & self.movers(self.k)).astype(np.float32)
+        active = self.active_after(self.k)
+        self.k += 1
+        self.ep_step += 1
+        term = np.full(self.num_agents, self.ep_step >= self.episode_len)
+        if term[0]:
+            self.ep_step = 0
+        self._draw()
+        infos = {"is_active": active.copy()} if self.dict_infos else \
+            [{} if f else {"is_active": False} for f in active.tolist()]
+        return self._out(), rew, term, np.zeros(self.num_agents, np.bool_), infos
+
+    def close(self):
+        pass
+
+
+def make_turn_based_masked_bandit_env(full_env_name, cfg=None, env_config=None, render_mode=None):
+    """cfg.synthetic_num_games / synthetic_num_actions / synthetic_episode_len size the env; cfg.synthetic_active_script
+    (bool [period, agents], nested lists) makes it the scripted variant"""
+    g = lambda name, d: (getattr(cfg, name, None) or d) if cfg is not None else d  # noqa: E731
+    seed = g("seed", 0) + int(getattr(env_config, "env_id", 0) or 0)
+    return TurnBasedMaskedBanditEnv(num_games=int(g("synthetic_num_games", 3)), num_actions=int(g("synthetic_num_actions", 4)),
+                                    episode_len=int(g("synthetic_episode_len", 5)), seed=seed,
+                                    script=g("synthetic_active_script", None), dict_infos=bool(g("synthetic_dict_infos", False)))
+
+
 class MaskedTupleBanditEnv:
     """MaskedBanditEnv on Tuple(Discrete(n_0), Discrete(n_1), ...): obs = the members' rewarded actions as one-hots side
     by side, obs["action_mask"] u8 [N, sum n_i] with one column per distribution parameter (member i owns the columns

@@ -52,7 +52,7 @@ SYMBOLS = [
     "sf_adam_step", "sf_adam_step_dlr", "sf_lr_kl_adaptive", "sf_clock_probe", "sf_lamb_step", "sf_rnn_cell_fwd", "sf_rnn_cell_bwd", "sf_rows_add_scale", "sf_mlp2_fwd", "sf_rnn_store_state", "sf_rnn_chunk_setup", "sf_lstm_seq_supported", "sf_lstm_seq_fwd", "sf_lstm_seq_bwd", "sf_gru_seq_fwd", "sf_gru_seq_bwd", "sf_seq_fwd_x_supported", "sf_lstm_seq_fwd_x", "sf_gru_seq_fwd_x", "sf_rnn_rowseq_supported", "sf_rnn_rowseq_fwd", "sf_rnn_rowseq_bwd", "sf_rnn_wideseq_supported", "sf_rnn_seq_slab_rows", "sf_rnn_wideseq_fwd", "sf_rnn_wideseq_bwd", "sf_linear_fwd_dual_supported", "sf_linear_fwd_dual",
     "sf_obsnorm_moments", "sf_obsnorm_update", "sf_obsnorm_apply", "sf_sample_write_step",
     "sf_sample_write_step_tuple", "sf_sample_write_step_masked", "sf_sample_write_step_tuple_masked",
-    "sf_traj_write_env_step", "sf_synth_obs",
+    "sf_traj_write_env_step", "sf_traj_write_env_step_active", "sf_rnn_store_state_held", "sf_synth_obs",
     "sf_synth_step", "sf_synth_vec_step", "sf_h2d_rows", "sf_copy_rows", "sf_framestack_step", "sf_conv_fwd", "sf_conv_fwd_workspace", "sf_conv_wgrad_workspace", "sf_conv_wgrad",
     "sf_conv_dgrad", "sf_conv_norm_supported", "sf_conv_fwd_norm", "sf_conv_wgrad_norm", "sf_conv_relu_mask_supported", "sf_conv_fwd_relu_mask", "sf_conv_wgrad_relu_mask", "sf_conv_kernel_name", "sf_conv_fwd_t_supported", "sf_conv_fwd_t_workspace", "sf_conv_fwd_t", "sf_transpose",
     "sf_conv_fwd_os_supported", "sf_conv_fwd_relu_mask_os", "sf_conv_fwd_t_os",
@@ -406,6 +406,25 @@ def rnn_store_state(h, c, dones_col, out) -> None:
     _check(load().sf_rnn_store_state(ptr(h, "f32", "h"), ptr(c, "f32", "c"), _vp(dones_col),
                                      i64(dones_col.stride(0)), _raw(out, "f32", "out"), i64(out.stride(0)), i64(B), int(H),
                                      stream()), "sf_rnn_store_state")
+
+
+def rnn_store_state_held(h, c, dones_col, prev, policy_id_col, out) -> None:
+    """rnn_store_state for a rollout that tracks inactive agents: rows with policy_id_col[b] < 0 keep prev[b] (the same
+    columns of the previous step's state); prev / out / the two columns may be strided views of the slab"""
+    B, H = h.shape
+    W = H if c is None else 2 * H
+    if dones_col.dtype not in (torch.bool, torch.uint8) or not dones_col.is_cuda or dones_col.shape != (B,):
+        raise SfHipError(f"rnn_store_state_held: dones must be a device bool/u8 [B] column, got {dones_col.dtype} {tuple(dones_col.shape)}")
+    if policy_id_col.dtype != torch.int32 or not policy_id_col.is_cuda or policy_id_col.shape != (B,):
+        raise SfHipError(f"rnn_store_state_held: policy_id must be a device i32 [B] column, got {policy_id_col.dtype} {tuple(policy_id_col.shape)}")
+    for name, x in (("out", out), ("prev", prev)):
+        if x.shape != (B, W) or x.stride(1) != 1:
+            raise SfHipError(f"rnn_store_state_held: {name} must be [B, {W}] with unit column stride")
+    _check(load().sf_rnn_store_state_held(ptr(h, "f32", "h"), ptr(c, "f32", "c"), _vp(dones_col),
+                                          i64(dones_col.stride(0)), _raw(prev, "f32", "prev"), i64(prev.stride(0)),
+                                          _raw(policy_id_col, "i32", "policy_id"), i64(policy_id_col.stride(0)),
+                                          _raw(out, "f32", "out"), i64(out.stride(0)), i64(B), int(H), stream()),
+           "sf_rnn_store_state_held")
 
 
 def rnn_chunk_setup(dones, valids, rnn_states, index, offset, Cn, R, keep_tm, h0, traj_T=0) -> None:
@@ -825,6 +844,25 @@ def traj_write_env_step(rewards, terminated, truncated, T, t, reward_scale, rewa
                                          ptr(traj_dones, "u8"), ptr(traj_time_outs, "u8"), ptr(traj_policy_id, "i32"),
                                          ptr(ep_return, "f32"), ptr(ep_len, "i32"), ptr(ep_stats, "f64"), stream()),
            "sf_traj_write_env_step")
+
+
+def traj_write_env_step_active(rewards, terminated, truncated, T, t, reward_scale, reward_clip, policy_id, traj_rewards,
+                               traj_dones, traj_time_outs, traj_policy_id, ep_return, ep_len, ep_stats, active_in,
+                               active_state) -> None:
+    """traj_write_env_step under is_active: policy_id[:, t] = active_state ? policy_id : -1, then active_state <- active_in
+    (both u8/bool [B], contiguous; see sf_hip.h)"""
+    B = rewards.numel()
+    for name, x in (("active_in", active_in), ("active_state", active_state)):
+        if x is not None and x.numel() != B:
+            raise SfHipError(f"traj_write_env_step_active: {name} has {x.numel()} elements, expected {B}")
+    _check(load().sf_traj_write_env_step_active(ptr(rewards, "f32", "rewards"), ptr(terminated, "u8", "terminated"),
+                                                ptr(truncated, "u8", "truncated"), B, int(T), int(t), f(reward_scale),
+                                                f(reward_clip), int(policy_id), ptr(traj_rewards, "f32"),
+                                                ptr(traj_dones, "u8"), ptr(traj_time_outs, "u8"),
+                                                ptr(traj_policy_id, "i32"), ptr(ep_return, "f32"), ptr(ep_len, "i32"),
+                                                ptr(ep_stats, "f64"), ptr(active_in, "u8", "active_in"),
+                                                ptr(active_state, "u8", "active_state"), stream()),
+           "sf_traj_write_env_step_active")
 
 
 def synth_vec_step(state, actions, obs_out, env0, seed, step, reset, rewards, terminated) -> None:
