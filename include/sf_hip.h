@@ -390,6 +390,34 @@ int sf_copy_rows(void *dst, int64_t dst_pitch, const void *src, int64_t src_pitc
 int sf_framestack_step(void *next, int64_t next_pitch, const void *prev, int64_t prev_pitch, const void *frame,
                        int64_t frame_pitch, int64_t frame_bytes, int k, const uint8_t *terminated,
                        const uint8_t *truncated, int rows, void *stream);
+/* ---- channel-last frames (csrc/sf_ingest.hip, --hwc_observations) ---------------------------------------------
+ * Most pixel envs deliver [H][W][C] frames (the reference transposes them on the host, in the env's wrapper stack:
+ * PixelFormatChwWrapper); the encoders read [C][H][W].  elem_bytes: 1 (u8) or 4 (f32).
+ * sf_hwc_to_chw: row b of `src` is one frame [H][W][C], rows src_pitch bytes apart; row b of `dst` is C planes of H W
+ * elements, rows dst_pitch bytes apart (a slab column obs[:, t], or the last C planes of a stacked column):
+ *   dst[b][c][p] = src[b][p][c]  for p < H W, bit for bit.
+ * One launch.  Alignment classes: when dst, src and both pitches are multiples of 4 — and, for u8, H W is too — every
+ * global access is a dword that is contiguous across the lanes of a wave (u8: a lane owns 4 pixels, loads its C
+ * interleaved dwords and de-interleaves them in registers with byte permutes for C <= 4; wider C gathers with byte loads
+ * and still stores dwords; f32: a lane owns a pixel).  Anything else takes a byte-wise path.  Any C >= 1; C == 1 is a
+ * row copy.  dst and src must not share bytes (not checked).
+ * Refused before any launch (SF_ERR_ARG): null dst / src, H, W or C < 1, elem_bytes not 1 or 4, a pitch below
+ * H W C elem_bytes, rows < 0.  rows == 0: SF_OK, nothing is launched. */
+int sf_hwc_to_chw(void *dst, int64_t dst_pitch, const void *src, int64_t src_pitch, int H, int W, int C, int elem_bytes,
+                  int rows, void *stream);
+/* sf_framestack_step with a mandatory separate `frame` buffer whose rows are [H][W][C] (frame_bytes = H W C elem_bytes):
+ * the same launch count, the transpose rides in it.  With done as above:
+ *   not done:                          next[b][j] = prev[b][j + 1] for j < k - 1 (ONE shifted contiguous copy, 16-byte
+ *                                      accesses where next, prev, their pitches and frame_bytes allow), next[b][k - 1] =
+ *                                      chw(frame[b])
+ *   done, or BOTH flag pointers NULL:  next[b][j] = chw(frame[b]) for every j; each source element is loaded once
+ * Alignment classes of the transpose as for sf_hwc_to_chw, over next, prev (k > 1), frame and the three pitches.
+ * Refused before any launch (SF_ERR_ARG): null next / prev / frame, k outside 1 .. 16, H, W or C < 1, elem_bytes not 1
+ * or 4, a pitch below k * frame_bytes, frame_pitch < frame_bytes, rows < 0, rows of next and prev that share bytes.
+ * rows == 0: SF_OK, nothing is launched. */
+int sf_framestack_step_hwc(void *next, int64_t next_pitch, const void *prev, int64_t prev_pitch, const void *frame,
+                           int64_t frame_pitch, int H, int W, int C, int elem_bytes, int k, const uint8_t *terminated,
+                           const uint8_t *truncated, int rows, void *stream);
 
 /* ---- synthetic vector env (SURVEY.md §8d "C2 synthetic inputs") ------------------------------------------------
  * Device-resident stand-in for a GPU env (the reference's pattern: sf_examples/brax/train_brax.py:160-204).

@@ -114,6 +114,20 @@ class BatchedVectorEnvRunner:
                         if self.fs_k > 1 and traj["obs"][k].dim() == 5}
         if self.fs_k > 1 and hasattr(env, "step_into"):
             raise NotImplementedError(f"device_framestack={self.fs_k} with a zero-copy (step_into) env")
+        # --hwc_observations: the env's image keys are [H, W, C].  hwc_keys: key -> ONE device staging
+        # buffer [B, H, W, C] the frame is sent to instead of the slab slot; sf_hwc_to_chw (no frame stack) or
+        # sf_framestack_step_hwc (in place of sf_framestack_step) transposes it into the column.  _hwc_src: where the
+        # newest frame of a key is — the staging buffer, or a device env's own tensor read in place.
+        self.hwc_keys: Dict[str, torch.Tensor] = {}
+        if getattr(cfg, "hwc_observations", False):
+            if hasattr(env, "step_into"):
+                raise NotImplementedError("hwc_observations with a zero-copy (step_into) env")
+            for k in self.obs_keys:
+                x = traj["obs"][k]
+                if x.dim() == 5:
+                    self.hwc_keys[k] = torch.empty((self.B, x.shape[3], x.shape[4], x.shape[2] // self.fs_k), dtype=x.dtype,
+                                                   device=dev)
+        self._hwc_src: Dict[str, torch.Tensor] = {}
         # --track_inactive_agents: one persistent byte per agent row, 1 = the env's last info did not say
         # is_active=False.  Step t records policy_id -1 and holds the recurrent state where the byte is 0, then the byte
         # takes what the env reported with step t.  The bytes belong to the runner: they outlive a rollout, set_slab and
@@ -204,22 +218,46 @@ class BatchedVectorEnvRunner:
         c1 = self.fs_keys.get(key)
         return x[:, t] if c1 is None else x[:, t, (self.fs_k - 1) * c1:]
 
+    def _store_key(self, name: str, key: str, src, t: int) -> None:
+        """the env's observation of `key` -> slab column t.  A channel-last key (--hwc_observations) goes to its staging
+        buffer by the same route — pinned double buffer or one DMA from the workers' registered pages; a device env's
+        tensor with contiguous rows is read where it is — and, without a frame stack, sf_hwc_to_chw follows on the same
+        stream; with one, _framestack transposes it inside the stack's launch"""
+        stage = self.hwc_keys.get(key)
+        if stage is None:
+            self._to_device(name, src, self._obs_slot(key, t))
+            return
+        if isinstance(src, torch.Tensor) and src.is_cuda and src.shape == stage.shape and src.dtype == stage.dtype and \
+                src[0].is_contiguous():
+            frame = src
+        else:
+            self._to_device(name, src, stage)
+            frame = stage
+        self._hwc_src[key] = frame
+        if key not in self.fs_keys:
+            lib.hwc_to_chw(self.traj["obs"][key][:, t], frame)
+
     def _store_obs(self, o, t: int) -> None:
         if self.multi_key:
             for k in self.obs_keys:
-                self._to_device("obs." + k, o[k], self._obs_slot(k, t))
+                self._store_key("obs." + k, k, o[k], t)
         else:
             key = "obs" if "obs" in self.traj["obs"] else self.obs_keys[0]
-            self._to_device("obs", o["obs"] if isinstance(o, dict) else o, self._obs_slot(key, t))
+            self._store_key("obs", key, o["obs"] if isinstance(o, dict) else o, t)
         if self.masked:
             self._to_device("mask", o["action_mask"], self.traj["obs"]["action_mask"][:, t])
 
     def _framestack(self, t: int, term, trunc) -> None:
-        """complete the stacked keys of slab column t around the frame _store_obs put into their last slot: one launch per
-        key (term / trunc: the device flags of the step that produced the frame; None, None: a reset)"""
+        """complete the stacked keys of slab column t around the frame _store_obs put into their last slot — or, a
+        channel-last key, left in its staging buffer: one launch per key either way (term / trunc: the device flags of the
+        step that produced the frame; None, None: a reset)"""
         for k in self.fs_keys:
             x = self.traj["obs"][k]
-            lib.framestack_step(x[:, t], x[:, t - 1 if t > 0 else 1], self.fs_k, None, term, trunc)
+            prev = x[:, t - 1 if t > 0 else 1]
+            if k in self.hwc_keys:
+                lib.framestack_step_hwc(x[:, t], prev, self.fs_k, self._hwc_src[k], term, trunc)
+            else:
+                lib.framestack_step(x[:, t], prev, self.fs_k, None, term, trunc)
 
     def policy_version(self) -> float:
         return float(self.policy_versions[self.policy_id].item()) if self.policy_versions is not None else 0.0

@@ -66,6 +66,23 @@ def with_device_framestack(env_info: EnvInfo, env, cfg) -> EnvInfo:
     return dataclasses.replace(env_info, obs_space=stacked)
 
 
+def with_hwc_observations(env_info: EnvInfo, env, cfg) -> EnvInfo:
+    """--hwc_observations: the EnvInfo the slab, the model and the learner are built from — a copy whose image keys are
+    Box(C, H, W) while the env delivers [H, W, C] (envs/spaces.py chw_obs_space).  Applied BEFORE with_device_framestack:
+    the stack then runs along the channel axis of the CHW space.  The env's own EnvInfo (the cached / probed one) keeps
+    describing the env.  Flag off: `env_info` itself.  Refuses what the device transpose cannot serve."""
+    import dataclasses
+
+    from sample_factory_amd.envs.spaces import chw_obs_space
+    if not getattr(cfg, "hwc_observations", False):
+        return env_info
+    chw = chw_obs_space(env_info.obs_space)  # ValueError: nothing to transpose
+    if hasattr(env, "step_into"):
+        raise NotImplementedError("hwc_observations with a zero-copy env (step_into writes whole observations into the "
+                                  "slab): write CHW there, or let the env return its HWC frames from step()")
+    return dataclasses.replace(env_info, obs_space=chw)
+
+
 def env_info_cache_filename(cfg) -> str:
     """env_info.py:113-114: one cache entry per env name under the per-user temporary directory"""
     import os

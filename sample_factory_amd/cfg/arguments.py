@@ -58,6 +58,8 @@ FLAGS = [
     ("actor_critic_share_weights", _bool, True), ("adaptive_stddev", _bool, True),
     ("continuous_tanh_scale", float, 0.0), ("initial_stddev", float, 1.0),
     ("use_env_info_cache", _bool, False), ("env_gpu_actions", _bool, False), ("env_gpu_observations", _bool, True),
+    # pixel_format stays the reference's ENV-FACTORY flag (its factories wrap an HWC env in PixelFormatChwWrapper when it
+    # says CHW); the engine never reads it.  Frames that arrive channel-last are declared with --hwc_observations below.
     ("env_frameskip", int, 1), ("env_framestack", int, 1), ("pixel_format", str, "CHW"),
     ("use_record_episode_statistics", _bool, False), ("with_wandb", _bool, False), ("with_pbt", _bool, False),
     ("help", _bool, False),
@@ -89,6 +91,10 @@ ENGINE_FLAGS = [
     ("track_inactive_agents", _bool, False),  # honour info["is_active"]: the step AFTER an agent reported False is recorded
     #                                          with policy_id = -1 (the learner's validity mask drops it) and leaves the
     #                                          agent's recurrent state as it was (off: infos are ignored)
+    ("hwc_observations", _bool, False),      # the env's image keys are [H, W, C]: slab, model and learner see Box(C, H, W) and
+    #                                          every frame is transposed on the device (sf_hwc_to_chw, or inside the frame
+    #                                          stack's launch: sf_framestack_step_hwc).  Explicit, never
+    #                                          guessed from the shape; off: 3-D keys are read as CHW
 ]
 
 

@@ -170,6 +170,29 @@ def stacked_obs_space(obs_space, k: int):
     return Dict(out)
 
 
+def chw_obs_space(obs_space):
+    """the observation space the slab, the model and the learner see under --hwc_observations: a Dict in which every 3-D
+    key (the keys framestack_keys picks; the env delivers them as [H, W, C]) has become Box(C, H, W) — array bounds
+    transposed, scalar bounds scalar, dtype kept — and every other key (vectors, the action mask) is the env's own space
+    object"""
+    keys = framestack_keys(obs_space)
+    if not keys:
+        raise ValueError(f"hwc_observations: the observation space {obs_space!r} has no key with three dimensions (HWC) to "
+                         "transpose")
+    out = {}
+    for name, sp in (obs_space.spaces.items() if hasattr(obs_space, "spaces") else [("obs", obs_space)]):
+        if name not in keys:
+            out[name] = sp
+            continue
+
+        def chw(b):
+            b = np.asarray(b)
+            return np.ascontiguousarray(b.transpose(2, 0, 1)) if b.ndim == 3 else (b.item() if b.ndim == 0 else b)
+        h, w, c = sp.shape
+        out[name] = Box(chw(sp.low), chw(sp.high), (int(c), int(h), int(w)), sp.dtype)
+    return Dict(out)
+
+
 def calc_num_actions(action_space) -> int:
     """action_distributions.py:14-26"""
     if is_discrete(action_space):

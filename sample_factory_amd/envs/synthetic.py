@@ -116,12 +116,16 @@ class HostFrameVecEnv:
     pitched H2D DMA into the slab, and a D2H of the int32 actions.  Frames come from a small pre-generated ring (the
     simulator's own cost is not what is being measured); rewards follow the synthetic env's rule."""
 
-    def __init__(self, num_agents=1024, obs_shape=(4, 84, 84), num_actions=6, seed=0, ring=4, sim_ms=0.0):
+    def __init__(self, num_agents=1024, obs_shape=(4, 84, 84), num_actions=6, seed=0, ring=4, sim_ms=0.0, hwc=False):
         self.num_agents, self.obs_shape, self.num_actions = int(num_agents), tuple(obs_shape), int(num_actions)
-        self.observation_space = spaces.Dict({"obs": spaces.Box(0, 255, self.obs_shape, np.uint8)})
         self.action_space = spaces.Discrete(num_actions)
         rng = np.random.default_rng(seed)
         self.ring = rng.integers(0, 256, size=(ring, self.num_agents) + self.obs_shape, dtype=np.uint8)
+        self.hwc = bool(hwc)
+        if self.hwc:  # the same ring served channel-last, as most pixel envs do (--hwc_observations): frame for frame the
+            # same pixels as [ring, N, H, W, C], transposed once, here; obs_shape stays the (C, H, W) it was asked for
+            self.ring = np.ascontiguousarray(self.ring.transpose(0, 1, 3, 4, 2))
+        self.observation_space = spaces.Dict({"obs": spaces.Box(0, 255, self.ring.shape[2:], np.uint8)})
         self.step_count = 0
         self.sim_ms = float(sim_ms)  # optional simulated emulator time per step (host sleep)
         self._ids = np.arange(self.num_agents)
@@ -150,8 +154,10 @@ def make_host_frame_env(full_env_name, cfg=None, env_config=None, render_mode=No
     seed = ((getattr(cfg, "seed", None) or 0) if cfg is not None else 0) + int(getattr(env_config, "env_id", 0) or 0)
     # cfg.host_env_obs_shape: e.g. (1, 84, 84) — single frames, stacked on the device with --device_framestack
     shape = tuple(getattr(cfg, "host_env_obs_shape", None) or (4, 84, 84)) if cfg is not None else (4, 84, 84)
+    # cfg.host_env_hwc: the frames leave the env as [H, W, C] (obs_shape stays C, H, W): the --hwc_observations test env
     return HostFrameVecEnv(num_agents=n, obs_shape=shape, seed=seed,
-                           sim_ms=getattr(cfg, "host_env_sim_ms", 0.0) if cfg is not None else 0.0)
+                           sim_ms=getattr(cfg, "host_env_sim_ms", 0.0) if cfg is not None else 0.0,
+                           hwc=bool(getattr(cfg, "host_env_hwc", False)) if cfg is not None else False)
 
 
 class SyntheticTupleEnv(SyntheticVecEnv):

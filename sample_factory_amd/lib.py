@@ -53,7 +53,7 @@ SYMBOLS = [
     "sf_obsnorm_moments", "sf_obsnorm_update", "sf_obsnorm_apply", "sf_sample_write_step",
     "sf_sample_write_step_tuple", "sf_sample_write_step_masked", "sf_sample_write_step_tuple_masked",
     "sf_traj_write_env_step", "sf_traj_write_env_step_active", "sf_rnn_store_state_held", "sf_synth_obs",
-    "sf_synth_step", "sf_synth_vec_step", "sf_h2d_rows", "sf_copy_rows", "sf_framestack_step", "sf_conv_fwd", "sf_conv_fwd_workspace", "sf_conv_wgrad_workspace", "sf_conv_wgrad",
+    "sf_synth_step", "sf_synth_vec_step", "sf_h2d_rows", "sf_copy_rows", "sf_framestack_step", "sf_hwc_to_chw", "sf_framestack_step_hwc", "sf_conv_fwd", "sf_conv_fwd_workspace", "sf_conv_wgrad_workspace", "sf_conv_wgrad",
     "sf_conv_dgrad", "sf_conv_norm_supported", "sf_conv_fwd_norm", "sf_conv_wgrad_norm", "sf_conv_relu_mask_supported", "sf_conv_fwd_relu_mask", "sf_conv_wgrad_relu_mask", "sf_conv_kernel_name", "sf_conv_fwd_t_supported", "sf_conv_fwd_t_workspace", "sf_conv_fwd_t", "sf_transpose",
     "sf_conv_fwd_os_supported", "sf_conv_fwd_relu_mask_os", "sf_conv_fwd_t_os",
     "sf_conv_fwd_os2_supported", "sf_conv_fwd_relu_mask_os2", "sf_conv_fwd_t_os2",
@@ -958,6 +958,66 @@ def framestack_step(next_: torch.Tensor, prev: torch.Tensor, k: int, frame: Opti
         _check(load().sf_framestack_step(_vp(next_), i64(pitch(next_, row_bytes)), _vp(prev), i64(pitch(prev, row_bytes)),
                                          fptr, i64(fpitch), i64(fb), int(k), ptr(terminated, "u8", "terminated"),
                                          ptr(truncated, "u8", "truncated"), rows, stream()), "sf_framestack_step")
+
+
+def _hwc_views(what: str, chw: torch.Tensor, frame: torch.Tensor, k: int = 1):
+    """argument checks shared by hwc_to_chw and framestack_step_hwc: chw is a device view [rows, k * C, H, W] and frame one
+    [rows, H, W, C] of the same dtype (u8 or f32), rows contiguous blocks on both sides -> (rows, H, W, C, element size,
+    pitch(tensor, row bytes))"""
+    if not (chw.is_cuda and frame.is_cuda) or chw.dtype != frame.dtype or chw.dtype not in (torch.uint8, torch.float32):
+        raise SfHipError(f"{what}: device views of one dtype (uint8 or float32) required, got {chw.dtype} on {chw.device} "
+                         f"and {frame.dtype} on {frame.device}")
+    if chw.dim() != 4 or frame.dim() != 4 or int(k) < 1 or \
+            tuple(chw.shape) != (frame.shape[0], int(k) * frame.shape[3], frame.shape[1], frame.shape[2]):
+        raise SfHipError(f"{what}: frame must be [rows, H, W, C] and the channel-first side [rows, {k} * C, H, W], got "
+                         f"{tuple(frame.shape)} and {tuple(chw.shape)}")
+    rows, es = int(chw.shape[0]), chw.element_size()
+    if rows and not (chw[0].is_contiguous() and frame[0].is_contiguous()):
+        raise SfHipError(f"{what}: rows must be contiguous blocks (strides {chw.stride()} / {frame.stride()})")
+
+    def pitch(t, rb):  # (a one-row view may carry any stride)
+        return int(t.stride(0)) * es if rows > 1 else max(int(t.stride(0)) * es, rb)
+    return rows, int(frame.shape[1]), int(frame.shape[2]), int(frame.shape[3]), es, pitch
+
+
+def hwc_to_chw(dst: torch.Tensor, src: torch.Tensor) -> None:
+    """sf_hwc_to_chw: dst [rows, C, H, W] <- src [rows, H, W, C], two device views of one dtype (u8 or f32) whose rows are
+    contiguous blocks at any pitch (dst: a slab column obs[:, t]): ONE launch, bit for bit"""
+    rows, H, W, Cn, es, pitch = _hwc_views("hwc_to_chw", dst, src)
+    if rows == 0:
+        return
+    rb = H * W * Cn * es
+    key = ("hwc_to_chw", rows, H, W, Cn, es) if _keys_wanted() else None  # (tools/hwc_frames_bench.py times it)
+    with _timed(key):
+        _check(load().sf_hwc_to_chw(_vp(dst), i64(pitch(dst, rb)), _vp(src), i64(pitch(src, rb)), H, W, Cn, es, rows,
+                                    stream()), "sf_hwc_to_chw")
+
+
+def framestack_step_hwc(next_: torch.Tensor, prev: torch.Tensor, k: int, frame: torch.Tensor,
+                        terminated: Optional[torch.Tensor] = None, truncated: Optional[torch.Tensor] = None) -> None:
+    """sf_framestack_step_hwc: framestack_step whose new frame arrives channel-last.  next_ / prev: device views
+    [rows, k * C, H, W] (obs[:, t + 1] / obs[:, t]); frame: [rows, H, W, C], same dtype, contiguous rows; terminated /
+    truncated: contiguous bool / u8 [rows], both None = a reset"""
+    if frame is None:
+        raise SfHipError("framestack_step_hwc: the channel-last frame buffer is mandatory")
+    if not prev.is_cuda or next_.shape != prev.shape or next_.dtype != prev.dtype:
+        raise SfHipError(f"framestack_step_hwc: next / prev must be device views of equal shape and dtype, got "
+                         f"{tuple(next_.shape)} {next_.dtype} / {tuple(prev.shape)} {prev.dtype} on {prev.device}")
+    rows, H, W, Cn, es, pitch = _hwc_views("framestack_step_hwc", next_, frame, k)
+    if rows == 0:
+        return
+    if not prev[0].is_contiguous():
+        raise SfHipError(f"framestack_step_hwc: rows must be contiguous blocks (strides {prev.stride()})")
+    for name, flags in (("terminated", terminated), ("truncated", truncated)):
+        if flags is not None and flags.numel() != rows:
+            raise SfHipError(f"framestack_step_hwc: {name} must hold one flag per row ({rows}), got {flags.numel()}")
+    fb = H * W * Cn * es
+    key = ("framestack_step_hwc", rows, int(k), H, W, Cn, es) if _keys_wanted() else None
+    with _timed(key):
+        _check(load().sf_framestack_step_hwc(_vp(next_), i64(pitch(next_, int(k) * fb)), _vp(prev),
+                                             i64(pitch(prev, int(k) * fb)), _vp(frame), i64(pitch(frame, fb)), H, W, Cn, es,
+                                             int(k), ptr(terminated, "u8", "terminated"), ptr(truncated, "u8", "truncated"),
+                                             rows, stream()), "sf_framestack_step_hwc")
 
 
 def synth_obs(obs_slot_ptr: int, env_stride, B, env0, obs_bytes, seed, step) -> None:
