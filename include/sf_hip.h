@@ -418,6 +418,39 @@ int sf_hwc_to_chw(void *dst, int64_t dst_pitch, const void *src, int64_t src_pit
 int sf_framestack_step_hwc(void *next, int64_t next_pitch, const void *prev, int64_t prev_pitch, const void *frame,
                            int64_t frame_pitch, int H, int W, int C, int elem_bytes, int k, const uint8_t *terminated,
                            const uint8_t *truncated, int rows, void *stream);
+/* ---- resize and grey-scale of u8 frames (csrc/sf_ingest.hip, --device_resize / --device_grayscale) ---------------
+ * The arithmetic a raw-pixel env's image wrappers do on the host (the reference's ResizeWrapper: cv2.resize, then
+ * COLOR_RGB2GRAY; the area resize + grey-scale of the usual Atari preprocessing), as ONE launch that also reads
+ * channel-last frames.  u8 in, u8 out, integer arithmetic only; sample_factory_amd/envs/frame_ops.py is the same
+ * arithmetic in NumPy, bit for bit.
+ * Row b of `src` is one frame, [H][W][C] when src_hwc, else [C][H][W], rows src_pitch bytes apart; row b of `dst` is C'
+ * planes of OH OW bytes (C' = gray ? 1 : C), rows dst_pitch bytes apart (a slab column obs[:, t] or the last slot of a
+ * stacked column).  Per channel:
+ *   interp 0, nearest:  out[y][x] = in[y H / OH][x W / OW]  (floor divisions); any OH, OW >= 1, up-scaling included.
+ *   interp 1, area:     the exact box average over fractional pixel coverage.  Along an axis, in units of 1 / (W OW) of
+ *                       it, destination pixel x covers [x W, (x + 1) W) and source pixel s covers [s OW, (s + 1) OW);
+ *                       wx(x, s) is the length of their overlap (the weights of one x sum to W), wy likewise.  With
+ *                       S = sum wy wx in and D = H W:  out = (2 S + D) / (2 D), floored: ties round half up.  Needs
+ *                       OH <= H and OW <= W.  S is a 32-bit sum: H W > 2^23 is REFUSED (255 H W must stay below 2^31).
+ *   gray (C == 3, channel order R, G, B):  (9798 R + 19235 G + 3735 B + 16384) >> 15 of the resized AND ROUNDED channels
+ *                       (resize first, then grey, the reference wrapper's order; ITU-R 601 luma in 15-bit fixed point).
+ *   Without gray every channel is resized on its own.  OH == H and OW == W is legal (grey-scale or de-interleave alone).
+ * This is the exact value of what OpenCV's INTER_AREA approximates in float: a result may differ from OpenCV's by 1 in
+ * the last bit on ties.
+ * Area launches stage the source rows a strip of output rows covers in LDS (at most 32 KB and 32 rows per work-group,
+ * lines padded to an odd dword stride), each source byte read from global memory once, contiguous across a wave: 16 bytes
+ * per lane when src, src_pitch and the line length (W C, planar: W) are multiples of 16, dwords when src and src_pitch are
+ * multiples of 4, bytewise otherwise; a lane then computes 4 consecutive output pixels from LDS.  A strip of one output row
+ * that covers more rows than a band walks them band after band.  Nearest launches gather from global memory (only the bytes kept are read).  Stores
+ * are dwords (4 output pixels per lane) when dst, dst_pitch and OH OW are multiples of 4, bytes otherwise: any alignment
+ * gives the same bytes.  Frames whose rows exceed the LDS band (W C, or 3 (W + 8) for planar grey, above 32 KB) or whose
+ * index products OH H, OW W, H W C leave 31 bits take a bytewise 64-bit path.  dst and src must not share bytes (not
+ * checked).
+ * Refused before any launch (SF_ERR_ARG): null dst / src; H, W, C, OH or OW < 1; interp not 0 or 1; area with OH > H or
+ * OW > W, or with H W > 2^23; gray with C != 3; src_pitch < H W C; dst_pitch < C' OH OW; rows < 0.
+ * rows == 0: SF_OK, nothing is launched. */
+int sf_frame_resize(void *dst, int64_t dst_pitch, const void *src, int64_t src_pitch, int H, int W, int C, int src_hwc,
+                    int OH, int OW, int interp, int gray, int rows, void *stream);
 
 /* ---- synthetic vector env (SURVEY.md §8d "C2 synthetic inputs") ------------------------------------------------
  * Device-resident stand-in for a GPU env (the reference's pattern: sf_examples/brax/train_brax.py:160-204).

@@ -21,6 +21,7 @@ import torch
 
 from sample_factory_amd import lib
 from sample_factory_amd.algo.sampling.parallel_env import infos_is_active
+from sample_factory_amd.algo.utils.env_info import device_resize_of
 from sample_factory_amd.algo.utils.tensor_dict import TensorDict
 from sample_factory_amd.envs.spaces import action_head_sizes, heads_mixed, is_box, split_tuple_actions
 
@@ -119,12 +120,28 @@ class BatchedVectorEnvRunner:
         # sf_framestack_step_hwc (in place of sf_framestack_step) transposes it into the column.  _hwc_src: where the
         # newest frame of a key is — the staging buffer, or a device env's own tensor read in place.
         self.hwc_keys: Dict[str, torch.Tensor] = {}
+        # --device_resize / --device_grayscale: the env delivers native u8 frames, the slab holds them
+        # preprocessed.  rs_keys: key -> ONE device staging buffer [B, native frame] in the env's own layout ([H, W, C]
+        # under --hwc_observations, else [C, H, W]) the frame is sent to by the existing routes; sf_frame_resize follows on
+        # the same stream into _obs_slot(key, t) — the column or the last slot of a stacked one — resizing, grey-scaling
+        # and de-interleaving in one launch: such a key never goes through the transpose kernels.
+        self.rs_keys: Dict[str, torch.Tensor] = {}
+        rs_size, self.rs_interp, self.rs_gray = device_resize_of(cfg)
+        self.rs_hwc = bool(getattr(cfg, "hwc_observations", False))
+        if rs_size is not None or self.rs_gray:
+            if hasattr(env, "step_into"):
+                raise NotImplementedError("device_resize / device_grayscale with a zero-copy (step_into) env")
+            space = env.observation_space
+            for k in self.obs_keys:
+                if traj["obs"][k].dim() == 5:
+                    native = tuple(int(d) for d in (space[k] if hasattr(space, "spaces") else space).shape)
+                    self.rs_keys[k] = torch.empty((self.B,) + native, dtype=torch.uint8, device=dev)
         if getattr(cfg, "hwc_observations", False):
             if hasattr(env, "step_into"):
                 raise NotImplementedError("hwc_observations with a zero-copy (step_into) env")
             for k in self.obs_keys:
                 x = traj["obs"][k]
-                if x.dim() == 5:
+                if x.dim() == 5 and k not in self.rs_keys:
                     self.hwc_keys[k] = torch.empty((self.B, x.shape[3], x.shape[4], x.shape[2] // self.fs_k), dtype=x.dtype,
                                                    device=dev)
         self._hwc_src: Dict[str, torch.Tensor] = {}
@@ -222,7 +239,19 @@ class BatchedVectorEnvRunner:
         """the env's observation of `key` -> slab column t.  A channel-last key (--hwc_observations) goes to its staging
         buffer by the same route — pinned double buffer or one DMA from the workers' registered pages; a device env's
         tensor with contiguous rows is read where it is — and, without a frame stack, sf_hwc_to_chw follows on the same
-        stream; with one, _framestack transposes it inside the stack's launch"""
+        stream; with one, _framestack transposes it inside the stack's launch.  A preprocessed key (--device_resize /
+        --device_grayscale) is staged the same way in its native size and layout and sf_frame_resize writes the slot: the
+        column, or the last slot of a stacked one, which _framestack then completes with the plain sf_framestack_step"""
+        stage = self.rs_keys.get(key)
+        if stage is not None:  # native frame -> staging buffer (or read in place) -> resized / grey into the slab slot
+            if isinstance(src, torch.Tensor) and src.is_cuda and src.shape == stage.shape and src.dtype == stage.dtype and \
+                    src[0].is_contiguous():
+                frame = src
+            else:
+                self._to_device(name, src, stage)
+                frame = stage
+            lib.frame_resize(self._obs_slot(key, t), frame, self.rs_hwc, self.rs_interp, self.rs_gray)
+            return
         stage = self.hwc_keys.get(key)
         if stage is None:
             self._to_device(name, src, self._obs_slot(key, t))

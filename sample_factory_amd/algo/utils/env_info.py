@@ -83,6 +83,54 @@ def with_hwc_observations(env_info: EnvInfo, env, cfg) -> EnvInfo:
     return dataclasses.replace(env_info, obs_space=chw)
 
 
+def device_resize_of(cfg):
+    """(OH, OW) | None, interpolation, grayscale as --device_resize / --device_resize_interpolation / --device_grayscale
+    say; ValueError for anything but 0 or 2 sizes, sizes below 1, or an unknown filter"""
+    size = list(getattr(cfg, "device_resize", None) or [])
+    interp, gray = str(getattr(cfg, "device_resize_interpolation", "area")), bool(getattr(cfg, "device_grayscale", False))
+    if len(size) not in (0, 2):
+        raise ValueError(f"device_resize takes two sizes, height first (--device_resize H W), got {size}")
+    if size and (int(size[0]) < 1 or int(size[1]) < 1):
+        raise ValueError(f"device_resize {size}: each size at least 1")
+    if interp not in ("area", "nearest"):
+        raise ValueError(f"device_resize_interpolation={interp!r}: 'area' or 'nearest'")
+    return ((int(size[0]), int(size[1])) if size else None), interp, gray
+
+
+def with_device_resize(env_info: EnvInfo, env, cfg) -> EnvInfo:
+    """--device_resize H W / --device_grayscale: the EnvInfo the slab, the model and the learner are built from — a copy
+    whose u8 image keys are Box(C', OH, OW) while the env delivers its native frames (envs/spaces.py resized_obs_space).
+    Applied AFTER with_hwc_observations (it acts on the CHW space) and BEFORE with_device_framestack (the preprocessed
+    frames are what gets stacked).  The env's own EnvInfo keeps describing the env.  Flags off: `env_info` itself.  Refuses
+    what the device kernel cannot serve."""
+    import dataclasses
+
+    from sample_factory_amd.envs.spaces import framestack_keys, resized_obs_space
+    size, interp, gray = device_resize_of(cfg)
+    if size is None and not gray:
+        return env_info
+    space = env_info.obs_space
+    if size is None:  # grey-scale alone: every image key keeps its own geometry
+        keys = framestack_keys(space)
+        shapes = {tuple(int(d) for d in (space[k] if hasattr(space, "spaces") else space).shape[1:]) for k in keys}
+        if len(shapes) > 1:
+            raise ValueError(f"device_grayscale without device_resize: the image keys {keys} differ in size {sorted(shapes)}; "
+                             "give --device_resize H W")
+        size = next(iter(shapes)) if shapes else (1, 1)
+    resized = resized_obs_space(space, size[0], size[1], gray)  # ValueError: no image key, not u8, grey of C != 3
+    if interp == "area":
+        for k in framestack_keys(space):
+            h, w = (space[k] if hasattr(space, "spaces") else space).shape[1:]
+            if size[0] > h or size[1] > w:
+                raise ValueError(f"device_resize {size[0]} {size[1]} with the area filter enlarges observation key {k!r} "
+                                 f"({h} x {w}): the area filter only shrinks, use --device_resize_interpolation=nearest")
+    if hasattr(env, "step_into"):
+        raise NotImplementedError("device_resize / device_grayscale with a zero-copy env (step_into writes whole "
+                                  "observations into the slab): preprocess inside the env, or let it return its native "
+                                  "frames from step()")
+    return dataclasses.replace(env_info, obs_space=resized)
+
+
 def env_info_cache_filename(cfg) -> str:
     """env_info.py:113-114: one cache entry per env name under the per-user temporary directory"""
     import os

@@ -17,7 +17,7 @@ SOURCES = [
     ("sf_rnn.hip", ["-ffp-contract=off"]),  # the fused cell arithmetic must equal k_rnn_cell_* of sf_rl.hip
     ("sf_dp.hip", []),                      # host code: RCCL gradient exchange (librccl resolved with dlopen at first use)
     ("sf_resnet.hip", ["-ffp-contract=off"]),  # resnet_impala: explicit fmaf in the dot products, torch's order elsewhere
-    ("sf_ingest.hip", []),                  # byte movers of the observation ingest (the device frame stack)
+    ("sf_ingest.hip", []),                  # observation ingest: the device frame stack, the HWC transpose, resize / grey-scale
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
           f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}"]

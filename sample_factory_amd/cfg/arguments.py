@@ -95,6 +95,14 @@ ENGINE_FLAGS = [
     #                                          every frame is transposed on the device (sf_hwc_to_chw, or inside the frame
     #                                          stack's launch: sf_framestack_step_hwc).  Explicit, never
     #                                          guessed from the shape; off: 3-D keys are read as CHW
+    ("device_resize", int, [], "*"),         # --device_resize H W (height first, like every shape here; the reference's
+    #                                          ResizeWrapper takes (w, h)): the env delivers native u8 frames, every image
+    #                                          key is resized to H x W on the device (sf_frame_resize);
+    #                                          [] = off, any other count than 0 or 2 is refused at set-up
+    ("device_resize_interpolation", str, "area"),  # area | nearest.  The default is the exact box average, not the
+    #                                          wrapper's nearest: on the device the better filter costs nothing
+    ("device_grayscale", _bool, False),      # R, G, B -> one luma plane after the resize, in the same launch (C must be 3);
+    #                                          works alone, at the env's own size
 ]
 
 

@@ -33,6 +33,27 @@ static inline int sf_hip_status(hipError_t e, const char *what) {
     return SF_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- exact n/d for n<2^31
+// s = ceil(log2 d), mul = floor(2^(31+s) / d) + 1: mul d = 2^(31+s) + e with 0 < e <= d <= 2^s, so n mul / 2^(31+s) exceeds
+// n / d by n e / (d 2^(31+s)) < 1 / d for n < 2^31 — never enough to reach the next integer.  sf_selftest_host checks it.
+struct FastDiv {
+    uint32_t d, mul, shr;
+};
+static inline FastDiv make_fastdiv(uint32_t d) {
+    FastDiv f;
+    f.d = d;
+    if (d <= 1) { f.mul = 0; f.shr = 0; return f; }
+    uint32_t s = 0;
+    while ((1u << s) < d) ++s;  // s = ceil(log2 d) >= 1
+    f.mul = (uint32_t)((((uint64_t)1) << (31 + s)) / d + 1);
+    f.shr = s - 1;
+    return f;
+}
+__host__ __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv &f) {
+    const uint32_t q = (uint32_t)(((uint64_t)n * f.mul) >> 32) >> f.shr;
+    return f.d <= 1 ? n : q;  // select, not a branch: keeps the loaders straight-line
+}
+
 constexpr int SF_WAVE = 64;  // CDNA wavefront
 
 __device__ __forceinline__ double sf_wave_sum(double v) {

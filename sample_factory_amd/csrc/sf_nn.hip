@@ -33,25 +33,7 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// ---------------------------------------------------------------------------------------------- exact n/d for n<2^31
-struct FastDiv {
-    uint32_t d, mul, shr;
-};
-static inline FastDiv make_fastdiv(uint32_t d) {
-    FastDiv f;
-    f.d = d;
-    if (d <= 1) { f.mul = 0; f.shr = 0; return f; }
-    uint32_t s = 0;
-    while ((1u << s) < d) ++s;  // s = ceil(log2 d) >= 1
-    f.mul = (uint32_t)((((uint64_t)1) << (31 + s)) / d + 1);
-    f.shr = s - 1;
-    return f;
-}
-__host__ __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv &f) {
-    const uint32_t q = (uint32_t)(((uint64_t)n * f.mul) >> 32) >> f.shr;
-    return f.d <= 1 ? n : q;  // select, not a branch: keeps the loaders straight-line
-}
-
+// (FastDiv / make_fastdiv / fdiv — exact n / d for n < 2^31 — live in sf_common.h: sf_ingest.hip divides with them too)
 extern "C" int sf_selftest_host(void) {  // exercised by the CPU test-suite: the index math everything rests on
     const uint32_t ds[] = {1, 2, 3, 4, 6, 7, 9, 20, 32, 33, 49, 64, 81, 84, 128, 400, 512, 576, 3136, 7056, 28224, 65535, 1000003};
     for (uint32_t d : ds) {
@@ -60,6 +42,20 @@ extern "C" int sf_selftest_host(void) {  // exercised by the CPU test-suite: the
         for (uint32_t n : ns) if (fdiv(n, f) != n / d) return -1;
         for (uint32_t n = 0; n < 200000; n += 7) if (fdiv(n, f) != n / d) return -2;
         for (uint32_t n = 0x7FFFFFFFu; n > 0x7FFFFFFFu - 100000; n -= 13) if (fdiv(n, f) != n / d) return -3;
+    }
+    // sf_frame_resize (sf_ingest.hip) rounds its box average with them: (2 S + D) / (2 D) == (S + D / 2) / D for every
+    // frame area D = H W <= 2^23 and every weighted sum S <= 255 D
+    const uint32_t areas[] = {1, 2, 3, 35, 70, 96, 485, 5760, 19200, 33600, 76800, 921600, 8388607, 8388608};
+    for (uint32_t D : areas) {
+        const FastDiv f = make_fastdiv(D);
+        for (uint64_t v = 0; v <= 255; ++v)
+            for (int64_t off = -2; off <= 2; ++off) {  // sums around every tie v + 1/2 and around every whole v
+                for (int tie = 0; tie < 2; ++tie) {
+                    const int64_t S = (int64_t)((2 * v + tie) * D / 2) + off;
+                    if (S < 0 || S > 255 * (int64_t)D) continue;
+                    if (fdiv((uint32_t)S + D / 2, f) != (uint32_t)((2 * (uint64_t)S + D) / (2 * (uint64_t)D))) return -4;
+                }
+            }
     }
     return 0;
 }

@@ -193,6 +193,36 @@ def chw_obs_space(obs_space):
     return Dict(out)
 
 
+def resized_obs_space(obs_space, OH: int, OW: int, grayscale: bool):
+    """the observation space the slab, the model and the learner see under --device_resize OH OW / --device_grayscale: a
+    Dict in which every 3-D key of the CHW space (the keys framestack_keys picks) has become Box(C', OH, OW), C' = 1 under
+    grayscale (C must be 3), else C.  The key must be u8.  Scalar bounds are kept; array bounds collapse to their min and
+    max (a resized pixel lies between the smallest and the largest bound of the pixels it averages).  Every other key
+    (vectors, the action mask) is the env's own space object."""
+    OH, OW = int(OH), int(OW)
+    if OH < 1 or OW < 1:
+        raise ValueError(f"device_resize {OH} {OW}: each at least 1")
+    keys = framestack_keys(obs_space)
+    if not keys:
+        raise ValueError(f"device_resize / device_grayscale: the observation space {obs_space!r} has no key with three "
+                         "dimensions (an image) to preprocess")
+    out = {}
+    for name, sp in (obs_space.spaces.items() if hasattr(obs_space, "spaces") else [("obs", obs_space)]):
+        if name not in keys:
+            out[name] = sp
+            continue
+        if np.dtype(sp.dtype) != np.uint8:
+            raise ValueError(f"device_resize / device_grayscale: observation key {name!r} is {np.dtype(sp.dtype).name}, only "
+                             "uint8 frames are preprocessed on the device")
+        c = int(sp.shape[0])
+        if grayscale and c != 3:
+            raise ValueError(f"device_grayscale: observation key {name!r} has {c} channels, grey-scale needs 3 (R, G, B)")
+        low, high = np.asarray(sp.low), np.asarray(sp.high)
+        out[name] = Box(low.item() if low.ndim == 0 else low.min().item(), high.item() if high.ndim == 0 else high.max().item(),
+                        (1 if grayscale else c, OH, OW), sp.dtype)
+    return Dict(out)
+
+
 def calc_num_actions(action_space) -> int:
     """action_distributions.py:14-26"""
     if is_discrete(action_space):

@@ -53,7 +53,7 @@ SYMBOLS = [
     "sf_obsnorm_moments", "sf_obsnorm_update", "sf_obsnorm_apply", "sf_sample_write_step",
     "sf_sample_write_step_tuple", "sf_sample_write_step_masked", "sf_sample_write_step_tuple_masked",
     "sf_traj_write_env_step", "sf_traj_write_env_step_active", "sf_rnn_store_state_held", "sf_synth_obs",
-    "sf_synth_step", "sf_synth_vec_step", "sf_h2d_rows", "sf_copy_rows", "sf_framestack_step", "sf_hwc_to_chw", "sf_framestack_step_hwc", "sf_conv_fwd", "sf_conv_fwd_workspace", "sf_conv_wgrad_workspace", "sf_conv_wgrad",
+    "sf_synth_step", "sf_synth_vec_step", "sf_h2d_rows", "sf_copy_rows", "sf_framestack_step", "sf_hwc_to_chw", "sf_framestack_step_hwc", "sf_frame_resize", "sf_conv_fwd", "sf_conv_fwd_workspace", "sf_conv_wgrad_workspace", "sf_conv_wgrad",
     "sf_conv_dgrad", "sf_conv_norm_supported", "sf_conv_fwd_norm", "sf_conv_wgrad_norm", "sf_conv_relu_mask_supported", "sf_conv_fwd_relu_mask", "sf_conv_wgrad_relu_mask", "sf_conv_kernel_name", "sf_conv_fwd_t_supported", "sf_conv_fwd_t_workspace", "sf_conv_fwd_t", "sf_transpose",
     "sf_conv_fwd_os_supported", "sf_conv_fwd_relu_mask_os", "sf_conv_fwd_t_os",
     "sf_conv_fwd_os2_supported", "sf_conv_fwd_relu_mask_os2", "sf_conv_fwd_t_os2",
@@ -1018,6 +1018,45 @@ def framestack_step_hwc(next_: torch.Tensor, prev: torch.Tensor, k: int, frame: 
                                              i64(pitch(prev, int(k) * fb)), _vp(frame), i64(pitch(frame, fb)), H, W, Cn, es,
                                              int(k), ptr(terminated, "u8", "terminated"), ptr(truncated, "u8", "truncated"),
                                              rows, stream()), "sf_framestack_step_hwc")
+
+
+INTERPOLATIONS = {"nearest": 0, "area": 1}  # sf_frame_resize's interp argument
+
+
+def frame_resize(dst: torch.Tensor, src: torch.Tensor, src_hwc: bool, interpolation: str = "area",
+                 grayscale: bool = False) -> None:
+    """sf_frame_resize: dst [rows, C', OH, OW] <- src [rows, H, W, C] (src_hwc) or [rows, C, H, W], two device u8 views
+    whose rows are contiguous blocks at any pitch (dst: a slab column obs[:, t] or the last slot of a stacked one); C' = 1
+    with grayscale (C must be 3), else C.  ONE launch: resize ("area": exact box average, only shrinks; "nearest"), then
+    grey-scale, bit for bit the arithmetic of envs/frame_ops.py"""
+    if not (dst.is_cuda and src.is_cuda) or dst.dtype != torch.uint8 or src.dtype != torch.uint8:
+        raise SfHipError(f"frame_resize: device views of dtype uint8 required, got {dst.dtype} on {dst.device} and "
+                         f"{src.dtype} on {src.device}")
+    if interpolation not in INTERPOLATIONS:
+        raise SfHipError(f"frame_resize: interpolation must be one of {sorted(INTERPOLATIONS)}, got {interpolation!r}")
+    if dst.dim() != 4 or src.dim() != 4 or dst.shape[0] != src.shape[0]:
+        raise SfHipError(f"frame_resize: src must be [rows, H, W, C] or [rows, C, H, W] and dst [rows, C', OH, OW], got "
+                         f"{tuple(src.shape)} and {tuple(dst.shape)}")
+    rows = int(dst.shape[0])
+    H, W, Cn = (int(src.shape[1]), int(src.shape[2]), int(src.shape[3])) if src_hwc else \
+        (int(src.shape[2]), int(src.shape[3]), int(src.shape[1]))
+    OH, OW = int(dst.shape[2]), int(dst.shape[3])
+    if int(dst.shape[1]) != (1 if grayscale else Cn):
+        raise SfHipError(f"frame_resize: dst has {int(dst.shape[1])} planes for a source of {Cn} channels"
+                         f"{' under grayscale' if grayscale else ''}, got {tuple(src.shape)} and {tuple(dst.shape)}")
+    if rows == 0:
+        return
+    if not (dst[0].is_contiguous() and src[0].is_contiguous()):
+        raise SfHipError(f"frame_resize: rows must be contiguous blocks (strides {dst.stride()} / {src.stride()})")
+
+    def pitch(t, rb):  # (a one-row view may carry any stride)
+        return int(t.stride(0)) if rows > 1 else max(int(t.stride(0)), rb)
+    key = ("frame_resize", rows, H, W, Cn, int(bool(src_hwc)), OH, OW, interpolation, int(bool(grayscale))) \
+        if _keys_wanted() else None  # (tools/device_resize_bench.py times it)
+    with _timed(key):
+        _check(load().sf_frame_resize(_vp(dst), i64(pitch(dst, int(dst.shape[1]) * OH * OW)), _vp(src),
+                                      i64(pitch(src, H * W * Cn)), H, W, Cn, int(bool(src_hwc)), OH, OW,
+                                      INTERPOLATIONS[interpolation], int(bool(grayscale)), rows, stream()), "sf_frame_resize")
 
 
 def synth_obs(obs_slot_ptr: int, env_stride, B, env0, obs_bytes, seed, step) -> None:
