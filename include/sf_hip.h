@@ -462,6 +462,36 @@ int sf_synth_obs(uint8_t *obs, int64_t env_stride, int B, int env0, int64_t obs_
 int sf_synth_step(const int32_t *actions, int B, int env0, int num_actions, uint32_t seed, uint32_t step,
                   float *rewards, uint8_t *terminated, void *stream);
 
+/* ---- PixelCatch: a learnable pixel game on the device (csrc/sf_pixcatch.hip, envs/pixel_catch.py) ------------------
+ * A ball falls down an H x W field and reflects off the side walls; the player moves a paddle along the bottom rows
+ * (action 0 stay, 1 left, 2 right; any other value is read as 0).  When the ball reaches the paddle's rows the reward is
+ * +1 if their column ranges overlap, else -1, and a new ball is drawn at the top; after `balls` balls terminated = 1 and
+ * the env resets itself in the same step (paddle centred, new ball, every plane shows the new first frame).  All
+ * arithmetic is integer; sample_factory_amd/envs/pixel_catch.py is the same game in NumPy, bit for bit (observations,
+ * rewards, flags, state words), and documents the constants (ball, paddle, speeds: fixed functions of H and W).
+ * Randomness: sf_philox4x32_10, counter (draw index, 0, 4, 0), key (seed, env0 + e); words 0, 1, 2 give column, vx and vy
+ * by multiply-high.  The draw index lives in the state: no argument changes from step to step.
+ * state: int32 [N][sf_pixcatch_state_words(k) = 4 + 3 k], contiguous: {draw index, balls left, vx, vy}, then per plane j
+ * {paddle x, ball x, ball y}; plane k - 1 is the current position, plane j the one k - 1 - j steps ago.
+ * obs_out: row e is k planes of H W bytes, oldest first, rows out_pitch bytes apart (a slab column obs[:, t + 1]):
+ * background 0, paddle 128, ball 255 (the maximum where they overlap).
+ * sf_pixcatch_reset writes the first state and observation of envs [env0, env0 + N); sf_pixcatch_step reads actions
+ * int32 [N], advances every env by one step and writes observation, rewards f32 [N] and terminated u8 [N].
+ * One launch, one work-group per env; the old state is read by every lane before a barrier, written by one lane after
+ * it.  The frame is stored in 16-byte units when obs_out, out_pitch and k H W are multiples of 16, in 4-byte units when
+ * they are multiples of 4; a unit may straddle a row end or a plane end.  Units away from ball and paddle store zeros; the
+ * others are built in registers (16-byte units of a field at least 16 wide whose planes are multiples of 16 bytes: one bit
+ * per byte from the rectangles' runs in the unit's two rows, spread to bytes with shifts; any other unit byte by byte with
+ * compares and selects).  No sub-dword store touches the frame.
+ * Refused before any launch (SF_ERR_ARG): a null pointer; N <= 0; k outside 1 .. 8; balls < 1; a field too small for
+ * ball and paddle (or a side above 1024); out_pitch < k H W; obs_out, out_pitch or k H W not a multiple of 4.
+ * sf_pixcatch_state_words returns SF_ERR_ARG for k outside 1 .. 8. */
+int sf_pixcatch_state_words(int k);
+int sf_pixcatch_reset(int32_t *state, uint8_t *obs_out, int64_t out_pitch, int N, int env0, uint32_t seed, int H, int W,
+                      int k, int balls, void *stream);
+int sf_pixcatch_step(int32_t *state, const int32_t *actions, uint8_t *obs_out, int64_t out_pitch, float *rewards,
+                     uint8_t *terminated, int N, int env0, uint32_t seed, int H, int W, int k, int balls, void *stream);
+
 /* ---- K2/K3/K8/K9/K15/K18: actor-critic network (fp32 MFMA) -------------------------------------------------------
  * model/encoder.py:90-150 (conv head + MLP), model/actor_critic.py:160-195 (critic_linear + distribution_linear),
  * utils/normalize.py:51-70 + rl_utils.py:36-42 (u8 -> f32, -mean, *1/scale fused into the first layer's loader;

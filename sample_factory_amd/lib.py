@@ -64,6 +64,7 @@ SYMBOLS = [
     "sf_dp_oneshot_allreduce_f64", "sf_dp_oneshot_status", "sf_dp_oneshot_destroy",
     "sf_res_conv_fwd", "sf_res_pool_fwd", "sf_res_pool_bwd", "sf_res_conv_dgrad", "sf_res_conv_wgrad_workspace",
     "sf_res_conv_wgrad", "sf_res_conv_fwd_norm", "sf_res_conv_wgrad_norm",
+    "sf_pixcatch_state_words", "sf_pixcatch_reset", "sf_pixcatch_step",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -1068,6 +1069,48 @@ def synth_step(actions, env0, num_actions, seed, step, rewards, terminated) -> N
     _check(load().sf_synth_step(ptr(actions, "i32", "actions"), actions.numel(), int(env0), int(num_actions),
                                 u32(seed), u32(step), ptr(rewards, "f32"), ptr(terminated, "u8"), stream()),
            "sf_synth_step")
+
+
+# ---- PixelCatch (csrc/sf_pixcatch.hip; the game itself: envs/pixel_catch.py)
+def pixcatch_state_words(k: int) -> int:
+    n = int(load().sf_pixcatch_state_words(int(k)))
+    if n < 0:
+        raise SfHipError(f"sf_pixcatch_state_words: k = {k} outside 1 .. 8")
+    return n
+
+
+def _pixcatch_obs(what: str, state: torch.Tensor, obs_out: torch.Tensor):
+    """obs_out: a device u8 view [N, k, H, W] whose rows are contiguous blocks (a slab column) -> (N, k, H, W, pitch)"""
+    if not obs_out.is_cuda or obs_out.dtype != torch.uint8 or obs_out.dim() != 4:
+        raise SfHipError(f"{what}: obs_out must be a device uint8 view [N, k, H, W], got {tuple(obs_out.shape)} "
+                         f"{obs_out.dtype} on {obs_out.device}")
+    N, k, H, W = (int(d) for d in obs_out.shape)
+    if N and not obs_out[0].is_contiguous():
+        raise SfHipError(f"{what}: rows of obs_out must be contiguous blocks (strides {obs_out.stride()})")
+    if state.dim() != 2 or state.shape[0] != N or (1 <= k <= 8 and state.shape[1] != 4 + 3 * k):
+        raise SfHipError(f"{what}: state must be int32 [N = {N}, 4 + 3 k = {4 + 3 * k}], got {tuple(state.shape)}")
+    pitch = int(obs_out.stride(0)) if N > 1 else max(int(obs_out.stride(0)), k * H * W)  # (a one-row view: any stride)
+    return N, k, H, W, pitch
+
+
+def pixcatch_reset(state, obs_out, env0, seed, balls) -> None:
+    """sf_pixcatch_reset: first state (int32 [N, 4 + 3 k]) and first observation of envs [env0, env0 + N)"""
+    N, k, H, W, pitch = _pixcatch_obs("sf_pixcatch_reset", state, obs_out)
+    _check(load().sf_pixcatch_reset(ptr(state, "i32", "state"), _vp(obs_out), i64(pitch), N, int(env0), u32(seed), H, W, k,
+                                    int(balls), stream()), "sf_pixcatch_reset")
+
+
+def pixcatch_step(state, actions, obs_out, rewards, terminated, env0, seed, balls) -> None:
+    """sf_pixcatch_step: one step of N games; the next observation goes to obs_out ([N, k, H, W] view of a slab column)"""
+    N, k, H, W, pitch = _pixcatch_obs("sf_pixcatch_step", state, obs_out)
+    for name, x in (("actions", actions), ("rewards", rewards), ("terminated", terminated)):
+        if x is not None and x.numel() != N:
+            raise SfHipError(f"sf_pixcatch_step: {name} has {x.numel()} elements, expected {N}")
+    key = ("pixcatch_step", N, k, H, W) if _keys_wanted() else None  # (per-launch HIP events inside a run: lib.PROFILE)
+    with _timed(key):
+        _check(load().sf_pixcatch_step(ptr(state, "i32", "state"), ptr(actions, "i32", "actions"), _vp(obs_out), i64(pitch),
+                                       ptr(rewards, "f32", "rewards"), ptr(terminated, "u8", "terminated"), N, int(env0),
+                                       u32(seed), H, W, k, int(balls), stream()), "sf_pixcatch_step")
 
 
 # ---- network kernels (csrc/sf_nn.hip)
