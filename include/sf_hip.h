@@ -492,6 +492,36 @@ int sf_pixcatch_reset(int32_t *state, uint8_t *obs_out, int64_t out_pitch, int N
 int sf_pixcatch_step(int32_t *state, const int32_t *actions, uint8_t *obs_out, int64_t out_pitch, float *rewards,
                      uint8_t *terminated, int N, int env0, uint32_t seed, int H, int W, int k, int balls, void *stream);
 
+/* ---- random-shift augmentation of a minibatch's frames (csrc/sf_augment.hip, --augment_random_shift) ---------------
+ * The random shift of RAD / DrQ / DrAC — pad every frame by `pad` pixels with edge replication, crop back to H x W at a
+ * random offset — as ONE gather launch.  The reference has no augmentation.  Sample i of the launch is dataset row
+ * d = index ? index[i] : offset + i, read at src + (traj_T > 0 ? d + d / traj_T : d) * src_sample_pitch (the learner's
+ * row addressing of a [E, T + 1, ...] slab leaf) and written densely at dst + i * dst_sample_pitch (pitches in bytes):
+ *   dst[i][c][y][x] = src[row][c][clip(y + dy - pad, 0, H - 1)][clip(x + dx - pad, 0, W - 1)]
+ * for elements of elem_bytes = 1 (u8) or 4 (f32) bytes, bit for bit; all C planes of a sample (a frame stack, RGB) move
+ * together.  The draw: w = sf_philox4x32_10(counter (draw_id, 0, 5, 0), key (seed, d / recurrence)), m = 2 pad + 1,
+ * dx = (w[0] * m) >> 32, dy = (w[1] * m) >> 32 as 64-bit products: both in [0, 2 pad], one draw per recurrence-long
+ * chunk of dataset rows, so that a recurrent state never sees the picture jump inside a BPTT chunk.  Counter lane 2 of the
+ * library's Philox streams: 0 .. 3 the samplers and synthetic envs of sf_rl.hip, 4 PixelCatch's balls, 5 this draw.
+ * sample_factory_amd/envs/frame_ops.py (random_shift_draws, random_shift_frames) is the same arithmetic in NumPy.
+ * pad == 0 is the plain indexed gather (no Philox block is computed); with C = H = 1, W = F it makes the dense copy of a
+ * vector key.
+ * One work-group per sample: the frame rows a strip of the output reads are staged in LDS as the aligned 16-byte granules
+ * that hold them (every source byte is loaded once, nothing bytewise; the clamped border rows and columns come from the
+ * staged image), a lane assembles 16 output bytes — a u8 dword inside one row from the 4-byte window of the staged row
+ * that holds its clamped columns (the two LDS dwords around it, funnel-shifted) and one byte permute that repeats the edge
+ * pixel, an f32 element at its clamped column, a dword with a row end inside it byte by byte from LDS — and stores them
+ * as one 16-byte unit; only the bytes in front of a sample's first and behind its last 16-byte boundary are stored singly.  Any alignment of src, dst,
+ * the pitches and the sample size gives the same bytes.  Samples whose rows do not fit 64 KB of LDS take a dword-wise path
+ * without LDS.  dst and src must not share bytes (not checked); index entries are trusted as the other consumers trust
+ * them.
+ * Refused before any launch (SF_ERR_ARG): null dst / src; n < 0; pad outside 0 .. 255; elem_bytes not 1 or 4;
+ * recurrence < 1; C, H or W < 1; traj_T < 0 or offset < 0; a pitch below C H W elem_bytes.  n == 0: SF_OK, nothing is
+ * launched. */
+int sf_random_shift_gather(void *dst, int64_t dst_sample_pitch, const void *src, int64_t src_sample_pitch,
+                           const int32_t *index, int64_t offset, int64_t n, int traj_T, int C, int H, int W, int elem_bytes,
+                           int pad, int recurrence, uint32_t seed, uint32_t draw_id, void *stream);
+
 /* ---- K2/K3/K8/K9/K15/K18: actor-critic network (fp32 MFMA) -------------------------------------------------------
  * model/encoder.py:90-150 (conv head + MLP), model/actor_critic.py:160-195 (critic_linear + distribution_linear),
  * utils/normalize.py:51-70 + rl_utils.py:36-42 (u8 -> f32, -mean, *1/scale fused into the first layer's loader;

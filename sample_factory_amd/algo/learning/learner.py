@@ -34,6 +34,7 @@ import torch
 from sample_factory_amd import lib
 from sample_factory_amd.algo.learning.dp import ReplicaGroup
 from sample_factory_amd.algo.utils.tensor_dict import TensorDict
+from sample_factory_amd.envs.frame_ops import random_shift_seed
 from sample_factory_amd.envs.spaces import (action_head_sizes, calc_num_action_parameters, calc_num_actions, is_box,
                                              is_discrete)
 from sample_factory_amd.model.actor_critic import ActorCritic
@@ -192,6 +193,9 @@ class Learner:
         self.actor_critic = create_actor_critic(cfg, self.env_info.obs_space, self.env_info.action_space, self.device,
                                                 all_reduce=ar)
         self.actor_critic.train()
+        self._shift_pad = self._augment_pad(cfg, self.actor_critic, self.env_info.obs_space)
+        # the Philox key of the shifts: replicas of a data-parallel group draw differently (envs/frame_ops.py)
+        self._shift_seed = random_shift_seed(cfg.seed, self.policy_id, self.group.rank if self.group is not None else 0)
         if self.dp:  # identical initial weights on every replica
             self.group.broadcast(self.actor_critic.flat_params, src=0)
             self.actor_critic.params_changed()
@@ -231,6 +235,45 @@ class Learner:
         self.is_initialized = True
         state_dict = None if cfg.serial_mode else self.actor_critic.state_dict()
         return self.policy_id, state_dict, self.device, self.train_step
+
+    @staticmethod
+    def _augment_pad(cfg, actor_critic, obs_space) -> int:
+        """cfg.augment_random_shift: the pad P of the random shift every SGD step's frames get, 0 = off.
+        Refused: P outside 0 .. 255, a model without an image key, and a network that runs in torch (a user-registered
+        module reads the slab through torch indexing, not through a dense launch buffer)"""
+        P = int(getattr(cfg, "augment_random_shift", 0) or 0)
+        if not 0 <= P <= 255:
+            raise ValueError(f"augment_random_shift={P} must lie in 0 .. 255 (0 = off)")
+        if P == 0:
+            return 0
+        from sample_factory_amd.model.torch_policy import TorchPolicyAdapter
+        if isinstance(actor_critic, TorchPolicyAdapter):
+            raise NotImplementedError("augment_random_shift with a network that runs in torch (a user-registered model or a "
+                                      "configuration the native kernels do not take): only the native models augment")
+        keys = getattr(actor_critic, "obs_keys", None) or ["obs"]
+        spaces_ = getattr(obs_space, "spaces", None) or {"obs": obs_space}
+        if not any(len(spaces_[k].shape) == 3 for k in keys if k in spaces_):
+            raise ValueError(f"augment_random_shift={P}: the observation has no image key [C, H, W] to shift")
+        return P
+
+    def _shifted_minibatch(self, buff: AttrDict, index, offset: int, n: int):
+        """cfg.augment_random_shift: the minibatch's frames of every observation key, gathered through (index | offset, T)
+        into dense per-key buffers [batch_size, obs_elems] — image keys shifted by this SGD step's draws (draw_id =
+        train_step as it stands before the step, one draw per recurrence-long chunk), other keys copied (shift 0).
+        Returns what stands for buff.obs in forward_heads / backward: dense row i IS dataset row index[i] | offset + i."""
+        cfg, ac = self.cfg, self.actor_critic
+        keyed = isinstance(buff.obs, dict)
+        out = {}
+        for k, leaf in (buff.obs.items() if keyed else [("obs", buff.obs)]):
+            shape = tuple(int(v) for v in leaf.shape[2:])  # the slab leaf is [E, T + 1, ...]
+            elems = int(np.prod(shape))
+            dense = ac._buf(("aug", k), (max(int(cfg.batch_size), n), elems), dtype=leaf.dtype)
+            image = len(shape) == 3
+            lib.random_shift_gather(dense, leaf, n, shape if image else (1, 1, elems), sample_stride=elems, index=index,
+                                    offset=offset, traj_T=buff.T, pad=self._shift_pad if image else 0,
+                                    recurrence=cfg.recurrence, seed=self._shift_seed, draw_id=self.train_step)
+            out[k] = dense[:n]
+        return out if keyed else out["obs"]
 
     @staticmethod
     def _mask_in_loss(cfg, env_info) -> bool:
@@ -542,7 +585,15 @@ class Learner:
             lib.rnn_chunk_setup(buff.dones, buff.valids, buff.rnn_states, index, offset, Cn, R, keep_tm, h0, traj_T=buff.T)
             rnn = dict(R=R, h0=h0, keep_tm=keep_tm)
         kw = {}
-        if first_of == (0, 0):
+        # where the network reads its frames: the slab through (index | offset, T), or — cfg.augment_random_shift — this
+        # step's dense shifted batch, row i of which pairs with dataset row index[i] | offset + i of everything else below
+        frames = (buff.obs, dict(index=index, offset=offset, traj_T=buff.T))
+        if getattr(self, "_shift_pad", 0) > 0:
+            frames = (self._shifted_minibatch(buff, index, offset, n), dict(index=None, offset=0, traj_T=0))
+            if first_of == (0, 0):
+                self.reuse_stats["plain"] += 1
+                self.reuse_stats["last_prefix"], self.reuse_stats["last_reason"] = 0, "augment_random_shift: the frames are shifted"
+        elif first_of == (0, 0):
             # the first minibatch of the first epoch, still on the rollout's weights: the conv activations the rollout kept
             # for exactly these rows stand in for conv1..conv3 (ActorCritic.kept_resume holds the guard); reuse_stats counts
             resume, why = ac.kept_resume(buff.obs, index, offset, n, buff.T, 0, 0) if hasattr(ac, "kept_resume") else (None, "model")
@@ -552,8 +603,8 @@ class Learner:
             st["fc_reused"] += 1 if resume is not None and resume.get("fc") is not None else 0  # (the fc layer too)
             if resume is not None:
                 kw["resume_from"] = resume
-        acts = ac.forward_heads(buff.obs, n, sample_stride=ac.obs_elems, index=index, offset=offset,
-                                traj_T=buff.T, tag="train", rnn=rnn, **kw)
+        self._mb_frames = frames  # _train hands the same buffers and addressing to ac.backward (conv1's weight gradient)
+        acts = ac.forward_heads(frames[0], n, sample_stride=ac.obs_elems, tag="train", rnn=rnn, **frames[1], **kw)
         heads = acts[-1]
         ld = ac.heads_ld  # 1 + A padded to a multiple of 4; padding columns of g_heads stay zero
         params, values = heads[:, 1:], heads[:, 0]
@@ -648,16 +699,14 @@ class Learner:
                 if self._dp_split is not None:
                     cut = ac._segs[self._dp_split][0]
                     pending = []
-                    ac.backward(acts, g_heads, buff.obs, n, sample_stride=ac.obs_elems, index=index, offset=offset,
-                                traj_T=buff.T,
+                    ac.backward(acts, g_heads, self._mb_frames[0], n, sample_stride=ac.obs_elems, **self._mb_frames[1],
                                 on_layer_done=lambda li: pending.append(self.group.all_reduce_grads_async(
                                     ac.flat_grads[cut:])) if li == self._dp_split else None)
                     self.group.all_reduce_grads(ac.flat_grads[:cut])
                     for work in pending:
                         work.wait()
                 else:
-                    ac.backward(acts, g_heads, buff.obs, n, sample_stride=ac.obs_elems, index=index, offset=offset,
-                                traj_T=buff.T)
+                    ac.backward(acts, g_heads, self._mb_frames[0], n, sample_stride=ac.obs_elems, **self._mb_frames[1])
                     if self.dp:
                         self.group.all_reduce_grads(ac.flat_grads)
                 actual_lr = self.curr_lr

@@ -103,6 +103,10 @@ ENGINE_FLAGS = [
     #                                          wrapper's nearest: on the device the better filter costs nothing
     ("device_grayscale", _bool, False),      # R, G, B -> one luma plane after the resize, in the same launch (C must be 3);
     #                                          works alone, at the env's own size
+    ("augment_random_shift", int, 0),        # P > 0: every SGD step trains on its minibatch's frames shifted at random by up
+    #                                          to P pixels (pad P with edge replication, crop back: RAD / DrQ), gathered on
+    #                                          the device in one launch (sf_random_shift_gather); rollouts,
+    #                                          bootstrap values and enjoy never augment; 0 = off, outside 0 .. 255 is refused
 ]
 
 
@@ -190,6 +194,8 @@ def verify_cfg(cfg, env_info) -> bool:
         err("RNN policies need recurrence > 1")
     if str(getattr(cfg, "reuse_rollout_activations", "auto")) not in ("auto", "off"):
         err(f"{cfg.reuse_rollout_activations=} must be 'auto' or 'off'")
+    if not 0 <= int(getattr(cfg, "augment_random_shift", 0) or 0) <= 255:
+        err(f"{cfg.augment_random_shift=} must lie in 0 .. 255 (0 = off)")
     total_agents = cfg.num_workers * cfg.num_envs_per_worker * env_info.num_agents
     per_iter = cfg.num_batches_per_epoch * cfg.batch_size
     per_rollout = total_agents * cfg.rollout // cfg.num_policies

@@ -13,10 +13,15 @@ only, u8 in, u8 out, vectorised over any leading batch axes:
             rounded channels (resize first, then grey: the order of the reference's ResizeWrapper).
 
 The area result is the exact value of what OpenCV's INTER_AREA approximates in float; it may differ from OpenCV by 1 in
-the last bit on ties."""
+the last bit on ties.
+
+The module also holds the NumPy model of the training-time random shift (--augment_random_shift, sf_random_shift_gather;
+DESIGN.md 3.17): `random_shift_draws`, `random_shift_frames` and the learner's `random_shift_seed`."""
 from __future__ import annotations
 
 import numpy as np
+
+from sample_factory_amd.envs.pixel_catch import philox
 
 INTERPOLATIONS = ("area", "nearest")
 GRAY_R, GRAY_G, GRAY_B, GRAY_SHIFT = 9798, 19235, 3735, 15
@@ -88,3 +93,42 @@ def preprocess_frames(frames, layout: str, OH: int, OW: int, interpolation: str 
         raise ValueError(f"grayscale needs 3 channels (R, G, B), got {chw.shape[1]}")
     out = (resize_area_u8 if interpolation == "area" else resize_nearest_u8)(chw, OH, OW)
     return np.ascontiguousarray(rgb_to_gray_u8(out, 1) if grayscale else out)
+
+
+# ---- random shift (sf_random_shift_gather) ---------------------------------------------------------------------------
+RANDOM_SHIFT_MAX_PAD = 255
+RANDOM_SHIFT_LANE = 5  # lane 2 of the Philox counter: 0 .. 3 are taken by sf_rl.hip, 4 by sf_pixcatch.hip
+
+
+def random_shift_seed(seed, policy_id: int, rank: int = 0) -> int:
+    """the Philox key word the learner of `policy_id` (data-parallel replica `rank`) draws its shifts under: distinct per
+    run seed, policy and replica, 32 bits"""
+    return (((int(seed or 0) * 7919 + int(policy_id)) * 1000003 + int(rank)) * 2654435761 + 1) & 0xFFFFFFFF
+
+
+def random_shift_draws(seed: int, draw_id: int, groups, pad: int):
+    """(dy, dx) int32 arrays, one pair per entry of `groups`, each in [0, 2 * pad]: w = philox4x32_10(counter
+    (draw_id, 0, 5, 0), key (seed, group)), dx = (w[0] * m) >> 32, dy = (w[1] * m) >> 32 with m = 2 * pad + 1"""
+    pad = int(pad)
+    if not 0 <= pad <= RANDOM_SHIFT_MAX_PAD:
+        raise ValueError(f"random shift: pad = {pad} outside 0 .. {RANDOM_SHIFT_MAX_PAD}")
+    groups = np.asarray(groups)
+    w = philox(int(draw_id) & 0xFFFFFFFF, 0, RANDOM_SHIFT_LANE, 0, int(seed) & 0xFFFFFFFF, groups.astype(np.int64))
+    m = np.uint64(2 * pad + 1)
+    dx = ((w[0].astype(np.uint64) * m) >> np.uint64(32)).astype(np.int32)
+    dy = ((w[1].astype(np.uint64) * m) >> np.uint64(32)).astype(np.int32)
+    return dy.reshape(groups.shape), dx.reshape(groups.shape)
+
+
+def random_shift_frames(frames, dy, dx, pad: int) -> np.ndarray:
+    """frames [N, C, H, W] (u8 or f32), dy / dx int [N] in [0, 2 * pad]: pad by `pad` pixels with edge replication and crop
+    back at (dy, dx): out[i, c, y, x] = frames[i, c, clip(y + dy[i] - pad, 0, H - 1), clip(x + dx[i] - pad, 0, W - 1)]"""
+    a = np.asarray(frames)
+    if a.ndim != 4:
+        raise ValueError(f"frames [N, C, H, W] expected, got shape {a.shape}")
+    N, _, H, W = a.shape
+    dy, dx = np.asarray(dy, dtype=np.int64).reshape(N), np.asarray(dx, dtype=np.int64).reshape(N)
+    ys = np.clip(np.arange(H, dtype=np.int64)[None, :] + dy[:, None] - int(pad), 0, H - 1)  # [N, H]
+    xs = np.clip(np.arange(W, dtype=np.int64)[None, :] + dx[:, None] - int(pad), 0, W - 1)  # [N, W]
+    return np.ascontiguousarray(a[np.arange(N)[:, None, None, None], np.arange(a.shape[1])[None, :, None, None],
+                                  ys[:, None, :, None], xs[:, None, None, :]])

@@ -65,6 +65,7 @@ SYMBOLS = [
     "sf_res_conv_fwd", "sf_res_pool_fwd", "sf_res_pool_bwd", "sf_res_conv_dgrad", "sf_res_conv_wgrad_workspace",
     "sf_res_conv_wgrad", "sf_res_conv_fwd_norm", "sf_res_conv_wgrad_norm",
     "sf_pixcatch_state_words", "sf_pixcatch_reset", "sf_pixcatch_step",
+    "sf_random_shift_gather",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -1058,6 +1059,37 @@ def frame_resize(dst: torch.Tensor, src: torch.Tensor, src_hwc: bool, interpolat
         _check(load().sf_frame_resize(_vp(dst), i64(pitch(dst, int(dst.shape[1]) * OH * OW)), _vp(src),
                                       i64(pitch(src, H * W * Cn)), H, W, Cn, int(bool(src_hwc)), OH, OW,
                                       INTERPOLATIONS[interpolation], int(bool(grayscale)), rows, stream()), "sf_frame_resize")
+
+
+def random_shift_gather(dst: torch.Tensor, src: torch.Tensor, n: int, shape, *, sample_stride: Optional[int] = None,
+                        index: Optional[torch.Tensor] = None, offset: int = 0, traj_T: int = 0, pad: int = 0,
+                        recurrence: int = 1, seed: int = 0, draw_id: int = 0) -> None:
+    """sf_random_shift_gather: dst[i] <- frame of dataset row d = index[i] | offset + i shifted by the draw of
+    (seed, draw_id, d // recurrence), for i < n.  src: any device view whose data_ptr is sample 0 (a slab leaf
+    [E, T + 1, C, H, W] with traj_T = T, or dense frames), samples `sample_stride` ELEMENTS apart (default C H W), addressed
+    as forward_heads addresses them; dst: a device tensor [>= n, C H W] or [>= n, C, H, W] of the same dtype (u8 or f32)
+    whose rows are contiguous blocks; shape = (C, H, W).  pad = 0: the plain gather.  ONE launch, bit for bit the
+    arithmetic of envs/frame_ops.py (random_shift_draws, random_shift_frames)"""
+    if not (dst.is_cuda and src.is_cuda) or dst.dtype != src.dtype or dst.dtype not in (torch.uint8, torch.float32):
+        raise SfHipError(f"random_shift_gather: device views of one dtype (uint8 or float32) required, got {dst.dtype} on "
+                         f"{dst.device} and {src.dtype} on {src.device}")
+    Cn, H, W = (int(v) for v in shape)
+    n, es, elems = int(n), dst.element_size(), Cn * H * W
+    if dst.dim() < 2 or dst.shape[0] < n or dst[0].numel() != elems or (dst.shape[0] and not dst[0].is_contiguous()):
+        raise SfHipError(f"random_shift_gather: dst must hold at least n = {n} contiguous rows of C H W = {elems} elements, "
+                         f"got {tuple(dst.shape)} with strides {dst.stride()}")
+    if index is not None and (index.dtype != torch.int32 or not index.is_cuda or not index.is_contiguous() or index.numel() < n):
+        raise SfHipError(f"random_shift_gather: index must be a contiguous device int32 tensor of at least n = {n} entries")
+    if n == 0:
+        return
+    stride = elems if sample_stride is None else int(sample_stride)
+    dpitch = int(dst.stride(0)) * es if dst.shape[0] > 1 else max(int(dst.stride(0)) * es, elems * es)
+    key = ("random_shift_gather", n, Cn, H, W, es, int(pad)) if _keys_wanted() else None  # (tools/augment_shift_bench.py)
+    with _timed(key):
+        _check(load().sf_random_shift_gather(_vp(dst), i64(dpitch), _vp(src), i64(stride * es),
+                                             C.c_void_p(0) if index is None else _vp(index), i64(offset), i64(n), int(traj_T),
+                                             Cn, H, W, es, int(pad), int(recurrence), u32(seed), u32(draw_id), stream()),
+               "sf_random_shift_gather")
 
 
 def synth_obs(obs_slot_ptr: int, env_stride, B, env0, obs_bytes, seed, step) -> None:
