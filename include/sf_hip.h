@@ -207,6 +207,36 @@ int sf_vtrace_masked(const float *params, int ld_params, const float *values, in
                      int64_t offset, int64_t n, int A, int action_kind, int recurrence, float gamma, float rho_hat,
                      float c_hat, float *vs, float *adv, const int32_t *head_n /* host, or NULL */, int num_heads,
                      const uint8_t *mask, int64_t ld_mask, int mask_T, void *stream);
+/* ---- consistency loss between two rows of a heads matrix (--augment_consistency_coeff) -------------
+ * DrAC (Raileanu et al.): the PPO loss stays on the clean frames, and a regulariser pulls policy and value on the
+ * augmented frames towards their values on the clean ones.  The reference has no augmentation.  Row i of the launch is
+ * dataset row d = index ? index[i] : offset + i (read for valids[d] only); its target is row i of params_t / values_t
+ * (a constant: nothing is written for it), its student row i of params_s / values_s; both pairs are strided column views
+ * (ld_params, ld_values in elements, rows 4-byte aligned), in the learner rows [0, n) and [n, 2n) of ONE heads matrix.
+ * Per valid row, summed over the members of the head list (action_kind / head_n / num_heads as sf_vtrace takes them;
+ * head_n NULL: one Discrete(A) or Box(A / 2)):
+ *   Discrete member, logits z, lp = log_softmax(z), p = exp(lp):
+ *     KL = sum_k p_t,k (lp_t,k - lp_s,k)                        d KL / d z_s,k = p_s,k - p_t,k
+ *   Box(D) member, column k, sd = clamp(exp(log_std), 1e-4, 1e4) (the loss's clamp):
+ *     vr = (sd_t / sd_s)^2,  dl = (mu_t - mu_s) / sd_s,  KL = (vr + dl^2 - 1 - ln vr) / 2
+ *     d KL / d mu_s = (mu_s - mu_t) / sd_s^2       d KL / d log_std_s = 1 - vr - dl^2, 0 where exp(log_std_s) is beyond the clamp
+ *   value: (v_s - v_t)^2
+ * With inv_n = 1 / moments[2] (the global valid count sf_ppo_loss divides by) the call writes, for every valid row,
+ *   g_params_s[i][:A] = coeff_policy inv_n dKL/dz_s      g_values_s[i] = coeff_value inv_n 2 (v_s - v_t)
+ * and an all-zero gradient row for an invalid one (valids[d] == 0), which is not counted; columns beyond A and other rows
+ * are not touched.  sums: device double[4], zeroed by the call: {sum KL, sum (v_s - v_t)^2, max KL, n_valid} over the
+ * valid rows; the loss is coeff_policy sums[0] inv_n + coeff_value sums[1] inv_n.  Rows with the same bits give exactly 0.
+ * A <= 128: one lane per row; A > 128: one wave64 per row (the wide family of sf_ppo_loss, same helpers, same rounding).
+ * Refused before any launch or memset (SF_ERR_ARG): a null pointer (index and head_n may be null), n < 0, A <= 0,
+ * offset < 0, ld_params < A, ld_values < 1, action_kind not 0 / 1 or 1 with an odd A, a head list sf_ppo_loss_heads
+ * refuses (num_heads outside 1 .. SF_MAX_ACTION_HEADS, an empty member, sizes that do not sum to A, a one-member list
+ * that is not the single space, several members with action_kind 1), a negative or non-finite coefficient.  n == 0:
+ * SF_OK, nothing is launched. */
+int sf_consistency_loss(const float *params_t, const float *params_s, int ld_params, const float *values_t,
+                        const float *values_s, int ld_values, const uint8_t *valids, const int32_t *index, int64_t offset,
+                        int64_t n, int A, int action_kind, const int32_t *head_n /* host, or NULL */, int num_heads,
+                        float coeff_policy, float coeff_value, const double *moments, double *sums, float *g_params_s,
+                        float *g_values_s, void *stream);
 /* out[0..3] = policy, exploration, kl, value losses; [4] kl mean; [5] kl max; [6] adv mean; [7] adv std;
  * [8] n_valid; [9] entropy (or symkl) mean — device float[16]. */
 int sf_loss_scalars(const double *sums, const double *moments, const sf_loss_cfg *h_cfg, float *out, void *stream);

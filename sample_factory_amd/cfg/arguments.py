@@ -107,7 +107,31 @@ ENGINE_FLAGS = [
     #                                          to P pixels (pad P with edge replication, crop back: RAD / DrQ), gathered on
     #                                          the device in one launch (sf_random_shift_gather); rollouts,
     #                                          bootstrap values and enjoy never augment; 0 = off, outside 0 .. 255 is refused
+    ("augment_consistency_coeff", float, 0.0),  # alpha > 0 (needs augment_random_shift > 0): DrAC.  The PPO loss stays on
+    #                                          the clean frames; alpha * (KL(clean || shifted) + (v_shifted - v_clean)^2)
+    #                                          is added on the shifted twin of every row, one 2n-row network pass per SGD
+    #                                          step (sf_consistency_loss); 0 = off: the shift alone (RAD);
+    #                                          negative, non-finite, or without the shift is refused
 ]
+
+
+def augment_consistency_coeff(cfg) -> float:
+    """cfg.augment_consistency_coeff checked against the flags it depends on: the coefficient alpha of the
+    consistency loss, 0.0 = off.  Raises ValueError for a negative or non-finite alpha and for alpha > 0 without
+    augment_random_shift, NotImplementedError for alpha > 0 with mask_actions_in_loss (verify_cfg and Learner.init)"""
+    import math
+    alpha = float(getattr(cfg, "augment_consistency_coeff", 0.0) or 0.0)
+    if not math.isfinite(alpha) or alpha < 0.0:
+        raise ValueError(f"augment_consistency_coeff={alpha} must be finite and not negative (0 = off)")
+    if alpha == 0.0:
+        return 0.0
+    if int(getattr(cfg, "augment_random_shift", 0) or 0) <= 0:
+        raise ValueError(f"augment_consistency_coeff={alpha} needs augment_random_shift > 0: the consistency loss compares "
+                         "the network on the shifted frames with the network on the clean ones")
+    if getattr(cfg, "mask_actions_in_loss", False):
+        raise NotImplementedError(f"augment_consistency_coeff={alpha} with mask_actions_in_loss=True: the consistency term "
+                                  "under an action mask is not implemented")
+    return alpha
 
 
 def parse_sf_args(argv: Optional[List[str]] = None, evaluation: bool = False) -> Tuple[argparse.ArgumentParser, argparse.Namespace]:
@@ -196,6 +220,10 @@ def verify_cfg(cfg, env_info) -> bool:
         err(f"{cfg.reuse_rollout_activations=} must be 'auto' or 'off'")
     if not 0 <= int(getattr(cfg, "augment_random_shift", 0) or 0) <= 255:
         err(f"{cfg.augment_random_shift=} must lie in 0 .. 255 (0 = off)")
+    try:
+        augment_consistency_coeff(cfg)  # (with mask_actions_in_loss it raises NotImplementedError: a missing feature, not a typo)
+    except ValueError as e:
+        err(str(e))
     total_agents = cfg.num_workers * cfg.num_envs_per_worker * env_info.num_agents
     per_iter = cfg.num_batches_per_epoch * cfg.batch_size
     per_rollout = total_agents * cfg.rollout // cfg.num_policies

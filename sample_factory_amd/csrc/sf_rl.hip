@@ -1654,6 +1654,208 @@ extern "C" int sf_ppo_loss_masked(const float *params, int ld_params, const floa
                            SF_MAX_ACTION_HEADS, moments, sums, g_params, g_values, ratio_out, mask, ld_mask, mask_T, stream);
 }
 
+// =========================================================================================== consistency loss (DrAC)
+// --augment_consistency_coeff: KL(target || student) of the action distributions plus the squared value
+// difference between two rows of one heads matrix — row i on the clean frames (the target, a constant) and its twin on the
+// shifted ones (the student) — with the gradient for the student row only.  The arithmetic is the PPO loss's: cat_lse /
+// wide_push for a Discrete member's statistics, box_sd for a Box column, so both round as sf_ppo_loss does; rows with the
+// same bits give exactly 0 (lp_t - lp_s, p_s - p_t, vr - 1, log 1 and mu_s - mu_t are all exact zeros).
+// column k of a Box(D) member: its KL(N_t || N_s), and the student's gradient scaled by `scale` into gz[k] / gz[D + k]
+__device__ __forceinline__ float box_consistency(const float *__restrict__ zt, const float *__restrict__ zs, int D, int k,
+                                                 float scale, float *__restrict__ gz) {
+    const float mut = zt[k], sdt = box_sd(zt[D + k]);
+    const float mus = zs[k], es = expf(zs[D + k]);
+    const float sds = clampf(es, 1e-4f, 1e4f);
+    const bool inside = es >= 1e-4f && es <= 1e4f;  // (beyond the clamp the standard deviation does not move: box_grad)
+    const float vr = (sdt / sds) * (sdt / sds);
+    const float dl = (mut - mus) / sds;
+    gz[k] = scale * ((mus - mut) / (sds * sds));
+    gz[D + k] = inside ? scale * (1.f - vr - dl * dl) : 0.f;
+    return 0.5f * (vr + dl * dl - 1.f - logf(vr));
+}
+// column k of a Discrete member from the two rows' statistics: its KL term, the student's gradient into *g
+__device__ __forceinline__ float cat_consistency(float ztk, float zsk, float mxt, float lset, float mxs, float lses,
+                                                 float scale, float *__restrict__ g) {
+    const float lpt = (ztk - mxt) - lset, pt = expf(lpt), lps = (zsk - mxs) - lses;
+    *g = scale * (expf(lps) - pt);
+    return pt * (lpt - lps);
+}
+// block reduction of {sum KL, sum (dv)^2, n_valid} and the largest KL into sums[0], [1], [3] and [2]
+__device__ __forceinline__ void consistency_epilogue(double (&acc)[3], float kl_max, double *__restrict__ sums) {
+    __shared__ double lds[4 * 3];
+    __shared__ float lds_max[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    kl_max = sf_wave_max(kl_max);
+    if (lane == 0) lds_max[wave] = kl_max;
+    sf_block_sum<3>(acc, lds);  // contains a __syncthreads()
+    if (threadIdx.x == 0) {
+        atomicAdd(&sums[0], acc[0]);
+        atomicAdd(&sums[1], acc[1]);
+        atomicAdd(&sums[3], acc[2]);
+        const float m = fmaxf(fmaxf(lds_max[0], lds_max[1]), fmaxf(lds_max[2], lds_max[3]));
+        if (m > -1.0f) atomic_max_float(&sums[2], m);
+    }
+}
+
+// A <= 128: one lane per row over the member list, both rows read in place (as k_ppo_loss_mh reads them)
+__global__ __launch_bounds__(256) void k_consistency_loss(const float *__restrict__ params_t,
+                                                          const float *__restrict__ params_s, int ldp,
+                                                          const float *__restrict__ values_t,
+                                                          const float *__restrict__ values_s, int ldv,
+                                                          const uint8_t *__restrict__ valids,
+                                                          const int32_t *__restrict__ index, int64_t offset, int64_t n,
+                                                          int A, HeadsDev hd, float coeff_policy, float coeff_value,
+                                                          const double *__restrict__ moments, double *__restrict__ sums,
+                                                          float *__restrict__ g_params_s, float *__restrict__ g_values_s) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const float inv_n = 1.0f / (float)moments[2];
+    double acc[3] = {0.0, 0.0, 0.0};
+    float kl_max = -1.0f;
+    if (i < n) {
+        const int64_t d = index ? (int64_t)index[i] : offset + i;
+        const float *zt = params_t + i * ldp, *zs = params_s + i * ldp;
+        float *gz = g_params_s + i * ldp;
+        if (valids[d] != 0) {
+            const float sp = coeff_policy * inv_n;
+            float kl = 0.f;
+            int off = 0;
+            for (int h = 0; h < hd.num_heads; ++h) {
+                const int nh = hd.head_n[h];
+                if (nh < 0) {  // Box(D) member
+                    const int D = -nh;
+                    for (int k = 0; k < D; ++k) kl += box_consistency(zt + off, zs + off, D, k, sp, gz + off);
+                    off += 2 * D;
+                    continue;
+                }
+                float mxt, lset, mxs, lses, kk = 0.f;
+                cat_lse(zt + off, nh, mxt, lset);
+                cat_lse(zs + off, nh, mxs, lses);
+                for (int k = 0; k < nh; ++k)
+                    kk += cat_consistency(zt[off + k], zs[off + k], mxt, lset, mxs, lses, sp, gz + off + k);
+                kl += kk;
+                off += nh;
+            }
+            const float dv = values_s[i * ldv] - values_t[i * ldv];
+            g_values_s[i * ldv] = coeff_value * inv_n * (2.f * dv);
+            acc[0] = kl;
+            acc[1] = dv * dv;
+            acc[2] = 1.0;
+            kl_max = kl;
+        } else {  // not counted, zero gradient row
+            for (int k = 0; k < A; ++k) gz[k] = 0.f;
+            g_values_s[i * ldv] = 0.f;
+        }
+    }
+    consistency_epilogue(acc, kl_max, sums);
+}
+
+// A > 128: one wave64 per row, four rows per block, lanes striding the columns of a member (the wide family's layout)
+__global__ __launch_bounds__(256) void k_consistency_loss_wide(const float *__restrict__ params_t,
+                                                               const float *__restrict__ params_s, int ldp,
+                                                               const float *__restrict__ values_t,
+                                                               const float *__restrict__ values_s, int ldv,
+                                                               const uint8_t *__restrict__ valids,
+                                                               const int32_t *__restrict__ index, int64_t offset,
+                                                               int64_t n, int A, HeadsDev hd, float coeff_policy,
+                                                               float coeff_value, const double *__restrict__ moments,
+                                                               double *__restrict__ sums, float *__restrict__ g_params_s,
+                                                               float *__restrict__ g_values_s) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float inv_n = 1.0f / (float)moments[2];
+    const float sp = coeff_policy * inv_n;
+    double acc[3] = {0.0, 0.0, 0.0};
+    float kl_max = -1.0f;
+    for (int64_t i = (int64_t)blockIdx.x * WIDE_ROWS + wave; i < n; i += (int64_t)gridDim.x * WIDE_ROWS) {
+        const int64_t d = index ? (int64_t)index[i] : offset + i;
+        const float *zt = params_t + i * ldp, *zs = params_s + i * ldp;
+        float *gz = g_params_s + i * ldp;
+        if (valids[d] == 0) {  // wave-uniform: not counted, zero gradient row
+            for (int k = lane; k < A; k += 64) gz[k] = 0.f;
+            if (lane == 0) g_values_s[i * ldv] = 0.f;
+            continue;
+        }
+        float kl = 0.f;
+        int off = 0;
+        for (int h = 0; h < hd.num_heads; ++h) {
+            const int nh = hd.head_n[h];
+            float kk = 0.f;
+            if (nh < 0) {  // Box(D) member
+                const int D = -nh;
+                for (int k = lane; k < D; k += 64) kk += box_consistency(zt + off, zs + off, D, k, sp, gz + off);
+                kl += wide_allsum(kk);
+                off += 2 * D;
+                continue;
+            }
+            float m1 = -INFINITY, s1 = 0.f, m2 = -INFINITY, s2 = 0.f;
+#pragma unroll 4
+            for (int k = lane; k < nh; k += 64) { wide_push(m1, s1, zt[off + k]); wide_push(m2, s2, zs[off + k]); }
+            float mxt, lset, mxs, lses;
+            wide_finish(m1, s1, mxt, lset);
+            wide_finish(m2, s2, mxs, lses);
+#pragma unroll 4
+            for (int k = lane; k < nh; k += 64)
+                kk += cat_consistency(zt[off + k], zs[off + k], mxt, lset, mxs, lses, sp, gz + off + k);
+            kl += wide_allsum(kk);
+            off += nh;
+        }
+        if (lane == 0) {
+            const float dv = values_s[i * ldv] - values_t[i * ldv];
+            g_values_s[i * ldv] = coeff_value * inv_n * (2.f * dv);
+            acc[0] += kl;
+            acc[1] += dv * dv;
+            acc[2] += 1.0;
+            kl_max = fmaxf(kl_max, kl);
+        }
+    }
+    consistency_epilogue(acc, kl_max, sums);
+}
+
+extern "C" int sf_consistency_loss(const float *params_t, const float *params_s, int ld_params, const float *values_t,
+                                   const float *values_s, int ld_values, const uint8_t *valids, const int32_t *index,
+                                   int64_t offset, int64_t n, int A, int action_kind, const int32_t *head_n,
+                                   int num_heads, float coeff_policy, float coeff_value, const double *moments,
+                                   double *sums, float *g_params_s, float *g_values_s, void *stream) {
+    const char *what = "sf_consistency_loss";
+    SF_REQUIRE(params_t && params_s && values_t && values_s && valids && moments && sums && g_params_s && g_values_s,
+               "%s: null pointer", what);
+    SF_REQUIRE(n >= 0 && A > 0 && offset >= 0, "%s: bad shape n=%lld A=%d offset=%lld", what, (long long)n, A,
+               (long long)offset);
+    SF_REQUIRE(ld_params >= A && ld_values >= 1, "%s: bad strides", what);
+    SF_REQUIRE(action_kind == 0 || (action_kind == 1 && A % 2 == 0), "%s: bad action_kind %d for A=%d", what,
+               action_kind, A);
+    // (comparisons, so that NaN fails too)
+    SF_REQUIRE(coeff_policy >= 0.f && coeff_policy <= 3.402823466e38f && coeff_value >= 0.f && coeff_value <= 3.402823466e38f,
+               "%s: the coefficients must be finite and not negative", what);
+    HeadsDev hd = single_head(A, action_kind);
+    if (head_n || num_heads > 1) {  // the member list, as sf_ppo_loss_heads takes it; every check comes before the memset
+        bool any_box;
+        const int tot = heads_from_host(what, head_n, num_heads, SF_MAX_ACTION_HEADS, hd.head_n, &any_box);
+        if (tot < 0) return SF_ERR_ARG;
+        hd.num_heads = num_heads;
+        if (num_heads == 1)
+            SF_REQUIRE(head_n[0] == (action_kind == 0 ? A : -(A / 2)),
+                       "%s: a one-member list must be Discrete(A) with action_kind 0 or Box(A / 2) with 1", what);
+        else
+            SF_REQUIRE(action_kind == 0, "%s: a head list needs action_kind 0", what);
+        SF_REQUIRE(tot == A, "%s: head sizes sum to %d, A = %d", what, tot, A);
+    }
+    if (n == 0) return SF_OK;
+    const bool wide = A >= WIDE_MIN_A;
+    const int64_t want = wide ? (n + WIDE_ROWS - 1) / WIDE_ROWS : (n + 255) / 256;
+    SF_REQUIRE(want <= 0x7fffffffLL, "%s: n=%lld too large", what, (long long)n);
+    int rc = sf_hip_status(hipMemsetAsync(sums, 0, 4 * sizeof(double), STREAM(stream)), "sf_consistency_loss memset");
+    if (rc) return rc;
+    if (wide)  // 256 CUs x 8 blocks; the rows are grid-strided
+        k_consistency_loss_wide<<<dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, STREAM(stream)>>>(
+            params_t, params_s, ld_params, values_t, values_s, ld_values, valids, index, offset, n, A, hd, coeff_policy,
+            coeff_value, moments, sums, g_params_s, g_values_s);
+    else
+        k_consistency_loss<<<dim3((unsigned)want), dim3(256), 0, STREAM(stream)>>>(
+            params_t, params_s, ld_params, values_t, values_s, ld_values, valids, index, offset, n, A, hd, coeff_policy,
+            coeff_value, moments, sums, g_params_s, g_values_s);
+    return sf_launch_status(what);
+}
+
 __global__ void k_loss_scalars(const double *__restrict__ sums, const double *__restrict__ moments, LossDev h,
                                float *__restrict__ out) {
     if (threadIdx.x || blockIdx.x) return;

@@ -66,6 +66,7 @@ SYMBOLS = [
     "sf_res_conv_wgrad", "sf_res_conv_fwd_norm", "sf_res_conv_wgrad_norm",
     "sf_pixcatch_state_words", "sf_pixcatch_reset", "sf_pixcatch_step",
     "sf_random_shift_gather",
+    "sf_consistency_loss",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -696,6 +697,26 @@ def ppo_loss(params, ld_params, values, ld_values, actions, old_logp, old_params
         _check(load().sf_ppo_loss_heads(*args, _head_array(head_sizes), len(head_sizes), stream()), "sf_ppo_loss_heads")
     else:
         _check(load().sf_ppo_loss(*args, stream()), "sf_ppo_loss")
+
+
+def consistency_loss(params_t, params_s, ld_params, values_t, values_s, ld_values, valids, index, offset, n, A, action_kind,
+                     coeff_policy, coeff_value, mom, sums, g_params_s, g_values_s, head_sizes=None) -> None:
+    """sf_consistency_loss: KL(target || student) + (v_s - v_t)^2 between row i of params_t / values_t
+    and row i of params_s / values_s, i < n — strided column views as ppo_loss takes them, in the learner the two halves of
+    one [2n, ld] heads matrix — with the student's gradient into g_params_s / g_values_s (same strides) and
+    {sum KL, sum dv^2, max KL, n_valid} into sums (device double[4]).  head_sizes: the Tuple's member list (any length up to
+    MAX_ACTION_HEADS), None or one member: the single Discrete(A) / Box(A / 2) of action_kind."""
+    hn = _head_array(head_sizes) if head_sizes and len(head_sizes) > 1 else None
+    key = ("consistency_loss", int(n), int(A)) if _keys_wanted() else None  # (tools/drac_bench.py)
+    with _timed(key):
+        _check(load().sf_consistency_loss(_raw(params_t, "f32", "params_t"), _raw(params_s, "f32", "params_s"),
+                                          int(ld_params), _raw(values_t, "f32", "values_t"),
+                                          _raw(values_s, "f32", "values_s"), int(ld_values), ptr(valids, "u8", "valids"),
+                                          ptr(index, "i32", "index"), i64(offset), i64(n), int(A), int(action_kind), hn,
+                                          len(head_sizes) if hn is not None else 0, f(coeff_policy), f(coeff_value),
+                                          ptr(mom, "f64", "moments"), ptr(sums, "f64", "sums"),
+                                          _raw(g_params_s, "f32", "g_params_s"), _raw(g_values_s, "f32", "g_values_s"),
+                                          stream()), "sf_consistency_loss")
 
 
 def loss_scalars(sums, mom, cfg: sf_loss_cfg, out) -> None:
