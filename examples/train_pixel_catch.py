@@ -11,6 +11,10 @@ into the trajectory slab); `pixel_catch_host` is the same game in NumPy on the h
 
   python -m sample_factory_amd.enjoy  does not know the env: evaluate with
   python examples/train_pixel_catch.py --enjoy --env=pixel_catch --experiment=pixel_catch --max_num_episodes=256
+
+Levels: `--pixel_catch_decoys=6 --pixel_catch_levels=8` trains on the 8 levels [0, 8), each with 6 static decoy balls; the
+flags are saved with the experiment, and `--enjoy ... --pixel_catch_start_level=1000000 --pixel_catch_levels=100000` plays the
+checkpoint on levels it has never seen.
 """
 import os
 import sys

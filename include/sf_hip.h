@@ -521,6 +521,30 @@ int sf_pixcatch_reset(int32_t *state, uint8_t *obs_out, int64_t out_pitch, int N
                       int k, int balls, void *stream);
 int sf_pixcatch_step(int32_t *state, const int32_t *actions, uint8_t *obs_out, int64_t out_pitch, float *rewards,
                      uint8_t *terminated, int N, int env0, uint32_t seed, int H, int W, int k, int balls, void *stream);
+/* Levels: sf_pixcatch_reset_levels / sf_pixcatch_step_levels are the two entry points above plus `decoys` (nd, 0 .. 8),
+ * `levels` (L >= 0) and `start_level` (S).  A level places nd static decoys in the field: bs x bs squares of 255 that never
+ * move.  Levels change the rendered frame only: state words, rewards and flags are those of the game without decoys, and
+ * with decoys = 0 the two entry points ARE sf_pixcatch_reset / sf_pixcatch_step (the same kernel; levels have no effect).
+ *   episode   ep = (state[0] - 1) / balls, from the state the launch writes (the draw index counts the balls drawn)
+ *   level     w = sf_philox4x32_10(counter (ep, 0, 6, 0), key (seed, env0 + e)); level = S + mulhi(w[0], L) for L > 0 (a
+ *             finite set of L levels), S + w[0] for L = 0 (unlimited levels), both mod 2^32
+ *   decoy d   w = sf_philox4x32_10(counter (d, 0, 7, 0), key (0x4C564C53, level)): the square at x = mulhi(w[0], W - bs + 1),
+ *             y = mulhi(w[1], D); its rows end at H - ph - 1 at the latest, above the paddle's.  Neither the seed nor the
+ *             env enters the key: a level looks the same in every run.
+ * Counter lane 2 of the library's Philox streams: 6 is the level of an episode, 7 the decoys of a level (0 .. 5: below).
+ * A pixel is 255 if it lies in the ball or in a decoy of the episode's level, else 128 if it lies in the paddle, else 0;
+ * all k planes show the current episode's decoys.  pixel_catch.py (episode_level, level_decoys, render) is the contract.
+ * The work-group keeps ONE plane of the level's decoys in LDS, as the bytes the frame gets (H W + 16 bytes, rounded up to
+ * dwords, and a dword): the level is drawn once from uniform values, lane d bs + i draws decoy d and writes row i of it
+ * between two barriers, and a store unit ORs the plane's 16 or 4 bytes at its first pixel's index over what it built from
+ * ball and paddle (or over zeros).  A unit that holds nothing but decoys costs one LDS read, whatever their number.
+ * Refused before any launch (SF_ERR_ARG), on top of the refusals above: decoys outside 0 .. 8; levels < 0; decoys > 0 on a
+ * field whose plane exceeds 64 KB of LDS (H W above 65 516 pixels: 255 x 255 runs, 256 x 256 does not). */
+int sf_pixcatch_reset_levels(int32_t *state, uint8_t *obs_out, int64_t out_pitch, int N, int env0, uint32_t seed, int H,
+                             int W, int k, int balls, int decoys, int levels, uint32_t start_level, void *stream);
+int sf_pixcatch_step_levels(int32_t *state, const int32_t *actions, uint8_t *obs_out, int64_t out_pitch, float *rewards,
+                            uint8_t *terminated, int N, int env0, uint32_t seed, int H, int W, int k, int balls, int decoys,
+                            int levels, uint32_t start_level, void *stream);
 
 /* ---- random-shift augmentation of a minibatch's frames (csrc/sf_augment.hip, --augment_random_shift) ---------------
  * The random shift of RAD / DrQ / DrAC — pad every frame by `pad` pixels with edge replication, crop back to H x W at a
@@ -532,7 +556,8 @@ int sf_pixcatch_step(int32_t *state, const int32_t *actions, uint8_t *obs_out, i
  * together.  The draw: w = sf_philox4x32_10(counter (draw_id, 0, 5, 0), key (seed, d / recurrence)), m = 2 pad + 1,
  * dx = (w[0] * m) >> 32, dy = (w[1] * m) >> 32 as 64-bit products: both in [0, 2 pad], one draw per recurrence-long
  * chunk of dataset rows, so that a recurrent state never sees the picture jump inside a BPTT chunk.  Counter lane 2 of the
- * library's Philox streams: 0 .. 3 the samplers and synthetic envs of sf_rl.hip, 4 PixelCatch's balls, 5 this draw.
+ * library's Philox streams: 0 .. 3 the samplers and synthetic envs of sf_rl.hip, 4 PixelCatch's balls, 5 this draw, 6 and 7
+ * PixelCatch's levels and their decoys.
  * sample_factory_amd/envs/frame_ops.py (random_shift_draws, random_shift_frames) is the same arithmetic in NumPy.
  * pad == 0 is the plain indexed gather (no Philox block is computed); with C = H = 1, W = F it makes the dense copy of a
  * vector key.

@@ -10,6 +10,16 @@
 // build their bytes in registers from the rectangles' coordinates, a row end (or a plane end) inside the unit included.
 // The launch is bound by its stores as long as the integer work stays small: building every unit byte by byte took 35.0 us
 // at 4096 x 4 x 84 x 84 where the stores alone take 28; with the zero test and pc_unit16 it takes 27.8 us.
+//
+// Levels (sf_pixcatch_reset_levels / sf_pixcatch_step_levels, template parameter DECOYS): the up to 8 static decoys of the
+// episode's level are the same in all k planes, so the work-group keeps ONE plane of them in LDS, as the bytes the frame
+// gets (255 in a decoy, else 0).  The level is drawn once, from uniform values (one Philox block on the scalar unit); lane
+// d bs + i of the first waves draws decoy d (one block) and writes row i of it, between two barriers, the first of which
+// is the barrier the state already needs.  A store unit then ORs the plane's bytes at its first pixel's index over what it
+// built from ball and paddle: one aligned 16-byte LDS read where planes are multiples of 16 bytes, aligned dwords shifted
+// by bytes elsewhere (bytes HW .. HW + 15 repeat bytes 0 .. 15, for a unit that runs into the next plane).  The background
+// test and the unit builders are those of the game without levels: a unit that holds nothing but decoys costs the LDS read
+// and four ORs, whatever the number of decoys.  DECOYS = false compiles to the kernel without levels: no LDS, one barrier.
 #include "sf_common.h"
 
 #define STREAM(s) reinterpret_cast<hipStream_t>(s)
@@ -20,6 +30,12 @@ constexpr int PC_BLOCK = 256;
 constexpr int PC_MAX_K = 8;
 constexpr int PC_HDR = 4;        // state words before the history: draw index, balls left, vx, vy
 constexpr int PC_MAX_SIDE = 1024;  // px, bx, by are packed into 10 bits each while a frame is rendered
+constexpr int PC_MAX_DECOYS = 8;
+constexpr uint32_t PC_LEVEL_KEY = 0x4C564C53u;  // key word 0 of the decoys' Philox stream: no seed, no env in it
+// counter lane 2 of the library's Philox streams (sf_hip.h): 4 is the ball's draw below, 5 the random shift's
+constexpr uint32_t PC_LANE_LEVEL = 6u;  // the level of an episode
+constexpr uint32_t PC_LANE_DECOY = 7u;  // the decoys of a level
+constexpr int PC_MAX_MAP_BYTES = 64 * 1024;     // the decoy plane has to fit the LDS of one work-group
 
 // The game's constants: fixed integer functions of the field (pixel_catch.geometry is the same arithmetic).
 struct PcGeom {
@@ -53,7 +69,12 @@ struct PcArgs {
     int H, W, HW, k, balls;
     PcGeom g;
     FastDiv dW;
+    int decoys, levels;  // DECOYS kernels only
+    uint32_t start_level;
 };
+
+// dwords of the decoy plane of an H x W field: bytes [0, HW + 16) and the dword behind them that the byte shift reads
+__host__ __device__ inline int pc_map_words(int HW) { return (HW + 16 + 3) / 4 + 1; }
 
 __device__ __forceinline__ uint32_t pc_mulhi(uint32_t word, uint32_t range) { return __umulhi(word, range); }
 
@@ -115,8 +136,9 @@ __device__ __forceinline__ void pc_unit16(uint32_t (&w)[4], uint32_t x, uint32_t
     }
 }
 
-// GENERIC: bytes one by one (fields narrower than 16, 4-byte units, units that straddle a plane end); else pc_unit16
-template <int U, bool GENERIC>
+// GENERIC: bytes one by one (fields narrower than 16, 4-byte units, units that straddle a plane end); else pc_unit16.
+// DECOYS: the levels of sf_pixcatch_*_levels; dynamic LDS of pc_map_words(HW) dwords.
+template <int U, bool GENERIC, bool DECOYS>
 __global__ __launch_bounds__(PC_BLOCK) void k_pixcatch(int32_t *state, const int32_t *actions, uint8_t *obs, int64_t pitch,
                                                        float *rewards, uint8_t *terminated, int N, int env0, uint32_t seed,
                                                        PcArgs a, int reset) {
@@ -187,7 +209,33 @@ __global__ __launch_bounds__(PC_BLOCK) void k_pixcatch(int32_t *state, const int
     for (int j = 0; j < PC_MAX_K; ++j) nh[j] = (fill || j + 1 >= k) ? cur : hist[j + 1 < PC_MAX_K ? j + 1 : j];
     nh[PC_MAX_K] = cur;
 
+    extern __shared__ uint4 pc_plane[];  // DECOYS: the decoys of the episode's level as a plane of bytes, 255 or 0
+    uint32_t *pc_map = reinterpret_cast<uint32_t *>(pc_plane);
+    uint32_t level = 0u;
+    if constexpr (DECOYS) {
+        const int nw = pc_map_words(a.HW);
+        for (int i = threadIdx.x; i < nw; i += PC_BLOCK) pc_map[i] = 0u;
+        const uint32_t ep = (uint32_t)(draw - 1) / (uint32_t)a.balls;  // uniform, as the level is
+        uint32_t r[4];
+        sf_philox4x32_10(ep, 0u, PC_LANE_LEVEL, 0u, seed, (uint32_t)(env0 + e), r);
+        level = a.start_level + (a.levels > 0 ? pc_mulhi(r[0], (uint32_t)a.levels) : r[0]);
+    }
     __syncthreads();  // every lane holds the old state: now it may be replaced
+    if constexpr (DECOYS) {
+        uint8_t *map = reinterpret_cast<uint8_t *>(pc_map);
+        const uint32_t ubs = (uint32_t)a.g.bs;
+        for (uint32_t t = threadIdx.x; t < (uint32_t)a.decoys * ubs; t += PC_BLOCK) {  // lane d bs + i: row i of decoy d
+            const uint32_t d = t / ubs, i = t - d * ubs;
+            uint32_t r[4];
+            sf_philox4x32_10(d, 0u, PC_LANE_DECOY, 0u, PC_LEVEL_KEY, level, r);
+            const uint32_t dx = pc_mulhi(r[0], (uint32_t)(W - a.g.bs + 1)), dy = pc_mulhi(r[1], (uint32_t)a.g.D);
+            const uint32_t q0 = (dy + i) * (uint32_t)W + dx;
+            for (uint32_t q = q0; q < q0 + ubs; ++q) {
+                map[q] = 255;
+                if (q < 16u) map[(uint32_t)a.HW + q] = 255;  // the bytes a unit reads past the plane's end: the next plane's first
+            }
+        }
+    }
     if (threadIdx.x == 0) {
         st[0] = draw; st[1] = left; st[2] = vx; st[3] = vy;
 #pragma unroll
@@ -202,6 +250,8 @@ __global__ __launch_bounds__(PC_BLOCK) void k_pixcatch(int32_t *state, const int
             terminated[e] = (uint8_t)term;
         }
     }
+
+    if constexpr (DECOYS) __syncthreads();  // the decoy plane is complete
 
     // ---- render: plane after plane, a lane per store unit
     uint8_t *row = obs + (int64_t)e * pitch;
@@ -228,6 +278,14 @@ __global__ __launch_bounds__(PC_BLOCK) void k_pixcatch(int32_t *state, const int
                 if constexpr (GENERIC) pc_unit<NW>(w, x0, y0, g0, g1, a);
                 else pc_unit16(w, x0, y0, g0, a);
             }
+            if constexpr (DECOYS && GENERIC) {  // the decoy plane's bytes [L, L + U): aligned dwords, shifted by bytes
+                const uint32_t *m = pc_map + (L >> 2);
+#pragma unroll
+                for (int i = 0; i < NW; ++i) w[i] |= __builtin_amdgcn_alignbyte(m[i + 1], m[i], L & 3u);
+            } else if constexpr (DECOYS) {       // L is a multiple of 16 here
+                const uint4 dv = pc_plane[L >> 4];
+                w[0] |= dv.x; w[1] |= dv.y; w[2] |= dv.z; w[3] |= dv.w;
+            }
             if constexpr (U == 16)
                 *reinterpret_cast<uint4 *>(row + (size_t)p * 16) = make_uint4(w[0], w[1], w[2], w[3]);
             else
@@ -237,7 +295,8 @@ __global__ __launch_bounds__(PC_BLOCK) void k_pixcatch(int32_t *state, const int
 }
 
 int pc_launch(const char *name, int32_t *state, const int32_t *actions, uint8_t *obs, int64_t pitch, float *rewards,
-              uint8_t *terminated, int N, int env0, uint32_t seed, int H, int W, int k, int balls, int reset, void *stream) {
+              uint8_t *terminated, int N, int env0, uint32_t seed, int H, int W, int k, int balls, int reset, void *stream,
+              int decoys = 0, int levels = 0, uint32_t start_level = 0) {
     SF_REQUIRE(state && obs, "%s: null state / obs_out", name);
     SF_REQUIRE(reset || (actions && rewards && terminated), "%s: null actions / rewards / terminated", name);
     SF_REQUIRE(N > 0, "%s: N = %d must be positive", name, N);
@@ -250,15 +309,27 @@ int pc_launch(const char *name, int32_t *state, const int32_t *actions, uint8_t 
     const uintptr_t mis = (uintptr_t)obs | (uintptr_t)pitch | (uintptr_t)bytes;
     SF_REQUIRE((mis & 3) == 0, "%s: obs_out, out_pitch and k H W = %lld must all be multiples of 4 (16 for the wide stores)",
                name, (long long)bytes);
+    SF_REQUIRE(decoys >= 0 && decoys <= PC_MAX_DECOYS, "%s: decoys = %d outside 0 .. %d", name, decoys, PC_MAX_DECOYS);
+    SF_REQUIRE(levels >= 0, "%s: levels = %d must be 0 (unlimited) or positive", name, levels);
+    const size_t lds = decoys > 0 ? (size_t)pc_map_words(H * W) * 4 : 0;
+    SF_REQUIRE(lds <= (size_t)PC_MAX_MAP_BYTES, "%s: with decoys a %d x %d field needs %zu bytes of LDS, above %d",
+               name, H, W, lds, PC_MAX_MAP_BYTES);
     PcArgs a;
     a.H = H; a.W = W; a.HW = H * W; a.k = k; a.balls = balls; a.g = g; a.dW = make_fastdiv((uint32_t)W);
+    a.decoys = decoys; a.levels = levels; a.start_level = start_level;
     const bool wide = (mis & 15) == 0, rows16 = W >= 16 && a.HW % 16 == 0;  // 16-byte units of at most two rows of one plane
     const dim3 grid((unsigned)N), block(PC_BLOCK);
-#define PC_GO(U, G) \
-    k_pixcatch<U, G><<<grid, block, 0, STREAM(stream)>>>(state, actions, obs, pitch, rewards, terminated, N, env0, seed, a, reset)
-    if (wide && rows16) PC_GO(16, false);
-    else if (wide) PC_GO(16, true);
-    else PC_GO(4, true);
+#define PC_GO(U, G, D) \
+    k_pixcatch<U, G, D><<<grid, block, lds, STREAM(stream)>>>(state, actions, obs, pitch, rewards, terminated, N, env0, seed, a, reset)
+#define PC_PICK(D) \
+    do { \
+        if (wide && rows16) PC_GO(16, false, D); \
+        else if (wide) PC_GO(16, true, D); \
+        else PC_GO(4, true, D); \
+    } while (0)
+    if (decoys > 0) PC_PICK(true);
+    else PC_PICK(false);
+#undef PC_PICK
 #undef PC_GO
     return sf_launch_status(name);
 }
@@ -278,4 +349,18 @@ extern "C" int sf_pixcatch_step(int32_t *state, const int32_t *actions, uint8_t 
                                 void *stream) {
     return pc_launch("sf_pixcatch_step", state, actions, obs_out, out_pitch, rewards, terminated, N, env0, seed, H, W, k, balls,
                      0, stream);
+}
+
+extern "C" int sf_pixcatch_reset_levels(int32_t *state, uint8_t *obs_out, int64_t out_pitch, int N, int env0, uint32_t seed,
+                                        int H, int W, int k, int balls, int decoys, int levels, uint32_t start_level,
+                                        void *stream) {
+    return pc_launch("sf_pixcatch_reset_levels", state, nullptr, obs_out, out_pitch, nullptr, nullptr, N, env0, seed, H, W, k,
+                     balls, 1, stream, decoys, levels, start_level);
+}
+
+extern "C" int sf_pixcatch_step_levels(int32_t *state, const int32_t *actions, uint8_t *obs_out, int64_t out_pitch,
+                                       float *rewards, uint8_t *terminated, int N, int env0, uint32_t seed, int H, int W, int k,
+                                       int balls, int decoys, int levels, uint32_t start_level, void *stream) {
+    return pc_launch("sf_pixcatch_step_levels", state, actions, obs_out, out_pitch, rewards, terminated, N, env0, seed, H, W, k,
+                     balls, 0, stream, decoys, levels, start_level);
 }

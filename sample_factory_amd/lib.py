@@ -64,7 +64,8 @@ SYMBOLS = [
     "sf_dp_oneshot_allreduce_f64", "sf_dp_oneshot_status", "sf_dp_oneshot_destroy",
     "sf_res_conv_fwd", "sf_res_pool_fwd", "sf_res_pool_bwd", "sf_res_conv_dgrad", "sf_res_conv_wgrad_workspace",
     "sf_res_conv_wgrad", "sf_res_conv_fwd_norm", "sf_res_conv_wgrad_norm",
-    "sf_pixcatch_state_words", "sf_pixcatch_reset", "sf_pixcatch_step",
+    "sf_pixcatch_state_words", "sf_pixcatch_reset", "sf_pixcatch_step", "sf_pixcatch_reset_levels",
+    "sf_pixcatch_step_levels",
     "sf_random_shift_gather",
     "sf_consistency_loss",
 ]
@@ -1164,6 +1165,28 @@ def pixcatch_step(state, actions, obs_out, rewards, terminated, env0, seed, ball
         _check(load().sf_pixcatch_step(ptr(state, "i32", "state"), ptr(actions, "i32", "actions"), _vp(obs_out), i64(pitch),
                                        ptr(rewards, "f32", "rewards"), ptr(terminated, "u8", "terminated"), N, int(env0),
                                        u32(seed), H, W, k, int(balls), stream()), "sf_pixcatch_step")
+
+
+def pixcatch_reset_levels(state, obs_out, env0, seed, balls, decoys, levels, start_level) -> None:
+    """sf_pixcatch_reset_levels: sf_pixcatch_reset with the `decoys` static decoys of each episode's level in the frame"""
+    N, k, H, W, pitch = _pixcatch_obs("sf_pixcatch_reset_levels", state, obs_out)
+    _check(load().sf_pixcatch_reset_levels(ptr(state, "i32", "state"), _vp(obs_out), i64(pitch), N, int(env0), u32(seed), H, W,
+                                           k, int(balls), int(decoys), int(levels), u32(start_level), stream()),
+           "sf_pixcatch_reset_levels")
+
+
+def pixcatch_step_levels(state, actions, obs_out, rewards, terminated, env0, seed, balls, decoys, levels, start_level) -> None:
+    """sf_pixcatch_step_levels: sf_pixcatch_step with the decoys of the level set [start_level, start_level + levels)"""
+    N, k, H, W, pitch = _pixcatch_obs("sf_pixcatch_step_levels", state, obs_out)
+    for name, x in (("actions", actions), ("rewards", rewards), ("terminated", terminated)):
+        if x is not None and x.numel() != N:
+            raise SfHipError(f"sf_pixcatch_step_levels: {name} has {x.numel()} elements, expected {N}")
+    key = ("pixcatch_step_levels", N, k, H, W) if _keys_wanted() else None
+    with _timed(key):
+        _check(load().sf_pixcatch_step_levels(ptr(state, "i32", "state"), ptr(actions, "i32", "actions"), _vp(obs_out),
+                                              i64(pitch), ptr(rewards, "f32", "rewards"), ptr(terminated, "u8", "terminated"),
+                                              N, int(env0), u32(seed), H, W, k, int(balls), int(decoys), int(levels),
+                                              u32(start_level), stream()), "sf_pixcatch_step_levels")
 
 
 # ---- network kernels (csrc/sf_nn.hip)
