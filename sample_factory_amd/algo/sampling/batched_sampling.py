@@ -20,8 +20,8 @@ import numpy as np
 import torch
 
 from sample_factory_amd import lib
+from sample_factory_amd.algo.sampling.obs_ingest import KeyRoute, ObsIngestPlan
 from sample_factory_amd.algo.sampling.parallel_env import infos_is_active
-from sample_factory_amd.algo.utils.env_info import device_resize_of
 from sample_factory_amd.algo.utils.tensor_dict import TensorDict
 from sample_factory_amd.envs.spaces import action_head_sizes, heads_mixed, is_box, split_tuple_actions
 
@@ -107,44 +107,14 @@ class BatchedVectorEnvRunner:
         self.keep_on, self.keep_row0 = False, 0  # the model keeps the conv activations of this runner's steps (Runner.init)
         if self.masked and self.zero_copy:
             raise NotImplementedError("action masks with a zero-copy (step_into) env")
-        # --device_framestack=k: the env delivers one frame per step; the slab's image keys hold k of them, oldest first.
-        # fs_keys: key -> channels of ONE frame.  The new frame goes into the last slot of obs[:, t + 1], the other slots
-        # are shifted over from obs[:, t] (or refilled where the episode ended) by sf_framestack_step.
-        self.fs_k = int(getattr(cfg, "device_framestack", 1))
-        self.fs_keys = {k: traj["obs"][k].shape[2] // self.fs_k for k in self.obs_keys
-                        if self.fs_k > 1 and traj["obs"][k].dim() == 5}
-        if self.fs_k > 1 and hasattr(env, "step_into"):
-            raise NotImplementedError(f"device_framestack={self.fs_k} with a zero-copy (step_into) env")
-        # --hwc_observations: the env's image keys are [H, W, C].  hwc_keys: key -> ONE device staging
-        # buffer [B, H, W, C] the frame is sent to instead of the slab slot; sf_hwc_to_chw (no frame stack) or
-        # sf_framestack_step_hwc (in place of sf_framestack_step) transposes it into the column.  _hwc_src: where the
-        # newest frame of a key is — the staging buffer, or a device env's own tensor read in place.
-        self.hwc_keys: Dict[str, torch.Tensor] = {}
-        # --device_resize / --device_grayscale: the env delivers native u8 frames, the slab holds them
-        # preprocessed.  rs_keys: key -> ONE device staging buffer [B, native frame] in the env's own layout ([H, W, C]
-        # under --hwc_observations, else [C, H, W]) the frame is sent to by the existing routes; sf_frame_resize follows on
-        # the same stream into _obs_slot(key, t) — the column or the last slot of a stacked one — resizing, grey-scaling
-        # and de-interleaving in one launch: such a key never goes through the transpose kernels.
-        self.rs_keys: Dict[str, torch.Tensor] = {}
-        rs_size, self.rs_interp, self.rs_gray = device_resize_of(cfg)
-        self.rs_hwc = bool(getattr(cfg, "hwc_observations", False))
-        if rs_size is not None or self.rs_gray:
-            if hasattr(env, "step_into"):
-                raise NotImplementedError("device_resize / device_grayscale with a zero-copy (step_into) env")
-            space = env.observation_space
-            for k in self.obs_keys:
-                if traj["obs"][k].dim() == 5:
-                    native = tuple(int(d) for d in (space[k] if hasattr(space, "spaces") else space).shape)
-                    self.rs_keys[k] = torch.empty((self.B,) + native, dtype=torch.uint8, device=dev)
-        if getattr(cfg, "hwc_observations", False):
-            if hasattr(env, "step_into"):
-                raise NotImplementedError("hwc_observations with a zero-copy (step_into) env")
-            for k in self.obs_keys:
-                x = traj["obs"][k]
-                if x.dim() == 5 and k not in self.rs_keys:
-                    self.hwc_keys[k] = torch.empty((self.B, x.shape[3], x.shape[4], x.shape[2] // self.fs_k), dtype=x.dtype,
-                                                   device=dev)
-        self._hwc_src: Dict[str, torch.Tensor] = {}
+        # --hwc_observations / --device_resize / --device_grayscale / --device_framestack: what the
+        # env delivers and what the slab holds, per key, is one plan; routes: key -> the way its frames take into the slab
+        plan = ObsIngestPlan.from_cfg(env.observation_space, cfg, hasattr(env, "step_into"))
+        for k in self.obs_keys:
+            if plan.keys[k].slab_shape != tuple(traj["obs"][k].shape[2:]):
+                raise ValueError(f"observation key {k!r}: the slab holds {tuple(traj['obs'][k].shape[2:])} per step, the env's "
+                                 f"space and the device ingest flags give {plan.keys[k].slab_shape}")
+        self.routes: Dict[str, KeyRoute] = {k: KeyRoute(plan.keys[k], traj["obs"][k]) for k in self.obs_keys}
         # --track_inactive_agents: one persistent byte per agent row, 1 = the env's last info did not say
         # is_active=False.  Step t records policy_id -1 and holds the recurrent state where the byte is 0, then the byte
         # takes what the env reported with step t.  The bytes belong to the runner: they outlive a rollout, set_slab and
@@ -167,7 +137,7 @@ class BatchedVectorEnvRunner:
             first = (o["obs"] if "obs" in o else o[self.obs_keys[0]]) if isinstance(o, dict) else o
             self.host_env = not (isinstance(first, torch.Tensor) and first.is_cuda)
             self._store_obs(o, 0)
-            self._framestack(0, None, None)
+            self._complete_obs(0, None, None)
         self._started = True
 
     # ---- host (CPU) envs: pinned staging, asynchronous H2D straight into the slab slot.  The only
@@ -228,65 +198,18 @@ class BatchedVectorEnvRunner:
             self.ingest_prof["act_wait_s"] = self.ingest_prof.get("act_wait_s", 0.0) + time.perf_counter() - t0
         return stage.numpy()
 
-    def _obs_slot(self, key: str, t: int) -> torch.Tensor:
-        """where the env's observation of `key` goes in slab column t: the column, or — a stacked key — its LAST frame slot
-        (rows stay contiguous blocks at the column's pitch: still one pitched DMA)"""
-        x = self.traj["obs"][key]
-        c1 = self.fs_keys.get(key)
-        return x[:, t] if c1 is None else x[:, t, (self.fs_k - 1) * c1:]
-
-    def _store_key(self, name: str, key: str, src, t: int) -> None:
-        """the env's observation of `key` -> slab column t.  A channel-last key (--hwc_observations) goes to its staging
-        buffer by the same route — pinned double buffer or one DMA from the workers' registered pages; a device env's
-        tensor with contiguous rows is read where it is — and, without a frame stack, sf_hwc_to_chw follows on the same
-        stream; with one, _framestack transposes it inside the stack's launch.  A preprocessed key (--device_resize /
-        --device_grayscale) is staged the same way in its native size and layout and sf_frame_resize writes the slot: the
-        column, or the last slot of a stacked one, which _framestack then completes with the plain sf_framestack_step"""
-        stage = self.rs_keys.get(key)
-        if stage is not None:  # native frame -> staging buffer (or read in place) -> resized / grey into the slab slot
-            if isinstance(src, torch.Tensor) and src.is_cuda and src.shape == stage.shape and src.dtype == stage.dtype and \
-                    src[0].is_contiguous():
-                frame = src
-            else:
-                self._to_device(name, src, stage)
-                frame = stage
-            lib.frame_resize(self._obs_slot(key, t), frame, self.rs_hwc, self.rs_interp, self.rs_gray)
-            return
-        stage = self.hwc_keys.get(key)
-        if stage is None:
-            self._to_device(name, src, self._obs_slot(key, t))
-            return
-        if isinstance(src, torch.Tensor) and src.is_cuda and src.shape == stage.shape and src.dtype == stage.dtype and \
-                src[0].is_contiguous():
-            frame = src
-        else:
-            self._to_device(name, src, stage)
-            frame = stage
-        self._hwc_src[key] = frame
-        if key not in self.fs_keys:
-            lib.hwc_to_chw(self.traj["obs"][key][:, t], frame)
-
     def _store_obs(self, o, t: int) -> None:
-        if self.multi_key:
-            for k in self.obs_keys:
-                self._store_key("obs." + k, k, o[k], t)
-        else:
-            key = "obs" if "obs" in self.traj["obs"] else self.obs_keys[0]
-            self._store_key("obs", key, o["obs"] if isinstance(o, dict) else o, t)
+        """the env's observation -> slab column t, every key along its route (obs_ingest.KeyRoute.store)"""
+        for k, route in self.routes.items():
+            src = o[k] if self.multi_key else (o["obs"] if isinstance(o, dict) else o)
+            route.store(self.traj["obs"][k], "obs." + k if self.multi_key else "obs", src, t, self._to_device)
         if self.masked:
             self._to_device("mask", o["action_mask"], self.traj["obs"]["action_mask"][:, t])
 
-    def _framestack(self, t: int, term, trunc) -> None:
-        """complete the stacked keys of slab column t around the frame _store_obs put into their last slot — or, a
-        channel-last key, left in its staging buffer: one launch per key either way (term / trunc: the device flags of the
-        step that produced the frame; None, None: a reset)"""
-        for k in self.fs_keys:
-            x = self.traj["obs"][k]
-            prev = x[:, t - 1 if t > 0 else 1]
-            if k in self.hwc_keys:
-                lib.framestack_step_hwc(x[:, t], prev, self.fs_k, self._hwc_src[k], term, trunc)
-            else:
-                lib.framestack_step(x[:, t], prev, self.fs_k, None, term, trunc)
+    def _complete_obs(self, t: int, term, trunc) -> None:
+        """complete the stacked keys of slab column t (term / trunc: the step's device flags; None, None: a reset)"""
+        for k, route in self.routes.items():
+            route.complete(self.traj["obs"][k], t, term, trunc)
 
     def policy_version(self) -> float:
         return float(self.policy_versions[self.policy_id].item()) if self.policy_versions is not None else 0.0
@@ -465,8 +388,8 @@ class BatchedVectorEnvRunner:
         """env outputs of step t -> slab (rewards shaped, dones, episode statistics), next-step recurrent state;
         active_in (--track_inactive_agents): the env's is_active report of this step"""
         tr, T, cfg = self.traj, self.T, self.cfg
-        if self.fs_keys:  # (behind the flag transfers: the stack of obs[:, t + 1] needs this step's terminated / truncated)
-            self._framestack(t + 1, term, trunc)
+        # (behind the flag transfers: the stack of obs[:, t + 1] needs this step's terminated / truncated)
+        self._complete_obs(t + 1, term, trunc)
         if self.track_active:  # policy_id[:, t] = -1 where the agent was told to wait, then the bytes take this step's report
             lib.traj_write_env_step_active(rew, term, trunc, T, t, cfg.reward_scale, cfg.reward_clip, self.policy_id,
                                            tr["rewards"], tr["dones"], tr["time_outs"], tr["policy_id"], self.ep_return,

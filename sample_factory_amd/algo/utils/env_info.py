@@ -39,50 +39,6 @@ def extract_env_info(env, cfg) -> EnvInfo:
                    get_default_reward_shaping(env), ENV_INFO_PROTOCOL_VERSION)
 
 
-_framestack_warned = False
-
-
-def with_device_framestack(env_info: EnvInfo, env, cfg) -> EnvInfo:
-    """--device_framestack=k: the EnvInfo the slab, the model and the learner are built from — a copy whose image keys hold
-    k frames (envs/spaces.py stacked_obs_space).  The env's own EnvInfo (the cached / probed one) keeps describing the env.
-    k == 1: `env_info` itself.  Refuses what the device stack cannot serve."""
-    import dataclasses
-
-    from sample_factory_amd.envs.spaces import stacked_obs_space
-    from sample_factory_amd.utils.utils import log
-    global _framestack_warned
-    k = int(getattr(cfg, "device_framestack", 1))
-    stacked = stacked_obs_space(env_info.obs_space, k)  # ValueError: k < 1, or nothing to stack
-    if k == 1:
-        return env_info
-    if hasattr(env, "step_into"):
-        raise NotImplementedError(f"device_framestack={k} with a zero-copy env (step_into writes whole observations into "
-                                  "the slab): stack inside the env, or let it return single frames from step()")
-    if int(getattr(cfg, "env_framestack", 1) or 1) > 1 and not _framestack_warned:
-        _framestack_warned = True
-        log.warning("env_framestack=%d and device_framestack=%d are both set: an env factory that reads env_framestack stacks "
-                    "on its own and the device would stack those stacks; set env_framestack=1 unless the factory ignores it",
-                    int(cfg.env_framestack), k)
-    return dataclasses.replace(env_info, obs_space=stacked)
-
-
-def with_hwc_observations(env_info: EnvInfo, env, cfg) -> EnvInfo:
-    """--hwc_observations: the EnvInfo the slab, the model and the learner are built from — a copy whose image keys are
-    Box(C, H, W) while the env delivers [H, W, C] (envs/spaces.py chw_obs_space).  Applied BEFORE with_device_framestack:
-    the stack then runs along the channel axis of the CHW space.  The env's own EnvInfo (the cached / probed one) keeps
-    describing the env.  Flag off: `env_info` itself.  Refuses what the device transpose cannot serve."""
-    import dataclasses
-
-    from sample_factory_amd.envs.spaces import chw_obs_space
-    if not getattr(cfg, "hwc_observations", False):
-        return env_info
-    chw = chw_obs_space(env_info.obs_space)  # ValueError: nothing to transpose
-    if hasattr(env, "step_into"):
-        raise NotImplementedError("hwc_observations with a zero-copy env (step_into writes whole observations into the "
-                                  "slab): write CHW there, or let the env return its HWC frames from step()")
-    return dataclasses.replace(env_info, obs_space=chw)
-
-
 def device_resize_of(cfg):
     """(OH, OW) | None, interpolation, grayscale as --device_resize / --device_resize_interpolation / --device_grayscale
     say; ValueError for anything but 0 or 2 sizes, sizes below 1, or an unknown filter"""
@@ -97,38 +53,15 @@ def device_resize_of(cfg):
     return ((int(size[0]), int(size[1])) if size else None), interp, gray
 
 
-def with_device_resize(env_info: EnvInfo, env, cfg) -> EnvInfo:
-    """--device_resize H W / --device_grayscale: the EnvInfo the slab, the model and the learner are built from — a copy
-    whose u8 image keys are Box(C', OH, OW) while the env delivers its native frames (envs/spaces.py resized_obs_space).
-    Applied AFTER with_hwc_observations (it acts on the CHW space) and BEFORE with_device_framestack (the preprocessed
-    frames are what gets stacked).  The env's own EnvInfo keeps describing the env.  Flags off: `env_info` itself.  Refuses
-    what the device kernel cannot serve."""
+def with_device_ingest(env_info: EnvInfo, env, cfg) -> EnvInfo:
+    """the EnvInfo the slab, the model and the learner are built from: a copy whose observation space is what the device
+    ingest stages leave in the slab (algo/sampling/obs_ingest.py ObsIngestPlan, which also refuses what they cannot serve).
+    The env's own EnvInfo (the cached / probed one) keeps describing the env.  No stage: `env_info` itself."""
     import dataclasses
 
-    from sample_factory_amd.envs.spaces import framestack_keys, resized_obs_space
-    size, interp, gray = device_resize_of(cfg)
-    if size is None and not gray:
-        return env_info
-    space = env_info.obs_space
-    if size is None:  # grey-scale alone: every image key keeps its own geometry
-        keys = framestack_keys(space)
-        shapes = {tuple(int(d) for d in (space[k] if hasattr(space, "spaces") else space).shape[1:]) for k in keys}
-        if len(shapes) > 1:
-            raise ValueError(f"device_grayscale without device_resize: the image keys {keys} differ in size {sorted(shapes)}; "
-                             "give --device_resize H W")
-        size = next(iter(shapes)) if shapes else (1, 1)
-    resized = resized_obs_space(space, size[0], size[1], gray)  # ValueError: no image key, not u8, grey of C != 3
-    if interp == "area":
-        for k in framestack_keys(space):
-            h, w = (space[k] if hasattr(space, "spaces") else space).shape[1:]
-            if size[0] > h or size[1] > w:
-                raise ValueError(f"device_resize {size[0]} {size[1]} with the area filter enlarges observation key {k!r} "
-                                 f"({h} x {w}): the area filter only shrinks, use --device_resize_interpolation=nearest")
-    if hasattr(env, "step_into"):
-        raise NotImplementedError("device_resize / device_grayscale with a zero-copy env (step_into writes whole "
-                                  "observations into the slab): preprocess inside the env, or let it return its native "
-                                  "frames from step()")
-    return dataclasses.replace(env_info, obs_space=resized)
+    from sample_factory_amd.algo.sampling.obs_ingest import ObsIngestPlan
+    plan = ObsIngestPlan.from_cfg(env_info.obs_space, cfg, hasattr(env, "step_into"))
+    return env_info if plan.identity else dataclasses.replace(env_info, obs_space=plan.slab_obs_space())
 
 
 def env_info_cache_filename(cfg) -> str:

@@ -44,8 +44,7 @@ def load_state_dict(cfg, actor_critic, device) -> dict:
 def enjoy(cfg) -> Tuple[int, float]:
     from sample_factory_amd import lib
     from sample_factory_amd.algo.sampling.batched_sampling import BatchedVectorEnvRunner
-    from sample_factory_amd.algo.utils.env_info import (extract_env_info, with_device_framestack, with_device_resize,
-                                                         with_hwc_observations)
+    from sample_factory_amd.algo.utils.env_info import extract_env_info, with_device_ingest
     from sample_factory_amd.algo.utils.shared_buffers import alloc_trajectory_tensors
     from sample_factory_amd.cfg.arguments import preprocess_cfg
     from sample_factory_amd.envs.env_utils import create_env
@@ -67,10 +66,8 @@ def enjoy(cfg) -> Tuple[int, float]:
         from sample_factory_amd.envs.env_utils import registered_env_factory
         env.close()
         env = ParallelHostEnvs(cfg, cfg.env, registered_env_factory(cfg.env), 1, 1, num_splits=1, inline=True).views[0]
-    # the pipeline the policy was trained behind: channel-last frames transposed, resized / grey-scaled, then stacked, on
-    # the device
-    env_info = with_device_resize(with_hwc_observations(extract_env_info(env, cfg), env, cfg), env, cfg)
-    env_info = with_device_framestack(env_info, env, cfg)
+    # the device ingest stages the policy was trained behind (algo/sampling/obs_ingest.py)
+    env_info = with_device_ingest(extract_env_info(env, cfg), env, cfg)
     if cfg.recurrence == -1:
         preprocess_cfg(cfg, env_info)
     actor_critic = create_actor_critic(cfg, env_info.obs_space, env_info.action_space, dev)

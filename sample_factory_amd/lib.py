@@ -946,6 +946,11 @@ def copy_rows(dst: torch.Tensor, src: torch.Tensor) -> None:
                                i64(rd), stream()), "sf_copy_rows")
 
 
+def _pitch(t: torch.Tensor, rows: int, row_bytes: int) -> int:
+    """bytes from one row (dim 0) of the view t to the next; a one-row view may carry any stride: at least its row"""
+    return int(t.stride(0)) * t.element_size() if rows > 1 else max(int(t.stride(0)) * t.element_size(), int(row_bytes))
+
+
 def framestack_step(next_: torch.Tensor, prev: torch.Tensor, k: int, frame: Optional[torch.Tensor] = None,
                     terminated: Optional[torch.Tensor] = None, truncated: Optional[torch.Tensor] = None) -> None:
     """sf_framestack_step on two columns of an observation slab: next_ / prev are device views [rows, k * C, ...] of one
@@ -967,27 +972,24 @@ def framestack_step(next_: torch.Tensor, prev: torch.Tensor, k: int, frame: Opti
     for name, flags in (("terminated", terminated), ("truncated", truncated)):
         if flags is not None and flags.numel() != rows:
             raise SfHipError(f"framestack_step: {name} must hold one flag per row ({rows}), got {flags.numel()}")
-
-    def pitch(t, rb):  # (a one-row view may carry any stride)
-        return int(t.stride(0)) * es if rows > 1 else max(int(t.stride(0)) * es, rb)
     fptr, fpitch = C.c_void_p(0), 0
     if frame is not None:
         if not frame.is_cuda or frame.dtype != next_.dtype or frame.shape[0] != rows or not frame[0].is_contiguous() or \
                 frame[0].numel() * es != fb:
             raise SfHipError(f"framestack_step: frame must be a device [rows, C, ...] view of {fb} contiguous bytes per "
                              f"row and dtype {next_.dtype}, got {tuple(frame.shape)} {frame.dtype} on {frame.device}")
-        fptr, fpitch = _vp(frame), pitch(frame, fb)
+        fptr, fpitch = _vp(frame), _pitch(frame, rows, fb)
     key = ("framestack_step", rows, int(k), fb) if _keys_wanted() else None  # (tools/framestack_bench.py times it)
     with _timed(key):
-        _check(load().sf_framestack_step(_vp(next_), i64(pitch(next_, row_bytes)), _vp(prev), i64(pitch(prev, row_bytes)),
-                                         fptr, i64(fpitch), i64(fb), int(k), ptr(terminated, "u8", "terminated"),
-                                         ptr(truncated, "u8", "truncated"), rows, stream()), "sf_framestack_step")
+        _check(load().sf_framestack_step(_vp(next_), i64(_pitch(next_, rows, row_bytes)), _vp(prev),
+                                         i64(_pitch(prev, rows, row_bytes)), fptr, i64(fpitch), i64(fb), int(k),
+                                         ptr(terminated, "u8", "terminated"), ptr(truncated, "u8", "truncated"), rows, stream()),
+               "sf_framestack_step")
 
 
 def _hwc_views(what: str, chw: torch.Tensor, frame: torch.Tensor, k: int = 1):
     """argument checks shared by hwc_to_chw and framestack_step_hwc: chw is a device view [rows, k * C, H, W] and frame one
-    [rows, H, W, C] of the same dtype (u8 or f32), rows contiguous blocks on both sides -> (rows, H, W, C, element size,
-    pitch(tensor, row bytes))"""
+    [rows, H, W, C] of the same dtype (u8 or f32), rows contiguous blocks on both sides -> (rows, H, W, C, element size)"""
     if not (chw.is_cuda and frame.is_cuda) or chw.dtype != frame.dtype or chw.dtype not in (torch.uint8, torch.float32):
         raise SfHipError(f"{what}: device views of one dtype (uint8 or float32) required, got {chw.dtype} on {chw.device} "
                          f"and {frame.dtype} on {frame.device}")
@@ -998,23 +1000,20 @@ def _hwc_views(what: str, chw: torch.Tensor, frame: torch.Tensor, k: int = 1):
     rows, es = int(chw.shape[0]), chw.element_size()
     if rows and not (chw[0].is_contiguous() and frame[0].is_contiguous()):
         raise SfHipError(f"{what}: rows must be contiguous blocks (strides {chw.stride()} / {frame.stride()})")
-
-    def pitch(t, rb):  # (a one-row view may carry any stride)
-        return int(t.stride(0)) * es if rows > 1 else max(int(t.stride(0)) * es, rb)
-    return rows, int(frame.shape[1]), int(frame.shape[2]), int(frame.shape[3]), es, pitch
+    return rows, int(frame.shape[1]), int(frame.shape[2]), int(frame.shape[3]), es
 
 
 def hwc_to_chw(dst: torch.Tensor, src: torch.Tensor) -> None:
     """sf_hwc_to_chw: dst [rows, C, H, W] <- src [rows, H, W, C], two device views of one dtype (u8 or f32) whose rows are
     contiguous blocks at any pitch (dst: a slab column obs[:, t]): ONE launch, bit for bit"""
-    rows, H, W, Cn, es, pitch = _hwc_views("hwc_to_chw", dst, src)
+    rows, H, W, Cn, es = _hwc_views("hwc_to_chw", dst, src)
     if rows == 0:
         return
     rb = H * W * Cn * es
     key = ("hwc_to_chw", rows, H, W, Cn, es) if _keys_wanted() else None  # (tools/hwc_frames_bench.py times it)
     with _timed(key):
-        _check(load().sf_hwc_to_chw(_vp(dst), i64(pitch(dst, rb)), _vp(src), i64(pitch(src, rb)), H, W, Cn, es, rows,
-                                    stream()), "sf_hwc_to_chw")
+        _check(load().sf_hwc_to_chw(_vp(dst), i64(_pitch(dst, rows, rb)), _vp(src), i64(_pitch(src, rows, rb)), H, W,
+                                    Cn, es, rows, stream()), "sf_hwc_to_chw")
 
 
 def framestack_step_hwc(next_: torch.Tensor, prev: torch.Tensor, k: int, frame: torch.Tensor,
@@ -1027,7 +1026,7 @@ def framestack_step_hwc(next_: torch.Tensor, prev: torch.Tensor, k: int, frame: 
     if not prev.is_cuda or next_.shape != prev.shape or next_.dtype != prev.dtype:
         raise SfHipError(f"framestack_step_hwc: next / prev must be device views of equal shape and dtype, got "
                          f"{tuple(next_.shape)} {next_.dtype} / {tuple(prev.shape)} {prev.dtype} on {prev.device}")
-    rows, H, W, Cn, es, pitch = _hwc_views("framestack_step_hwc", next_, frame, k)
+    rows, H, W, Cn, es = _hwc_views("framestack_step_hwc", next_, frame, k)
     if rows == 0:
         return
     if not prev[0].is_contiguous():
@@ -1038,10 +1037,10 @@ def framestack_step_hwc(next_: torch.Tensor, prev: torch.Tensor, k: int, frame: 
     fb = H * W * Cn * es
     key = ("framestack_step_hwc", rows, int(k), H, W, Cn, es) if _keys_wanted() else None
     with _timed(key):
-        _check(load().sf_framestack_step_hwc(_vp(next_), i64(pitch(next_, int(k) * fb)), _vp(prev),
-                                             i64(pitch(prev, int(k) * fb)), _vp(frame), i64(pitch(frame, fb)), H, W, Cn, es,
-                                             int(k), ptr(terminated, "u8", "terminated"), ptr(truncated, "u8", "truncated"),
-                                             rows, stream()), "sf_framestack_step_hwc")
+        _check(load().sf_framestack_step_hwc(_vp(next_), i64(_pitch(next_, rows, int(k) * fb)), _vp(prev),
+                                             i64(_pitch(prev, rows, int(k) * fb)), _vp(frame), i64(_pitch(frame, rows, fb)),
+                                             H, W, Cn, es, int(k), ptr(terminated, "u8", "terminated"),
+                                             ptr(truncated, "u8", "truncated"), rows, stream()), "sf_framestack_step_hwc")
 
 
 INTERPOLATIONS = {"nearest": 0, "area": 1}  # sf_frame_resize's interp argument
@@ -1072,14 +1071,11 @@ def frame_resize(dst: torch.Tensor, src: torch.Tensor, src_hwc: bool, interpolat
         return
     if not (dst[0].is_contiguous() and src[0].is_contiguous()):
         raise SfHipError(f"frame_resize: rows must be contiguous blocks (strides {dst.stride()} / {src.stride()})")
-
-    def pitch(t, rb):  # (a one-row view may carry any stride)
-        return int(t.stride(0)) if rows > 1 else max(int(t.stride(0)), rb)
     key = ("frame_resize", rows, H, W, Cn, int(bool(src_hwc)), OH, OW, interpolation, int(bool(grayscale))) \
         if _keys_wanted() else None  # (tools/device_resize_bench.py times it)
     with _timed(key):
-        _check(load().sf_frame_resize(_vp(dst), i64(pitch(dst, int(dst.shape[1]) * OH * OW)), _vp(src),
-                                      i64(pitch(src, H * W * Cn)), H, W, Cn, int(bool(src_hwc)), OH, OW,
+        _check(load().sf_frame_resize(_vp(dst), i64(_pitch(dst, rows, int(dst.shape[1]) * OH * OW)), _vp(src),
+                                      i64(_pitch(src, rows, H * W * Cn)), H, W, Cn, int(bool(src_hwc)), OH, OW,
                                       INTERPOLATIONS[interpolation], int(bool(grayscale)), rows, stream()), "sf_frame_resize")
 
 
@@ -1105,11 +1101,10 @@ def random_shift_gather(dst: torch.Tensor, src: torch.Tensor, n: int, shape, *, 
     if n == 0:
         return
     stride = elems if sample_stride is None else int(sample_stride)
-    dpitch = int(dst.stride(0)) * es if dst.shape[0] > 1 else max(int(dst.stride(0)) * es, elems * es)
     key = ("random_shift_gather", n, Cn, H, W, es, int(pad)) if _keys_wanted() else None  # (tools/augment_shift_bench.py)
     with _timed(key):
-        _check(load().sf_random_shift_gather(_vp(dst), i64(dpitch), _vp(src), i64(stride * es),
-                                             C.c_void_p(0) if index is None else _vp(index), i64(offset), i64(n), int(traj_T),
+        _check(load().sf_random_shift_gather(_vp(dst), i64(_pitch(dst, int(dst.shape[0]), elems * es)), _vp(src),
+                                             i64(stride * es), C.c_void_p(0) if index is None else _vp(index), i64(offset), i64(n), int(traj_T),
                                              Cn, H, W, es, int(pad), int(recurrence), u32(seed), u32(draw_id), stream()),
                "sf_random_shift_gather")
 
@@ -1143,8 +1138,7 @@ def _pixcatch_obs(what: str, state: torch.Tensor, obs_out: torch.Tensor):
         raise SfHipError(f"{what}: rows of obs_out must be contiguous blocks (strides {obs_out.stride()})")
     if state.dim() != 2 or state.shape[0] != N or (1 <= k <= 8 and state.shape[1] != 4 + 3 * k):
         raise SfHipError(f"{what}: state must be int32 [N = {N}, 4 + 3 k = {4 + 3 * k}], got {tuple(state.shape)}")
-    pitch = int(obs_out.stride(0)) if N > 1 else max(int(obs_out.stride(0)), k * H * W)  # (a one-row view: any stride)
-    return N, k, H, W, pitch
+    return N, k, H, W, _pitch(obs_out, N, k * H * W)
 
 
 def pixcatch_reset(state, obs_out, env0, seed, balls) -> None:

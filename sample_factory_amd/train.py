@@ -19,8 +19,7 @@ import torch
 
 from sample_factory_amd.algo.learning.learner import Learner, ParameterServer
 from sample_factory_amd.algo.sampling.batched_sampling import BatchedVectorEnvRunner
-from sample_factory_amd.algo.utils.env_info import (extract_env_info, with_device_framestack, with_device_resize,
-                                                     with_hwc_observations)
+from sample_factory_amd.algo.utils.env_info import extract_env_info, with_device_ingest
 from sample_factory_amd.algo.learning.batcher import Batcher
 from sample_factory_amd.algo.utils.shared_buffers import BufferMgr
 from sample_factory_amd.cfg.arguments import cfg_dict, preprocess_cfg
@@ -249,12 +248,9 @@ class Runner:
                                                            vector_index=e % int(cfg.num_envs_per_worker), env_id=e))
                          for e in range(E)]
         self.env = self.envs[0]
-        # (--hwc_observations: slab, model and learner see Box(C, H, W) for the env's [H, W, C] keys; then --device_framestack:
-        # they see the image keys stacked along the channels; the env keeps delivering single channel-last frames)
-        self.env_info = with_hwc_observations(extract_env_info(self.env, cfg), self.env, cfg)
-        # (--device_resize / --device_grayscale: the image keys at the size and channel count the device preprocesses them to)
-        self.env_info = with_device_resize(self.env_info, self.env, cfg)
-        self.env_info = with_device_framestack(self.env_info, self.env, cfg)
+        # (slab, model and learner see the image keys as the device stages leave them — transposed, resized / grey-scaled,
+        # stacked: algo/sampling/obs_ingest.py; the env keeps delivering its own frames)
+        self.env_info = with_device_ingest(extract_env_info(self.env, cfg), self.env, cfg)
         n = self.env_info.num_agents
         if any(env.num_agents != n for env in self.envs):
             raise ValueError("all env instances must have the same number of agents")

@@ -83,17 +83,17 @@ def test_flags_default_to_off_and_parse():
 
 
 def test_wrong_number_of_sizes_and_unknown_filter_are_refused_at_set_up():
-    from sample_factory_amd.algo.utils.env_info import EnvInfo, device_resize_of, with_device_resize
+    from sample_factory_amd.algo.utils.env_info import EnvInfo, device_resize_of, with_device_ingest
     from sample_factory_amd.cfg.arguments import default_cfg
     info = EnvInfo(spaces.Dict({"obs": spaces.Box(0, 255, (3, 20, 24), np.uint8)}), spaces.Discrete(3), 8)
     env = types.SimpleNamespace()
     for bad in ([84], [84, 84, 3], [1, 2, 3, 4]):
         with pytest.raises(ValueError, match="device_resize"):
-            with_device_resize(info, env, default_cfg(env="x", device_resize=bad))
+            with_device_ingest(info, env, default_cfg(env="x", device_resize=bad))
     with pytest.raises(ValueError, match="at least 1"):
-        with_device_resize(info, env, default_cfg(env="x", device_resize=[0, 8]))
+        with_device_ingest(info, env, default_cfg(env="x", device_resize=[0, 8]))
     with pytest.raises(ValueError, match="device_resize_interpolation"):
-        with_device_resize(info, env, default_cfg(env="x", device_resize=[8, 8], device_resize_interpolation="cubic"))
+        with_device_ingest(info, env, default_cfg(env="x", device_resize=[8, 8], device_resize_interpolation="cubic"))
     assert device_resize_of(default_cfg(env="x")) == (None, "area", False)
     assert device_resize_of(default_cfg(env="x", device_resize=[8, 9], device_grayscale=True)) == ((8, 9), "area", True)
 
@@ -144,36 +144,39 @@ def test_resized_obs_space_changes_the_image_keys_only():
 
 
 def test_env_info_order_with_hwc_and_framestack_and_typed_refusals():
-    from sample_factory_amd.algo.utils.env_info import (EnvInfo, with_device_framestack, with_device_resize,
-                                                        with_hwc_observations)
+    from sample_factory_amd.algo.sampling.obs_ingest import ObsIngestPlan
+    from sample_factory_amd.algo.utils.env_info import EnvInfo, with_device_ingest
     from sample_factory_amd.cfg.arguments import default_cfg
     info = EnvInfo(spaces.Dict({"obs": spaces.Box(0, 255, (90, 64, 3), np.uint8)}), spaces.Discrete(3), 8)
+    chw = EnvInfo(spaces.Dict({"obs": spaces.Box(0, 255, (3, 90, 64), np.uint8)}), spaces.Discrete(3), 8)  # a CHW env
     env = types.SimpleNamespace()
     off = default_cfg(env="x")
-    assert with_device_resize(info, env, off) is info                               # flags off: the same object
+    assert with_device_ingest(info, env, off) is info                               # flags off: the same object
     on = default_cfg(env="x", hwc_observations=True, device_resize=[36, 32], device_grayscale=True, device_framestack=4)
-    chw = with_hwc_observations(info, env, on)
-    out = with_device_resize(chw, env, on)                                          # after hwc ...
-    assert out.obs_space["obs"].shape == (1, 36, 32) and chw.obs_space["obs"].shape == (3, 90, 64)
+    key = ObsIngestPlan.from_cfg(info.obs_space, on, False).keys["obs"]
+    out = with_device_ingest(info, env, on)
+    assert key.hwc and key.native_shape[2:] + key.native_shape[:2] == (3, 90, 64)   # the resize: after hwc ...
+    assert key.frame_shape == (1, 36, 32)
     assert info.obs_space["obs"].shape == (90, 64, 3)                               # the env's own EnvInfo keeps describing it
     assert (out.action_space, out.num_agents, out.frameskip) == (info.action_space, 8, info.frameskip)
-    assert with_device_framestack(out, env, on).obs_space["obs"].shape == (4, 36, 32)   # ... and before the stack
+    assert out.obs_space["obs"].shape == (4, 36, 32) and key.slab_shape == (4, 36, 32)   # ... and before the stack
+    assert (key.hwc, key.resize, key.interp, key.gray, key.k) == (True, (36, 32), "area", True, 4)
     colour = default_cfg(env="x", hwc_observations=True, device_resize=[36, 32], device_resize_interpolation="nearest")
-    assert with_device_resize(chw, env, colour).obs_space["obs"].shape == (3, 36, 32)
+    assert with_device_ingest(info, env, colour).obs_space["obs"].shape == (3, 36, 32)
     alone = default_cfg(env="x", hwc_observations=True, device_grayscale=True)      # grey-scale alone keeps the size
-    assert with_device_resize(chw, env, alone).obs_space["obs"].shape == (1, 90, 64)
+    assert with_device_ingest(info, env, alone).obs_space["obs"].shape == (1, 90, 64)
     up = default_cfg(env="x", device_resize=[100, 64])
     with pytest.raises(ValueError, match="only shrinks"):
-        with_device_resize(chw, env, up)
+        with_device_ingest(chw, env, up)
     up.device_resize_interpolation = "nearest"
-    assert with_device_resize(chw, env, up).obs_space["obs"].shape == (3, 100, 64)
+    assert with_device_ingest(chw, env, up).obs_space["obs"].shape == (3, 100, 64)
     f32 = EnvInfo(spaces.Dict({"obs": spaces.Box(0.0, 1.0, (3, 20, 24), np.float32)}), spaces.Discrete(3), 8)
     with pytest.raises(ValueError, match="'obs'"):
-        with_device_resize(f32, env, default_cfg(env="x", device_resize=[8, 8]))
+        with_device_ingest(f32, env, default_cfg(env="x", device_resize=[8, 8]))
     zero_copy = types.SimpleNamespace(step_into=lambda *a: None)
     with pytest.raises(NotImplementedError, match="step_into"):
-        with_device_resize(chw, zero_copy, on)
-    assert with_device_resize(chw, zero_copy, off) is chw
+        with_device_ingest(info, zero_copy, on)
+    assert with_device_ingest(chw, zero_copy, off) is chw
 
 
 # ------------------------------------------------------------------------------------------------ the NumPy model

@@ -91,23 +91,23 @@ def test_stacked_obs_space_stacks_the_image_keys_only():
 def test_env_info_for_the_engine_is_a_stacked_copy_and_refusals_are_typed():
     import types
 
-    from sample_factory_amd.algo.utils.env_info import EnvInfo, with_device_framestack
+    from sample_factory_amd.algo.utils.env_info import EnvInfo, with_device_ingest
     from sample_factory_amd.cfg.arguments import default_cfg
     info = EnvInfo(spaces.Dict({"obs": spaces.Box(0, 255, (1, 12, 12), np.uint8)}), spaces.Discrete(3), 8)
     env = types.SimpleNamespace()
-    assert with_device_framestack(info, env, default_cfg(env="x")) is info
-    out = with_device_framestack(info, env, default_cfg(env="x", device_framestack=4))
+    assert with_device_ingest(info, env, default_cfg(env="x")) is info
+    out = with_device_ingest(info, env, default_cfg(env="x", device_framestack=4))
     assert out.obs_space["obs"].shape == (4, 12, 12) and info.obs_space["obs"].shape == (1, 12, 12)
     assert (out.action_space, out.num_agents, out.frameskip) == (info.action_space, 8, info.frameskip)
     with pytest.raises(ValueError):
-        with_device_framestack(info, env, default_cfg(env="x", device_framestack=0))
+        with_device_ingest(info, env, default_cfg(env="x", device_framestack=0))
     vec_info = EnvInfo(spaces.Dict({"obs": spaces.Box(-1, 1, (5,), np.float32)}), spaces.Discrete(3), 8)
     with pytest.raises(ValueError):
-        with_device_framestack(vec_info, env, default_cfg(env="x", device_framestack=2))
+        with_device_ingest(vec_info, env, default_cfg(env="x", device_framestack=2))
     zero_copy = types.SimpleNamespace(step_into=lambda *a: None)
     with pytest.raises(NotImplementedError, match="step_into"):
-        with_device_framestack(info, zero_copy, default_cfg(env="x", device_framestack=2))
-    assert with_device_framestack(info, zero_copy, default_cfg(env="x")) is info
+        with_device_ingest(info, zero_copy, default_cfg(env="x", device_framestack=2))
+    assert with_device_ingest(info, zero_copy, default_cfg(env="x")) is info
 
 
 def test_flag_defaults_to_one_and_parses():

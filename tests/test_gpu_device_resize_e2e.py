@@ -111,6 +111,16 @@ def _cfg(on: bool, hwc=True, device_resize=(), device_resize_interpolation="area
     return default_cfg(**base)
 
 
+def _preprocessed(sampler):
+    """the keys whose route goes through sf_frame_resize"""
+    return [k for k, r in sampler.routes.items() if r.key.resize is not None]
+
+
+def _stacked(sampler):
+    """key -> channels of one frame, for the keys the device stacks"""
+    return {k: r.key.frame_shape[0] for k, r in sampler.routes.items() if r.key.k > 1}
+
+
 def _snapshot(rows):
     snap = {f: rows[f].cpu().numpy().copy() for f in FIELDS}
     snap["values"] = rows["values"][:, :T].cpu().numpy().copy()
@@ -163,8 +173,9 @@ def test_grey_area_stacked_run_on_native_hwc_frames_equals_the_host_preprocessed
     assert ra.env.observation_space["obs"].shape == NATIVE and rb.env.observation_space["obs"].shape == (1,) + OUT
     assert ra.env_info.obs_space["obs"].shape == rb.env_info.obs_space["obs"].shape == (K,) + OUT
     sm = ra.sampler
-    assert list(sm.rs_keys) == ["obs"] and sm.rs_keys["obs"].shape == (N,) + NATIVE and not rb.sampler.rs_keys
-    assert not sm.hwc_keys and sm.host_env and sm.fs_keys == {"obs": 1}   # the resize launch reads HWC itself
+    assert _preprocessed(sm) == ["obs"] and sm.routes["obs"].stage.shape == (N,) + NATIVE and not _preprocessed(rb.sampler)
+    assert sm.routes["obs"].key.hwc and not [k for k, r in sm.routes.items() if r.key.hwc and r.key.resize is None]
+    assert sm.host_env and _stacked(sm) == {"obs": 1}                      # the resize launch reads HWC itself
     for r, (sa, sb) in enumerate(zip(a, b)):
         _same(sa[0], sb[0], f"rollout {r}")
     want = _expected_last_frames(range(N), 2 * T, "area", True)
@@ -183,7 +194,8 @@ def test_colour_nearest_run_on_native_chw_frames_without_a_stack(tmp_path):
     a, _, pa, ra = run(True, train_dir=str(tmp_path / "dev"), **COLOUR_NEAREST)
     b, _, pb, rb = run(False, train_dir=str(tmp_path / "host"), **COLOUR_NEAREST)
     assert ra.env.observation_space["obs"].shape == (3, 90, 64) and ra.env_info.obs_space["obs"].shape == (3,) + OUT
-    assert ra.sampler.rs_keys["obs"].shape == (N, 3, 90, 64) and not ra.sampler.fs_keys and not ra.sampler.rs_hwc
+    assert ra.sampler.routes["obs"].stage.shape == (N, 3, 90, 64) and not _stacked(ra.sampler)
+    assert _preprocessed(ra.sampler) == ["obs"] and not ra.sampler.routes["obs"].key.hwc
     for r, (sa, sb) in enumerate(zip(a, b)):
         _same(sa[0], sb[0], f"rollout {r}")
     want = _expected_last_frames(range(N), 2 * T, "nearest", False)
@@ -232,9 +244,9 @@ def test_env_worker_processes_two_splits_sync(tmp_path):
     the staging buffer of their split"""
     a, _, pa, ra = run(True, train_dir=str(tmp_path / "dev"), **_workers(**GRAY_STACK))
     b, _, pb, rb = run(False, train_dir=str(tmp_path / "host"), **_workers(**GRAY_STACK))
-    assert len(ra.samplers) == 2 and all(s.async_env and s.host_env and list(s.rs_keys) == ["obs"] for s in ra.samplers)
+    assert len(ra.samplers) == 2 and all(s.async_env and s.host_env and _preprocessed(s) == ["obs"] for s in ra.samplers)
     assert ra.samplers[0].env.observation_space["obs"].shape == NATIVE
-    assert all(s.rs_keys["obs"].shape == (W * n,) + NATIVE for s in ra.samplers)
+    assert all(s.routes["obs"].stage.shape == (W * n,) + NATIVE for s in ra.samplers)
     for r, (sa, sb) in enumerate(zip(a, b)):
         for split in range(2):
             _same(sa[split], sb[split], f"rollout {r} split {split}")

@@ -55,6 +55,16 @@ def make_dict_env(full_env_name, cfg=None, env_config=None, render_mode=None):
     return HostFrameDictEnv(make_host_frame_env(full_env_name, cfg, env_config, render_mode))
 
 
+def _transposed(sampler):
+    """the keys whose route goes through the transpose kernels"""
+    return [k for k, r in sampler.routes.items() if r.key.hwc and r.key.resize is None]
+
+
+def _stacked(sampler):
+    """key -> channels of one frame, for the keys the device stacks"""
+    return {k: r.key.frame_shape[0] for k, r in sampler.routes.items() if r.key.k > 1}
+
+
 def _cfg(hwc: bool, **kw):
     """hwc: the env serves channel-last frames AND the engine is told so; off: the channel-first env, the parent's path"""
     from sample_factory_amd.cfg.arguments import default_cfg
@@ -121,8 +131,9 @@ def test_run_on_the_channel_last_env_equals_the_run_on_the_channel_first_env(k, 
     assert ra.env.observation_space["obs"].shape == SHAPE[1:] + SHAPE[:1] and rb.env.observation_space["obs"].shape == SHAPE
     assert ra.env_info.obs_space["obs"].shape == rb.env_info.obs_space["obs"].shape == (k * SHAPE[0],) + SHAPE[1:]
     sm = ra.sampler
-    assert list(sm.hwc_keys) == ["obs"] and sm.hwc_keys["obs"].shape == (N,) + SHAPE[1:] + SHAPE[:1] and not rb.sampler.hwc_keys
-    assert sm.host_env and sm.fs_keys == ({"obs": SHAPE[0]} if k > 1 else {})
+    assert _transposed(sm) == ["obs"] and sm.routes["obs"].stage.shape == (N,) + SHAPE[1:] + SHAPE[:1]
+    assert not _transposed(rb.sampler)
+    assert sm.host_env and _stacked(sm) == ({"obs": SHAPE[0]} if k > 1 else {})
     for r, (sa, sb) in enumerate(zip(a, b)):
         _same(sa[0], sb[0], f"rollout {r}")
     # the frames are the ring's (k = 1: column t of rollout r is ring slot (r T + t) % 4; stacked: its last C planes)
@@ -163,7 +174,7 @@ def test_env_worker_processes_two_splits_sync(tmp_path):
     into the staging buffer of their split"""
     a, _, pa, ra = run(True, device_framestack=K, train_dir=str(tmp_path / "hwc"), **_workers())
     b, _, pb, rb = run(False, device_framestack=K, train_dir=str(tmp_path / "chw"), **_workers())
-    assert len(ra.samplers) == 2 and all(s.async_env and s.host_env and list(s.hwc_keys) == ["obs"] for s in ra.samplers)
+    assert len(ra.samplers) == 2 and all(s.async_env and s.host_env and _transposed(s) == ["obs"] for s in ra.samplers)
     # the workers' pages hold [rows, H, W, C] as the env's own space says: where the runtime registered them, the DMA into
     # the staging buffer reads them in place, no host copy touches a frame
     assert all(bool(s._direct_ok.get("obs")) == reg for s, reg in zip(ra.samplers, ra.pages_were_registered))
@@ -216,7 +227,7 @@ def test_env_worker_processes_async(threaded):
 def test_dict_env_transposes_the_image_key_only(k):
     a, _, pa, ra = run(True, env="hwc_host_frames_dict", device_framestack=k)
     b, _, pb, rb = run(False, env="hwc_host_frames_dict", device_framestack=k)
-    assert ra.sampler.multi_key and list(ra.sampler.hwc_keys) == ["obs"]
+    assert ra.sampler.multi_key and _transposed(ra.sampler) == ["obs"]
     assert ra.env_info.obs_space["obs"].shape == (k * SHAPE[0],) + SHAPE[1:] and ra.env_info.obs_space["vec"].shape == (3,)
     assert ra.env.observation_space["obs"].shape == SHAPE[1:] + SHAPE[:1]
     for r, (sa, sb) in enumerate(zip(a, b)):
@@ -271,9 +282,9 @@ def test_device_tensor_env_is_read_in_place_when_its_rows_are_contiguous(k, layo
     a, _, pa, ra = run(True, env="hwc_device_frames", device_framestack=k, hwc_test_layout=layout)
     b, _, pb, rb = run(False, env="hwc_device_frames", device_framestack=k, hwc_test_layout="tight")
     sm = ra.sampler
-    assert not sm.host_env and not sm.zero_copy and list(sm.hwc_keys) == ["obs"]
-    in_place = sm._hwc_src["obs"].data_ptr() == ra.env.out.data_ptr()
-    assert in_place == (layout != "strided") and (in_place or sm._hwc_src["obs"] is sm.hwc_keys["obs"])
+    assert not sm.host_env and not sm.zero_copy and _transposed(sm) == ["obs"]
+    in_place = sm.routes["obs"].frame.data_ptr() == ra.env.out.data_ptr()
+    assert in_place == (layout != "strided") and (in_place or sm.routes["obs"].frame is sm.routes["obs"].stage)
     for r, (sa, sb) in enumerate(zip(a, b)):
         _same(sa[0], sb[0], f"rollout {r}")
     assert torch.equal(pa, pb)

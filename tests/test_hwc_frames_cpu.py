@@ -108,23 +108,27 @@ def test_the_frame_stack_composes_along_the_channels_of_the_chw_space():
 
 
 def test_env_info_for_the_engine_is_a_chw_copy_and_refusals_are_typed():
-    from sample_factory_amd.algo.utils.env_info import EnvInfo, with_device_framestack, with_hwc_observations
+    from sample_factory_amd.algo.sampling.obs_ingest import ObsIngestPlan
+    from sample_factory_amd.algo.utils.env_info import EnvInfo, with_device_ingest
     from sample_factory_amd.cfg.arguments import default_cfg
     info = EnvInfo(spaces.Dict({"obs": spaces.Box(0, 255, (20, 24, 3), np.uint8)}), spaces.Discrete(3), 8)
     env = types.SimpleNamespace()
-    assert with_hwc_observations(info, env, default_cfg(env="x")) is info
+    assert with_device_ingest(info, env, default_cfg(env="x")) is info
+    alone = with_device_ingest(info, env, default_cfg(env="x", hwc_observations=True))
+    assert alone.obs_space["obs"].shape == (3, 20, 24) and info.obs_space["obs"].shape == (20, 24, 3)
     on = default_cfg(env="x", hwc_observations=True, device_framestack=4)
-    out = with_hwc_observations(info, env, on)
-    assert out.obs_space["obs"].shape == (3, 20, 24) and info.obs_space["obs"].shape == (20, 24, 3)
+    out = with_device_ingest(info, env, on)
+    key = ObsIngestPlan.from_cfg(info.obs_space, on, False).keys["obs"]
+    assert key.hwc and key.native_shape == (20, 24, 3) and key.frame_shape == (3, 20, 24)   # one frame, transposed
     assert (out.action_space, out.num_agents, out.frameskip) == (info.action_space, 8, info.frameskip)
-    assert with_device_framestack(out, env, on).obs_space["obs"].shape == (12, 20, 24)  # applied before the stack
+    assert out.obs_space["obs"].shape == (12, 20, 24) and key.slab_shape == (12, 20, 24)  # transposed before the stack
     vec_info = EnvInfo(spaces.Dict({"obs": spaces.Box(-1, 1, (5,), np.float32)}), spaces.Discrete(3), 8)
     with pytest.raises(ValueError, match="three dimensions"):
-        with_hwc_observations(vec_info, env, on)
+        with_device_ingest(vec_info, env, on)
     zero_copy = types.SimpleNamespace(step_into=lambda *a: None)
     with pytest.raises(NotImplementedError, match="step_into"):
-        with_hwc_observations(info, zero_copy, on)
-    assert with_hwc_observations(info, zero_copy, default_cfg(env="x")) is info
+        with_device_ingest(info, zero_copy, on)
+    assert with_device_ingest(info, zero_copy, default_cfg(env="x")) is info
 
 
 def test_flag_defaults_to_off_and_parses():
