@@ -557,7 +557,7 @@ int sf_pixcatch_step_levels(int32_t *state, const int32_t *actions, uint8_t *obs
  * dx = (w[0] * m) >> 32, dy = (w[1] * m) >> 32 as 64-bit products: both in [0, 2 pad], one draw per recurrence-long
  * chunk of dataset rows, so that a recurrent state never sees the picture jump inside a BPTT chunk.  Counter lane 2 of the
  * library's Philox streams: 0 .. 3 the samplers and synthetic envs of sf_rl.hip, 4 PixelCatch's balls, 5 this draw, 6 and 7
- * PixelCatch's levels and their decoys.
+ * PixelCatch's levels and their decoys, 8 .. 10 the cutout, the intensity and the op draw of sf_augment_gather (below).
  * sample_factory_amd/envs/frame_ops.py (random_shift_draws, random_shift_frames) is the same arithmetic in NumPy.
  * pad == 0 is the plain indexed gather (no Philox block is computed); with C = H = 1, W = F it makes the dense copy of a
  * vector key.
@@ -576,6 +576,31 @@ int sf_pixcatch_step_levels(int32_t *state, const int32_t *actions, uint8_t *obs
 int sf_random_shift_gather(void *dst, int64_t dst_sample_pitch, const void *src, int64_t src_sample_pitch,
                            const int32_t *index, int64_t offset, int64_t n, int traj_T, int C, int H, int W, int elem_bytes,
                            int pad, int recurrence, uint32_t seed, uint32_t draw_id, void *stream);
+
+/* ---- cutout and intensity behind the shift, in the same launch (--augment_cutout, --augment_intensity) -------------
+ * sf_augment_gather is sf_random_shift_gather — the same addressing, draws, alignment rules and launch shape — with two
+ * more per-sample transformations applied to every output dword in registers before it is stored, in ONE fixed order:
+ * shift, then intensity, then cutout.  All planes of a sample are transformed alike.  With mulhi(a, m) = (a * m) >> 32 as
+ * a 64-bit product and w = sf_philox4x32_10(counter (draw_id, 0, LANE, 0), key (seed, d / recurrence)):
+ *   cutout     LANE = 8 (AUG_LANE_CUTOUT), on when cut_max > 0: ch = lo_h + mulhi(w[0], hi_h - lo_h + 1) with
+ *              lo_h = min(cut_min, H), hi_h = min(cut_max, H); cw the same from w[1] and W; y0 = mulhi(w[2], H - ch + 1),
+ *              x0 = mulhi(w[3], W - cw + 1).  out[c][y0 .. y0 + ch)[x0 .. x0 + cw) = fill in OUTPUT coordinates: the
+ *              rectangle always lies inside the frame and may be all of it.  fill = 0 (0.0f) with cut_fill = 0, the
+ *              sample's byte w'[1] >> 24 of the LANE = 9 block with cut_fill = 1 (u8 only).  The fill is not scaled.
+ *   intensity  LANE = 9 (AUG_LANE_INTENSITY), on when intensity = A > 0: s = 256 - A + mulhi(w[0], 2 A + 1), in
+ *              [256 - A, 256 + A].  u8: min(255, (x * s + 128) >> 8); f32: x * (float)(s / 256), ONE rounded multiply.
+ *   LANE = 10  (AUGMENT_LANE_SELECT) is drawn on the host only: which op an SGD step applies under --augment_mix one.
+ * sample_factory_amd/envs/frame_ops.py (cutout_draws, intensity_draws, augment_frames, augment_op_of_step) is the same
+ * arithmetic in NumPy, bit for bit.  A Philox block is computed per sample only for the ops that are on; with cut_max = 0
+ * and intensity = 0 the launch IS sf_random_shift_gather's.  A dword inside one row takes the scale and a byte select
+ * between itself and the fill (the selector from its row and its columns against the rectangle: interior, edge and outside
+ * dwords run the same instructions); bytes gathered singly take the same arithmetic per pixel.
+ * Refused before any launch (SF_ERR_ARG): everything sf_random_shift_gather refuses; cut_max outside 0 .. 65535; with
+ * cut_max > 0, cut_min < 1 or cut_min > cut_max; cut_fill not 0 or 1; cut_fill = 1 with elem_bytes = 4; intensity outside
+ * 0 .. 255.  n == 0: SF_OK, nothing is launched. */
+int sf_augment_gather(void *dst, int64_t dst_sample_pitch, const void *src, int64_t src_sample_pitch, const int32_t *index,
+                      int64_t offset, int64_t n, int traj_T, int C, int H, int W, int elem_bytes, int pad, int cut_min,
+                      int cut_max, int cut_fill, int intensity, int recurrence, uint32_t seed, uint32_t draw_id, void *stream);
 
 /* ---- K2/K3/K8/K9/K15/K18: actor-critic network (fp32 MFMA) -------------------------------------------------------
  * model/encoder.py:90-150 (conv head + MLP), model/actor_critic.py:160-195 (critic_linear + distribution_linear),

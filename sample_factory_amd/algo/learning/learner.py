@@ -34,8 +34,8 @@ import torch
 from sample_factory_amd import lib
 from sample_factory_amd.algo.learning.dp import ReplicaGroup
 from sample_factory_amd.algo.utils.tensor_dict import TensorDict
-from sample_factory_amd.cfg.arguments import augment_consistency_coeff
-from sample_factory_amd.envs.frame_ops import random_shift_seed
+from sample_factory_amd.cfg.arguments import augment_consistency_coeff, augment_ops
+from sample_factory_amd.envs.frame_ops import augment_op_of_step, random_shift_seed
 from sample_factory_amd.envs.spaces import (action_head_sizes, calc_num_action_parameters, calc_num_actions, is_box,
                                              is_discrete)
 from sample_factory_amd.model.actor_critic import ActorCritic
@@ -180,8 +180,9 @@ class Learner:
             raise NotImplementedError(f"{cfg.exploration_loss} not supported!")
         self._loss_mask_on = self._mask_in_loss(cfg, self.env_info)
         # DrAC: alpha of the consistency loss between the clean and the shifted half of a 2n-row pass, 0 =
-        # off; refused here, before anything is launched: negative / non-finite, without the shift, under the loss mask
+        # off; refused here, before anything is launched: negative / non-finite, without an augmentation, under the loss mask
         self._cons_coeff = augment_consistency_coeff(cfg)
+        augment_ops(cfg)  # (bad values of the augmentation flags: ValueError)
         if cfg.optimizer not in ("adam", "lamb"):
             raise RuntimeError(f"Unknown optimizer {cfg.optimizer}")  # learner.py:228-230
         if cfg.seed is not None:
@@ -198,6 +199,8 @@ class Learner:
                                                 all_reduce=ar)
         self.actor_critic.train()
         self._shift_pad = self._augment_pad(cfg, self.actor_critic, self.env_info.obs_space)
+        # cutout / intensity: the resolved flags when one of them is on, else None: the shift alone, or nothing
+        self._aug_ops = self._augment_plan(cfg, self.actor_critic, self.env_info.obs_space)
         # the Philox key of the shifts: replicas of a data-parallel group draw differently (envs/frame_ops.py)
         self._shift_seed = random_shift_seed(cfg.seed, self.policy_id, self.group.rank if self.group is not None else 0)
         if self.dp:  # identical initial weights on every replica
@@ -260,16 +263,59 @@ class Learner:
             raise ValueError(f"augment_random_shift={P}: the observation has no image key [C, H, W] to shift")
         return P
 
+    @staticmethod
+    def _augment_plan(cfg, actor_critic, obs_space):
+        """cfg.augment_cutout / augment_intensity: the flags as cfg/arguments.py's augment_ops resolves them
+        when one of the two is on, None otherwise (the shift alone keeps its own launch: _augment_pad).  Refused like the
+        shift: a network that runs in torch, a model without an image key; and augment_cutout_fill=random (one byte per
+        sample) with a float32 image key"""
+        ops = augment_ops(cfg)
+        if not (ops.cutout or ops.intensity):
+            return None
+        from sample_factory_amd.model.torch_policy import TorchPolicyAdapter
+        if isinstance(actor_critic, TorchPolicyAdapter):
+            raise NotImplementedError("augment_cutout / augment_intensity with a network that runs in torch (a user-registered "
+                                      "model or a configuration the native kernels do not take): only the native models augment")
+        keys = getattr(actor_critic, "obs_keys", None) or ["obs"]
+        spaces_ = getattr(obs_space, "spaces", None) or {"obs": obs_space}
+        images = [k for k in keys if k in spaces_ and len(spaces_[k].shape) == 3]
+        if not images:
+            raise ValueError("augment_cutout / augment_intensity: the observation has no image key [C, H, W] to augment")
+        if ops.cutout and ops.cutout_fill == "random":
+            for k in images:
+                if np.dtype(spaces_[k].dtype) != np.uint8:
+                    raise ValueError(f"augment_cutout_fill=random is one byte per sample: image key {k!r} is "
+                                     f"{np.dtype(spaces_[k].dtype)}, not uint8 (use augment_cutout_fill=zero)")
+        return ops
+
+    def _augments(self) -> bool:
+        return getattr(self, "_shift_pad", 0) > 0 or getattr(self, "_aug_ops", None) is not None
+
+    def _step_augmentation(self):
+        """the parameters of lib.augment_gather for the SGD step about to run, or None when the shift alone is on (its own
+        launch).  augment_mix=one: the step's op is drawn from its draw id and the others' parameters are zeroed"""
+        ops = getattr(self, "_aug_ops", None)
+        if ops is None:
+            return None
+        on = set(ops.enabled)
+        if ops.mix == "one":
+            on = {augment_op_of_step(self._shift_seed, self.train_step, ops.enabled)}
+        return dict(pad=ops.pad if "shift" in on else 0, cutout=ops.cutout if "cutout" in on else (),
+                    cutout_fill=ops.cutout_fill, intensity=ops.intensity if "intensity" in on else 0)
+
     def _shifted_minibatch(self, buff: AttrDict, index, offset: int, n: int):
-        """cfg.augment_random_shift: the minibatch's frames of every observation key, gathered through (index | offset, T)
-        into dense per-key buffers [batch_size, obs_elems] — image keys shifted by this SGD step's draws (draw_id =
-        train_step as it stands before the step, one draw per recurrence-long chunk), other keys copied (shift 0).
+        """cfg.augment_random_shift / augment_cutout / augment_intensity: the minibatch's frames of every observation key,
+        gathered through (index | offset, T) into dense per-key buffers [batch_size, obs_elems] — image keys augmented by
+        this SGD step's draws (draw_id = train_step as it stands before the step, one draw per recurrence-long chunk), other
+        keys copied (shift 0).  The shift alone goes through lib.random_shift_gather, anything more through
+        lib.augment_gather with the step's parameters (_step_augmentation): one launch per key either way.
         Returns what stands for buff.obs in forward_heads / backward: dense row i IS dataset row index[i] | offset + i.
         cfg.augment_consistency_coeff > 0: the buffers hold 2n rows — rows [0, n) the plain gather
-        (pad 0), rows [n, 2n) the same dataset rows under the draws above; row n + i is the shifted twin of row i."""
+        (pad 0), rows [n, 2n) the same dataset rows under the draws above; row n + i is the augmented twin of row i."""
         cfg, ac = self.cfg, self.actor_critic
         keyed = isinstance(buff.obs, dict)
         twin = getattr(self, "_cons_coeff", 0.0) > 0.0
+        step_ops = self._step_augmentation()
         out = {}
         for k, leaf in (buff.obs.items() if keyed else [("obs", buff.obs)]):
             shape = tuple(int(v) for v in leaf.shape[2:])  # the slab leaf is [E, T + 1, ...]
@@ -281,8 +327,11 @@ class Learner:
                           seed=self._shift_seed, draw_id=self.train_step)
             if twin:
                 lib.random_shift_gather(dense[:n], leaf, n, shape if image else (1, 1, elems), pad=0, **gather)
-            lib.random_shift_gather(dense[n:2 * n] if twin else dense, leaf, n, shape if image else (1, 1, elems),
-                                    pad=self._shift_pad if image else 0, **gather)
+            if image and step_ops is not None:
+                lib.augment_gather(dense[n:2 * n] if twin else dense, leaf, n, shape, **step_ops, **gather)
+            else:
+                lib.random_shift_gather(dense[n:2 * n] if twin else dense, leaf, n, shape if image else (1, 1, elems),
+                                        pad=self._shift_pad if image else 0, **gather)
             out[k] = dense[:2 * n if twin else n]
         return out if keyed else out["obs"]
 
@@ -590,7 +639,7 @@ class Learner:
         A = self.num_action_params
         # DrAC: the network runs ONCE on m = 2n rows — [0, n) the clean frames, [n, 2n) their shifted twins;
         # everything that reads the dataset below (V-trace, moments, the PPO loss, the summaries) sees rows [0, n) only
-        alpha = getattr(self, "_cons_coeff", 0.0) if getattr(self, "_shift_pad", 0) > 0 else 0.0
+        alpha = getattr(self, "_cons_coeff", 0.0) if self._augments() else 0.0
         m = 2 * n if alpha > 0.0 else n
         rnn = None
         if cfg.use_rnn:  # learner.py:557-569: chunk-start states, done-or-invalid boundaries (masked-loop BPTT)
@@ -609,11 +658,13 @@ class Learner:
         # where the network reads its frames: the slab through (index | offset, T), or — cfg.augment_random_shift — this
         # step's dense shifted batch, row i of which pairs with dataset row index[i] | offset + i of everything else below
         frames = (buff.obs, dict(index=index, offset=offset, traj_T=buff.T))
-        if getattr(self, "_shift_pad", 0) > 0:
+        if self._augments():
             frames = (self._shifted_minibatch(buff, index, offset, n), dict(index=None, offset=0, traj_T=0))
             if first_of == (0, 0):
                 self.reuse_stats["plain"] += 1
-                self.reuse_stats["last_prefix"], self.reuse_stats["last_reason"] = 0, "augment_random_shift: the frames are shifted"
+                why = "augment_random_shift: the frames are shifted" if getattr(self, "_aug_ops", None) is None else \
+                    "augment_cutout / augment_intensity: the frames are augmented"
+                self.reuse_stats["last_prefix"], self.reuse_stats["last_reason"] = 0, why
         elif first_of == (0, 0):
             # the first minibatch of the first epoch, still on the rollout's weights: the conv activations the rollout kept
             # for exactly these rows stand in for conv1..conv3 (ActorCritic.kept_resume holds the guard); reuse_stats counts

@@ -19,7 +19,7 @@ SOURCES = [
     ("sf_resnet.hip", ["-ffp-contract=off"]),  # resnet_impala: explicit fmaf in the dot products, torch's order elsewhere
     ("sf_ingest.hip", []),                  # observation ingest: the device frame stack, the HWC transpose, resize / grey-scale
     ("sf_pixcatch.hip", []),                # PixelCatch: the device-resident pixel game (step + render in one launch)
-    ("sf_augment.hip", []),                 # training-time augmentation: the random-shift gather of a minibatch's frames
+    ("sf_augment.hip", []),                 # training-time augmentation: the shift / intensity / cutout gather of a minibatch's frames
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
           f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}"]

@@ -107,27 +107,65 @@ ENGINE_FLAGS = [
     #                                          to P pixels (pad P with edge replication, crop back: RAD / DrQ), gathered on
     #                                          the device in one launch (sf_random_shift_gather); rollouts,
     #                                          bootstrap values and enjoy never augment; 0 = off, outside 0 .. 255 is refused
-    ("augment_consistency_coeff", float, 0.0),  # alpha > 0 (needs augment_random_shift > 0): DrAC.  The PPO loss stays on
+    ("augment_consistency_coeff", float, 0.0),  # alpha > 0 (needs an augmentation: augment_random_shift > 0, augment_cutout
+    #                                          or augment_intensity): DrAC.  The PPO loss stays on
     #                                          the clean frames; alpha * (KL(clean || shifted) + (v_shifted - v_clean)^2)
-    #                                          is added on the shifted twin of every row, one 2n-row network pass per SGD
-    #                                          step (sf_consistency_loss); 0 = off: the shift alone (RAD);
-    #                                          negative, non-finite, or without the shift is refused
+    #                                          is added on the augmented twin of every row, one 2n-row network pass per SGD
+    #                                          step (sf_consistency_loss); 0 = off: the augmentation alone
+    #                                          (RAD); negative, non-finite, or without an augmentation is refused
+    ("augment_cutout", int, [], "*"),        # --augment_cutout MIN MAX: every SGD step's frames get one rectangle per sample
+    #                                          filled, its side lengths drawn from [MIN, MAX] pixels and clipped to the
+    #                                          frame, in the shift's launch (sf_augment_gather); [] = off;
+    #                                          any other count than 0 or 2, MIN < 1, MIN > MAX or MAX > 65535 is refused
+    ("augment_cutout_fill", str, "zero"),    # zero | random.  random: one byte per sample, u8 image keys only
+    ("augment_intensity", int, 0),           # A > 0: the pixels of a sample are scaled by s / 256, s uniform in
+    #                                          [256 - A, 256 + A] (u8 saturates at 255); 0 = off, outside 0 .. 255 is refused
+    ("augment_mix", str, "all"),             # all: every enabled op (shift, cutout, intensity) is composed on every SGD
+    #                                          step; one: each SGD step applies exactly ONE enabled op, drawn statelessly
+    #                                          from the step's draw id (Rand-DrAC; nothing new in the checkpoint)
 ]
+
+
+def augment_ops(cfg):
+    """The augmentation flags resolved and checked, for verify_cfg and Learner.init: an AttrDict
+    pad (augment_random_shift), cutout (() = off, or (MIN, MAX)), cutout_fill, intensity, mix, and enabled: the switched-on
+    ops in the order shift, cutout, intensity.  Raises ValueError for a bad value"""
+    from sample_factory_amd.utils.attr_dict import AttrDict
+    pad = int(getattr(cfg, "augment_random_shift", 0) or 0)
+    if not 0 <= pad <= 255:
+        raise ValueError(f"augment_random_shift={pad} must lie in 0 .. 255 (0 = off)")
+    cut = tuple(int(v) for v in (getattr(cfg, "augment_cutout", None) or ()))
+    if len(cut) not in (0, 2):
+        raise ValueError(f"augment_cutout={list(cut)} takes MIN MAX (two side lengths in pixels), or nothing for off")
+    if cut and not 1 <= cut[0] <= cut[1] <= 65535:
+        raise ValueError(f"augment_cutout={list(cut)} needs 1 <= MIN <= MAX <= 65535")
+    fill = str(getattr(cfg, "augment_cutout_fill", "zero"))
+    if fill not in ("zero", "random"):
+        raise ValueError(f"augment_cutout_fill={fill!r} must be 'zero' or 'random'")
+    amp = int(getattr(cfg, "augment_intensity", 0) or 0)
+    if not 0 <= amp <= 255:
+        raise ValueError(f"augment_intensity={amp} must lie in 0 .. 255 (0 = off)")
+    mix = str(getattr(cfg, "augment_mix", "all"))
+    if mix not in ("all", "one"):
+        raise ValueError(f"augment_mix={mix!r} must be 'all' or 'one'")
+    enabled = [name for name, on in (("shift", pad > 0), ("cutout", bool(cut)), ("intensity", amp > 0)) if on]
+    return AttrDict(pad=pad, cutout=cut, cutout_fill=fill, intensity=amp, mix=mix, enabled=enabled)
 
 
 def augment_consistency_coeff(cfg) -> float:
     """cfg.augment_consistency_coeff checked against the flags it depends on: the coefficient alpha of the
-    consistency loss, 0.0 = off.  Raises ValueError for a negative or non-finite alpha and for alpha > 0 without
-    augment_random_shift, NotImplementedError for alpha > 0 with mask_actions_in_loss (verify_cfg and Learner.init)"""
+    consistency loss, 0.0 = off.  Raises ValueError for a negative or non-finite alpha and for alpha > 0 without an
+    augmentation, NotImplementedError for alpha > 0 with mask_actions_in_loss (verify_cfg and Learner.init)"""
     import math
     alpha = float(getattr(cfg, "augment_consistency_coeff", 0.0) or 0.0)
     if not math.isfinite(alpha) or alpha < 0.0:
         raise ValueError(f"augment_consistency_coeff={alpha} must be finite and not negative (0 = off)")
     if alpha == 0.0:
         return 0.0
-    if int(getattr(cfg, "augment_random_shift", 0) or 0) <= 0:
-        raise ValueError(f"augment_consistency_coeff={alpha} needs augment_random_shift > 0: the consistency loss compares "
-                         "the network on the shifted frames with the network on the clean ones")
+    if not augment_ops(cfg).enabled:
+        raise ValueError(f"augment_consistency_coeff={alpha} needs an augmentation (augment_random_shift > 0, augment_cutout "
+                         "or augment_intensity): the consistency loss compares the network on the augmented frames with "
+                         "the network on the clean ones")
     if getattr(cfg, "mask_actions_in_loss", False):
         raise NotImplementedError(f"augment_consistency_coeff={alpha} with mask_actions_in_loss=True: the consistency term "
                                   "under an action mask is not implemented")
@@ -218,9 +256,8 @@ def verify_cfg(cfg, env_info) -> bool:
         err("RNN policies need recurrence > 1")
     if str(getattr(cfg, "reuse_rollout_activations", "auto")) not in ("auto", "off"):
         err(f"{cfg.reuse_rollout_activations=} must be 'auto' or 'off'")
-    if not 0 <= int(getattr(cfg, "augment_random_shift", 0) or 0) <= 255:
-        err(f"{cfg.augment_random_shift=} must lie in 0 .. 255 (0 = off)")
     try:
+        augment_ops(cfg)
         augment_consistency_coeff(cfg)  # (with mask_actions_in_loss it raises NotImplementedError: a missing feature, not a typo)
     except ValueError as e:
         err(str(e))

@@ -16,7 +16,10 @@ The area result is the exact value of what OpenCV's INTER_AREA approximates in f
 the last bit on ties.
 
 The module also holds the NumPy model of the training-time random shift (--augment_random_shift, sf_random_shift_gather;
-DESIGN.md 3.17): `random_shift_draws`, `random_shift_frames` and the learner's `random_shift_seed`."""
+DESIGN.md 3.17): `random_shift_draws`, `random_shift_frames` and the learner's `random_shift_seed`; and of the cutout and
+intensity augmentations that ride in the same launch (--augment_cutout, --augment_intensity, sf_augment_gather; DESIGN.md
+3.20): `cutout_draws`, `intensity_draws`, `intensity_frames`, `cutout_frames`, their composition `augment_frames`, and
+the host's per-step op draw `augment_op_of_step` (--augment_mix one)."""
 from __future__ import annotations
 
 import numpy as np
@@ -132,3 +135,124 @@ def random_shift_frames(frames, dy, dx, pad: int) -> np.ndarray:
     xs = np.clip(np.arange(W, dtype=np.int64)[None, :] + dx[:, None] - int(pad), 0, W - 1)  # [N, W]
     return np.ascontiguousarray(a[np.arange(N)[:, None, None, None], np.arange(a.shape[1])[None, :, None, None],
                                   ys[:, None, :, None], xs[:, None, None, :]])
+
+
+# ---- cutout and intensity (sf_augment_gather) ------------------------------------------------------------------------
+AUGMENT_LANE_CUTOUT = 8      # lane 2 of the Philox counter (6 and 7: PixelCatch's levels): the cutout rectangle
+AUGMENT_LANE_INTENSITY = 9   # ... the intensity scale and the fill byte
+AUGMENT_LANE_SELECT = 10     # ... which op an SGD step applies under --augment_mix one (drawn on the host only)
+CUTOUT_MAX_SIDE = 65535
+INTENSITY_MAX = 255
+CUTOUT_FILLS = ("zero", "random")
+AUGMENT_OPS = ("shift", "cutout", "intensity")  # the order of `enabled` in augment_op_of_step
+
+
+def _mulhi(w, m: int) -> np.ndarray:
+    """(w * m) >> 32 as a 64-bit product, w uint32 words, 0 <= m < 2^32"""
+    return ((np.asarray(w).astype(np.uint64) * np.uint64(m)) >> np.uint64(32)).astype(np.int64)
+
+
+def _lane_words(seed: int, draw_id: int, groups, lane: int):
+    groups = np.asarray(groups)
+    w = philox(int(draw_id) & 0xFFFFFFFF, 0, lane, 0, int(seed) & 0xFFFFFFFF, groups.astype(np.int64))
+    return w, groups.shape
+
+
+def cutout_draws(seed: int, draw_id: int, groups, H: int, W: int, cut_min: int, cut_max: int):
+    """(y0, x0, ch, cw) int32 arrays, one rectangle per entry of `groups`: w = philox4x32_10(counter (draw_id, 0, 8, 0),
+    key (seed, group)); ch = lo_h + mulhi(w[0], hi_h - lo_h + 1) with lo_h = min(cut_min, H), hi_h = min(cut_max, H); cw the
+    same from w[1] and W; y0 = mulhi(w[2], H - ch + 1), x0 = mulhi(w[3], W - cw + 1): always inside the frame"""
+    H, W, cut_min, cut_max = int(H), int(W), int(cut_min), int(cut_max)
+    if H < 1 or W < 1:
+        raise ValueError(f"cutout: frame of {H} x {W}")
+    if not 1 <= cut_min <= cut_max <= CUTOUT_MAX_SIDE:
+        raise ValueError(f"cutout: side lengths [{cut_min}, {cut_max}] need 1 <= MIN <= MAX <= {CUTOUT_MAX_SIDE}")
+    w, shape = _lane_words(seed, draw_id, groups, AUGMENT_LANE_CUTOUT)
+    lo_h, hi_h, lo_w, hi_w = min(cut_min, H), min(cut_max, H), min(cut_min, W), min(cut_max, W)
+    ch = lo_h + _mulhi(w[0], hi_h - lo_h + 1)
+    cw = lo_w + _mulhi(w[1], hi_w - lo_w + 1)
+    y0 = (w[2].astype(np.uint64) * (H - ch + 1).astype(np.uint64)) >> np.uint64(32)
+    x0 = (w[3].astype(np.uint64) * (W - cw + 1).astype(np.uint64)) >> np.uint64(32)
+    return tuple(np.asarray(v).astype(np.int32).reshape(shape) for v in (y0, x0, ch, cw))
+
+
+def intensity_draws(seed: int, draw_id: int, groups, amp: int):
+    """(s, fill) int32 arrays, one pair per entry of `groups`: w = philox4x32_10(counter (draw_id, 0, 9, 0), key (seed,
+    group)); s = 256 - amp + mulhi(w[0], 2 amp + 1) in [256 - amp, 256 + amp] (the scale is s / 256), fill = w[1] >> 24"""
+    amp = int(amp)
+    if not 0 <= amp <= INTENSITY_MAX:
+        raise ValueError(f"intensity: amplitude {amp} outside 0 .. {INTENSITY_MAX}")
+    w, shape = _lane_words(seed, draw_id, groups, AUGMENT_LANE_INTENSITY)
+    s = 256 - amp + _mulhi(w[0], 2 * amp + 1)
+    fill = w[1].astype(np.int64) >> 24
+    return s.astype(np.int32).reshape(shape), fill.astype(np.int32).reshape(shape)
+
+
+def intensity_frames(frames, s) -> np.ndarray:
+    """frames [N, C, H, W], s int [N]: u8 -> min(255, (x * s + 128) >> 8); f32 -> x * float32(s / 256), ONE float32
+    multiply (s / 256 is exact in float32)"""
+    a = np.asarray(frames)
+    if a.ndim != 4:
+        raise ValueError(f"frames [N, C, H, W] expected, got shape {a.shape}")
+    s = np.asarray(s, dtype=np.int64).reshape(a.shape[0], 1, 1, 1)
+    if a.dtype == np.uint8:
+        return np.minimum(255, (a.astype(np.int64) * s + 128) >> 8).astype(np.uint8)
+    if a.dtype == np.float32:
+        return a * (s.astype(np.float32) / np.float32(256.0))
+    raise ValueError(f"u8 or f32 frames expected, got dtype {a.dtype}")
+
+
+def cutout_frames(frames, y0, x0, ch, cw, fill=None) -> np.ndarray:
+    """frames [N, C, H, W]: out[i, :, y0[i]:y0[i] + ch[i], x0[i]:x0[i] + cw[i]] = fill[i] (None: 0), every plane alike"""
+    a = np.asarray(frames)
+    if a.ndim != 4:
+        raise ValueError(f"frames [N, C, H, W] expected, got shape {a.shape}")
+    N = a.shape[0]
+    y0, x0, ch, cw = (np.asarray(v, dtype=np.int64).reshape(N) for v in (y0, x0, ch, cw))
+    if fill is not None and a.dtype != np.uint8:
+        raise ValueError(f"a fill byte is for u8 frames, got dtype {a.dtype}")
+    fill = np.zeros(N, np.int64) if fill is None else np.asarray(fill, dtype=np.int64).reshape(N)
+    out = a.copy()
+    for i in range(N):
+        out[i, :, y0[i]:y0[i] + ch[i], x0[i]:x0[i] + cw[i]] = fill[i]
+    return out
+
+
+def augment_frames(frames, seed: int, draw_id: int, groups, *, pad: int = 0, cutout=(), cutout_fill: str = "zero",
+                   intensity: int = 0) -> np.ndarray:
+    """what sf_augment_gather does to frames [N, C, H, W] (u8 or f32) whose sample i draws under groups[i]: the shift, then
+    the intensity, then the cutout (in output coordinates, its fill not scaled); a stage whose parameter is 0 / () is
+    skipped.  With only `pad` it is random_shift_frames under random_shift_draws"""
+    a = np.asarray(frames)
+    if a.ndim != 4:
+        raise ValueError(f"frames [N, C, H, W] expected, got shape {a.shape}")
+    if cutout_fill not in CUTOUT_FILLS:
+        raise ValueError(f"cutout_fill must be one of {CUTOUT_FILLS}, got {cutout_fill!r}")
+    cut = tuple(int(v) for v in (cutout or ()))
+    if len(cut) not in (0, 2):
+        raise ValueError(f"cutout must be () or (MIN, MAX), got {cutout!r}")
+    if cut and cutout_fill == "random" and a.dtype != np.uint8:
+        raise ValueError(f"cutout_fill=random is one byte per sample: u8 frames only, got dtype {a.dtype}")
+    groups = np.asarray(groups).reshape(a.shape[0])
+    out = a
+    if int(pad) > 0:
+        dy, dx = random_shift_draws(seed, draw_id, groups, pad)
+        out = random_shift_frames(out, dy, dx, pad)
+    s, fill = intensity_draws(seed, draw_id, groups, intensity)  # (amp = 0: s = 256, and the fill byte is still drawn)
+    if int(intensity) > 0:
+        out = intensity_frames(out, s)
+    if cut:
+        y0, x0, ch, cw = cutout_draws(seed, draw_id, groups, a.shape[2], a.shape[3], *cut)
+        out = cutout_frames(out, y0, x0, ch, cw, fill if cutout_fill == "random" else None)
+    return np.ascontiguousarray(out)
+
+
+def augment_op_of_step(seed: int, draw_id: int, enabled):
+    """--augment_mix one: the op SGD step `draw_id` applies, out of `enabled` (the switched-on ops in the order shift,
+    cutout, intensity): enabled[mulhi(w[0], len(enabled))], w = philox4x32_10(counter (draw_id, 0, 10, 0), key (seed, 0)).
+    Stateless: a resumed run draws what the uninterrupted one would have"""
+    enabled = list(enabled)
+    if not enabled:
+        raise ValueError("augment_op_of_step: no op is enabled")
+    w, _ = _lane_words(seed, draw_id, np.zeros((), np.int64), AUGMENT_LANE_SELECT)
+    return enabled[int(_mulhi(w[0], len(enabled)))]

@@ -66,7 +66,7 @@ SYMBOLS = [
     "sf_res_conv_wgrad", "sf_res_conv_fwd_norm", "sf_res_conv_wgrad_norm",
     "sf_pixcatch_state_words", "sf_pixcatch_reset", "sf_pixcatch_step", "sf_pixcatch_reset_levels",
     "sf_pixcatch_step_levels",
-    "sf_random_shift_gather",
+    "sf_random_shift_gather", "sf_augment_gather",
     "sf_consistency_loss",
 ]
 
@@ -1107,6 +1107,45 @@ def random_shift_gather(dst: torch.Tensor, src: torch.Tensor, n: int, shape, *, 
                                              i64(stride * es), C.c_void_p(0) if index is None else _vp(index), i64(offset), i64(n), int(traj_T),
                                              Cn, H, W, es, int(pad), int(recurrence), u32(seed), u32(draw_id), stream()),
                "sf_random_shift_gather")
+
+
+CUTOUT_FILLS = {"zero": 0, "random": 1}  # sf_augment_gather's cut_fill argument
+
+
+def augment_gather(dst: torch.Tensor, src: torch.Tensor, n: int, shape, *, sample_stride: Optional[int] = None,
+                   index: Optional[torch.Tensor] = None, offset: int = 0, traj_T: int = 0, recurrence: int = 1, seed: int = 0,
+                   draw_id: int = 0, pad: int = 0, cutout=(), cutout_fill: str = "zero", intensity: int = 0) -> None:
+    """sf_augment_gather: random_shift_gather's launch with two more per-sample transformations behind the shift, in the
+    fixed order shift, intensity, cutout: `intensity` = A > 0 scales the pixels by s / 256, s drawn from [256 - A, 256 + A];
+    `cutout` = (MIN, MAX) fills a rectangle whose sides are drawn from [MIN, MAX] (clipped to the frame) with zeros
+    (cutout_fill "zero") or with one random byte per sample ("random", u8 only); () / 0 switch an op off.  Arguments and
+    addressing as random_shift_gather.  ONE launch, bit for bit envs/frame_ops.py (augment_frames and its draws)"""
+    if not (dst.is_cuda and src.is_cuda) or dst.dtype != src.dtype or dst.dtype not in (torch.uint8, torch.float32):
+        raise SfHipError(f"augment_gather: device views of one dtype (uint8 or float32) required, got {dst.dtype} on "
+                         f"{dst.device} and {src.dtype} on {src.device}")
+    Cn, H, W = (int(v) for v in shape)
+    n, es, elems = int(n), dst.element_size(), Cn * H * W
+    if dst.dim() < 2 or dst.shape[0] < n or dst[0].numel() != elems or (dst.shape[0] and not dst[0].is_contiguous()):
+        raise SfHipError(f"augment_gather: dst must hold at least n = {n} contiguous rows of C H W = {elems} elements, "
+                         f"got {tuple(dst.shape)} with strides {dst.stride()}")
+    if index is not None and (index.dtype != torch.int32 or not index.is_cuda or not index.is_contiguous() or index.numel() < n):
+        raise SfHipError(f"augment_gather: index must be a contiguous device int32 tensor of at least n = {n} entries")
+    cut = tuple(int(v) for v in (cutout or ()))
+    if len(cut) not in (0, 2):
+        raise SfHipError(f"augment_gather: cutout must be () or (MIN, MAX), got {cutout!r}")
+    if cutout_fill not in CUTOUT_FILLS:
+        raise SfHipError(f"augment_gather: cutout_fill must be one of {sorted(CUTOUT_FILLS)}, got {cutout_fill!r}")
+    if n == 0:
+        return
+    cut_min, cut_max = cut if cut else (0, 0)
+    stride = elems if sample_stride is None else int(sample_stride)
+    key = ("augment_gather", n, Cn, H, W, es, int(pad), cut_min, cut_max, CUTOUT_FILLS[cutout_fill], int(intensity)) \
+        if _keys_wanted() else None  # (tools/augment_ops_bench.py)
+    with _timed(key):
+        _check(load().sf_augment_gather(_vp(dst), i64(_pitch(dst, int(dst.shape[0]), elems * es)), _vp(src), i64(stride * es),
+                                        C.c_void_p(0) if index is None else _vp(index), i64(offset), i64(n), int(traj_T), Cn, H, W,
+                                        es, int(pad), cut_min, cut_max, CUTOUT_FILLS[cutout_fill], int(intensity),
+                                        int(recurrence), u32(seed), u32(draw_id), stream()), "sf_augment_gather")
 
 
 def synth_obs(obs_slot_ptr: int, env_stride, B, env0, obs_bytes, seed, step) -> None:

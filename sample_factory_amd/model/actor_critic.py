@@ -878,8 +878,9 @@ class ActorCritic(NativeTower):
         self._keep, cfg = None, self.cfg
         if str(getattr(cfg, "reuse_rollout_activations", "auto")) != "auto" or not _REUSE:
             return 0
-        if int(getattr(cfg, "augment_random_shift", 0) or 0) > 0:
-            return 0  # every SGD step trains on shifted frames: the rollout's activations belong to the unshifted ones
+        if (int(getattr(cfg, "augment_random_shift", 0) or 0) > 0 or getattr(cfg, "augment_cutout", None) or
+                int(getattr(cfg, "augment_intensity", 0) or 0) > 0):
+            return 0  # every SGD step trains on augmented frames: the rollout's activations belong to the clean ones
         # the learner's dataset must be exactly ONE sampling round: with k rounds per dataset every round overwrites the same
         # kept rows and minibatch 0 comes from the first one — the guard could never hold, the strided launches and the
         # buffers would be pure cost
