@@ -843,6 +843,15 @@ int sf_rnn_wideseq_bwd(int kind, const float *dout, const float *gates, const fl
                        const float *cout, const float *keep, const float *whh, float *dgx, float *dgh, uint32_t *sync,
                        int R, int Cn, int H, int env_major, void *stream);
 
+/* The name of the kernel instantiation a fused pass runs, as rocprofv3 prints it (`k_lstm_seq_fwd<512, 16, 2, 0>`,
+ * `k_gru_seq_bwd_r<256, 4>`, `k_rowseq_fwd<1, 64>`, `k_wideseq_bwd<0, 2>`): answered from the launch plan and the dispatch
+ * table the entry points themselves use.  family: 0 = sf_lstm_seq_* / sf_gru_seq_* (H 256 / 512), 1 = sf_rnn_rowseq_*,
+ * 2 = sf_rnn_wideseq_*; kind 0 = GRU, 1 = LSTM; pass 0 = forward, 1 = backward; Kx != 0: the forward pass with the input
+ * projection fused in (sf_*_seq_fwd_x), 0: the gx form.  A call of more than sf_rnn_seq_slab_rows rows is named by its
+ * first, full slab (the shorter last slab may run another instantiation).  out: at least 48 bytes.  Fails, with a message,
+ * for a (family, kind, Cn, H, Kx) the entry point refuses; the limits that depend on R (2 GiB) are not its business. */
+int sf_rnn_seq_kernel_name(int family, int kind, int pass, int Cn, int H, int Kx, char *out, int cap);
+
 /* ---- data-parallel learner replicas (SURVEY.md §8(b) "DP -> sf_allreduce_grads", §8(e)) ----------------------------
  * New capability: the reference runs ONE learner per policy (algo/utils/shared_buffers.py:26-32), so these replace no
  * reference function; a host without torch.distributed binds them for the exchange algo/learning/learner.py performs

@@ -20,7 +20,10 @@
 // Work-groups spin on the counter, so all of them must be co-resident: the grid is ngroups * H/JB <= #CUs with one
 // work-group per CU (LDS-limited).  A bounded spin turns a lost work-group (GPU shared with another process) into an
 // error flag instead of a hang.
+#include <limits.h>
 #include <stdlib.h>
+#include <algorithm>
+#include <initializer_list>
 #include <type_traits>
 
 #include "sf_common.h"
@@ -864,31 +867,49 @@ __global__ __launch_bounds__(256, 1) void k_gru_seq_bwd(GruSeqBwd p) {
     }
 }
 
-// The plan of ONE launch over Cn rows: row groups (at most 8, at most #CUs / (H / JB)) of at most 64 * SEQ_MAX_SUB rows.
-// Rows of a pass are independent, so a call with more rows than one launch serves runs as consecutive launches over row
-// slabs [r0, r1) of the same buffers (seq_slab_rows rows each, the last one shorter); every slab gets the plan of a
-// stand-alone call on r1 - r0 rows, which makes its results those of that call bit for bit.
-int seq_plan(int Cn, int H, int *ngroups, int *rows_per_group, int *jb) {
-    // widths with a compiled instantiation (JB = 16; the k-blocking needs H % 128 == 0 forward, an even number of
-    // 128-column blocks backward: 256 and 512 satisfy both for LSTM and GRU); 32 / 64 / 128 take the row-owned passes
-    // (sf_rnn_rowseq.h), 1024 the 8-unit passes of sf_rnn_wideseq.h, every other width the per-step path
-    if (H != 512 && H != 256) return 0;
-    *jb = 16;
+// ---- launch plans.  Every persistent pass splits the rows of ONE launch into row groups by the same rule: as many groups
+// as the CUs hold (`wgs_per_group` co-resident work-groups each), at most `max_groups` (the hand-off counters) and at most
+// one per `row_tile` rows; a group's rows are rounded up to the tile and must not exceed `max_rows_per_group`.
+struct RowGroupPlan {
+    int ngroups = 0, rows_per_group = 0;  // ngroups == 0: no plan
+    explicit operator bool() const { return ngroups > 0; }
+};
+
+int device_cus() {  // of the current device; 0 on error
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
         return 0;
-    const int ncol = H / *jb;
-    int ng = cus / ncol;
-    if (ng > 8) ng = 8;
-    const int need = (Cn + 15) / 16;
-    if (ng > need) ng = need;
-    if (ng < 1) return 0;
-    *ngroups = ng;
-    *rows_per_group = ((Cn + ng - 1) / ng + 15) / 16 * 16;
-    return *rows_per_group <= 64 * SEQ_MAX_SUB;
+    return cus;
 }
 
-// rows of one slab = the largest Cn seq_plan accepts on this device (2048 on 256 CUs); 0: no fused pass at this width.
+int row_groups_max(int wgs_per_group, int max_groups) {
+    const int ng = device_cus() / wgs_per_group;
+    return ng > max_groups ? max_groups : ng;
+}
+
+RowGroupPlan row_group_plan(int rows, int wgs_per_group, int max_groups, int row_tile, int max_rows_per_group) {
+    int ng = row_groups_max(wgs_per_group, max_groups);
+    const int need = (rows + row_tile - 1) / row_tile;
+    if (ng > need) ng = need;
+    if (ng < 1) return {};
+    const int rpg = ((rows + ng - 1) / ng + row_tile - 1) / row_tile * row_tile;
+    if (rpg > max_rows_per_group) return {};
+    return {ng, rpg};
+}
+
+// The LDS passes: 16 hidden units per work-group, at most 8 row groups of at most 64 * SEQ_MAX_SUB rows.
+// Widths with a compiled instantiation: 256 and 512 (the k-blocking needs H % 128 == 0 forward, an even number of
+// 128-column blocks backward; both hold for LSTM and GRU); 32 / 64 / 128 take the row-owned passes (sf_rnn_rowseq.h),
+// 1024 the 8-unit passes of sf_rnn_wideseq.h, every other width the per-step path.
+constexpr int SEQ_JB = 16;
+RowGroupPlan seq_plan(int Cn, int H) {
+    if (H != 512 && H != 256) return {};
+    return row_group_plan(Cn, H / SEQ_JB, 8, 16, 64 * SEQ_MAX_SUB);
+}
+
+// Rows of a pass are independent, so a call with more rows than one launch serves runs as consecutive launches over row
+// slabs [r0, r1) of the same buffers (seq_run_slabs below).  Rows of one slab = the largest Cn seq_plan accepts on this
+// device (2048 on 256 CUs); 0: no fused pass at this width.
 // Both passes use it: a backward slab of this height runs k_*_seq_bwd (LDS), a shorter tail whatever seq_plan_r /
 // seq_plan give a call of its size.  (1024-row slabs on the register-resident backward would make a 1025..2048-row call,
 // one LDS launch today, differ from its own first slab; DESIGN.md 3.4 has the timing of both heights, taken with
@@ -897,56 +918,166 @@ int seq_plan(int Cn, int H, int *ngroups, int *rows_per_group, int *jb) {
 // hand-off tensor whatever the slabs; the forward entry points check the backward pass's tensor as well.
 int seq_slab_rows(int H) {
     if (H != 512 && H != 256) return 0;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return 0;
-    int ng = cus / (H / 16);
-    if (ng > 8) ng = 8;
-    return ng < 1 ? 0 : ng * 64 * SEQ_MAX_SUB;
+    return row_groups_max(H / SEQ_JB, 8) * 64 * SEQ_MAX_SUB;
 }
 
 #include "sf_rnn_regw.h"
 #include "sf_rnn_rowseq.h"
 #include "sf_rnn_wideseq.h"
 
+// One launch of a fused pass: `family` as sf_rnn_seq_kernel_name numbers them
+enum { FAM_PERSISTENT = 0, FAM_ROW_OWNED = 1, FAM_WIDE = 2 };
+struct SeqLaunch {
+    int targ[4] = {0, 0, 0, 0}, ntarg = 0;  // the chosen instantiation: its template arguments, as the dispatch tables list them
+    unsigned grid = 0;
+    int ngroups = 0, rows_per_group = 0;     // (row-owned: none)
+    void set(std::initializer_list<int> a) { ntarg = (int)a.size(); std::copy(a.begin(), a.end(), targ); }
+    bool is(std::initializer_list<int> a) const { return (int)a.size() == ntarg && std::equal(a.begin(), a.end(), targ); }
+};
+
+// rows ONE launch of the family serves at this width on this device; 0: the family has no pass at this width
+int seq_family_slab_rows(int family, int H) {
+    if (family == FAM_PERSISTENT) return seq_slab_rows(H);
+    if (family == FAM_ROW_OWNED) return rowseq_width_ok(H) ? INT_MAX : 0;
+    if (family == FAM_WIDE) return H == WIDE_H ? wide_groups_max() * 64 * SEQ_MAX_SUB : 0;
+    return 0;
+}
+
+// The plan of ONE launch of (family, kind, pass) over `rows` rows; Kx != 0: the forward pass with the input projection
+// fused in.  false: no such launch.
+bool seq_launch(int family, int kind, int pass, int rows, int H, int Kx, SeqLaunch *L) {
+    if ((kind != 0 && kind != 1) || (pass != 0 && pass != 1) || rows <= 0 || (Kx && (family != FAM_PERSISTENT || pass))) return false;
+    // 64-row sub-tiles per work-group, unrolled at compile time (register-resident state): 1, 2 or 4 are compiled, 3 runs on 4
+    auto nsub_of = [](const RowGroupPlan &g) { const int n = (g.rows_per_group + 63) / 64; return n == 3 ? 4 : n; };
+    RowGroupPlan g;
+    if (family == FAM_ROW_OWNED) {  // a work-group owns a tile of rows: grid = ceil(rows / tile rows of the instantiation)
+        static_assert(RowSeqCfg<0, 32>::ROWS == RowSeqCfg<1, 32>::ROWS && RowSeqCfg<0, 64>::ROWS == RowSeqCfg<1, 64>::ROWS &&
+                      RowSeqCfg<0, 128>::ROWS == RowSeqCfg<1, 128>::ROWS, "the tile depends on the width only");
+        if (!rowseq_width_ok(H)) return false;
+        const int tile = H == 32 ? RowSeqCfg<0, 32>::ROWS : H == 64 ? RowSeqCfg<0, 64>::ROWS : RowSeqCfg<0, 128>::ROWS;
+        L->set({kind, H});
+        L->grid = (unsigned)((rows + tile - 1) / tile);
+    } else if (family == FAM_WIDE) {
+        if (H != WIDE_H || !(g = wide_plan(rows))) return false;
+        L->set({kind, nsub_of(g)});
+        L->grid = (unsigned)(g.ngroups * WIDE_NCOL);
+    } else if (family == FAM_PERSISTENT) {
+        if (pass == 1 && (g = seq_plan_r(rows, H))) {  // 32 hidden units per work-group, W_hh slice in registers
+            L->set({H, g.rows_per_group / 16});
+            L->grid = (unsigned)(g.ngroups * (H / 32));
+        } else {
+            if (!(g = seq_plan(rows, H))) return false;
+            const int nsub = nsub_of(g);
+            if (Kx && (Kx != 64 || nsub > 2)) return false;  // x has 64 columns; register budget: one or two sub-tiles
+            if (pass == 0) L->set({H, SEQ_JB, nsub, Kx / 16});
+            else L->set({H, SEQ_JB, nsub});
+            L->grid = (unsigned)(g.ngroups * (H / SEQ_JB));
+        }
+    } else {
+        return false;
+    }
+    L->ngroups = g.ngroups;
+    L->rows_per_group = g.rows_per_group;
+    return true;
+}
+// the fused input projection is a one-launch feature: the whole call must have a plan
+bool seq_fwd_x_plan(int Cn, int H, int Kx) {
+    SeqLaunch L;
+    return Kx != 0 && seq_launch(FAM_PERSISTENT, 0, 0, Cn, H, Kx, &L);
+}
+
+// ---- dispatch tables: how the plan's runtime choice reaches a template argument.  A row is one compiled instantiation;
+// the row that matches the plan launches it (p != nullptr) and returns its name as rocprofv3 prints it, from the same tokens.
+#define SEQ_ROW(KERN, ...)                                                         \
+    if (L.is({__VA_ARGS__})) {                                                     \
+        if (p) KERN<__VA_ARGS__><<<dim3(L.grid), dim3(256), 0, stream>>>(*p);      \
+        return #KERN "<" #__VA_ARGS__ ">";                                         \
+    }
+// <prefix..., X>, <prefix..., Y>, <prefix..., Z>
+#define SEQ_ROWS3(KERN, X, Y, Z, ...) SEQ_ROW(KERN, __VA_ARGS__, X) SEQ_ROW(KERN, __VA_ARGS__, Y) SEQ_ROW(KERN, __VA_ARGS__, Z)
+// forward <H, JB, sub-tiles, 16-column blocks of x>: without the input projection, then with it
+#define SEQ_ROWS_FWD(KERN)                                                                                     \
+    SEQ_ROW(KERN, 512, 16, 1, 0) SEQ_ROW(KERN, 512, 16, 2, 0) SEQ_ROW(KERN, 512, 16, 4, 0)                     \
+    SEQ_ROW(KERN, 256, 16, 1, 0) SEQ_ROW(KERN, 256, 16, 2, 0) SEQ_ROW(KERN, 256, 16, 4, 0)                     \
+    SEQ_ROW(KERN, 512, 16, 1, 4) SEQ_ROW(KERN, 512, 16, 2, 4) SEQ_ROW(KERN, 256, 16, 1, 4) SEQ_ROW(KERN, 256, 16, 2, 4)
+
+const char *seq_dispatch(const SeqLaunch &L, const LstmSeqFwd *p, hipStream_t stream) { SEQ_ROWS_FWD(k_lstm_seq_fwd) return nullptr; }
+const char *seq_dispatch(const SeqLaunch &L, const LstmSeqBwd *p, hipStream_t stream) {
+    // <H, row tiles per group>: the weights in registers (sf_rnn_regw.h); <H, JB, sub-tiles>: in LDS
+    SEQ_ROW(k_lstm_seq_bwd_r, 512, 2) SEQ_ROW(k_lstm_seq_bwd_r, 512, 4) SEQ_ROW(k_lstm_seq_bwd_r, 256, 2) SEQ_ROW(k_lstm_seq_bwd_r, 256, 4)
+    SEQ_ROWS3(k_lstm_seq_bwd, 1, 2, 4, 512, 16) SEQ_ROWS3(k_lstm_seq_bwd, 1, 2, 4, 256, 16)
+    return nullptr;
+}
+const char *seq_dispatch(const SeqLaunch &L, const GruSeqFwd *p, hipStream_t stream) { SEQ_ROWS_FWD(k_gru_seq_fwd) return nullptr; }
+const char *seq_dispatch(const SeqLaunch &L, const GruSeqBwd *p, hipStream_t stream) {
+    SEQ_ROW(k_gru_seq_bwd_r, 512, 2) SEQ_ROW(k_gru_seq_bwd_r, 512, 4) SEQ_ROW(k_gru_seq_bwd_r, 256, 2) SEQ_ROW(k_gru_seq_bwd_r, 256, 4)
+    SEQ_ROWS3(k_gru_seq_bwd, 1, 2, 4, 512, 16) SEQ_ROWS3(k_gru_seq_bwd, 1, 2, 4, 256, 16)
+    return nullptr;
+}
+const char *seq_dispatch(const SeqLaunch &L, const RowSeqFwd *p, hipStream_t stream) {  // <kind, H>
+    SEQ_ROWS3(k_rowseq_fwd, 32, 64, 128, 0) SEQ_ROWS3(k_rowseq_fwd, 32, 64, 128, 1)
+    return nullptr;
+}
+const char *seq_dispatch(const SeqLaunch &L, const RowSeqBwd *p, hipStream_t stream) {
+    SEQ_ROWS3(k_rowseq_bwd, 32, 64, 128, 0) SEQ_ROWS3(k_rowseq_bwd, 32, 64, 128, 1)
+    return nullptr;
+}
+const char *seq_dispatch(const SeqLaunch &L, const WideSeqFwd *p, hipStream_t stream) {  // <kind, sub-tiles>
+    SEQ_ROWS3(k_wideseq_fwd, 1, 2, 4, 0) SEQ_ROWS3(k_wideseq_fwd, 1, 2, 4, 1)
+    return nullptr;
+}
+const char *seq_dispatch(const SeqLaunch &L, const WideSeqBwd *p, hipStream_t stream) {
+    SEQ_ROWS3(k_wideseq_bwd, 1, 2, 4, 0) SEQ_ROWS3(k_wideseq_bwd, 1, 2, 4, 1)
+    return nullptr;
+}
+#undef SEQ_ROWS_FWD
+#undef SEQ_ROWS3
+#undef SEQ_ROW
+
+// the printed name of the instantiation L selects, from the table that launches it
+const char *seq_kernel_name(const SeqLaunch &L, int family, int kind, int pass) {
+    if (family == FAM_ROW_OWNED)
+        return pass ? seq_dispatch(L, (const RowSeqBwd *)nullptr, nullptr) : seq_dispatch(L, (const RowSeqFwd *)nullptr, nullptr);
+    if (family == FAM_WIDE)
+        return pass ? seq_dispatch(L, (const WideSeqBwd *)nullptr, nullptr) : seq_dispatch(L, (const WideSeqFwd *)nullptr, nullptr);
+    if (kind)
+        return pass ? seq_dispatch(L, (const LstmSeqBwd *)nullptr, nullptr) : seq_dispatch(L, (const LstmSeqFwd *)nullptr, nullptr);
+    return pass ? seq_dispatch(L, (const GruSeqBwd *)nullptr, nullptr) : seq_dispatch(L, (const GruSeqFwd *)nullptr, nullptr);
+}
+
+// hout / dout element (row, t) lives at row * rs + t * ts (+ unit): [R][Cn][H] (time-major) or, env_major, [Cn][R][H] = the
+// row order of the minibatch itself (no transpose copy)
+struct SeqStrides {
+    int64_t rs, ts;
+    SeqStrides(int env_major, int R, int Cn, int H) : rs(env_major ? (int64_t)R * H : (int64_t)H), ts(env_major ? (int64_t)H : (int64_t)Cn * H) {}
+};
+
+// The slab loop of the persistent entry points: one launch per row slab [r0, r1) of `slab` rows (a single one up to `slab`
+// rows, the last one shorter).  Every slab gets the plan of a stand-alone call on r1 - r0 rows, which makes its results
+// those of that call bit for bit; the hand-off counters are cleared before each launch, the abort word never.
+template <class P>
+int seq_run_slabs(const char *what, int family, int kind, int pass, int H, int Kx, int slab, P p, void *stream) {
+    char memset_what[64];
+    snprintf(memset_what, sizeof(memset_what), "%s memset", what);
+    for (int r0 = 0; r0 < p.Cn; r0 += slab) {
+        const int r1 = p.Cn - r0 < slab ? p.Cn : r0 + slab;
+        SeqLaunch L;
+        SF_REQUIRE(seq_launch(family, kind, pass, r1 - r0, H, Kx, &L), family == FAM_WIDE ? "%s: no plan for %d rows" : "%s: no plan for %d rows at H=%d",
+                   what, r1 - r0, H);
+        int rc = sf_hip_status(hipMemsetAsync(p.sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), memset_what);
+        if (rc) return rc;
+        p.ngroups = L.ngroups;
+        p.rows_per_group = L.rows_per_group;
+        p.row0 = r0;
+        p.row_end = r1;
+        SF_REQUIRE(seq_dispatch(L, &p, STREAM(stream)), "%s: no kernel for the plan", what);
+        rc = sf_launch_status(what);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 }  // namespace
-
-// backward passes with the weights in registers (sf_rnn_regw.h): one instantiation per (width, row tiles per group)
-#define SEQ_DISPATCH_R(KERN)                                                         \
-    do {                                                                             \
-        if (H == 512) {                                                              \
-            if (rpg == 32) KERN<512, 2><<<grid, block, 0, STREAM(stream)>>>(p);      \
-            else KERN<512, 4><<<grid, block, 0, STREAM(stream)>>>(p);                \
-        } else {                                                                     \
-            if (rpg == 32) KERN<256, 2><<<grid, block, 0, STREAM(stream)>>>(p);      \
-            else KERN<256, 4><<<grid, block, 0, STREAM(stream)>>>(p);                \
-        }                                                                            \
-    } while (0)
-
-// one instantiation per (width, sub-tiles per work-group)
-#define SEQ_DISPATCH(KERN, ...)                                                                       \
-    do {                                                                                              \
-        if (H == 512) {                                                                               \
-            if (nsub == 1) KERN<512, 16, 1 __VA_ARGS__><<<grid, block, 0, STREAM(stream)>>>(p);       \
-            else if (nsub == 2) KERN<512, 16, 2 __VA_ARGS__><<<grid, block, 0, STREAM(stream)>>>(p);  \
-            else KERN<512, 16, 4 __VA_ARGS__><<<grid, block, 0, STREAM(stream)>>>(p);                 \
-        } else {                                                                                      \
-            if (nsub == 1) KERN<256, 16, 1 __VA_ARGS__><<<grid, block, 0, STREAM(stream)>>>(p);       \
-            else if (nsub == 2) KERN<256, 16, 2 __VA_ARGS__><<<grid, block, 0, STREAM(stream)>>>(p);  \
-            else KERN<256, 16, 4 __VA_ARGS__><<<grid, block, 0, STREAM(stream)>>>(p);                 \
-        }                                                                                             \
-    } while (0)
-// forward passes with the input projection fused in (x has 64 columns; register budget: one or two sub-tiles)
-#define SEQ_DISPATCH_X(KERN)                                                                  \
-    do {                                                                                      \
-        if (H == 512) {                                                                       \
-            if (nsub == 1) KERN<512, 16, 1, 4><<<grid, block, 0, STREAM(stream)>>>(p);        \
-            else KERN<512, 16, 2, 4><<<grid, block, 0, STREAM(stream)>>>(p);                  \
-        } else {                                                                              \
-            if (nsub == 1) KERN<256, 16, 1, 4><<<grid, block, 0, STREAM(stream)>>>(p);        \
-            else KERN<256, 16, 2, 4><<<grid, block, 0, STREAM(stream)>>>(p);                  \
-        }                                                                                     \
-    } while (0)
 
 extern "C" int sf_lstm_seq_supported(int Cn, int H) {
     // the OFFER ends at one launch, as before row slabs: on them Learner.train measured 1.09 - 1.55 x the per-step time at
@@ -955,57 +1086,44 @@ extern "C" int sf_lstm_seq_supported(int Cn, int H) {
     return Cn > 0 && Cn <= seq_slab_rows(H);
 }
 
-static int lstm_seq_fwd_impl(const float *gx, const float *x, const float *wih_t, const float *bih, int Kx,
-                             const float *whh, const float *bhh, const float *keep, float *gates, float *hprev, float *hout,
-                             float *cprev, float *cout, uint32_t *sync, int R, int Cn, int H, int env_major, void *stream) {
-    SF_REQUIRE((gx || (x && wih_t && bih)) && whh && bhh && keep && gates && hprev && hout && cprev && cout && sync && R > 0 && Cn > 0,
-               "sf_lstm_seq_fwd: bad args");
+// the forward pass of both kinds (cprev / cout: LSTM only), on gx or, gx == nullptr, with the input projection x W_ih^T + b_ih
+static int seq_fwd_impl(int kind, const float *gx, const float *x, const float *wih_t, const float *bih, int Kx, const float *whh,
+                        const float *bhh, const float *keep, float *gates, float *hprev, float *hout, float *cprev, float *cout,
+                        uint32_t *sync, int R, int Cn, int H, int env_major, void *stream) {
+    const char *what = kind ? "sf_lstm_seq_fwd" : "sf_gru_seq_fwd";
+    SF_REQUIRE((gx || (x && wih_t && bih)) && whh && bhh && keep && gates && hprev && hout && (!kind || (cprev && cout)) && sync && R > 0 &&
+                   Cn > 0, "%s: bad args", what);
     const int slab = seq_slab_rows(H);
-    SF_REQUIRE(slab > 0, "sf_lstm_seq_fwd: unsupported shape Cn=%d H=%d (see sf_lstm_seq_supported)", Cn, H);
-    SF_REQUIRE((int64_t)(R + 1) * Cn * H * 4 < 0x7FFFFFF0LL, "sf_lstm_seq_fwd: state buffer exceeds 2 GiB");
+    SF_REQUIRE(slab > 0, "%s: unsupported shape Cn=%d H=%d (see sf_lstm_seq_supported)", what, Cn, H);
+    SF_REQUIRE((int64_t)(R + 1) * Cn * H * 4 < 0x7FFFFFF0LL, "%s: state buffer exceeds 2 GiB", what);
     // (the backward pass's limit, checked HERE too: a pass pair is refused before its forward half runs)
-    SF_REQUIRE((int64_t)R * Cn * 4 * H * 4 < 0x7FFFFFF0LL, "sf_lstm_seq_fwd: the backward pass's gate-gradient buffer would exceed 2 GiB");
-    if (!gx) {  // the fused input projection is a one-launch feature
-        int ng, rpg, jb;
-        SF_REQUIRE(Kx == 64 && seq_plan(Cn, H, &ng, &rpg, &jb) && (rpg + 63) / 64 <= 2 && (((uintptr_t)x | (uintptr_t)wih_t) & 15) == 0,
-                   "sf_lstm_seq_fwd_x: unsupported shape Cn=%d H=%d Kx=%d (see sf_seq_fwd_x_supported)", Cn, H, Kx);
-    }
-    for (int r0 = 0; r0 < Cn; r0 += slab) {  // one launch per row slab (a single one up to `slab` rows)
-        const int r1 = Cn - r0 < slab ? Cn : r0 + slab;
-        int ng, rpg, jb;
-        SF_REQUIRE(seq_plan(r1 - r0, H, &ng, &rpg, &jb), "sf_lstm_seq_fwd: no plan for %d rows at H=%d", r1 - r0, H);
-        const int nsub = (rpg + 63) / 64;  // 64-row sub-tiles per work-group, unrolled at compile time (register-resident state)
-        int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_lstm_seq_fwd memset");
-        if (rc) return rc;
-        // hout [R][Cn][H] (time-major) or, env_major, [Cn][R][H] = the row order of the minibatch itself (no transpose copy)
-        LstmSeqFwd p{gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, ng, rpg,
-                     env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, x, wih_t, bih, r0, r1};
-        const dim3 grid((unsigned)(ng * (H / jb))), block(256);
-        if (gx) SEQ_DISPATCH(k_lstm_seq_fwd, , 0);
-        else SEQ_DISPATCH_X(k_lstm_seq_fwd);
-        rc = sf_launch_status("sf_lstm_seq_fwd");
-        if (rc) return rc;
-    }
-    return 0;
+    SF_REQUIRE((int64_t)R * Cn * (kind ? 4 : 3) * H * 4 < 0x7FFFFFF0LL, "%s: the backward pass's gate-gradient buffer would exceed 2 GiB", what);
+    SF_REQUIRE(gx || (seq_fwd_x_plan(Cn, H, Kx) && (((uintptr_t)x | (uintptr_t)wih_t) & 15) == 0),
+               "%s_x: unsupported shape Cn=%d H=%d Kx=%d (see sf_seq_fwd_x_supported)", what, Cn, H, Kx);
+    const SeqStrides ho(env_major, R, Cn, H);
+    if (kind)
+        return seq_run_slabs(what, FAM_PERSISTENT, 1, 0, H, gx ? 0 : Kx, slab, LstmSeqFwd{gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync,
+                             R, Cn, 0, 0, ho.rs, ho.ts, x, wih_t, bih, 0, 0}, stream);
+    return seq_run_slabs(what, FAM_PERSISTENT, 0, 0, H, gx ? 0 : Kx, slab, GruSeqFwd{gx, whh, bhh, keep, gates, hprev, hout, sync,
+                         R, Cn, 0, 0, ho.rs, ho.ts, x, wih_t, bih, 0, 0}, stream);
 }
 extern "C" int sf_lstm_seq_fwd(const float *gx, const float *whh, const float *bhh, const float *keep, float *gates,
                                float *hprev, float *hout, float *cprev, float *cout, uint32_t *sync, int R, int Cn, int H,
                                int env_major, void *stream) {
     SF_REQUIRE(gx, "sf_lstm_seq_fwd: bad args");
-    return lstm_seq_fwd_impl(gx, nullptr, nullptr, nullptr, 0, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, H,
-                             env_major, stream);
+    return seq_fwd_impl(1, gx, nullptr, nullptr, nullptr, 0, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, H,
+                        env_major, stream);
 }
 extern "C" int sf_seq_fwd_x_supported(int Cn, int H, int Kx) {
     static const int on = getenv("SF_SEQ_FWD_X") ? atoi(getenv("SF_SEQ_FWD_X")) : 1;
-    int ng, rpg, jb;
-    return on && Cn > 0 && Kx == 64 && seq_plan(Cn, H, &ng, &rpg, &jb) && (rpg + 63) / 64 <= 2;
+    return on && seq_fwd_x_plan(Cn, H, Kx);
 }
 extern "C" int sf_lstm_seq_fwd_x(const float *x, const float *wih_t, const float *bih, int Kx, const float *whh,
                                  const float *bhh, const float *keep, float *gates, float *hprev, float *hout, float *cprev,
                                  float *cout, uint32_t *sync, int R, int Cn, int H, int env_major, void *stream) {
     SF_REQUIRE(x && wih_t && bih, "sf_lstm_seq_fwd_x: bad args");
-    return lstm_seq_fwd_impl(nullptr, x, wih_t, bih, Kx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, H,
-                             env_major, stream);
+    return seq_fwd_impl(1, nullptr, x, wih_t, bih, Kx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, H,
+                        env_major, stream);
 }
 
 extern "C" int sf_lstm_seq_bwd(const float *dout, const float *gates, const float *cprev, const float *cout,
@@ -1017,75 +1135,24 @@ extern "C" int sf_lstm_seq_bwd(const float *dout, const float *gates, const floa
     SF_REQUIRE(slab > 0, "sf_lstm_seq_bwd: unsupported shape Cn=%d H=%d (see sf_lstm_seq_supported)", Cn, H);
     SF_REQUIRE((int64_t)R * Cn * 4 * H * 4 < 0x7FFFFFF0LL, "sf_lstm_seq_bwd: gate-gradient buffer exceeds 2 GiB");
     static const int ablate = getenv("SF_LSTM_ABLATE") ? atoi(getenv("SF_LSTM_ABLATE")) : 0;
-    for (int r0 = 0; r0 < Cn; r0 += slab) {  // one launch per row slab (a single one up to `slab` rows)
-        const int r1 = Cn - r0 < slab ? Cn : r0 + slab;
-        int ng, rpg, jb;
-        SF_REQUIRE(seq_plan(r1 - r0, H, &ng, &rpg, &jb), "sf_lstm_seq_bwd: no plan for %d rows at H=%d", r1 - r0, H);
-        int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_lstm_seq_bwd memset");
-        if (rc) return rc;
-        int ngr, rpgr;
-        if (seq_plan_r(r1 - r0, H, &ngr, &rpgr)) {  // 32 hidden units per work-group, W_hh slice in registers
-            const int rpg = rpgr;
-            LstmSeqBwd p{dout, gates, cprev, cout, keep, whh, dgx, sync, R, Cn, ngr, rpg,
-                         env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, ablate, r0, r1};
-            const dim3 grid((unsigned)(ngr * (H / 32))), block(256);
-            SEQ_DISPATCH_R(k_lstm_seq_bwd_r);
-        } else {
-            LstmSeqBwd p{dout, gates, cprev, cout, keep, whh, dgx, sync, R, Cn, ng, rpg,
-                         env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, ablate, r0, r1};
-            const dim3 grid((unsigned)(ng * (H / jb))), block(256);
-            const int nsub = (rpg + 63) / 64;
-            SEQ_DISPATCH(k_lstm_seq_bwd);
-        }
-        rc = sf_launch_status("sf_lstm_seq_bwd");
-        if (rc) return rc;
-    }
-    return 0;
+    const SeqStrides d(env_major, R, Cn, H);
+    LstmSeqBwd p{dout, gates, cprev, cout, keep, whh, dgx, sync, R, Cn, 0, 0, d.rs, d.ts, ablate, 0, 0};
+    return seq_run_slabs("sf_lstm_seq_bwd", FAM_PERSISTENT, 1, 1, H, 0, slab, p, stream);
 }
 
-static int gru_seq_fwd_impl(const float *gx, const float *x, const float *wih_t, const float *bih, int Kx, const float *whh,
-                            const float *bhh, const float *keep, float *gates, float *hprev, float *hout, uint32_t *sync,
-                            int R, int Cn, int H, int env_major, void *stream) {
-    SF_REQUIRE((gx || (x && wih_t && bih)) && whh && bhh && keep && gates && hprev && hout && sync && R > 0 && Cn > 0,
-               "sf_gru_seq_fwd: bad args");
-    const int slab = seq_slab_rows(H);
-    SF_REQUIRE(slab > 0, "sf_gru_seq_fwd: unsupported shape Cn=%d H=%d (see sf_lstm_seq_supported)", Cn, H);
-    SF_REQUIRE((int64_t)(R + 1) * Cn * H * 4 < 0x7FFFFFF0LL, "sf_gru_seq_fwd: state buffer exceeds 2 GiB");
-    SF_REQUIRE((int64_t)R * Cn * 3 * H * 4 < 0x7FFFFFF0LL, "sf_gru_seq_fwd: the backward pass's gate-gradient buffer would exceed 2 GiB");
-    if (!gx) {  // the fused input projection is a one-launch feature
-        int ng, rpg, jb;
-        SF_REQUIRE(Kx == 64 && seq_plan(Cn, H, &ng, &rpg, &jb) && (rpg + 63) / 64 <= 2 && (((uintptr_t)x | (uintptr_t)wih_t) & 15) == 0,
-                   "sf_gru_seq_fwd_x: unsupported shape Cn=%d H=%d Kx=%d (see sf_seq_fwd_x_supported)", Cn, H, Kx);
-    }
-    for (int r0 = 0; r0 < Cn; r0 += slab) {  // one launch per row slab (a single one up to `slab` rows)
-        const int r1 = Cn - r0 < slab ? Cn : r0 + slab;
-        int ng, rpg, jb;
-        SF_REQUIRE(seq_plan(r1 - r0, H, &ng, &rpg, &jb), "sf_gru_seq_fwd: no plan for %d rows at H=%d", r1 - r0, H);
-        const int nsub = (rpg + 63) / 64;
-        int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_gru_seq_fwd memset");
-        if (rc) return rc;
-        GruSeqFwd p{gx, whh, bhh, keep, gates, hprev, hout, sync, R, Cn, ng, rpg,
-                    env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, x, wih_t, bih, r0, r1};
-        const dim3 grid((unsigned)(ng * (H / jb))), block(256);
-        if (gx) SEQ_DISPATCH(k_gru_seq_fwd, , 0);
-        else SEQ_DISPATCH_X(k_gru_seq_fwd);
-        rc = sf_launch_status("sf_gru_seq_fwd");
-        if (rc) return rc;
-    }
-    return 0;
-}
 extern "C" int sf_gru_seq_fwd(const float *gx, const float *whh, const float *bhh, const float *keep, float *gates,
                               float *hprev, float *hout, uint32_t *sync, int R, int Cn, int H, int env_major,
                               void *stream) {
     SF_REQUIRE(gx, "sf_gru_seq_fwd: bad args");
-    return gru_seq_fwd_impl(gx, nullptr, nullptr, nullptr, 0, whh, bhh, keep, gates, hprev, hout, sync, R, Cn, H, env_major,
-                            stream);
+    return seq_fwd_impl(0, gx, nullptr, nullptr, nullptr, 0, whh, bhh, keep, gates, hprev, hout, nullptr, nullptr, sync, R, Cn, H,
+                        env_major, stream);
 }
 extern "C" int sf_gru_seq_fwd_x(const float *x, const float *wih_t, const float *bih, int Kx, const float *whh,
                                 const float *bhh, const float *keep, float *gates, float *hprev, float *hout, uint32_t *sync,
                                 int R, int Cn, int H, int env_major, void *stream) {
     SF_REQUIRE(x && wih_t && bih, "sf_gru_seq_fwd_x: bad args");
-    return gru_seq_fwd_impl(nullptr, x, wih_t, bih, Kx, whh, bhh, keep, gates, hprev, hout, sync, R, Cn, H, env_major, stream);
+    return seq_fwd_impl(0, nullptr, x, wih_t, bih, Kx, whh, bhh, keep, gates, hprev, hout, nullptr, nullptr, sync, R, Cn, H,
+                        env_major, stream);
 }
 
 extern "C" int sf_gru_seq_bwd(const float *dout, const float *gates, const float *hprev, const float *keep,
@@ -1095,48 +1162,22 @@ extern "C" int sf_gru_seq_bwd(const float *dout, const float *gates, const float
     const int slab = seq_slab_rows(H);
     SF_REQUIRE(slab > 0, "sf_gru_seq_bwd: unsupported shape Cn=%d H=%d (see sf_lstm_seq_supported)", Cn, H);
     SF_REQUIRE((int64_t)R * Cn * 3 * H * 4 < 0x7FFFFFF0LL, "sf_gru_seq_bwd: gate-gradient buffer exceeds 2 GiB");
-    for (int r0 = 0; r0 < Cn; r0 += slab) {  // one launch per row slab (a single one up to `slab` rows)
-        const int r1 = Cn - r0 < slab ? Cn : r0 + slab;
-        int ng, rpg, jb;
-        SF_REQUIRE(seq_plan(r1 - r0, H, &ng, &rpg, &jb), "sf_gru_seq_bwd: no plan for %d rows at H=%d", r1 - r0, H);
-        int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_gru_seq_bwd memset");
-        if (rc) return rc;
-        int ngr, rpgr;
-        if (seq_plan_r(r1 - r0, H, &ngr, &rpgr)) {
-            const int rpg = rpgr;
-            GruSeqBwd p{dout, gates, hprev, keep, whh, dgx, dgh, sync, R, Cn, ngr, rpg,
-                        env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, r0, r1};
-            const dim3 grid((unsigned)(ngr * (H / 32))), block(256);
-            SEQ_DISPATCH_R(k_gru_seq_bwd_r);
-        } else {
-            GruSeqBwd p{dout, gates, hprev, keep, whh, dgx, dgh, sync, R, Cn, ng, rpg,
-                        env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H, r0, r1};
-            const dim3 grid((unsigned)(ng * (H / jb))), block(256);
-            const int nsub = (rpg + 63) / 64;
-            SEQ_DISPATCH(k_gru_seq_bwd);
-        }
-        rc = sf_launch_status("sf_gru_seq_bwd");
-        if (rc) return rc;
-    }
-    return 0;
+    const SeqStrides d(env_major, R, Cn, H);
+    GruSeqBwd p{dout, gates, hprev, keep, whh, dgx, dgh, sync, R, Cn, 0, 0, d.rs, d.ts, 0, 0};
+    return seq_run_slabs("sf_gru_seq_bwd", FAM_PERSISTENT, 0, 1, H, 0, slab, p, stream);
 }
 
-// ---- row-owned sequence passes (sf_rnn_rowseq.h): a work-group owns a tile of chunk rows for all R steps
-// grid = ceil(Cn / tile rows of the instantiation)
-#define ROWSEQ_LAUNCH(KERN, K, W) \
-    KERN<K, W><<<dim3((unsigned)((Cn + RowSeqCfg<K, W>::ROWS - 1) / RowSeqCfg<K, W>::ROWS)), dim3(256), 0, STREAM(stream)>>>(p)
-#define ROWSEQ_DISPATCH(KERN)                              \
-    do {                                                   \
-        if (kind == 0 && H == 32) ROWSEQ_LAUNCH(KERN, 0, 32);        \
-        else if (kind == 0 && H == 64) ROWSEQ_LAUNCH(KERN, 0, 64);   \
-        else if (kind == 0) ROWSEQ_LAUNCH(KERN, 0, 128);             \
-        else if (H == 32) ROWSEQ_LAUNCH(KERN, 1, 32);                \
-        else if (H == 64) ROWSEQ_LAUNCH(KERN, 1, 64);                \
-        else ROWSEQ_LAUNCH(KERN, 1, 128);                            \
-    } while (0)
-
+// ---- row-owned sequence passes (sf_rnn_rowseq.h): a work-group owns a tile of chunk rows for all R steps, one launch
 extern "C" int sf_rnn_rowseq_supported(int kind, int Cn, int H) {
     return (kind == 0 || kind == 1) && Cn > 0 && rowseq_width_ok(H);
+}
+
+template <class P>
+static int rowseq_run(const char *what, int kind, int pass, int H, const P &p, void *stream) {
+    SeqLaunch L;
+    SF_REQUIRE(seq_launch(FAM_ROW_OWNED, kind, pass, p.Cn, H, 0, &L) && seq_dispatch(L, &p, STREAM(stream)), "%s: no plan for %d rows at H=%d",
+               what, p.Cn, H);
+    return sf_launch_status(what);
 }
 
 extern "C" int sf_rnn_rowseq_fwd(int kind, const float *gx, const float *whh, const float *bhh, const float *keep, float *gates,
@@ -1149,10 +1190,9 @@ extern "C" int sf_rnn_rowseq_fwd(int kind, const float *gx, const float *whh, co
     SF_REQUIRE(((uintptr_t)whh & 15) == 0 && (((uintptr_t)gx | (uintptr_t)bhh | (uintptr_t)keep | (uintptr_t)gates | (uintptr_t)hprev |
                                                 (uintptr_t)hout | (uintptr_t)cprev | (uintptr_t)cout) & 3) == 0,
                "sf_rnn_rowseq_fwd: whh must be 16-byte aligned, every other operand 4-byte aligned");
-    RowSeqFwd p{gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, R, Cn,
-                env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H};
-    ROWSEQ_DISPATCH(k_rowseq_fwd);
-    return sf_launch_status("sf_rnn_rowseq_fwd");
+    const SeqStrides ho(env_major, R, Cn, H);
+    return rowseq_run("sf_rnn_rowseq_fwd", kind, 0, H, RowSeqFwd{gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, R, Cn, ho.rs, ho.ts},
+                      stream);
 }
 
 extern "C" int sf_rnn_rowseq_bwd(int kind, const float *dout, const float *gates, const float *hprev, const float *cprev,
@@ -1166,26 +1206,12 @@ extern "C" int sf_rnn_rowseq_bwd(int kind, const float *dout, const float *gates
     SF_REQUIRE(((uintptr_t)whh & 15) == 0 && (((uintptr_t)dout | (uintptr_t)gates | (uintptr_t)hprev | (uintptr_t)cprev | (uintptr_t)cout |
                                                 (uintptr_t)keep | (uintptr_t)dgx | (uintptr_t)dgh) & 3) == 0,
                "sf_rnn_rowseq_bwd: whh must be 16-byte aligned, every other operand 4-byte aligned");
-    RowSeqBwd p{dout, gates, hprev, cprev, cout, keep, whh, dgx, dgh, R, Cn,
-                env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H};
-    ROWSEQ_DISPATCH(k_rowseq_bwd);
-    return sf_launch_status("sf_rnn_rowseq_bwd");
+    const SeqStrides d(env_major, R, Cn, H);
+    return rowseq_run("sf_rnn_rowseq_bwd", kind, 1, H, RowSeqBwd{dout, gates, hprev, cprev, cout, keep, whh, dgx, dgh, R, Cn, d.rs, d.ts},
+                      stream);
 }
 
 // ---- persistent passes at H = 1024 (sf_rnn_wideseq.h): 8 hidden units per work-group, row slabs as above
-#define WIDESEQ_DISPATCH(KERN)                                                                    \
-    do {                                                                                          \
-        if (kind == 0) {                                                                          \
-            if (nsub == 1) KERN<0, 1><<<grid, block, 0, STREAM(stream)>>>(p);                     \
-            else if (nsub == 2) KERN<0, 2><<<grid, block, 0, STREAM(stream)>>>(p);                \
-            else KERN<0, 4><<<grid, block, 0, STREAM(stream)>>>(p);                               \
-        } else {                                                                                  \
-            if (nsub == 1) KERN<1, 1><<<grid, block, 0, STREAM(stream)>>>(p);                     \
-            else if (nsub == 2) KERN<1, 2><<<grid, block, 0, STREAM(stream)>>>(p);                \
-            else KERN<1, 4><<<grid, block, 0, STREAM(stream)>>>(p);                               \
-        }                                                                                         \
-    } while (0)
-
 // what the wide kernels can run: any Cn > 0 (row slabs beyond one launch)
 static int wideseq_shape_ok(int kind, int Cn, int H) {
     return (kind == 0 || kind == 1) && Cn > 0 && H == WIDE_H && wide_groups_max() >= 1;
@@ -1203,8 +1229,7 @@ extern "C" int sf_rnn_wideseq_supported(int kind, int Cn, int H) {
 
 extern "C" int sf_rnn_seq_slab_rows(int kind, int H, int pass) {
     if ((kind != 0 && kind != 1) || (pass != 0 && pass != 1)) return 0;
-    if (H == WIDE_H) return wide_groups_max() * 64 * SEQ_MAX_SUB;
-    return seq_slab_rows(H);
+    return seq_family_slab_rows(H == WIDE_H ? FAM_WIDE : FAM_PERSISTENT, H);
 }
 
 extern "C" int sf_rnn_wideseq_fwd(int kind, const float *gx, const float *whh, const float *bhh, const float *keep, float *gates,
@@ -1220,22 +1245,9 @@ extern "C" int sf_rnn_wideseq_fwd(int kind, const float *gx, const float *whh, c
     SF_REQUIRE((int64_t)(R + 1) * Cn * H * 4 < 0x7FFFFFF0LL, "sf_rnn_wideseq_fwd: state buffer exceeds 2 GiB");
     SF_REQUIRE((int64_t)R * Cn * (kind ? 4 : 3) * H * 4 < 0x7FFFFFF0LL,
                "sf_rnn_wideseq_fwd: the backward pass's gate-gradient buffer would exceed 2 GiB");
-    const int slab = sf_rnn_seq_slab_rows(kind, H, 0);
-    for (int r0 = 0; r0 < Cn; r0 += slab) {
-        const int r1 = Cn - r0 < slab ? Cn : r0 + slab;
-        int ng, rpg;
-        SF_REQUIRE(wide_plan(r1 - r0, &ng, &rpg), "sf_rnn_wideseq_fwd: no plan for %d rows", r1 - r0);
-        const int nsub = (rpg + 63) / 64;
-        int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_rnn_wideseq_fwd memset");
-        if (rc) return rc;
-        WideSeqFwd p{gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, ng, rpg, r0, r1,
-                     env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H};
-        const dim3 grid((unsigned)(ng * WIDE_NCOL)), block(256);
-        WIDESEQ_DISPATCH(k_wideseq_fwd);
-        rc = sf_launch_status("sf_rnn_wideseq_fwd");
-        if (rc) return rc;
-    }
-    return 0;
+    const SeqStrides ho(env_major, R, Cn, H);
+    WideSeqFwd p{gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, 0, 0, 0, 0, ho.rs, ho.ts};
+    return seq_run_slabs("sf_rnn_wideseq_fwd", FAM_WIDE, kind, 0, H, 0, seq_family_slab_rows(FAM_WIDE, H), p, stream);
 }
 
 extern "C" int sf_rnn_wideseq_bwd(int kind, const float *dout, const float *gates, const float *hprev, const float *cprev,
@@ -1252,21 +1264,26 @@ extern "C" int sf_rnn_wideseq_bwd(int kind, const float *dout, const float *gate
                      (uintptr_t)dgx | (uintptr_t)sync) & 3) == 0,
                "sf_rnn_wideseq_bwd: whh and the gate-gradient payload must be 16-byte aligned, every other operand 4-byte aligned");
     SF_REQUIRE((int64_t)R * Cn * (kind ? 4 : 3) * H * 4 < 0x7FFFFFF0LL, "sf_rnn_wideseq_bwd: gate-gradient buffer exceeds 2 GiB");
-    const int slab = sf_rnn_seq_slab_rows(kind, H, 1);
-    for (int r0 = 0; r0 < Cn; r0 += slab) {
-        const int r1 = Cn - r0 < slab ? Cn : r0 + slab;
-        int ng, rpg;
-        SF_REQUIRE(wide_plan(r1 - r0, &ng, &rpg), "sf_rnn_wideseq_bwd: no plan for %d rows", r1 - r0);
-        const int nsub = (rpg + 63) / 64;
-        int rc = sf_hip_status(hipMemsetAsync(sync, 0, SEQ_ABORT_SLOT * sizeof(uint32_t), STREAM(stream)), "sf_rnn_wideseq_bwd memset");
-        if (rc) return rc;
-        WideSeqBwd p{dout, gates, hprev, cprev, cout, keep, whh, dgx, pay, sync, R, Cn, ng, rpg, r0, r1,
-                     env_major ? (int64_t)R * H : (int64_t)H, env_major ? (int64_t)H : (int64_t)Cn * H};
-        const dim3 grid((unsigned)(ng * WIDE_NCOL)), block(256);
-        WIDESEQ_DISPATCH(k_wideseq_bwd);
-        rc = sf_launch_status("sf_rnn_wideseq_bwd");
-        if (rc) return rc;
-    }
+    const SeqStrides d(env_major, R, Cn, H);
+    WideSeqBwd p{dout, gates, hprev, cprev, cout, keep, whh, dgx, pay, sync, R, Cn, 0, 0, 0, 0, d.rs, d.ts};
+    return seq_run_slabs("sf_rnn_wideseq_bwd", FAM_WIDE, kind, 1, H, 0, seq_family_slab_rows(FAM_WIDE, H), p, stream);
+}
+
+// The name of the kernel a pass runs, as rocprofv3 prints it, from the plan and the table the entry points launch from.  A
+// call of more than one slab is named by its first, full slab (a shorter tail may run another instantiation).
+extern "C" int sf_rnn_seq_kernel_name(int family, int kind, int pass, int Cn, int H, int Kx, char *out, int cap) {
+    SF_REQUIRE(out && cap >= 48 && (kind == 0 || kind == 1) && (pass == 0 || pass == 1) && Cn > 0,
+               "sf_rnn_seq_kernel_name: bad args (kind=%d pass=%d Cn=%d)", kind, pass, Cn);
+    const int slab = seq_family_slab_rows(family, H);
+    SF_REQUIRE(slab > 0, "sf_rnn_seq_kernel_name: unsupported family=%d H=%d", family, H);
+    SF_REQUIRE(Kx == 0 || (family == FAM_PERSISTENT && pass == 0 && seq_fwd_x_plan(Cn, H, Kx)),
+               "sf_rnn_seq_kernel_name: unsupported shape Cn=%d H=%d Kx=%d (see sf_seq_fwd_x_supported)", Cn, H, Kx);
+    SeqLaunch L;
+    const int rows = Cn < slab ? Cn : slab;
+    SF_REQUIRE(seq_launch(family, kind, pass, rows, H, Kx, &L), "sf_rnn_seq_kernel_name: no plan for %d rows at H=%d", rows, H);
+    const char *name = seq_kernel_name(L, family, kind, pass);
+    SF_REQUIRE(name, "sf_rnn_seq_kernel_name: no kernel for the plan");
+    snprintf(out, (size_t)cap, "%s", name);
     return 0;
 }
 

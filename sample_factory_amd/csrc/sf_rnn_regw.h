@@ -336,20 +336,9 @@ __global__ __launch_bounds__(256, 1) void k_gru_seq_bwd_r(GruSeqBwd p) {
     }
 }
 
-// 16 row groups of H/32 work-groups; a row group is 32 or 64 rows (RT = 2 / 4 row tiles)
-int seq_plan_r(int Cn, int H, int *ngroups, int *rows_per_group) {
+// up to SEQ_MAX_GROUPS_R row groups of H/32 work-groups; a row group is 32 or 64 rows (RT = 2 / 4 row tiles)
+RowGroupPlan seq_plan_r(int Cn, int H) {
     static const int on = getenv("SF_SEQ_BWD_REGW") ? atoi(getenv("SF_SEQ_BWD_REGW")) : 1;
-    if (!on || (H != 512 && H != 256)) return 0;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return 0;
-    const int ncol = H / 32;
-    int ng = cus / ncol;
-    if (ng > SEQ_MAX_GROUPS_R) ng = SEQ_MAX_GROUPS_R;
-    const int need = (Cn + 31) / 32;
-    if (ng > need) ng = need;
-    if (ng < 1) return 0;
-    *ngroups = ng;
-    *rows_per_group = ((Cn + ng - 1) / ng + 31) / 32 * 32;
-    return *rows_per_group <= 64;
+    if (!on || (H != 512 && H != 256)) return {};
+    return row_group_plan(Cn, H / 32, SEQ_MAX_GROUPS_R, 32, 64);
 }

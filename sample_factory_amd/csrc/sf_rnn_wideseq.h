@@ -341,20 +341,6 @@ __global__ __launch_bounds__(256, 1) void k_wideseq_bwd(WideSeqBwd p) {
 }
 
 // row groups of one launch: 128 work-groups each, at most 8 (the counters in front of the abort word)
-int wide_groups_max() {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return 0;
-    const int ng = cus / WIDE_NCOL;
-    return ng > 8 ? 8 : ng;
-}
+int wide_groups_max() { return row_groups_max(WIDE_NCOL, 8); }
 // the plan of ONE launch over n rows (seq_plan's rule with 128 work-groups per group)
-int wide_plan(int n, int *ngroups, int *rows_per_group) {
-    int ng = wide_groups_max();
-    const int need = (n + 15) / 16;
-    if (ng > need) ng = need;
-    if (ng < 1) return 0;
-    *ngroups = ng;
-    *rows_per_group = ((n + ng - 1) / ng + 15) / 16 * 16;
-    return *rows_per_group <= 64 * SEQ_MAX_SUB;
-}
+RowGroupPlan wide_plan(int n) { return row_group_plan(n, WIDE_NCOL, 8, 16, 64 * SEQ_MAX_SUB); }

@@ -49,7 +49,7 @@ class sf_res_desc(C.Structure):
 SYMBOLS = [
     "sf_last_error", "sf_abi_version", "sf_valid_mask", "sf_gae_returns", "sf_moments", "sf_rms_update",
     "sf_rms_apply", "sf_vtrace", "sf_vtrace_masked", "sf_ppo_loss", "sf_ppo_loss_heads", "sf_ppo_loss_masked", "sf_loss_scalars", "sf_train_summaries", "sf_minibatch_indices", "sf_minibatch_expand", "sf_grad_sumsq",
-    "sf_adam_step", "sf_adam_step_dlr", "sf_lr_kl_adaptive", "sf_clock_probe", "sf_lamb_step", "sf_rnn_cell_fwd", "sf_rnn_cell_bwd", "sf_rows_add_scale", "sf_mlp2_fwd", "sf_rnn_store_state", "sf_rnn_chunk_setup", "sf_lstm_seq_supported", "sf_lstm_seq_fwd", "sf_lstm_seq_bwd", "sf_gru_seq_fwd", "sf_gru_seq_bwd", "sf_seq_fwd_x_supported", "sf_lstm_seq_fwd_x", "sf_gru_seq_fwd_x", "sf_rnn_rowseq_supported", "sf_rnn_rowseq_fwd", "sf_rnn_rowseq_bwd", "sf_rnn_wideseq_supported", "sf_rnn_seq_slab_rows", "sf_rnn_wideseq_fwd", "sf_rnn_wideseq_bwd", "sf_linear_fwd_dual_supported", "sf_linear_fwd_dual",
+    "sf_adam_step", "sf_adam_step_dlr", "sf_lr_kl_adaptive", "sf_clock_probe", "sf_lamb_step", "sf_rnn_cell_fwd", "sf_rnn_cell_bwd", "sf_rows_add_scale", "sf_mlp2_fwd", "sf_rnn_store_state", "sf_rnn_chunk_setup", "sf_lstm_seq_supported", "sf_lstm_seq_fwd", "sf_lstm_seq_bwd", "sf_gru_seq_fwd", "sf_gru_seq_bwd", "sf_seq_fwd_x_supported", "sf_lstm_seq_fwd_x", "sf_gru_seq_fwd_x", "sf_rnn_rowseq_supported", "sf_rnn_rowseq_fwd", "sf_rnn_rowseq_bwd", "sf_rnn_wideseq_supported", "sf_rnn_seq_slab_rows", "sf_rnn_wideseq_fwd", "sf_rnn_wideseq_bwd", "sf_rnn_seq_kernel_name", "sf_linear_fwd_dual_supported", "sf_linear_fwd_dual",
     "sf_obsnorm_moments", "sf_obsnorm_update", "sf_obsnorm_apply", "sf_sample_write_step",
     "sf_sample_write_step_tuple", "sf_sample_write_step_masked", "sf_sample_write_step_tuple_masked",
     "sf_traj_write_env_step", "sf_traj_write_env_step_active", "sf_rnn_store_state_held", "sf_synth_obs",
@@ -450,34 +450,34 @@ def lstm_seq_supported(Cn: int, H: int) -> bool:
     return bool(load().sf_lstm_seq_supported(int(Cn), int(H)))
 
 
-def _seq_key(op, R, Cn, H, steps, G=4, x_cols=0):
-    """profiling key of a fused LSTM pass in bench.py's layout: 2 * (steps*Cn) * 4H * H algorithmic FLOPs of the
-    recurrent products (forward: R steps; backward: R-1, the first step has no state in front of it).  A call beyond one
-    launch (row slabs: several launches, a shorter tail possibly on another instantiation) is keyed by the instantiation of
-    its FULL slabs; the timed region is the whole call."""
+# the families of fused recurrent passes, as sf_rnn_seq_kernel_name numbers them and as ActorCritic._rnn_saved names them
+RNN_FAMILIES = ("persistent", "row_owned", "persistent_wide")
+
+
+def rnn_seq_kernel_name(family: int, kind: int, pass_: int, Cn: int, H: int, Kx: int = 0) -> str:
+    """the kernel instantiation the library's own launch plan selects for this pass, as rocprofv3 prints it (a call of
+    more than one slab: the instantiation of its first, full slab)"""
+    buf = C.create_string_buffer(96)
+    _check(load().sf_rnn_seq_kernel_name(int(family), int(kind), int(pass_), int(Cn), int(H), int(Kx), buf, 96),
+           "sf_rnn_seq_kernel_name")
+    return buf.value.decode()
+
+
+def _rnn_key(op, family, kind, pass_, Cn, H, steps, x_cols=0):
+    """profiling key of a fused recurrent pass in bench.py's layout: 2 * (steps*Cn) * G*H * H algorithmic FLOPs of the
+    recurrent products (forward: R steps; backward: R-1, the first step has no state in front of it; K = H + x_cols: the
+    fused input projection's FLOPs count as the pass's own).  The timed region is the whole call, slabs included."""
     if not _keys_wanted():
         return None
-    kind, direction = op.split("_")
-    name = None
-    Cn_all, Cn = Cn, min(int(Cn), rnn_seq_slab_rows(0 if kind == "gru" else 1, H, 0 if direction == "fwd" else 1) or int(Cn))
-    if direction == "bwd" and int(os.environ.get("SF_SEQ_BWD_REGW", "1")) and H in (256, 512):
-        # csrc/sf_rnn_regw.h seq_plan_r: 32 hidden units per work-group, row groups of 32 / 64 rows
-        cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
-        ng = max(1, min(cus // (H // 32), 16, (Cn + 31) // 32))
-        rpg = ((Cn + ng - 1) // ng + 31) // 32 * 32
-        if rpg <= 64:
-            name = f"k_{kind}_seq_bwd_r<{int(H)}, {rpg // 16}>"
+    nk = ("rnn", family, int(kind), pass_, int(Cn), int(H), int(x_cols))
+    name = _names.get(nk)
     if name is None:
-        ng = min(8, (Cn + 15) // 16)
-        rpg = ((Cn + ng - 1) // ng + 15) // 16 * 16
-        nsub = {1: 1, 2: 2}.get((rpg + 63) // 64, 4)
-        name = f"k_{kind}_seq_{direction}<{int(H)}, 16, {nsub}" + (f", {x_cols // 16}>" if direction == "fwd" else ">")
-    # (K = H + x_cols: the fused input projection's FLOPs count as the pass's own)
-    return (op, int(steps * Cn_all), int(H + x_cols), 1, 1, int(G * H), 1, 1, 1, 1, name)
+        name = _names[nk] = rnn_seq_kernel_name(family, kind, pass_, Cn, H, x_cols)
+    return (op, int(steps * Cn), int(H + x_cols), 1, 1, int((4 if kind else 3) * H), 1, 1, 1, 1, name)
 
 
 def lstm_seq_fwd(gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, H, env_major=False) -> None:
-    with _timed(_seq_key("lstm_fwd", R, Cn, H, R)):
+    with _timed(_rnn_key("lstm_fwd", 0, 1, 0, Cn, H, R)):
         _check(load().sf_lstm_seq_fwd(ptr(gx, "f32", "gx"), ptr(whh, "f32", "whh"), ptr(bhh, "f32", "bhh"),
                                       ptr(keep, "f32", "keep"), ptr(gates, "f32", "gates"), ptr(hprev, "f32", "hprev"),
                                       ptr(hout, "f32", "hout"), ptr(cprev, "f32", "cprev"), ptr(cout, "f32", "cout"),
@@ -486,7 +486,7 @@ def lstm_seq_fwd(gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, C
 
 
 def lstm_seq_bwd(dout, gates, cprev, cout, keep, whh, dgx, sync, R, Cn, H, env_major=False) -> None:
-    with _timed(_seq_key("lstm_bwd", R, Cn, H, R - 1)):
+    with _timed(_rnn_key("lstm_bwd", 0, 1, 1, Cn, H, R - 1)):
         _check(load().sf_lstm_seq_bwd(ptr(dout, "f32", "dout"), ptr(gates, "f32", "gates"), ptr(cprev, "f32", "cprev"),
                                       ptr(cout, "f32", "cout"), ptr(keep, "f32", "keep"), ptr(whh, "f32", "whh"),
                                       ptr(dgx, "f32", "dgx"),
@@ -495,7 +495,7 @@ def lstm_seq_bwd(dout, gates, cprev, cout, keep, whh, dgx, sync, R, Cn, H, env_m
 
 
 def gru_seq_fwd(gx, whh, bhh, keep, gates, hprev, hout, sync, R, Cn, H, env_major=False) -> None:
-    with _timed(_seq_key("gru_fwd", R, Cn, H, R, 3)):
+    with _timed(_rnn_key("gru_fwd", 0, 0, 0, Cn, H, R)):
         _check(load().sf_gru_seq_fwd(ptr(gx, "f32", "gx"), ptr(whh, "f32", "whh"), ptr(bhh, "f32", "bhh"),
                                      ptr(keep, "f32", "keep"), ptr(gates, "f32", "gates"), ptr(hprev, "f32", "hprev"),
                                      ptr(hout, "f32", "hout"), ptr(sync, "i32", "sync"), int(R), int(Cn), int(H),
@@ -525,7 +525,7 @@ def seq_fwd_x_supported(Cn: int, H: int, Kx: int) -> bool:
 def lstm_seq_fwd_x(x, wih_t, bih, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, H, env_major=False) -> None:
     """sf_lstm_seq_fwd with the input projection fused in: x [R*Cn, Kx] time-major, wih_t [4H, Kx], bih [4H]"""
     Kx = int(wih_t.shape[1])
-    with _timed(_seq_key("lstm_fwd", R, Cn, H, R, x_cols=Kx)):
+    with _timed(_rnn_key("lstm_fwd", 0, 1, 0, Cn, H, R, x_cols=Kx)):
         _check(load().sf_lstm_seq_fwd_x(ptr(x, "f32", "x"), ptr(wih_t, "f32", "wih_t"), ptr(bih, "f32", "bih"), Kx,
                                         ptr(whh, "f32", "whh"), ptr(bhh, "f32", "bhh"), ptr(keep, "f32", "keep"),
                                         ptr(gates, "f32", "gates"), ptr(hprev, "f32", "hprev"), ptr(hout, "f32", "hout"),
@@ -535,7 +535,7 @@ def lstm_seq_fwd_x(x, wih_t, bih, whh, bhh, keep, gates, hprev, hout, cprev, cou
 
 def gru_seq_fwd_x(x, wih_t, bih, whh, bhh, keep, gates, hprev, hout, sync, R, Cn, H, env_major=False) -> None:
     Kx = int(wih_t.shape[1])
-    with _timed(_seq_key("gru_fwd", R, Cn, H, R, 3, x_cols=Kx)):
+    with _timed(_rnn_key("gru_fwd", 0, 0, 0, Cn, H, R, x_cols=Kx)):
         _check(load().sf_gru_seq_fwd_x(ptr(x, "f32", "x"), ptr(wih_t, "f32", "wih_t"), ptr(bih, "f32", "bih"), Kx,
                                        ptr(whh, "f32", "whh"), ptr(bhh, "f32", "bhh"), ptr(keep, "f32", "keep"),
                                        ptr(gates, "f32", "gates"), ptr(hprev, "f32", "hprev"), ptr(hout, "f32", "hout"),
@@ -544,7 +544,7 @@ def gru_seq_fwd_x(x, wih_t, bih, whh, bhh, keep, gates, hprev, hout, sync, R, Cn
 
 
 def gru_seq_bwd(dout, gates, hprev, keep, whh, dgx, dgh, sync, R, Cn, H, env_major=False) -> None:
-    with _timed(_seq_key("gru_bwd", R, Cn, H, R - 1, 3)):
+    with _timed(_rnn_key("gru_bwd", 0, 0, 1, Cn, H, R - 1)):
         _check(load().sf_gru_seq_bwd(ptr(dout, "f32", "dout"), ptr(gates, "f32", "gates"), ptr(hprev, "f32", "hprev"),
                                      ptr(keep, "f32", "keep"), ptr(whh, "f32", "whh"), ptr(dgx, "f32", "dgx"),
                                      ptr(dgh, "f32", "dgh"), ptr(sync, "i32", "sync"), int(R), int(Cn), int(H),
@@ -555,17 +555,9 @@ def rnn_rowseq_supported(kind: int, Cn: int, H: int) -> bool:
     return bool(load().sf_rnn_rowseq_supported(int(kind), int(Cn), int(H)))
 
 
-def _rowseq_key(direction, kind, R, Cn, H, steps):
-    """profiling key of a row-owned pass, in _seq_key's layout"""
-    if not _keys_wanted():
-        return None
-    G = 4 if kind else 3
-    return (f"rowseq_{direction}", int(steps * Cn), int(H), 1, 1, int(G * H), 1, 1, 1, 1, f"k_rowseq_{direction}<{int(kind)}, {int(H)}>")
-
-
 def rnn_rowseq_fwd(kind, gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, R, Cn, H, env_major=False) -> None:
     """sf_rnn_rowseq_fwd: the forward time loop of a narrow GRU (kind 0) / LSTM (1) core in one launch, no sync buffer"""
-    with _timed(_rowseq_key("fwd", kind, R, Cn, H, R)):
+    with _timed(_rnn_key("rowseq_fwd", 1, kind, 0, Cn, H, R)):
         _check(load().sf_rnn_rowseq_fwd(int(kind), ptr(gx, "f32", "gx"), ptr(whh, "f32", "whh"), ptr(bhh, "f32", "bhh"),
                                         ptr(keep, "f32", "keep"), ptr(gates, "f32", "gates"), ptr(hprev, "f32", "hprev"),
                                         ptr(hout, "f32", "hout"), ptr(cprev, "f32", "cprev"), ptr(cout, "f32", "cout"),
@@ -575,7 +567,7 @@ def rnn_rowseq_fwd(kind, gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, R,
 def rnn_rowseq_bwd(kind, dout, gates, hprev, cprev, cout, keep, whh, dgx, dgh, R, Cn, H, env_major=False) -> None:
     """sf_rnn_rowseq_bwd: the backward time loop of the same pass; writes dgx and, for a GRU, dgh (None for an LSTM, whose two
     gradients are equal); hprev may be None for an LSTM, cprev / cout for a GRU"""
-    with _timed(_rowseq_key("bwd", kind, R, Cn, H, R - 1)):
+    with _timed(_rnn_key("rowseq_bwd", 1, kind, 1, Cn, H, R - 1)):
         _check(load().sf_rnn_rowseq_bwd(int(kind), ptr(dout, "f32", "dout"), ptr(gates, "f32", "gates"),
                                         ptr(hprev, "f32", "hprev"), ptr(cprev, "f32", "cprev"), ptr(cout, "f32", "cout"),
                                         ptr(keep, "f32", "keep"), ptr(whh, "f32", "whh"), ptr(dgx, "f32", "dgx"),
@@ -592,22 +584,9 @@ def rnn_seq_slab_rows(kind: int, H: int, pass_: int) -> int:
     return int(load().sf_rnn_seq_slab_rows(int(kind), int(H), int(pass_)))
 
 
-def _wideseq_key(direction, kind, R, Cn, H, steps):
-    """profiling key of a wide pass, in _seq_key's layout (the instantiation of a full slab, or of the whole call if smaller)"""
-    if not _keys_wanted():
-        return None
-    G = 4 if kind else 3
-    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
-    n = min(int(Cn), rnn_seq_slab_rows(kind, H, 0 if direction == "fwd" else 1))
-    ng = max(1, min(cus // 128, 8, (n + 15) // 16))
-    rpg = ((n + ng - 1) // ng + 15) // 16 * 16
-    nsub = {1: 1, 2: 2}.get((rpg + 63) // 64, 4)
-    return (f"wideseq_{direction}", int(steps * Cn), int(H), 1, 1, int(G * H), 1, 1, 1, 1, f"k_wideseq_{direction}<{int(kind)}, {nsub}>")
-
-
 def rnn_wideseq_fwd(kind, gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, H, env_major=False) -> None:
     """sf_rnn_wideseq_fwd: the forward time loop of a GRU (kind 0) / LSTM (1) core of width 1024 as persistent launches"""
-    with _timed(_wideseq_key("fwd", kind, R, Cn, H, R)):
+    with _timed(_rnn_key("wideseq_fwd", 2, kind, 0, Cn, H, R)):
         _check(load().sf_rnn_wideseq_fwd(int(kind), ptr(gx, "f32", "gx"), ptr(whh, "f32", "whh"), ptr(bhh, "f32", "bhh"),
                                          ptr(keep, "f32", "keep"), ptr(gates, "f32", "gates"), ptr(hprev, "f32", "hprev"),
                                          ptr(hout, "f32", "hout"), ptr(cprev, "f32", "cprev"), ptr(cout, "f32", "cout"),
@@ -617,12 +596,59 @@ def rnn_wideseq_fwd(kind, gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, s
 
 def rnn_wideseq_bwd(kind, dout, gates, hprev, cprev, cout, keep, whh, dgx, dgh, sync, R, Cn, H, env_major=False) -> None:
     """sf_rnn_wideseq_bwd: the backward time loop of the same pass; operands as rnn_rowseq_bwd, plus the sync buffer"""
-    with _timed(_wideseq_key("bwd", kind, R, Cn, H, R - 1)):
+    with _timed(_rnn_key("wideseq_bwd", 2, kind, 1, Cn, H, R - 1)):
         _check(load().sf_rnn_wideseq_bwd(int(kind), ptr(dout, "f32", "dout"), ptr(gates, "f32", "gates"),
                                          ptr(hprev, "f32", "hprev"), ptr(cprev, "f32", "cprev"), ptr(cout, "f32", "cout"),
                                          ptr(keep, "f32", "keep"), ptr(whh, "f32", "whh"), ptr(dgx, "f32", "dgx"),
                                          ptr(dgh, "f32", "dgh"), ptr(sync, "i32", "sync"), int(R), int(Cn), int(H),
                                          int(bool(env_major)), stream()), "sf_rnn_wideseq_bwd")
+
+
+def rnn_seq_family(kind: int, Cn: int, H: int) -> Optional[str]:
+    """the family of fused passes OFFERED for this core and chunk count (one of RNN_FAMILIES), None: per-step launches.  The
+    three queries are asked in the order the families were introduced (as module globals, looked up at call time: a test may
+    replace one)."""
+    if lstm_seq_supported(Cn, H):
+        return "persistent"
+    if rnn_rowseq_supported(kind, Cn, H):
+        return "row_owned"
+    if rnn_wideseq_supported(kind, Cn, H):
+        return "persistent_wide"
+    return None
+
+
+def rnn_seq_fwd(family, kind, gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, H, env_major=False,
+                x=None, wih_t=None, bih=None) -> None:
+    """the forward pass of `family` (rnn_seq_family) on the operands of rnn_rowseq_fwd / rnn_wideseq_fwd; sync: None for the
+    row-owned family.  x, wih_t, bih instead of gx (persistent family only): the form with the input projection fused in"""
+    if family == "row_owned":
+        rnn_rowseq_fwd(kind, gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, R, Cn, H, env_major)
+    elif family == "persistent_wide":
+        rnn_wideseq_fwd(kind, gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, H, env_major)
+    elif family != "persistent":
+        raise SfHipError(f"rnn_seq_fwd: no family {family!r}")
+    elif x is not None and kind == 1:
+        lstm_seq_fwd_x(x, wih_t, bih, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, H, env_major)
+    elif x is not None:
+        gru_seq_fwd_x(x, wih_t, bih, whh, bhh, keep, gates, hprev, hout, sync, R, Cn, H, env_major)
+    elif kind == 1:
+        lstm_seq_fwd(gx, whh, bhh, keep, gates, hprev, hout, cprev, cout, sync, R, Cn, H, env_major)
+    else:
+        gru_seq_fwd(gx, whh, bhh, keep, gates, hprev, hout, sync, R, Cn, H, env_major)
+
+
+def rnn_seq_bwd(family, kind, dout, gates, hprev, cprev, cout, keep, whh, dgx, dgh, sync, R, Cn, H, env_major=False) -> None:
+    """the backward pass of `family` on the operands of rnn_rowseq_bwd / rnn_wideseq_bwd (dgh: GRU only)"""
+    if family == "row_owned":
+        rnn_rowseq_bwd(kind, dout, gates, hprev, cprev, cout, keep, whh, dgx, dgh, R, Cn, H, env_major)
+    elif family == "persistent_wide":
+        rnn_wideseq_bwd(kind, dout, gates, hprev, cprev, cout, keep, whh, dgx, dgh, sync, R, Cn, H, env_major)
+    elif family != "persistent":
+        raise SfHipError(f"rnn_seq_bwd: no family {family!r}")
+    elif kind == 1:
+        lstm_seq_bwd(dout, gates, cprev, cout, keep, whh, dgx, sync, R, Cn, H, env_major)
+    else:  # GRU: the candidate gate's recurrent part is scaled by r -> W_hh sees its own gate gradients
+        gru_seq_bwd(dout, gates, hprev, keep, whh, dgx, dgh, sync, R, Cn, H, env_major)
 
 
 def rows_add_scale(a, b, keep, Cn, H, y) -> None:

@@ -1025,46 +1025,29 @@ class ActorCritic(NativeTower):
         if kind == 1:
             lib.copy_rows(Cprev[0], h0[:, H:])
         out = self._buf((tag, "core_out", li), (n, H))
-        fused = _LSTM_SEQ and lib.lstm_seq_supported(Cn, H)
-        if fused:  # ONE persistent launch for the whole time loop (csrc/sf_rnn.hip): W_hh slices resident in LDS; the
-            # core output is written in the minibatch's own row order (chunk-major), no transpose copy
-            sync = self._seq_sync_buf()
+        # the fused passes walk the whole time loop in one call (lib.rnn_seq_family: persistent launches with the W_hh slices
+        # resident in LDS, csrc/sf_rnn.hip; row-owned tiles for narrow cores, csrc/sf_rnn_rowseq.h; 8-unit work-groups at width
+        # 1024, csrc/sf_rnn_wideseq.h) and write the core output in the minibatch's own row order (chunk-major), no transpose copy
+        family = lib.rnn_seq_family(kind, Cn, H) if _LSTM_SEQ else None
+        if family is not None:
+            # the row-owned passes hand nothing between work-groups: no sync buffer, no abort.  x_tm: the input projection
+            # x W_ih^T + b_ih runs inside the same launch
+            sync = None if family == "row_owned" else self._seq_sync_buf()
             Li = self.layers[li]
-            if x_tm is not None and kind == 1:   # ... and the input projection x W_ih^T + b_ih inside the same launch
-                lib.lstm_seq_fwd_x(x_tm, Li.wt, Li.b, Lh.w, Lh.b, keep, gates, Hprev, out, Cprev, Cout, sync, R, Cn, H, env_major=True)
-            elif x_tm is not None:
-                lib.gru_seq_fwd_x(x_tm, Li.wt, Li.b, Lh.w, Lh.b, keep, gates, Hprev, out, sync, R, Cn, H, env_major=True)
-            elif kind == 1:
-                lib.lstm_seq_fwd(GX, Lh.w, Lh.b, keep, gates, Hprev, out, Cprev, Cout, sync, R, Cn, H, env_major=True)
-            else:
-                lib.gru_seq_fwd(GX, Lh.w, Lh.b, keep, gates, Hprev, out, sync, R, Cn, H, env_major=True)
-            self._rnn_saved_l[li] = self._rnn_saved = dict(gates=gates, Hprev=Hprev, Cprev=Cprev, Cout=Cout, keep=keep, R=R, Cn=Cn,
-                                                           fused=True, family="persistent")
-            return out
-        if _LSTM_SEQ and lib.rnn_rowseq_supported(kind, Cn, H):  # narrow cores: one launch, a work-group owns a tile of chunk
-            # rows for all R steps (csrc/sf_rnn_rowseq.h); no hand-off between work-groups, so no sync buffer and no abort
-            lib.rnn_rowseq_fwd(kind, GX, Lh.w, Lh.b, keep, gates, Hprev, out, Cprev, Cout, R, Cn, H, env_major=True)
-            self._rnn_saved_l[li] = self._rnn_saved = dict(gates=gates, Hprev=Hprev, Cprev=Cprev, Cout=Cout, keep=keep, R=R, Cn=Cn,
-                                                           fused=True, family="row_owned")
-            return out
-        if _LSTM_SEQ and lib.rnn_wideseq_supported(kind, Cn, H):  # width 1024: persistent launches with 8 hidden units per
-            # work-group (csrc/sf_rnn_wideseq.h); same sync buffer and abort word as the persistent family
-            lib.rnn_wideseq_fwd(kind, GX, Lh.w, Lh.b, keep, gates, Hprev, out, Cprev, Cout, self._seq_sync_buf(), R, Cn, H,
-                                env_major=True)
-            self._rnn_saved_l[li] = self._rnn_saved = dict(gates=gates, Hprev=Hprev, Cprev=Cprev, Cout=Cout, keep=keep, R=R, Cn=Cn,
-                                                           fused=True, family="persistent_wide")
-            return out
-        Hout = self._buf((tag, "Hout", li), (R, Cn, H))
-        gh = self._buf((tag, "gh_seq", li), (Cn, GH))
-        GXv = GX.view(R, Cn, GH)
-        for t in range(R):
-            lib.conv_fwd_raw(Hprev[t], H, None, 0, Lh.w, Lh.b, gh, Cn, Lh.desc)
-            lib.rnn_cell_fwd(kind, GXv[t], gh, Hprev[t], H, Cprev[t] if kind == 1 else None, H, keep[t], Cn, H,
-                             gates[t], Hout[t], Cout[t] if kind == 1 else None, Hprev[t + 1],
-                             Cprev[t + 1] if kind == 1 else None)
-        out.view(Cn, R, H).copy_(Hout.transpose(0, 1))
+            lib.rnn_seq_fwd(family, kind, GX, Lh.w, Lh.b, keep, gates, Hprev, out, Cprev, Cout, sync, R, Cn, H, env_major=True,
+                            x=x_tm, wih_t=Li.wt, bih=Li.b)
+        else:
+            Hout = self._buf((tag, "Hout", li), (R, Cn, H))
+            gh = self._buf((tag, "gh_seq", li), (Cn, GH))
+            GXv = GX.view(R, Cn, GH)
+            for t in range(R):
+                lib.conv_fwd_raw(Hprev[t], H, None, 0, Lh.w, Lh.b, gh, Cn, Lh.desc)
+                lib.rnn_cell_fwd(kind, GXv[t], gh, Hprev[t], H, Cprev[t] if kind == 1 else None, H, keep[t], Cn, H,
+                                 gates[t], Hout[t], Cout[t] if kind == 1 else None, Hprev[t + 1],
+                                 Cprev[t + 1] if kind == 1 else None)
+            out.view(Cn, R, H).copy_(Hout.transpose(0, 1))
         self._rnn_saved_l[li] = self._rnn_saved = dict(gates=gates, Hprev=Hprev, Cprev=Cprev, Cout=Cout, keep=keep, R=R, Cn=Cn,
-                                                       fused=False, family="per_step")
+                                                       fused=family is not None, family=family or "per_step")
         return out
 
     def _rnn_sequence_bwd(self, li, d_core, n):
@@ -1074,26 +1057,13 @@ class ActorCritic(NativeTower):
         R, Cn, keep = sv["R"], sv["Cn"], sv["keep"]
         GH = Lh.N
         dGX = self._buf(("g", "dGX", li), (R, Cn, GH))
-        if sv.get("fused"):  # the whole backward time loop in one persistent launch (cell backward + W_hh^T product + carries)
-            dGH = dGX
+        if sv.get("fused"):  # the whole backward time loop in one call (cell backward + W_hh^T product + carries)
+            # GRU: the candidate gate's recurrent part is scaled by r -> W_hh sees its own gate gradients
+            dGH = self._buf(("g", "dGH", li), (R, Cn, GH)) if kind == 0 else dGX
             dOut = d_core if d_core.is_contiguous() else d_core.contiguous()  # read in the minibatch's row order
-            if sv["family"] == "row_owned":
-                if kind == 0:
-                    dGH = self._buf(("g", "dGH", li), (R, Cn, GH))
-                lib.rnn_rowseq_bwd(kind, dOut, sv["gates"], sv["Hprev"], sv["Cprev"], sv["Cout"], keep, Lh.w, dGX,
-                                   dGH if kind == 0 else None, R, Cn, H, env_major=True)
-            elif sv["family"] == "persistent_wide":
-                if kind == 0:
-                    dGH = self._buf(("g", "dGH", li), (R, Cn, GH))
-                lib.rnn_wideseq_bwd(kind, dOut, sv["gates"], sv["Hprev"], sv["Cprev"], sv["Cout"], keep, Lh.w, dGX,
-                                    dGH if kind == 0 else None, self._seq_sync_buf(), R, Cn, H, env_major=True)
-            elif kind == 1:
-                sync = self._seq_sync_buf()
-                lib.lstm_seq_bwd(dOut, sv["gates"], sv["Cprev"], sv["Cout"], keep, Lh.w, dGX, sync, R, Cn, H, env_major=True)
-            else:  # GRU: the candidate gate's recurrent part is scaled by r -> W_hh sees its own gate gradients
-                sync = self._seq_sync_buf()
-                dGH = self._buf(("g", "dGH", li), (R, Cn, GH))
-                lib.gru_seq_bwd(dOut, sv["gates"], sv["Hprev"], keep, Lh.w, dGX, dGH, sync, R, Cn, H, env_major=True)
+            sync = None if sv["family"] == "row_owned" else self._seq_sync_buf()
+            lib.rnn_seq_bwd(sv["family"], kind, dOut, sv["gates"], sv["Hprev"], sv["Cprev"], sv["Cout"], keep, Lh.w, dGX,
+                            dGH if kind == 0 else None, sync, R, Cn, H, env_major=True)
             ws = self._workspace(lib.conv_wgrad_workspace(n, Lh.desc))
             lib.conv_wgrad_raw(sv["Hprev"][:R].reshape(n, H), H, None, 0, dGH.view(n, GH), Lh.gw, Lh.gb, n, Lh.desc, ws)
             return dGX.view(n, GH)
