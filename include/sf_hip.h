@@ -381,6 +381,32 @@ int sf_traj_write_env_step_active(const float *rewards, const uint8_t *terminate
                                   int32_t *ep_len, double *ep_stats, const uint8_t *active_in, uint8_t *active_state,
                                   void *stream);
 
+/* ---- statistics an env defines itself (csrc/sf_traj.hip) ------------------------------------
+ * batched_sampling.py:235-251: every per-agent tensor of a vectorised env's `infos` is a statistic, taken at the envs
+ * that finished (`value[finished]`); runner.py:263-278 averages them.  Here the values stay on the device: one launch
+ * per env step adds them to per-channel accumulators that the runner reads back with ep_stats, once per report.
+ * A channel is one such tensor: element b of channel k is ptr[k][b * stride[k]] (stride in ELEMENTS of its dtype). */
+#define SF_EPSTAT_MAX_CHANNELS 16
+#define SF_EPSTAT_F32 0
+#define SF_EPSTAT_F64 1
+#define SF_EPSTAT_I32 2
+#define SF_EPSTAT_I64 3
+#define SF_EPSTAT_U8 4 /* u8 and 1-byte bool */
+typedef struct {
+    const void *ptr[SF_EPSTAT_MAX_CHANNELS]; /* device pointers */
+    int64_t stride[SF_EPSTAT_MAX_CHANNELS];  /* >= 1, in elements */
+    int32_t dtype[SF_EPSTAT_MAX_CHANNELS];   /* SF_EPSTAT_* */
+} sf_epstat_channels;
+/* For every b < B with terminated[b] | truncated[b] (and active[b] != 0 where active is given) and every channel k < K:
+ * acc[k][0] += (double)value_k[b], acc[k][1] += 1.  acc: device double [K][2]; the call adds to it and never zeroes it.
+ * h_ch is read on the host and travels by value in the launch: it may be reused as soon as the call returns.
+ * One launch, one lane per env: the values are converted to f64 on load and summed over the wave and the block in f64,
+ * then one atomicAdd pair per channel and block (blocks without a finished env add nothing).
+ * Refused before any launch (SF_ERR_ARG): K outside 1 .. SF_EPSTAT_MAX_CHANNELS; a null h_ch, terminated, truncated, acc
+ * or channel pointer; B < 0; a stride < 1; an unknown dtype code.  B == 0: SF_OK, nothing is launched. */
+int sf_episode_stats_add(const sf_epstat_channels *h_ch, int K, const uint8_t *terminated, const uint8_t *truncated,
+                         const uint8_t *active /* or NULL */, int64_t B, double *acc, void *stream);
+
 /* Ant-shaped continuous stand-in env (config 5): f32 observations [B, D], Box actions [B, A] (row stride act_stride
  * floats, e.g. traj.actions[:, t]).  One launch per env step writes the next observation into `state` (the env's own
  * [B, D] copy) AND into obs_out (row stride out_stride floats = slot t+1 of the slab); reset != 0: fresh observations

@@ -20,10 +20,13 @@ import numpy as np
 import torch
 
 from sample_factory_amd import lib
+from sample_factory_amd.algo.sampling.episode_stats import (IS_ACTIVE, HostEpisodeStats, flatten_infos, merge_sums,
+                                                            per_env_array, stat_key)
 from sample_factory_amd.algo.sampling.obs_ingest import KeyRoute, ObsIngestPlan
 from sample_factory_amd.algo.sampling.parallel_env import infos_is_active
 from sample_factory_amd.algo.utils.tensor_dict import TensorDict
 from sample_factory_amd.envs.spaces import action_head_sizes, heads_mixed, is_box, split_tuple_actions
+from sample_factory_amd.utils.utils import log
 
 
 def tracks_inactive_agents(cfg, env, multi_key: bool = False) -> bool:
@@ -39,6 +42,8 @@ def tracks_inactive_agents(cfg, env, multi_key: bool = False) -> bool:
 
 
 class BatchedVectorEnvRunner:
+    MAX_STAT_CHANNELS = 64  # device channels of env-defined statistics one runner accumulates (further leaves: a warning)
+
     def __init__(self, cfg, env_info, env, actor_critic, traj: TensorDict, policy_id: int = 0,
                  policy_versions: Optional[torch.Tensor] = None, sample_seed: int = 0, row0: int = 0, tag: str = "inf"):
         self.cfg, self.env_info, self.env, self.ac = cfg, env_info, env, actor_critic
@@ -68,7 +73,18 @@ class BatchedVectorEnvRunner:
                                        device=dev)
         self.ep_return = torch.zeros(self.B, dtype=torch.float32, device=dev)
         self.ep_len = torch.zeros(self.B, dtype=torch.int32, device=dev)
-        self.ep_stats = torch.zeros(3, dtype=torch.float64, device=dev)  # sum_return, sum_len, episodes
+        # one read-back buffer: [sum_return, sum_len, episodes | {sum, count} per device channel of the env's own statistics]
+        self._stats_all = torch.zeros(3 + 2 * self.MAX_STAT_CHANNELS, dtype=torch.float64, device=dev)
+        self.ep_stats = self._stats_all[:3]  # sum_return, sum_len, episodes
+        # statistics the env defines itself.  Dict infos: the channel set is fixed at the first step —
+        # _stat_dev: flattened keys of the device leaves (channel k adds to _stats_all[3 + 2 k:][:2]), _stat_host: of the host
+        # leaves; list infos and worker replies go to host_stats.  None: no step has been seen yet.
+        self._stat_dev: Optional[list] = None
+        self._stat_index: Dict[str, int] = {}
+        self._stat_host: set = set()
+        self._stat_seen: set = set()    # every flattened key of the first infos, whatever its shape
+        self._stat_warned: set = set()
+        self.host_stats = HostEpisodeStats()
         self.sample_seed = int(sample_seed)
         self.row0 = int(row0)  # global index of this replica's first env (Philox key of the action sampler)
         self.global_step = 0
@@ -338,6 +354,8 @@ class BatchedVectorEnvRunner:
                 self.ingest_prof["env_step_s"] = self.ingest_prof.get("env_step_s", 0.0) + time.perf_counter() - t0
             self._store_obs(o, t + 1)
             if self.host_env:
+                if info:  # the env's own statistics: host arithmetic on host flags, nothing is launched
+                    self._host_infos(info, term, trunc)
                 self._to_device("rew", rew, self._rew)
                 self._to_device("term", term, self._term)
                 self._to_device("trunc", trunc, self._trunc)
@@ -353,6 +371,8 @@ class BatchedVectorEnvRunner:
                 rew = torch.as_tensor(rew, dtype=torch.float32, device=self.device).contiguous()
                 term = torch.as_tensor(term, dtype=torch.bool, device=self.device).contiguous()
                 trunc = torch.as_tensor(trunc, dtype=torch.bool, device=self.device).contiguous()
+                if info and isinstance(info, dict):  # the env's own statistics, summed where they live (one launch)
+                    self._device_infos(info, term, trunc)
         parts = self.ac.new_rnn_parts_of(self.tag) if self.rnn else None
         if (self.rnn and parts is None) or not (self.zero_copy or self.host_env):
             prog = rec_key = None  # torch model path (the state store is a torch op) / env outputs in fresh tensors every step
@@ -383,6 +403,93 @@ class BatchedVectorEnvRunner:
             return v.contiguous() if v.dtype in (torch.bool, torch.uint8) else (v != 0)
         flags = infos_is_active(info, self.B)
         return self._all_active if flags is None else torch.as_tensor(flags, device=self.device)
+
+    # ---- statistics the env defines itself (batched_sampling.py:235-251, non_batched_sampling.py:290-301)
+    def _fix_stat_channels(self, info: dict) -> None:
+        """the first dict infos fix the channel set: device leaves with one numeric / bool element per agent are channels
+        of sf_episode_stats_add, host leaves of that shape go to the host accumulator, everything else is ignored"""
+        self._stat_dev, self._stat_seen = [], set()
+        for key, v in flatten_infos(info):
+            self._stat_seen.add(key)
+            if key == IS_ACTIVE:
+                continue
+            if isinstance(v, torch.Tensor) and v.is_cuda:
+                if v.numel() == self.B and v.dtype in lib._EPSTAT_DT:
+                    if len(self._stat_dev) < self.MAX_STAT_CHANNELS:
+                        self._stat_dev.append(key)
+                    else:
+                        log.warning(f"infos[{key!r}]: more than {self.MAX_STAT_CHANNELS} per-agent statistics, ignored")
+            elif per_env_array(v, self.B) is not None:
+                self._stat_host.add(key)
+        self._stat_index = {key: k for k, key in enumerate(self._stat_dev)}
+
+    def _late_stat_key(self, key: str, v) -> None:
+        """a key that first appears after the channel set was fixed: ignored, one warning per key"""
+        self._stat_seen.add(key)
+        n = v.numel() if isinstance(v, torch.Tensor) else getattr(v, "size", 0)
+        if key != IS_ACTIVE and n == self.B and key not in self._stat_warned:
+            self._stat_warned.add(key)
+            log.warning(f"infos[{key!r}] first appeared after the statistics of this env were fixed at its first step: "
+                        "ignored (report every key from the first step on)")
+
+    def _device_infos(self, info: dict, term: torch.Tensor, trunc: torch.Tensor) -> None:
+        """dict infos of a device env at one step; term / trunc: contiguous device bool [B]"""
+        if self._stat_dev is None:
+            self._fix_stat_channels(info)
+        chans, host = [], False
+        for key, v in flatten_infos(info):
+            k = self._stat_index.get(key)
+            if k is not None:
+                if isinstance(v, torch.Tensor) and v.is_cuda and v.numel() == self.B and v.dtype in lib._EPSTAT_DT:
+                    chans.append((k, v.reshape(-1)))
+            elif key in self._stat_host:
+                host = True
+            elif key not in self._stat_seen:
+                self._late_stat_key(key, v)
+        chans.sort(key=lambda c: c[0])
+        i = 0
+        while i < len(chans):  # (a key missing at this step splits the launch: acc rows are contiguous per call)
+            j = i + 1
+            while j < len(chans) and chans[j][0] == chans[j - 1][0] + 1:
+                j += 1
+            k0 = chans[i][0]
+            lib.episode_stats_add([c[1] for c in chans[i:j]], term, trunc, None,
+                                  self._stats_all[3 + 2 * k0:3 + 2 * (k0 + j - i)].view(j - i, 2))
+            i = j
+        if host:  # host arrays in a device env's infos need the flags on the host: the one sync such an env asks for
+            self.host_stats.add_dict_infos(info, (term | trunc).cpu().numpy(), self._stat_host)
+
+    def _host_infos(self, info, term, trunc) -> None:
+        """infos of a host env at one step; term / trunc: what the env returned (host arrays)"""
+        if isinstance(info, (list, tuple)):
+            done = np.asarray(term).reshape(-1) | np.asarray(trunc).reshape(-1)
+            if done.any():
+                self.host_stats.add_list_infos(info, done)
+        elif isinstance(info, dict):
+            if self._stat_dev is None:
+                self._fix_stat_channels(info)
+            if self._stat_host:
+                done = np.asarray(term).reshape(-1) | np.asarray(trunc).reshape(-1)
+                self.host_stats.add_dict_infos(info, done, self._stat_host)
+            for key, v in flatten_infos(info):
+                if key not in self._stat_seen:
+                    self._late_stat_key(key, v)
+
+    def read_stats(self):
+        """(ep_stats as a host tensor, {key: [sum, count]} of the env's own statistics) since the last call, then reset:
+        ONE device-to-host copy of ep_stats and the channel accumulators behind it, on the current stream"""
+        n = 3 + 2 * len(self._stat_dev or ())
+        dev = self._stats_all[:n]
+        host = dev.cpu()
+        dev.zero_()
+        sums = self.host_stats.pop()
+        pop = getattr(self.env, "pop_episode_stats", None)  # env worker processes / inline instance steppers
+        if pop is not None:
+            merge_sums(sums, pop())
+        for k, key in enumerate(self._stat_dev or ()):
+            if float(host[3 + 2 * k + 1]) > 0:
+                merge_sums(sums, {stat_key(key): [float(host[3 + 2 * k]), float(host[3 + 2 * k + 1])]})
+        return host[:3], sums
 
     def _record_step(self, t: int, rew, term, trunc, active_in=None) -> None:
         """env outputs of step t -> slab (rewards shaped, dones, episode statistics), next-step recurrent state;

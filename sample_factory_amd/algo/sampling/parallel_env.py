@@ -29,6 +29,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple
 
 import numpy as np
 
+from sample_factory_amd.algo.sampling.episode_stats import HostEpisodeStats
 from sample_factory_amd.envs.env_utils import RewardShapingInterface
 from sample_factory_amd.envs.spaces import action_head_sizes, heads_action_cols, heads_mixed, is_box, split_tuple_actions
 from sample_factory_amd.utils.attr_dict import AttrDict
@@ -147,6 +148,8 @@ class _InstanceStepper:
         self.arrays, self.heads, self.continuous, self.envs = arrays, heads, continuous, []
         self.training_info_ifaces, self.reward_shaping_ifaces = [], []
         self._shaping_rows = []  # (split, first row, rows, interface) of every instance that can be re-shaped
+        # the envs' own episode statistics (true_objective, episode_extra_stats), per split: key -> [sum, count]
+        self.episode_stats: Dict[int, HostEpisodeStats] = {}
         for split, vidx, env_id, row0, nrows in instances:
             env = make_env_func(env_name, cfg, AttrDict(worker_index=widx, vector_index=vidx, env_id=env_id), render_mode)
             self.envs.append((split, env, env_is_batched(env), row0, nrows, env_id))
@@ -207,6 +210,17 @@ class _InstanceStepper:
             if "active" in a:  # --track_inactive_agents: the agents' info["is_active"] beside their rewards (a missing key: active)
                 flags = infos_is_active(info, nrows)
                 a["active"][row0:row0 + nrows] = True if flags is None else flags
+            if info:  # what the env reports about the episodes that end with this step (nothing for {} / None)
+                host = lambda x: np.asarray(x.cpu() if hasattr(x, "cpu") else x).reshape(-1)  # noqa: E731
+                done = (host(term) | host(trunc)) if batched else np.array([bool(term) or bool(trunc)])
+                if done.any():
+                    stats = self.episode_stats.get(split)
+                    if stats is None:
+                        stats = self.episode_stats[split] = HostEpisodeStats()
+                    if batched:
+                        stats.add_infos(info, done)
+                    else:
+                        stats.add_single(info, True)
             if batched:
                 a["rew"][row0:row0 + nrows] = np.asarray(rew.cpu() if hasattr(rew, "cpu") else rew, dtype=np.float32).reshape(-1)
                 a["term"][row0:row0 + nrows] = np.asarray(term.cpu() if hasattr(term, "cpu") else term).reshape(-1)
@@ -216,6 +230,11 @@ class _InstanceStepper:
                     obs, _ = env.reset()
                 a["rew"][row0], a["term"][row0], a["trunc"][row0] = rew, bool(term), bool(trunc)
             self._put_obs(a, obs, row0, nrows, batched)
+
+    def pop_episode_stats(self, split: int) -> Dict[str, List[float]]:
+        """{key: [sum, count]} the instances of `split` reported since the last call (empty: nothing finished / reported)"""
+        stats = self.episode_stats.get(split)
+        return stats.pop() if stats else {}
 
     def close(self) -> None:
         for _sp, env, *_ in self.envs:
@@ -250,6 +269,9 @@ def _worker_main(widx: int, conn, done_sems, make_env_func: Callable, env_name: 
                 stepper.set_reward_shaping(scheme, slice(*idx) if is_slice else idx, sp_)
                 continue
             stepper.run(cmd, split)
+            reported = stepper.pop_episode_stats(split) if cmd == CMD_STEP else None
+            if reported:  # rides with the step reply, in front of the completion signal: _wait() finds it in the pipe
+                conn.send(("episode_stats", split, reported))
             done_sems[split].release()
     except BaseException:  # noqa: BLE001 - reported to the main process, which raises
         try:
@@ -306,6 +328,10 @@ class ParallelVecEnvView(RewardShapingInterface):
     def step(self, actions):
         self.step_async(actions)
         return self.step_wait()
+
+    def pop_episode_stats(self) -> Dict[str, List[float]]:
+        """what this view's env instances reported about finished episodes since the last call"""
+        return self.parent.pop_episode_stats(self.split)
 
     def set_training_info(self, training_info) -> None:
         """forwarded to every env instance that implements TrainingInfoInterface (in its worker process)"""
@@ -392,6 +418,7 @@ class ParallelHostEnvs:
             self.arrays.append(arr)
             specs.append(spec)
         self.inline, self._steppers = inline, []
+        self._episode_stats = [HostEpisodeStats() for _ in range(num_splits)]  # the workers' replies, merged per split
         if inline:
             for w in range(num_workers):
                 inst = []
@@ -486,6 +513,14 @@ class ParallelHostEnvs:
         for c in self._conns:
             c.send((CMD_REWARD_SHAPING, (dict(reward_shaping), idx, isinstance(agent_idx, slice), split)))
 
+    def pop_episode_stats(self, split: int) -> Dict[str, List[float]]:
+        """{key: [sum, count]} the env instances of `split` reported since the last call: the inline steppers' own
+        dictionaries, or what the worker processes sent with their step replies"""
+        stats = self._episode_stats[split]
+        for st in self._steppers:
+            stats.merge(st.pop_episode_stats(split))
+        return stats.pop()
+
     def _command(self, split: int, cmd: int) -> None:
         if self.inline:
             for st in self._steppers:
@@ -508,11 +543,13 @@ class ParallelHostEnvs:
                 if waited >= timeout:
                     self.close()
                     raise RuntimeError(f"env worker {w} did not answer within {timeout} s")
-            if self._conns[w].poll(0):
+            while self._conns[w].poll(0):
                 msg = self._conns[w].recv()
                 if msg[0] == "error":
                     self.close()
                     raise RuntimeError(f"env worker {w} died:\n{msg[1]}")
+                if msg[0] == "episode_stats":  # a worker's {key: [sum, count]}, filed under the split it belongs to
+                    self._episode_stats[msg[1]].merge(msg[2])
 
     def close(self) -> None:
         if getattr(self, "_closed", True):

@@ -20,6 +20,7 @@ SOURCES = [
     ("sf_ingest.hip", []),                  # observation ingest: the device frame stack, the HWC transpose, resize / grey-scale
     ("sf_pixcatch.hip", []),                # PixelCatch: the device-resident pixel game (step + render in one launch)
     ("sf_augment.hip", []),                 # training-time augmentation: the shift / intensity / cutout gather of a minibatch's frames
+    ("sf_traj.hip", []),                    # statistics an env defines itself: per-channel sums over the finished envs
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
           f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}"]

@@ -29,6 +29,9 @@ from sample_factory_amd.cfg.arguments import load_from_checkpoint  # noqa: E402,
 from sample_factory_amd.utils.utils import cfg_file, log  # noqa: E402,F401
 
 
+last_env_stats: dict = {}  # key -> average over the episodes of the last enjoy() of what the env reported itself
+
+
 def load_state_dict(cfg, actor_critic, device) -> dict:
     """enjoy.py:92-100"""
     from sample_factory_amd.algo.learning.learner import Learner
@@ -92,6 +95,12 @@ def enjoy(cfg) -> Tuple[int, float]:
         ret_sum, episodes = float(st[0]), float(st[2])
         if (max_episodes is not None and episodes >= max_episodes) or (max_frames is not None and frames > max_frames):
             break
+    # what the env reports itself (enjoy.py:140-257 prints the true objective next to the reward): read once, at the end
+    _, sums = sampler.read_stats()
+    global last_env_stats
+    last_env_stats = {k: s / c for k, (s, c) in sums.items() if c > 0}
+    if "true_objective" in last_env_stats:
+        print(f"Avg true_objective: {last_env_stats['true_objective']:.3f}")
     if hasattr(env, "close"):
         env.close()
     return ExperimentStatus.SUCCESS, (ret_sum / episodes if episodes else 0.0)

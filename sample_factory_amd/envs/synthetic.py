@@ -353,6 +353,136 @@ def make_turn_based_masked_bandit_env(full_env_name, cfg=None, env_config=None, 
                                     script=g("synthetic_active_script", None), dict_infos=bool(g("synthetic_dict_infos", False)))
 
 
+def episode_stats_lengths(ids: np.ndarray) -> np.ndarray:
+    """the episode length of the agents with global ids `ids` in the two episode-statistics envs below: 3 .. 7 steps"""
+    return 3 + (np.asarray(ids) % 5)
+
+
+class EpisodeStatsVecEnv:
+    """GPU vector env that reports statistics of its own the way the reference's vectorised envs do: its
+    step() returns ONE infos dict of device tensors,
+
+        {"true_objective": 2 * return + 1 (f32), "episode_extra_stats": {"first_action": the episode's first action (i32),
+         "len_parity": steps so far % 2 (i64)}, "junk": an [N, 3] tensor that is no statistic}
+
+    with one element per agent at EVERY step; only the elements of the agents whose episode ends count.  Episodes have
+    deterministic lengths (episode_stats_lengths of the global agent id), the reward is action % 2: every statistic is an
+    integer.  `ledger`: (key, value) of every finished episode, in order — kept on the host, so this env synchronises the
+    device once per step, which a test env may do."""
+
+    def __init__(self, num_agents=32, num_actions=4, env0=0, device="cuda"):
+        self.num_agents, self.A, self.env0 = int(num_agents), int(num_actions), int(env0)
+        self.observation_space = spaces.Dict({"obs": spaces.Box(-np.inf, np.inf, (2,), np.float32)})
+        self.action_space = spaces.Discrete(self.A)
+        self.device = torch.device(device)
+        self.length = torch.from_numpy(episode_stats_lengths(self.env0 + np.arange(self.num_agents))).to(torch.int32).to(self.device)
+        self.ledger = []
+        self._zero()
+
+    def _zero(self):
+        n, dev = self.num_agents, self.device
+        self.ret = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.steps = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.first = torch.zeros(n, dtype=torch.int32, device=dev)
+
+    def _obs(self):
+        return {"obs": torch.stack([self.steps.float(), self.ret], 1)}
+
+    def reset(self, **kwargs):
+        self._zero()
+        return self._obs(), {}
+
+    def step(self, actions):
+        a = torch.as_tensor(actions, device=self.device).reshape(-1).to(torch.int32)
+        self.first = torch.where(self.steps == 0, a, self.first)
+        rew = (a % 2).float()
+        self.ret = self.ret + rew
+        self.steps = self.steps + 1
+        term = self.steps >= self.length
+        infos = {"true_objective": 2.0 * self.ret + 1.0,
+                 "episode_extra_stats": {"first_action": self.first.clone(), "len_parity": (self.steps % 2).long()},
+                 "junk": torch.zeros((self.num_agents, 3), device=self.device)}
+        idx = term.nonzero().reshape(-1)
+        if idx.numel():
+            for key, v in (("reward", self.ret), ("len", self.steps), ("true_objective", infos["true_objective"]),
+                           ("first_action", self.first), ("len_parity", infos["episode_extra_stats"]["len_parity"])):
+                self.ledger.extend((key, float(x)) for x in v[idx].cpu().tolist())
+        keep = ~term
+        self.ret, self.steps = self.ret * keep, self.steps * keep  # auto-reset
+        return self._obs(), rew, term, torch.zeros_like(term), infos
+
+    def close(self):
+        pass
+
+
+class EpisodeStatsHostEnv:
+    """the same game on the host, reporting as host envs do: a list with one info dict per agent, which carries
+    true_objective and episode_extra_stats (and an entry that is no number) at the step that ends the agent's episode.
+    `ledger` as above; with `ledger_path` every finished episode is also appended to that file as a JSON line (an env that
+    lives in a worker process has no other way to show its ledger)."""
+
+    def __init__(self, num_agents=16, num_actions=4, env0=0, ledger_path=None):
+        self.num_agents, self.A, self.env0 = int(num_agents), int(num_actions), int(env0)
+        self.is_multiagent = True
+        self.observation_space = spaces.Dict({"obs": spaces.Box(-np.inf, np.inf, (2,), np.float32)})
+        self.action_space = spaces.Discrete(self.A)
+        self.length = episode_stats_lengths(self.env0 + np.arange(self.num_agents)).astype(np.int32)
+        self.ledger, self.ledger_path = [], ledger_path
+        self._zero()
+
+    def _zero(self):
+        self.ret = np.zeros(self.num_agents, np.float32)
+        self.steps = np.zeros(self.num_agents, np.int32)
+        self.first = np.zeros(self.num_agents, np.int32)
+
+    def _obs(self):
+        return {"obs": np.stack([self.steps.astype(np.float32), self.ret], 1)}
+
+    def reset(self, **kwargs):
+        self._zero()
+        return self._obs(), [{} for _ in range(self.num_agents)]
+
+    def step(self, actions):
+        a = np.asarray(actions).reshape(-1).astype(np.int32)
+        self.first = np.where(self.steps == 0, a, self.first)
+        rew = (a % 2).astype(np.float32)
+        self.ret = self.ret + rew
+        self.steps = self.steps + 1
+        term = self.steps >= self.length
+        infos, lines = [{} for _ in range(self.num_agents)], []
+        for i in np.flatnonzero(term).tolist():
+            rec = dict(reward=float(self.ret[i]), len=float(self.steps[i]), true_objective=2.0 * float(self.ret[i]) + 1.0,
+                       first_action=float(self.first[i]), len_parity=float(self.steps[i] % 2))
+            infos[i] = {"true_objective": rec["true_objective"], "note": "episode over",
+                        "episode_extra_stats": {"first_action": int(self.first[i]), "len_parity": int(self.steps[i] % 2)}}
+            self.ledger.extend(rec.items())
+            lines.append(rec)
+        if lines and self.ledger_path:
+            import json
+            with open(self.ledger_path, "a") as f:
+                f.writelines(json.dumps(rec) + "\n" for rec in lines)
+        self.ret, self.steps = self.ret * ~term, self.steps * ~term  # auto-reset
+        return self._obs(), rew, term, np.zeros(self.num_agents, np.bool_), infos
+
+    def close(self):
+        pass
+
+
+def make_episode_stats_vec_env(full_env_name, cfg=None, env_config=None, render_mode=None):
+    n = int(getattr(cfg, "synthetic_num_agents", None) or 32) if cfg is not None else 32
+    e = int(getattr(env_config, "env_id", 0) or 0) if env_config is not None else 0
+    return EpisodeStatsVecEnv(num_agents=n, env0=e * n)
+
+
+def make_episode_stats_host_env(full_env_name, cfg=None, env_config=None, render_mode=None):
+    """cfg.synthetic_ledger_dir: every instance appends its finished episodes to <dir>/ledger_<env_id>.jsonl"""
+    import os
+    n = int(getattr(cfg, "synthetic_num_agents", None) or 16) if cfg is not None else 16
+    e = int(getattr(env_config, "env_id", 0) or 0) if env_config is not None else 0
+    d = getattr(cfg, "synthetic_ledger_dir", None) if cfg is not None else None
+    return EpisodeStatsHostEnv(num_agents=n, env0=e * n, ledger_path=os.path.join(d, f"ledger_{e}.jsonl") if d else None)
+
+
 class MaskedTupleBanditEnv:
     """MaskedBanditEnv on Tuple(Discrete(n_0), Discrete(n_1), ...): obs = the members' rewarded actions as one-hots side
     by side, obs["action_mask"] u8 [N, sum n_i] with one column per distribution parameter (member i owns the columns

@@ -45,6 +45,20 @@ class sf_res_desc(C.Structure):
                 ("act_in", C.c_int32), ("traj_T", C.c_int32), ("sub_mean", C.c_float), ("inv_scale", C.c_float)]
 
 
+EPSTAT_MAX_CHANNELS = 16
+
+
+class sf_epstat_channels(C.Structure):
+    """the channels of one sf_episode_stats_add launch: device pointer, element stride, dtype code (SF_EPSTAT_*)"""
+    _fields_ = [("ptr", C.c_void_p * EPSTAT_MAX_CHANNELS), ("stride", C.c_int64 * EPSTAT_MAX_CHANNELS),
+                ("dtype", C.c_int32 * EPSTAT_MAX_CHANNELS)]
+
+
+EPSTAT_F32, EPSTAT_F64, EPSTAT_I32, EPSTAT_I64, EPSTAT_U8 = 0, 1, 2, 3, 4  # sf_epstat_channels.dtype
+_EPSTAT_DT = {torch.float32: EPSTAT_F32, torch.float64: EPSTAT_F64, torch.int32: EPSTAT_I32, torch.int64: EPSTAT_I64,
+              torch.uint8: EPSTAT_U8, torch.bool: EPSTAT_U8}
+
+
 # every symbol include/sf_hip.h declares (tests/test_abi.py checks the header against this list and the .so)
 SYMBOLS = [
     "sf_last_error", "sf_abi_version", "sf_valid_mask", "sf_gae_returns", "sf_moments", "sf_rms_update",
@@ -68,6 +82,7 @@ SYMBOLS = [
     "sf_pixcatch_step_levels",
     "sf_random_shift_gather", "sf_augment_gather",
     "sf_consistency_loss",
+    "sf_episode_stats_add",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -913,6 +928,35 @@ def traj_write_env_step_active(rewards, terminated, truncated, T, t, reward_scal
                                                 ptr(ep_stats, "f64"), ptr(active_in, "u8", "active_in"),
                                                 ptr(active_state, "u8", "active_state"), stream()),
            "sf_traj_write_env_step_active")
+
+
+def episode_stats_add(channels, terminated, truncated, active, acc) -> None:
+    """acc[k] += {sum of channels[k] over the finished envs, their number} (sf_hip.h: sf_episode_stats_add).
+    channels: device tensors of B elements each, 1-d views of any element stride (a column of a matrix is fine), dtype
+    f32 / f64 / i32 / i64 / u8 / bool; terminated, truncated, active (or None): u8 / bool [B], contiguous; acc: f64
+    [len(channels), 2], contiguous, NOT zeroed.  One launch per EPSTAT_MAX_CHANNELS channels."""
+    B, K = terminated.numel(), len(channels)
+    if K < 1:
+        raise SfHipError("episode_stats_add: no channels")
+    if acc.shape != (K, 2):
+        raise SfHipError(f"episode_stats_add: acc must be [{K}, 2], got {tuple(acc.shape)}")
+    for name, x in (("truncated", truncated), ("active", active)):
+        if x is not None and x.numel() != B:
+            raise SfHipError(f"episode_stats_add: {name} has {x.numel()} elements, expected {B}")
+    p_term, p_trunc = ptr(terminated, "u8", "terminated"), ptr(truncated, "u8", "truncated")
+    p_act, p_acc = ptr(active, "u8", "active"), ptr(acc, "f64", "acc")
+    for k0 in range(0, K, EPSTAT_MAX_CHANNELS):
+        part = channels[k0:k0 + EPSTAT_MAX_CHANNELS]
+        ch = sf_epstat_channels()
+        for k, t in enumerate(part):
+            code = _EPSTAT_DT.get(t.dtype)
+            if code is None or not t.is_cuda or t.dim() != 1 or t.numel() != B or (B > 1 and t.stride(0) < 1):
+                raise SfHipError(f"episode_stats_add: channel {k0 + k}: a 1-d device view of {B} numeric elements is "
+                                 f"required, got {tuple(t.shape)} {t.dtype} on {t.device}, strides {t.stride()}")
+            _keep(t)
+            ch.ptr[k], ch.stride[k], ch.dtype[k] = t.data_ptr(), max(1, t.stride(0)), code
+        _check(load().sf_episode_stats_add(C.byref(ch), len(part), p_term, p_trunc, p_act, i64(B),
+                                           C.c_void_p(p_acc.value + 16 * k0), stream()), "sf_episode_stats_add")
 
 
 def synth_vec_step(state, actions, obs_out, env0, seed, step, reset, rewards, terminated) -> None:

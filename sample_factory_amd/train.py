@@ -19,6 +19,7 @@ import torch
 
 from sample_factory_amd.algo.learning.learner import Learner, ParameterServer
 from sample_factory_amd.algo.sampling.batched_sampling import BatchedVectorEnvRunner
+from sample_factory_amd.algo.sampling.episode_stats import episodic_message, merge_sums
 from sample_factory_amd.algo.utils.env_info import extract_env_info, with_device_ingest
 from sample_factory_amd.algo.learning.batcher import Batcher
 from sample_factory_amd.algo.utils.shared_buffers import BufferMgr
@@ -78,6 +79,8 @@ class Runner:
         self.policy_avg_stats: Dict[str, List[deque]] = dict()
         self.msg_handlers: Dict[str, List[Callable]] = dict()
         self.policy_msg_handlers: Dict[str, List[Callable]] = {EPISODIC: [Runner._episodic_stats_handler]}
+        self._env_stat_sums: Dict[str, List[float]] = {}  # env-defined statistics read back but not yet reported
+        self._best_metric_notes: set = set()              # one log line per remark about cfg.save_best_metric
 
     def register_observer(self, observer: AlgoObserver) -> None:
         self.observers.append(observer)
@@ -133,12 +136,15 @@ class Runner:
                     self._cv.wait(0.05)
                 tot = self._ep_stats_result if self._ep_stats_result is not None else torch.zeros(3, dtype=torch.float64)
                 self._ep_stats_result = None
+                sums, self._env_stat_sums = self._env_stat_sums, {}
         else:
             tot = self._read_ep_stats()
-        k = float(tot[2])
-        if k > 0:
-            self._process_msg({EPISODIC: dict(reward=float(tot[0]) / k, len=float(tot[1]) / k, episodes=k),
-                               POLICY_ID_KEY: 0})
+            sums, self._env_stat_sums = self._env_stat_sums, {}
+        # what the envs define themselves (true_objective, episode_extra_stats, per-agent tensors of dict infos; DESIGN.md
+        # 3.21) came back in the same read: their means join the message under the reference's key names
+        msg = episodic_message(float(tot[0]), float(tot[1]), float(tot[2]), sums)
+        if msg is not None:
+            self._process_msg({EPISODIC: msg, POLICY_ID_KEY: 0})
 
     # ------------------------------------------------------------------------------------------ experiment directory
     def _handle_restart(self) -> None:
@@ -174,9 +180,11 @@ class Runner:
         rollout kernels add to them on (async: the rollout stream), so no episode is lost between read and reset"""
         st = self.rollout_stream if self.cfg.async_rl else torch.cuda.current_stream()
         with torch.cuda.stream(st):  # read AND reset in the rollout stream's order (.cpu() waits for that stream)
-            tot = sum(sm.ep_stats.cpu() for sm in self.samplers)
-            for sm in self.samplers:
-                sm.ep_stats.zero_()
+            tot = 0
+            for sm in self.samplers:  # one copy per env instance: ep_stats and the env's own statistics behind them
+                ep, sums = sm.read_stats()
+                tot = tot + ep
+                merge_sums(self._env_stat_sums, sums)
         return tot
 
     def init(self) -> int:
@@ -653,9 +661,24 @@ class Runner:
         """runner.py:459-475: once save_best_after env steps are in, save when the running average of
         cfg.save_best_metric improved (the threshold test is Learner.save_best's)"""
         metric = self.cfg.save_best_metric
-        if self.rank != 0 or metric not in self.policy_avg_stats or self.learner.env_steps < self.cfg.save_best_after:
+        if self.rank != 0 or self.learner.env_steps < self.cfg.save_best_after:
             return
-        stats = self.policy_avg_stats[metric][0]
+        source = metric
+        if metric not in self.policy_avg_stats:
+            if metric == "true_objective" and "reward" in self.policy_avg_stats:
+                # no env reported it: its value is the episode's reward (non_batched_sampling.py:292-293)
+                source = "reward"
+                if "fallback" not in self._best_metric_notes:
+                    self._best_metric_notes.add("fallback")
+                    log.info("save_best_metric=true_objective: no env reports it, using the episode reward in its place")
+            else:
+                if "reward" in self.policy_avg_stats and "missing" not in self._best_metric_notes:
+                    self._best_metric_notes.add("missing")  # episodes have finished, none of them carried the metric
+                    log.warning(f"save_best_metric={metric}: no env has reported this statistic after "
+                                f"{self.learner.env_steps} env steps (known: {sorted(self.policy_avg_stats)}); "
+                                "no best checkpoint is written")
+                return
+        stats = self.policy_avg_stats[source][0]
         if len(stats) > 0:
             self.learner.save_best(0, metric, float(np.mean(stats)))
 
