@@ -7,7 +7,13 @@ bit equality with it (sf_rl.hip is compiled with -ffp-contract=off, so an expres
 its operation order unchanged gives the same bits).  Needs a GPU.
 
 The double sums of the loss are atomics, one per block and slot.  Lane-per-row cases have n <= 256 rows (one block);
-wave-per-row cases have n = 7 (two blocks of four rows, the second partial: 0 + a + b is the same in either order)."""
+wave-per-row cases have n = 7 (two blocks of four rows, the second partial: 0 + a + b is the same in either order).
+
+    python tools/gen_golden_rl_heads_parent.py --second [out.npz]
+writes the second fixture, tests/golden/rl_heads_parent2.npz, from the case lists MASKED_LOSS_CASES, MASKED_VTRACE_CASES
+and CONSISTENCY_CASES: the entry points that came after the first fixture (sf_ppo_loss_masked, sf_vtrace_masked,
+sf_consistency_loss).  Commit PARENT2 wrote it; tests/test_gpu_rl_heads_parent2_bits.py asks for bit equality with it, so
+that a later rewrite of these kernels that keeps the operation order can be held to their bits as well."""
 import math
 import os
 import sys
@@ -19,6 +25,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 PARENT = "dea0c8f"  # "Sample Tuple action spaces under an action mask on native samplers"
+PARENT2 = "5652c55"  # "Report env-defined episode statistics: true_objective and extra stats"
 SENT = -7.0         # what a sampler's slab holds before the launch: every step but t must still hold it after
 CLIP_RATIO, CLIP_VALUE = 0.1, 0.5
 
@@ -31,14 +38,17 @@ def n_cols(heads):
     return sum(1 if h > 0 else -h for h in heads)
 
 
-def logp64(params, actions, heads):
-    """float64 log-prob of the recorded actions (places the ratios; not a reference for the outputs)"""
+def logp64(params, actions, heads, mask=None):
+    """float64 log-prob of the recorded actions (places the ratios; not a reference for the outputs); mask: -1e9 on the
+    masked-out columns of a Discrete member, rounded to f32 as the kernels add it (an all-masked member is uniform)"""
     p, a = params.astype(np.float64), actions.astype(np.float64)
     lp = np.zeros(len(p))
     off = col = 0
     for h in heads:
         if h > 0:
             z = p[:, off:off + h]
+            if mask is not None:
+                z = np.where(mask[:, off:off + h] != 0, z, (z - 1e9).astype(np.float32).astype(np.float64))
             z = z - z.max(1, keepdims=True)
             ls = z - np.log(np.exp(z).sum(1, keepdims=True))
             lp += ls[np.arange(len(p)), a[:, col].astype(np.int64)]
@@ -104,12 +114,61 @@ LOSS_CASES = [
     ("loss_heads_10_wide", "heads", [3] * 9 + [130], 7, 2, 0.1, "index", 0, 0),
     ("loss_heads_130_b2_3", "heads", [130, -2, 3], 7, 1, 0.1, "index", 0, 5),
 ]
+# the same fields and mask_T: sf_ppo_loss_masked (k_masked_ppo_loss_md / _mh / _wide); the datasets have 2 n + 3 rows, so
+# draw_mask's all-masked member rows are among the minibatch's
+MASKED_LOSS_CASES = [
+    ("mloss_d7_flat", "masked", [7], 70, 1, 0.2, "index", 0, 0, 0),
+    ("mloss_d7_slab", "masked", [7], 70, 0, 0.0, "offset", 0, 5, 5),
+    ("mloss_3_b2_5_flat", "masked", [3, -2, 5], 70, 1, 0.1, "offset", 1, 0, 0),
+    ("mloss_3_b2_5_slab", "masked", [3, -2, 5], 70, 1, 0.0, "index", 0, 5, 5),
+    ("mloss_11_flat", "masked", [3] * 9 + [-2, 4], 70, 1, 0.1, "index", 0, 0, 0),
+    ("mloss_11_slab", "masked", [3] * 9 + [-2, 4], 70, 0, 0.2, "offset", 0, 0, 5),
+    ("mloss_130_b2_3_flat", "masked", [130, -2, 3], 7, 1, 0.1, "offset", 0, 0, 0),
+    ("mloss_130_b2_3_slab", "masked", [130, -2, 3], 7, 1, 0.2, "index", 0, 5, 5),
+]
+
+
+def allowed_actions(mask, heads, actions):
+    """in place: a recorded action of a Discrete member that its mask slice rules out becomes the slice's first allowed
+    one, as a sampler under that mask would never have drawn it (an all-masked slice keeps what was drawn)"""
+    off = col = 0
+    for h in heads:
+        if h > 0:
+            sl = mask[:, off:off + h]
+            a = actions[:, col].astype(np.int64)
+            bad = (sl[np.arange(len(sl)), a] == 0) & sl.any(1)
+            actions[bad, col] = sl[bad].argmax(1)
+        off, col = off + (h if h > 0 else -2 * h), col + (1 if h > 0 else -h)
+
+
+def all_masked_member(mask_row, heads):
+    """whether a Discrete member's whole slice of the mask row is zero"""
+    off, hit = 0, False
+    for h in heads:
+        hit = hit or (h > 0 and not mask_row[off:off + h].any())
+        off += h if h > 0 else -2 * h
+    return hit
+
+
+def slab_mask(mask, mask_T):
+    """the device mask of dataset rows [N, A]: flat (mask_T = 0), or inside the slab's [E, mask_T + 1, A] array whose
+    last step of every env holds ones the kernels must never read for these rows"""
+    if not mask_T:
+        return dev(mask)
+    E = -(-len(mask) // mask_T)
+    rows = np.arange(len(mask))
+    slab = np.ones((E * (mask_T + 1), mask.shape[1]), np.uint8)
+    slab[rows + rows // mask_T] = mask  # dataset row e * T + t -> e * (T + 1) + t
+    return dev(slab.reshape(E, mask_T + 1, -1))
 
 
 def run_loss_case(lib, case):
+    """a case of LOSS_CASES, or of MASKED_LOSS_CASES (one more field, mask_T: sf_ppo_loss_masked under draw_mask's rows,
+    flat [N, A] with mask_T = 0 or the slab's [E, mask_T + 1, A] read in place)"""
     import ctypes as C
     import torch
-    name, entry, heads, n, expl_kind, kl_coeff, read, dense_adv, ov_T = case
+    name, entry, heads, n, expl_kind, kl_coeff, read, dense_adv, ov_T = case[:9]
+    mask_T = case[9] if len(case) > 9 else None
     rng = np.random.default_rng(hash_name(name))
     A = n_params(heads)
     E = -(-(2 * n + 3) // ov_T) if ov_T else 0
@@ -125,8 +184,14 @@ def run_loss_case(lib, case):
     # [0.05, 20], the others around 1
     shift = rng.standard_normal(n) * 0.05
     shift[:4] = [-math.log(60.0), math.log(60.0), -0.3, 0.3]
+    mask = None
+    if mask_T is not None:  # (its own generator: the draws below stay those of an unmasked case of the same name)
+        mask = draw_mask(np.random.default_rng(hash_name(name + "/mask")), heads, N)
+        first = next(i for i, h in enumerate(heads) if h > 0)  # minibatch row 2 (valid below): an all-masked member
+        mask[rows[2], n_params(heads[:first]):n_params(heads[:first + 1])] = 0
+        allowed_actions(mask, heads, actions)
     old_logp = np.zeros(N, np.float32)
-    old_logp[rows] = (logp64(params, actions[rows], heads) + shift).astype(np.float32)
+    old_logp[rows] = (logp64(params, actions[rows], heads, None if mask is None else mask[rows]) + shift).astype(np.float32)
     valids = rng.random(N) > 0.15
     valids[rows[:6]] = True
     valids[rows[6]] = False
@@ -160,7 +225,9 @@ def run_loss_case(lib, case):
     lib.moments(d_adv, d_valids, idx, n, mom, offset=offset, dense_x=bool(dense_adv))
     args = (m[:, 1:], 1 + A, m[:, 0], 1 + A, dev(actions), dev(old_logp), dev(old_params), dev(old_values), d_adv,
             dev(targets), d_valids, idx, offset, n, A, cfg, mom, sums, g[:, 1:], g[:, 0], ratio)
-    if entry == "cfg":
+    if entry == "masked":
+        lib.ppo_loss(*args, head_sizes=heads, mask=slab_mask(mask, mask_T), mask_T=mask_T)
+    elif entry == "cfg":
         lib.ppo_loss(*args)
     else:  # sf_ppo_loss_heads with the list as its argument, whatever its length
         p, r = lib.ptr, lib._raw
@@ -173,8 +240,11 @@ def run_loss_case(lib, case):
         lib._check(rc, "sf_ppo_loss_heads")
     lib.loss_scalars(sums, mom, cfg, out)
     torch.cuda.synchronize()
-    return dict(sums=sums.cpu().numpy(), moments=mom.cpu().numpy(), grads=g.cpu().numpy(), ratio=ratio.cpu().numpy(),
-                scalars=out.cpu().numpy())
+    o = dict(sums=sums.cpu().numpy(), moments=mom.cpu().numpy(), grads=g.cpu().numpy(), ratio=ratio.cpu().numpy(),
+             scalars=out.cpu().numpy())
+    if mask is not None:  # valid minibatch rows with an all-masked Discrete member (what the case is there for)
+        o["all_masked_rows"] = np.int32(sum(valids[r] and all_masked_member(mask[r], heads) for r in rows))
+    return o
 
 
 def hash_name(name):
@@ -196,11 +266,18 @@ VTRACE_CASES = [
     ("vtrace_box70_wide", [-70], 5, 14, 1.0, 1.0, "offset"),
     ("vtrace_5_130_b2_7", [5, 130, -2, 7], 7, 10, 2.0, 0.5, "index"),
 ]
+# the same fields and mask_T: sf_vtrace_masked (k_masked_vtrace_ratio / _wide)
+MASKED_VTRACE_CASES = [
+    ("mvtrace_d9", [9], 7, 10, 1.0, 1.0, "index", 0),
+    ("mvtrace_3_b2_5", [3, -2, 5], 5, 14, 2.0, 0.5, "offset", 5),
+    ("mvtrace_130_4", [130, 4], 7, 10, 0.5, 2.0, "index", 7),
+]
 
 
 def run_vtrace_case(lib, case):
     import torch
-    name, heads, rec, ntraj, rho_hat, c_hat, read = case
+    name, heads, rec, ntraj, rho_hat, c_hat, read = case[:7]
+    mask_T = case[7] if len(case) > 7 else None
     rng = np.random.default_rng(hash_name(name))
     A, n = n_params(heads), rec * ntraj
     N = 2 * n
@@ -213,8 +290,12 @@ def run_vtrace_case(lib, case):
         rows = np.arange(offset, offset + n)
     shift = rng.standard_normal(n) * 0.5
     shift[0], shift[1] = -90.0, 4.0  # logp - old_logp = 90 (f32 exp overflows), ratio e^-4 < 0.05
+    mask = None
+    if mask_T is not None:
+        mask = draw_mask(np.random.default_rng(hash_name(name + "/mask")), heads, N)
+        allowed_actions(mask, heads, actions)
     old_logp = np.zeros(N, np.float32)
-    old_logp[rows] = (logp64(params, actions[rows], heads) + shift).astype(np.float32)
+    old_logp[rows] = (logp64(params, actions[rows], heads, None if mask is None else mask[rows]) + shift).astype(np.float32)
     values = rng.standard_normal(n).astype(np.float32)
     rewards = rng.standard_normal(N).astype(np.float32)
     dones = rng.random(N) < 0.1
@@ -223,9 +304,53 @@ def run_vtrace_case(lib, case):
     vs, adv = torch.full((n,), SENT, device="cuda"), torch.full((n,), SENT, device="cuda")
     lib.vtrace(m[:, 1:], 1 + A, m[:, 0], 1 + A, dev(actions), dev(old_logp), dev(rewards), dev(dones),
                dev(index) if index is not None else None, offset, n, A, kind, rec, 0.99, rho_hat, c_hat, vs, adv,
-               head_sizes=heads)
+               head_sizes=heads, **({} if mask is None else dict(mask=slab_mask(mask, mask_T), mask_T=mask_T)))
     torch.cuda.synchronize()
     return dict(vs=vs.cpu().numpy(), adv=adv.cpu().numpy())
+
+
+# ---------------------------------------------------------------------------------------------------- consistency loss
+# (name, heads, n, read through): k_consistency_loss up to 128 parameters (at most 256 rows), k_consistency_loss_wide
+# beyond (7 rows)
+CONSISTENCY_CASES = [
+    (f"cons_{tag}_{read}", heads, n, read)
+    for tag, heads, n in (("d7", [7], 70), ("box3", [-3], 70), ("3_b2_5", [3, -2, 5], 70), ("d129", [129], 7),
+                          ("130_b2_3", [130, -2, 3], 7))
+    for read in ("index", "offset")
+]
+
+
+def run_consistency_case(lib, case):
+    """target rows and student rows are the two halves of one [2 n, 1 + A] heads matrix, as the learner holds them; some
+    student rows equal their target's bits (KL and gradient exactly 0), some log_std sit beyond both clamp ends"""
+    import torch
+    name, heads, n, read = case
+    rng = np.random.default_rng(hash_name(name))
+    A, N = n_params(heads), 2 * n + 3
+    params_s, _, _ = draw_dists(rng, heads, N, n)
+    params_t = (params_s + rng.standard_normal((n, A)) * 0.3).astype(np.float32)
+    params_t[2::5] = params_s[2::5]
+    values = rng.standard_normal((2 * n, 1)).astype(np.float32)
+    values[2] = values[n + 2]
+    if read == "index":
+        index, offset = rng.permutation(N)[:n].astype(np.int32), 0
+        rows = index.astype(np.int64)
+    else:
+        index, offset = None, 3
+        rows = np.arange(offset, offset + n)
+    valids = rng.random(N) > 0.15
+    valids[rows[:3]] = True
+    valids[rows[3]] = False
+    m = dev(np.concatenate([values, np.concatenate([params_t, params_s])], 1))
+    g = torch.full_like(m, SENT)
+    mom = dev(np.array([0.0, 0.0, valids[rows].sum()]))
+    sums = torch.full((4,), SENT, dtype=torch.float64, device="cuda")
+    kind = 1 if len(heads) == 1 and heads[0] < 0 else 0
+    lib.consistency_loss(m[:n, 1:], m[n:, 1:], 1 + A, m[:n, 0], m[n:, 0], 1 + A, dev(valids),
+                         dev(index) if index is not None else None, offset, n, A, kind, 0.7, 0.3, mom, sums, g[n:, 1:],
+                         g[n:, 0], head_sizes=heads)
+    torch.cuda.synchronize()
+    return dict(sums=sums.cpu().numpy(), grads=g.cpu().numpy())
 
 
 # ---------------------------------------------------------------------------------------------------- samplers
@@ -329,12 +454,24 @@ def run_all(lib):
     return rec
 
 
+def run_all_second(lib):
+    """the second fixture's {"<case>/<array>": host array}"""
+    rec = {}
+    for cases, run in ((MASKED_LOSS_CASES, run_loss_case), (MASKED_VTRACE_CASES, run_vtrace_case),
+                       (CONSISTENCY_CASES, run_consistency_case)):
+        for case in cases:
+            rec.update({f"{case[0]}/{k}": v for k, v in run(lib, case).items()})
+    return rec
+
+
 def main():
     from sample_factory_amd import lib
     lib.load()
-    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "tests", "golden", "rl_heads_parent.npz")
-    rec = run_all(lib)
-    rec["parent"] = np.array(PARENT)
+    argv = [a for a in sys.argv[1:] if a != "--second"]
+    second = len(argv) < len(sys.argv) - 1
+    out = argv[0] if argv else os.path.join(ROOT, "tests", "golden", "rl_heads_parent2.npz" if second else "rl_heads_parent.npz")
+    rec = run_all_second(lib) if second else run_all(lib)
+    rec["parent"] = np.array(PARENT2 if second else PARENT)
     os.makedirs(os.path.dirname(out), exist_ok=True)
     np.savez_compressed(out, **rec)
     print(f"wrote {out}: {len(rec) - 1} arrays, {os.path.getsize(out)} bytes")
