@@ -422,6 +422,12 @@ int sf_synth_vec_step(float *state, const float *actions, int64_t act_stride, fl
  * (hipMemcpy2DAsync) on `stream` — no contiguous device staging copy, no kernel.  Returns without synchronising. */
 int sf_h2d_rows(void *dst, int64_t dst_pitch, const void *src, int64_t src_pitch, int64_t row_bytes, int64_t rows,
                 void *stream);
+/* Page-lock `bytes` bytes at `ptr` that the process already owns (the env workers' shared-memory pages), so that
+ * sf_h2d_rows reads them in place; sf_host_unregister before they are unmapped.  Not every runtime can do this (a
+ * virtualised GPU refuses): then the return value is SF_ERR_LAUNCH, sf_last_error() says why, and NO error stays behind
+ * in the HIP runtime for a later launch to report — the caller stages the rows through pinned memory of its own. */
+int sf_host_register(void *ptr, int64_t bytes);
+int sf_host_unregister(void *ptr);
 /* device -> device row copy with pitches (one launch): the column copies of the slab protocol — the next rollout's
  * obs[:, 0] / rnn_states[:, 0] <- this rollout's [:, T] (batched_sampling.py:289-296, TensorDict `copy_` per leaf in the
  * reference), the bootstrap value -> values[:, T] (learner.py:962-969). */

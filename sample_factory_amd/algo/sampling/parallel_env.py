@@ -467,19 +467,22 @@ class ParallelHostEnvs:
     # ---- pinned pages: let the DMA engine read the workers' pages directly
     def register_with_device(self) -> bool:
         """hipHostRegister the observation pages (main process only; a no-op without a GPU).  Returns True if the pages are
-        now page-locked: the rollout runner then hands them to sf_h2d_rows without a staging copy."""
+        now page-locked: the rollout runner then hands them to sf_h2d_rows without a staging copy.  False where the runtime
+        cannot page-lock memory the process already owns (a virtualised GPU): the runner then stages every step through
+        pinned buffers of its own, and the library has taken the refusal off the runtime's error state (through torch's
+        binding it would stay there for the next launch to report)."""
         if self.inline:
             return False
         try:
             import torch
             if not torch.cuda.is_available():
                 return False
-            rt = torch.cuda.cudart()
+            from sample_factory_amd import lib
+            torch.cuda.init()
             for arr in self.arrays:
                 for k, a in arr.items():
                     if k.startswith("obs."):
-                        err = rt.cudaHostRegister(a.ctypes.data, a.nbytes, 0)
-                        if int(err) != 0:
+                        if not lib.host_register(a.ctypes.data, a.nbytes):
                             return False
                         self._registered.append(int(a.ctypes.data))
             for v in self.views:
@@ -568,10 +571,9 @@ class ParallelHostEnvs:
                 p.terminate()
         if self._registered:  # the pages must leave the HIP runtime's tables before they are unmapped
             try:
-                import torch
-                rt = torch.cuda.cudart()
+                from sample_factory_amd import lib
                 for ptr in self._registered:
-                    rt.cudaHostUnregister(ptr)
+                    lib.host_unregister(ptr)
             except Exception:  # noqa: BLE001 - best effort at shutdown
                 pass
             self._registered = []

@@ -2085,6 +2085,20 @@ extern "C" int sf_h2d_rows(void *dst, int64_t dst_pitch, const void *src, int64_
     SF_REQUIRE(e == hipSuccess, "sf_h2d_rows: hipMemcpy2DAsync: %s", hipGetErrorString(e));
     return 0;
 }
+// A runtime that cannot page-lock memory the process already owns (a virtualised GPU) answers hipErrorInvalidValue AND keeps
+// it as the thread's last error: the next launch's status query would report it.  The refusal is taken off here.
+extern "C" int sf_host_register(void *ptr, int64_t bytes) {
+    SF_REQUIRE(ptr && bytes > 0, "sf_host_register: ptr=%p bytes=%lld", ptr, (long long)bytes);
+    const hipError_t e = hipHostRegister(ptr, (size_t)bytes, hipHostRegisterDefault);
+    if (e != hipSuccess) (void)hipGetLastError();
+    return sf_hip_status(e, "sf_host_register: hipHostRegister");
+}
+extern "C" int sf_host_unregister(void *ptr) {
+    SF_REQUIRE(ptr, "sf_host_unregister: ptr is NULL");
+    const hipError_t e = hipHostUnregister(ptr);
+    if (e != hipSuccess) (void)hipGetLastError();
+    return sf_hip_status(e, "sf_host_unregister: hipHostUnregister");
+}
 
 // =========================================================================================== K14 minibatch indices
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {

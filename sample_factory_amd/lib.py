@@ -67,7 +67,7 @@ SYMBOLS = [
     "sf_obsnorm_moments", "sf_obsnorm_update", "sf_obsnorm_apply", "sf_sample_write_step",
     "sf_sample_write_step_tuple", "sf_sample_write_step_masked", "sf_sample_write_step_tuple_masked",
     "sf_traj_write_env_step", "sf_traj_write_env_step_active", "sf_rnn_store_state_held", "sf_synth_obs",
-    "sf_synth_step", "sf_synth_vec_step", "sf_h2d_rows", "sf_copy_rows", "sf_framestack_step", "sf_hwc_to_chw", "sf_framestack_step_hwc", "sf_frame_resize", "sf_conv_fwd", "sf_conv_fwd_workspace", "sf_conv_wgrad_workspace", "sf_conv_wgrad",
+    "sf_synth_step", "sf_synth_vec_step", "sf_h2d_rows", "sf_host_register", "sf_host_unregister", "sf_copy_rows", "sf_framestack_step", "sf_hwc_to_chw", "sf_framestack_step_hwc", "sf_frame_resize", "sf_conv_fwd", "sf_conv_fwd_workspace", "sf_conv_wgrad_workspace", "sf_conv_wgrad",
     "sf_conv_dgrad", "sf_conv_norm_supported", "sf_conv_fwd_norm", "sf_conv_wgrad_norm", "sf_conv_relu_mask_supported", "sf_conv_fwd_relu_mask", "sf_conv_wgrad_relu_mask", "sf_conv_kernel_name", "sf_conv_fwd_t_supported", "sf_conv_fwd_t_workspace", "sf_conv_fwd_t", "sf_transpose",
     "sf_conv_fwd_os_supported", "sf_conv_fwd_relu_mask_os", "sf_conv_fwd_t_os",
     "sf_conv_fwd_os2_supported", "sf_conv_fwd_relu_mask_os2", "sf_conv_fwd_t_os2",
@@ -95,7 +95,7 @@ _lib: Optional[C.CDLL] = None
 # else — pointers, strides, sizes, the stream — is constant under the key the caller files the program under.
 _REC = threading.local()  # .rec: the _Recorder of the program this THREAD is recording (the learner thread is not affected)
 _QUERIES = ("_supported", "_workspace", "_kernel_name", "sf_last_error", "sf_abi_version")  # no launch: never recorded
-_HOST_STATE = ("sf_h2d_rows", "sf_dp_", "sf_allreduce_grads", "sf_clock_probe")  # read host memory / communicators: not replayable
+_HOST_STATE = ("sf_h2d_rows", "sf_host_", "sf_dp_", "sf_allreduce_grads", "sf_clock_probe")  # read host memory / communicators: not replayable
 LAUNCH_PROGRAMS = os.environ.get("SF_LAUNCH_PROGRAMS", "1") != "0"
 
 
@@ -987,6 +987,16 @@ def h2d_rows(dst: torch.Tensor, src_pinned: torch.Tensor) -> None:
         pitch = dst.stride(0) * dst.element_size()
     _check(load().sf_h2d_rows(C.c_void_p(dst.data_ptr()), i64(pitch), C.c_void_p(src_pinned.data_ptr()), i64(row_bytes),
                               i64(row_bytes), i64(rows), stream()), "sf_h2d_rows")
+
+
+def host_register(address: int, nbytes: int) -> bool:
+    """page-lock host memory this process already owns; False where the runtime cannot (nothing stays behind in the HIP
+    runtime then: the next launch does not report the refusal)"""
+    return load().sf_host_register(C.c_void_p(int(address)), i64(nbytes)) == 0
+
+
+def host_unregister(address: int) -> bool:
+    return load().sf_host_unregister(C.c_void_p(int(address))) == 0
 
 
 def copy_rows(dst: torch.Tensor, src: torch.Tensor) -> None:

@@ -466,6 +466,31 @@ def test_host_env_async_sampler_thread_with_recurrent_core(rnn_type):
         assert float(nxt[~dn].abs().max()) > 0.0
 
 
+def test_page_locking_owned_memory_leaves_no_error_behind_where_the_runtime_refuses_it():
+    """sf_host_register on pages the process already owns (what the env workers' shared memory is): either they are
+    page-locked — torch sees them pinned, sf_h2d_rows reads them in place — or the runtime refuses and says why; in BOTH
+    cases the next launch reports no error, and a refusal sends the frames through pinned staging memory instead."""
+    from sample_factory_amd import lib
+    torch.cuda.init()
+    host = (np.arange(3 * 4096) % 251).astype(np.uint8).reshape(3, 4096)
+    ok = lib.host_register(host.ctypes.data, host.nbytes)
+    dev = torch.zeros(3, 2, 4096, dtype=torch.uint8, device="cuda")  # (the launch that reported a refusal left behind)
+    torch.cuda.synchronize()
+    try:
+        src = torch.from_numpy(host)
+        assert src.is_pinned() == ok
+        if not ok:
+            assert b"hipHostRegister" in lib.load().sf_last_error()
+            src = torch.empty(host.shape, dtype=torch.uint8, pin_memory=True)
+            src.numpy()[:] = host
+        lib.h2d_rows(dev[:, 1], src)
+        torch.cuda.synchronize()
+        assert np.array_equal(dev[:, 1].cpu().numpy(), host) and int(dev[:, 0].max()) == 0
+    finally:
+        if ok:
+            assert lib.host_unregister(host.ctypes.data)
+
+
 @pytest.mark.parametrize("async_rl", [False, True], ids=["sync", "async"])
 def test_host_envs_in_worker_processes_double_buffered(async_rl):
     """The reference's default deployment for CPU envs (serial_mode=False): `num_workers` env worker PROCESSES x
