@@ -993,7 +993,9 @@ int sf_conv_fwd_t_os2(const float *in, int64_t in_sample_stride, const float *in
 /* Profiling aid (no reference counterpart): the kernel instantiation a conv/linear launch resolves to, spelled as
  * rocprofv3 prints it ("k_conv_fwd<128, 64, 2, 2, 0>").  op: 0 forward, 1 wgrad, 2 dgrad, 3 sf_conv_fwd_t,
  * 4 sf_conv_fwd_norm, 5 sf_conv_wgrad_norm, 6 sf_conv_fwd_relu_mask_os, 7 sf_conv_fwd_t_os
- * (also the names of the two-segment entry points _os2; for a linear layer op 7 names k_fwd_glds_z_os). */
+ * (also the names of the two-segment entry points _os2; for a linear layer op 7 names k_fwd_glds_z_os).  The reported
+ * name holds for aligned, dense, un-indexed operands (and a large enough split-K workspace); DESIGN.md 4.1 lists the
+ * operand-driven exceptions and the kernel each of them runs. */
 int sf_conv_kernel_name(int op, int64_t n, const sf_conv_desc *desc, int split_k_allowed, char *out, int cap);
 /* dense layer: out[M,N] = act(in[M,K] * w[K,N] + bias); wgrad: dw[K,N] = in^T dout, db = colsum(dout);
  * dgrad: din[M,K] = (dout[M,N] * w^T) * relu_mask(in_act). */

@@ -1103,10 +1103,14 @@ static FwdPlan plan_fwd(int64_t Mtot, int N, int K, int64_t ws_floats) {
         const int smax = K / 256;  // keep >= 8 chunks per split
         if (s > smax) s = smax;
         if (s > 16) s = 16;
-        if (s > 1 && (int64_t)s * Mtot * N <= ws_floats) {
-            const int chunks = (K + 31) / 32;
-            p.k_per_split = ((chunks + s - 1) / s) * 32;
-            p.splits = (K + p.k_per_split - 1) / p.k_per_split;
+        if (s > 1) {
+            // whole 32-deep chunks per slice can leave fewer slices than s (K = 3136, s = 12: 11 slices of 288); the
+            // workspace has to hold the slices that are written, which is what sf_conv_fwd_workspace reports
+            const int chunks = (K + 31) / 32, kps = ((chunks + s - 1) / s) * 32, z = (K + kps - 1) / kps;
+            if (z > 1 && (int64_t)z * Mtot * N <= ws_floats) {
+                p.k_per_split = kps;
+                p.splits = z;
+            }
         }
     }
     return p;
@@ -1946,7 +1950,10 @@ static int conv_wgrad_impl(const void *in, int64_t in_sample_stride, const int32
     float *partial_w = reinterpret_cast<float *>(workspace);
     float *partial_b = db ? partial_w + (int64_t)p.partials * K * N : nullptr;
     hipStream_t st = STREAM(stream);
-    const float *inf = reinterpret_cast<const float *>(in);
+    // k_linear_wgrad_small, k_wgrad_img and k_wgrad_glds(_z) take neither index nor offset: the plan selects them for
+    // dense f32 samples only (no index, traj_T == 0), whose first sample is `offset` strides past `in` (the stride is a
+    // multiple of 4 floats wherever the kernel loads vectors, so the base keeps its alignment)
+    const float *inf = reinterpret_cast<const float *>(in) + offset * in_sample_stride;
     switch (p.kernel) {
         case K_CONV1_WGRAD_BF16:
             if (p.variant) WGRAD_STRIP(k_conv1_wgrad_bf16<true>, dmask); else WGRAD_STRIP(k_conv1_wgrad_bf16<false>, dmask);
