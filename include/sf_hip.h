@@ -1015,7 +1015,9 @@ int sf_relu_mask(float *g, const float *act, int64_t n, void *stream);
  * padding 1, NHWC activations, weights K-major [9*Cin, Cout], k = (kh*3 + kw)*Cin + c.  The fully connected layers after
  * the last stage are sf_conv_fwd / sf_conv_wgrad / sf_conv_dgrad as 1x1 layers. */
 typedef struct {
-    int32_t Cin, H, W, Cout; /* input = output feature map (same padding); Cout 16 or 32, Cin <= 32 (16 or 32 for dgrad) */
+    int32_t Cin, H, W, Cout; /* input = output feature map (same padding).  f32 layers: Cin, Cout in {16, 32, 64, 128}, every
+                                pair (64 or 128 on either side: the MFMA family below); first layers (u8 frames, or f32 with
+                                another Cin): Cin <= 32, Cout in {16, 32, 64}, no data gradient */
     int32_t in_u8;           /* 1: the raw u8 NCHW frames, (x - sub_mean) * inv_scale on load (utils/normalize.py:51-70);
                                 0: f32 NHWC [n, H, W, Cin], dense */
     int32_t act_in;          /* activation applied to the input on load, 0 none 1 ReLU 2 tanh 3 ELU (model_utils.py:27-35);
@@ -1061,6 +1063,22 @@ int sf_res_conv_wgrad(const void *in, int64_t in_sample_stride, const int32_t *i
 int sf_res_conv_wgrad_norm(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *mu,
                            const float *rstd, const float *dout, float *dw, float *db, int64_t n,
                            const sf_res_desc *h_desc, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* The same three passes on v_mfma_f32_16x16x4_f32 (csrc/sf_resnet_mfma.hip), for dense f32 NHWC layers (in_u8 = 0, index
+ * NULL, traj_T = 0) with Cin and Cout in {16, 32, 64, 128}, every pair: signatures and semantics of their siblings above;
+ * in (and in_sample_stride * 4 bytes) 16-byte aligned as well.  sf_res_conv_fwd / _dgrad / _wgrad / _wgrad_workspace call
+ * these for a layer with 64 or 128 channels on either side (cfg.encoder_resnet_width = 2, 4) and keep their own kernels
+ * everywhere else.  The weight gradient needs sf_res_conv_wgrad_mfma_workspace(...) bytes and returns SF_ERR_UNSUPPORTED
+ * for an image too wide for one row band in LDS (about 80 columns at Cout = 128). */
+int sf_res_conv_fwd_mfma(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *w,
+                         const float *bias, const float *residual, float *out, float *out_act, int act_out, int64_t n,
+                         const sf_res_desc *h_desc, void *stream);
+int sf_res_conv_dgrad_mfma(const float *dout, const float *w, const float *pre, const float *g_add, float *din, int64_t n,
+                           const sf_res_desc *h_desc, void *stream);
+int64_t sf_res_conv_wgrad_mfma_workspace(int64_t n, const sf_res_desc *h_desc);
+int sf_res_conv_wgrad_mfma(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *dout,
+                           float *dw, float *db, int64_t n, const sf_res_desc *h_desc, void *workspace,
+                           int64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -103,6 +103,10 @@ ENGINE_FLAGS = [
     #                                          wrapper's nearest: on the device the better filter costs nothing
     ("device_grayscale", _bool, False),      # R, G, B -> one luma plane after the resize, in the same launch (C must be 3);
     #                                          works alone, at the env's own size
+    ("encoder_resnet_width", int, 1),        # k in {1, 2, 4}: the channel multiplier of resnet_impala (Cobbe et al. run x1,
+    #                                          x2, x4), stages of 16k / 32k / 32k channels, two residual blocks each; k > 1
+    #                                          runs its 64- and 128-channel 3x3 convs on the MFMA family;
+    #                                          any other value, or k != 1 with another architecture, is refused
     ("augment_random_shift", int, 0),        # P > 0: every SGD step trains on its minibatch's frames shifted at random by up
     #                                          to P pixels (pad P with edge replication, crop back: RAD / DrQ), gathered on
     #                                          the device in one launch (sf_random_shift_gather); rollouts,
@@ -229,9 +233,27 @@ def preprocess_cfg(cfg, env_info) -> bool:
     return verify_cfg(cfg, env_info)
 
 
+def resnet_width(cfg) -> int:
+    """cfg.encoder_resnet_width, checked: 1, 2 or 4, and 1 unless the architecture is resnet_impala (ValueError)"""
+    k = getattr(cfg, "encoder_resnet_width", 1)
+    if isinstance(k, bool) or k not in (1, 2, 4):
+        raise ValueError(f"encoder_resnet_width={k} must be 1, 2 or 4")
+    if k != 1 and cfg.encoder_conv_architecture != "resnet_impala":
+        raise ValueError(f"encoder_resnet_width={k} needs encoder_conv_architecture=resnet_impala, got "
+                         f"encoder_conv_architecture={cfg.encoder_conv_architecture}")
+    return int(k)
+
+
+def resnet_stages(cfg):
+    """((channels, residual blocks), ...) of the resnet_impala tower at cfg.encoder_resnet_width"""
+    k = resnet_width(cfg)
+    return ((16 * k, 2), (32 * k, 2), (32 * k, 2))  # encoder.py:180-182 (configuration from the IMPALA paper), times k
+
+
 def verify_cfg(cfg, env_info) -> bool:
     """The constraints of cfg/arguments.py:105-201 that concern the hot path."""
     ok = True
+    resnet_width(cfg)  # raises ValueError
 
     def err(msg):
         nonlocal ok

@@ -3,18 +3,20 @@
 // Reference op sequences replaced by each entry point are cited in include/sf_hip.h.
 //
 // Layout as in the rest of the library: activations NHWC, weights K-major [9*Cin, Cout] with k = (kh*3 + kw)*Cin + c.
-// The widths are the ones the architecture fixes (Cout in {16, 32}; the data gradient also needs Cin in {16, 32});
-// the first layer takes any Cin <= 32 and reads the raw u8 NCHW frames in place.
+// The fp32 FMA kernels of this file serve the widths of the default tower (Cout in {16, 32}; the data gradient also needs
+// Cin in {16, 32}) and the first layer of every tower: any Cin <= 32, Cout up to 64, the raw u8 NCHW frames read in place.
+// An f32 layer with 64 or 128 channels on either side (cfg.encoder_resnet_width = 2, 4) is routed by the same entry
+// points to the MFMA family of sf_resnet_mfma.hip.
 //
 // Compiled with -ffp-contract=off: the dot products use explicit fmaf (as every GEMM library does), every other op
 // (bias, residual add, activation derivative, gradient add) rounds after each op in torch's order.
 #include "sf_common.h"
+#include "sf_resnet_shared.h"
 
 #define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
 namespace {
 
-constexpr int RES_BLOCK = 256;
 constexpr int RES_MAX_K = 9 * 32;         // 3x3 taps x at most 32 input channels
 constexpr int RES_WG_TILE = 16;           // output pixels staged per weight-gradient step
 constexpr int RES_WG_MAX_PARTS = 1024;    // partial sums of the two-stage weight-gradient reduction
@@ -25,25 +27,6 @@ struct ResG {
     float sub_mean, inv_scale;
     const float *nmu, *nrstd;  // sf_res_conv_fwd_norm / _wgrad_norm: the observation normaliser's f32 tables [Cin*H*W], else NULL
 };
-
-__device__ __forceinline__ float act_fwd(int kind, float z) {
-    switch (kind) {
-        case 1: return fmaxf(z, 0.0f);
-        case 2: return tanhf(z);
-        case 3: return z > 0.0f ? z : expm1f(z);
-        default: return z;
-    }
-}
-
-// derivative of the activation at the PRE-activation value z (torch's elu_backward / tanh_backward / threshold_backward)
-__device__ __forceinline__ float act_grad(int kind, float z) {
-    switch (kind) {
-        case 1: return z > 0.0f ? 1.0f : 0.0f;
-        case 2: { const float t = tanhf(z); return 1.0f - t * t; }
-        case 3: return z > 0.0f ? 1.0f : expf(z);
-        default: return 1.0f;
-    }
-}
 
 // element offset of sample `smp`'s first input element: dataset row index[smp] | offset + smp, slab row d + d / traj_T
 __device__ __forceinline__ int64_t res_sample_base(const ResG &g, const int32_t *__restrict__ index, int64_t smp) {
@@ -294,6 +277,7 @@ __global__ __launch_bounds__(RES_BLOCK) void k_res_conv_wgrad_part(const void *_
     }
 }
 
+// stage 2 of both weight gradients: partial sums part[parts][KC + Cout] added in part order
 __global__ __launch_bounds__(RES_BLOCK) void k_res_conv_wgrad_sum(const float *__restrict__ part, int parts, int KC, int Cout,
                                                                   float *__restrict__ gw, float *__restrict__ gb) {
     const int e = blockIdx.x * RES_BLOCK + threadIdx.x;
@@ -305,17 +289,27 @@ __global__ __launch_bounds__(RES_BLOCK) void k_res_conv_wgrad_sum(const float *_
     else gb[e - KC] = s;
 }
 
-int res_check(const sf_res_desc *d, bool need_inner) {
+// the layer belongs to the MFMA family: an f32 layer, 64 or 128 channels on either side
+bool res_is_mfma(const sf_res_desc *d) {
+    return (d->Cin >= 64 || d->Cout >= 64) && !d->in_u8 && res_mfma_width(d->Cin) && res_mfma_width(d->Cout);
+}
+
+int res_check(const sf_res_desc *d, bool need_inner, bool *mfma) {
     SF_REQUIRE(d != nullptr, "sf_res_*: desc is NULL");
     SF_REQUIRE(d->H >= 1 && d->W >= 1 && d->Cin >= 1, "sf_res_*: bad geometry Cin=%d H=%d W=%d", d->Cin, d->H, d->W);
     SF_REQUIRE(d->act_in >= 0 && d->act_in <= 3, "sf_res_*: act_in=%d not in 0..3", d->act_in);
     SF_REQUIRE(d->traj_T >= 0, "sf_res_*: traj_T=%d", d->traj_T);
-    if (d->Cout != 16 && d->Cout != 32) {
-        snprintf(sf_err_buf, sizeof(sf_err_buf), "sf_res_*: Cout=%d (16 or 32 only)", d->Cout);
-        return SF_ERR_UNSUPPORTED;
-    }
-    if (d->Cin > 32 || (need_inner && d->Cin != 16 && d->Cin != 32)) {
-        snprintf(sf_err_buf, sizeof(sf_err_buf), "sf_res_*: Cin=%d unsupported here", d->Cin);
+    const bool wide = d->Cin >= 64 || d->Cout >= 64;
+    *mfma = res_is_mfma(d);
+    if (*mfma) return SF_OK;
+    // the first layer (any Cin <= 32) reaches Cout = 64 at width 4; it has no data gradient
+    const bool fma = need_inner ? !wide && res_mfma_width(d->Cin) && res_mfma_width(d->Cout)
+                                : d->Cin <= 32 && (d->Cout == 16 || d->Cout == 32 || d->Cout == 64);
+    if (!fma) {
+        snprintf(sf_err_buf, sizeof(sf_err_buf),
+                 "sf_res_*: Cin=%d Cout=%d in_u8=%d unsupported%s (served: f32 layers with Cin and Cout in {16, 32, 64, 128}; "
+                 "first layers, u8 or f32, with Cin <= 32 and Cout in {16, 32, 64}, forward and weight gradient only)",
+                 d->Cin, d->Cout, d->in_u8, need_inner ? " by the data gradient" : "");
         return SF_ERR_UNSUPPORTED;
     }
     return SF_OK;
@@ -337,17 +331,25 @@ int64_t res_wgrad_parts(int64_t np) {
     return (np + rows - 1) / rows;
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
+
+int sf_res_wgrad_sum_launch(const float *part, int parts, int KC, int Cout, float *gw, float *gb, hipStream_t s) {
+    hipLaunchKernelGGL(k_res_conv_wgrad_sum, dim3((unsigned)((KC + Cout + RES_BLOCK - 1) / RES_BLOCK)), dim3(RES_BLOCK), 0, s,
+                       part, parts, KC, Cout, gw, gb);
+    return sf_launch_status("sf_res_conv_wgrad");
+}
 
 // mu / rstd: the observation normaliser's tables (sf_res_conv_fwd_norm), else NULL
 static int res_conv_fwd_impl(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,
                              const float *w, const float *bias, const float *residual, float *out, float *out_act,
                              int act_out, int64_t n, const sf_res_desc *h_desc, void *stream, const float *mu,
                              const float *rstd) {
-    int rc = res_check(h_desc, false);
+    bool mfma;
+    int rc = res_check(h_desc, false, &mfma);
     if (rc) return rc;
+    if (mfma)
+        return sf_res_conv_fwd_mfma(in, in_sample_stride, index, offset, w, bias, residual, out, out_act, act_out, n, h_desc,
+                                    stream);
     SF_REQUIRE(in && w && bias && out, "sf_res_conv_fwd: NULL operand");
     SF_REQUIRE(n >= 0 && offset >= 0, "sf_res_conv_fwd: n=%lld offset=%lld", (long long)n, (long long)offset);
     SF_REQUIRE(act_out >= 0 && act_out <= 3, "sf_res_conv_fwd: act_out=%d", act_out);
@@ -369,8 +371,10 @@ static int res_conv_fwd_impl(const void *in, int64_t in_sample_stride, const int
                        act_out, n, g)
     if (d.Cout == 16) {
         if (d.in_u8) RES_FWD(16, true); else RES_FWD(16, false);
-    } else {
+    } else if (d.Cout == 32) {
         if (d.in_u8) RES_FWD(32, true); else RES_FWD(32, false);
+    } else {
+        if (d.in_u8) RES_FWD(64, true); else RES_FWD(64, false);
     }
 #undef RES_FWD
     return sf_launch_status("sf_res_conv_fwd");
@@ -420,8 +424,10 @@ extern "C" int sf_res_pool_bwd(const float *dout, const uint8_t *argmax, float *
 
 extern "C" int sf_res_conv_dgrad(const float *dout, const float *w, const float *pre, const float *g_add, float *din,
                                  int64_t n, const sf_res_desc *h_desc, void *stream) {
-    int rc = res_check(h_desc, true);
+    bool mfma;
+    int rc = res_check(h_desc, true, &mfma);
     if (rc) return rc;
+    if (mfma) return sf_res_conv_dgrad_mfma(dout, w, pre, g_add, din, n, h_desc, stream);
     SF_REQUIRE(dout && w && din, "sf_res_conv_dgrad: NULL operand");
     SF_REQUIRE(!h_desc->act_in || pre, "sf_res_conv_dgrad: act_in=%d needs the pre-activation input", h_desc->act_in);
     SF_REQUIRE(!h_desc->in_u8, "sf_res_conv_dgrad: the raw-frame layer has no data gradient");
@@ -443,6 +449,7 @@ extern "C" int sf_res_conv_dgrad(const float *dout, const float *w, const float 
 
 extern "C" int64_t sf_res_conv_wgrad_workspace(int64_t n, const sf_res_desc *h_desc) {
     if (!h_desc || n < 0) return 0;
+    if (res_is_mfma(h_desc)) return sf_res_conv_wgrad_mfma_workspace(n, h_desc);
     const int64_t E = 9LL * h_desc->Cin * h_desc->Cout + h_desc->Cout;
     return res_wgrad_parts(n * h_desc->H * h_desc->W) * E * (int64_t)sizeof(float);
 }
@@ -452,8 +459,12 @@ static int res_conv_wgrad_impl(const void *in, int64_t in_sample_stride, const i
                                const float *dout, float *dw, float *db, int64_t n, const sf_res_desc *h_desc,
                                void *workspace, int64_t workspace_bytes, void *stream, const float *mu,
                                const float *rstd) {
-    int rc = res_check(h_desc, false);
+    bool mfma;
+    int rc = res_check(h_desc, false, &mfma);
     if (rc) return rc;
+    if (mfma)
+        return sf_res_conv_wgrad_mfma(in, in_sample_stride, index, offset, dout, dw, db, n, h_desc, workspace, workspace_bytes,
+                                      stream);
     SF_REQUIRE(in && dout && dw && db, "sf_res_conv_wgrad: NULL operand");
     SF_REQUIRE(n >= 0 && offset >= 0, "sf_res_conv_wgrad: n=%lld offset=%lld", (long long)n, (long long)offset);
     const sf_res_desc &d = *h_desc;
@@ -465,7 +476,7 @@ static int res_conv_wgrad_impl(const void *in, int64_t in_sample_stride, const i
     const int64_t need = sf_res_conv_wgrad_workspace(n, h_desc);
     SF_REQUIRE(workspace && workspace_bytes >= need, "sf_res_conv_wgrad: workspace %lld bytes < %lld",
                (long long)workspace_bytes, (long long)need);
-    const int KC = 9 * d.Cin * d.Cout, E = KC + d.Cout;
+    const int KC = 9 * d.Cin * d.Cout;
     hipStream_t s = STREAM(stream);
     const int64_t NP = n * d.H * d.W;
     const int64_t parts = res_wgrad_parts(NP);
@@ -478,15 +489,15 @@ static int res_conv_wgrad_impl(const void *in, int64_t in_sample_stride, const i
                        part, n, rows, g)
     if (d.Cout == 16) {
         if (d.in_u8) RES_WG(16, true); else RES_WG(16, false);
-    } else {
+    } else if (d.Cout == 32) {
         if (d.in_u8) RES_WG(32, true); else RES_WG(32, false);
+    } else {
+        if (d.in_u8) RES_WG(64, true); else RES_WG(64, false);
     }
 #undef RES_WG
     rc = sf_launch_status("sf_res_conv_wgrad (partials)");
     if (rc) return rc;
-    hipLaunchKernelGGL(k_res_conv_wgrad_sum, dim3((unsigned)((E + RES_BLOCK - 1) / RES_BLOCK)), dim3(RES_BLOCK), 0, s,
-                       part, (int)parts, KC, d.Cout, dw, db);
-    return sf_launch_status("sf_res_conv_wgrad");
+    return sf_res_wgrad_sum_launch(part, (int)parts, KC, d.Cout, dw, db, s);
 }
 
 extern "C" int sf_res_conv_wgrad(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset,

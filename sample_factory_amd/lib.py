@@ -78,6 +78,7 @@ SYMBOLS = [
     "sf_dp_oneshot_allreduce_f64", "sf_dp_oneshot_status", "sf_dp_oneshot_destroy",
     "sf_res_conv_fwd", "sf_res_pool_fwd", "sf_res_pool_bwd", "sf_res_conv_dgrad", "sf_res_conv_wgrad_workspace",
     "sf_res_conv_wgrad", "sf_res_conv_fwd_norm", "sf_res_conv_wgrad_norm",
+    "sf_res_conv_fwd_mfma", "sf_res_conv_dgrad_mfma", "sf_res_conv_wgrad_mfma_workspace", "sf_res_conv_wgrad_mfma",
     "sf_pixcatch_state_words", "sf_pixcatch_reset", "sf_pixcatch_step", "sf_pixcatch_reset_levels",
     "sf_pixcatch_step_levels",
     "sf_random_shift_gather", "sf_augment_gather",
@@ -262,6 +263,7 @@ def load() -> C.CDLL:
         lib.sf_conv_fwd_t_workspace.restype = C.c_int64
         lib.sf_linear_wgrad_workspace.restype = C.c_int64
         lib.sf_res_conv_wgrad_workspace.restype = C.c_int64
+        lib.sf_res_conv_wgrad_mfma_workspace.restype = C.c_int64
         _lib = lib
     return _lib
 
@@ -1620,13 +1622,13 @@ def _res_in(t: torch.Tensor, desc: sf_res_desc) -> C.c_void_p:
 
 
 def res_conv_fwd(inp, in_sample_stride, index, offset, w, bias, out, n, desc: sf_res_desc, residual=None, out_act=None,
-                 act_out=0) -> None:
+                 act_out=0, sym="sf_res_conv_fwd") -> None:
     """3x3 same conv: out = [residual +] conv(act_in(inp)) + bias, out_act = act_out(out); `inp` may be a strided view
     (u8 frames: index / offset / traj_T addressing as conv_fwd_raw)"""
-    _check(load().sf_res_conv_fwd(_res_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"), i64(offset),
-                                  ptr(w, "f32", "w"), ptr(bias, "f32", "bias"), ptr(residual, "f32", "residual"),
-                                  ptr(out, "f32", "out"), ptr(out_act, "f32", "out_act"), int(act_out), i64(n),
-                                  C.byref(desc), stream()), "sf_res_conv_fwd")
+    _check(getattr(load(), sym)(_res_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"), i64(offset),
+                                ptr(w, "f32", "w"), ptr(bias, "f32", "bias"), ptr(residual, "f32", "residual"),
+                                ptr(out, "f32", "out"), ptr(out_act, "f32", "out_act"), int(act_out), i64(n),
+                                C.byref(desc), stream()), sym)
 
 
 def res_pool_fwd(inp, out, argmax, n, H, W, Cn) -> None:
@@ -1639,22 +1641,38 @@ def res_pool_bwd(dout, argmax, din, n, H, W, Cn) -> None:
                                   int(H), int(W), int(Cn), stream()), "sf_res_pool_bwd")
 
 
-def res_conv_dgrad(dout, w, pre, din, n, desc: sf_res_desc, g_add=None) -> None:
+def res_conv_dgrad(dout, w, pre, din, n, desc: sf_res_desc, g_add=None, sym="sf_res_conv_dgrad") -> None:
     """din = [g_add +] conv_transpose(dout, w) * act_in'(pre)"""
-    _check(load().sf_res_conv_dgrad(ptr(dout, "f32", "dout"), ptr(w, "f32", "w"), ptr(pre, "f32", "pre"),
-                                    ptr(g_add, "f32", "g_add"), ptr(din, "f32", "din"), i64(n), C.byref(desc), stream()),
-           "sf_res_conv_dgrad")
+    _check(getattr(load(), sym)(ptr(dout, "f32", "dout"), ptr(w, "f32", "w"), ptr(pre, "f32", "pre"),
+                                ptr(g_add, "f32", "g_add"), ptr(din, "f32", "din"), i64(n), C.byref(desc), stream()), sym)
 
 
 def res_conv_wgrad_workspace(n, desc: sf_res_desc) -> int:
     return int(load().sf_res_conv_wgrad_workspace(i64(n), C.byref(desc)))
 
 
-def res_conv_wgrad(inp, in_sample_stride, index, offset, dout, dw, db, n, desc: sf_res_desc, workspace) -> None:
-    _check(load().sf_res_conv_wgrad(_res_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"), i64(offset),
-                                    ptr(dout, "f32", "dout"), ptr(dw, "f32", "dw"), ptr(db, "f32", "db"), i64(n),
-                                    C.byref(desc), ptr(workspace, "u8", "workspace"), i64(workspace.numel()), stream()),
-           "sf_res_conv_wgrad")
+def res_conv_wgrad(inp, in_sample_stride, index, offset, dout, dw, db, n, desc: sf_res_desc, workspace,
+                   sym="sf_res_conv_wgrad") -> None:
+    _check(getattr(load(), sym)(_res_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"), i64(offset),
+                                ptr(dout, "f32", "dout"), ptr(dw, "f32", "dw"), ptr(db, "f32", "db"), i64(n),
+                                C.byref(desc), ptr(workspace, "u8", "workspace"), i64(workspace.numel()), stream()), sym)
+
+
+# the MFMA family (csrc/sf_resnet_mfma.hip) called directly: what the entry points above route wide f32 layers to
+def res_conv_fwd_mfma(*a, **kw) -> None:
+    res_conv_fwd(*a, sym="sf_res_conv_fwd_mfma", **kw)
+
+
+def res_conv_dgrad_mfma(*a, **kw) -> None:
+    res_conv_dgrad(*a, sym="sf_res_conv_dgrad_mfma", **kw)
+
+
+def res_conv_wgrad_mfma(*a, **kw) -> None:
+    res_conv_wgrad(*a, sym="sf_res_conv_wgrad_mfma", **kw)
+
+
+def res_conv_wgrad_mfma_workspace(n, desc: sf_res_desc) -> int:
+    return int(load().sf_res_conv_wgrad_mfma_workspace(i64(n), C.byref(desc)))
 
 
 def res_conv_fwd_norm(inp, in_sample_stride, index, offset, mu, rstd, w, bias, out, n, desc: sf_res_desc) -> None:

@@ -17,6 +17,7 @@ import torch
 from torch import Tensor, nn
 
 from sample_factory_amd.algo.utils.torch_utils import calc_num_elements
+from sample_factory_amd.cfg.arguments import resnet_stages
 from sample_factory_amd.model.model_utils import ModelModule, create_mlp, model_device, nonlinearity
 from sample_factory_amd.utils.utils import log
 
@@ -123,15 +124,15 @@ class ResBlock(nn.Module):
 
 
 class ResnetEncoder(Encoder):
-    """cfg.encoder_conv_architecture = resnet_impala: three (conv3x3, maxpool/2, 2 residual blocks) stages of 16 / 32 / 32
-    channels, then cfg.encoder_conv_mlp_layers"""
+    """cfg.encoder_conv_architecture = resnet_impala: three (conv3x3, maxpool/2, 2 residual blocks) stages of 16k / 32k / 32k
+    channels, k = cfg.encoder_resnet_width, then cfg.encoder_conv_mlp_layers"""
 
     def __init__(self, cfg, obs_space):
         super().__init__(cfg)
         if cfg.encoder_conv_architecture != "resnet_impala":
             raise NotImplementedError(f"Unknown resnet architecture {cfg.encoder_conv_architecture}")
         c, layers = int(obs_space.shape[0]), []
-        for cout, blocks in ((16, 2), (32, 2), (32, 2)):
+        for cout, blocks in resnet_stages(cfg):
             layers += [nn.Conv2d(c, cout, 3, stride=1, padding=1), nn.MaxPool2d(3, stride=2, padding=1)]
             layers += [ResBlock(cfg, cout, cout) for _ in range(blocks)]
             c = cout

@@ -1,6 +1,7 @@
 """The resnet_impala image encoder on the native kernels (reference: ResnetEncoder, sample_factory/model/encoder.py:153-221):
 three stages of Conv2d(3x3, padding 1) -> MaxPool2d(3, 2, 1) -> two residual blocks x + conv(act(conv(act(x)))), with
-16 / 32 / 32 channels, then act, the flatten in the reference's C*H*W order and cfg.encoder_conv_mlp_layers.
+16k / 32k / 32k channels (k = cfg.encoder_resnet_width), then act, the flatten in the reference's C*H*W order and
+cfg.encoder_conv_mlp_layers.
 
 `ResnetImpalaTower` is an encoder tower of model/actor_critic_multikey.py (the same surface as `ActorCritic(part="encoder")`):
 its forward ends at the encoder output, its backward starts from d(loss) / d(pre-activation of that output), which is the
@@ -16,10 +17,9 @@ import numpy as np
 import torch
 
 from sample_factory_amd import lib
+from sample_factory_amd.cfg.arguments import resnet_stages
 from sample_factory_amd.model import actor_critic as _ac
 from sample_factory_amd.model.actor_critic import ACT_KIND, NativeTower, _Layer, _linear_desc, _pad
-
-RESNET_STAGES = ((16, 2), (32, 2), (32, 2))  # encoder.py:180-182 (configuration from the IMPALA paper)
 
 
 def uses_resnet(cfg, obs_space) -> bool:
@@ -86,7 +86,7 @@ class ResnetImpalaTower(NativeTower):
         # sf_res_conv_wgrad_norm); only with SF_CONV1_NORM=0 it reads on.apply's f32 NHWC batch
         self._fused_norm = norm_input and _ac._CONV1_NORM
         cin, h, w, i = C, H, W, 0
-        for cout, blocks in RESNET_STAGES:
+        for cout, blocks in resnet_stages(cfg):  # 16 / 32 / 32 at width 1; wider: the same entry points, MFMA kernels
             first = i == 0 and (not norm_input or self._fused_norm)
             conv = _Conv3(f"{pfx}conv_head.{i}", cin, cout, h, w, 0, u8=first, sub_mean=sub_mean if first else 0.0,
                           inv_scale=inv_scale if first else 1.0)
@@ -101,6 +101,12 @@ class ResnetImpalaTower(NativeTower):
             self.stages.append((conv, blk, (h, w), (oh, ow)))
             self.convs += [conv] + [c for b in blk for c in b]
             cin, h, w = cout, oh, ow
+        for c in self.convs:  # refuse here what the first Learner.train would refuse: the query answers 0 for such a layer
+            if lib.res_conv_wgrad_workspace(1, c.desc) == 0:
+                raise NotImplementedError(
+                    f"resnet_impala tower at encoder_resnet_width={cfg.encoder_resnet_width}: the weight gradient of a "
+                    f"{c.Cin} -> {c.N} layer stages whole rows in a 64 KB LDS band, and a row of {c.W} pixels does not fit "
+                    f"(84 pixels at 64 -> 128, 124 at 32 -> 64: frames up to 168 pixels wide at width 4, 248 at width 2)")
         self.conv_out_chw = (cin, h, w)
         feat = cin * h * w
         self.fcs: List[_Layer] = []
