@@ -1080,6 +1080,26 @@ int sf_res_conv_wgrad_mfma(const void *in, int64_t in_sample_stride, const int32
                            float *dw, float *db, int64_t n, const sf_res_desc *h_desc, void *workspace,
                            int64_t workspace_bytes, void *stream);
 
+/* The same three passes on v_mfma_f32_16x16x32_bf16 (csrc/sf_resnet_bf16.hip; cfg.encoder_resnet_bf16), for dense f32 NHWC
+ * layers (in_u8 = 0, index NULL, traj_T = 0) with Cin and Cout in {32, 64, 128}, every pair: signatures, alignment and
+ * semantics of the _mfma siblings above, with both operands of the matrix product rounded to bf16 (nearest even, once per
+ * element; the input after its activation): conv(bf16(act_in(in)), bf16(w)), conv_transpose(bf16(dout), bf16(w)),
+ * patches(bf16(act_in(in)))^T bf16(dout), db = sum bf16(dout).  Accumulation, bias, residual, activations, act_in'(pre) and
+ * g_add are fp32, and every tensor in memory stays fp32: w is the same [9*Cin, Cout] block, converted inside the launch.
+ * An output element's value does not depend on n or on its sample's position in the batch.  Reached by name only: the
+ * plain sf_res_conv_* entry points never route here.  The weight gradient needs sf_res_conv_wgrad_bf16_workspace(...)
+ * bytes; the query answers 0 and the entry point SF_ERR_UNSUPPORTED for a layer outside the family or an image too wide
+ * for one row band in LDS (above 96 columns at 32 -> 32, 120 at Cout = 128). */
+int sf_res_conv_fwd_bf16(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *w,
+                         const float *bias, const float *residual, float *out, float *out_act, int act_out, int64_t n,
+                         const sf_res_desc *h_desc, void *stream);
+int sf_res_conv_dgrad_bf16(const float *dout, const float *w, const float *pre, const float *g_add, float *din, int64_t n,
+                           const sf_res_desc *h_desc, void *stream);
+int64_t sf_res_conv_wgrad_bf16_workspace(int64_t n, const sf_res_desc *h_desc);
+int sf_res_conv_wgrad_bf16(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *dout,
+                           float *dw, float *db, int64_t n, const sf_res_desc *h_desc, void *workspace,
+                           int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

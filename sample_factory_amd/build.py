@@ -18,6 +18,7 @@ SOURCES = [
     ("sf_dp.hip", []),                      # host code: RCCL gradient exchange (librccl resolved with dlopen at first use)
     ("sf_resnet.hip", ["-ffp-contract=off"]),  # resnet_impala: explicit fmaf in the dot products, torch's order elsewhere
     ("sf_resnet_mfma.hip", ["-ffp-contract=off"]),  # its 3x3 convs on fp32 MFMA; the epilogues round like sf_resnet.hip's
+    ("sf_resnet_bf16.hip", ["-ffp-contract=off"]),  # ... and on bf16 MFMA (cfg.encoder_resnet_bf16): the same flags
     ("sf_ingest.hip", []),                  # observation ingest: the device frame stack, the HWC transpose, resize / grey-scale
     ("sf_pixcatch.hip", []),                # PixelCatch: the device-resident pixel game (step + render in one launch)
     ("sf_augment.hip", []),                 # training-time augmentation: the shift / intensity / cutout gather of a minibatch's frames

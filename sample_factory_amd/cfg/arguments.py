@@ -107,6 +107,11 @@ ENGINE_FLAGS = [
     #                                          x2, x4), stages of 16k / 32k / 32k channels, two residual blocks each; k > 1
     #                                          runs its 64- and 128-channel 3x3 convs on the MFMA family;
     #                                          any other value, or k != 1 with another architecture, is refused
+    ("encoder_resnet_bf16", _bool, False),   # resnet_impala only: its f32 3x3 convs with 32, 64 or 128 channels on both sides
+    #                                          run on the bf16 matrix pipe in every pass (rollout, enjoy, training forward,
+    #                                          both gradients): operands rounded to bf16, fp32 accumulation, fp32 tensors
+    #                                          and master weights (csrc/sf_resnet_bf16.hip); off: every
+    #                                          launch and result as before; with another architecture it is refused
     ("augment_random_shift", int, 0),        # P > 0: every SGD step trains on its minibatch's frames shifted at random by up
     #                                          to P pixels (pad P with edge replication, crop back: RAD / DrQ), gathered on
     #                                          the device in one launch (sf_random_shift_gather); rollouts,
@@ -244,6 +249,15 @@ def resnet_width(cfg) -> int:
     return int(k)
 
 
+def resnet_bf16(cfg) -> bool:
+    """cfg.encoder_resnet_bf16, checked: only with encoder_conv_architecture=resnet_impala (ValueError)"""
+    on = bool(getattr(cfg, "encoder_resnet_bf16", False))
+    if on and cfg.encoder_conv_architecture != "resnet_impala":
+        raise ValueError(f"encoder_resnet_bf16=True needs encoder_conv_architecture=resnet_impala, got "
+                         f"encoder_conv_architecture={cfg.encoder_conv_architecture}")
+    return on
+
+
 def resnet_stages(cfg):
     """((channels, residual blocks), ...) of the resnet_impala tower at cfg.encoder_resnet_width"""
     k = resnet_width(cfg)
@@ -254,6 +268,7 @@ def verify_cfg(cfg, env_info) -> bool:
     """The constraints of cfg/arguments.py:105-201 that concern the hot path."""
     ok = True
     resnet_width(cfg)  # raises ValueError
+    resnet_bf16(cfg)   # ... too
 
     def err(msg):
         nonlocal ok

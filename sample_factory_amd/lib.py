@@ -79,6 +79,7 @@ SYMBOLS = [
     "sf_res_conv_fwd", "sf_res_pool_fwd", "sf_res_pool_bwd", "sf_res_conv_dgrad", "sf_res_conv_wgrad_workspace",
     "sf_res_conv_wgrad", "sf_res_conv_fwd_norm", "sf_res_conv_wgrad_norm",
     "sf_res_conv_fwd_mfma", "sf_res_conv_dgrad_mfma", "sf_res_conv_wgrad_mfma_workspace", "sf_res_conv_wgrad_mfma",
+    "sf_res_conv_fwd_bf16", "sf_res_conv_dgrad_bf16", "sf_res_conv_wgrad_bf16_workspace", "sf_res_conv_wgrad_bf16",
     "sf_pixcatch_state_words", "sf_pixcatch_reset", "sf_pixcatch_step", "sf_pixcatch_reset_levels",
     "sf_pixcatch_step_levels",
     "sf_random_shift_gather", "sf_augment_gather",
@@ -264,6 +265,7 @@ def load() -> C.CDLL:
         lib.sf_linear_wgrad_workspace.restype = C.c_int64
         lib.sf_res_conv_wgrad_workspace.restype = C.c_int64
         lib.sf_res_conv_wgrad_mfma_workspace.restype = C.c_int64
+        lib.sf_res_conv_wgrad_bf16_workspace.restype = C.c_int64
         _lib = lib
     return _lib
 
@@ -1673,6 +1675,24 @@ def res_conv_wgrad_mfma(*a, **kw) -> None:
 
 def res_conv_wgrad_mfma_workspace(n, desc: sf_res_desc) -> int:
     return int(load().sf_res_conv_wgrad_mfma_workspace(i64(n), C.byref(desc)))
+
+
+# the bf16 family (csrc/sf_resnet_bf16.hip; cfg.encoder_resnet_bf16), reached by name only: operands of the matrix product
+# rounded to bf16, fp32 accumulation and epilogue, f32 layers with Cin and Cout in {32, 64, 128}
+def res_conv_fwd_bf16(*a, **kw) -> None:
+    res_conv_fwd(*a, sym="sf_res_conv_fwd_bf16", **kw)
+
+
+def res_conv_dgrad_bf16(*a, **kw) -> None:
+    res_conv_dgrad(*a, sym="sf_res_conv_dgrad_bf16", **kw)
+
+
+def res_conv_wgrad_bf16(*a, **kw) -> None:
+    res_conv_wgrad(*a, sym="sf_res_conv_wgrad_bf16", **kw)
+
+
+def res_conv_wgrad_bf16_workspace(n, desc: sf_res_desc) -> int:
+    return int(load().sf_res_conv_wgrad_bf16_workspace(i64(n), C.byref(desc)))
 
 
 def res_conv_fwd_norm(inp, in_sample_stride, index, offset, mu, rstd, w, bias, out, n, desc: sf_res_desc) -> None:

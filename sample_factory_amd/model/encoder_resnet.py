@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from sample_factory_amd import lib
-from sample_factory_amd.cfg.arguments import resnet_stages
+from sample_factory_amd.cfg.arguments import resnet_bf16, resnet_stages
 from sample_factory_amd.model import actor_critic as _ac
 from sample_factory_amd.model.actor_critic import ACT_KIND, NativeTower, _Layer, _linear_desc, _pad
 
@@ -34,13 +34,30 @@ class _Conv3:
     """one Conv2d(Cin, Cout, 3, stride=1, padding=1): weights K-major [9*Cin, Cout], k = (kh*3 + kw)*Cin + c"""
 
     def __init__(self, name: str, cin: int, cout: int, h: int, w: int, act_in: int, u8: bool = False,
-                 sub_mean: float = 0.0, inv_scale: float = 1.0):
+                 sub_mean: float = 0.0, inv_scale: float = 1.0, bf16: bool = False):
         self.wname, self.bname = name + ".weight", name + ".bias"
         self.Cin, self.N, self.H, self.W = cin, cout, h, w
         self.K = 9 * cin
         self.ref_w_shape = (cout, cin, 3, 3)
         self.desc = lib.sf_res_desc(Cin=cin, H=h, W=w, Cout=cout, in_u8=int(u8), act_in=act_in, traj_T=0,
                                     sub_mean=sub_mean, inv_scale=inv_scale)
+        # cfg.encoder_resnet_bf16: an f32 layer with 32, 64 or 128 channels on both sides runs EVERY pass on the bf16 family
+        # (csrc/sf_resnet_bf16.hip), so rollout, enjoy and training evaluate the same function; else the plain entry points
+        self.bf16 = bf16 and not u8 and cin in (32, 64, 128) and cout in (32, 64, 128)
+        if self.bf16:
+            self.fwd, self.dgrad, self.wgrad = lib.res_conv_fwd_bf16, lib.res_conv_dgrad_bf16, lib.res_conv_wgrad_bf16
+            self.wgrad_workspace = lib.res_conv_wgrad_bf16_workspace
+        else:
+            self.fwd, self.dgrad, self.wgrad = lib.res_conv_fwd, lib.res_conv_dgrad, lib.res_conv_wgrad
+            self.wgrad_workspace = lib.res_conv_wgrad_workspace
+
+    def max_width(self) -> int:
+        """the widest image whose row this layer's weight gradient can stage (its workspace query answers 0 above it)"""
+        d = lib.sf_res_desc.from_buffer_copy(self.desc)
+        d.W = 1
+        while d.W < 4096 and self.wgrad_workspace(1, d):
+            d.W += 1
+        return d.W - 1
 
     def w_from_ref(self, w_ref: torch.Tensor) -> torch.Tensor:
         return w_ref.permute(2, 3, 1, 0).reshape(self.K, self.N).contiguous()
@@ -85,24 +102,30 @@ class ResnetImpalaTower(NativeTower):
         # normalize_input: the first conv stays the raw-frame layer and normalises in its loader (sf_res_conv_fwd_norm /
         # sf_res_conv_wgrad_norm); only with SF_CONV1_NORM=0 it reads on.apply's f32 NHWC batch
         self._fused_norm = norm_input and _ac._CONV1_NORM
+        bf16 = resnet_bf16(cfg)
         cin, h, w, i = C, H, W, 0
         for cout, blocks in resnet_stages(cfg):  # 16 / 32 / 32 at width 1; wider: the same entry points, MFMA kernels
             first = i == 0 and (not norm_input or self._fused_norm)
             conv = _Conv3(f"{pfx}conv_head.{i}", cin, cout, h, w, 0, u8=first, sub_mean=sub_mean if first else 0.0,
-                          inv_scale=inv_scale if first else 1.0)
+                          inv_scale=inv_scale if first else 1.0, bf16=bf16)
             oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
             i += 2
             blk = []
             for _ in range(blocks):
-                c1 = _Conv3(f"{pfx}conv_head.{i}.res_block_core.1", cout, cout, oh, ow, act)
-                c2 = _Conv3(f"{pfx}conv_head.{i}.res_block_core.3", cout, cout, oh, ow, act)
+                c1 = _Conv3(f"{pfx}conv_head.{i}.res_block_core.1", cout, cout, oh, ow, act, bf16=bf16)
+                c2 = _Conv3(f"{pfx}conv_head.{i}.res_block_core.3", cout, cout, oh, ow, act, bf16=bf16)
                 blk.append((c1, c2))
                 i += 1
             self.stages.append((conv, blk, (h, w), (oh, ow)))
             self.convs += [conv] + [c for b in blk for c in b]
             cin, h, w = cout, oh, ow
         for c in self.convs:  # refuse here what the first Learner.train would refuse: the query answers 0 for such a layer
-            if lib.res_conv_wgrad_workspace(1, c.desc) == 0:
+            if c.bf16 and c.wgrad_workspace(1, c.desc) == 0:
+                raise NotImplementedError(
+                    f"resnet_impala tower with encoder_resnet_bf16: the bf16 weight gradient of a {c.Cin} -> {c.N} layer stages "
+                    f"whole rows in a 64 KB LDS band, and a row of {c.W} pixels does not fit: this layer takes at most "
+                    f"{c.max_width()} pixels (96 at 32 -> 32, 152 at Cout = 64, 120 at Cout = 128)")
+            if not c.bf16 and lib.res_conv_wgrad_workspace(1, c.desc) == 0:
                 raise NotImplementedError(
                     f"resnet_impala tower at encoder_resnet_width={cfg.encoder_resnet_width}: the weight gradient of a "
                     f"{c.Cin} -> {c.N} layer stages whole rows in a 64 KB LDS band, and a row of {c.W} pixels does not fit "
@@ -253,7 +276,7 @@ class ResnetImpalaTower(NativeTower):
             if s == 0 and norm_tabs is not None:
                 lib.res_conv_fwd_norm(x, stride, idx, off, norm_tabs[0], norm_tabs[1], wt, bs, full, n, d)
             else:
-                lib.res_conv_fwd(x, stride, idx, off, wt, bs, full, n, d)
+                conv.fwd(x, stride, idx, off, wt, bs, full, n, d)
             li += 1
             pooled = self._buf((tag, "s", s, "pool"), (n, oh, ow, conv.N))
             arg = self._buf((tag, "s", s, "arg"), (n, oh, ow, conv.N), dtype=torch.uint8)
@@ -264,15 +287,14 @@ class ResnetImpalaTower(NativeTower):
             for b, (c1, c2) in enumerate(blk):
                 t = self._buf((tag, "s", s, "b", b, "t"), (n, oh, ow, c1.N))
                 w1, b1 = self._wb(li, tag)
-                lib.res_conv_fwd(xb, oh * ow * c1.Cin, None, 0, w1, b1, t, n, c1.desc)
+                c1.fwd(xb, oh * ow * c1.Cin, None, 0, w1, b1, t, n, c1.desc)
                 y = self._buf((tag, "s", s, "b", b, "y"), (n, oh, ow, c2.N))
                 w2, b2 = self._wb(li + 1, tag)
                 if s == last_stage and b == len(blk) - 1:  # encoder.py:205: act after the last stage, from this epilogue
                     y_act = self._buf((tag, "y_act"), (n, oh, ow, c2.N))
-                    lib.res_conv_fwd(t, oh * ow * c2.Cin, None, 0, w2, b2, y, n, c2.desc, residual=xb, out_act=y_act,
-                                     act_out=act)
+                    c2.fwd(t, oh * ow * c2.Cin, None, 0, w2, b2, y, n, c2.desc, residual=xb, out_act=y_act, act_out=act)
                 else:
-                    lib.res_conv_fwd(t, oh * ow * c2.Cin, None, 0, w2, b2, y, n, c2.desc, residual=xb)
+                    c2.fwd(t, oh * ow * c2.Cin, None, 0, w2, b2, y, n, c2.desc, residual=xb)
                 li += 2
                 bl.append((xb, t, y))
                 xb = y
@@ -313,13 +335,13 @@ class ResnetImpalaTower(NativeTower):
             for b in range(len(blk) - 1, -1, -1):
                 c1, c2 = blk[b]
                 xb, t, _ = bl[b]
-                ws = self._workspace(lib.res_conv_wgrad_workspace(n, c2.desc))
-                lib.res_conv_wgrad(t, oh * ow * c2.Cin, None, 0, g, c2.gw, c2.gb, n, c2.desc, ws)
+                ws = self._workspace(c2.wgrad_workspace(n, c2.desc))  # c1 has c2's shape: the same size
+                c2.wgrad(t, oh * ow * c2.Cin, None, 0, g, c2.gw, c2.gb, n, c2.desc, ws)
                 g_t = self._buf(("g", "s", s, "b", b, "t"), (n, oh, ow, c1.N))
-                lib.res_conv_dgrad(g, c2.w, t, g_t, n, c2.desc)  # * act'(t)
-                lib.res_conv_wgrad(xb, oh * ow * c1.Cin, None, 0, g_t, c1.gw, c1.gb, n, c1.desc, ws)
+                c2.dgrad(g, c2.w, t, g_t, n, c2.desc)  # * act'(t)
+                c1.wgrad(xb, oh * ow * c1.Cin, None, 0, g_t, c1.gw, c1.gb, n, c1.desc, ws)
                 g_x = self._buf(("g", "s", s, "b", b, "x"), (n, oh, ow, c1.Cin))
-                lib.res_conv_dgrad(g_t, c1.w, xb, g_x, n, c1.desc, g_add=g)  # g_y + dgrad * act'(x): the skip
+                c1.dgrad(g_t, c1.w, xb, g_x, n, c1.desc, g_add=g)  # g_y + dgrad * act'(x): the skip
                 g = g_x
             g_full = self._buf(("g", "s", s, "full"), (n, h, w, conv.N))
             lib.res_pool_bwd(g, arg, g_full, n, h, w, conv.N)
@@ -328,13 +350,13 @@ class ResnetImpalaTower(NativeTower):
             if tT:
                 d = lib.sf_res_desc.from_buffer_copy(conv.desc)
                 d.traj_T = int(tT)
-            ws = self._workspace(lib.res_conv_wgrad_workspace(n, d))
+            ws = self._workspace(conv.wgrad_workspace(n, d))
             if s == 0 and ctx.get("norm_tabs") is not None:  # the forward normalised in the loader: so does the gradient
                 mu_, rstd_ = ctx["norm_tabs"]
                 lib.res_conv_wgrad_norm(x, stride, idx, off, mu_, rstd_, g_full, conv.gw, conv.gb, n, d, ws)
             else:
-                lib.res_conv_wgrad(x, stride, idx, off, g_full, conv.gw, conv.gb, n, d, ws)
+                conv.wgrad(x, stride, idx, off, g_full, conv.gw, conv.gb, n, d, ws)
             if s > 0:
                 g_in = self._buf(("g", "s", s, "in"), (n, h, w, conv.Cin))
-                lib.res_conv_dgrad(g_full, conv.w, None, g_in, n, conv.desc)
+                conv.dgrad(g_full, conv.w, None, g_in, n, conv.desc)
                 g = g_in
