@@ -107,10 +107,11 @@ ENGINE_FLAGS = [
     #                                          x2, x4), stages of 16k / 32k / 32k channels, two residual blocks each; k > 1
     #                                          runs its 64- and 128-channel 3x3 convs on the MFMA family;
     #                                          any other value, or k != 1 with another architecture, is refused
-    ("encoder_resnet_bf16", _bool, False),   # resnet_impala only: its f32 3x3 convs with 32, 64 or 128 channels on both sides
-    #                                          run on the bf16 matrix pipe in every pass (rollout, enjoy, training forward,
+    ("encoder_resnet_bf16", _bool, False),   # resnet_impala only: its f32 3x3 convs with 32, 64 or 128 channels on both sides,
+    #                                          and the 16 -> 16 and 16 -> 32 ones of the width-1 tower (every layer but the
+    #                                          raw-frame one), run on the bf16 matrix pipe in every pass (rollout, enjoy, training forward,
     #                                          both gradients): operands rounded to bf16, fp32 accumulation, fp32 tensors
-    #                                          and master weights (csrc/sf_resnet_bf16.hip); off: every
+    #                                          and master weights (csrc/sf_resnet_bf16.hip, sf_resnet_bf16_c16.hip); off: every
     #                                          launch and result as before; with another architecture it is refused
     ("augment_random_shift", int, 0),        # P > 0: every SGD step trains on its minibatch's frames shifted at random by up
     #                                          to P pixels (pad P with edge replication, crop back: RAD / DrQ), gathered on

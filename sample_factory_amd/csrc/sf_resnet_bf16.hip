@@ -1,6 +1,7 @@
 // sf_resnet_bf16.hip — the 3x3 / stride 1 / pad 1 conv family of the resnet_impala encoder on v_mfma_f32_16x16x32_bf16, for
 // f32 NHWC layers with Cin, Cout in {32, 64, 128} (every pair): cfg.encoder_resnet_bf16.  Reached by name only
-// (sf_res_conv_*_bf16); the plain entry points never route here.
+// (sf_res_conv_*_bf16); the plain entry points never route here.  The same entry points hand the pairs 16 -> 16 and
+// 16 -> 32 to sf_resnet_bf16_c16.hip (kernels built for 16 channels, the same arithmetic); any other pair with a 16 is refused.
 //
 // Arithmetic: both MFMA operands are rounded to bf16 (round to nearest even, v_cvt_pk_bf16_f32) once per element, the input
 // after its activation: bf16(act_in(x)), bf16(w), bf16(dout).  Accumulation is fp32 and everything outside the matrix
@@ -53,6 +54,8 @@ constexpr int RB_GRID_TARGET = 1024;       // work-groups the weight gradient ai
 extern __shared__ float4 rb_lds4[];
 
 inline bool rb_width(int c) { return c == 32 || c == 64 || c == 128; }
+// a 16 on the input side goes to sf_resnet_bf16_c16.hip; any other pair with a 16 is refused
+inline bool rb_served(int cin, int cout) { return (rb_width(cin) && rb_width(cout)) || sf_res_c16_pair(cin, cout); }
 
 __device__ __forceinline__ bf16x8 rb_pack(const float4 &a, const float4 &b) {
     bf16x8 r;
@@ -372,10 +375,10 @@ int rb_check(const sf_res_desc *d, const char *what) {
     SF_REQUIRE(d != nullptr, "%s: desc is NULL", what);
     SF_REQUIRE(d->H >= 1 && d->W >= 1, "%s: bad geometry H=%d W=%d", what, d->H, d->W);
     SF_REQUIRE(d->act_in >= 0 && d->act_in <= 3, "%s: act_in=%d not in 0..3", what, d->act_in);
-    if (d->in_u8 || d->traj_T != 0 || !rb_width(d->Cin) || !rb_width(d->Cout)) {
+    if (d->in_u8 || d->traj_T != 0 || !rb_served(d->Cin, d->Cout)) {
         snprintf(sf_err_buf, sizeof(sf_err_buf),
                  "%s: Cin=%d Cout=%d in_u8=%d traj_T=%d (the bf16 family serves dense f32 NHWC layers with Cin and Cout in "
-                 "{32, 64, 128})", what, d->Cin, d->Cout, d->in_u8, d->traj_T);
+                 "{32, 64, 128}, and the pairs 16 -> 16 and 16 -> 32)", what, d->Cin, d->Cout, d->in_u8, d->traj_T);
         return SF_ERR_UNSUPPORTED;
     }
     return SF_OK;
@@ -399,6 +402,9 @@ extern "C" int sf_res_conv_fwd_bf16(const void *in, int64_t in_sample_stride, co
                    (!residual || aligned16(residual)),
                "sf_res_conv_fwd_bf16: in, w, out, out_act and residual must be 16-byte aligned");
     if (n == 0) return SF_OK;
+    if (sf_res_c16_pair(d.Cin, d.Cout))
+        return sf_res_c16_conv_launch(false, (const float *)in, in_sample_stride, offset, w, bias, residual, nullptr, out, out_act,
+                                      d.act_in, act_out, n, d.H, d.W, d.Cin, d.Cout, STREAM(stream));
     const RbTile t = rb_tile(d.H, d.W, d.Cin, n);
     const int64_t groups = ((n + t.S - 1) / t.S) * t.nrt * t.nct;
     SF_REQUIRE(groups <= 0x7fffffffLL, "sf_res_conv_fwd_bf16: %lld work-groups", (long long)groups);
@@ -417,6 +423,9 @@ extern "C" int sf_res_conv_dgrad_bf16(const float *dout, const float *w, const f
     SF_REQUIRE(n >= 0, "sf_res_conv_dgrad_bf16: n=%lld", (long long)n);
     SF_REQUIRE(aligned16(w) && aligned16(dout), "sf_res_conv_dgrad_bf16: w and dout must be 16-byte aligned");
     if (n == 0) return SF_OK;
+    if (sf_res_c16_pair(d.Cin, d.Cout))
+        return sf_res_c16_conv_launch(true, dout, (int64_t)d.H * d.W * d.Cout, 0, w, nullptr, pre, g_add, din, nullptr, d.act_in, 0,
+                                      n, d.H, d.W, d.Cout, d.Cin, STREAM(stream));
     const RbTile t = rb_tile(d.H, d.W, d.Cout, n);
     const int64_t groups = ((n + t.S - 1) / t.S) * t.nrt * t.nct;
     SF_REQUIRE(groups <= 0x7fffffffLL, "sf_res_conv_dgrad_bf16: %lld work-groups", (long long)groups);
@@ -426,9 +435,12 @@ extern "C" int sf_res_conv_dgrad_bf16(const float *dout, const float *w, const f
 }
 
 extern "C" int64_t sf_res_conv_wgrad_bf16_workspace(int64_t n, const sf_res_desc *h_desc) {
-    if (!h_desc || n < 0 || h_desc->in_u8 || h_desc->traj_T != 0 || !rb_width(h_desc->Cin) || !rb_width(h_desc->Cout) ||
+    if (!h_desc || n < 0 || h_desc->in_u8 || h_desc->traj_T != 0 || !rb_served(h_desc->Cin, h_desc->Cout) ||
         h_desc->H < 1 || h_desc->W < 1)
         return 0;
+    if (sf_res_c16_pair(h_desc->Cin, h_desc->Cout))
+        return sf_res_c16_wgrad_parts(h_desc->H, h_desc->W, h_desc->Cout, n) * (9LL * 16 * h_desc->Cout + h_desc->Cout) *
+               (int64_t)sizeof(float);
     RbBand t;
     if (!rb_band(h_desc->H, h_desc->W, h_desc->Cin, h_desc->Cout, n, &t)) return 0;
     return t.parts * (9LL * h_desc->Cin * h_desc->Cout + h_desc->Cout) * (int64_t)sizeof(float);
@@ -446,6 +458,16 @@ extern "C" int sf_res_conv_wgrad_bf16(const void *in, int64_t in_sample_stride, 
     SF_REQUIRE(in_sample_stride >= (int64_t)d.Cin * d.H * d.W && (in_sample_stride & 3) == 0,
                "sf_res_conv_wgrad_bf16: in_sample_stride %lld (at least Cin*H*W, a multiple of 4)", (long long)in_sample_stride);
     SF_REQUIRE(aligned16(in) && aligned16(dout), "sf_res_conv_wgrad_bf16: in and dout must be 16-byte aligned");
+    if (sf_res_c16_pair(d.Cin, d.Cout)) {
+        const int KC = 9 * d.Cin * d.Cout;
+        const int64_t parts = sf_res_c16_wgrad_parts(d.H, d.W, d.Cout, n), need = parts * (KC + d.Cout) * (int64_t)sizeof(float);
+        SF_REQUIRE(parts == 0 || (workspace && workspace_bytes >= need), "sf_res_conv_wgrad_bf16: workspace %lld bytes < %lld",
+                   (long long)workspace_bytes, (long long)need);
+        rc = sf_res_c16_wgrad_launch((const float *)in, in_sample_stride, offset, dout, static_cast<float *>(workspace), d.act_in,
+                                     n, d.H, d.W, d.Cout, STREAM(stream));  // parts == 0: refuses, the row does not fit
+        if (rc) return rc;
+        return sf_res_wgrad_sum_launch(static_cast<const float *>(workspace), (int)parts, KC, d.Cout, dw, db, STREAM(stream));
+    }
     RbBand t;
     if (!rb_band(d.H, d.W, d.Cin, d.Cout, n, &t)) {
         snprintf(sf_err_buf, sizeof(sf_err_buf), "sf_res_conv_wgrad_bf16: a row of W=%d pixels x (Cin=%d, Cout=%d) exceeds the "

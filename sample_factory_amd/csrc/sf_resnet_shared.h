@@ -6,6 +6,17 @@
 // stage 2 of both weight gradients (defined in sf_resnet.hip): partial sums part[parts][KC + Cout] added in part order
 int sf_res_wgrad_sum_launch(const float *part, int parts, int KC, int Cout, float *gw, float *gb, hipStream_t s);
 
+// the bf16 family's kernels for 16 -> 16 and 16 -> 32 layers (defined in sf_resnet_bf16_c16.hip), behind sf_res_conv_*_bf16.
+// conv_launch: Cr reduced, Cn produced channels; a1 / a2 = residual / unused (forward), pre / g_add (data gradient).
+// wgrad_parts: rows of the [parts][9*16*Cout + Cout] workspace the launch fills; 0: a row of W pixels does not fit the band.
+bool sf_res_c16_pair(int Cin, int Cout);
+int sf_res_c16_conv_launch(bool dgrad, const float *in, int64_t in_stride, int64_t in_offset, const float *w, const float *bias,
+                           const float *a1, const float *a2, float *out, float *out_act, int act, int act_out, int64_t n,
+                           int H, int W, int Cr, int Cn, hipStream_t s);
+int64_t sf_res_c16_wgrad_parts(int H, int W, int Cout, int64_t n);
+int sf_res_c16_wgrad_launch(const float *x, int64_t in_stride, int64_t in_offset, const float *gy, float *part, int act,
+                            int64_t n, int H, int W, int Cout, hipStream_t s);
+
 namespace {
 
 constexpr int RES_BLOCK = 256;

@@ -1678,7 +1678,8 @@ def res_conv_wgrad_mfma_workspace(n, desc: sf_res_desc) -> int:
 
 
 # the bf16 family (csrc/sf_resnet_bf16.hip; cfg.encoder_resnet_bf16), reached by name only: operands of the matrix product
-# rounded to bf16, fp32 accumulation and epilogue, f32 layers with Cin and Cout in {32, 64, 128}
+# rounded to bf16, fp32 accumulation and epilogue, f32 layers with Cin and Cout in {32, 64, 128} and the 16-channel pairs
+# 16 -> 16 and 16 -> 32 (csrc/sf_resnet_bf16_c16.hip); any other pair with a 16 is refused
 def res_conv_fwd_bf16(*a, **kw) -> None:
     res_conv_fwd(*a, sym="sf_res_conv_fwd_bf16", **kw)
 

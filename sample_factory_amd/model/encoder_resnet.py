@@ -41,9 +41,10 @@ class _Conv3:
         self.ref_w_shape = (cout, cin, 3, 3)
         self.desc = lib.sf_res_desc(Cin=cin, H=h, W=w, Cout=cout, in_u8=int(u8), act_in=act_in, traj_T=0,
                                     sub_mean=sub_mean, inv_scale=inv_scale)
-        # cfg.encoder_resnet_bf16: an f32 layer with 32, 64 or 128 channels on both sides runs EVERY pass on the bf16 family
-        # (csrc/sf_resnet_bf16.hip), so rollout, enjoy and training evaluate the same function; else the plain entry points
-        self.bf16 = bf16 and not u8 and cin in (32, 64, 128) and cout in (32, 64, 128)
+        # cfg.encoder_resnet_bf16: an f32 layer with 32, 64 or 128 channels on both sides, or a 16 -> 16 / 16 -> 32 one, runs
+        # EVERY pass on the bf16 family (csrc/sf_resnet_bf16.hip, sf_resnet_bf16_c16.hip), so rollout, enjoy and training
+        # evaluate the same function; else the plain entry points
+        self.bf16 = bf16 and not u8 and ((cin in (32, 64, 128) and cout in (32, 64, 128)) or (cin == 16 and cout in (16, 32)))
         if self.bf16:
             self.fwd, self.dgrad, self.wgrad = lib.res_conv_fwd_bf16, lib.res_conv_dgrad_bf16, lib.res_conv_wgrad_bf16
             self.wgrad_workspace = lib.res_conv_wgrad_bf16_workspace
@@ -124,7 +125,8 @@ class ResnetImpalaTower(NativeTower):
                 raise NotImplementedError(
                     f"resnet_impala tower with encoder_resnet_bf16: the bf16 weight gradient of a {c.Cin} -> {c.N} layer stages "
                     f"whole rows in a 64 KB LDS band, and a row of {c.W} pixels does not fit: this layer takes at most "
-                    f"{c.max_width()} pixels (96 at 32 -> 32, 152 at Cout = 64, 120 at Cout = 128)")
+                    f"{c.max_width()} pixels (200 at 16 -> 16, 184 at 16 -> 32, 96 at 32 -> 32, 152 at Cout = 64, 120 at "
+                    f"Cout = 128)")
             if not c.bf16 and lib.res_conv_wgrad_workspace(1, c.desc) == 0:
                 raise NotImplementedError(
                     f"resnet_impala tower at encoder_resnet_width={cfg.encoder_resnet_width}: the weight gradient of a "
