@@ -1100,6 +1100,32 @@ int sf_res_conv_wgrad_bf16(const void *in, int64_t in_sample_stride, const int32
                            float *dw, float *db, int64_t n, const sf_res_desc *h_desc, void *workspace,
                            int64_t workspace_bytes, void *stream);
 
+/* The inner conv layers of convnet_simple / convnet_atari on v_mfma_f32_16x16x32_bf16 (csrc/sf_conv_bf16.hip;
+ * cfg.encoder_conv_bf16): signatures and semantics of sf_conv_fwd / sf_conv_dgrad / sf_conv_wgrad on the same sf_conv_desc
+ * (activation desc->relu fused in the forward epilogue; sf_conv_dgrad_bf16: desc->relu names the activation whose derivative,
+ * through the stored in_act, multiplies the result; in_act = NULL with relu = 0 is the unmasked gradient), for dense f32
+ * NHWC layers without padding: in_u8 = 0, index = NULL, traj_T = 0, 16-byte aligned operands, KH = KW, (kernel, stride) in
+ * {(4, 2), (3, 1), (3, 2)}, Cin in {32, 64}, Cout in {32, 64, 128}, any image geometry whose row band fits LDS.  Both
+ * operands of the matrix product are rounded to bf16 (nearest even, once per element): conv(bf16(in), bf16(w)),
+ * conv_transpose(bf16(dout), bf16(w)), patches(bf16(in))^T bf16(dout), db = sum bf16(dout).  Accumulation, bias, activation
+ * and activation derivative are fp32 on unrounded values; every tensor in memory stays fp32 and w is the same
+ * [KH*KW*Cin, Cout] block, converted inside the launch.  The forward never splits the reduction (its workspace arguments are
+ * ignored): an output element does not depend on n or on its sample's position in the batch.  The weight gradient is
+ * deterministic (partials in sf_conv_wgrad_bf16_workspace(...) bytes, added in part order) and, unlike sf_conv_wgrad, is
+ * told the size of the workspace it was given.  Everything else is refused before any launch: SF_ERR_UNSUPPORTED from the
+ * entry points, 0 from the queries.  sf_conv_bf16_supported: op 0 forward, 1 weight gradient, 2 data gradient.  Reached by
+ * name only: the plain sf_conv_* entry points never route here. */
+int sf_conv_bf16_supported(int op, int64_t n, const sf_conv_desc *h_desc);
+int sf_conv_fwd_bf16(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *w,
+                     const float *bias, float *out, int64_t n, const sf_conv_desc *h_desc, void *workspace,
+                     int64_t workspace_bytes, void *stream);
+int sf_conv_dgrad_bf16(const float *dout, const float *w, const float *in_act, float *din, int64_t n,
+                       const sf_conv_desc *h_desc, void *stream);
+int64_t sf_conv_wgrad_bf16_workspace(int64_t n, const sf_conv_desc *h_desc);
+int sf_conv_wgrad_bf16(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *dout,
+                       float *dw, float *db, int64_t n, const sf_conv_desc *h_desc, void *workspace,
+                       int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,12 @@ ENGINE_FLAGS = [
     #                                          both gradients): operands rounded to bf16, fp32 accumulation, fp32 tensors
     #                                          and master weights (csrc/sf_resnet_bf16.hip, sf_resnet_bf16_c16.hip); off: every
     #                                          launch and result as before; with another architecture it is refused
+    ("encoder_conv_bf16", _bool, False),     # convnet_simple / convnet_atari only: every inner conv layer (f32 NHWC input: all
+    #                                          but the raw-frame one) runs on the bf16 matrix pipe in every pass (rollout,
+    #                                          bootstrap, enjoy, training forward, both gradients): operands rounded to bf16,
+    #                                          fp32 accumulation, fp32 tensors and master weights (csrc/sf_conv_bf16.hip,
+    #                                          DESIGN.md 3.24); reuse_rollout_activations resolves to off; off: every launch
+    #                                          and result as before; with another architecture it is refused
     ("augment_random_shift", int, 0),        # P > 0: every SGD step trains on its minibatch's frames shifted at random by up
     #                                          to P pixels (pad P with edge replication, crop back: RAD / DrQ), gathered on
     #                                          the device in one launch (sf_random_shift_gather); rollouts,
@@ -259,6 +265,24 @@ def resnet_bf16(cfg) -> bool:
     return on
 
 
+CONV_BF16_ARCHS = ("convnet_simple", "convnet_atari")
+
+
+def conv_bf16(cfg, env_info=None) -> bool:
+    """cfg.encoder_conv_bf16, checked: only with an image encoder of encoder_conv_architecture convnet_simple or
+    convnet_atari (ValueError; convnet_impala's 16 -> 32 layer has no kernel in the family).  env_info (optional): its
+    observation space must have an image key, else the encoder is an MLP and has no conv layer to serve"""
+    on = bool(getattr(cfg, "encoder_conv_bf16", False))
+    if on and cfg.encoder_conv_architecture not in CONV_BF16_ARCHS:
+        raise ValueError(f"encoder_conv_bf16=True needs encoder_conv_architecture in {CONV_BF16_ARCHS}, got "
+                         f"encoder_conv_architecture={cfg.encoder_conv_architecture}")
+    spaces_ = getattr(getattr(env_info, "obs_space", None), "spaces", None)
+    if on and spaces_ is not None and not any(len(getattr(s, "shape", None) or ()) == 3 for s in spaces_.values()):
+        raise ValueError("encoder_conv_bf16=True needs an image observation: this observation space gets an MLP encoder "
+                         f"(encoder_mlp_layers={cfg.encoder_mlp_layers}), encoder_conv_architecture is not used")
+    return on
+
+
 def resnet_stages(cfg):
     """((channels, residual blocks), ...) of the resnet_impala tower at cfg.encoder_resnet_width"""
     k = resnet_width(cfg)
@@ -270,6 +294,7 @@ def verify_cfg(cfg, env_info) -> bool:
     ok = True
     resnet_width(cfg)  # raises ValueError
     resnet_bf16(cfg)   # ... too
+    conv_bf16(cfg, env_info)  # ... too
 
     def err(msg):
         nonlocal ok

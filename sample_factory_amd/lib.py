@@ -80,6 +80,7 @@ SYMBOLS = [
     "sf_res_conv_wgrad", "sf_res_conv_fwd_norm", "sf_res_conv_wgrad_norm",
     "sf_res_conv_fwd_mfma", "sf_res_conv_dgrad_mfma", "sf_res_conv_wgrad_mfma_workspace", "sf_res_conv_wgrad_mfma",
     "sf_res_conv_fwd_bf16", "sf_res_conv_dgrad_bf16", "sf_res_conv_wgrad_bf16_workspace", "sf_res_conv_wgrad_bf16",
+    "sf_conv_bf16_supported", "sf_conv_fwd_bf16", "sf_conv_dgrad_bf16", "sf_conv_wgrad_bf16_workspace", "sf_conv_wgrad_bf16",
     "sf_pixcatch_state_words", "sf_pixcatch_reset", "sf_pixcatch_step", "sf_pixcatch_reset_levels",
     "sf_pixcatch_step_levels",
     "sf_random_shift_gather", "sf_augment_gather",
@@ -266,6 +267,7 @@ def load() -> C.CDLL:
         lib.sf_res_conv_wgrad_workspace.restype = C.c_int64
         lib.sf_res_conv_wgrad_mfma_workspace.restype = C.c_int64
         lib.sf_res_conv_wgrad_bf16_workspace.restype = C.c_int64
+        lib.sf_conv_wgrad_bf16_workspace.restype = C.c_int64
         _lib = lib
     return _lib
 
@@ -1400,6 +1402,35 @@ def conv_dgrad(dout, w, in_act, din, n, desc: sf_conv_desc) -> None:
     with _timed(_dkey("dgrad", n, desc)):
         _check(load().sf_conv_dgrad(ptr(dout, "f32", "dout"), ptr(w, "f32", "w"), ptr(in_act, "f32", "in_act"),
                                   ptr(din, "f32", "din"), i64(n), C.byref(desc), stream()), "sf_conv_dgrad")
+
+
+# the bf16 family of the inner conv layers (csrc/sf_conv_bf16.hip; cfg.encoder_conv_bf16), reached by name only: operands of
+# the matrix product rounded to bf16, fp32 accumulation and epilogue; dense f32 NHWC layers, no index, no slab addressing
+def conv_bf16_supported(op: str, n, desc: sf_conv_desc) -> bool:
+    """op: "fwd" | "wgrad" | "dgrad" """
+    return bool(load().sf_conv_bf16_supported(_OPS[op], i64(n), C.byref(desc)))
+
+
+def conv_fwd_bf16(inp, in_sample_stride, index, offset, w, bias, out, n, desc: sf_conv_desc) -> None:
+    _check(load().sf_conv_fwd_bf16(_raw_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"), i64(offset),
+                                   ptr(w, "f32", "w"), ptr(bias, "f32", "bias"), ptr(out, "f32", "out"), i64(n),
+                                   C.byref(desc), C.c_void_p(0), i64(0), stream()), "sf_conv_fwd_bf16")
+
+
+def conv_dgrad_bf16(dout, w, in_act, din, n, desc: sf_conv_desc) -> None:
+    _check(load().sf_conv_dgrad_bf16(ptr(dout, "f32", "dout"), ptr(w, "f32", "w"), ptr(in_act, "f32", "in_act"),
+                                     ptr(din, "f32", "din"), i64(n), C.byref(desc), stream()), "sf_conv_dgrad_bf16")
+
+
+def conv_wgrad_bf16_workspace(n, desc: sf_conv_desc) -> int:
+    return int(load().sf_conv_wgrad_bf16_workspace(i64(n), C.byref(desc)))
+
+
+def conv_wgrad_bf16(inp, in_sample_stride, index, offset, dout, dw, db, n, desc: sf_conv_desc, workspace) -> None:
+    _check(load().sf_conv_wgrad_bf16(_raw_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"), i64(offset),
+                                     ptr(dout, "f32", "dout"), ptr(dw, "f32", "dw"), ptr(db, "f32", "db"), i64(n),
+                                     C.byref(desc), ptr(workspace, "u8", "workspace"), i64(workspace.numel()), stream()),
+           "sf_conv_wgrad_bf16")
 
 
 def conv_fwd_t_supported(n, desc: sf_conv_desc) -> bool:

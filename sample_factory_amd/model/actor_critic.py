@@ -31,6 +31,7 @@ import torch
 from sample_factory_amd import lib
 from sample_factory_amd.algo.learning.rollout_reuse import SlotRecord, fc_reusable, keep_n, keep_rows, reuse_prefix, twin_name
 from sample_factory_amd.algo.utils.running_mean_std import RunningMeanStdInPlace
+from sample_factory_amd.cfg.arguments import conv_bf16
 from sample_factory_amd.envs.spaces import is_box, calc_num_action_parameters
 
 import os
@@ -81,6 +82,7 @@ class _Layer:
         self.role = role          # "chain" | "rnn_ih" (x projection, followed by the cell) | "rnn_hh" (side branch)
         self.in_act_kind = 0      # activation kind of the tensor feeding this layer (fused into its dgrad epilogue)
         self.rnn_l = 0            # index of the stacked recurrent layer a "rnn_ih" / "rnn_hh" projection belongs to
+        self.bf16 = False         # cfg.encoder_conv_bf16: every pass of this layer runs on the bf16 family (sf_conv_*_bf16)
         self.desc = desc
         self.kind = kind          # "conv_u8" | "conv_f32frame" | "conv" | "linear" | "linear_after_conv" | "heads"
         self.ref_w_shape = ref_w_shape
@@ -303,6 +305,17 @@ class ActorCritic(NativeTower):
                 self.layers.append(_Layer(f"{pfx}conv_head.{2 * i}", desc, (cout, cin, k, k),
                                           frame_kind if first else "conv"))
                 cin, h, w = cout, oh, ow
+            if conv_bf16(cfg):  # every inner conv layer (f32 NHWC input) on the bf16 family, in every pass
+                for i, L in enumerate(self.layers[1:], 1):
+                    d = L.desc
+                    for op in ("fwd", "dgrad", "wgrad"):
+                        if not lib.conv_bf16_supported(op, 1, d):
+                            raise NotImplementedError(
+                                f"encoder_conv_bf16: layer {L.name} ({d.Cin} -> {d.Cout}, {d.KH}x{d.KW} stride {d.stride}, "
+                                f"{d.H}x{d.W} input) is outside the bf16 family's {op} kernels: they take (kernel, stride) in "
+                                f"{{(4, 2), (3, 1), (3, 2)}}, Cin in {{32, 64}}, Cout in {{32, 64, 128}} and images of which "
+                                f"one row band fits 64 KiB of LDS as bf16")
+                    L.bf16 = True
             feat, chw = cin * h * w, (cin, h, w)
             for j, size in enumerate(cfg.encoder_conv_mlp_layers):
                 self.layers.append(_Layer(f"{pfx}mlp_layers.{2 * j}", _linear_desc(feat, size, act), (size, feat),
@@ -639,6 +652,9 @@ class ActorCritic(NativeTower):
             d = lib.sf_conv_desc.from_buffer_copy(L.desc)
             d.traj_T = int(traj_T)
         w, b, wt = self._wb(li, tag)
+        if L.bf16:  # never conv_fwd_t or the split-K path: the behaviour policy and the learner evaluate the same function
+            lib.conv_fwd_bf16(x, stride, index, offset, w, b, out, n, d)
+            return
         if wt is not None and index is None and not traj_T and lib.conv_fwd_t_supported(n, d):
             wsb = lib.conv_fwd_t_workspace(n, d)  # non-zero: wide layer, few rows -> split along K
             lib.conv_fwd_t(x, stride, wt, b, out, n, d, self._workspace(wsb) if wsb else None)  # LDS-DMA kernel
@@ -881,6 +897,8 @@ class ActorCritic(NativeTower):
         if (int(getattr(cfg, "augment_random_shift", 0) or 0) > 0 or getattr(cfg, "augment_cutout", None) or
                 int(getattr(cfg, "augment_intensity", 0) or 0) > 0):
             return 0  # every SGD step trains on augmented frames: the rollout's activations belong to the clean ones
+        if getattr(cfg, "encoder_conv_bf16", False):
+            return 0  # the bf16 family has no strided-output twins
         # the learner's dataset must be exactly ONE sampling round: with k rounds per dataset every round overwrites the same
         # kept rows and minibatch 0 comes from the first one — the guard could never hold, the strided launches and the
         # buffers would be pure cost
@@ -1179,16 +1197,18 @@ class ActorCritic(NativeTower):
                     lib.conv_wgrad_raw(x0, stride0, idx0, off0, g, L.gw, L.gb, n, d0, ws)
             else:
                 x = inputs[li]
-                ws = self._workspace(lib.conv_wgrad_workspace(n, d))
-                lib.conv_wgrad_raw(x, d.H * d.W * d.Cin, None, 0, g, L.gw, L.gb, n, d, ws)
+                wgrad_ws, wgrad, dgrad = (lib.conv_wgrad_bf16_workspace, lib.conv_wgrad_bf16, lib.conv_dgrad_bf16) if L.bf16 else \
+                    (lib.conv_wgrad_workspace, lib.conv_wgrad_raw, lib.conv_dgrad)
+                ws = self._workspace(wgrad_ws(n, d))
+                wgrad(x, d.H * d.W * d.Cin, None, 0, g, L.gw, L.gb, n, d, ws)
                 gin = self._buf(("g", li - 1), tuple(x.shape))
                 dd = lib.sf_conv_desc.from_buffer_copy(d)
                 dd.relu = L.in_act_kind  # derivative of the activation that produced x, fused into the epilogue
                 if pos == 1 and mask0 is not None:  # conv1's sign bits are applied by its weight-gradient kernel instead
                     dd.relu = 0
-                    lib.conv_dgrad(g, L.w, None, gin, n, dd)
+                    dgrad(g, L.w, None, gin, n, dd)
                 else:
-                    lib.conv_dgrad(g, L.w, x if L.in_act_kind else None, gin, n, dd)
+                    dgrad(g, L.w, x if L.in_act_kind else None, gin, n, dd)
                 g = gin
                 if L.role == "rnn_ih":  # back to sample-major for the encoder
                     R, Cn = self._rnn_saved["R"], self._rnn_saved["Cn"]
