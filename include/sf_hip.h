@@ -1126,6 +1126,28 @@ int sf_conv_wgrad_bf16(const void *in, int64_t in_sample_stride, const int32_t *
                        float *dw, float *db, int64_t n, const sf_conv_desc *h_desc, void *workspace,
                        int64_t workspace_bytes, void *stream);
 
+/* The fully connected layers on v_mfma_f32_16x16x32_bf16 (csrc/sf_linear_bf16.hip; cfg.mlp_bf16): dense f32 rows in [n, K],
+ * w [K, N], out / dout [n, N], all 16-byte aligned, with the arithmetic contract of sf_conv_*_bf16 above.  Both operands of
+ * each matrix product are rounded to bf16 (nearest even, once per element): out = act(bf16(in) bf16(w) + bias),
+ * din = (bf16(dout) bf16(w)^T) * act'(in_act) (act' through the stored tensor, kinds 0..3 as sf_conv_dgrad_bf16; in_act =
+ * NULL: unmasked), dw = bf16(in)^T bf16(dout), db = column sums of bf16(dout).  Accumulation, bias, activation and mask are
+ * fp32; every tensor in memory stays fp32.  The forward and the data gradient never split the reduction: a row's result
+ * does not depend on n or on the row's place in the launch.  The weight gradient is deterministic: the sample rows are cut
+ * into chunks of 64 and the chunks into contiguous parts (one part up to n = 64; sf_linear_wgrad_bf16_workspace(...) bytes =
+ * parts * (K*N + N) floats), added in part order; the entry point is told the workspace size and refuses a short one
+ * (SF_ERR_ARG).  Served: K % 8 == 0, N % 8 == 0, K >= 8, N >= 8, n >= 1; everything else is refused before any launch and
+ * before any pointer is looked at: SF_ERR_UNSUPPORTED from the entry points, 0 from the queries.  sf_linear_bf16_supported:
+ * op 0 forward, 1 weight gradient, 2 data gradient.  Reached by name only: sf_linear_*, sf_conv_* and sf_conv_kernel_name
+ * never route here. */
+int sf_linear_bf16_supported(int op, int64_t n, int K, int N);
+int sf_linear_fwd_bf16(const float *in, const float *w, const float *bias, float *out, int64_t n, int K, int N, int act,
+                       void *stream);
+int sf_linear_dgrad_bf16(const float *dout, const float *w, const float *in_act, float *din, int64_t n, int K, int N,
+                         int act, void *stream);
+int64_t sf_linear_wgrad_bf16_workspace(int64_t n, int K, int N);
+int sf_linear_wgrad_bf16(const float *in, const float *dout, float *dw, float *db, int64_t n, int K, int N,
+                         void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

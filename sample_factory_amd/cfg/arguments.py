@@ -119,7 +119,15 @@ ENGINE_FLAGS = [
     #                                          fp32 accumulation, fp32 tensors and master weights (csrc/sf_conv_bf16.hip,
     #                                          DESIGN.md 3.24); reuse_rollout_activations resolves to off; off: every launch
     #                                          and result as before; with another architecture it is refused
-    ("augment_random_shift", int, 0),        # P > 0: every SGD step trains on its minibatch's frames shifted at random by up
+    ("mlp_bf16", _bool, False),              # the fully connected layers that read another layer's output
+    #                                          (encoder_conv_mlp_layers, the second and later encoder_mlp_layers,
+    #                                          decoder_mlp_layers) run on the bf16 matrix pipe in every pass, same arithmetic
+    #                                          contract as encoder_conv_bf16 (csrc/sf_linear_bf16.hip).  The
+    #                                          layer that reads the observations, the recurrent projections and the heads
+    #                                          stay fp32; a flagged layer needs K % 8 == 0 and N % 8 == 0;
+    #                                          reuse_rollout_activations resolves to off; composes with encoder_conv_bf16;
+    #                                          refused with resnet_impala
+    ("augment_random_shift", int, 0),       # P > 0: every SGD step trains on its minibatch's frames shifted at random by up
     #                                          to P pixels (pad P with edge replication, crop back: RAD / DrQ), gathered on
     #                                          the device in one launch (sf_random_shift_gather); rollouts,
     #                                          bootstrap values and enjoy never augment; 0 = off, outside 0 .. 255 is refused
@@ -283,6 +291,19 @@ def conv_bf16(cfg, env_info=None) -> bool:
     return on
 
 
+def mlp_bf16(cfg, env_info=None) -> bool:
+    """cfg.mlp_bf16, checked: not with an image encoder of encoder_conv_architecture=resnet_impala (ValueError; that tower
+    launches its own fully connected layers, which have no bf16 path, and refuses the flag itself).  Checked against
+    env_info's observation space: without an image key the architecture is not used and the flag stands"""
+    on = bool(getattr(cfg, "mlp_bf16", False))
+    spaces_ = getattr(getattr(env_info, "obs_space", None), "spaces", None)
+    image = spaces_ is not None and any(len(getattr(s, "shape", None) or ()) == 3 for s in spaces_.values())
+    if on and image and cfg.encoder_conv_architecture == "resnet_impala":
+        raise ValueError("mlp_bf16=True is not served with encoder_conv_architecture=resnet_impala: the fully connected "
+                         "layers of that tower have no bf16 path")
+    return on
+
+
 def resnet_stages(cfg):
     """((channels, residual blocks), ...) of the resnet_impala tower at cfg.encoder_resnet_width"""
     k = resnet_width(cfg)
@@ -295,6 +316,7 @@ def verify_cfg(cfg, env_info) -> bool:
     resnet_width(cfg)  # raises ValueError
     resnet_bf16(cfg)   # ... too
     conv_bf16(cfg, env_info)  # ... too
+    mlp_bf16(cfg, env_info)   # ... too
 
     def err(msg):
         nonlocal ok

@@ -81,6 +81,8 @@ SYMBOLS = [
     "sf_res_conv_fwd_mfma", "sf_res_conv_dgrad_mfma", "sf_res_conv_wgrad_mfma_workspace", "sf_res_conv_wgrad_mfma",
     "sf_res_conv_fwd_bf16", "sf_res_conv_dgrad_bf16", "sf_res_conv_wgrad_bf16_workspace", "sf_res_conv_wgrad_bf16",
     "sf_conv_bf16_supported", "sf_conv_fwd_bf16", "sf_conv_dgrad_bf16", "sf_conv_wgrad_bf16_workspace", "sf_conv_wgrad_bf16",
+    "sf_linear_bf16_supported", "sf_linear_fwd_bf16", "sf_linear_dgrad_bf16", "sf_linear_wgrad_bf16_workspace",
+    "sf_linear_wgrad_bf16",
     "sf_pixcatch_state_words", "sf_pixcatch_reset", "sf_pixcatch_step", "sf_pixcatch_reset_levels",
     "sf_pixcatch_step_levels",
     "sf_random_shift_gather", "sf_augment_gather",
@@ -268,6 +270,7 @@ def load() -> C.CDLL:
         lib.sf_res_conv_wgrad_mfma_workspace.restype = C.c_int64
         lib.sf_res_conv_wgrad_bf16_workspace.restype = C.c_int64
         lib.sf_conv_wgrad_bf16_workspace.restype = C.c_int64
+        lib.sf_linear_wgrad_bf16_workspace.restype = C.c_int64
         _lib = lib
     return _lib
 
@@ -1431,6 +1434,35 @@ def conv_wgrad_bf16(inp, in_sample_stride, index, offset, dout, dw, db, n, desc:
                                      ptr(dout, "f32", "dout"), ptr(dw, "f32", "dw"), ptr(db, "f32", "db"), i64(n),
                                      C.byref(desc), ptr(workspace, "u8", "workspace"), i64(workspace.numel()), stream()),
            "sf_conv_wgrad_bf16")
+
+
+# the bf16 family of the fully connected layers (csrc/sf_linear_bf16.hip; cfg.mlp_bf16), reached by name only: dense rows
+# inp [n, K], w [K, N], out / dout [n, N]; K % 8 == 0 and N % 8 == 0; act: activation kind 0 .. 3
+def linear_bf16_supported(op: str, n, K, N) -> bool:
+    """op: "fwd" | "wgrad" | "dgrad" """
+    return bool(load().sf_linear_bf16_supported(_OPS[op], i64(n), int(K), int(N)))
+
+
+def linear_fwd_bf16(inp, w, bias, out, n, K, N, act) -> None:
+    _check(load().sf_linear_fwd_bf16(ptr(inp, "f32", "inp"), ptr(w, "f32", "w"), ptr(bias, "f32", "bias"),
+                                     ptr(out, "f32", "out"), i64(n), int(K), int(N), int(act), stream()), "sf_linear_fwd_bf16")
+
+
+def linear_dgrad_bf16(dout, w, in_act, din, n, K, N, act) -> None:
+    """in_act: the stored tensor whose activation derivative multiplies the result (None: unmasked)"""
+    _check(load().sf_linear_dgrad_bf16(ptr(dout, "f32", "dout"), ptr(w, "f32", "w"), ptr(in_act, "f32", "in_act"),
+                                       ptr(din, "f32", "din"), i64(n), int(K), int(N), int(act), stream()),
+           "sf_linear_dgrad_bf16")
+
+
+def linear_wgrad_bf16_workspace(n, K, N) -> int:
+    return int(load().sf_linear_wgrad_bf16_workspace(i64(n), int(K), int(N)))
+
+
+def linear_wgrad_bf16(inp, dout, dw, db, n, K, N, workspace) -> None:
+    _check(load().sf_linear_wgrad_bf16(ptr(inp, "f32", "inp"), ptr(dout, "f32", "dout"), ptr(dw, "f32", "dw"),
+                                       ptr(db, "f32", "db"), i64(n), int(K), int(N), ptr(workspace, "u8", "workspace"),
+                                       i64(workspace.numel()), stream()), "sf_linear_wgrad_bf16")
 
 
 def conv_fwd_t_supported(n, desc: sf_conv_desc) -> bool:

@@ -31,7 +31,7 @@ import torch
 from sample_factory_amd import lib
 from sample_factory_amd.algo.learning.rollout_reuse import SlotRecord, fc_reusable, keep_n, keep_rows, reuse_prefix, twin_name
 from sample_factory_amd.algo.utils.running_mean_std import RunningMeanStdInPlace
-from sample_factory_amd.cfg.arguments import conv_bf16
+from sample_factory_amd.cfg.arguments import conv_bf16, mlp_bf16
 from sample_factory_amd.envs.spaces import is_box, calc_num_action_parameters
 
 import os
@@ -82,7 +82,8 @@ class _Layer:
         self.role = role          # "chain" | "rnn_ih" (x projection, followed by the cell) | "rnn_hh" (side branch)
         self.in_act_kind = 0      # activation kind of the tensor feeding this layer (fused into its dgrad epilogue)
         self.rnn_l = 0            # index of the stacked recurrent layer a "rnn_ih" / "rnn_hh" projection belongs to
-        self.bf16 = False         # cfg.encoder_conv_bf16: every pass of this layer runs on the bf16 family (sf_conv_*_bf16)
+        self.bf16 = False         # cfg.encoder_conv_bf16 (a conv layer) / cfg.mlp_bf16 (a fully connected one): every pass
+        #                           of this layer runs on the bf16 family (sf_conv_*_bf16 / sf_linear_*_bf16)
         self.desc = desc
         self.kind = kind          # "conv_u8" | "conv_f32frame" | "conv" | "linear" | "linear_after_conv" | "heads"
         self.ref_w_shape = ref_w_shape
@@ -378,8 +379,21 @@ class ActorCritic(NativeTower):
             L.in_act_kind = prev_kind
             prev_kind = 0 if L.role == "rnn_ih" else L.desc.relu
         self.obs_elems = int(np.prod(self.obs_shape))
-        # vector observations through a two-layer MLP encoder: the rollout can take the fused inference kernel
-        self._mlp2_ok = (len(self.obs_shape) == 1 and len(self.layers) >= (2 if self.headless else 3) and not self.features_in and
+        if mlp_bf16(cfg):
+            # every fully connected chain layer that reads another layer's output (a trunk's features included) on the bf16
+            # family, in every pass.  The layer that reads the observations keeps fp32 (unnormalised values must not lose
+            # their mantissa, and it owns the index / normaliser loaders); so do the recurrent projections and the heads
+            for li, L in enumerate(self.layers):
+                if L.role != "chain" or L.kind not in ("linear", "linear_after_conv") or (li == 0 and not self.features_in):
+                    continue
+                for op in ("fwd", "dgrad", "wgrad"):
+                    if not lib.linear_bf16_supported(op, 1, L.K, L.N):
+                        raise NotImplementedError(f"mlp_bf16: layer {L.name} ({L.K} -> {L.N}) is outside the bf16 family's "
+                                                  f"{op} kernels: they take K % 8 == 0 and N % 8 == 0 (K, N >= 8)")
+                L.bf16 = True
+        # vector observations through a two-layer MLP encoder: the rollout can take the fused inference kernel (not under
+        # mlp_bf16: the fused fp32 kernel would make the rollout differ from training)
+        self._mlp2_ok = (len(self.obs_shape) == 1 and not getattr(cfg, "mlp_bf16", False) and len(self.layers) >= (2 if self.headless else 3) and not self.features_in and
                          all(L.kind == "linear" and L.role == "chain" and L.desc.relu == act for L in self.layers[:2]) and
                          len(cfg.encoder_mlp_layers) == 2 and
                          lib.mlp2_supported(self.obs_shape[0], self.layers[0].N, self.layers[1].N))
@@ -653,7 +667,11 @@ class ActorCritic(NativeTower):
             d.traj_T = int(traj_T)
         w, b, wt = self._wb(li, tag)
         if L.bf16:  # never conv_fwd_t or the split-K path: the behaviour policy and the learner evaluate the same function
-            lib.conv_fwd_bf16(x, stride, index, offset, w, b, out, n, d)
+            if L.kind == "conv":
+                lib.conv_fwd_bf16(x, stride, index, offset, w, b, out, n, d)
+            else:  # cfg.mlp_bf16: a layer behind another layer reads dense rows
+                assert index is None and not offset and not traj_T and stride == L.K, (L.name, stride, L.K)
+                lib.linear_fwd_bf16(x, w, b, out, n, L.K, L.N, d.relu)
             return
         if wt is not None and index is None and not traj_T and lib.conv_fwd_t_supported(n, d):
             wsb = lib.conv_fwd_t_workspace(n, d)  # non-zero: wide layer, few rows -> split along K
@@ -897,8 +915,8 @@ class ActorCritic(NativeTower):
         if (int(getattr(cfg, "augment_random_shift", 0) or 0) > 0 or getattr(cfg, "augment_cutout", None) or
                 int(getattr(cfg, "augment_intensity", 0) or 0) > 0):
             return 0  # every SGD step trains on augmented frames: the rollout's activations belong to the clean ones
-        if getattr(cfg, "encoder_conv_bf16", False):
-            return 0  # the bf16 family has no strided-output twins
+        if getattr(cfg, "encoder_conv_bf16", False) or getattr(cfg, "mlp_bf16", False):
+            return 0  # the bf16 families have no strided-output twins
         # the learner's dataset must be exactly ONE sampling round: with k rounds per dataset every round overwrites the same
         # kept rows and minibatch 0 comes from the first one — the guard could never hold, the strided launches and the
         # buffers would be pure cost
@@ -1199,6 +1217,11 @@ class ActorCritic(NativeTower):
                 x = inputs[li]
                 wgrad_ws, wgrad, dgrad = (lib.conv_wgrad_bf16_workspace, lib.conv_wgrad_bf16, lib.conv_dgrad_bf16) if L.bf16 else \
                     (lib.conv_wgrad_workspace, lib.conv_wgrad_raw, lib.conv_dgrad)
+                if L.bf16 and L.kind != "conv":  # cfg.mlp_bf16: a fully connected layer, dense rows [n, K] and [n, N]
+                    K_, N_ = L.K, L.N
+                    wgrad_ws = lambda n_, d_: lib.linear_wgrad_bf16_workspace(n_, K_, N_)  # noqa: E731
+                    wgrad = lambda x_, s_, i_, o_, g_, gw_, gb_, n_, d_, ws_: lib.linear_wgrad_bf16(x_, g_, gw_, gb_, n_, K_, N_, ws_)  # noqa: E731
+                    dgrad = lambda g_, w_, a_, gin_, n_, dd_: lib.linear_dgrad_bf16(g_, w_, a_, gin_, n_, K_, N_, dd_.relu)  # noqa: E731
                 ws = self._workspace(wgrad_ws(n, d))
                 wgrad(x, d.H * d.W * d.Cin, None, 0, g, L.gw, L.gb, n, d, ws)
                 gin = self._buf(("g", li - 1), tuple(x.shape))

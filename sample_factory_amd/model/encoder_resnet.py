@@ -85,6 +85,8 @@ class ResnetImpalaTower(NativeTower):
         C, H, W = self.obs_shape
         if C > 32:
             raise NotImplementedError(f"resnet_impala tower: at most 32 input channels, got {C}")
+        if getattr(cfg, "mlp_bf16", False):  # this tower launches its own fc layers: the flag would be served by half
+            raise NotImplementedError("mlp_bf16 with the resnet_impala tower: its fully connected layers have no bf16 path")
         self.obs_elems = int(np.prod(self.obs_shape))
         self.training = True
         act = self.act_kind = ACT_KIND[cfg.nonlinearity]
