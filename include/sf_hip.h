@@ -1126,6 +1126,31 @@ int sf_conv_wgrad_bf16(const void *in, int64_t in_sample_stride, const int32_t *
                        float *dw, float *db, int64_t n, const sf_conv_desc *h_desc, void *workspace,
                        int64_t workspace_bytes, void *stream);
 
+/* The raw-frame conv layer on v_mfma_f32_16x16x32_bf16 (csrc/sf_conv1_bf16.hip; cfg.encoder_conv1_bf16): the forward and
+ * the weight / bias gradient of sf_conv_fwd_norm / sf_conv_wgrad_norm on the same sf_conv_desc, for u8 or f32 NCHW frames
+ * (in_u8 = 1 or 2), KH = KW = 8, stride 4, Cin 1 .. 16, Cout in {16, 32}, any H, W >= 8 whose one-row band fits LDS
+ * ("image too wide" otherwise), n >= 1.  Sample addressing (index | offset, traj_T, any sample stride) and weight order
+ * (k = (c*KH + kh)*KW + kw) as sf_conv_fwd_norm.  mu / rstd: both NULL (the input value is (float(px) - sub_mean) *
+ * inv_scale) or both set (x' = clamp(((float(px) - sub_mean) * inv_scale - mu[d]) * rstd[d], +-5)); evaluated in that
+ * order, every operation rounded to fp32, then x' is rounded once to bf16 (nearest even).  bf16(w) and bf16(dout) are
+ * rounded once; accumulation, bias and activation are fp32; db = sum bf16(dout); dout arrives already masked by the
+ * activation derivative.  u8 frames at any byte alignment, f32 frames and tables 4-byte aligned, out / dout / workspace
+ * 16-byte aligned; vector loads where W % 4 == 0, the frames and their sample stride are 4-byte (u8) / 16-byte (f32)
+ * aligned and the tables 16-byte aligned, scalar loads otherwise: both loaders produce the same value.  A forward
+ * element depends on neither n nor its sample's position in the batch; the weight gradient adds ordered partials
+ * (sf_conv1_wgrad_bf16_workspace(...) bytes; a smaller workspace is refused) without float atomics.  Everything else is
+ * refused before any launch and before any pointer is looked at: SF_ERR_UNSUPPORTED from the entry points, 0 from the
+ * queries; n == 0 is SF_OK without a launch.  sf_conv1_bf16_supported: op 0 forward, 1 weight gradient.  Reached by name
+ * only: the plain sf_conv_* entry points and sf_conv_kernel_name never route here. */
+int sf_conv1_bf16_supported(int op, int64_t n, const sf_conv_desc *h_desc);
+int sf_conv1_fwd_bf16(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *mu,
+                      const float *rstd, const float *w, const float *bias, float *out, int64_t n,
+                      const sf_conv_desc *h_desc, void *stream);
+int64_t sf_conv1_wgrad_bf16_workspace(int64_t n, const sf_conv_desc *h_desc);
+int sf_conv1_wgrad_bf16(const void *in, int64_t in_sample_stride, const int32_t *index, int64_t offset, const float *mu,
+                        const float *rstd, const float *dout, float *dw, float *db, int64_t n, const sf_conv_desc *h_desc,
+                        void *workspace, int64_t workspace_bytes, void *stream);
+
 /* The fully connected layers on v_mfma_f32_16x16x32_bf16 (csrc/sf_linear_bf16.hip; cfg.mlp_bf16): dense f32 rows in [n, K],
  * w [K, N], out / dout [n, N], all 16-byte aligned, with the arithmetic contract of sf_conv_*_bf16 above.  Both operands of
  * each matrix product are rounded to bf16 (nearest even, once per element): out = act(bf16(in) bf16(w) + bias),

@@ -34,7 +34,7 @@ import torch
 from sample_factory_amd import lib
 from sample_factory_amd.algo.learning.dp import ReplicaGroup
 from sample_factory_amd.algo.utils.tensor_dict import TensorDict
-from sample_factory_amd.cfg.arguments import augment_consistency_coeff, augment_ops, conv_bf16, mlp_bf16, resnet_bf16
+from sample_factory_amd.cfg.arguments import augment_consistency_coeff, augment_ops, conv1_bf16, conv_bf16, mlp_bf16, resnet_bf16
 from sample_factory_amd.envs.frame_ops import augment_op_of_step, random_shift_seed
 from sample_factory_amd.envs.spaces import (action_head_sizes, calc_num_action_parameters, calc_num_actions, is_box,
                                              is_discrete)
@@ -210,6 +210,12 @@ class Learner:
                 raise NotImplementedError("encoder_conv_bf16 with a network that runs in torch (a user-registered model or a "
                                           "configuration the native kernels do not take): only the native convnet_simple / "
                                           "convnet_atari tower has the bf16 convs")
+        if conv1_bf16(cfg):  # ... and encoder_conv1_bf16, for the raw-frame layer of the native conv towers
+            from sample_factory_amd.model.torch_policy import TorchPolicyAdapter
+            if isinstance(self.actor_critic, TorchPolicyAdapter):
+                raise NotImplementedError("encoder_conv1_bf16 with a network that runs in torch (a user-registered model or a "
+                                          "configuration the native kernels do not take): only the native convnet_simple / "
+                                          "convnet_atari / convnet_impala tower has the bf16 raw-frame layer")
         if mlp_bf16(cfg):  # ... and mlp_bf16, for the fully connected layers of the native towers
             from sample_factory_amd.model.torch_policy import TorchPolicyAdapter
             if isinstance(self.actor_critic, TorchPolicyAdapter):

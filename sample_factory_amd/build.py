@@ -21,6 +21,7 @@ SOURCES = [
     ("sf_resnet_bf16.hip", ["-ffp-contract=off"]),  # ... and on bf16 MFMA (cfg.encoder_resnet_bf16): the same flags
     ("sf_resnet_bf16_c16.hip", ["-ffp-contract=off"]),  # ... its kernels for the 16-channel layers of the width-1 tower
     ("sf_conv_bf16.hip", ["-ffp-contract=off"]),  # convnet_simple / convnet_atari inner convs on bf16 MFMA (cfg.encoder_conv_bf16)
+    ("sf_conv1_bf16.hip", ["-ffp-contract=off"]),  # ... and their raw-frame layer, convnet_impala's too (cfg.encoder_conv1_bf16)
     ("sf_linear_bf16.hip", ["-ffp-contract=off"]),  # the fully connected layers on bf16 MFMA (cfg.mlp_bf16)
     ("sf_ingest.hip", []),             # observation ingest: the device frame stack, the HWC transpose, resize / grey-scale
     ("sf_pixcatch.hip", []),                # PixelCatch: the device-resident pixel game (step + render in one launch)

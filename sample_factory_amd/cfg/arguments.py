@@ -127,6 +127,14 @@ ENGINE_FLAGS = [
     #                                          stay fp32; a flagged layer needs K % 8 == 0 and N % 8 == 0;
     #                                          reuse_rollout_activations resolves to off; composes with encoder_conv_bf16;
     #                                          refused with resnet_impala
+    ("encoder_conv1_bf16", _bool, False),    # convnet_simple / convnet_atari / convnet_impala: the raw-frame layer (u8 or f32
+    #                                          frames, with or without the observation normaliser's tables) runs its forward
+    #                                          in every pass and its weight / bias gradient on the bf16 matrix pipe: the
+    #                                          normalised pixel rounded once to bf16, same arithmetic contract as
+    #                                          encoder_conv_bf16 (csrc/sf_conv1_bf16.hip);
+    #                                          reuse_rollout_activations resolves to off; independent of encoder_conv_bf16 and
+    #                                          mlp_bf16 and composes with both; refused with resnet_impala, without an image
+    #                                          observation, and with normalize_input=True under SF_CONV1_NORM=0
     ("augment_random_shift", int, 0),       # P > 0: every SGD step trains on its minibatch's frames shifted at random by up
     #                                          to P pixels (pad P with edge replication, crop back: RAD / DrQ), gathered on
     #                                          the device in one launch (sf_random_shift_gather); rollouts,
@@ -291,6 +299,24 @@ def conv_bf16(cfg, env_info=None) -> bool:
     return on
 
 
+def conv1_bf16(cfg, env_info=None) -> bool:
+    """cfg.encoder_conv1_bf16, checked (ValueError): not with encoder_conv_architecture=resnet_impala (that tower launches
+    its own first layer), not with normalize_input=True under SF_CONV1_NORM=0 (the first layer then reads a materialised
+    NHWC batch and is no raw-frame layer), and, given env_info, only with an image key in its observation space"""
+    on = bool(getattr(cfg, "encoder_conv1_bf16", False))
+    if on and cfg.encoder_conv_architecture == "resnet_impala":
+        raise ValueError("encoder_conv1_bf16=True is not served with encoder_conv_architecture=resnet_impala: that tower "
+                         "launches its own first layer")
+    if on and getattr(cfg, "normalize_input", False) and os.environ.get("SF_CONV1_NORM", "1") == "0":
+        raise ValueError("encoder_conv1_bf16=True with normalize_input=True needs the normaliser fused into the first layer: "
+                         "under SF_CONV1_NORM=0 that layer reads a materialised f32 batch and is no raw-frame layer")
+    spaces_ = getattr(getattr(env_info, "obs_space", None), "spaces", None)
+    if on and spaces_ is not None and not any(len(getattr(s, "shape", None) or ()) == 3 for s in spaces_.values()):
+        raise ValueError("encoder_conv1_bf16=True needs an image observation: this observation space gets an MLP encoder "
+                         f"(encoder_mlp_layers={cfg.encoder_mlp_layers}), encoder_conv_architecture is not used")
+    return on
+
+
 def mlp_bf16(cfg, env_info=None) -> bool:
     """cfg.mlp_bf16, checked: not with an image encoder of encoder_conv_architecture=resnet_impala (ValueError; that tower
     launches its own fully connected layers, which have no bf16 path, and refuses the flag itself).  Checked against
@@ -316,6 +342,7 @@ def verify_cfg(cfg, env_info) -> bool:
     resnet_width(cfg)  # raises ValueError
     resnet_bf16(cfg)   # ... too
     conv_bf16(cfg, env_info)  # ... too
+    conv1_bf16(cfg, env_info)  # ... too
     mlp_bf16(cfg, env_info)   # ... too
 
     def err(msg):

@@ -81,6 +81,7 @@ SYMBOLS = [
     "sf_res_conv_fwd_mfma", "sf_res_conv_dgrad_mfma", "sf_res_conv_wgrad_mfma_workspace", "sf_res_conv_wgrad_mfma",
     "sf_res_conv_fwd_bf16", "sf_res_conv_dgrad_bf16", "sf_res_conv_wgrad_bf16_workspace", "sf_res_conv_wgrad_bf16",
     "sf_conv_bf16_supported", "sf_conv_fwd_bf16", "sf_conv_dgrad_bf16", "sf_conv_wgrad_bf16_workspace", "sf_conv_wgrad_bf16",
+    "sf_conv1_bf16_supported", "sf_conv1_fwd_bf16", "sf_conv1_wgrad_bf16_workspace", "sf_conv1_wgrad_bf16",
     "sf_linear_bf16_supported", "sf_linear_fwd_bf16", "sf_linear_dgrad_bf16", "sf_linear_wgrad_bf16_workspace",
     "sf_linear_wgrad_bf16",
     "sf_pixcatch_state_words", "sf_pixcatch_reset", "sf_pixcatch_step", "sf_pixcatch_reset_levels",
@@ -270,6 +271,7 @@ def load() -> C.CDLL:
         lib.sf_res_conv_wgrad_mfma_workspace.restype = C.c_int64
         lib.sf_res_conv_wgrad_bf16_workspace.restype = C.c_int64
         lib.sf_conv_wgrad_bf16_workspace.restype = C.c_int64
+        lib.sf_conv1_wgrad_bf16_workspace.restype = C.c_int64
         lib.sf_linear_wgrad_bf16_workspace.restype = C.c_int64
         _lib = lib
     return _lib
@@ -1434,6 +1436,33 @@ def conv_wgrad_bf16(inp, in_sample_stride, index, offset, dout, dw, db, n, desc:
                                      ptr(dout, "f32", "dout"), ptr(dw, "f32", "dw"), ptr(db, "f32", "db"), i64(n),
                                      C.byref(desc), ptr(workspace, "u8", "workspace"), i64(workspace.numel()), stream()),
            "sf_conv_wgrad_bf16")
+
+
+# the bf16 family of the raw-frame conv layer (csrc/sf_conv1_bf16.hip; cfg.encoder_conv1_bf16), reached by name only: u8 / f32
+# NCHW frames read in place (index | offset, traj_T, any sample stride), 8x8 stride 4, Cin <= 16, Cout 16 or 32; mu / rstd:
+# the observation normaliser's tables, or both None
+def conv1_bf16_supported(op: str, n, desc: sf_conv_desc) -> bool:
+    """op: "fwd" | "wgrad" """
+    return bool(load().sf_conv1_bf16_supported(_OPS[op], i64(n), C.byref(desc)))
+
+
+def conv1_fwd_bf16(inp, in_sample_stride, index, offset, mu, rstd, w, bias, out, n, desc: sf_conv_desc) -> None:
+    _check(load().sf_conv1_fwd_bf16(_raw_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"), i64(offset),
+                                    ptr(mu, "f32", "mu"), ptr(rstd, "f32", "rstd"), ptr(w, "f32", "w"),
+                                    ptr(bias, "f32", "bias"), ptr(out, "f32", "out"), i64(n), C.byref(desc), stream()),
+           "sf_conv1_fwd_bf16")
+
+
+def conv1_wgrad_bf16_workspace(n, desc: sf_conv_desc) -> int:
+    return int(load().sf_conv1_wgrad_bf16_workspace(i64(n), C.byref(desc)))
+
+
+def conv1_wgrad_bf16(inp, in_sample_stride, index, offset, mu, rstd, dout, dw, db, n, desc: sf_conv_desc, workspace) -> None:
+    _check(load().sf_conv1_wgrad_bf16(_raw_in(inp, desc), i64(in_sample_stride), ptr(index, "i32", "index"), i64(offset),
+                                      ptr(mu, "f32", "mu"), ptr(rstd, "f32", "rstd"), ptr(dout, "f32", "dout"),
+                                      ptr(dw, "f32", "dw"), ptr(db, "f32", "db"), i64(n), C.byref(desc),
+                                      ptr(workspace, "u8", "workspace"), i64(workspace.numel()), stream()),
+           "sf_conv1_wgrad_bf16")
 
 
 # the bf16 family of the fully connected layers (csrc/sf_linear_bf16.hip; cfg.mlp_bf16), reached by name only: dense rows

@@ -31,7 +31,7 @@ import torch
 from sample_factory_amd import lib
 from sample_factory_amd.algo.learning.rollout_reuse import SlotRecord, fc_reusable, keep_n, keep_rows, reuse_prefix, twin_name
 from sample_factory_amd.algo.utils.running_mean_std import RunningMeanStdInPlace
-from sample_factory_amd.cfg.arguments import conv_bf16, mlp_bf16
+from sample_factory_amd.cfg.arguments import conv1_bf16, conv_bf16, mlp_bf16
 from sample_factory_amd.envs.spaces import is_box, calc_num_action_parameters
 
 import os
@@ -317,6 +317,19 @@ class ActorCritic(NativeTower):
                                 f"{{(4, 2), (3, 1), (3, 2)}}, Cin in {{32, 64}}, Cout in {{32, 64, 128}} and images of which "
                                 f"one row band fits 64 KiB of LDS as bf16")
                     L.bf16 = True
+            if conv1_bf16(cfg):  # the raw-frame layer on the bf16 family (sf_conv1_*_bf16), in every pass
+                L = self.layers[0]
+                d = L.desc
+                if L.kind not in FRAME_KINDS:
+                    raise NotImplementedError(f"encoder_conv1_bf16: layer {L.name} reads a materialised normalised f32 batch "
+                                              f"(SF_CONV1_NORM=0), not the raw frames")
+                for op in ("fwd", "wgrad"):
+                    if not lib.conv1_bf16_supported(op, 1, d):
+                        raise NotImplementedError(
+                            f"encoder_conv1_bf16: layer {L.name} ({d.Cin} -> {d.Cout}, {d.KH}x{d.KW} stride {d.stride}, "
+                            f"{d.H}x{d.W} frames) is outside the raw-frame bf16 family's {op} kernel: it takes 8x8 stride 4, "
+                            f"Cin <= 16, Cout in {{16, 32}} and frames of which one output row's band fits LDS")
+                L.bf16 = True
             feat, chw = cin * h * w, (cin, h, w)
             for j, size in enumerate(cfg.encoder_conv_mlp_layers):
                 self.layers.append(_Layer(f"{pfx}mlp_layers.{2 * j}", _linear_desc(feat, size, act), (size, feat),
@@ -797,7 +810,7 @@ class ActorCritic(NativeTower):
             inputs[li] = x
             out = self._buf((tag, li), (n * L.out_pixels, L.N))
             mask = None
-            if tag == "train" and li == 0 and norm_tabs is None and li + 1 < len(self.layers) and self.layers[1].role == "chain":
+            if tag == "train" and li == 0 and norm_tabs is None and not L.bf16 and li + 1 < len(self.layers) and self.layers[1].role == "chain":
                 d0 = L.desc
                 if tT:
                     d0 = lib.sf_conv_desc.from_buffer_copy(L.desc)
@@ -821,7 +834,17 @@ class ActorCritic(NativeTower):
                 # projection was a launch of its own that is all fill and drain (GRU: the candidate gate's parts stay apart)
                 fuse_dual = (self._wb(li, tag)[2] is not None and self._wb(li + 1, tag)[2] is not None and
                              self.rnn_H % 64 == 0 and lib.linear_fwd_dual_supported(n, 4 * self.rnn_H, L.K, self.rnn_H))
-            if li == 0 and norm_tabs is not None:
+            if li == 0 and L.bf16 and L.kind in FRAME_KINDS:
+                # cfg.encoder_conv1_bf16: the same kernel in rollout, bootstrap and training forward, with the tables or
+                # without; no sign-bit twin, conv2's data gradient reads the activation
+                w_, b_, _ = self._wb(li, tag)
+                dn = L.desc
+                if tT:
+                    dn = lib.sf_conv_desc.from_buffer_copy(L.desc)
+                    dn.traj_T = int(tT)
+                mu_, rstd_ = norm_tabs if norm_tabs is not None else (None, None)
+                lib.conv1_fwd_bf16(x, stride, idx, off, mu_, rstd_, w_, b_, out, n, dn)
+            elif li == 0 and norm_tabs is not None:
                 w_, b_, _ = self._wb(li, tag)
                 dn = L.desc
                 if tT:
@@ -915,7 +938,8 @@ class ActorCritic(NativeTower):
         if (int(getattr(cfg, "augment_random_shift", 0) or 0) > 0 or getattr(cfg, "augment_cutout", None) or
                 int(getattr(cfg, "augment_intensity", 0) or 0) > 0):
             return 0  # every SGD step trains on augmented frames: the rollout's activations belong to the clean ones
-        if getattr(cfg, "encoder_conv_bf16", False) or getattr(cfg, "mlp_bf16", False):
+        if (getattr(cfg, "encoder_conv_bf16", False) or getattr(cfg, "mlp_bf16", False) or
+                getattr(cfg, "encoder_conv1_bf16", False)):
             return 0  # the bf16 families have no strided-output twins
         # the learner's dataset must be exactly ONE sampling round: with k rounds per dataset every round overwrites the same
         # kept rows and minibatch 0 comes from the first one — the guard could never hold, the strided launches and the
@@ -1205,8 +1229,12 @@ class ActorCritic(NativeTower):
             if pos == 0 and not self.features_in:
                 d0 = lib.sf_conv_desc.from_buffer_copy(d)
                 d0.traj_T = int(tT0)
-                ws = self._workspace(lib.conv_wgrad_workspace(n, d0))
-                if ctx.get("norm_tabs") is not None:  # the forward normalised in conv1's loader: so does the gradient
+                bf16_0 = L.bf16 and L.kind in FRAME_KINDS
+                ws = self._workspace((lib.conv1_wgrad_bf16_workspace if bf16_0 else lib.conv_wgrad_workspace)(n, d0))
+                if bf16_0:  # cfg.encoder_conv1_bf16: g is already masked (conv2's data gradient read the activation)
+                    mu_, rstd_ = ctx.get("norm_tabs") or (None, None)
+                    lib.conv1_wgrad_bf16(x0, stride0, idx0, off0, mu_, rstd_, g, L.gw, L.gb, n, d0, ws)
+                elif ctx.get("norm_tabs") is not None:  # the forward normalised in conv1's loader: so does the gradient
                     mu_, rstd_ = ctx["norm_tabs"]
                     lib.conv_wgrad_norm(x0, stride0, idx0, off0, mu_, rstd_, g, L.gw, L.gb, n, d0, ws)
                 elif mask0 is not None:  # g is the gradient wrt conv1's ReLU output, unmasked: the kernel applies the bits
