@@ -34,7 +34,7 @@ import torch
 from sample_factory_amd import lib
 from sample_factory_amd.algo.learning.dp import ReplicaGroup
 from sample_factory_amd.algo.utils.tensor_dict import TensorDict
-from sample_factory_amd.cfg.arguments import augment_consistency_coeff, augment_ops, conv1_bf16, conv_bf16, mlp_bf16, resnet_bf16
+from sample_factory_amd.cfg.arguments import BF16_FLAGS, augment_consistency_coeff, augment_ops
 from sample_factory_amd.envs.frame_ops import augment_op_of_step, random_shift_seed
 from sample_factory_amd.envs.spaces import (action_head_sizes, calc_num_action_parameters, calc_num_actions, is_box,
                                              is_discrete)
@@ -198,30 +198,12 @@ class Learner:
         self.actor_critic = create_actor_critic(cfg, self.env_info.obs_space, self.env_info.action_space, self.device,
                                                 all_reduce=ar)
         self.actor_critic.train()
-        if resnet_bf16(cfg):  # the flag names kernels of the native tower: a torch network would silently train in fp32
-            from sample_factory_amd.model.torch_policy import TorchPolicyAdapter
-            if isinstance(self.actor_critic, TorchPolicyAdapter):
-                raise NotImplementedError("encoder_resnet_bf16 with a network that runs in torch (SF_NATIVE_RESNET=0, a "
-                                          "user-registered model or a configuration the native kernels do not take): only "
-                                          "the native resnet_impala tower has the bf16 convs")
-        if conv_bf16(cfg):  # ... and so does encoder_conv_bf16, for the native convnet_simple / convnet_atari tower
-            from sample_factory_amd.model.torch_policy import TorchPolicyAdapter
-            if isinstance(self.actor_critic, TorchPolicyAdapter):
-                raise NotImplementedError("encoder_conv_bf16 with a network that runs in torch (a user-registered model or a "
-                                          "configuration the native kernels do not take): only the native convnet_simple / "
-                                          "convnet_atari tower has the bf16 convs")
-        if conv1_bf16(cfg):  # ... and encoder_conv1_bf16, for the raw-frame layer of the native conv towers
-            from sample_factory_amd.model.torch_policy import TorchPolicyAdapter
-            if isinstance(self.actor_critic, TorchPolicyAdapter):
-                raise NotImplementedError("encoder_conv1_bf16 with a network that runs in torch (a user-registered model or a "
-                                          "configuration the native kernels do not take): only the native convnet_simple / "
-                                          "convnet_atari / convnet_impala tower has the bf16 raw-frame layer")
-        if mlp_bf16(cfg):  # ... and mlp_bf16, for the fully connected layers of the native towers
-            from sample_factory_amd.model.torch_policy import TorchPolicyAdapter
-            if isinstance(self.actor_critic, TorchPolicyAdapter):
-                raise NotImplementedError("mlp_bf16 with a network that runs in torch (a user-registered model or a "
-                                          "configuration the native kernels do not take): only the native towers have the "
-                                          "bf16 fully connected layers")
+        for check, flag, tower in BF16_FLAGS:  # a flag names kernels of a native tower: a torch network would silently train in fp32
+            if check(cfg):
+                from sample_factory_amd.model.torch_policy import TorchPolicyAdapter
+                if isinstance(self.actor_critic, TorchPolicyAdapter):
+                    raise NotImplementedError(f"{flag} with a network that runs in torch (a user-registered model or a "
+                                              f"configuration the native kernels do not take): only {tower}")
         self._shift_pad = self._augment_pad(cfg, self.actor_critic, self.env_info.obs_space)
         # cutout / intensity: the resolved flags when one of them is on, else None: the shift alone, or nothing
         self._aug_ops = self._augment_plan(cfg, self.actor_critic, self.env_info.obs_space)

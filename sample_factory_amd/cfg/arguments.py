@@ -284,6 +284,20 @@ def resnet_bf16(cfg) -> bool:
 CONV_BF16_ARCHS = ("convnet_simple", "convnet_atari")
 
 
+def _image_key(env_info):
+    """does env_info's observation space have an image (3-d) key?  None: no observation space known"""
+    spaces_ = getattr(getattr(env_info, "obs_space", None), "spaces", None)
+    if spaces_ is None:
+        return None
+    return any(len(getattr(s, "shape", None) or ()) == 3 for s in spaces_.values())
+
+
+def _needs_image(flag, cfg, env_info) -> None:
+    if _image_key(env_info) is False:
+        raise ValueError(f"{flag}=True needs an image observation: this observation space gets an MLP encoder "
+                         f"(encoder_mlp_layers={cfg.encoder_mlp_layers}), encoder_conv_architecture is not used")
+
+
 def conv_bf16(cfg, env_info=None) -> bool:
     """cfg.encoder_conv_bf16, checked: only with an image encoder of encoder_conv_architecture convnet_simple or
     convnet_atari (ValueError; convnet_impala's 16 -> 32 layer has no kernel in the family).  env_info (optional): its
@@ -292,10 +306,8 @@ def conv_bf16(cfg, env_info=None) -> bool:
     if on and cfg.encoder_conv_architecture not in CONV_BF16_ARCHS:
         raise ValueError(f"encoder_conv_bf16=True needs encoder_conv_architecture in {CONV_BF16_ARCHS}, got "
                          f"encoder_conv_architecture={cfg.encoder_conv_architecture}")
-    spaces_ = getattr(getattr(env_info, "obs_space", None), "spaces", None)
-    if on and spaces_ is not None and not any(len(getattr(s, "shape", None) or ()) == 3 for s in spaces_.values()):
-        raise ValueError("encoder_conv_bf16=True needs an image observation: this observation space gets an MLP encoder "
-                         f"(encoder_mlp_layers={cfg.encoder_mlp_layers}), encoder_conv_architecture is not used")
+    if on:
+        _needs_image("encoder_conv_bf16", cfg, env_info)
     return on
 
 
@@ -310,10 +322,8 @@ def conv1_bf16(cfg, env_info=None) -> bool:
     if on and getattr(cfg, "normalize_input", False) and os.environ.get("SF_CONV1_NORM", "1") == "0":
         raise ValueError("encoder_conv1_bf16=True with normalize_input=True needs the normaliser fused into the first layer: "
                          "under SF_CONV1_NORM=0 that layer reads a materialised f32 batch and is no raw-frame layer")
-    spaces_ = getattr(getattr(env_info, "obs_space", None), "spaces", None)
-    if on and spaces_ is not None and not any(len(getattr(s, "shape", None) or ()) == 3 for s in spaces_.values()):
-        raise ValueError("encoder_conv1_bf16=True needs an image observation: this observation space gets an MLP encoder "
-                         f"(encoder_mlp_layers={cfg.encoder_mlp_layers}), encoder_conv_architecture is not used")
+    if on:
+        _needs_image("encoder_conv1_bf16", cfg, env_info)
     return on
 
 
@@ -322,12 +332,22 @@ def mlp_bf16(cfg, env_info=None) -> bool:
     launches its own fully connected layers, which have no bf16 path, and refuses the flag itself).  Checked against
     env_info's observation space: without an image key the architecture is not used and the flag stands"""
     on = bool(getattr(cfg, "mlp_bf16", False))
-    spaces_ = getattr(getattr(env_info, "obs_space", None), "spaces", None)
-    image = spaces_ is not None and any(len(getattr(s, "shape", None) or ()) == 3 for s in spaces_.values())
-    if on and image and cfg.encoder_conv_architecture == "resnet_impala":
+    if on and _image_key(env_info) and cfg.encoder_conv_architecture == "resnet_impala":
         raise ValueError("mlp_bf16=True is not served with encoder_conv_architecture=resnet_impala: the fully connected "
                          "layers of that tower have no bf16 path")
     return on
+
+
+# (checker, flag, which native tower has the kernels): verify_cfg runs every checker, Learner.init refuses every flag that is
+# on for a network that runs in torch
+BF16_FLAGS = (
+    (resnet_bf16, "encoder_resnet_bf16", "the native resnet_impala tower has the bf16 convs (SF_NATIVE_RESNET=0 runs the "
+                                         "torch one)"),
+    (conv_bf16, "encoder_conv_bf16", "the native convnet_simple / convnet_atari tower has the bf16 convs"),
+    (conv1_bf16, "encoder_conv1_bf16", "the native convnet_simple / convnet_atari / convnet_impala tower has the bf16 "
+                                       "raw-frame layer"),
+    (mlp_bf16, "mlp_bf16", "the native towers have the bf16 fully connected layers"),
+)
 
 
 def resnet_stages(cfg):
@@ -340,10 +360,11 @@ def verify_cfg(cfg, env_info) -> bool:
     """The constraints of cfg/arguments.py:105-201 that concern the hot path."""
     ok = True
     resnet_width(cfg)  # raises ValueError
-    resnet_bf16(cfg)   # ... too
-    conv_bf16(cfg, env_info)  # ... too
-    conv1_bf16(cfg, env_info)  # ... too
-    mlp_bf16(cfg, env_info)   # ... too
+    for check, _, _ in BF16_FLAGS:  # ... too (resnet_bf16 has nothing to check against the observation space)
+        if check is resnet_bf16:
+            check(cfg)
+        else:
+            check(cfg, env_info)
 
     def err(msg):
         nonlocal ok

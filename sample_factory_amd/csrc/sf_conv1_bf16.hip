@@ -35,6 +35,7 @@
 // hundreds of partials.
 #include "sf_common.h"
 #include "sf_resnet_shared.h"
+#include "sf_bf16.h"
 
 #include <algorithm>
 
@@ -42,9 +43,7 @@
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int C1_K = 8, C1_ST = 4;
 constexpr int C1_FW = 4;                    // fragments a wave holds at a time (forward)
@@ -74,8 +73,7 @@ struct C1Tile {
     FastDiv dcols, dLH, dCin, dRPR, dTR;
 };
 
-inline int c1_ceil(int a, int b) { return (a + b - 1) / b; }
-inline int c1_odd(int x, int unit) { x = c1_ceil(x, unit); return (x | 1) * unit; }  // smallest odd multiple of unit >= x
+inline int c1_odd(int x, int unit) { x = ceil_div(x, unit); return (x | 1) * unit; }  // smallest odd multiple of unit >= x
 
 inline bool c1_served(const sf_conv_desc *d) {
     if (!d || (d->in_u8 != 1 && d->in_u8 != 2) || d->KH != C1_K || d->KW != C1_K || d->stride != C1_ST) return false;
@@ -102,8 +100,8 @@ bool c1_tile(const sf_conv_desc &d, bool wgrad, int64_t n, C1Tile *out) {
     if (bytes(1, 1) > budget) return false;
     int TR = d.OH;
     while (TR > 1 && bytes(1, TR) > budget) --TR;
-    t.nrt = c1_ceil(d.OH, TR);
-    t.TR = c1_ceil(d.OH, t.nrt);
+    t.nrt = ceil_div(d.OH, TR);
+    t.TR = ceil_div(d.OH, t.nrt);
     t.S = 1;
     if (t.nrt == 1)
         while (t.S < n && (t.S + 1) * d.OH * d.OW <= C1_TILE_M && bytes(t.S + 1, t.TR) <= budget) ++t.S;
@@ -300,9 +298,10 @@ __global__ __launch_bounds__(256) void k_conv1_wgrad_bf16(const void *__restrict
 #pragma unroll
         for (int c = 0; c < CB; ++c) acc[c][u] = (floatx4){0.0f, 0.0f, 0.0f, 0.0f};
     }
-    bf16x8 ones8, zero8;
+    const bf16x8 ones8 = bf16_ones8();
+    bf16x8 zero8;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { ones8[k] = (__bf16)1.0f; zero8[k] = zero; }
+    for (int k = 0; k < 8; ++k) zero8[k] = zero;
     // the lane's A row: k = c*64 + 16*wave + lr, i.e. tap row 2*wave + lr/8, tap column lr%8
     const int arow = ((2 * wave + (lr >> 3)) * C1_K + (lr & 7)) * OWp;
     const int64_t b0 = (int64_t)blockIdx.x * t.bpp, b1 = min(t.nb, b0 + t.bpp);

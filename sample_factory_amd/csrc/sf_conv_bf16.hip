@@ -40,13 +40,11 @@
 // Compiled with -ffp-contract=off like its siblings: the epilogues round after each op.
 #include "sf_common.h"
 #include "sf_resnet_shared.h"
+#include "sf_bf16.h"
 
 #define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int CB_CHUNK = 8;                // M fragments the four waves hold at a time
 constexpr int CB_TILE_M = 16 * CB_CHUNK;   // ... = 128 pixels: the samples of a tile are chosen to fill them
@@ -55,25 +53,6 @@ constexpr int CB_MIN_PARTS = 64;
 constexpr int CB_GRID_TARGET = 1024;       // work-groups the weight gradient aims at: parts x Cin blocks
 
 extern __shared__ float4 cb_lds4[];
-
-__device__ __forceinline__ bf16x8 cb_pack(const float4 &a, const float4 &b) {
-    bf16x8 r;
-    r[0] = (__bf16)a.x; r[1] = (__bf16)a.y; r[2] = (__bf16)a.z; r[3] = (__bf16)a.w;
-    r[4] = (__bf16)b.x; r[5] = (__bf16)b.y; r[6] = (__bf16)b.z; r[7] = (__bf16)b.w;
-    return r;
-}
-
-// derivative of the activation through its OUTPUT y (sf_conv_dgrad's contract: in_act is the stored activation)
-__device__ __forceinline__ float cb_act_bwd(int kind, float y) {
-    switch (kind) {
-        case 1: return y > 0.0f ? 1.0f : 0.0f;
-        case 2: return 1.0f - y * y;
-        case 3: return y > 0.0f ? 1.0f : y + 1.0f;
-        default: return 1.0f;
-    }
-}
-
-inline int cb_ceil(int a, int b) { return (a + b - 1) / b; }
 
 inline bool cb_served(const sf_conv_desc *d) {
     if (!d || d->in_u8 != 0 || d->traj_T != 0 || d->KH != d->KW) return false;
@@ -101,17 +80,17 @@ struct CbTile {
 // false: one row band of this layer does not fit the LDS budget (the image is too wide)
 bool cb_tile(const CbGeo &g, bool dgrad, int64_t n, CbTile *out) {
     CbTile t;
-    t.T = cb_ceil(g.K, g.st);
+    t.T = ceil_div(g.K, g.st);
     t.cs = (dgrad ? g.Cout : g.Cin) + 8;
-    const int rows = dgrad ? cb_ceil(g.H, g.st) : g.OH, cols = dgrad ? cb_ceil(g.W, g.st) : g.OW;
+    const int rows = dgrad ? ceil_div(g.H, g.st) : g.OH, cols = dgrad ? ceil_div(g.W, g.st) : g.OW;
     t.LW = dgrad ? cols + t.T - 1 : (g.OW - 1) * g.st + g.K;
     auto lh = [&](int TR) { return dgrad ? TR + t.T - 1 : (TR - 1) * g.st + g.K; };
     auto bytes = [&](int S, int TR) { return (int64_t)S * lh(TR) * t.LW * t.cs * 2; };
     int TR = rows;
     while (TR > 1 && bytes(1, TR) > CB_LDS_BUDGET) --TR;
     if (bytes(1, TR) > CB_LDS_BUDGET) return false;
-    t.nrt = cb_ceil(rows, TR);
-    t.TR = cb_ceil(rows, t.nrt);
+    t.nrt = ceil_div(rows, TR);
+    t.TR = ceil_div(rows, t.nrt);
     t.S = 1;
     if (t.nrt == 1)
         while (t.S < n && (t.S + 1) * rows * cols <= CB_TILE_M && bytes(t.S + 1, t.TR) <= CB_LDS_BUDGET) ++t.S;
@@ -148,7 +127,7 @@ __global__ __launch_bounds__(256) void k_conv_bf16(const float *__restrict__ src
             v0 = p[0];
             v1 = p[1];
         }
-        *reinterpret_cast<bf16x8 *>(lds + lp * cs + 8 * q) = cb_pack(v0, v1);
+        *reinterpret_cast<bf16x8 *>(lds + lp * cs + 8 * q) = bf16_pack(v0, v1);
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, pair = wave % NP, wg = wave / NP;
@@ -204,7 +183,7 @@ __global__ __launch_bounds__(256) void k_conv_bf16(const float *__restrict__ src
             load_b(0, 0, 0);
             int tr = 0, tc = 0, ch = 0;
             for (int it = 0; it < steps; ++it) {
-                const bf16x8 b0 = cb_pack(braw[0][0], braw[0][1]), b1 = cb_pack(braw[1][0], braw[1][1]);
+                const bf16x8 b0 = bf16_pack(braw[0][0], braw[0][1]), b1 = bf16_pack(braw[1][0], braw[1][1]);
                 const int aoff = (DGRAD ? -(tr * LW + tc) : tr * LW + tc) * cs + ch * 32;
                 if (++ch == nch) {
                     ch = 0;
@@ -236,7 +215,7 @@ __global__ __launch_bounds__(256) void k_conv_bf16(const float *__restrict__ src
                         float v = acc[f][u][j];
                         if (DGRAD) {
                             const int64_t idx = (((s0 + s) * g.H + ph + st * (r0 + r)) * g.W + pw + st * c) * Cn + o;
-                            if (act) v = v * cb_act_bwd(act, in_act[idx]);
+                            if (act) v = v * act_bwd_out(act, in_act[idx]);
                             out[idx] = v;
                         } else {
                             const int64_t idx = (((s0 + s) * g.OH + r0 + r) * g.OW + c) * Cn + o;
@@ -273,14 +252,12 @@ struct CbBand {
     int64_t lds_bytes;
 };
 
-int cb_odd8(int x) { return ((x >> 3) & 1) ? x : x + 8; }
-
 CbBand cb_band(const sf_conv_desc &d, int64_t n) {
     CbBand t;
     const int rows = d.KH * d.KW * 16 + d.Cout;
     t.PT = 256;
-    while (t.PT > 32 && (int64_t)rows * cb_odd8(t.PT) * 2 > CB_LDS_BUDGET) t.PT -= 32;
-    t.cs = cb_odd8(t.PT);
+    while (t.PT > 32 && (int64_t)rows * odd8(t.PT) * 2 > CB_LDS_BUDGET) t.PT -= 32;
+    t.cs = odd8(t.PT);
     t.lds_bytes = (int64_t)rows * t.cs * 2;
     t.blocks = d.Cin / 16;
     t.NPX = n * d.OH * d.OW;
@@ -310,9 +287,7 @@ __global__ __launch_bounds__(64 * NCOG) void k_conv_wgrad_bf16(const float *__re
 #pragma unroll
         for (int tap = 0; tap < TAPS; ++tap) acc[tap][u] = (floatx4){0.0f, 0.0f, 0.0f, 0.0f};
     }
-    bf16x8 ones8;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) ones8[k] = (__bf16)1.0f;
+    const bf16x8 ones8 = bf16_ones8();
     const int64_t t0 = (int64_t)blockIdx.x * t.tpp, t1 = min(t.NT, t0 + t.tpp);
     const __bf16 *xa = la + lr * cs, *ga = lgy + (cog * CT * 16 + lr) * cs;
     for (int64_t tile = t0; tile < t1; ++tile) {

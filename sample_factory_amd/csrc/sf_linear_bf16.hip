@@ -39,29 +39,17 @@
 // Compiled with -ffp-contract=off like its siblings: the epilogues round after each op.
 #include "sf_common.h"
 #include "sf_resnet_shared.h"
+#include "sf_bf16.h"
 
 #define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int LB_T = 128;             // outputs of a tile, both ways
 constexpr int LB_KC = 64;             // reduction elements of a stage
 constexpr int LB_PITCH = LB_KC + 8;   // bf16 elements of an LDS row
 constexpr int LB_XCD = 8;
 constexpr int LB_WGRAD_GRID = 1024;   // work-groups the weight gradient aims at: tiles x parts
-
-// derivative of the activation through its OUTPUT y (sf_conv_dgrad's contract: in_act is the stored activation)
-__device__ __forceinline__ float lb_act_bwd(int kind, float y) {
-    switch (kind) {
-        case 1: return y > 0.0f ? 1.0f : 0.0f;
-        case 2: return 1.0f - y * y;
-        case 3: return y > 0.0f ? 1.0f : y + 1.0f;
-        default: return 1.0f;
-    }
-}
 
 // T[i][k] = X[(i0 + i) * ld + k0 + k], zero for i0 + i >= I or k0 + k >= R (R % 8 == 0: a run of 8 is in or out as a whole)
 __device__ __forceinline__ void lb_load_rows(float4 (&v)[8], const float *__restrict__ X, int64_t ld, int64_t i0, int64_t I,
@@ -146,9 +134,7 @@ __device__ __forceinline__ void lb_mma(const __bf16 *TA, const __bf16 *TB, float
 #pragma unroll
             for (int u = 0; u < 4; ++u) acc[f][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[f], b[u], acc[f][u], 0, 0, 0);
         if (BIAS && bias_on) {
-            bf16x8 ones8;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) ones8[k] = (__bf16)1.0f;
+            const bf16x8 ones8 = bf16_ones8();
 #pragma unroll
             for (int u = 0; u < 4; ++u) accb[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones8, b[u], accb[u], 0, 0, 0);
         }
@@ -209,7 +195,7 @@ __global__ __launch_bounds__(256) void k_linear_bf16(const float *__restrict__ A
                 const int64_t idx = row * Cn + col;
                 float v = acc[f][u][j];
                 if (DGRAD) {
-                    if (in_act != nullptr) v = v * lb_act_bwd(act, in_act[idx]);
+                    if (in_act != nullptr) v = v * act_bwd_out(act, in_act[idx]);
                     out[idx] = v;
                 } else {
                     v = v + bo;
@@ -265,13 +251,12 @@ __global__ __launch_bounds__(256) void k_linear_wgrad_bf16(const float *__restri
     }
 }
 
-inline int64_t lb_ceil(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 // op 0 forward, 1 weight gradient, 2 data gradient
 bool lb_served(int op, int64_t n, int K, int N) {
     if (op < 0 || op > 2 || n < 1 || K < 8 || N < 8 || (K & 7) || (N & 7)) return false;
     if ((int64_t)K * N + N > 0x7fffffffLL) return false;  // the parts' sum indexes a part with an int
-    const int64_t tiles = op == 1 ? lb_ceil(K, LB_T) * lb_ceil(N, LB_T) : lb_ceil(n, LB_T) * lb_ceil(op == 0 ? N : K, LB_T);
+    const int64_t tiles = op == 1 ? ceil_div<int64_t>(K, LB_T) * ceil_div<int64_t>(N, LB_T)
+                                  : ceil_div<int64_t>(n, LB_T) * ceil_div<int64_t>(op == 0 ? N : K, LB_T);
     return tiles <= 0x7fffffffLL - LB_XCD;
 }
 
@@ -281,11 +266,11 @@ struct LbParts {
 
 LbParts lb_parts(int64_t n, int K, int N) {
     LbParts p;
-    p.tiles = lb_ceil(K, LB_T) * lb_ceil(N, LB_T);
-    p.NT = lb_ceil(n, LB_KC);
+    p.tiles = ceil_div<int64_t>(K, LB_T) * ceil_div<int64_t>(N, LB_T);
+    p.NT = ceil_div<int64_t>(n, LB_KC);
     const int64_t target = std::max<int64_t>(1, LB_WGRAD_GRID / p.tiles);
-    p.cpp = lb_ceil(p.NT, target);
-    p.parts = lb_ceil(p.NT, p.cpp);
+    p.cpp = ceil_div<int64_t>(p.NT, target);
+    p.parts = ceil_div<int64_t>(p.NT, p.cpp);
     return p;
 }
 
@@ -301,9 +286,9 @@ int lb_check(int op, int64_t n, int K, int N, int act, const char *what) {
 template <bool DGRAD>
 void lb_launch(hipStream_t s, const float *A, const float *W, const float *bias, const float *in_act, float *out, int act,
                int64_t M, int R, int Cn) {
-    const int nct = (int)lb_ceil(Cn, LB_T);
-    const int64_t tiles = lb_ceil(M, LB_T) * nct;
-    const unsigned grid = (unsigned)(lb_ceil(tiles, LB_XCD) * LB_XCD);
+    const int nct = (int)ceil_div<int64_t>(Cn, LB_T);
+    const int64_t tiles = ceil_div<int64_t>(M, LB_T) * nct;
+    const unsigned grid = (unsigned)(ceil_div<int64_t>(tiles, LB_XCD) * LB_XCD);
     hipLaunchKernelGGL((k_linear_bf16<DGRAD>), dim3(grid), dim3(256), 0, s, A, W, bias, in_act, out, act, M, R, Cn, nct, tiles);
 }
 
@@ -350,7 +335,7 @@ extern "C" int sf_linear_wgrad_bf16(const float *in, const float *dout, float *d
     hipStream_t s = STREAM(stream);
     float *part = static_cast<float *>(workspace);
     hipLaunchKernelGGL(k_linear_wgrad_bf16, dim3((unsigned)p.tiles, (unsigned)p.parts), dim3(256), 0, s, in, dout, part, n, K, N,
-                       (int)lb_ceil(N, LB_T), p.cpp, p.NT);
+                       (int)ceil_div<int64_t>(N, LB_T), p.cpp, p.NT);
     rc = sf_launch_status("sf_linear_wgrad_bf16 (partials)");
     if (rc) return rc;
     return sf_res_wgrad_sum_launch(part, (int)p.parts, K * N, N, dw, db, s);

@@ -36,13 +36,11 @@
 // Compiled with -ffp-contract=off like sf_resnet_mfma.hip: the epilogues round after each op.
 #include "sf_common.h"
 #include "sf_resnet_shared.h"
+#include "sf_bf16.h"
 
 #define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int RB_FRAGS = 8;                // M fragments of a forward / data-gradient tile
 constexpr int RB_TILE_M = 16 * RB_FRAGS;   // ... = 128 output pixels
@@ -56,13 +54,6 @@ extern __shared__ float4 rb_lds4[];
 inline bool rb_width(int c) { return c == 32 || c == 64 || c == 128; }
 // a 16 on the input side goes to sf_resnet_bf16_c16.hip; any other pair with a 16 is refused
 inline bool rb_served(int cin, int cout) { return (rb_width(cin) && rb_width(cout)) || sf_res_c16_pair(cin, cout); }
-
-__device__ __forceinline__ bf16x8 rb_pack(const float4 &a, const float4 &b) {
-    bf16x8 r;
-    r[0] = (__bf16)a.x; r[1] = (__bf16)a.y; r[2] = (__bf16)a.z; r[3] = (__bf16)a.w;
-    r[4] = (__bf16)b.x; r[5] = (__bf16)b.y; r[6] = (__bf16)b.z; r[7] = (__bf16)b.w;
-    return r;
-}
 
 __device__ __forceinline__ float4 rb_act4(int act, const float4 &v) {
     return make_float4(act_fwd(act, v.x), act_fwd(act, v.y), act_fwd(act, v.z), act_fwd(act, v.w));
@@ -119,7 +110,7 @@ __global__ __launch_bounds__(256) void k_res_conv_bf16(const float *__restrict__
             v1 = p[1];
             if (!DGRAD && act) { v0 = rb_act4(act, v0); v1 = rb_act4(act, v1); }
         }
-        *reinterpret_cast<bf16x8 *>(lds + hp * cs + 8 * q) = rb_pack(v0, v1);
+        *reinterpret_cast<bf16x8 *>(lds + hp * cs + 8 * q) = bf16_pack(v0, v1);
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, pair = wave % NP, f0 = (wave / NP) * FW;
@@ -156,7 +147,7 @@ __global__ __launch_bounds__(256) void k_res_conv_bf16(const float *__restrict__
     load_b(0, 0);
     int tap = 0, ch = 0;
     for (int it = 0; it < steps; ++it) {
-        const bf16x8 b0 = rb_pack(braw[0][0], braw[0][1]), b1 = rb_pack(braw[1][0], braw[1][1]);
+        const bf16x8 b0 = bf16_pack(braw[0][0], braw[0][1]), b1 = bf16_pack(braw[1][0], braw[1][1]);
         const int aoff = ((tap / 3) * HW2 + tap % 3) * cs + ch * 32;
         if (++ch == nch) { ch = 0; ++tap; }
         if (it + 1 < steps) load_b(tap, ch);
@@ -223,8 +214,6 @@ struct RbBand {
     int64_t lds_bytes;
 };
 
-int rb_odd8(int x) { return ((x >> 3) & 1) ? x : x + 8; }
-
 // false: a single row of this layer does not fit the LDS budget
 bool rb_band(int H, int W, int Cin, int Cout, int64_t n, RbBand *out) {
     RbBand t;
@@ -235,7 +224,7 @@ bool rb_band(int H, int W, int Cin, int Cout, int64_t n, RbBand *out) {
     t.WP8 = (W + 7) & ~7;
     t.RW = t.WP8 >> 3;
     auto bytes = [&](int S, int TH) {
-        return 2 * ((int64_t)3 * t.CW * rb_odd8(S * (TH + 2) * t.WP8) + (int64_t)Cout * rb_odd8(S * TH * t.WP8));
+        return 2 * ((int64_t)3 * t.CW * odd8(S * (TH + 2) * t.WP8) + (int64_t)Cout * odd8(S * TH * t.WP8));
     };
     int TH = std::max(1, std::min(H, RB_BAND_PIX / t.WP8));
     while (TH > 1 && bytes(1, TH) > RB_LDS_BUDGET) --TH;
@@ -245,8 +234,8 @@ bool rb_band(int H, int W, int Cin, int Cout, int64_t n, RbBand *out) {
     t.S = 1;
     if (t.nrt == 1)
         while (t.S < n && (t.S + 1) * H * t.WP8 <= RB_BAND_PIX && bytes(t.S + 1, t.TH) <= RB_LDS_BUDGET) ++t.S;
-    t.csa = rb_odd8(t.S * (t.TH + 2) * t.WP8);
-    t.csg = rb_odd8(t.S * t.TH * t.WP8);
+    t.csa = odd8(t.S * (t.TH + 2) * t.WP8);
+    t.csg = odd8(t.S * t.TH * t.WP8);
     t.lds_bytes = bytes(t.S, t.TH);
     t.NB = ((n + t.S - 1) / t.S) * t.nrt;
     const int64_t target = std::max(RB_MIN_PARTS, RB_GRID_TARGET / t.blocks);
@@ -276,9 +265,10 @@ __global__ __launch_bounds__(256) void k_res_wgrad_bf16(const float *__restrict_
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) acc[tap][u] = (floatx4){0.0f, 0.0f, 0.0f, 0.0f};
     }
-    bf16x8 zero8, ones8;
+    const bf16x8 ones8 = bf16_ones8();
+    bf16x8 zero8;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { zero8[k] = (__bf16)0.0f; ones8[k] = (__bf16)1.0f; }
+    for (int k = 0; k < 8; ++k) zero8[k] = (__bf16)0.0f;
     const int64_t b0 = (int64_t)blockIdx.x * t.bpp, b1 = min(t.NB, b0 + t.bpp);
     const int qa = CW >> 2, qg = Cout >> 2;
     const __bf16 *xa = la + (cit * 16 + lr) * csa, *ga = lgy + (cog * CT * 16 + lr) * csg;

@@ -34,11 +34,9 @@
 // as many rows as 64 KB holds (six rows of 48 pixels at 16 -> 32).
 #include "sf_common.h"
 #include "sf_resnet_shared.h"
+#include "sf_bf16.h"
 
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int RC_TILE_M = 512;              // output pixels of a forward / data-gradient tile: 32 M fragments
 constexpr int RC_TBL_BYTES = RC_TILE_M * 4 + 16;  // the pixel table and one zeroed 16-byte word in front of the halo band
@@ -47,13 +45,6 @@ constexpr int RC_GRID = 1024;               // work-groups of a launch: more til
 constexpr int RC_BAND_SAMPLE_PIX = 1024;    // padded pixels up to which a weight-gradient band packs whole samples
 
 extern __shared__ float4 rc_lds4[];
-
-__device__ __forceinline__ bf16x8 rc_pack(const float4 &a, const float4 &b) {
-    bf16x8 r;
-    r[0] = (__bf16)a.x; r[1] = (__bf16)a.y; r[2] = (__bf16)a.z; r[3] = (__bf16)a.w;
-    r[4] = (__bf16)b.x; r[5] = (__bf16)b.y; r[6] = (__bf16)b.z; r[7] = (__bf16)b.w;
-    return r;
-}
 
 __device__ __forceinline__ float4 rc_act4(int act, const float4 &v) {
     return make_float4(act_fwd(act, v.x), act_fwd(act, v.y), act_fwd(act, v.z), act_fwd(act, v.w));
@@ -148,7 +139,7 @@ __global__ __launch_bounds__(256) void k_res_conv_bf16_c16(const float *__restri
                 v1 = p[1];
                 if (!DGRAD && act) { v0 = rc_act4(act, v0); v1 = rc_act4(act, v1); }
             }
-            *reinterpret_cast<bf16x8 *>(lds + hp * cs + 8 * q) = rc_pack(v0, v1);
+            *reinterpret_cast<bf16x8 *>(lds + hp * cs + 8 * q) = bf16_pack(v0, v1);
         }
         __syncthreads();
         for (int fb = wave * 2; fb < nfr; fb += 8) {
@@ -212,15 +203,13 @@ struct RcBand {
     int64_t lds_bytes;
 };
 
-int rc_odd8(int x) { return ((x >> 3) & 1) ? x : x + 8; }
-
 // false: a single row of this layer does not fit the LDS budget (W > 200 at 16 -> 16, W > 184 at 16 -> 32)
 bool rc_band(int H, int W, int Cout, int64_t n, RcBand *out) {
     RcBand t;
     t.WP8 = (W + 7) & ~7;
     t.RW = t.WP8 >> 3;
     auto bytes = [&](int64_t S, int TH) {
-        return 2 * ((int64_t)3 * 16 * rc_odd8((int)(S * (TH + 2) * t.WP8)) + (int64_t)Cout * rc_odd8((int)(S * TH * t.WP8)));
+        return 2 * ((int64_t)3 * 16 * odd8((int)(S * (TH + 2) * t.WP8)) + (int64_t)Cout * odd8((int)(S * TH * t.WP8)));
     };
     if (bytes(1, 1) > RC_LDS_BUDGET) return false;
     int TH = std::max<int64_t>(1, std::min<int64_t>(H, RC_LDS_BUDGET / (2 * (48 + Cout) * (int64_t)t.WP8)));
@@ -230,8 +219,8 @@ bool rc_band(int H, int W, int Cout, int64_t n, RcBand *out) {
     t.S = 1;
     if (t.nrt == 1)
         while (t.S < n && (int64_t)(t.S + 1) * H * t.WP8 <= RC_BAND_SAMPLE_PIX && bytes(t.S + 1, t.TH) <= RC_LDS_BUDGET) ++t.S;
-    t.csa = rc_odd8(t.S * (t.TH + 2) * t.WP8);
-    t.csg = rc_odd8(t.S * t.TH * t.WP8);
+    t.csa = odd8(t.S * (t.TH + 2) * t.WP8);
+    t.csg = odd8(t.S * t.TH * t.WP8);
     // the waves' accumulators meet in two slots of (9 + 1) * CT float4 per lane
     t.lds_bytes = std::max<int64_t>(bytes(t.S, t.TH), 2LL * 10 * (Cout / 16) * 64 * 16);
     t.NB = ((n + t.S - 1) / t.S) * t.nrt;
@@ -257,9 +246,10 @@ __global__ __launch_bounds__(256) void k_res_wgrad_bf16_c16(const float *__restr
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) acc[tap][u] = (floatx4){0.0f, 0.0f, 0.0f, 0.0f};
     }
-    bf16x8 zero8, ones8;
+    const bf16x8 ones8 = bf16_ones8();
+    bf16x8 zero8;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { zero8[k] = (__bf16)0.0f; ones8[k] = (__bf16)1.0f; }
+    for (int k = 0; k < 8; ++k) zero8[k] = (__bf16)0.0f;
     const int64_t b0 = (int64_t)blockIdx.x * t.bpp, b1 = min(t.NB, b0 + t.bpp);
     constexpr int qa = Cin >> 2, qg = Cout >> 2;
     const __bf16 *xa = la + lr * csa, *ga = lgy + lr * csg;

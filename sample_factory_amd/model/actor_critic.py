@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import math
 import threading
-from typing import Dict, List, Optional
+from typing import Callable, Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -82,8 +82,8 @@ class _Layer:
         self.role = role          # "chain" | "rnn_ih" (x projection, followed by the cell) | "rnn_hh" (side branch)
         self.in_act_kind = 0      # activation kind of the tensor feeding this layer (fused into its dgrad epilogue)
         self.rnn_l = 0            # index of the stacked recurrent layer a "rnn_ih" / "rnn_hh" projection belongs to
-        self.bf16 = False         # cfg.encoder_conv_bf16 (a conv layer) / cfg.mlp_bf16 (a fully connected one): every pass
-        #                           of this layer runs on the bf16 family (sf_conv_*_bf16 / sf_linear_*_bf16)
+        self.route = None         # None: the fp32 dispatch; a _Route (cfg.encoder_conv_bf16 / encoder_conv1_bf16 / mlp_bf16):
+        #                           every pass of this layer runs on that bf16 family
         self.desc = desc
         self.kind = kind          # "conv_u8" | "conv_f32frame" | "conv" | "linear" | "linear_after_conv" | "heads"
         self.ref_w_shape = ref_w_shape
@@ -95,6 +95,10 @@ class _Layer:
     @property
     def out_pixels(self):
         return self.desc.OH * self.desc.OW
+
+    @property
+    def bf16(self) -> bool:
+        return self.route is not None
 
     # ---- layout conversion (reference <-> native)
     def w_from_ref(self, w_ref: torch.Tensor) -> torch.Tensor:
@@ -123,6 +127,90 @@ class _Layer:
 def _linear_desc(K, N, relu) -> lib.sf_conv_desc:
     return lib.sf_conv_desc(Cin=K, H=1, W=1, Cout=N, KH=1, KW=1, stride=1, OH=1, OW=1, in_u8=0, relu=int(relu),
                             traj_T=0, sub_mean=0.0, inv_scale=1.0)
+
+
+def _desc_at(L: _Layer, traj_T) -> lib.sf_conv_desc:
+    """the layer's desc for a launch that reads a slab of trajectories traj_T long (0: the layer's own desc)"""
+    if not traj_T:
+        return L.desc
+    d = lib.sf_conv_desc.from_buffer_copy(L.desc)
+    d.traj_T = int(traj_T)
+    return d
+
+
+class _Route(NamedTuple):
+    """The launches of ONE bf16 family behind one signature per op, whatever the family's wrappers take:
+    fwd(x, stride, index, offset, tabs, w, b, out, n, desc), wgrad_workspace(n, desc) -> bytes,
+    wgrad(x, stride, index, offset, tabs, g, gw, gb, n, desc, ws), dgrad(g, w, in_act, gin, n, desc); tabs = (mu, rstd) of the
+    normaliser fused into a raw-frame loader, else (None, None).  A routed layer runs these in every pass: never conv_fwd_t,
+    split-K or a sign-bit twin, so the behaviour policy and the learner evaluate the same function.  The wrappers are looked
+    up in lib at every call."""
+    fwd: Callable
+    wgrad_workspace: Callable
+    wgrad: Callable
+    dgrad: Optional[Callable] = None  # (the raw-frame layer has no input to hand a gradient to)
+
+
+def _conv_route(L: _Layer) -> _Route:
+    """cfg.encoder_conv_bf16: an inner conv layer (f32 NHWC input) on sf_conv_*_bf16"""
+    def fwd(x, stride, index, offset, tabs, w, b, out, n, desc):
+        lib.conv_fwd_bf16(x, stride, index, offset, w, b, out, n, desc)
+
+    def wgrad_workspace(n, desc):
+        return lib.conv_wgrad_bf16_workspace(n, desc)
+
+    def wgrad(x, stride, index, offset, tabs, g, gw, gb, n, desc, ws):
+        lib.conv_wgrad_bf16(x, stride, index, offset, g, gw, gb, n, desc, ws)
+
+    def dgrad(g, w, in_act, gin, n, desc):
+        lib.conv_dgrad_bf16(g, w, in_act, gin, n, desc)
+    return _Route(fwd, wgrad_workspace, wgrad, dgrad)
+
+
+def _conv1_route(L: _Layer) -> _Route:
+    """cfg.encoder_conv1_bf16: the raw-frame layer on sf_conv1_*_bf16, with the normaliser's tables or without; its gradient
+    arrives masked (no sign-bit twin: conv2's data gradient reads the activation)"""
+    def fwd(x, stride, index, offset, tabs, w, b, out, n, desc):
+        lib.conv1_fwd_bf16(x, stride, index, offset, tabs[0], tabs[1], w, b, out, n, desc)
+
+    def wgrad_workspace(n, desc):
+        return lib.conv1_wgrad_bf16_workspace(n, desc)
+
+    def wgrad(x, stride, index, offset, tabs, g, gw, gb, n, desc, ws):
+        lib.conv1_wgrad_bf16(x, stride, index, offset, tabs[0], tabs[1], g, gw, gb, n, desc, ws)
+    return _Route(fwd, wgrad_workspace, wgrad)
+
+
+def _linear_route(L: _Layer) -> _Route:
+    """cfg.mlp_bf16: a fully connected layer behind another layer on sf_linear_*_bf16: dense rows [n, K] and [n, N]"""
+    K, N = L.K, L.N
+
+    def fwd(x, stride, index, offset, tabs, w, b, out, n, desc):
+        assert index is None and not offset and not desc.traj_T and stride == K, (L.name, stride, K)
+        lib.linear_fwd_bf16(x, w, b, out, n, K, N, desc.relu)
+
+    def wgrad_workspace(n, desc):
+        return lib.linear_wgrad_bf16_workspace(n, K, N)
+
+    def wgrad(x, stride, index, offset, tabs, g, gw, gb, n, desc, ws):
+        lib.linear_wgrad_bf16(x, g, gw, gb, n, K, N, ws)
+
+    def dgrad(g, w, in_act, gin, n, desc):
+        lib.linear_dgrad_bf16(g, w, in_act, gin, n, K, N, desc.relu)
+    return _Route(fwd, wgrad_workspace, wgrad, dgrad)
+
+
+def _linear_bf16_supported(op, n, desc) -> bool:
+    return lib.linear_bf16_supported(op, n, desc.Cin, desc.Cout)  # (a fully connected layer's desc: 1x1 on a 1x1 image)
+
+
+def _set_route(L: _Layer, flag, ops, supported, serves, route) -> None:
+    """put layer L on a bf16 family, or refuse the flag: every op is probed at n = 1.  serves: what the family's kernels
+    take, a format string over the layer's desc `d` and the op"""
+    for op in ops:
+        if not supported(op, 1, L.desc):
+            raise NotImplementedError(f"{flag}: layer {L.name} " + serves.format(d=L.desc, op=op))
+    L.route = route(L)
 
 
 class NativeModel:
@@ -307,29 +395,20 @@ class ActorCritic(NativeTower):
                                           frame_kind if first else "conv"))
                 cin, h, w = cout, oh, ow
             if conv_bf16(cfg):  # every inner conv layer (f32 NHWC input) on the bf16 family, in every pass
-                for i, L in enumerate(self.layers[1:], 1):
-                    d = L.desc
-                    for op in ("fwd", "dgrad", "wgrad"):
-                        if not lib.conv_bf16_supported(op, 1, d):
-                            raise NotImplementedError(
-                                f"encoder_conv_bf16: layer {L.name} ({d.Cin} -> {d.Cout}, {d.KH}x{d.KW} stride {d.stride}, "
-                                f"{d.H}x{d.W} input) is outside the bf16 family's {op} kernels: they take (kernel, stride) in "
-                                f"{{(4, 2), (3, 1), (3, 2)}}, Cin in {{32, 64}}, Cout in {{32, 64, 128}} and images of which "
-                                f"one row band fits 64 KiB of LDS as bf16")
-                    L.bf16 = True
+                for L in self.layers[1:]:
+                    _set_route(L, "encoder_conv_bf16", ("fwd", "dgrad", "wgrad"), lib.conv_bf16_supported,
+                               "({d.Cin} -> {d.Cout}, {d.KH}x{d.KW} stride {d.stride}, {d.H}x{d.W} input) is outside the bf16 "
+                               "family's {op} kernels: they take (kernel, stride) in {{(4, 2), (3, 1), (3, 2)}}, Cin in {{32, 64}}, "
+                               "Cout in {{32, 64, 128}} and images of which one row band fits 64 KiB of LDS as bf16", _conv_route)
             if conv1_bf16(cfg):  # the raw-frame layer on the bf16 family (sf_conv1_*_bf16), in every pass
                 L = self.layers[0]
-                d = L.desc
                 if L.kind not in FRAME_KINDS:
                     raise NotImplementedError(f"encoder_conv1_bf16: layer {L.name} reads a materialised normalised f32 batch "
                                               f"(SF_CONV1_NORM=0), not the raw frames")
-                for op in ("fwd", "wgrad"):
-                    if not lib.conv1_bf16_supported(op, 1, d):
-                        raise NotImplementedError(
-                            f"encoder_conv1_bf16: layer {L.name} ({d.Cin} -> {d.Cout}, {d.KH}x{d.KW} stride {d.stride}, "
-                            f"{d.H}x{d.W} frames) is outside the raw-frame bf16 family's {op} kernel: it takes 8x8 stride 4, "
-                            f"Cin <= 16, Cout in {{16, 32}} and frames of which one output row's band fits LDS")
-                L.bf16 = True
+                _set_route(L, "encoder_conv1_bf16", ("fwd", "wgrad"), lib.conv1_bf16_supported,
+                           "({d.Cin} -> {d.Cout}, {d.KH}x{d.KW} stride {d.stride}, {d.H}x{d.W} frames) is outside the raw-frame "
+                           "bf16 family's {op} kernel: it takes 8x8 stride 4, Cin <= 16, Cout in {{16, 32}} and frames of which "
+                           "one output row's band fits LDS", _conv1_route)
             feat, chw = cin * h * w, (cin, h, w)
             for j, size in enumerate(cfg.encoder_conv_mlp_layers):
                 self.layers.append(_Layer(f"{pfx}mlp_layers.{2 * j}", _linear_desc(feat, size, act), (size, feat),
@@ -399,11 +478,9 @@ class ActorCritic(NativeTower):
             for li, L in enumerate(self.layers):
                 if L.role != "chain" or L.kind not in ("linear", "linear_after_conv") or (li == 0 and not self.features_in):
                     continue
-                for op in ("fwd", "dgrad", "wgrad"):
-                    if not lib.linear_bf16_supported(op, 1, L.K, L.N):
-                        raise NotImplementedError(f"mlp_bf16: layer {L.name} ({L.K} -> {L.N}) is outside the bf16 family's "
-                                                  f"{op} kernels: they take K % 8 == 0 and N % 8 == 0 (K, N >= 8)")
-                L.bf16 = True
+                _set_route(L, "mlp_bf16", ("fwd", "dgrad", "wgrad"), _linear_bf16_supported,
+                           "({d.Cin} -> {d.Cout}) is outside the bf16 family's {op} kernels: they take K % 8 == 0 and N % 8 == 0 "
+                           "(K, N >= 8)", _linear_route)
         # vector observations through a two-layer MLP encoder: the rollout can take the fused inference kernel (not under
         # mlp_bf16: the fused fp32 kernel would make the rollout differ from training)
         self._mlp2_ok = (len(self.obs_shape) == 1 and not getattr(cfg, "mlp_bf16", False) and len(self.layers) >= (2 if self.headless else 3) and not self.features_in and
@@ -674,17 +751,10 @@ class ActorCritic(NativeTower):
 
     def _gemm(self, li, x, stride, index, offset, traj_T, out, n, tag):
         L = self.layers[li]
-        d = L.desc
-        if traj_T:
-            d = lib.sf_conv_desc.from_buffer_copy(L.desc)
-            d.traj_T = int(traj_T)
+        d = _desc_at(L, traj_T)
         w, b, wt = self._wb(li, tag)
-        if L.bf16:  # never conv_fwd_t or the split-K path: the behaviour policy and the learner evaluate the same function
-            if L.kind == "conv":
-                lib.conv_fwd_bf16(x, stride, index, offset, w, b, out, n, d)
-            else:  # cfg.mlp_bf16: a layer behind another layer reads dense rows
-                assert index is None and not offset and not traj_T and stride == L.K, (L.name, stride, L.K)
-                lib.linear_fwd_bf16(x, w, b, out, n, L.K, L.N, d.relu)
+        if L.route:  # never conv_fwd_t or the split-K path: the behaviour policy and the learner evaluate the same function
+            L.route.fwd(x, stride, index, offset, (None, None), w, b, out, n, d)
             return
         if wt is not None and index is None and not traj_T and lib.conv_fwd_t_supported(n, d):
             wsb = lib.conv_fwd_t_workspace(n, d)  # non-zero: wide layer, few rows -> split along K
@@ -810,11 +880,8 @@ class ActorCritic(NativeTower):
             inputs[li] = x
             out = self._buf((tag, li), (n * L.out_pixels, L.N))
             mask = None
-            if tag == "train" and li == 0 and norm_tabs is None and not L.bf16 and li + 1 < len(self.layers) and self.layers[1].role == "chain":
-                d0 = L.desc
-                if tT:
-                    d0 = lib.sf_conv_desc.from_buffer_copy(L.desc)
-                    d0.traj_T = int(tT)
+            if tag == "train" and li == 0 and norm_tabs is None and not L.route and li + 1 < len(self.layers) and self.layers[1].role == "chain":
+                d0 = _desc_at(L, tT)
                 w_, b_, _ = self._wb(li, tag)
                 aligned = x.data_ptr() % 4 == 0 and stride % 4 == 0 and w_.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
                 if aligned and lib.conv_relu_mask_supported(n, d0):  # (the launch fails hard on operands it cannot take)
@@ -834,23 +901,14 @@ class ActorCritic(NativeTower):
                 # projection was a launch of its own that is all fill and drain (GRU: the candidate gate's parts stay apart)
                 fuse_dual = (self._wb(li, tag)[2] is not None and self._wb(li + 1, tag)[2] is not None and
                              self.rnn_H % 64 == 0 and lib.linear_fwd_dual_supported(n, 4 * self.rnn_H, L.K, self.rnn_H))
-            if li == 0 and L.bf16 and L.kind in FRAME_KINDS:
-                # cfg.encoder_conv1_bf16: the same kernel in rollout, bootstrap and training forward, with the tables or
-                # without; no sign-bit twin, conv2's data gradient reads the activation
+            if li == 0 and L.route:
+                # the raw-frame family: the same kernel in rollout, bootstrap and training forward, with the tables or without.
+                # (A trunk's routed fully connected layer 0 also lands here: the launch _gemm would make, norm_tabs is None)
                 w_, b_, _ = self._wb(li, tag)
-                dn = L.desc
-                if tT:
-                    dn = lib.sf_conv_desc.from_buffer_copy(L.desc)
-                    dn.traj_T = int(tT)
-                mu_, rstd_ = norm_tabs if norm_tabs is not None else (None, None)
-                lib.conv1_fwd_bf16(x, stride, idx, off, mu_, rstd_, w_, b_, out, n, dn)
+                L.route.fwd(x, stride, idx, off, norm_tabs or (None, None), w_, b_, out, n, _desc_at(L, tT))
             elif li == 0 and norm_tabs is not None:
                 w_, b_, _ = self._wb(li, tag)
-                dn = L.desc
-                if tT:
-                    dn = lib.sf_conv_desc.from_buffer_copy(L.desc)
-                    dn.traj_T = int(tT)
-                lib.conv_fwd_norm(x, stride, idx, off, norm_tabs[0], norm_tabs[1], w_, b_, out, n, dn)
+                lib.conv_fwd_norm(x, stride, idx, off, norm_tabs[0], norm_tabs[1], w_, b_, out, n, _desc_at(L, tT))
             elif mask is None and not fuse_x and not fuse_dual:
                 self._gemm(li, x, stride, idx, off, tT, out, n, tag)
             if li == 0:
@@ -1223,17 +1281,14 @@ class ActorCritic(NativeTower):
         for pos in range(len(chain) - 1, -1, -1):
             li = chain[pos]
             L = self.layers[li]
-            d = L.desc
+            d, route = L.desc, L.route
             if L.role == "rnn_ih":
                 g = self._rnn_sequence_bwd(li, g, n)  # dL/d(core_out) [n,H] -> dL/d(gx) time-major
             if pos == 0 and not self.features_in:
-                d0 = lib.sf_conv_desc.from_buffer_copy(d)
-                d0.traj_T = int(tT0)
-                bf16_0 = L.bf16 and L.kind in FRAME_KINDS
-                ws = self._workspace((lib.conv1_wgrad_bf16_workspace if bf16_0 else lib.conv_wgrad_workspace)(n, d0))
-                if bf16_0:  # cfg.encoder_conv1_bf16: g is already masked (conv2's data gradient read the activation)
-                    mu_, rstd_ = ctx.get("norm_tabs") or (None, None)
-                    lib.conv1_wgrad_bf16(x0, stride0, idx0, off0, mu_, rstd_, g, L.gw, L.gb, n, d0, ws)
+                d0 = _desc_at(L, tT0)
+                ws = self._workspace((route.wgrad_workspace if route else lib.conv_wgrad_workspace)(n, d0))
+                if route:  # g is already masked (conv2's data gradient read the activation)
+                    route.wgrad(x0, stride0, idx0, off0, ctx.get("norm_tabs") or (None, None), g, L.gw, L.gb, n, d0, ws)
                 elif ctx.get("norm_tabs") is not None:  # the forward normalised in conv1's loader: so does the gradient
                     mu_, rstd_ = ctx["norm_tabs"]
                     lib.conv_wgrad_norm(x0, stride0, idx0, off0, mu_, rstd_, g, L.gw, L.gb, n, d0, ws)
@@ -1243,15 +1298,13 @@ class ActorCritic(NativeTower):
                     lib.conv_wgrad_raw(x0, stride0, idx0, off0, g, L.gw, L.gb, n, d0, ws)
             else:
                 x = inputs[li]
-                wgrad_ws, wgrad, dgrad = (lib.conv_wgrad_bf16_workspace, lib.conv_wgrad_bf16, lib.conv_dgrad_bf16) if L.bf16 else \
-                    (lib.conv_wgrad_workspace, lib.conv_wgrad_raw, lib.conv_dgrad)
-                if L.bf16 and L.kind != "conv":  # cfg.mlp_bf16: a fully connected layer, dense rows [n, K] and [n, N]
-                    K_, N_ = L.K, L.N
-                    wgrad_ws = lambda n_, d_: lib.linear_wgrad_bf16_workspace(n_, K_, N_)  # noqa: E731
-                    wgrad = lambda x_, s_, i_, o_, g_, gw_, gb_, n_, d_, ws_: lib.linear_wgrad_bf16(x_, g_, gw_, gb_, n_, K_, N_, ws_)  # noqa: E731
-                    dgrad = lambda g_, w_, a_, gin_, n_, dd_: lib.linear_dgrad_bf16(g_, w_, a_, gin_, n_, K_, N_, dd_.relu)  # noqa: E731
-                ws = self._workspace(wgrad_ws(n, d))
-                wgrad(x, d.H * d.W * d.Cin, None, 0, g, L.gw, L.gb, n, d, ws)
+                if route:
+                    ws = self._workspace(route.wgrad_workspace(n, d))
+                    route.wgrad(x, d.H * d.W * d.Cin, None, 0, (None, None), g, L.gw, L.gb, n, d, ws)
+                else:
+                    ws = self._workspace(lib.conv_wgrad_workspace(n, d))
+                    lib.conv_wgrad_raw(x, d.H * d.W * d.Cin, None, 0, g, L.gw, L.gb, n, d, ws)
+                dgrad = route.dgrad if route else lib.conv_dgrad
                 gin = self._buf(("g", li - 1), tuple(x.shape))
                 dd = lib.sf_conv_desc.from_buffer_copy(d)
                 dd.relu = L.in_act_kind  # derivative of the activation that produced x, fused into the epilogue
